@@ -2,7 +2,7 @@
 """bench.py -- the hot path's headline metric on MI355X (BASELINE.json):
     "depth-maps/sec @ 640x480x7-view x 3-stage; TSDF voxels integrated/sec".
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,10 @@ A "step" is one pass of the DrMvsnet hot path (pre-process .. edge filter) over 
 that is already resident in HBM when the timed region starts.  Workload at every N = BASELINE configs[1]:
 640x480, ref + 6 src views, 3-stage cascade with (48,32,8) depth planes, fp32, view aggregation on.
 Multi-GPU: independent replicas, one window stream per rank, no data-path collective ("scaling": "weak");
-value = depth maps of all ranks / max-over-ranks time.  Rank 0 prints ONE JSON line.  Riding along in it:
+value = depth maps of all ranks / max-over-ranks time of ONE timed region of exactly K steps; ms_per_step = that span / K.
+Rank 0 prints ONE JSON line.  A plain run does only that (set up, warm up, time, --dump-outputs); with --full, riding along in it:
+  "repeats", "gpu_state", "single_engine", "roofline", "pipeline", "scene_depth_range", "cpu_baseline", "parity" (the committed
+              reference fixture through the library before anything is timed);
   "boundary"  the same windows through the operator boundary the reference times (CallAsync / Ready / GetResult,
               dr_mvsnet.cpp:540-545): host u8 images in, four float maps out -- PCIe-inclusive, never `value`;
   "tsdf"      BASELINE configs[3]: 1000 distinct depth maps of a camera loop through an analytic room fused into a 5 mm
@@ -177,14 +180,18 @@ def mvsnet_leg(args, rank, dev, world):
     # different windows overlap, which fills the CUs during the many small kernels of the coarse UNet levels
     # (measured: 275 -> 338 -> 366 depth-maps/s for E = 1, 2, 3).  E = 1 is the single-window latency configuration.
     E = max(1, min(args.engines, args.steps))
-    engines, wins = [], []
+    # the E windows are synthesised side by side (numpy's ufuncs release the GIL): same seeds, same arrays, a third of the wait
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(E) as pool:
+        wins = list(pool.map(lambda e: make_window(H, W, V, rank * 16 + e), range(E)))
+    engines = []
     for e in range(E):
-        win = make_window(H, W, V, rank * 16 + e)
+        win = wins[e]
         m = DrMvsnet(blob, device=dev)
         m.upload(H, W, V, win["ref_index"], win["bgrs"], win["K"], list(win["c2ws"]), DEPTH_MIN, DEPTH_MAX, DISCARD)
         if args.warmup > 0:
             m.forward(args.warmup)
-        engines.append(m); wins.append(win)
+        engines.append(m)
     m, win = engines[0], wins[0]
     share = [args.steps // E + (1 if e < args.steps % E else 0) for e in range(E)]  # exactly K steps in total
     ev = [0.0] * E
@@ -192,13 +199,8 @@ def mvsnet_leg(args, rank, dev, world):
     def run(e):
         ev[e] = engines[e].forward(share[e])  # enqueues share[e] forwards on the engine's stream, then stream-synchronises
 
-    # The timed region -- EXACTLY K steps between barrier + synchronize on both sides, max over ranks -- is repeated and the
-    # MEDIAN repeat is reported (a 20-step region is 50 ms: one shot of it is at the mercy of a clock ramp or a stray
-    # interrupt); min / max of the repeats ride along.  9 repeats at the driver's K = 20, 3 at the default K = 300.
-    repeats = max(3, min(9, -(-400 // max(1, args.steps))))
-    spans = []
-    state_before = gpu_state() if rank == 0 and not DRY else None
-    for _ in range(repeats):
+    def timed_region():
+        """EXACTLY K steps between barrier + synchronize on both sides; (max over ranks of the span, steps of all ranks, slowest hipEvent span)."""
         threads = [threading.Thread(target=run, args=(e,)) for e in range(E)]
         replicas.barrier(dev)
         gpu_sync()
@@ -211,14 +213,41 @@ def mvsnet_leg(args, rank, dev, world):
         t1 = time.perf_counter()
         replicas.barrier(dev)
         tmax, units = replicas.reduce_max_sum(t1 - t0, args.steps, dev)
-        spans.append((tmax, units, max(ev)))
-    tmax, units, evmax = sorted(spans)[len(spans) // 2]
+        return tmax, units, max(ev)
+
+    # Spin-up (part of the warm-up, untimed): the engines together, as the timed region runs them, for >= 0.25 s.  The warm-up forwards above
+    # load each engine's kernels; the card settles only under sustained load -- the first 20-step region straight after them ran 1.74 - 1.77 ms
+    # per step, every later region 1.71 (measured; the tracker leg's 0.25 s spin-up is the same remedy).  A stand-in engine has no clocks.
+    if args.warmup > 0 and not DRY:
+        t_spin = time.perf_counter()
+        while time.perf_counter() - t_spin < 0.25:
+            spin = [threading.Thread(target=lambda m=m: m.forward(args.warmup)) for m in engines]
+            for t in spin:
+                t.start()
+            for t in spin:
+                t.join()
+        gpu_sync()
+    # The headline: ONE timed region of K steps, so that --steps is the number of steps timed and ms_per_step x K is its span
+    tmax, units, evmax = timed_region()
+    res = dict(value=units / tmax, units=units, ms_per_step=1e3 * tmax / args.steps, event_ms_per_step=evmax / args.steps, engines_per_gpu=E)  # engines run concurrently: the slowest one's hipEvent span covers the job
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engines, rank, world)
+    if not args.full:
+        for extra in engines:
+            extra.close()
+        return res
+    # --full: the region is repeated (a 20-step region is 50 ms: one shot of it is at the mercy of a clock ramp or a stray interrupt) and
+    # the median / min / max of the repeats ride along.  9 repeats at the driver's K = 20, 3 at the default K = 300.
+    repeats = max(3, min(9, -(-400 // max(1, args.steps))))
+    state_before = gpu_state() if rank == 0 and not DRY else None
+    spans = sorted(timed_region() for _ in range(repeats))
     state_after = gpu_state() if rank == 0 and not DRY else None
-    res = dict(value=units / tmax, units=units, ms_per_step=1e3 * tmax / args.steps, event_ms_per_step=evmax / args.steps, engines_per_gpu=E,  # engines run concurrently: the slowest one's hipEvent span covers the job
-               repeats=dict(n=repeats, statistic="median", ms_per_step_min=1e3 * min(s[0] for s in spans) / args.steps,
-                            ms_per_step_max=1e3 * max(s[0] for s in spans) / args.steps))
+    res["repeats"] = dict(n=repeats, statistic="median", ms_per_step_median=1e3 * spans[len(spans) // 2][0] / args.steps,
+                          ms_per_step_min=1e3 * spans[0][0] / args.steps, ms_per_step_max=1e3 * spans[-1][0] / args.steps,
+                          note="timed regions of K steps repeated after the headline region (`value` / `ms_per_step` are the headline region's)")
     if state_before is not None:
-        res["gpu_state"] = dict(before_timed_region=state_before, after_timed_region=state_after, source="rocm-smi -d 0 --showclocks --showpower --showtemp")
+        res["gpu_state"] = dict(before_timed_region=state_before, after_timed_region=state_after, source="rocm-smi -d 0 --showclocks --showpower --showtemp",
+                                note="around the repeated regions")
     if rank == 0:  # the single-window latency (ONE DrMvsnet object = TANDEM's usage) next to the throughput figure
         nlat = max(10, min(100, args.steps))
         lat = m.forward(nlat) / nlat
@@ -264,6 +293,26 @@ def mvsnet_leg(args, rank, dev, world):
             res["cpu_baseline"] = mvsnet_cpu_baseline(win, blob)
     m.close()
     return res
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, engines, rank, world):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step -- the four float32 maps (depth, confidence,
+    depth_dense, confidence_dense) of every engine's window -- as DIR/[rank<r>_]window<e>_<map>.npy; windows stop at 64 MB in all.
+    The windows are seeded (rank * 16 + e), so the same arguments give the same inputs on every run."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for e, eng in enumerate(engines):
+        out = eng.download()
+        maps = [(k, getattr(out, k)) for k in ("depth", "confidence", "depth_dense", "confidence_dense") if hasattr(out, k)]
+        size = sum(a.nbytes for _, a in maps)
+        if total + size > DUMP_BYTES:
+            break
+        total += size
+        for k, a in maps:
+            np.save(os.path.join(path, "%swindow%d_%s.npy" % ("rank%d_" % rank if world > 1 else "", e, k)), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def golden_parity(dev):
@@ -826,8 +875,12 @@ def respawn_under_torchrun(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=300)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=300, help="steps in the timed region (all engines of a GPU together)")
+    ap.add_argument("--warmup", type=int, default=10, help="untimed forwards of each engine, then >= 0.25 s of the engines together, before the timed region (0: neither)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the four float32 maps of every window's last timed step to DIR/*.npy")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: repeated regions, GPU state, single-window latency, "
+                                                         "roofline, golden-fixture parity, CPU baselines, TSDF, tracker, boundary, TandemBackend loop, "
+                                                         "shipped model, view-sharded leg (N > 1); the --no-* options below trim that")
     ap.add_argument("--tsdf-frames", type=int, default=1000, help="distinct synthetic depth maps fused by the TSDF leg (BASELINE configs[3])")
     ap.add_argument("--loop-keyframes", type=int, default=100, help="keyframes of the TandemBackend-shaped loop (tools/tandem_loop.cpp)")
     ap.add_argument("--no-boundary", action="store_true", help="skip the operator-boundary (CallAsync/GetResult) leg")
@@ -858,7 +911,7 @@ def main():
     if DRY:  # launcher / plumbing rehearsal on a CPU box: gloo, stand-in engines, only the legs every rank takes part in
         replicas.init("gloo", None)
         mv = mvsnet_leg(args, rank, None, world)
-        vs = view_shard_leg(args, rank, None, world) if world > 1 and not args.no_view_shard else None
+        vs = view_shard_leg(args, rank, None, world) if args.full and world > 1 and not args.no_view_shard else None
         if rank == 0:
             print(json.dumps({"metric": "depth-maps/sec @ 640\u00d7480\u00d77-view\u00d73-stage; TSDF voxels integrated/sec", "value": None, "unit": "depth-maps/s",
                               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": None, "higher_is_better": True, "scaling": "weak",
@@ -878,15 +931,26 @@ def main():
     torch.cuda.set_device(local_rank)
     replicas.init("gloo" if one_dev else "nccl", local_rank)
 
-    par = golden_parity(local_rank) if (rank == 0 and args.config == "headline") else None  # before anything is timed
+    # a plain run is the headline alone (set up, warm up, K timed steps, outputs); every other leg runs under --full
+    full = args.full
+    par = None
+    if rank == 0 and args.config == "headline":
+        if full:
+            par = golden_parity(local_rank)  # before anything is timed
+        else:
+            # The headline's engines were tuned and measured behind the parity check's engine.  The runtime gives each new stream the
+            # least-shared hardware queue, so the streams created earlier decide which engines share a queue (profiles/r06_queues_side_stream.txt):
+            # without that engine the same four engines take 1.85 instead of 1.71 ms per step, every region of the process.  A plain run keeps
+            # the same stream history: one engine created and dropped where --full runs the check.
+            engine_class()(model_blob(), device=local_rank).close()
     mv = mvsnet_leg(args, rank, local_rank, world)
-    ts = None if args.no_tsdf else tsdf_leg(args, rank, local_rank, world)
-    tr = tracker_leg(args, local_rank) if (rank == 0 and not args.no_tsdf) else None
-    bd = boundary_leg(args, local_rank) if (rank == 0 and world == 1 and not args.no_boundary) else None
-    lp = tandem_loop_leg(args, local_rank) if (rank == 0 and world == 1 and not args.no_loop) else None
-    sh = shipped_leg(args, local_rank) if (rank == 0 and world == 1 and not args.no_boundary) else None
+    ts = None if (not full or args.no_tsdf) else tsdf_leg(args, rank, local_rank, world)
+    tr = tracker_leg(args, local_rank) if (full and rank == 0 and not args.no_tsdf) else None
+    bd = boundary_leg(args, local_rank) if (full and rank == 0 and world == 1 and not args.no_boundary) else None
+    lp = tandem_loop_leg(args, local_rank) if (full and rank == 0 and world == 1 and not args.no_loop) else None
+    sh = shipped_leg(args, local_rank) if (full and rank == 0 and world == 1 and not args.no_boundary) else None
     vs, vs_hung = None, False
-    if world > 1 and not args.no_view_shard:
+    if full and world > 1 and not args.no_view_shard:
         # The sharded leg is the only part of this program with a data-path collective.  It runs under a watchdog: if a
         # rank gets stuck in it (a collective that never completes cannot be cancelled from Python) the headline line
         # above is still printed and every rank leaves with os._exit instead of hanging the launcher.
@@ -910,7 +974,7 @@ def main():
                        else "depth-maps/sec @ %d\u00d7%d\u00d77-view\u00d73-stage; TSDF voxels integrated/sec" % (W, H)),
             "value": mv["value"], "unit": "depth-maps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": mv["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": ("%dx%d ref+6-src keyframe window, 3-stage cascade (%d/%d/%d hypotheses), view aggregation, fp32; " % ((W, H) + PLANES)) +
                                    "independent windows, %d in flight per GPU (one DrMvsnet engine each) x %d GPU replica(s); trained weights recovered from the reference's exported "
                                    "tandem_512x320 model (same architecture), inputs resident in HBM" % (mv["engines_per_gpu"], world),

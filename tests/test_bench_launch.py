@@ -17,7 +17,7 @@ def test_eight_rank_launch_through_bench_spawn_path(tmp_path):
     env = dict(os.environ, DR_BENCH_DRY_RUN="1", DR_BENCH_DRY_DIR=str(tmp_path), OMP_NUM_THREADS="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "12", "--warmup", "1"], capture_output=True, text=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "12", "--warmup", "1", "--full"], capture_output=True, text=True,
                        timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -48,3 +48,26 @@ def test_eight_rank_launch_through_bench_spawn_path(tmp_path):
             assert all(e["comm_init"] is None and e["set_view_shard"] is None for e in engines)
             idle = [e for e in engines if e["forwards"] == 0]
             assert len(idle) == 1 and idle[0]["uploads"] == []
+
+
+def test_plain_run_times_exactly_k_steps_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) is the headline alone: ONE timed region of exactly K steps -- the stand-in engines are asked for
+    K steps beside their warm-up and nothing else -- no other leg in the line, and --dump-outputs writes every window's maps."""
+    import numpy as np
+    env = dict(os.environ, DR_BENCH_DRY_RUN="1", DR_BENCH_DRY_DIR=str(tmp_path), OMP_NUM_THREADS="1")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dump = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "2", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 10 and out["units_counted"] == 10 and out["view_sharded"] is None
+    logs = [json.load(open(f)) for f in glob.glob(os.path.join(str(tmp_path), "rank*_*.json"))]
+    assert len(logs) == out["engines_per_gpu"] == 4
+    assert sum(e["forwards"] for e in logs) == 10 + 4 * 2  # K timed steps + W warm-up forwards per engine
+    assert sorted(os.listdir(dump)) == ["window%d_depth_dense.npy" % e for e in range(4)]  # the stand-in's result holds one map
+    a = np.load(str(dump / "window0_depth_dense.npy"))
+    assert a.dtype == np.float32 and a.shape == (480, 640)

@@ -80,11 +80,13 @@ def test_table_complement_symmetry():
         assert set(T[c]) == set(T[255 - c])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference checkout not present")
 def test_table_equals_published_copy_in_reference():
+    """tests/golden/mc_tri_table_reference.npz: the reference's triTable[256][16] (ref:tandem/libdr/dr_fusion/src/marching_cubes/
+    lookup_tables.h, read by tools/pack_mc_tables.py::parse) as int8 rows."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import pack_mc_tables
-    ref = pack_mc_tables.parse("/root/reference/tandem/libdr/dr_fusion/src/marching_cubes/lookup_tables.h")
+    ref = np.load(os.path.join(ROOT, "tests", "golden", "mc_tri_table_reference.npz"))["tri_table"].astype(int).tolist()
+    assert len(ref) == 256 and all(len(r) == 16 and r[-1] == -1 for r in ref)
     assert [pack_mc_tables.pack(r) for r in ref] == packed_table()
 
 

@@ -14,7 +14,7 @@ import pytest
 from oracle import ref_handoff
 from oracle.tracker_oracle import TrackerOracle
 
-pytestmark = pytest.mark.skipif(not ref_handoff.available(), reason="oracle/_ref/libdense_handoff_ref*.so not built (needs /root/reference at build time)")
+pytestmark = pytest.mark.skipif(not ref_handoff.available(), reason="neither oracle/_ref/libdense_handoff_ref*.so nor tests/golden/ref_handoff.npz")
 
 
 def run_both(p, step, dense_only, sum_left, with_sparse=True):

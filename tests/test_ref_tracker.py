@@ -9,7 +9,8 @@ ref:tandem/libdr/cuda_coarse_tracker/src/cuda_coarse_tracker_private.cu by oracl
   ~1e4 terms); calcG against the reference kernel's own double-accumulator instantiation with one point per thread
   (loops = 1, no float partial sums): 1e-12.
 
-Skipped when neither oracle/_ref/libcoarse_tracker_ref.so nor /root/reference exists."""
+Where oracle/_ref is not built, the reference's results come from tests/golden/ref_tracker.npz, recorded from that build
+(oracle/ref_replay.py: DR_REF_RECORD=1 python -m pytest tests/test_ref_tracker.py)."""
 import numpy as np
 import pytest
 
@@ -17,7 +18,7 @@ from oracle import ref_tracker
 from synth import scene
 from oracle.tracker_oracle import TrackerOracle
 
-pytestmark = pytest.mark.skipif(not ref_tracker.available(), reason="reference build (oracle/_ref) not available")
+pytestmark = pytest.mark.skipif(not ref_tracker.available(), reason="neither the reference build (oracle/_ref) nor tests/golden/ref_tracker.npz")
 
 
 def _setup(H, W, seed, frac, huber=9.0, exposure=(1.0, 1.0), ref_aff=(0.0, 0.0), motion=1.0):

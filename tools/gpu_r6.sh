@@ -36,12 +36,12 @@ for step in "$@"; do
       for abl in 0 1 2 4 3 5 7; do echo "DR_CV5_ABL=$abl (1 no gathers, 2 no stores, 4 no tap arithmetic): $(DR_CV5_ABL=$abl timeout 300 python tools/profile_ops.py "costvol" 2>&1 | tail -1)"; done | tee $OUT/${TAG}_costvol_abl.txt
       unset DR_MI355X_LIB DR_OPS_RANGE ;;
     tsdf16m)  # SURVEY 8(d)'s fusion configuration once: a pool of 16 M voxel blocks (64 GB), everything else as the bench runs it
-      timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-boundary --no-loop --no-tsdf-native --no-tsdf-boundary --tsdf-blocks 16000000 > $OUT/${TAG}_bench_tsdf16m.json 2> $OUT/${TAG}_bench_tsdf16m.err
+      timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-boundary --no-loop --no-tsdf-native --no-tsdf-boundary --tsdf-blocks 16000000 > $OUT/${TAG}_bench_tsdf16m.json 2> $OUT/${TAG}_bench_tsdf16m.err
       python -c "import json; d=json.load(open('$OUT/${TAG}_bench_tsdf16m.json'))['tsdf']; print({k: d[k] for k in ('value','ms_per_frame','blocks','kernel_ms_per_frame')}); print(d['config']['workload'][:400])" ;;
     tests_fc) timeout 1200 python -m pytest tests/test_mvsnet_gpu.py -m gpu -x -q -k "feature_cache or golden" > $OUT/${TAG}_gpu_tests_fc.log 2>&1; tail -15 $OUT/${TAG}_gpu_tests_fc.log ;;
     fc_time) timeout 600 python tools/time_feature_cache.py 2>&1 | tee $OUT/${TAG}_feature_cache_time.txt ;;
     loop_sliding)  # the TandemBackend loop on a sliding window, feature cache off / on
-      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-tsdf --no-boundary > $OUT/${TAG}_bench_loop.json 2> $OUT/${TAG}_bench_loop.err
+      timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-tsdf --no-boundary > $OUT/${TAG}_bench_loop.json 2> $OUT/${TAG}_bench_loop.err
       python -c "import json; d=json.load(open('$OUT/${TAG}_bench_loop.json'))['tandem_loop']; print({k: (v.get('keyframes_per_s'), v.get('mean_ms')) for k, v in d.items() if isinstance(v, dict) and 'keyframes_per_s' in v}); print(json.dumps(d.get('sliding_window'), indent=1))" ;;
     ab_classloop)  # k_conv's class loop (one workgroup per tile walks all parity classes of a single-pass transposed layer) against class-per-workgroup launches
       export DR_MI355X_LIB=$PWD/tandem_amd/libdr_mi355x_hooks.so DR_OPS_RANGE=0.01,10
@@ -55,8 +55,8 @@ for step in "$@"; do
     tests) timeout 2400 python -m pytest tests -m gpu -x -q > $OUT/${TAG}_gpu_tests.log 2>&1; tail -5 $OUT/${TAG}_gpu_tests.log ;;
     tests_fast) timeout 1200 python -m pytest tests -m gpu -x -q -k "${DR_TESTS_K:-mvsnet or conv}" > $OUT/${TAG}_gpu_tests_fast.log 2>&1; tail -5 $OUT/${TAG}_gpu_tests_fast.log ;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/${TAG}_smoke.txt 2>&1; tail -2 $OUT/${TAG}_smoke.txt ;;
-    bench) timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; tail -c 600 $OUT/${TAG}_bench.json ;;
-    bench_quick) timeout 900 python bench.py --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_quick.json 2> $OUT/${TAG}_bench_quick.err
+    bench) timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; tail -c 600 $OUT/${TAG}_bench.json ;;
+    bench_quick) timeout 900 python bench.py --full --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_quick.json 2> $OUT/${TAG}_bench_quick.err
                  python - <<PY
 import json
 d=json.load(open("$OUT/${TAG}_bench_quick.json"))
@@ -82,7 +82,7 @@ PY
       for cfg in "" "DR_CV_DCHUNK1=8" "DR_CV_DCHUNK1=12" "DR_CV_DCHUNK1=16" "DR_CV_DCHUNK2=4" "DR_CV_DCHUNK2=16" "DR_CV_DCHUNK3=4"; do echo "[$cfg] $(env $cfg timeout 300 python tools/profile_ops.py "costvol" 2>&1 | tail -1)"; done
       for so in build/ab/libdr_*.so; do nme=$(basename $so .so); echo "--- $nme: $(DR_MI355X_LIB=$PWD/$so timeout 300 python tools/profile_ops.py "costvol" 2>&1 | tail -1)"; done ;;
     bench_host)  # the legs that cross the operator boundary: boundary, tandem_loop (no TSDF loop, no CPU baselines)
-      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-tsdf > $OUT/${TAG}_bench_host.json 2> $OUT/${TAG}_bench_host.err
+      timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-tsdf > $OUT/${TAG}_bench_host.json 2> $OUT/${TAG}_bench_host.err
       python - <<PY
 import json
 d=json.load(open("$OUT/${TAG}_bench_host.json"))
@@ -105,7 +105,7 @@ PY
        # k_fn_front against the three launches it replaces: per-op times, then the quick bench line, both ways
       for f in 1 0; do echo "DR_FN_FRONT=$f: $(DR_FN_FRONT=$f timeout 300 python tools/profile_ops.py "preprocess|fn.front|fn.conv0|fn.conv1.0" 2>&1 | tail -1)"; done | tee $OUT/${TAG}_front_ops.txt
       for f in 1 0 1 0; do
-        DR_FN_FRONT=$f timeout 600 python bench.py --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_front$f.json 2> $OUT/${TAG}_bench_front$f.err
+        DR_FN_FRONT=$f timeout 600 python bench.py --full --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_front$f.json 2> $OUT/${TAG}_bench_front$f.err
         python -c "import json; d=json.load(open('$OUT/${TAG}_bench_front$f.json')); print('DR_FN_FRONT=$f: value %.1f /s  ms_per_step %.3f  single_window %.3f ms' % (d['value'], d['ms_per_step'], d['single_window_ms']))"
       done | tee -a $OUT/${TAG}_front_ops.txt 
       unset DR_MI355X_LIB ;;
@@ -114,19 +114,19 @@ PY
        # k_fn_head3 against the four launches it replaces
       for f in 1 0; do echo "DR_FN_HEAD3=$f: $(DR_FN_HEAD3=$f timeout 300 python tools/profile_ops.py "fn.head3|fn.out3|fn.out2|fn.skip2" 2>&1 | tail -1)"; done | tee $OUT/${TAG}_head3_ops.txt
       for f in 1 0 1 0; do
-        DR_FN_HEAD3=$f timeout 600 python bench.py --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_head3$f.json 2> $OUT/${TAG}_bench_head3$f.err
+        DR_FN_HEAD3=$f timeout 600 python bench.py --full --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_head3$f.json 2> $OUT/${TAG}_bench_head3$f.err
         python -c "import json; d=json.load(open('$OUT/${TAG}_bench_head3$f.json')); print('DR_FN_HEAD3=$f: value %.1f /s  ms_per_step %.3f  single_window %.3f ms' % (d['value'], d['ms_per_step'], d['single_window_ms']))"
       done | tee -a $OUT/${TAG}_head3_ops.txt 
       unset DR_MI355X_LIB ;;
     fn_quick)  # the two fused FeatureNet kernels as they stand: per-op times and the quick bench line, twice
       echo "$(timeout 300 python tools/profile_ops.py "fn.front|fn.head3" 2>&1 | tail -1)" | tee $OUT/${TAG}_fn_quick.txt
       for r in 1 2; do
-        timeout 600 python bench.py --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_fnq.json 2> $OUT/${TAG}_bench_fnq.err
+        timeout 600 python bench.py --full --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_fnq.json 2> $OUT/${TAG}_bench_fnq.err
         python -c "import json; d=json.load(open('$OUT/${TAG}_bench_fnq.json')); print('value %.1f /s  ms_per_step %.3f  single_window %.3f ms' % (d['value'], d['ms_per_step'], d['single_window_ms']))"
       done | tee -a $OUT/${TAG}_fn_quick.txt ;;
     engines)  # windows in flight: 2 / 3 / 4 engines (the quick bench line each)
       for n in ${DR_ENGINES_LIST:-3 4 2 3 4}; do
-        timeout 600 python bench.py --gpus 1 --steps 60 --warmup 5 --engines $n --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_eng.json 2> $OUT/${TAG}_bench_eng.err
+        timeout 600 python bench.py --full --gpus 1 --steps 60 --warmup 5 --engines $n --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_eng.json 2> $OUT/${TAG}_bench_eng.err
         python -c "import json; d=json.load(open('$OUT/${TAG}_bench_eng.json')); print('engines $n: value %.1f /s  ms_per_step %.3f' % (d['value'], d['ms_per_step']))"
       done | tee $OUT/${TAG}_engines.txt ;;
     ab_launches)  # (switches of the parity build: these A/Bs run on libdr_mi355x_hooks.so)
@@ -134,7 +134,7 @@ PY
        # the edge filter's folded scans and prob + regression in one launch, against the forms they replace
       for f in 1 0; do echo "DR_FILTER_FUSED=$f DR_PROB_REGRESS=$f: $(DR_FILTER_FUSED=$f DR_PROB_REGRESS=$f timeout 300 python tools/profile_ops.py "filter|s3.prob|s3.regress" 2>&1 | tail -1)"; done | tee $OUT/${TAG}_launches_ops.txt
       for f in 1 0 1 0; do
-        DR_FILTER_FUSED=$f DR_PROB_REGRESS=$f timeout 600 python bench.py --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_l$f.json 2> $OUT/${TAG}_bench_l$f.err
+        DR_FILTER_FUSED=$f DR_PROB_REGRESS=$f timeout 600 python bench.py --full --gpus 1 --steps 60 --warmup 5 --no-cpu --no-loop --no-boundary --no-tsdf > $OUT/${TAG}_bench_l$f.json 2> $OUT/${TAG}_bench_l$f.err
         python -c "import json; d=json.load(open('$OUT/${TAG}_bench_l$f.json')); print('fused=$f: value %.1f /s  ms_per_step %.3f  single_window %.3f ms' % (d['value'], d['ms_per_step'], d['single_window_ms']))"
       done | tee -a $OUT/${TAG}_launches_ops.txt 
       unset DR_MI355X_LIB ;;
@@ -143,22 +143,22 @@ PY
       export DR_MVS_NO_SIDE_STREAM=1
       S="--no-cpu --engines 1 --no-boundary --no-loop --no-tsdf-native --no-tsdf-boundary"; A="--steps 3 --warmup 1 --tsdf-frames 60 $S"
       rm -rf $OUT/pm1 $OUT/pm2 $OUT/pm3 $OUT/pm4
-      timeout 600 rocprofv3 --pmc FETCH_SIZE GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pm1 -o pmc -- python bench.py $A > $OUT/pm1.log 2>&1
-      timeout 600 rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pm2 -o pmc -- python bench.py $A > $OUT/pm2.log 2>&1
-      timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pm3 -o pmc -- python bench.py $A > $OUT/pm3.log 2>&1
-      timeout 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_WAIT_INST_LDS TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pm4 -o pmc -- python bench.py $A > $OUT/pm4.log 2>&1
+      timeout 600 rocprofv3 --pmc FETCH_SIZE GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pm1 -o pmc -- python bench.py --full $A > $OUT/pm1.log 2>&1
+      timeout 600 rocprofv3 --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pm2 -o pmc -- python bench.py --full $A > $OUT/pm2.log 2>&1
+      timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pm3 -o pmc -- python bench.py --full $A > $OUT/pm3.log 2>&1
+      timeout 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SALU SQ_WAIT_INST_LDS TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pm4 -o pmc -- python bench.py --full $A > $OUT/pm4.log 2>&1
       for i in 1 2 3 4; do d=$(dirname $(find $OUT/pm$i -name "pmc_counter_collection.csv" | head -1)); echo "== pass $i"; python tools/pmc_summary.py $d 2>&1 | grep -v "^at::\|elementwise\|    .*at::\|rocclr\|^void at" ; done > $OUT/${TAG}_pmc_summary.txt
       python tools/pmc_to_json.py profiles/r06_pmc_traffic.json $(for i in 1 2 3; do dirname $(find $OUT/pm$i -name "pmc_counter_collection.csv" | head -1); done)
       cp profiles/r06_pmc_traffic.json $OUT/; rm -rf $OUT/pm1 $OUT/pm2 $OUT/pm3 $OUT/pm4
       unset DR_MVS_NO_SIDE_STREAM ;;
-    shipped) timeout 600 python bench.py --config shipped --steps 240 --no-tsdf --no-loop --no-cpu > $OUT/${TAG}_bench_shipped.json 2> $OUT/${TAG}_bench_shipped.err; head -c 300 $OUT/${TAG}_bench_shipped.json; echo ;;
+    shipped) timeout 600 python bench.py --full --config shipped --steps 240 --no-tsdf --no-loop --no-cpu > $OUT/${TAG}_bench_shipped.json 2> $OUT/${TAG}_bench_shipped.err; head -c 300 $OUT/${TAG}_bench_shipped.json; echo ;;
     prof_seq)  # per-kernel durations without overlap: one engine, side stream off
       rm -rf $OUT/prof
-      DR_MVS_NO_SIDE_STREAM=1 timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --steps 20 --warmup 3 --tsdf-frames 200 --no-cpu --engines 1 --no-boundary --no-loop --no-tsdf-native --no-tsdf-boundary > $OUT/${TAG}_bench_prof.json 2> $OUT/prof.err
+      DR_MVS_NO_SIDE_STREAM=1 timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --full --steps 20 --warmup 3 --tsdf-frames 200 --no-cpu --engines 1 --no-boundary --no-loop --no-tsdf-native --no-tsdf-boundary > $OUT/${TAG}_bench_prof.json 2> $OUT/prof.err
       python tools/rocprof_summary.py $(find $OUT/prof -name "*_results.db" | head -1) > $OUT/${TAG}_bench_kernel_stats.txt 2>&1; head -14 $OUT/${TAG}_bench_kernel_stats.txt; rm -rf $OUT/prof ;;
     prof_driver)  # the same under the driver's own command (three engines in flight)
       rm -rf $OUT/prof
-      timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-boundary --no-loop --no-tsdf > $OUT/${TAG}_bench_prof_driver.json 2> $OUT/prof.err
+      timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-boundary --no-loop --no-tsdf > $OUT/${TAG}_bench_prof_driver.json 2> $OUT/prof.err
       python tools/rocprof_summary.py $(find $OUT/prof -name "*_results.db" | head -1) > $OUT/${TAG}_bench_kernel_stats_driver_cmd.txt 2>&1; head -14 $OUT/${TAG}_bench_kernel_stats_driver_cmd.txt; rm -rf $OUT/prof ;;
     *) echo "unknown step $step" ;;
   esac
