@@ -249,6 +249,41 @@ int drf_bench_sequence(drf_t *h, const void *d_bgr, const void *d_depth, const f
  * caller that reaches this overlap: through the operator API GetRenderResult(k) returns before IntegrateScanAsync(k + 1) is called). */
 int drf_bench_render_host(drf_t *h, int stream, int back, const uint8_t **bgr, const float **depth);
 
+/* --- streaming: a bounded device pool and a host store for the rest of the map (no reference counterpart; the reference's
+ * HashTable::DeleteBlock / Heap::Append, hash_table.cu:117-139 and heap.cu:27, are never called by DrFusion).  DESIGN.md
+ * "Streaming voxel blocks", INTEGRATION.md "Streaming".
+ * Automatic mode (drf_set_streaming with radius > 0): each drf_integrate_scan_async / drf_integrate_device with camera centre p
+ *   (1) folds the blocks evicted after the previous scan into the host store, (2) brings back every stored block whose
+ *   centre ((8 b + 3.5) voxel_size per axis) lies within `radius` of p -- before the allocation pass --, (3) integrates
+ *   unchanged, (4) evicts the resident blocks whose centre lies beyond radius + one block edge (8 voxel_size) of p.
+ * Exactness contract: with radius >= drf_streaming_min_radius, the voxel state of the map (resident blocks plus host store)
+ *   after every scan is bit-identical to an engine whose pool never runs out, and so are the update counts.  A ray-cast
+ *   equals that engine's when its pose lies within radius - drf_streaming_min_radius of the last scan's camera centre (the
+ *   scan pose itself always qualifies).  Farther renders see the resident blocks only.
+ * drf_export_blocks, mesh extraction and rendering cover the RESIDENT blocks; bring a region back with drf_stream_in_region
+ *   before meshing it.  drf_bench_* return DR_ERR_UNSUPPORTED while streaming is on or the host store holds blocks, and
+ *   integrating with streaming off while the host store holds blocks is DR_ERR_PROTOCOL. */
+/* Smallest exact radius for these options: the farthest a block centre can lie from a scan's camera centre and still be
+ * allocated, updated or ray-cast by it at the scan pose, plus one block diagonal; host-only, needs no device.
+ * With rho = max |((u - cx)/fx, (v - cy)/fy, 1)| over the image corners and s = sqrt(3) * voxel_size:
+ *   max(max_sensor_depth * rho + truncation_distance + 4.5 s, 12.5 s) + 8 s + voxel_size */
+int drf_streaming_min_radius(const drf_options_t *o, float *radius);
+/* radius = 0: off (the default).  A radius below drf_streaming_min_radius is DR_ERR_ARG; changing the mode while the host
+ * store holds blocks is DR_ERR_PROTOCOL.  host_capacity_blocks bounds the host store (0 = unbounded): a region that does not
+ * fit is DR_ERR_CAPACITY, and automatic eviction stops when the store is full (the pool then reports DR_ERR_CAPACITY). */
+int drf_set_streaming(drf_t *h, float radius, size_t host_capacity_blocks);
+/* Explicit moves of every block whose origin (8 b voxel_size per axis) lies in [lower, upper] (inclusive); legal where
+ * drf_integrate_scan_async is, in either mode.  drf_stream_in_region that would not fit in the pool's free blocks returns
+ * DR_ERR_CAPACITY and moves nothing; so does drf_stream_out_region that would not fit in the host store. */
+int drf_stream_out_region(drf_t *h, const float lower[3], const float upper[3]);
+int drf_stream_in_region(drf_t *h, const float lower[3], const float upper[3]);
+/* out: [0] resident blocks, [1] blocks in the host store, [2] blocks streamed out, [3] blocks streamed in (totals),
+ * [4] bytes moved (4096 per block either way), [5] device time of the last scan's stream-in and eviction launches in us
+ * (0 when it had none). */
+int drf_streaming_stats(drf_t *h, uint64_t out[6]);
+/* The host store in the format of drf_export_blocks. */
+int drf_export_host_blocks(drf_t *h, int max_blocks, int32_t *coords, uint8_t *voxels, int *n);
+
 /* ======================================================================================================
  * DrCoarseTracker -- the dense coarse tracker operator.  Replaces
  *   tandem/libdr/cuda_coarse_tracker/include/public/cuda_coarse_tracker.h   (class CudaCoarseTracker)

@@ -110,6 +110,12 @@ SIGNATURES = {
     "drf_visited_blocks": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "drf_bench_render_host": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp)]),
     "drf_bench_integrate": (C.c_int, [vp, vp, vp, f32p, C.c_int, f32p, f32p]),
+    "drf_streaming_min_radius": (C.c_int, [C.POINTER(FusionOptions), f32p]),
+    "drf_set_streaming": (C.c_int, [vp, C.c_float, C.c_size_t]),
+    "drf_stream_out_region": (C.c_int, [vp, f32p, f32p]),
+    "drf_stream_in_region": (C.c_int, [vp, f32p, f32p]),
+    "drf_streaming_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_export_host_blocks": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int)]),
 }
 
 

@@ -27,7 +27,11 @@
 #include <cstdio>
 #include <cstring>
 #include <chrono>
+#include <array>
+#include <cmath>
 #include <memory>
+#include <unordered_map>
+#include <vector>
 
 #include <rocprim/rocprim.hpp>  // device radix sort (block keys) and exclusive scan (triangle offsets) of the mesh path
 
@@ -1055,6 +1059,8 @@ __global__ void k_fill_keys(unsigned long long *keys, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) keys[i] = kEmptyKey;
 }
 
+#include "stream_kernels.h"
+
 }  // namespace dr
 #include "mesh_kernels.h"
 namespace dr {
@@ -1098,6 +1104,123 @@ __global__ __launch_bounds__(256) void k_publish(const unsigned char *__restrict
   for (size_t i = (qa << 4) + t; i < na; i += nt) ha[i] = a[i];
   for (size_t i = (qb << 4) + t; i < nb; i += nt) hb[i] = b[i];
 }
+
+// ------------------------------------------------------------------ streaming (host side)
+// Farthest a block centre can lie from the camera centre of a scan whose valid depths do not exceed `depth` and still be
+// read or written by that scan (DESIGN.md "Streaming voxel blocks" derives each term):
+//   allocation DDA  depth*rho + trunc + 4.5*sqrt(3)*vs    (points of the ray up to surf + trunc; block centre within 4.5 sqrt(3) vs)
+//                   12.5*sqrt(3)*vs                       (the start block shifted one block back on negative axes)
+//   voxel update    depth*rho + trunc + 3.5*sqrt(3)*vs    (updated voxels have vd < sd + trunc)
+//   ray-cast        depth*rho + 4.5*sqrt(3)*vs            (samples at cur < max_sensor_depth, trilinear corners within sqrt(3) vs)
+// plus one block diagonal (8 sqrt(3) vs) and one voxel of margin.  rho = the largest |((u - cx)/fx, (v - cy)/fy, 1)| over
+// the image corners.  Evaluated in double.
+static double stream_reach(const drf_options_t &o, double depth) {
+  const double s3 = std::sqrt(3.0), vs = o.voxel_size;
+  double rho = 0.0;
+  for (int k = 0; k < 4; ++k) {
+    const double u = (k & 1) ? o.width - 1 : 0, v = (k & 2) ? o.height - 1 : 0;
+    const double a = (u - o.cx) / o.fx, b = (v - o.cy) / o.fy;
+    rho = std::max(rho, std::sqrt(a * a + b * b + 1.0));
+  }
+  const double scan = std::max(depth * rho + (double)o.truncation_distance + 4.5 * s3 * vs, 12.5 * s3 * vs);
+  return scan + 8.0 * s3 * vs + vs;
+}
+static bool stream_options_ok(const drf_options_t &o) {
+  auto pos = [](double x) { return std::isfinite(x) && x > 0.0; };
+  return pos(o.voxel_size) && pos(o.fx) && pos(o.fy) && std::isfinite(o.cx) && std::isfinite(o.cy) && o.width > 0 && o.height > 0 &&
+         pos(o.max_sensor_depth) && std::isfinite(o.truncation_distance) && o.truncation_distance >= 0.0f;
+}
+static float streaming_min_radius(const drf_options_t &o) { return (float)stream_reach(o, o.max_sensor_depth); }
+
+static inline void unpack_key_host(unsigned long long k, int c[3]) {
+  const int B = 1 << 20;
+  c[0] = (int)((k >> 42) & 0x1fffff) - B;
+  c[1] = (int)((k >> 21) & 0x1fffff) - B;
+  c[2] = (int)(k & 0x1fffff) - B;
+}
+static inline float blk_origin_host(int c, float vs) { return (float)(c * kBS) * vs; }
+static inline double blk_centre_host(int c, float vs) { return ((double)(c * kBS) + 3.5) * vs; }
+
+// The host half of the map: block key -> 4 KB, in slabs of 1024 blocks, with a coarse spatial index (cells of 8^3 blocks)
+// so that the per-scan "stored blocks within the radius" query visits cells near the camera only.
+class HostBlockStore {
+ public:
+  size_t size() const { return slot_.size(); }
+  bool empty() const { return slot_.empty(); }
+  void put(unsigned long long key, const void *vox) {
+    unsigned s;
+    if (!free_.empty()) { s = free_.back(); free_.pop_back(); }
+    else {
+      s = next_++;
+      if ((s >> kSlabShift) >= slabs_.size()) slabs_.emplace_back(new uint8_t[(size_t)4096 << kSlabShift]);
+    }
+    memcpy(at(s), vox, 4096);
+    slot_[key] = s;
+    cells_[cell_of(key)].push_back(key);
+  }
+  const uint8_t *get(unsigned long long key) const { return at(slot_.at(key)); }
+  void erase(unsigned long long key) {
+    auto it = slot_.find(key);
+    free_.push_back(it->second);
+    slot_.erase(it);
+    auto c = cells_.find(cell_of(key));
+    auto &v = c->second;
+    for (size_t i = 0; i < v.size(); ++i)
+      if (v[i] == key) { v[i] = v.back(); v.pop_back(); break; }
+    if (v.empty()) cells_.erase(c);
+  }
+  template <class F> void for_each(F f) const { for (auto &kv : slot_) f(kv.first, at(kv.second)); }
+  // keys of the stored blocks whose streaming centre lies within r of p
+  void query_sphere(const double p[3], double r, float vs, std::vector<unsigned long long> &out) const {
+    if (slot_.empty()) return;
+    const double cell = 64.0 * vs;  // 8 blocks
+    long lo[3], hi[3];
+    double span = 1.0;
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = (long)std::floor((p[a] - r) / cell) - 1;
+      hi[a] = (long)std::floor((p[a] + r) / cell) + 1;
+      span *= (double)(hi[a] - lo[a] + 1);
+    }
+    auto test_cell = [&](const std::vector<unsigned long long> &v) {
+      for (unsigned long long k : v) {
+        int c[3]; unpack_key_host(k, c);
+        const double dx = blk_centre_host(c[0], vs) - p[0], dy = blk_centre_host(c[1], vs) - p[1], dz = blk_centre_host(c[2], vs) - p[2];
+        if (dx * dx + dy * dy + dz * dz <= r * r) out.push_back(k);
+      }
+    };
+    if (span > (double)cells_.size()) {  // fewer occupied cells than cells in range: walk the occupied ones
+      for (auto &kv : cells_) {
+        const long cx = cell_coord(kv.first, 0), cy = cell_coord(kv.first, 1), cz = cell_coord(kv.first, 2);
+        if (cx >= lo[0] && cx <= hi[0] && cy >= lo[1] && cy <= hi[1] && cz >= lo[2] && cz <= hi[2]) test_cell(kv.second);
+      }
+      return;
+    }
+    for (long x = lo[0]; x <= hi[0]; ++x)
+      for (long y = lo[1]; y <= hi[1]; ++y)
+        for (long z = lo[2]; z <= hi[2]; ++z) {
+          auto it = cells_.find(pack_cell(x, y, z));
+          if (it != cells_.end()) test_cell(it->second);
+        }
+  }
+
+ private:
+  static constexpr int kSlabShift = 10;
+  uint8_t *at(unsigned s) const { return slabs_[s >> kSlabShift].get() + (size_t)(s & ((1u << kSlabShift) - 1)) * 4096; }
+  static unsigned long long pack_cell(long x, long y, long z) {
+    const long B = 1 << 20;
+    return ((unsigned long long)(x + B) << 42) | ((unsigned long long)(y + B) << 21) | (unsigned long long)(z + B);
+  }
+  static long cell_coord(unsigned long long ck, int a) { return (long)((ck >> (42 - 21 * a)) & 0x1fffff) - (1 << 20); }
+  static unsigned long long cell_of(unsigned long long key) {
+    int c[3]; unpack_key_host(key, c);
+    return pack_cell(c[0] >> 3, c[1] >> 3, c[2] >> 3);  // arithmetic shift = floor division by 8
+  }
+  std::unordered_map<unsigned long long, unsigned> slot_;
+  std::unordered_map<unsigned long long, std::vector<unsigned long long>> cells_;
+  std::vector<std::unique_ptr<uint8_t[]>> slabs_;
+  std::vector<unsigned> free_;
+  unsigned next_ = 0;
+};
 
 // ------------------------------------------------------------------ engine
 constexpr int kDefaultFusionPriority = 1;  // 0 least (the reference's), 1 normal (measured best in the TandemBackend loop), 2 greatest
@@ -1199,21 +1322,31 @@ class FusionEngine {
     (void)hipFree(mesh_axis_); (void)hipFree(mesh_keys_); (void)hipFree(mesh_total_); (void)hipFree(mesh_counts_);
     (void)hipFree(mesh_offsets_); (void)hipFree(mesh_tmp_); (void)hipFree(mesh_vert_); (void)hipFree(mesh_cols_);
     if (mesh_done_) (void)hipEventDestroy(mesh_done_);
+    if (st_cap_) {
+      (void)hipFree(sd_.ctl); (void)hipFree(sd_.list); (void)hipFree(sd_.mv_dst); (void)hipFree(sd_.mv_src);
+      (void)hipHostFree(h_ev_keys_); (void)hipHostFree(h_ev_vox_); (void)hipHostFree(sd_.h_out); (void)hipHostFree(h_in_keys_); (void)hipHostFree(h_in_vox_);
+      for (auto &e : st_ev_) (void)hipEventDestroy(e);
+    }
   }
 
   // tsdf_volume.cu:515-598
   void integrate_scan_async(const uint8_t *bgr, const float *depth, const float *pose16) {
     if (!bgr || !depth || !pose16) fail(DR_ERR_ARG, "IntegrateScanAsync: null argument");
     expect(kIntegrate, "Please call the functions like Integration -> RenderAsync -> GetRenderResults.");
+    if (st_radius_ <= 0.0f && !store_.empty()) fail(DR_ERR_PROTOCOL, "IntegrateScanAsync: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", store_.size());
     next_ = kRender;
     DR_HIP(hipSetDevice(device_));
     DR_HIP(hipEventSynchronize(int_done_));  // previous scan's use of the pinned staging buffers
+    if (st_radius_ > 0.0f) {
+      stream_before_scan(pose16, max_valid_depth(depth));
+    }
     memcpy(h_bgr_in_, bgr, npix_ * 3);
     memcpy(h_depth_in_, depth, npix_ * 4);
     DR_HIP(hipMemcpyAsync(d_bgr_in_, h_bgr_in_, npix_ * 3, hipMemcpyHostToDevice, int_stream_));
     DR_HIP(hipMemcpyAsync(d_depth_in_, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
     // the ray-casts read the volume; their result copies do not (the reference waits for the copies, tsdf_volume.cu:553-556)
     enqueue_scan(d_bgr_in_, d_depth_in_, pose16, true);
+    if (st_radius_ > 0.0f) stream_after_scan(pose16);
     DR_HIP(hipEventRecord(int_done_, int_stream_));
   }
   void launch_raycast(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P) {
@@ -1300,6 +1433,7 @@ class FusionEngine {
   // bench_sequence wrote -- the second-to-last one ran BESIDE the allocation of the last scan (enqueue_scan), which is what a test of
   // that overlap has to look at.
   void bench_render_host(int i, int back, const uint8_t **bgr, const float **depth) {
+    no_bench_while_streaming("drf_bench_render_host");
     if (i < 0 || i >= (int)renders_.size() || back < 0 || back > 1) fail(DR_ERR_ARG, "bench_render_host: stream %d of %zu, back %d", i, renders_.size(), back);
     DR_HIP(hipSetDevice(device_));
     DR_HIP(hipDeviceSynchronize());
@@ -1403,9 +1537,23 @@ class FusionEngine {
   // bench path: inputs already resident in HBM
   void integrate_device(const void *d_bgr, const void *d_depth, const float *pose16) {
     DR_HIP(hipSetDevice(device_));
+    if (st_radius_ > 0.0f) {  // the depths are on the device: bound the scan by max_sensor_depth
+      if (!d_bgr || !d_depth || !pose16) fail(DR_ERR_ARG, "drf_integrate_device: null argument");
+      DR_HIP(hipEventSynchronize(int_done_));
+      stream_before_scan(pose16, o_.max_sensor_depth);
+      enqueue_scan((const unsigned char *)d_bgr, (const float *)d_depth, pose16);
+      stream_after_scan(pose16);
+      DR_HIP(hipEventRecord(int_done_, int_stream_));
+      return;
+    }
+    if (!store_.empty()) fail(DR_ERR_PROTOCOL, "drf_integrate_device: blocks are in the host store while streaming is off");
     enqueue_scan((const unsigned char *)d_bgr, (const float *)d_depth, pose16);
   }
+  void no_bench_while_streaming(const char *what) {
+    if (st_radius_ > 0.0f || !store_.empty()) fail(DR_ERR_UNSUPPORTED, "%s: not available while streaming is on or the host store holds blocks", what);
+  }
   void bench_integrate(const void *d_bgr, const void *d_depth, const float *poses, int nscans, float *ms, float *kernel_ms) {
+    no_bench_while_streaming("drf_bench_integrate");
     DR_HIP(hipSetDevice(device_));
     std::vector<hipEvent_t> ev(2 * (size_t)nscans + 2);
     for (auto &e : ev) DR_HIP(hipEventCreate(&e));
@@ -1432,6 +1580,7 @@ class FusionEngine {
   // pinned double buffers, ordered by the same events as the operator path.  ms[0] = first allocate .. last copy
   // (hipEvents), ms[1..4] = sums of the allocate / integrate / ray-cast / D2H intervals, ms[5] = host wall clock.
   void bench_sequence(const void *d_bgr, const void *d_depth, const float *poses, int n, int render, float ms[6]) {
+    no_bench_while_streaming("drf_bench_sequence");
     if (!d_bgr || !d_depth || !poses || !ms || n <= 0) fail(DR_ERR_ARG, "bench_sequence: bad argument");
     expect(kIntegrate, "bench_sequence starts where IntegrateScanAsync may be called.");
     DR_HIP(hipSetDevice(device_));
@@ -1482,8 +1631,257 @@ class FusionEngine {
     check_device_flags();
   }
 
+  // ---- streaming: a bounded device pool plus a host store for the rest of the map (DESIGN.md "Streaming voxel blocks") ----
+  void set_streaming(float radius, size_t host_capacity_blocks) {
+    if (!(radius >= 0.0f) || !std::isfinite(radius)) fail(DR_ERR_ARG, "drf_set_streaming: radius must be finite and >= 0 (got %g)", radius);
+    const float rmin = streaming_min_radius(o_);
+    if (radius > 0.0f && radius < rmin) fail(DR_ERR_ARG, "drf_set_streaming: radius %g is below drf_streaming_min_radius = %g", radius, rmin);
+    settle();
+    if (!store_.empty()) fail(DR_ERR_PROTOCOL, "drf_set_streaming: the host store holds %zu blocks; bring them back with drf_stream_in_region first", store_.size());
+    if (radius > 0.0f) ensure_staging();
+    st_radius_ = radius;
+    st_host_cap_ = host_capacity_blocks ? host_capacity_blocks : (size_t)-1;
+    reach_.clear();
+    // blocks integrated before now are bounded by nothing the host knows: the first scan runs the selection pass
+    if (radius > 0.0f) reach_.push_back({0.0, 0.0, 0.0, HUGE_VAL});
+  }
+  void stream_out_region(const float *lower, const float *upper) {
+    if (!lower || !upper) fail(DR_ERR_ARG, "drf_stream_out_region: null argument");
+    expect(kIntegrate, "drf_stream_out_region: call it where IntegrateScanAsync may be called.");
+    settle();
+    ensure_staging();
+    F3 lo, hi, p{0.f, 0.f, 0.f};
+    lo.x = lower[0]; lo.y = lower[1]; lo.z = lower[2]; hi.x = upper[0]; hi.y = upper[1]; hi.z = upper[2];
+    // count first: a region that does not fit in the host store moves nothing
+    launch_eviction(p, 0.0f, lo, hi, 1, 0);
+    DR_HIP(hipStreamSynchronize(int_stream_));
+    ev_pending_ = false;
+    const size_t want = (size_t)sd_.h_out[1];
+    if (want > host_free()) fail(DR_ERR_CAPACITY, "drf_stream_out_region: %zu blocks do not fit in the host store (%zu free)", want, host_free());
+    for (;;) {
+      launch_eviction(p, 0.0f, lo, hi, 1, st_cap_);
+      DR_HIP(hipStreamSynchronize(int_stream_));
+      const bool more = sd_.h_out[1] > sd_.h_out[0];
+      fold_evicted();
+      if (!more) break;
+    }
+  }
+  void stream_in_region(const float *lower, const float *upper) {
+    if (!lower || !upper) fail(DR_ERR_ARG, "drf_stream_in_region: null argument");
+    expect(kIntegrate, "drf_stream_in_region: call it where IntegrateScanAsync may be called.");
+    settle();
+    std::vector<unsigned long long> keys;
+    double bl[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, bh[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    store_.for_each([&](unsigned long long k, const uint8_t *) {
+      int c[3]; unpack_key_host(k, c);
+      for (int a = 0; a < 3; ++a) {
+        const float org = blk_origin_host(c[a], o_.voxel_size);
+        if (!(org >= lower[a] && org <= upper[a])) return;
+      }
+      keys.push_back(k);
+      for (int a = 0; a < 3; ++a) { bl[a] = std::min(bl[a], blk_centre_host(c[a], o_.voxel_size)); bh[a] = std::max(bh[a], blk_centre_host(c[a], o_.voxel_size)); }
+    });
+    if (keys.empty()) return;
+    upload(keys);  // checks the pool's free room before anything moves
+    DR_HIP(hipStreamSynchronize(int_stream_));
+    if (st_radius_ > 0.0f) {  // the ball around the uploaded centres bounds them for the selection skip
+      double c[3], r = 0.0;
+      for (int a = 0; a < 3; ++a) { c[a] = 0.5 * (bl[a] + bh[a]); r += (bh[a] - bl[a]) * (bh[a] - bl[a]); }
+      reach_.push_back({c[0], c[1], c[2], 0.5 * std::sqrt(r) + o_.voxel_size});
+    }
+  }
+  // out: resident blocks, blocks in the host store, blocks streamed out / in (totals), bytes moved, last scan's streaming time (us)
+  void streaming_stats(uint64_t out[6]) {
+    settle();
+    int na = 0;
+    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
+    out[0] = (uint64_t)std::min(na, o_.num_blocks); out[1] = store_.size(); out[2] = st_out_total_; out[3] = st_in_total_;
+    out[4] = 4096 * (st_out_total_ + st_in_total_); out[5] = (uint64_t)std::llround(st_last_us_);
+  }
+  void export_host_blocks(int max_blocks, int32_t *coords, uint8_t *voxels, int *n) {
+    if (max_blocks < 0 || (max_blocks > 0 && (!coords || !voxels))) fail(DR_ERR_ARG, "drf_export_host_blocks: bad argument");
+    settle();
+    int i = 0;
+    store_.for_each([&](unsigned long long k, const uint8_t *v) {
+      if (i >= max_blocks) return;
+      unpack_key_host(k, coords + 3 * i);
+      memcpy(voxels + (size_t)i * 4096, v, 4096);
+      ++i;
+    });
+    if (n) *n = i;
+  }
+
  private:
   enum Next { kIntegrate, kRender, kGetRender };
+  static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
+  size_t host_free() const { return st_host_cap_ - std::min(st_host_cap_, store_.size()); }
+  // every pending eviction folded into the host store, the device idle
+  void settle() {
+    DR_HIP(hipSetDevice(device_));
+    DR_HIP(hipDeviceSynchronize());
+    fold_evicted();
+  }
+  void ensure_staging() {
+    if (st_cap_) return;
+    st_cap_ = std::min(o_.num_blocks, kStageBlocks);
+    sd_.ctl = dalloc<int>(8);
+    DR_HIP(hipMemset(sd_.ctl, 0, 32));
+    sd_.list = dalloc<int>(st_cap_);
+    sd_.mv_dst = dalloc<int>(st_cap_);
+    sd_.mv_src = dalloc<int>(st_cap_);
+    DR_HIP(hipHostMalloc((void **)&h_ev_keys_, (size_t)st_cap_ * 8, hipHostMallocDefault));
+    DR_HIP(hipHostMalloc((void **)&h_ev_vox_, (size_t)st_cap_ * 4096, hipHostMallocDefault));
+    DR_HIP(hipHostMalloc((void **)&sd_.h_out, 16, hipHostMallocDefault));  // 4 ints
+    memset(sd_.h_out, 0, 16);
+    DR_HIP(hipHostGetDevicePointer((void **)&sd_.h_keys, h_ev_keys_, 0));
+    DR_HIP(hipHostGetDevicePointer((void **)&sd_.h_vox, h_ev_vox_, 0));
+    DR_HIP(hipHostMalloc((void **)&h_in_keys_, (size_t)st_cap_ * 8, hipHostMallocDefault));
+    DR_HIP(hipHostMalloc((void **)&h_in_vox_, (size_t)st_cap_ * 4096, hipHostMallocDefault));
+    DR_HIP(hipHostGetDevicePointer((void **)&hd_in_keys_, h_in_keys_, 0));
+    DR_HIP(hipHostGetDevicePointer((void **)&hd_in_vox_, h_in_vox_, 0));
+    for (auto &e : st_ev_) DR_HIP(hipEventCreate(&e));
+  }
+  // Enqueue the eviction chain on int_stream_ behind every render stream's last ray-cast (blocks move).  box = 0: blocks whose
+  // centre lies beyond sqrt(r2) of p; box = 1: blocks whose origin lies in [lo, hi].  cap = 0 only counts (sd_.h_out[1]).
+  void launch_eviction(F3 p, float r2, F3 lo, F3 hi, int box, int cap) {
+    for (auto &r : renders_) DR_HIP(hipStreamWaitEvent(int_stream_, r.cast, 0));
+    StreamDev s = sd_;
+    s.cap = cap;
+    const int g = 512;
+    hipLaunchKernelGGL(k_ev_select, dim3(g), dim3(256), 0, int_stream_, d_, s, p, r2, lo, hi, box);
+    if (cap > 0) {
+      hipLaunchKernelGGL(k_ev_gather, dim3(g), dim3(256), 0, int_stream_, d_, s);
+      hipLaunchKernelGGL(k_ev_pair, dim3(cdiv(cap, 256)), dim3(256), 0, int_stream_, d_, s);
+      hipLaunchKernelGGL(k_ev_move, dim3(g), dim3(256), 0, int_stream_, d_, s);
+      hipLaunchKernelGGL(k_ev_zero_tail, dim3(g), dim3(256), 0, int_stream_, d_, s);
+      hipLaunchKernelGGL(k_ev_clear, dim3(1024), dim3(256), 0, int_stream_, d_, s, d_.cmask + 1u);
+      hipLaunchKernelGGL(k_ev_reindex, dim3(g), dim3(256), 0, int_stream_, d_, s);
+    }
+    hipLaunchKernelGGL(k_ev_finish, dim3(1), dim3(64), 0, int_stream_, d_, s);
+    DR_HIP(hipGetLastError());
+    ev_pending_ = cap > 0;
+  }
+  // the blocks the last eviction chain gathered -> host store (int_stream_ must be idle)
+  void fold_evicted() {
+    if (st_scan_done_) {  // device time of the last scan's stream-in and eviction launches (0 if it had none)
+      float a = 0.f, b = 0.f;
+      if (st_timed_ & 1) DR_HIP(hipEventElapsedTime(&a, st_ev_[0], st_ev_[1]));
+      if (st_timed_ & 2) DR_HIP(hipEventElapsedTime(&b, st_ev_[2], st_ev_[3]));
+      st_last_us_ = 1000.0 * (a + b);
+      st_timed_ = 0;
+      st_scan_done_ = false;
+    }
+    if (!ev_pending_) return;
+    ev_pending_ = false;
+    const int m = sd_.h_out[0];
+    for (int i = 0; i < m; ++i) store_.put(h_ev_keys_[i], h_ev_vox_ + (size_t)i * 4096);
+    st_out_total_ += (uint64_t)m;
+    // the automatic pass took every block beyond radius + hysteresis: what is resident now lies within the largest distance it
+    // saw among the blocks that stayed (plus a voxel for the fp32 distance) of its centre
+    if (ev_auto_ && sd_.h_out[1] == m) {
+      float kept2;
+      memcpy(&kept2, &sd_.h_out[3], 4);
+      const double r = std::min((double)st_radius_ + hysteresis(), std::sqrt((double)kept2) + o_.voxel_size);
+      reach_.assign(1, {ev_p_[0], ev_p_[1], ev_p_[2], r});
+    }
+    ev_auto_ = false;
+  }
+  // stored blocks -> the end of the pool (behind every render stream's last ray-cast).  DR_ERR_CAPACITY before anything moves
+  // if they do not fit.
+  void upload(const std::vector<unsigned long long> &keys) {
+    ensure_staging();
+    int na = 0;
+    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
+    na = std::min(na, o_.num_blocks);
+    if ((size_t)na + keys.size() > (size_t)o_.num_blocks)
+      fail(DR_ERR_CAPACITY, "stream-in of %zu blocks does not fit in the pool (%d of num_blocks=%d in use)", keys.size(), na, o_.num_blocks);
+    for (auto &r : renders_) DR_HIP(hipStreamWaitEvent(int_stream_, r.cast, 0));
+    for (size_t b = 0; b < keys.size(); b += st_cap_) {
+      if (b) DR_HIP(hipStreamSynchronize(int_stream_));  // the pinned upload is reused
+      const int n = (int)std::min(keys.size() - b, (size_t)st_cap_);
+      for (int i = 0; i < n; ++i) {
+        h_in_keys_[i] = keys[b + i];
+        memcpy(h_in_vox_ + (size_t)i * 4096, store_.get(keys[b + i]), 4096);
+        store_.erase(keys[b + i]);
+      }
+      hipLaunchKernelGGL(k_in_place, dim3(std::min(cdiv(n, 4), 1024)), dim3(256), 0, int_stream_, d_, hd_in_keys_, (const uint4 *)hd_in_vox_, n);
+      hipLaunchKernelGGL(k_in_finish, dim3(1), dim3(64), 0, int_stream_, d_.n_alloc, n);
+      DR_HIP(hipGetLastError());
+    }
+    st_in_total_ += keys.size();
+  }
+  double hysteresis() const { return (double)kBS * o_.voxel_size; }  // one block edge
+  // the scan's largest valid depth bounds what it touches (stream_reach); eight branch-free running maxima so that the host
+  // compiler vectorises the pass over the image
+  float max_valid_depth(const float *depth) const {
+    const float lo = o_.min_sensor_depth, hi = o_.max_sensor_depth;
+    float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, r = 0.f;
+    size_t i = 0;
+    for (; i + 8 <= npix_; i += 8)
+      for (int k = 0; k < 8; ++k) {
+        const float z = depth[i + k], v = (z >= lo && z <= hi) ? z : 0.f;
+        m[k] = v > m[k] ? v : m[k];
+      }
+    for (; i < npix_; ++i) {
+      const float z = depth[i];
+      if (z >= lo && z <= hi && z > r) r = z;
+    }
+    for (int k = 0; k < 8; ++k) r = m[k] > r ? m[k] : r;
+    return r;
+  }
+  // Automatic mode, before k_allocate: fold the previous scan's evictions, bring back every stored block whose centre lies
+  // within the radius of this scan's camera centre.  No launch and no wait when nothing comes in.
+  void stream_before_scan(const float *pose16, float depth_bound) {
+    DR_HIP(hipStreamSynchronize(int_stream_));
+    fold_evicted();
+    const double p[3] = {pose16[3], pose16[7], pose16[11]};
+    std::vector<unsigned long long> in;
+    store_.query_sphere(p, st_radius_, o_.voxel_size, in);
+    double r = stream_reach(o_, depth_bound);
+    if (!in.empty()) {
+      DR_HIP(hipEventRecord(st_ev_[0], int_stream_));
+      upload(in);
+      DR_HIP(hipEventRecord(st_ev_[1], int_stream_));
+      st_timed_ |= 1;
+      r = std::max(r, (double)st_radius_);
+    }
+    add_reach(p, r);
+  }
+  // After the scan: select resident blocks beyond radius + hysteresis, unless the host can tell that there are none -- every
+  // block centre lies within reach_[j].r of some reach_[j].p, so if max_j |p - p_j| + r_j <= radius + hysteresis nothing is launched.
+  void stream_after_scan(const float *pose16) {
+    const double p[3] = {pose16[3], pose16[7], pose16[11]};
+    const double lim = (double)st_radius_ + hysteresis();
+    double far = 0.0;
+    for (auto &b : reach_) far = std::max(far, std::sqrt((p[0] - b[0]) * (p[0] - b[0]) + (p[1] - b[1]) * (p[1] - b[1]) + (p[2] - b[2]) * (p[2] - b[2])) + b[3]);
+    const int cap = (int)std::min((size_t)st_cap_, host_free());
+    st_scan_done_ = true;
+    if (far <= lim || cap == 0) return;
+    F3 pf; pf.x = pose16[3]; pf.y = pose16[7]; pf.z = pose16[11];
+    const float r2 = (float)(lim * lim);
+    DR_HIP(hipEventRecord(st_ev_[2], int_stream_));
+    launch_eviction(pf, r2, pf, pf, 0, cap);
+    DR_HIP(hipEventRecord(st_ev_[3], int_stream_));
+    st_timed_ |= 2;
+    ev_auto_ = true;
+    ev_p_[0] = p[0]; ev_p_[1] = p[1]; ev_p_[2] = p[2];
+  }
+  // reach_: balls that hold every block centre of the map; a new ball drops the ones it contains, and a long list collapses into
+  // one ball around the newest centre
+  void add_reach(const double p[3], double r) {
+    std::vector<std::array<double, 4>> keep;
+    for (auto &b : reach_) {
+      const double d = std::sqrt((p[0] - b[0]) * (p[0] - b[0]) + (p[1] - b[1]) * (p[1] - b[1]) + (p[2] - b[2]) * (p[2] - b[2]));
+      if (d + b[3] > r) keep.push_back(b);
+    }
+    keep.push_back({p[0], p[1], p[2], r});
+    if (keep.size() > 256) {
+      double R = 0.0;
+      for (auto &b : keep) R = std::max(R, std::sqrt((p[0] - b[0]) * (p[0] - b[0]) + (p[1] - b[1]) * (p[1] - b[1]) + (p[2] - b[2]) * (p[2] - b[2])) + b[3]);
+      keep.assign(1, {p[0], p[1], p[2], R});
+    }
+    reach_.swap(keep);
+  }
   void expect(Next want, const char *msg) {
     static const char *names[] = {"IntegrateScanAsync", "RenderAsync", "GetRenderResult"};
     if (next_ != want) fail(DR_ERR_PROTOCOL, "%s You should have called %s", msg, names[next_]);
@@ -1655,6 +2053,22 @@ class FusionEngine {
   unsigned *mesh_counts_ = nullptr, *mesh_offsets_ = nullptr;
   unsigned char *mesh_tmp_ = nullptr;
   float *mesh_vert_ = nullptr, *mesh_cols_ = nullptr;
+  // streaming state (staging allocated with the first drf_set_streaming / region call)
+  float st_radius_ = 0.0f;                  // 0 = off
+  size_t st_host_cap_ = (size_t)-1;         // host store capacity in blocks
+  HostBlockStore store_;
+  int st_cap_ = 0;                          // staging capacity in blocks (0 = not allocated)
+  StreamDev sd_{};
+  unsigned long long *h_ev_keys_ = nullptr, *h_in_keys_ = nullptr, *hd_in_keys_ = nullptr;
+  uint8_t *h_ev_vox_ = nullptr, *h_in_vox_ = nullptr, *hd_in_vox_ = nullptr;
+  hipEvent_t st_ev_[4] = {nullptr, nullptr, nullptr, nullptr};  // [0..1] stream-in, [2..3] eviction of the last scan
+  int st_timed_ = 0;
+  bool st_scan_done_ = false;
+  double st_last_us_ = 0.0;
+  bool ev_pending_ = false, ev_auto_ = false;  // an eviction chain awaits folding; it was the automatic one (centre ev_p_)
+  double ev_p_[3] = {0.0, 0.0, 0.0};
+  std::vector<std::array<double, 4>> reach_;  // balls (centre, radius) that hold every block centre of the map
+  uint64_t st_out_total_ = 0, st_in_total_ = 0;
 };
 
 }  // namespace dr
@@ -1747,6 +2161,28 @@ int drf_bench_render_host(drf_t *h, int stream, int back, const uint8_t **bgr, c
 }
 int drf_bench_integrate(drf_t *h, const void *d_bgr, const void *d_depth, const float *poses16, int nscans, float *ms, float *kernel_ms) {
   return guarded([&] { eng(h)->bench_integrate(d_bgr, d_depth, poses16, nscans, ms, kernel_ms); });
+}
+int drf_streaming_min_radius(const drf_options_t *o, float *radius) {
+  return guarded([&] {
+    if (!o || !radius) dr::fail(DR_ERR_ARG, "drf_streaming_min_radius: null argument");
+    if (!dr::stream_options_ok(*o)) dr::fail(DR_ERR_ARG, "drf_streaming_min_radius: invalid options (voxel_size, fx, fy, max_sensor_depth must be > 0, width and height > 0)");
+    *radius = dr::streaming_min_radius(*o);
+  });
+}
+int drf_set_streaming(drf_t *h, float radius, size_t host_capacity_blocks) {
+  return guarded([&] { eng(h)->set_streaming(radius, host_capacity_blocks); });
+}
+int drf_stream_out_region(drf_t *h, const float lower[3], const float upper[3]) {
+  return guarded([&] { eng(h)->stream_out_region(lower, upper); });
+}
+int drf_stream_in_region(drf_t *h, const float lower[3], const float upper[3]) {
+  return guarded([&] { eng(h)->stream_in_region(lower, upper); });
+}
+int drf_streaming_stats(drf_t *h, uint64_t out[6]) {
+  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_streaming_stats: null argument"); eng(h)->streaming_stats(out); });
+}
+int drf_export_host_blocks(drf_t *h, int max_blocks, int32_t *coords, uint8_t *voxels, int *n) {
+  return guarded([&] { eng(h)->export_host_blocks(max_blocks, coords, voxels, n); });
 }
 
 }  // extern "C"

@@ -1,0 +1,225 @@
+// stream_kernels.h -- moving voxel blocks between the device pool and the host store (DESIGN.md "Streaming voxel blocks").
+// Included by dr_fusion.hip inside namespace dr, after FusionDev and the block-index helpers.
+//
+// Eviction is one chain on the integration stream, launched after the scan's k_fold_counter:
+//   k_ev_select    one lane per pool block: blocks whose centre lies beyond the radius (or whose origin lies in a box) go to
+//                  the selection list, at most `cap` of them (the rest wait for the next chain)
+//   k_ev_gather    one wave per selected block: its key and 4 KB straight into mapped pinned host staging; grid cell and
+//                  presence bit cleared, blk_key marked empty
+//   k_ev_pair      holes below the new block count <-> surviving blocks of the tail [new n_alloc, old n_alloc)
+//   k_ev_move      one wave per pair: a surviving tail block moves into a hole (voxels, key, grid cell)
+//   k_ev_zero_tail the vacated tail slots get zero voxels again (k_alloc_commit hands slots out assuming so)
+//   k_ev_clear     superblock flags -- and the open-addressing table when it holds blocks -- emptied
+//   k_ev_reindex   rebuilt from the surviving blocks [0, new n_alloc)
+//   k_ev_finish    n_alloc (and the table's block count) updated, the counts published to pinned memory
+// Every kernel after k_ev_select exits at once when the selection is empty.  Stream-in (k_in_place + k_in_finish) appends
+// blocks from a pinned upload to the pool and publishes them the way k_alloc_commit does.
+
+struct StreamDev {
+  int *ctl;                    // [0] blocks selected (uncapped), [1] holes, [2] tail survivors, [3] table blocks re-inserted,
+                               // [4] largest squared centre distance of an UNselected block (radius mode; fp32 bits)
+  int *list;                   // [cap] pool indices of the selected blocks
+  int *mv_dst, *mv_src;        // [cap] compaction pairs
+  unsigned long long *h_keys;  // mapped pinned staging (device addresses): keys of the gathered blocks
+  uint4 *h_vox;                //   and their voxels, 4 KB per block
+  int *h_out;                  // mapped pinned: [0] blocks gathered, [1] blocks selected (uncapped), [2] n_alloc afterwards, [3] = ctl[4]
+  int cap;                     // blocks this chain may take (staging size, bounded by the host store's free capacity)
+};
+
+__device__ inline int pool_count(const FusionDev &d) { return min(*d.n_alloc, d.o.num_blocks); }
+__device__ inline int ev_taken(const StreamDev &s) { return min(s.ctl[0], s.cap); }
+
+// Streaming centre of block P: the centre of the cube of points that map into it, ((8 P + 3.5) voxel_size) per axis
+// (voxel g covers ((g - 0.5) vs, (g + 0.5) vs)).  Origin: 8 P voxel_size, the corner k_cull and k_integrate use.
+__device__ inline float blk_centre(int c, float vs) { return ((float)(c * kBS) + 3.5f) * vs; }
+__device__ inline float blk_origin(int c, float vs) { return (float)(c * kBS) * vs; }
+
+// box == 0: select blocks whose centre lies farther than sqrt(r2) from p;  box != 0: blocks whose origin lies in [lo, hi]
+__global__ __launch_bounds__(256) void k_ev_select(const FusionDev d, const StreamDev s, F3 p, float r2, F3 lo, F3 hi, int box) {
+  const int n = pool_count(d);
+  const float vs = d.o.voxel_size;
+  const int lane = threadIdx.x & 63;
+  float kept = 0.0f;  // largest squared distance among the blocks that stay (lets the host skip later passes)
+  for (int e0 = (blockIdx.x * blockDim.x + threadIdx.x) & ~63; e0 < n; e0 += gridDim.x * blockDim.x) {
+    const int e = e0 + lane;
+    bool sel = false;
+    if (e < n) {
+      const I3 P = unpack_key(d.blk_key[e]);
+      if (box) {
+        const float ox = blk_origin(P.x, vs), oy = blk_origin(P.y, vs), oz = blk_origin(P.z, vs);
+        sel = ox >= lo.x && ox <= hi.x && oy >= lo.y && oy <= hi.y && oz >= lo.z && oz <= hi.z;
+      } else {
+        const float dx = blk_centre(P.x, vs) - p.x, dy = blk_centre(P.y, vs) - p.y, dz = blk_centre(P.z, vs) - p.z;
+        const float q = dx * dx + dy * dy + dz * dz;
+        sel = q > r2;
+        if (!sel) kept = fmaxf(kept, q);
+      }
+    }
+    const unsigned long long m = __ballot(sel);
+    if (!m) continue;
+    const int leader = __ffsll((long long)m) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(&s.ctl[0], __popcll(m));
+    base = __builtin_amdgcn_readlane(base, leader);
+    if (sel) {
+      const int slot = base + __popcll(m & ((1ull << lane) - 1));
+      if (slot < s.cap) s.list[slot] = e;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) kept = fmaxf(kept, __shfl_xor(kept, off));
+  if (lane == 0 && kept > 0.0f) atomicMax(reinterpret_cast<unsigned *>(&s.ctl[4]), __float_as_uint(kept));  // non-negative floats order as their bits
+}
+
+__global__ __launch_bounds__(256) void k_ev_gather(const FusionDev d, const StreamDev s) {
+  const int m = ev_taken(s);
+  if (m == 0) return;
+  const int lane = threadIdx.x & 63;
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < m; i += gridDim.x * 4) {
+    const int e = s.list[i];
+    const uint4 *src = reinterpret_cast<const uint4 *>(d.vox + (size_t)e * 512);
+    uint4 *dst = s.h_vox + (size_t)i * 256;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dst[lane + 64 * k] = src[lane + 64 * k];
+    if (lane == 0) {
+      const unsigned long long key = d.blk_key[e];
+      s.h_keys[i] = key;
+      d.blk_key[e] = kEmptyKey;  // k_ev_pair: this slot is not a survivor
+      unsigned idx;
+      if (grid_index(unpack_key(key), idx)) {
+        d.grid[idx] = 0;
+        atomicAnd(&d.present[idx >> 5], ~(1u << (idx & 31)));
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ev_pair(const FusionDev d, const StreamDev s) {
+  const int m = ev_taken(s);
+  if (m == 0) return;
+  const int n2 = pool_count(d) - m;
+  // holes = selected blocks below n2; survivors = unselected blocks of [n2, n2 + m): equally many
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
+    const int e = s.list[i];
+    if (e < n2) s.mv_dst[atomicAdd(&s.ctl[1], 1)] = e;
+    if (d.blk_key[n2 + i] != kEmptyKey) s.mv_src[atomicAdd(&s.ctl[2], 1)] = n2 + i;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ev_move(const FusionDev d, const StreamDev s) {
+  const int nm = s.ctl[1];
+  if (nm == 0) return;
+  const int lane = threadIdx.x & 63;
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < nm; i += gridDim.x * 4) {
+    const int src = s.mv_src[i], dst = s.mv_dst[i];
+    const uint4 *a = reinterpret_cast<const uint4 *>(d.vox + (size_t)src * 512);
+    uint4 *b = reinterpret_cast<uint4 *>(d.vox + (size_t)dst * 512);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[lane + 64 * k] = a[lane + 64 * k];
+    if (lane == 0) {
+      const unsigned long long key = d.blk_key[src];
+      d.blk_key[dst] = key;
+      unsigned idx;
+      if (grid_index(unpack_key(key), idx)) d.grid[idx] = dst + 1;  // table blocks: k_ev_reindex
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ev_zero_tail(const FusionDev d, const StreamDev s) {
+  const int m = ev_taken(s);
+  if (m == 0) return;
+  const int n2 = pool_count(d) - m;
+  const int lane = threadIdx.x & 63;
+  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < m; i += gridDim.x * 4) {
+    uint4 *b = reinterpret_cast<uint4 *>(d.vox + (size_t)(n2 + i) * 512);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[lane + 64 * k] = z;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ev_clear(const FusionDev d, const StreamDev s, unsigned table_cap) {
+  if (ev_taken(s) == 0) return;
+  const bool table = d.n_alloc[3] != 0;
+  const unsigned n0 = 1u << (3 * (kGridBits - kSuperShift[0])), n1 = 1u << (3 * (kGridBits - kSuperShift[1]));
+  const unsigned n = max(max(n0, n1), table ? table_cap : 0u);
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    if (i < n0) d.super[0][i] = 0;
+    if (i < n1) d.super[1][i] = 0;
+    if (table && i < table_cap) { d.keys[i] = kEmptyKey; d.vals[i] = -1; }
+  }
+}
+
+// insert a block that is known to be absent from the table with its pool index (HashTable::AllocateBlock without the pool)
+__device__ inline void table_insert(const FusionDev &d, unsigned long long key, int val) {
+  unsigned s = hash_key(key) & d.cmask;
+  for (unsigned probe = 0; probe <= d.cmask; ++probe) {
+    const unsigned long long cur = atomicCAS(&d.keys[s], kEmptyKey, key);
+    if (cur == kEmptyKey || cur == key) {
+      __hip_atomic_store(&d.vals[s], val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+    s = (s + 1) & d.cmask;
+  }
+  d.err[0] = 1;
+}
+
+__device__ inline void set_super(const FusionDev &d, unsigned idx) {
+  d.super[0][super_index<kSuperShift[0]>(idx)] = 1;
+  d.super[1][super_index<kSuperShift[1]>(idx)] = 1;
+}
+
+__global__ __launch_bounds__(256) void k_ev_reindex(const FusionDev d, const StreamDev s) {
+  const int m = ev_taken(s);
+  if (m == 0) return;
+  const bool table = d.n_alloc[3] != 0;
+  const int n2 = pool_count(d) - m;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < n2; e += gridDim.x * blockDim.x) {
+    const unsigned long long key = d.blk_key[e];
+    unsigned idx;
+    if (grid_index(unpack_key(key), idx)) set_super(d, idx);
+    else if (table) { table_insert(d, key, e); atomicAdd(&s.ctl[3], 1); }
+  }
+}
+
+__global__ void k_ev_finish(const FusionDev d, const StreamDev s) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int raw = s.ctl[0], m = min(raw, s.cap);
+  int n = pool_count(d);
+  if (m > 0) {
+    n -= m;
+    d.n_alloc[0] = n;
+    if (d.n_alloc[3] != 0) d.n_alloc[3] = s.ctl[3];
+  }
+  s.h_out[0] = m; s.h_out[1] = raw; s.h_out[2] = n; s.h_out[3] = s.ctl[4];
+  s.ctl[0] = s.ctl[1] = s.ctl[2] = s.ctl[3] = s.ctl[4] = 0;
+}
+
+// Stream-in: n blocks from the pinned upload (keys, 4 KB each) appended at the end of the pool.  The host has checked that
+// they fit and that none of them is resident.
+__global__ __launch_bounds__(256) void k_in_place(const FusionDev d, const unsigned long long *__restrict__ keys, const uint4 *__restrict__ vox, int n) {
+  const int base = pool_count(d);
+  const int lane = threadIdx.x & 63;
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+    const int p = base + i;
+    const uint4 *a = vox + (size_t)i * 256;
+    uint4 *b = reinterpret_cast<uint4 *>(d.vox + (size_t)p * 512);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[lane + 64 * k] = a[lane + 64 * k];
+    if (lane == 0) {
+      const unsigned long long key = keys[i];
+      d.blk_key[p] = key;
+      unsigned idx;
+      if (grid_index(unpack_key(key), idx)) {
+        d.grid[idx] = p + 1;
+        atomicOr(&d.present[idx >> 5], 1u << (idx & 31));
+        set_super(d, idx);
+      } else {
+        table_insert(d, key, p);
+        atomicAdd(&d.n_alloc[3], 1);
+      }
+    }
+  }
+}
+__global__ void k_in_finish(int *n_alloc, int n) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) n_alloc[0] += n;
+}

@@ -18,6 +18,13 @@ def DrFusionOptions(**kw):
     return FusionOptions(**d)
 
 
+def streaming_min_radius(options):
+    """drf_streaming_min_radius: the smallest exact streaming radius for these options (host-only)."""
+    r = C.c_float()
+    check(_lib.lib().drf_streaming_min_radius(C.byref(options), C.byref(r)))
+    return float(r.value)
+
+
 class DrFusion:
     def __init__(self, options, device=0):
         self.options = options
@@ -154,6 +161,44 @@ class DrFusion:
         bgr = np.ctypeslib.as_array(C.cast(b, u8p), shape=(H, W, 3)).copy()
         depth = np.ctypeslib.as_array(C.cast(d, C.POINTER(C.c_float)), shape=(H, W)).copy()
         return bgr, depth
+
+    # ---- streaming: bounded device pool + host store (include/dr_mi355x.h, DESIGN.md "Streaming voxel blocks") ----
+    def set_streaming(self, radius, host_capacity_blocks=0):
+        """radius 0 = off; otherwise >= streaming_min_radius(options).  host_capacity_blocks 0 = unbounded host store."""
+        check(self._L.drf_set_streaming(self._h, float(radius), int(host_capacity_blocks)))
+
+    def stream_out_region(self, lower, upper):
+        """Moves every resident block whose origin lies in [lower, upper] to the host store."""
+        lo, up = (np.ascontiguousarray(a, np.float32) for a in (lower, upper))
+        check(self._L.drf_stream_out_region(self._h, fptr(lo), fptr(up)))
+
+    def stream_in_region(self, lower, upper):
+        """Brings every stored block whose origin lies in [lower, upper] back into the pool (DrError DR_ERR_CAPACITY, nothing moved, if they do not fit)."""
+        lo, up = (np.ascontiguousarray(a, np.float32) for a in (lower, upper))
+        check(self._L.drf_stream_in_region(self._h, fptr(lo), fptr(up)))
+
+    def streaming_stats(self):
+        out = (C.c_uint64 * 6)()
+        check(self._L.drf_streaming_stats(self._h, out))
+        return dict(resident=int(out[0]), host=int(out[1]), streamed_out=int(out[2]), streamed_in=int(out[3]), bytes_moved=int(out[4]),
+                    last_scan_us=int(out[5]))
+
+    def export_host_blocks(self):
+        """The host store as export_blocks() formats the resident blocks."""
+        n = self.streaming_stats()["host"]
+        coords = np.empty((max(n, 1), 3), np.int32)
+        vox = np.empty((max(n, 1), 4096), np.uint8)
+        got = C.c_int()
+        check(self._L.drf_export_host_blocks(self._h, n, coords.ctypes.data_as(C.POINTER(C.c_int32)), vox.ctypes.data_as(u8p), C.byref(got)))
+        return {tuple(int(v) for v in coords[i]): vox[i] for i in range(got.value)}
+
+    def export_all_blocks(self):
+        """The whole map: resident blocks and the host store merged (a block is in exactly one of them)."""
+        a, b = self.export_blocks(), self.export_host_blocks()
+        both = a.keys() & b.keys()
+        assert not both, "blocks both resident and stored: %s" % sorted(both)[:3]
+        a.update(b)
+        return a
 
     def bench_integrate(self, bgrs, depths, poses):
         """Uploads the scans once, then times back-to-back allocate+integrate of all of them (HBM-resident)."""

@@ -82,6 +82,12 @@ public:
   }
   void Synchronize() { check(drf_synchronize(impl)); }
 
+  // Extension (no reference counterpart): stream voxel blocks to host memory so the map may outgrow num_blocks
+  // (dr_mi355x.h, INTEGRATION.md "Streaming").  radius 0 = off; otherwise at least drf_streaming_min_radius of the options.
+  void SetStreaming(float radius, size_t host_capacity_blocks) { check(drf_set_streaming(impl, radius, host_capacity_blocks)); }
+  void StreamOutRegion(float lower_corner[3], float upper_corner[3]) { check(drf_stream_out_region(impl, lower_corner, upper_corner)); }
+  void StreamInRegion(float lower_corner[3], float upper_corner[3]) { check(drf_stream_in_region(impl, lower_corner, upper_corner)); }
+
   size_t dr_mesh_num = 0;
   const size_t dr_mesh_num_max = 60000000;
   float *dr_mesh_vert;
