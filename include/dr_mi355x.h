@@ -260,9 +260,10 @@ int drf_bench_render_host(drf_t *h, int stream, int back, const uint8_t **bgr, c
  *   after every scan is bit-identical to an engine whose pool never runs out, and so are the update counts.  A ray-cast
  *   equals that engine's when its pose lies within radius - drf_streaming_min_radius of the last scan's camera centre (the
  *   scan pose itself always qualifies).  Farther renders see the resident blocks only.
- * drf_export_blocks, mesh extraction and rendering cover the RESIDENT blocks; bring a region back with drf_stream_in_region
- *   before meshing it.  drf_bench_* return DR_ERR_UNSUPPORTED while streaming is on or the host store holds blocks, and
- *   integrating with streaming off while the host store holds blocks is DR_ERR_PROTOCOL. */
+ * drf_export_blocks and rendering cover the RESIDENT blocks.  Mesh extraction covers them too by default; after
+ *   drf_set_mesh_scope(h, DRF_MESH_MAP) it covers resident blocks and host store together, without moving a block.
+ *   drf_bench_* return DR_ERR_UNSUPPORTED while streaming is on or the host store holds blocks, and integrating with
+ *   streaming off while the host store holds blocks is DR_ERR_PROTOCOL. */
 /* Smallest exact radius for these options: the farthest a block centre can lie from a scan's camera centre and still be
  * allocated, updated or ray-cast by it at the scan pose, plus one block diagonal; host-only, needs no device.
  * With rho = max |((u - cx)/fx, (v - cy)/fy, 1)| over the image corners and s = sqrt(3) * voxel_size:
@@ -283,6 +284,18 @@ int drf_stream_in_region(drf_t *h, const float lower[3], const float upper[3]);
 int drf_streaming_stats(drf_t *h, uint64_t out[6]);
 /* The host store in the format of drf_export_blocks. */
 int drf_export_host_blocks(drf_t *h, int max_blocks, int32_t *coords, uint8_t *voxels, int *n);
+/* What drf_extract_mesh_async (with drf_mesh_num_triangles / drf_get_mesh_sync) and drf_save_mesh mesh.
+ * DRF_MESH_RESIDENT (the default): the pool's blocks.  DRF_MESH_MAP: the pool and the host store together; the mesh equals,
+ *   byte for byte and in the same triangle order (blocks by ascending packed key, then cells), the one an engine whose pool
+ *   never ran out returns for the same scans and box.  It first folds pending evictions, then stages the host blocks it needs
+ *   chunk by chunk through a bounded device scratch: the pool, its slot order, the host store and the streaming state stay
+ *   unchanged, and it works with a full pool.  With an empty host store it is the resident pass.  DESIGN.md §7c.
+ * A scope other than the two is DR_ERR_ARG; changing it while an extraction is pending is DR_ERR_PROTOCOL. */
+enum { DRF_MESH_RESIDENT = 0, DRF_MESH_MAP = 1 };
+int drf_set_mesh_scope(drf_t *h, int scope);
+/* Last extraction: [0] blocks meshed (resident + stored), [1] host blocks uploaded (a block staged by k chunks counts k
+ * times), [2] chunks (1 for a resident pass over a non-empty pool). */
+int drf_mesh_stats(drf_t *h, uint64_t out[3]);
 
 /* ======================================================================================================
  * DrCoarseTracker -- the dense coarse tracker operator.  Replaces

@@ -27,10 +27,12 @@
 #include <cstdio>
 #include <cstring>
 #include <chrono>
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <memory>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>  // device radix sort (block keys) and exclusive scan (triangle offsets) of the mesh path
@@ -1138,6 +1140,13 @@ static inline void unpack_key_host(unsigned long long k, int c[3]) {
   c[1] = (int)((k >> 21) & 0x1fffff) - B;
   c[2] = (int)(k & 0x1fffff) - B;
 }
+static inline bool pack_key_host(const int c[3], unsigned long long &k) {
+  const int B = 1 << 20;
+  for (int a = 0; a < 3; ++a)
+    if (c[a] < -B || c[a] >= B) return false;
+  k = ((unsigned long long)(unsigned)(c[0] + B) << 42) | ((unsigned long long)(unsigned)(c[1] + B) << 21) | (unsigned long long)(unsigned)(c[2] + B);
+  return true;
+}
 static inline float blk_origin_host(int c, float vs) { return (float)(c * kBS) * vs; }
 static inline double blk_centre_host(int c, float vs) { return ((double)(c * kBS) + 3.5) * vs; }
 
@@ -1159,6 +1168,7 @@ class HostBlockStore {
     cells_[cell_of(key)].push_back(key);
   }
   const uint8_t *get(unsigned long long key) const { return at(slot_.at(key)); }
+  bool contains(unsigned long long key) const { return slot_.count(key) != 0; }
   void erase(unsigned long long key) {
     auto it = slot_.find(key);
     free_.push_back(it->second);
@@ -1322,6 +1332,12 @@ class FusionEngine {
     (void)hipFree(mesh_axis_); (void)hipFree(mesh_keys_); (void)hipFree(mesh_total_); (void)hipFree(mesh_counts_);
     (void)hipFree(mesh_offsets_); (void)hipFree(mesh_tmp_); (void)hipFree(mesh_vert_); (void)hipFree(mesh_cols_);
     if (mesh_done_) (void)hipEventDestroy(mesh_done_);
+    for (int b = 0; b < 2; ++b) {
+      (void)hipFree(ms_dev_[b]); (void)hipHostFree(ms_host_[b]);
+      if (ms_copied_[b]) (void)hipEventDestroy(ms_copied_[b]);
+      if (ms_used_[b]) (void)hipEventDestroy(ms_used_[b]);
+    }
+    if (ms_copy_stream_) (void)hipStreamDestroy(ms_copy_stream_);
     if (st_cap_) {
       (void)hipFree(sd_.ctl); (void)hipFree(sd_.list); (void)hipFree(sd_.mv_dst); (void)hipFree(sd_.mv_src);
       (void)hipHostFree(h_ev_keys_); (void)hipHostFree(h_ev_vox_); (void)hipHostFree(sd_.h_out); (void)hipHostFree(h_in_keys_); (void)hipHostFree(h_in_vox_);
@@ -1497,7 +1513,7 @@ class FusionEngine {
     if (!lower || !upper) fail(DR_ERR_ARG, "ExtractMeshAsync: null argument");
     expect(kIntegrate, "Please call this functions after GetRenderResult.");
     if (mesh_pending_) fail(DR_ERR_PROTOCOL, "mesh_extractor should be NULL (fetch the previous mesh with GetMeshSync first)");
-    launch_mesh(lower, upper);
+    launch_extraction(lower, upper);
     mesh_pending_ = true;
   }
   size_t mesh_num_triangles() {  // blocks until the pending extraction is done; does not consume it
@@ -1521,7 +1537,7 @@ class FusionEngine {
   void save_mesh(const char *filename, const float *lower, const float *upper) {
     if (!filename || !lower || !upper) fail(DR_ERR_ARG, "SaveMeshToFile: null argument");
     if (mesh_pending_) fail(DR_ERR_PROTOCOL, "SaveMeshToFile: an ExtractMeshAsync is pending, call GetMeshSync first");
-    launch_mesh(lower, upper);
+    launch_extraction(lower, upper);
     const size_t ntri = finish_mesh();
     std::vector<float> v(ntri * 9), c(ntri * 9);
     DR_HIP(hipMemcpy(v.data(), mesh_vert_, ntri * 36, hipMemcpyDeviceToHost));
@@ -1532,6 +1548,17 @@ class FusionEngine {
       fprintf(f, "v %g %g %g %g %g %g\n", v[3 * i], v[3 * i + 1], v[3 * i + 2], c[3 * i], c[3 * i + 1], c[3 * i + 2]);
     for (size_t i = 1; i <= ntri * 3; i += 3) fprintf(f, "f %zu %zu %zu\n", i, i + 1, i + 2);
     if (fclose(f) != 0) fail(DR_ERR_IO, "SaveMeshToFile: write to %s failed", filename);
+  }
+  // DRF_MESH_RESIDENT: the pool only (the default); DRF_MESH_MAP: the pool and the host store together
+  void set_mesh_scope(int scope) {
+    if (scope != DRF_MESH_RESIDENT && scope != DRF_MESH_MAP) fail(DR_ERR_ARG, "drf_set_mesh_scope: unknown scope %d", scope);
+    if (mesh_pending_) fail(DR_ERR_PROTOCOL, "drf_set_mesh_scope: an extraction is pending, call GetMeshSync first");
+    mesh_scope_ = scope;
+  }
+  // last extraction: blocks meshed (workgroups of each pass), host blocks uploaded (once per chunk that stages them), chunks
+  void mesh_stats(uint64_t out[3]) const {
+    if (!out) fail(DR_ERR_ARG, "drf_mesh_stats: null argument");
+    for (int i = 0; i < 3; ++i) out[i] = mesh_stats_[i];
   }
 
   // bench path: inputs already resident in HBM
@@ -1914,27 +1941,24 @@ class FusionEngine {
     if (f <= -2147483648.0f) return -2147483647 - 1;
     return (int)f;
   }
-  // Enqueue the whole extraction on int_stream_ (after the last integration, before the next one).
-  void launch_mesh(const float *lower, const float *upper) {
-    DR_HIP(hipSetDevice(device_));
-    DR_HIP(hipStreamSynchronize(int_stream_));  // the block count lives on the device
-    int na = 0;
-    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
-    const int nblk = std::min(na, o_.num_blocks);
+  // Lattice cells per axis (ExtractMeshKernel, mesh_extractor.cu:241-245); returns the axis table length.
+  size_t mesh_lattice(const float *lower, const float *upper, int n[3]) {
     const float vs = o_.voxel_size;
-    int n[3];
     size_t ntab = 0;
-    for (int a = 0; a < 3; ++a) {  // ExtractMeshKernel, mesh_extractor.cu:241-245
+    for (int a = 0; a < 3; ++a) {
       n[a] = f2i_host(fabsf(lower[a] - upper[a]) / vs);
       if (n[a] > (1 << 22)) fail(DR_ERR_ARG, "ExtractMesh: %d lattice cells along axis %d (box too large for voxel_size %g)", n[a], a, vs);
       ntab += (size_t)std::max(n[a], 0);
     }
     if (!mesh_total_) mesh_total_ = dalloc<unsigned long long>(1);
-    if (nblk <= 0 || n[0] <= 0 || n[1] <= 0 || n[2] <= 0) {
-      DR_HIP(hipMemsetAsync(mesh_total_, 0, 8, int_stream_));
-      DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
-      return;
-    }
+    return ntab;
+  }
+  void mesh_empty() {
+    DR_HIP(hipMemsetAsync(mesh_total_, 0, 8, int_stream_));
+    DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
+  }
+  // the axis tables, the per-block arrays and the 20 M-triangle output (allocated with the first extraction), then k_mc_axes
+  void mesh_prepare(const float *lower, const int n[3], size_t ntab, McArgs &a) {
     if (ntab > mesh_axis_cap_) {
       if (mesh_axis_) DR_HIP(hipFree(mesh_axis_));
       mesh_axis_ = dalloc<McAxis>(ntab);
@@ -1953,17 +1977,39 @@ class FusionEngine {
       mesh_vert_ = dalloc<float>((size_t)kMeshMaxTriangles * 9);
       mesh_cols_ = dalloc<float>((size_t)kMeshMaxTriangles * 9);
     }
-    McArgs a{};
     McAxis *p = mesh_axis_;
     for (int k = 0; k < 3; ++k) {
-      hipLaunchKernelGGL(k_mc_axes, dim3(cdiv(n[k], 256)), dim3(256), 0, int_stream_, p, n[k], lower[k], vs);
+      hipLaunchKernelGGL(k_mc_axes, dim3(cdiv(n[k], 256)), dim3(256), 0, int_stream_, p, n[k], lower[k], o_.voxel_size);
       a.ax[k] = p; a.n[k] = n[k];
       p += n[k];
     }
+    a.counts = mesh_counts_; a.offsets = mesh_offsets_;
+    a.vert = mesh_vert_; a.cols = mesh_cols_; a.cap_tri = kMeshMaxTriangles;
+  }
+  // DRF_MESH_MAP folds pending evictions first; with an empty host store it is the resident pass
+  void launch_extraction(const float *lower, const float *upper) {
+    if (mesh_scope_ == DRF_MESH_MAP) {
+      settle();
+      if (!store_.empty()) return launch_mesh_map(lower, upper);
+    }
+    launch_mesh(lower, upper);
+  }
+  // Enqueue the whole extraction on int_stream_ (after the last integration, before the next one).
+  void launch_mesh(const float *lower, const float *upper) {
+    DR_HIP(hipSetDevice(device_));
+    DR_HIP(hipStreamSynchronize(int_stream_));  // the block count lives on the device
+    int na = 0;
+    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
+    const int nblk = std::min(na, o_.num_blocks);
+    int n[3];
+    const size_t ntab = mesh_lattice(lower, upper, n);
+    mesh_stats_[0] = mesh_stats_[1] = mesh_stats_[2] = 0;
+    if (nblk <= 0 || n[0] <= 0 || n[1] <= 0 || n[2] <= 0) return mesh_empty();
+    McArgs a{};
+    mesh_prepare(lower, n, ntab, a);
     size_t tb = mesh_tmp_bytes_;
     DR_HIP(rocprim::radix_sort_keys(mesh_tmp_, tb, d_.blk_key, mesh_keys_, (size_t)nblk, 0, 63, int_stream_));
-    a.sorted_keys = mesh_keys_; a.nblk = nblk; a.counts = mesh_counts_; a.offsets = mesh_offsets_;
-    a.vert = mesh_vert_; a.cols = mesh_cols_; a.cap_tri = kMeshMaxTriangles;
+    a.sorted_keys = mesh_keys_; a.nblk = nblk;
     hipLaunchKernelGGL((k_mc_cells<false>), dim3(nblk), dim3(256), 0, int_stream_, d_, a);
     tb = mesh_tmp_bytes_;
     DR_HIP(rocprim::exclusive_scan(mesh_tmp_, tb, mesh_counts_, mesh_offsets_, 0u, (size_t)nblk, rocprim::plus<unsigned>(), int_stream_));
@@ -1971,6 +2017,132 @@ class FusionEngine {
     hipLaunchKernelGGL(k_mc_total, dim3(1), dim3(1), 0, int_stream_, mesh_counts_, mesh_offsets_, nblk, mesh_total_);
     DR_HIP(hipGetLastError());
     DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
+    mesh_stats_[0] = (uint64_t)nblk; mesh_stats_[2] = 1;
+  }
+  // ---- the map pass (DRF_MESH_MAP with blocks in the host store; DESIGN.md §7c "Meshing the whole map") ----
+  // Global order = ascending key over resident and stored blocks, as the resident pass orders the pool.  The merged list is cut
+  // into chunks; a chunk stages its own stored blocks and every stored block among the 26 neighbours of its blocks (at most
+  // ms_stage_cap() of them), packed with the chunk's keys into pinned memory and copied to one of two device buffers on a copy
+  // stream, so that packing and copying chunk k + 1 overlap the kernels of chunk k.  Per chunk: count pass, scan, emit pass at
+  // the running base (mesh_total_), advance.  Neither the pool nor the host store changes.
+  int ms_own_cap() const { return std::min(o_.num_blocks, kStageBlocks); }
+  int ms_stage_cap() const { return std::max(ms_own_cap(), 27); }  // one block's 27 neighbours always fit
+  void ensure_mesh_staging() {
+    if (ms_dev_[0]) return;
+    ms_bytes_ = (size_t)ms_own_cap() * 8 + (size_t)ms_stage_cap() * (8 + 4096);
+    DR_HIP(hipStreamCreateWithFlags(&ms_copy_stream_, hipStreamNonBlocking));
+    for (int b = 0; b < 2; ++b) {
+      ms_dev_[b] = dalloc<unsigned char>(ms_bytes_);
+      DR_HIP(hipHostMalloc((void **)&ms_host_[b], ms_bytes_, hipHostMallocDefault));
+      DR_HIP(hipEventCreateWithFlags(&ms_copied_[b], hipEventDisableTiming));
+      DR_HIP(hipEventCreateWithFlags(&ms_used_[b], hipEventDisableTiming));
+      DR_HIP(hipEventRecord(ms_copied_[b], ms_copy_stream_));
+      DR_HIP(hipEventRecord(ms_used_[b], int_stream_));
+    }
+  }
+  void launch_mesh_map(const float *lower, const float *upper) {
+    int na = 0;
+    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
+    const int nblk = std::min(na, o_.num_blocks);
+    int n[3];
+    const size_t ntab = mesh_lattice(lower, upper, n);
+    mesh_stats_[0] = mesh_stats_[1] = mesh_stats_[2] = 0;
+    if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) return mesh_empty();
+    McArgs a{};
+    mesh_prepare(lower, n, ntab, a);
+    std::vector<unsigned long long> res(nblk), sto;
+    if (nblk > 0) {
+      size_t tb = mesh_tmp_bytes_;
+      DR_HIP(rocprim::radix_sort_keys(mesh_tmp_, tb, d_.blk_key, mesh_keys_, (size_t)nblk, 0, 63, int_stream_));
+      DR_HIP(hipMemcpyAsync(res.data(), mesh_keys_, (size_t)nblk * 8, hipMemcpyDeviceToHost, int_stream_));
+    }
+    sto.reserve(store_.size());
+    store_.for_each([&](unsigned long long k, const uint8_t *) { sto.push_back(k); });
+    std::sort(sto.begin(), sto.end());
+    // blocks that can own cells of the lattice: floor(mc / 8) between those of the first and last cell per axis (k_mc_axes'
+    // expression restated on the host), widened by one block -- the kernel finds the exact range, this only skips the rest
+    int blo[3], bhi[3];
+    for (int k = 0; k < 3; ++k) {
+      int m[2];
+      for (int e = 0; e < 2; ++e) {
+        const float pa = (float)(e ? n[k] - 1 : 0) * o_.voxel_size + lower[k];
+        m[e] = f2i_host(pa / o_.voxel_size + (float)((pa > 0) - (pa < 0)) * 0.5f);
+      }
+      auto fdiv = [](int v) { return v < 0 ? (v - kBS + 1) / kBS : v / kBS; };
+      blo[k] = fdiv(std::min(m[0], m[1])) - 1;
+      bhi[k] = fdiv(std::max(m[0], m[1])) + 1;
+    }
+    auto in_range = [&](unsigned long long key) {
+      int c[3]; unpack_key_host(key, c);
+      return c[0] >= blo[0] && c[0] <= bhi[0] && c[1] >= blo[1] && c[1] <= bhi[1] && c[2] >= blo[2] && c[2] <= bhi[2];
+    };
+    DR_HIP(hipStreamSynchronize(int_stream_));
+    // plan: own[] = the chunks' blocks in global order, stg[] = each chunk's staged keys (ascending), chunk c = own[ob[c], ob[c+1]),
+    // stg[sb[c], sb[c+1])
+    const size_t own_cap = (size_t)ms_own_cap(), stage_cap = (size_t)ms_stage_cap();
+    std::vector<unsigned long long> own, stg, cur;
+    std::vector<size_t> ob{0}, sb{0};
+    std::unordered_set<unsigned long long> in_cur;
+    auto close_chunk = [&]() {
+      std::sort(cur.begin(), cur.end());
+      stg.insert(stg.end(), cur.begin(), cur.end());
+      ob.push_back(own.size()); sb.push_back(stg.size());
+      cur.clear(); in_cur.clear();
+    };
+    size_t i = 0, j = 0;
+    unsigned long long need[27];
+    while (i < res.size() || j < sto.size()) {
+      const bool stored = j < sto.size() && (i >= res.size() || sto[j] < res[i]);
+      const unsigned long long key = stored ? sto[j++] : res[i++];
+      if (!in_range(key)) continue;
+      int c[3]; unpack_key_host(key, c);
+      int nn = 0, fresh = 0;  // stored blocks this block reads / those not staged for the chunk yet
+      for (int k = 0; k < 27; ++k) {
+        const int q[3] = {c[0] + k / 9 - 1, c[1] + (k / 3) % 3 - 1, c[2] + k % 3 - 1};
+        unsigned long long qk;
+        if (k == 13 ? stored : (pack_key_host(q, qk) && store_.contains(qk))) {
+          need[nn++] = k == 13 ? key : qk;
+          fresh += !in_cur.count(need[nn - 1]);
+        }
+      }
+      if (own.size() - ob.back() == own_cap || cur.size() + fresh > stage_cap) {
+        close_chunk();
+      }
+      own.push_back(key);
+      for (int k = 0; k < nn; ++k)
+        if (in_cur.insert(need[k]).second) cur.push_back(need[k]);
+    }
+    if (own.size() > ob.back()) close_chunk();
+    const int nchunk = (int)ob.size() - 1;
+    DR_HIP(hipMemsetAsync(mesh_total_, 0, 8, int_stream_));
+    if (nchunk > 0) ensure_mesh_staging();
+    for (int ch = 0; ch < nchunk; ++ch) {
+      const int b = ch & 1;
+      const size_t no = ob[ch + 1] - ob[ch], ns = sb[ch + 1] - sb[ch];
+      DR_HIP(hipEventSynchronize(ms_copied_[b]));  // the copy of chunk ch - 2 has left this pinned buffer
+      unsigned char *h = ms_host_[b];
+      memcpy(h, own.data() + ob[ch], no * 8);
+      memcpy(h + no * 8, stg.data() + sb[ch], ns * 8);
+      unsigned char *hv = h + (no + ns) * 8;
+      for (size_t k = 0; k < ns; ++k) memcpy(hv + k * 4096, store_.get(stg[sb[ch] + k]), 4096);
+      DR_HIP(hipStreamWaitEvent(ms_copy_stream_, ms_used_[b], 0));  // the kernels of chunk ch - 2 have read this device buffer
+      DR_HIP(hipMemcpyAsync(ms_dev_[b], h, (no + ns) * 8 + ns * 4096, hipMemcpyHostToDevice, ms_copy_stream_));
+      DR_HIP(hipEventRecord(ms_copied_[b], ms_copy_stream_));
+      DR_HIP(hipStreamWaitEvent(int_stream_, ms_copied_[b], 0));
+      const unsigned long long *dk = (const unsigned long long *)ms_dev_[b];
+      a.sorted_keys = dk; a.nblk = (int)no;
+      a.st_keys = dk + no; a.st_n = (int)ns; a.st_vox = (const Voxel *)(dk + no + ns);
+      a.base = mesh_total_;
+      hipLaunchKernelGGL((k_mc_cells<false, true>), dim3((unsigned)no), dim3(256), 0, int_stream_, d_, a);
+      size_t tb = mesh_tmp_bytes_;
+      DR_HIP(rocprim::exclusive_scan(mesh_tmp_, tb, mesh_counts_, mesh_offsets_, 0u, no, rocprim::plus<unsigned>(), int_stream_));
+      hipLaunchKernelGGL((k_mc_cells<true, true>), dim3((unsigned)no), dim3(256), 0, int_stream_, d_, a);
+      hipLaunchKernelGGL(k_mc_advance, dim3(1), dim3(1), 0, int_stream_, mesh_counts_, mesh_offsets_, (int)no, mesh_total_);
+      DR_HIP(hipEventRecord(ms_used_[b], int_stream_));
+    }
+    DR_HIP(hipGetLastError());
+    DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
+    mesh_stats_[0] = own.size(); mesh_stats_[1] = stg.size(); mesh_stats_[2] = (uint64_t)nchunk;
   }
   hipEvent_t mesh_done_ev() {
     if (!mesh_done_) DR_HIP(hipEventCreateWithFlags(&mesh_done_, hipEventDisableTiming));
@@ -2053,6 +2225,14 @@ class FusionEngine {
   unsigned *mesh_counts_ = nullptr, *mesh_offsets_ = nullptr;
   unsigned char *mesh_tmp_ = nullptr;
   float *mesh_vert_ = nullptr, *mesh_cols_ = nullptr;
+  int mesh_scope_ = DRF_MESH_RESIDENT;
+  uint64_t mesh_stats_[3] = {0, 0, 0};
+  // map pass staging (allocated with the first map-scope extraction that meets a non-empty host store): two pinned / device
+  // buffer pairs of ms_bytes_ = own keys + staged keys + staged voxels, a copy stream and the events that order the reuse
+  size_t ms_bytes_ = 0;
+  unsigned char *ms_dev_[2] = {nullptr, nullptr}, *ms_host_[2] = {nullptr, nullptr};
+  hipEvent_t ms_copied_[2] = {nullptr, nullptr}, ms_used_[2] = {nullptr, nullptr};
+  hipStream_t ms_copy_stream_ = nullptr;
   // streaming state (staging allocated with the first drf_set_streaming / region call)
   float st_radius_ = 0.0f;                  // 0 = off
   size_t st_host_cap_ = (size_t)-1;         // host store capacity in blocks
@@ -2184,5 +2364,7 @@ int drf_streaming_stats(drf_t *h, uint64_t out[6]) {
 int drf_export_host_blocks(drf_t *h, int max_blocks, int32_t *coords, uint8_t *voxels, int *n) {
   return guarded([&] { eng(h)->export_host_blocks(max_blocks, coords, voxels, n); });
 }
+int drf_set_mesh_scope(drf_t *h, int scope) { return guarded([&] { eng(h)->set_mesh_scope(scope); }); }
+int drf_mesh_stats(drf_t *h, uint64_t out[3]) { return guarded([&] { eng(h)->mesh_stats(out); }); }
 
 }  // extern "C"

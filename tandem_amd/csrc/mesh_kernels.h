@@ -35,6 +35,12 @@ struct McArgs {
   const unsigned *offsets;   // [nblk] exclusive scan of counts (emit pass)
   float *vert, *cols;        // [cap_tri * 9]
   unsigned cap_tri;
+  // staged form only (k_mc_cells<EMIT, true>, one chunk of the map pass; DESIGN.md §7c "Meshing the whole map"):
+  // sorted_keys / nblk are the chunk's blocks, resident or stored; the host blocks they read are staged here
+  const unsigned long long *st_keys;  // [st_n] ascending keys of the host blocks staged for this chunk
+  const Voxel *st_vox;                // [st_n * 512] their voxels
+  int st_n;
+  const unsigned long long *base;     // triangles emitted by the chunks before this one (the chunk's first output row)
 };
 
 __global__ void k_mc_axes(McAxis *out, int n, float lo, float vs) {
@@ -66,6 +72,27 @@ __device__ inline Voxel voxel_at(const FusionDev &d, int vx, int vy, int vz) {  
   return d.vox[(size_t)p * 512 + pos_mod(vx, kBS) * 64 + pos_mod(vy, kBS) * 8 + pos_mod(vz, kBS)];
 }
 
+// Staged form: index of block p among the chunk's staged host blocks (binary search of the ascending keys), -1 if absent.
+__device__ inline int staged_block(const McArgs &a, I3 p) {
+  unsigned long long key;
+  if (!pack_key(p, key)) return -1;
+  int lo = 0, hi = a.st_n;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.st_keys[mid] < key) lo = mid + 1; else hi = mid; }
+  return lo < a.st_n && a.st_keys[lo] == key ? lo : -1;
+}
+// voxel_at through both levels: the pool first, then the staged host blocks.  The fallback samples it serves lie in the
+// 27 blocks around the cell's block, and the chunk stages every stored block among those.
+__device__ inline Voxel voxel_at_staged(const FusionDev &d, const McArgs &a, int vx, int vy, int vz) {
+  Voxel z; z.sdf = 0.f; z.c[0] = z.c[1] = z.c[2] = 0; z.weight = 0;
+  I3 b; b.x = floor_div(vx, kBS); b.y = floor_div(vy, kBS); b.z = floor_div(vz, kBS);
+  const int off = pos_mod(vx, kBS) * 64 + pos_mod(vy, kBS) * 8 + pos_mod(vz, kBS);
+  const int p = find_block(d, b);
+  if (p >= 0) return d.vox[(size_t)p * 512 + off];
+  const int s = staged_block(a, b);
+  if (s >= 0) return a.st_vox[(size_t)s * 512 + off];
+  return z;
+}
+
 // VertexInterpolation, mesh_extractor.cu:105-134 (isolevel 0, both colours = the cell's centre voxel)
 __device__ inline F3 mc_vertex_pos(F3 p1, F3 p2, float d1, float d2) {
   if (fabsf(0.0f - d1) < 0.00001f) return p1;
@@ -79,7 +106,10 @@ __device__ inline F3 mc_vertex_pos(F3 p1, F3 p2, float d1, float d2) {
   return r;
 }
 
-template <bool EMIT>
+// STAGED = false: the resident blocks (sorted_keys = every pool block).  STAGED = true: one chunk of the map pass -- a
+// neighbour that is not in the pool resolves among the chunk's staged host blocks (nbptr = -2 - staged index), and the
+// emit pass writes behind the triangles of the earlier chunks (*a.base).
+template <bool EMIT, bool STAGED = false>
 __global__ __launch_bounds__(256) void k_mc_cells(const FusionDev d, const McArgs a) {
   __shared__ Voxel nb[1000];   // voxels [8B-1, 8B+8]^3 of this block's neighbourhood, index (lx*10 + ly)*10 + lz
   __shared__ int nbptr[27];
@@ -103,13 +133,17 @@ __global__ __launch_bounds__(256) void k_mc_cells(const FusionDev d, const McArg
   if (tid >= 64 && tid < 64 + 27) {
     const int k = tid - 64;
     I3 q; q.x = B.x + k / 9 - 1; q.y = B.y + (k / 3) % 3 - 1; q.z = B.z + k % 3 - 1;
-    nbptr[k] = find_block(d, q);
+    int p = find_block(d, q);
+    if constexpr (STAGED) {
+      if (p < 0) { const int st = staged_block(a, q); p = st >= 0 ? -2 - st : -1; }
+    }
+    nbptr[k] = p;
   }
   if (tid == 0) run_base = 0;
   __syncthreads();
   const int gx0 = rng[0][0], gy0 = rng[1][0], gz0 = rng[2][0];
   const int rx = rng[0][1] - gx0, ry = rng[1][1] - gy0, rz = rng[2][1] - gz0;
-  if (rx <= 0 || ry <= 0 || rz <= 0 || nbptr[13] < 0) {
+  if (rx <= 0 || ry <= 0 || rz <= 0 || (STAGED ? nbptr[13] == -1 : nbptr[13] < 0)) {
     if (!EMIT && tid == 0) a.counts[bi] = 0;
     return;
   }
@@ -118,6 +152,7 @@ __global__ __launch_bounds__(256) void k_mc_cells(const FusionDev d, const McArg
     const int p = nbptr[((lx + 7) >> 3) * 9 + ((ly + 7) >> 3) * 3 + ((lz + 7) >> 3)];
     Voxel v; v.sdf = 0.f; v.c[0] = v.c[1] = v.c[2] = 0; v.weight = 0;
     if (p >= 0) v = d.vox[(size_t)p * 512 + ((lx + 7) & 7) * 64 + ((ly + 7) & 7) * 8 + ((lz + 7) & 7)];
+    else if (STAGED && p != -1) v = a.st_vox[(size_t)(-2 - p) * 512 + ((lx + 7) & 7) * 64 + ((ly + 7) & 7) * 8 + ((lz + 7) & 7)];
     nb[i] = v;
   }
   __syncthreads();
@@ -125,7 +160,9 @@ __global__ __launch_bounds__(256) void k_mc_cells(const FusionDev d, const McArg
   auto fetch = [&](int vx, int vy, int vz) -> Voxel {
     const unsigned lx = (unsigned)(vx - ox), ly = (unsigned)(vy - oy), lz = (unsigned)(vz - oz);
     if (lx < 10u && ly < 10u && lz < 10u) return nb[(lx * 10 + ly) * 10 + lz];
-    return voxel_at(d, vx, vy, vz);  // only if float rounding pushes a sample outside the +-1 neighbourhood
+    // only if float rounding pushes a sample outside the +-1 neighbourhood
+    if constexpr (STAGED) return voxel_at_staged(d, a, vx, vy, vz);
+    else return voxel_at(d, vx, vy, vz);
   };
   const int ncell = rx * ry * rz;
   unsigned my_total = 0;
@@ -184,6 +221,10 @@ __global__ __launch_bounds__(256) void k_mc_cells(const FusionDev d, const McArg
     for (int w = 0; w < wave; ++w) before += wsum[w];
     const unsigned round_total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     unsigned t_out = a.offsets[bi] + before + incl - ntri;
+    if constexpr (STAGED) {  // past the cap every store is skipped, as in the resident form
+      const unsigned long long t = *a.base + t_out;
+      t_out = t < a.cap_tri ? (unsigned)t : a.cap_tri;
+    }
     for (int i = 0; i < 15 && ((row >> (4 * i)) & 15) != 15; i += 3, ++t_out) {
       if (t_out >= a.cap_tri) break;
       float *vv = a.vert + (size_t)t_out * 9, *cc = a.cols + (size_t)t_out * 9;
@@ -216,6 +257,10 @@ __global__ __launch_bounds__(256) void k_mc_cells(const FusionDev d, const McArg
 
 __global__ void k_mc_total(const unsigned *counts, const unsigned *offsets, int nblk, unsigned long long *total) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *total = nblk > 0 ? (unsigned long long)offsets[nblk - 1] + counts[nblk - 1] : 0ull;
+}
+// map pass: the chunk's triangles move the running base of the next chunk (mesh_total_ once the last chunk is done)
+__global__ void k_mc_advance(const unsigned *counts, const unsigned *offsets, int nblk, unsigned long long *total) {
+  if (threadIdx.x == 0 && blockIdx.x == 0 && nblk > 0) *total += (unsigned long long)offsets[nblk - 1] + counts[nblk - 1];
 }
 
 }  // namespace dr

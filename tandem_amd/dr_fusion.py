@@ -18,6 +18,10 @@ def DrFusionOptions(**kw):
     return FusionOptions(**d)
 
 
+# drf_set_mesh_scope: what the mesh calls cover (include/dr_mi355x.h)
+MESH_RESIDENT, MESH_MAP = 0, 1
+
+
 def streaming_min_radius(options):
     """drf_streaming_min_radius: the smallest exact streaming radius for these options (host-only)."""
     r = C.c_float()
@@ -191,6 +195,16 @@ class DrFusion:
         got = C.c_int()
         check(self._L.drf_export_host_blocks(self._h, n, coords.ctypes.data_as(C.POINTER(C.c_int32)), vox.ctypes.data_as(u8p), C.byref(got)))
         return {tuple(int(v) for v in coords[i]): vox[i] for i in range(got.value)}
+
+    def set_mesh_scope(self, scope):
+        """MESH_RESIDENT (default): meshes cover the pool; MESH_MAP: the pool and the host store, without moving a block."""
+        check(self._L.drf_set_mesh_scope(self._h, int(scope)))
+
+    def mesh_stats(self):
+        """Last extraction: (blocks meshed, host blocks uploaded -- once per chunk that stages them, chunks)."""
+        out = (C.c_uint64 * 3)()
+        check(self._L.drf_mesh_stats(self._h, out))
+        return tuple(int(v) for v in out)
 
     def export_all_blocks(self):
         """The whole map: resident blocks and the host store merged (a block is in exactly one of them)."""

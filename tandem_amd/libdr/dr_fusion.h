@@ -87,6 +87,8 @@ public:
   void SetStreaming(float radius, size_t host_capacity_blocks) { check(drf_set_streaming(impl, radius, host_capacity_blocks)); }
   void StreamOutRegion(float lower_corner[3], float upper_corner[3]) { check(drf_stream_out_region(impl, lower_corner, upper_corner)); }
   void StreamInRegion(float lower_corner[3], float upper_corner[3]) { check(drf_stream_in_region(impl, lower_corner, upper_corner)); }
+  // DRF_MESH_MAP: SaveMeshToFile / ExtractMeshAsync / GetMeshSync / GetMesh cover the host store too (DRF_MESH_RESIDENT: the pool only)
+  void SetMeshScope(int scope) { check(drf_set_mesh_scope(impl, scope)); }
 
   size_t dr_mesh_num = 0;
   const size_t dr_mesh_num_max = 60000000;
