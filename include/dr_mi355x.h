@@ -297,6 +297,47 @@ int drf_set_mesh_scope(drf_t *h, int scope);
  * times), [2] chunks (1 for a resident pass over a non-empty pool). */
 int drf_mesh_stats(drf_t *h, uint64_t out[3]);
 
+/* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
+ * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").
+ * The engine keeps a BASELINE: the box of the last update that was fetched and the scans integrated since that update was
+ * launched.  An update over [lower, upper] returns PATCHES in ascending packed-key order (x, then y, then z, each biased by
+ * 2^20: the block order of a full extraction): a block's coordinates and its triangles, exactly the rows drf_extract_mesh_async
+ * + drf_get_mesh_sync over the same box emit for that block, in the same order.  A block is listed whenever its triangles MAY
+ * differ from what the earlier updates of this baseline described (listed with zero triangles: it has none now); a block that
+ * is not listed has not changed.  A consumer that keeps {block -> rows}, replaces the entry of every listed block and
+ * concatenates its entries in ascending key order holds, byte for byte, the full extraction over that box at that moment.
+ * An update is FULL -- every block of the scope is listed, the consumer starts from an empty store -- when it is the first,
+ * when its box differs from the baseline's (the six floats compared bitwise), after drf_mesh_update_reset, after more than
+ * DRF_MESH_UPDATE_MAX_SCANS scans since the previous update was launched (the drf_bench_* loops record their scans like
+ * drf_integrate_scan_async and drf_integrate_device do), after a scan whose pose is not a finite rigid motion, and after a scan
+ * that reported round-trip voxel mismatches (drf_stats [3]).  An update launched with no scan since the previous one lists
+ * nothing and launches no mesh kernel.
+ * Which blocks: block b is listed iff, for one of the 27 blocks around it and the pose of one recorded scan, the integration's
+ * visibility test holds (block origin in front of the camera, block centre projects into the image) and the block origin lies
+ * within max_sensor_depth * rho + truncation_distance + (15 sqrt(3) + 1) voxel_size of the camera centre (rho as in
+ * drf_streaming_min_radius): a superset of the blocks a scan can have written, widened by the neighbours a block's cells read.
+ * Protocol: legal where drf_extract_mesh_async is; one extraction of either kind may be pending, and launching while one is
+ * pending or fetching with the other kind's getter is DR_ERR_PROTOCOL with the state untouched.  drf_extract_mesh_async and
+ * drf_save_mesh never move the baseline.  The baseline advances when drf_get_mesh_update_sync succeeds; DR_ERR_CAPACITY
+ * (max_blocks or num_max too small, or above 20 M triangles) leaves the update pending and the baseline where it was.  Scans
+ * integrated after the launch belong to the next update.
+ * Scope follows drf_set_mesh_scope.  DRF_MESH_MAP: the patches describe resident and stored blocks together and equal an
+ * unbounded engine's.  DRF_MESH_RESIDENT while the host store holds blocks: the launch is DR_ERR_PROTOCOL -- the resident view
+ * changes by eviction alone, which an update does not track.  Like the map pass an update folds pending evictions first and is
+ * otherwise read-only: pool, slot order, host store, streaming state and the counters stay as they were. */
+#define DRF_MESH_UPDATE_MAX_SCANS 16
+int drf_extract_mesh_update_async(drf_t *h, const float lower[3], const float upper[3]);
+/* Size of the pending update (waits for it, does not consume it): listed blocks, triangles, full. */
+int drf_mesh_update_size(drf_t *h, size_t *nblk, size_t *ntri, int *full);
+/* coords: 3 per listed block (max_blocks blocks of room); first: max_blocks + 1 rows of room, block i owns triangles
+ * [first[i], first[i + 1]) of vert / cols (laid out as drf_get_mesh_sync's; num_max vertices of room); *num = 3 * triangles. */
+int drf_get_mesh_update_sync(drf_t *h, size_t max_blocks, size_t num_max, size_t *nblk, int32_t *coords, uint64_t *first, size_t *num,
+                             float *vert, float *cols, int *full);
+/* The next update is full. */
+int drf_mesh_update_reset(drf_t *h);
+/* Last update launched: [0] blocks in scope, [1] blocks meshed again (= listed), [2] scans folded in, [3] full. */
+int drf_mesh_update_stats(drf_t *h, uint64_t out[4]);
+
 /* ======================================================================================================
  * DrCoarseTracker -- the dense coarse tracker operator.  Replaces
  *   tandem/libdr/cuda_coarse_tracker/include/public/cuda_coarse_tracker.h   (class CudaCoarseTracker)

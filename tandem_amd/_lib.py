@@ -118,6 +118,12 @@ SIGNATURES = {
     "drf_export_host_blocks": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int)]),
     "drf_set_mesh_scope": (C.c_int, [vp, C.c_int]),
     "drf_mesh_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_extract_mesh_update_async": (C.c_int, [vp, f32p, f32p]),
+    "drf_mesh_update_size": (C.c_int, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "drf_get_mesh_update_sync": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32), C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_size_t), f32p, f32p, C.POINTER(C.c_int)]),
+    "drf_mesh_update_reset": (C.c_int, [vp]),
+    "drf_mesh_update_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
 
 

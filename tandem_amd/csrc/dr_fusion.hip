@@ -24,6 +24,7 @@
 // fp32 arithmetic is written in the reference's expression order and compiled with -ffp-contract=off;
 // divisions and square roots are IEEE-correct (hipcc default -fhip-fp32-correctly-rounded-divide-sqrt).
 #include <cfloat>
+#include <climits>
 #include <cstdio>
 #include <cstring>
 #include <chrono>
@@ -429,10 +430,24 @@ __global__ void k_test_combine(const Voxel *__restrict__ a, const Voxel *__restr
 // projects into the image) for EVERY allocated block, one LANE per block; survivors go to the visible list (one
 // atomicAdd per wave).  The map keeps growing while the camera sees a room-sized part of it: with one wave per allocated
 // block this test was half of k_integrate's instructions at 110 k blocks and would dominate at a million.
-__global__ __launch_bounds__(256) void k_cull(const FusionDev d, const Mat Ti) {
-  const drf_options_t &o = d.o;
+// The test itself, a pure function of (block coordinates, Ti, options): shared with the mesh update's selection kernel
+// (mesh_update_kernels.h), which must agree with the visible list to the last bit.  pc = the block origin in the camera frame.
+__device__ inline bool cull_block_visible(const drf_options_t &o, const I3 P, const Mat &Ti, F3 &pc) {
   constexpr int bs = kBS;
   const float vs = o.voxel_size;
+  F3 position; position.x = P.x * vs * bs; position.y = P.y * vs * bs; position.z = P.z * vs * bs;
+  pc = xform(Ti, position);
+  if (pc.z < 0) return false;
+  F3 center;  // tsdf_volume.cu:461-465 -- the half-block offset is added in double
+  center.x = (float)((double)pc.x + 0.5 * (double)vs * (double)bs);
+  center.y = (float)((double)pc.y + 0.5 * (double)vs * (double)bs);
+  center.z = (float)((double)pc.z + 0.5 * (double)vs * (double)bs);
+  int cx, cy;
+  project(o, center, cx, cy);
+  return cx >= 0 && cy >= 0 && cx < o.width && cy < o.height;
+}
+__global__ __launch_bounds__(256) void k_cull(const FusionDev d, const Mat Ti) {
+  const drf_options_t &o = d.o;
   const int lane = threadIdx.x & 63;
   const int n_blocks = min(*d.n_alloc, o.num_blocks);  // written by k_alloc_commit earlier on this stream
   __shared__ int wcount[4], wbase;
@@ -440,18 +455,8 @@ __global__ __launch_bounds__(256) void k_cull(const FusionDev d, const Mat Ti) {
     const int e = e0 + lane;
     bool vis = false;
     if (e < n_blocks) {
-      const I3 P = unpack_key(d.blk_key[e]);
-      F3 position; position.x = P.x * vs * bs; position.y = P.y * vs * bs; position.z = P.z * vs * bs;
-      const F3 pc = xform(Ti, position);
-      if (!(pc.z < 0)) {
-        F3 center;  // tsdf_volume.cu:461-465 -- the half-block offset is added in double
-        center.x = (float)((double)pc.x + 0.5 * (double)vs * (double)bs);
-        center.y = (float)((double)pc.y + 0.5 * (double)vs * (double)bs);
-        center.z = (float)((double)pc.z + 0.5 * (double)vs * (double)bs);
-        int cx, cy;
-        project(o, center, cx, cy);
-        vis = cx >= 0 && cy >= 0 && cx < o.width && cy < o.height;
-      }
+      F3 pc;
+      vis = cull_block_visible(o, unpack_key(d.blk_key[e]), Ti, pc);
     }
     // one atomicAdd per WORKGROUP and iteration (a single address takes ~10^8 atomics/s: one per wave was measurable)
     const unsigned long long m = __ballot(vis);
@@ -1065,6 +1070,7 @@ __global__ void k_fill_keys(unsigned long long *keys, size_t n) {
 
 }  // namespace dr
 #include "mesh_kernels.h"
+#include "mesh_update_kernels.h"
 namespace dr {
 
 // cofactor inverse on the host in the reference's term order (matrix_utils.h:958-1083), fp32, no contraction
@@ -1116,14 +1122,18 @@ __global__ __launch_bounds__(256) void k_publish(const unsigned char *__restrict
 //   ray-cast        depth*rho + 4.5*sqrt(3)*vs            (samples at cur < max_sensor_depth, trilinear corners within sqrt(3) vs)
 // plus one block diagonal (8 sqrt(3) vs) and one voxel of margin.  rho = the largest |((u - cx)/fx, (v - cy)/fy, 1)| over
 // the image corners.  Evaluated in double.
-static double stream_reach(const drf_options_t &o, double depth) {
-  const double s3 = std::sqrt(3.0), vs = o.voxel_size;
+static double corner_rho(const drf_options_t &o) {
   double rho = 0.0;
   for (int k = 0; k < 4; ++k) {
     const double u = (k & 1) ? o.width - 1 : 0, v = (k & 2) ? o.height - 1 : 0;
     const double a = (u - o.cx) / o.fx, b = (v - o.cy) / o.fy;
     rho = std::max(rho, std::sqrt(a * a + b * b + 1.0));
   }
+  return rho;
+}
+static double stream_reach(const drf_options_t &o, double depth) {
+  const double s3 = std::sqrt(3.0), vs = o.voxel_size;
+  const double rho = corner_rho(o);
   const double scan = std::max(depth * rho + (double)o.truncation_distance + 4.5 * s3 * vs, 12.5 * s3 * vs);
   return scan + 8.0 * s3 * vs + vs;
 }
@@ -1133,6 +1143,16 @@ static bool stream_options_ok(const drf_options_t &o) {
          pos(o.max_sensor_depth) && std::isfinite(o.truncation_distance) && o.truncation_distance >= 0.0f;
 }
 static float streaming_min_radius(const drf_options_t &o) { return (float)stream_reach(o, o.max_sensor_depth); }
+// Mesh update: farthest a block ORIGIN can lie from the camera centre of a scan that writes one of its voxels (DESIGN.md
+// "Incremental mesh"): the "voxel update" term above taken at the origin (voxels lie within 7 sqrt(3) vs of it) plus the same
+// block diagonal and voxel of margin.  Options the bound is not defined for leave k_cull's test alone in charge.
+static float mesh_update_reach2(const drf_options_t &o) {
+  if (!stream_options_ok(o)) return INFINITY;
+  const double s3 = std::sqrt(3.0), vs = o.voxel_size;
+  const double r = (double)o.max_sensor_depth * corner_rho(o) + (double)o.truncation_distance + 7.0 * s3 * vs + 8.0 * s3 * vs + vs;
+  const float r2 = (float)(r * r * (1.0 + 1e-5));
+  return std::isfinite(r2) ? r2 : INFINITY;
+}
 
 static inline void unpack_key_host(unsigned long long k, int c[3]) {
   const int B = 1 << 20;
@@ -1332,6 +1352,8 @@ class FusionEngine {
     (void)hipFree(mesh_axis_); (void)hipFree(mesh_keys_); (void)hipFree(mesh_total_); (void)hipFree(mesh_counts_);
     (void)hipFree(mesh_offsets_); (void)hipFree(mesh_tmp_); (void)hipFree(mesh_vert_); (void)hipFree(mesh_cols_);
     if (mesh_done_) (void)hipEventDestroy(mesh_done_);
+    (void)hipFree(mu_flags_); (void)hipFree(mu_pos_); (void)hipFree(mu_sel_); (void)hipFree(mu_scope_); (void)hipFree(mu_first_);
+    (void)hipFree(mu_nsel_); (void)hipFree(mu_coords_);
     for (int b = 0; b < 2; ++b) {
       (void)hipFree(ms_dev_[b]); (void)hipHostFree(ms_host_[b]);
       if (ms_copied_[b]) (void)hipEventDestroy(ms_copied_[b]);
@@ -1518,6 +1540,7 @@ class FusionEngine {
   }
   size_t mesh_num_triangles() {  // blocks until the pending extraction is done; does not consume it
     if (!mesh_pending_) fail(DR_ERR_PROTOCOL, "mesh_extractor should not be NULL (did you call ExtractMeshAsync before)?");
+    if (mesh_pending_update_) fail(DR_ERR_PROTOCOL, "GetMeshSync: the pending extraction is a mesh update, fetch it with drf_get_mesh_update_sync");
     return finish_mesh();
   }
   // vert / cols hold num_max vertices (3 floats each).  The reference compares num_max with the TRIANGLE count
@@ -1559,6 +1582,61 @@ class FusionEngine {
   void mesh_stats(uint64_t out[3]) const {
     if (!out) fail(DR_ERR_ARG, "drf_mesh_stats: null argument");
     for (int i = 0; i < 3; ++i) out[i] = mesh_stats_[i];
+  }
+  // ---- incremental mesh: an extraction that lists only the blocks whose triangles may have changed since the baseline
+  // (the last update fetched); no reference counterpart.  DESIGN.md §7c "Incremental mesh".
+  void extract_mesh_update_async(const float *lower, const float *upper) {
+    if (!lower || !upper) fail(DR_ERR_ARG, "drf_extract_mesh_update_async: null argument");
+    expect(kIntegrate, "Please call this functions after GetRenderResult.");
+    if (mesh_pending_) fail(DR_ERR_PROTOCOL, "drf_extract_mesh_update_async: an extraction is pending, fetch it first");
+    settle();  // in either scope: what the host store holds decides below
+    if (mesh_scope_ == DRF_MESH_RESIDENT && !store_.empty())
+      fail(DR_ERR_PROTOCOL, "drf_extract_mesh_update_async: %zu blocks are in the host store; the resident view changes by eviction, which an update does not track (use DRF_MESH_MAP)", store_.size());
+    unsigned long long redirects = 0;  // a round-trip mismatch writes a block that is not on the visible list (k_integrate)
+    DR_HIP(hipMemcpy(&redirects, d_.cnt + 2, 8, hipMemcpyDeviceToHost));
+    float box[6];
+    memcpy(box, lower, 12); memcpy(box + 3, upper, 12);
+    const bool full = !mu_valid_ || mu_force_full_ || mu_overflow_ || memcmp(box, mu_box_, 24) != 0 || redirects != mu_redirects_;
+    if (store_.empty()) launch_mesh_update(lower, upper, full);
+    else launch_mesh_map(lower, upper, true, full);
+    // launched: the scans recorded so far belong to this update, later ones to the next
+    memcpy(mu_l_box_, box, 24);
+    mu_l_full_ = full; mu_l_redirects_ = redirects;
+    mu_force_full_ = false; mu_overflow_ = false;
+    mu_poses_.clear();
+    mesh_pending_ = mesh_pending_update_ = true;
+  }
+  void mesh_update_size(size_t *nblk, size_t *ntri, int *full) {
+    if (!nblk || !ntri || !full) fail(DR_ERR_ARG, "drf_mesh_update_size: null argument");
+    if (!mesh_pending_ || !mesh_pending_update_) fail(DR_ERR_PROTOCOL, "drf_mesh_update_size: no mesh update is pending");
+    *ntri = finish_mesh(); *nblk = mu_l_nblk_; *full = mu_l_full_ ? 1 : 0;
+  }
+  void get_mesh_update_sync(size_t max_blocks, size_t num_max, size_t *nblk, int32_t *coords, uint64_t *first, size_t *num, float *vert,
+                            float *cols, int *full) {
+    if (!nblk || !coords || !first || !num || !vert || !cols || !full) fail(DR_ERR_ARG, "drf_get_mesh_update_sync: null argument");
+    if (!mesh_pending_ || !mesh_pending_update_) fail(DR_ERR_PROTOCOL, "drf_get_mesh_update_sync: no mesh update is pending");
+    const size_t ntri = finish_mesh(), nb = mu_l_nblk_;
+    if (max_blocks < nb) fail(DR_ERR_CAPACITY, "Did not provide enough storage for the patch table (%zu blocks > %zu).", nb, max_blocks);
+    if (num_max < 3 * ntri) fail(DR_ERR_CAPACITY, "Did not provide enough storage for mesh (%zu vertices > %zu).", 3 * ntri, num_max);
+    first[0] = 0;
+    if (nb > 0) {
+      DR_HIP(hipMemcpy(coords, mu_coords_, nb * 12, hipMemcpyDeviceToHost));
+      DR_HIP(hipMemcpy(first, mu_first_, (nb + 1) * 8, hipMemcpyDeviceToHost));
+      DR_HIP(hipMemcpy(vert, mesh_vert_, ntri * 36, hipMemcpyDeviceToHost));
+      DR_HIP(hipMemcpy(cols, mesh_cols_, ntri * 36, hipMemcpyDeviceToHost));
+    }
+    *nblk = nb; *num = 3 * ntri; *full = mu_l_full_ ? 1 : 0;
+    // the baseline advances: this box, the voxel state at the launch
+    memcpy(mu_box_, mu_l_box_, 24);
+    mu_redirects_ = mu_l_redirects_;
+    mu_valid_ = true;
+    mesh_pending_ = mesh_pending_update_ = false;
+  }
+  void mesh_update_reset() { mu_force_full_ = true; }
+  // last update launched: blocks in scope, blocks meshed again, scans folded in, full
+  void mesh_update_stats(uint64_t out[4]) const {
+    if (!out) fail(DR_ERR_ARG, "drf_mesh_update_stats: null argument");
+    for (int i = 0; i < 4; ++i) out[i] = mu_stats_[i];
   }
 
   // bench path: inputs already resident in HBM
@@ -1924,6 +2002,7 @@ class FusionEngine {
     Mat T, Ti;
     memcpy(T.m, pose16, 64);
     inverse4_host(T.m, Ti.m);
+    record_scan_pose(Ti);
     hipLaunchKernelGGL(k_allocate, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, d_, d_bgr, d_depth, T);
     hipLaunchKernelGGL(k_alloc_commit, dim3(64), dim3(256), 0, int_stream_, d_);
     hipLaunchKernelGGL(k_cull, dim3(512), dim3(256), 0, int_stream_, d_, Ti);
@@ -2019,6 +2098,99 @@ class FusionEngine {
     DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
     mesh_stats_[0] = (uint64_t)nblk; mesh_stats_[2] = 1;
   }
+  // ---- mesh update: selection and the resident form ----
+  // every entry point that integrates comes through enqueue_scan.  A pose that is not a finite rigid motion (the reach bound
+  // assumes one) or one scan too many makes the next update full.
+  void record_scan_pose(const Mat &Ti) {
+    bool rigid = true;
+    for (int i = 0; i < 3 && rigid; ++i)
+      for (int j = i; j < 3; ++j) {
+        const double dot = (double)Ti.m[4 * i] * Ti.m[4 * j] + (double)Ti.m[4 * i + 1] * Ti.m[4 * j + 1] + (double)Ti.m[4 * i + 2] * Ti.m[4 * j + 2];
+        if (!(std::fabs(dot - (i == j ? 1.0 : 0.0)) < 1e-3)) rigid = false;
+      }
+    for (int i = 0; i < 12; ++i) rigid = rigid && std::isfinite(Ti.m[i]);
+    if (!rigid || mu_poses_.size() == (size_t)DRF_MESH_UPDATE_MAX_SCANS) { mu_overflow_ = true; return; }
+    MuPose p;
+    memcpy(p.m, Ti.m, 48);
+    mu_poses_.push_back(p);
+  }
+  // scan scratch for n items (the mesh path's is sized for the pool; a map's scope may be longer)
+  void mesh_tmp_reserve(size_t n) {
+    size_t t = 0;
+    DR_HIP(rocprim::exclusive_scan(nullptr, t, mesh_counts_, mesh_offsets_, 0u, n, rocprim::plus<unsigned>(), int_stream_));
+    if (t <= mesh_tmp_bytes_) return;
+    DR_HIP(hipStreamSynchronize(int_stream_));
+    DR_HIP(hipFree(mesh_tmp_));
+    mesh_tmp_ = nullptr;
+    mesh_tmp_ = dalloc<unsigned char>(t);
+    mesh_tmp_bytes_ = t;
+  }
+  template <class T> void mu_grow(T *&p, size_t &cap, size_t n) {
+    if (n <= cap) return;
+    DR_HIP(hipStreamSynchronize(int_stream_));
+    if (p) DR_HIP(hipFree(p));
+    p = nullptr; cap = 0;
+    p = dalloc<T>(n);
+    cap = n;
+  }
+  // Blocks of keys[0, n) (device, ascending) to mesh again after the recorded scans, compacted in order into mu_sel_; returns
+  // their number (one 4-byte read back: the mesh kernels' grid).
+  int mu_select(const unsigned long long *keys, int n) {
+    mu_grow(mu_flags_, mu_flags_cap_, (size_t)n);
+    mu_grow(mu_pos_, mu_pos_cap_, (size_t)n);
+    mu_grow(mu_sel_, mu_sel_cap_, (size_t)n);
+    if (!mu_nsel_) mu_nsel_ = dalloc<int>(1);
+    mesh_tmp_reserve((size_t)n);
+    MuArgs m{};
+    m.keys = keys; m.n = n; m.nposes = (int)mu_poses_.size(); m.reach2 = mesh_update_reach2(o_); m.flags = mu_flags_;
+    memcpy(m.Ti, mu_poses_.data(), mu_poses_.size() * sizeof(MuPose));
+    hipLaunchKernelGGL(k_mu_select, dim3(cdiv(n, 256)), dim3(256), 0, int_stream_, o_, m);
+    size_t tb = mesh_tmp_bytes_;
+    DR_HIP(rocprim::exclusive_scan(mesh_tmp_, tb, mu_flags_, mu_pos_, 0u, (size_t)n, rocprim::plus<unsigned>(), int_stream_));
+    hipLaunchKernelGGL(k_mu_compact, dim3(cdiv(n, 256)), dim3(256), 0, int_stream_, keys, mu_flags_, mu_pos_, n, mu_sel_, mu_nsel_);
+    DR_HIP(hipGetLastError());
+    int nsel = 0;
+    DR_HIP(hipMemcpyAsync(&nsel, mu_nsel_, 4, hipMemcpyDeviceToHost, int_stream_));
+    DR_HIP(hipStreamSynchronize(int_stream_));
+    return std::max(0, std::min(nsel, n));
+  }
+  void mu_table_reserve(size_t nblk) {
+    mu_grow(mu_coords_, mu_coords_cap_, 3 * nblk);
+    mu_grow(mu_first_, mu_first_cap_, nblk + 1);
+  }
+  // The resident pass of launch_mesh over the selected blocks only (all of them when full), plus the patch table.
+  void launch_mesh_update(const float *lower, const float *upper, bool full) {
+    int na = 0;
+    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
+    const int nblk = std::min(na, o_.num_blocks);
+    int n[3];
+    const size_t ntab = mesh_lattice(lower, upper, n);
+    mesh_stats_[0] = mesh_stats_[1] = mesh_stats_[2] = 0;
+    mu_stats_[0] = (uint64_t)std::max(nblk, 0); mu_stats_[1] = 0; mu_stats_[2] = mu_poses_.size(); mu_stats_[3] = full;
+    mu_l_nblk_ = 0;
+    if (nblk <= 0 || n[0] <= 0 || n[1] <= 0 || n[2] <= 0 || (!full && mu_poses_.empty())) return mesh_empty();
+    McArgs a{};
+    mesh_prepare(lower, n, ntab, a);
+    size_t tb = mesh_tmp_bytes_;
+    DR_HIP(rocprim::radix_sort_keys(mesh_tmp_, tb, d_.blk_key, mesh_keys_, (size_t)nblk, 0, 63, int_stream_));
+    const unsigned long long *sel = mesh_keys_;
+    int nsel = nblk;
+    if (!full) { nsel = mu_select(mesh_keys_, nblk); sel = mu_sel_; }
+    if (nsel == 0) return mesh_empty();
+    mu_table_reserve((size_t)nsel);
+    a.sorted_keys = sel; a.nblk = nsel;
+    hipLaunchKernelGGL((k_mc_cells<false>), dim3(nsel), dim3(256), 0, int_stream_, d_, a);
+    tb = mesh_tmp_bytes_;
+    DR_HIP(rocprim::exclusive_scan(mesh_tmp_, tb, mesh_counts_, mesh_offsets_, 0u, (size_t)nsel, rocprim::plus<unsigned>(), int_stream_));
+    hipLaunchKernelGGL((k_mc_cells<true>), dim3(nsel), dim3(256), 0, int_stream_, d_, a);
+    hipLaunchKernelGGL(k_mc_total, dim3(1), dim3(1), 0, int_stream_, mesh_counts_, mesh_offsets_, nsel, mesh_total_);
+    hipLaunchKernelGGL(k_mu_table, dim3(cdiv(nsel + 1, 256)), dim3(256), 0, int_stream_, sel, nsel, mesh_counts_, mesh_offsets_,
+                       (const unsigned long long *)nullptr, (size_t)0, mu_coords_, mu_first_);
+    DR_HIP(hipGetLastError());
+    DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
+    mesh_stats_[0] = (uint64_t)nsel; mesh_stats_[2] = 1;
+    mu_stats_[1] = (uint64_t)nsel; mu_l_nblk_ = (size_t)nsel;
+  }
   // ---- the map pass (DRF_MESH_MAP with blocks in the host store; DESIGN.md §7c "Meshing the whole map") ----
   // Global order = ascending key over resident and stored blocks, as the resident pass orders the pool.  The merged list is cut
   // into chunks; a chunk stages its own stored blocks and every stored block among the 26 neighbours of its blocks (at most
@@ -2040,13 +2212,19 @@ class FusionEngine {
       DR_HIP(hipEventRecord(ms_used_[b], int_stream_));
     }
   }
-  void launch_mesh_map(const float *lower, const float *upper) {
+  // update: the mesh-update form (drf_extract_mesh_update_async) -- only the blocks the selection kernel keeps (all of the scope
+  // when full) are planned into chunks, staged and meshed, and each chunk adds its rows to the patch table.
+  void launch_mesh_map(const float *lower, const float *upper, bool update = false, bool full = true) {
     int na = 0;
     DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
     const int nblk = std::min(na, o_.num_blocks);
     int n[3];
     const size_t ntab = mesh_lattice(lower, upper, n);
     mesh_stats_[0] = mesh_stats_[1] = mesh_stats_[2] = 0;
+    if (update) {
+      mu_stats_[0] = mu_stats_[1] = 0; mu_stats_[2] = mu_poses_.size(); mu_stats_[3] = full;
+      mu_l_nblk_ = 0;
+    }
     if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) return mesh_empty();
     McArgs a{};
     mesh_prepare(lower, n, ntab, a);
@@ -2089,12 +2267,40 @@ class FusionEngine {
       ob.push_back(own.size()); sb.push_back(stg.size());
       cur.clear(); in_cur.clear();
     };
-    size_t i = 0, j = 0;
+    // update: the scope is the merged list within the range; the selection kernel runs over it and the survivors come back
+    std::vector<unsigned long long> picked;
+    if (update) {
+      std::vector<unsigned long long> scope;
+      scope.reserve(res.size() + sto.size());
+      for (size_t i = 0, j = 0; i < res.size() || j < sto.size();) {
+        const bool stored = j < sto.size() && (i >= res.size() || sto[j] < res[i]);
+        const unsigned long long key = stored ? sto[j++] : res[i++];
+        if (in_range(key)) scope.push_back(key);
+      }
+      mu_stats_[0] = scope.size();
+      if (scope.empty() || (!full && mu_poses_.empty())) return mesh_empty();
+      if (scope.size() > (size_t)INT_MAX) fail(DR_ERR_CAPACITY, "mesh update: %zu blocks in scope", scope.size());
+      if (full) picked.swap(scope);
+      else {
+        mu_grow(mu_scope_, mu_scope_cap_, scope.size());
+        DR_HIP(hipMemcpyAsync(mu_scope_, scope.data(), scope.size() * 8, hipMemcpyHostToDevice, int_stream_));
+        const int nsel = mu_select(mu_scope_, (int)scope.size());
+        if (nsel == 0) return mesh_empty();
+        picked.resize((size_t)nsel);
+        DR_HIP(hipMemcpy(picked.data(), mu_sel_, (size_t)nsel * 8, hipMemcpyDeviceToHost));
+      }
+      mu_table_reserve(picked.size());
+    }
+    size_t i = 0, j = 0, pk = 0;
     unsigned long long need[27];
     while (i < res.size() || j < sto.size()) {
       const bool stored = j < sto.size() && (i >= res.size() || sto[j] < res[i]);
       const unsigned long long key = stored ? sto[j++] : res[i++];
       if (!in_range(key)) continue;
+      if (update) {  // picked is a subsequence of the merged list
+        if (pk == picked.size() || picked[pk] != key) continue;
+        ++pk;
+      }
       int c[3]; unpack_key_host(key, c);
       int nn = 0, fresh = 0;  // stored blocks this block reads / those not staged for the chunk yet
       for (int k = 0; k < 27; ++k) {
@@ -2137,12 +2343,16 @@ class FusionEngine {
       size_t tb = mesh_tmp_bytes_;
       DR_HIP(rocprim::exclusive_scan(mesh_tmp_, tb, mesh_counts_, mesh_offsets_, 0u, no, rocprim::plus<unsigned>(), int_stream_));
       hipLaunchKernelGGL((k_mc_cells<true, true>), dim3((unsigned)no), dim3(256), 0, int_stream_, d_, a);
+      if (update)
+        hipLaunchKernelGGL(k_mu_table, dim3(cdiv((int)no + 1, 256)), dim3(256), 0, int_stream_, dk, (int)no, mesh_counts_, mesh_offsets_,
+                           (const unsigned long long *)mesh_total_, ob[ch], mu_coords_, mu_first_);
       hipLaunchKernelGGL(k_mc_advance, dim3(1), dim3(1), 0, int_stream_, mesh_counts_, mesh_offsets_, (int)no, mesh_total_);
       DR_HIP(hipEventRecord(ms_used_[b], int_stream_));
     }
     DR_HIP(hipGetLastError());
     DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
     mesh_stats_[0] = own.size(); mesh_stats_[1] = stg.size(); mesh_stats_[2] = (uint64_t)nchunk;
+    if (update) { mu_stats_[1] = own.size(); mu_l_nblk_ = own.size(); }
   }
   hipEvent_t mesh_done_ev() {
     if (!mesh_done_) DR_HIP(hipEventCreateWithFlags(&mesh_done_, hipEventDisableTiming));
@@ -2227,6 +2437,20 @@ class FusionEngine {
   float *mesh_vert_ = nullptr, *mesh_cols_ = nullptr;
   int mesh_scope_ = DRF_MESH_RESIDENT;
   uint64_t mesh_stats_[3] = {0, 0, 0};
+  // mesh update (incremental mesh).  Baseline = the last update fetched: its box, the round-trip redirect count at its launch;
+  // mu_poses_ = Ti of the scans since the last update was LAUNCHED (they belong to the next one).  mu_l_* describe the pending
+  // update and become the baseline when it is fetched.  Device scratch grows with the scope.
+  bool mesh_pending_update_ = false;
+  bool mu_valid_ = false, mu_force_full_ = false, mu_overflow_ = false, mu_l_full_ = false;
+  float mu_box_[6] = {0, 0, 0, 0, 0, 0}, mu_l_box_[6] = {0, 0, 0, 0, 0, 0};
+  unsigned long long mu_redirects_ = 0, mu_l_redirects_ = 0;
+  std::vector<MuPose> mu_poses_;
+  size_t mu_l_nblk_ = 0;
+  uint64_t mu_stats_[4] = {0, 0, 0, 0};
+  unsigned *mu_flags_ = nullptr, *mu_pos_ = nullptr;
+  unsigned long long *mu_sel_ = nullptr, *mu_scope_ = nullptr, *mu_first_ = nullptr;
+  int *mu_nsel_ = nullptr, *mu_coords_ = nullptr;
+  size_t mu_flags_cap_ = 0, mu_pos_cap_ = 0, mu_sel_cap_ = 0, mu_scope_cap_ = 0, mu_first_cap_ = 0, mu_coords_cap_ = 0;
   // map pass staging (allocated with the first map-scope extraction that meets a non-empty host store): two pinned / device
   // buffer pairs of ms_bytes_ = own keys + staged keys + staged voxels, a copy stream and the events that order the reuse
   size_t ms_bytes_ = 0;
@@ -2366,5 +2590,15 @@ int drf_export_host_blocks(drf_t *h, int max_blocks, int32_t *coords, uint8_t *v
 }
 int drf_set_mesh_scope(drf_t *h, int scope) { return guarded([&] { eng(h)->set_mesh_scope(scope); }); }
 int drf_mesh_stats(drf_t *h, uint64_t out[3]) { return guarded([&] { eng(h)->mesh_stats(out); }); }
+int drf_extract_mesh_update_async(drf_t *h, const float *lower, const float *upper) {
+  return guarded([&] { eng(h)->extract_mesh_update_async(lower, upper); });
+}
+int drf_mesh_update_size(drf_t *h, size_t *nblk, size_t *ntri, int *full) { return guarded([&] { eng(h)->mesh_update_size(nblk, ntri, full); }); }
+int drf_get_mesh_update_sync(drf_t *h, size_t max_blocks, size_t num_max, size_t *nblk, int32_t *coords, uint64_t *first, size_t *num,
+                             float *vert, float *cols, int *full) {
+  return guarded([&] { eng(h)->get_mesh_update_sync(max_blocks, num_max, nblk, coords, first, num, vert, cols, full); });
+}
+int drf_mesh_update_reset(drf_t *h) { return guarded([&] { eng(h)->mesh_update_reset(); }); }
+int drf_mesh_update_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->mesh_update_stats(out); }); }
 
 }  // extern "C"

@@ -22,6 +22,52 @@ def DrFusionOptions(**kw):
 MESH_RESIDENT, MESH_MAP = 0, 1
 
 
+MESH_UPDATE_MAX_SCANS = 16  # DRF_MESH_UPDATE_MAX_SCANS: one scan more between two updates makes the next one full
+
+
+def pack_block_key(coords):
+    """The packed key that orders blocks in every extraction: x, then y, then z, each biased by 2^20 (21 bits each)."""
+    c = np.asarray(coords, np.int64) + (1 << 20)
+    return (c[..., 0] << 42) | (c[..., 1] << 21) | c[..., 2]
+
+
+class MeshPatches:
+    """The consumer's side of the incremental mesh: {block -> its triangle rows}.  apply() takes what GetMeshUpdateSync
+    returns -- a full update empties the store first, every listed block's entry is replaced (an empty patch deletes it) --
+    and assemble() concatenates the entries in ascending packed-key order, which is byte for byte the full extraction over
+    the same box at the moment the update was launched.  Pure numpy: a viewer keeps one of these per mesh."""
+
+    def __init__(self):
+        self.blocks = {}  # (bx, by, bz) -> (vert (3t, 3) float32, cols (3t, 3) float32)
+
+    def apply(self, update):
+        full, coords, first, vert, cols = update
+        coords = np.asarray(coords, np.int32).reshape(-1, 3)
+        first = np.asarray(first, np.uint64).astype(np.int64)
+        assert len(first) == len(coords) + 1, "first has one row more than there are blocks"
+        if full:
+            self.blocks.clear()
+        for i, c in enumerate(coords):
+            k, a, b = tuple(int(v) for v in c), 3 * int(first[i]), 3 * int(first[i + 1])
+            if b > a:
+                self.blocks[k] = (np.array(vert[a:b], np.float32), np.array(cols[a:b], np.float32))
+            else:
+                self.blocks.pop(k, None)
+        return self
+
+    def assemble(self):
+        """(vert, cols), each (3 * triangles, 3) float32."""
+        if not self.blocks:
+            return np.empty((0, 3), np.float32), np.empty((0, 3), np.float32)
+        keys = list(self.blocks)
+        order = np.argsort(pack_block_key(np.array(keys, np.int64)), kind="stable")
+        return (np.concatenate([self.blocks[keys[i]][0] for i in order]).reshape(-1, 3),
+                np.concatenate([self.blocks[keys[i]][1] for i in order]).reshape(-1, 3))
+
+    def num_triangles(self):
+        return sum(len(v) for v, _ in self.blocks.values()) // 3
+
+
 def streaming_min_radius(options):
     """drf_streaming_min_radius: the smallest exact streaming radius for these options (host-only)."""
     r = C.c_float()
@@ -205,6 +251,44 @@ class DrFusion:
         out = (C.c_uint64 * 3)()
         check(self._L.drf_mesh_stats(self._h, out))
         return tuple(int(v) for v in out)
+
+    # ---- incremental mesh (include/dr_mi355x.h, DESIGN.md "Incremental mesh") ----
+    def ExtractMeshUpdateAsync(self, lower_corner, upper_corner):
+        """Launches a mesh update over the box: only the blocks whose triangles may have changed since the last update that
+        was fetched are meshed again (all of them when the update is full).  Legal where ExtractMeshAsync is."""
+        lo, up = (np.ascontiguousarray(a, np.float32) for a in (lower_corner, upper_corner))
+        check(self._L.drf_extract_mesh_update_async(self._h, fptr(lo), fptr(up)))
+
+    def mesh_update_size(self):
+        """(listed blocks, triangles, full) of the pending update; waits for it, does not consume it."""
+        nb, nt, full = C.c_size_t(), C.c_size_t(), C.c_int()
+        check(self._L.drf_mesh_update_size(self._h, C.byref(nb), C.byref(nt), C.byref(full)))
+        return int(nb.value), int(nt.value), bool(full.value)
+
+    def GetMeshUpdateSync(self):
+        """(full, coords (n, 3) int32, first (n + 1,) uint64, vert, cols): block i owns triangles [first[i], first[i + 1]) of
+        vert / cols ((3 * triangles, 3) float32 as GetMeshSync's).  MeshPatches.apply takes the tuple."""
+        nb, nt, _ = self.mesh_update_size()
+        coords, first = np.empty((max(nb, 1), 3), np.int32), np.zeros(nb + 1, np.uint64)
+        vert, cols = np.empty((max(3 * nt, 1), 3), np.float32), np.empty((max(3 * nt, 1), 3), np.float32)
+        n, num, full = C.c_size_t(), C.c_size_t(), C.c_int()
+        check(self._L.drf_get_mesh_update_sync(self._h, nb, max(3 * nt, 1), C.byref(n), coords.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               first.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(num), fptr(vert), fptr(cols), C.byref(full)))
+        return bool(full.value), coords[:n.value], first, vert[:num.value], cols[:num.value]
+
+    def GetMeshUpdate(self, lower_corner, upper_corner):
+        self.ExtractMeshUpdateAsync(lower_corner, upper_corner)
+        return self.GetMeshUpdateSync()
+
+    def mesh_update_reset(self):
+        """The next update is full."""
+        check(self._L.drf_mesh_update_reset(self._h))
+
+    def mesh_update_stats(self):
+        """Last update launched: dict(scope=blocks in scope, meshed=blocks meshed again, scans=scans folded in, full)."""
+        out = (C.c_uint64 * 4)()
+        check(self._L.drf_mesh_update_stats(self._h, out))
+        return dict(scope=int(out[0]), meshed=int(out[1]), scans=int(out[2]), full=bool(out[3]))
 
     def export_all_blocks(self):
         """The whole map: resident blocks and the host store merged (a block is in exactly one of them)."""

@@ -90,6 +90,33 @@ public:
   // DRF_MESH_MAP: SaveMeshToFile / ExtractMeshAsync / GetMeshSync / GetMesh cover the host store too (DRF_MESH_RESIDENT: the pool only)
   void SetMeshScope(int scope) { check(drf_set_mesh_scope(impl, scope)); }
 
+  // Incremental mesh (dr_mi355x.h "incremental mesh", INTEGRATION.md "Incremental mesh"): GetMeshUpdateSync fills dr_mesh_num /
+  // dr_mesh_vert / dr_mesh_cols with the triangles of the listed blocks only, and the members below name the blocks: block i has
+  // coordinates dr_mesh_update_coords[3 i ..] and owns triangles [dr_mesh_update_first[i], dr_mesh_update_first[i + 1]).
+  // dr_mesh_update_full: every block is listed, drop what was kept before.
+  void ExtractMeshUpdateAsync(float lower_corner[3], float upper_corner[3]) { check(drf_extract_mesh_update_async(impl, lower_corner, upper_corner)); }
+  void GetMeshUpdateSync() {
+    size_t nblk = 0, ntri = 0;
+    int full = 0;
+    check(drf_mesh_update_size(impl, &nblk, &ntri, &full));
+    if (!dr_mesh_vert) {
+      dr_mesh_vert = (float *) malloc(sizeof(float) * dr_mesh_num_max * 3);
+      dr_mesh_cols = (float *) malloc(sizeof(float) * dr_mesh_num_max * 3);
+    }
+    dr_mesh_update_coords.resize(3 * nblk + 3);
+    dr_mesh_update_first.resize(nblk + 1);
+    check(drf_get_mesh_update_sync(impl, nblk, dr_mesh_num_max, &dr_mesh_update_blocks, dr_mesh_update_coords.data(), dr_mesh_update_first.data(),
+                                   &dr_mesh_num, dr_mesh_vert, dr_mesh_cols, &full));
+    dr_mesh_update_coords.resize(3 * dr_mesh_update_blocks);
+    dr_mesh_update_full = full != 0;
+  }
+  void ResetMeshUpdate() { check(drf_mesh_update_reset(impl)); }
+
+  bool dr_mesh_update_full = false;
+  size_t dr_mesh_update_blocks = 0;
+  std::vector<int32_t> dr_mesh_update_coords;
+  std::vector<uint64_t> dr_mesh_update_first;
+
   size_t dr_mesh_num = 0;
   const size_t dr_mesh_num_max = 60000000;
   float *dr_mesh_vert;
