@@ -29,22 +29,19 @@
 #include <cstring>
 #include <chrono>
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <memory>
-#include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>  // device radix sort (block keys) and exclusive scan (triangle offsets) of the mesh path
 
 #include "dr_common.h"
+#include "fusion_host.h"  // the host half of the map: block keys (kBS), reach bounds, host store, chunk planner
 #define DR_MC_CONST __device__ static const
 #include "mc_tables.h"
 
 namespace dr {
 
-constexpr int kBS = 8;        // voxel block edge (DrFusionOptions::block_size must be 8, as TANDEM sets it)
 constexpr int kMaxDDA = 4096;  // cap on DDA steps per ray (the reference loops unboundedly)
 constexpr unsigned long long kEmptyKey = ~0ull;
 
@@ -1113,146 +1110,77 @@ __global__ __launch_bounds__(256) void k_publish(const unsigned char *__restrict
   for (size_t i = (qb << 4) + t; i < nb; i += nt) hb[i] = b[i];
 }
 
-// ------------------------------------------------------------------ streaming (host side)
-// Farthest a block centre can lie from the camera centre of a scan whose valid depths do not exceed `depth` and still be
-// read or written by that scan (DESIGN.md "Streaming voxel blocks" derives each term):
-//   allocation DDA  depth*rho + trunc + 4.5*sqrt(3)*vs    (points of the ray up to surf + trunc; block centre within 4.5 sqrt(3) vs)
-//                   12.5*sqrt(3)*vs                       (the start block shifted one block back on negative axes)
-//   voxel update    depth*rho + trunc + 3.5*sqrt(3)*vs    (updated voxels have vd < sd + trunc)
-//   ray-cast        depth*rho + 4.5*sqrt(3)*vs            (samples at cur < max_sensor_depth, trilinear corners within sqrt(3) vs)
-// plus one block diagonal (8 sqrt(3) vs) and one voxel of margin.  rho = the largest |((u - cx)/fx, (v - cy)/fy, 1)| over
-// the image corners.  Evaluated in double.
-static double corner_rho(const drf_options_t &o) {
-  double rho = 0.0;
-  for (int k = 0; k < 4; ++k) {
-    const double u = (k & 1) ? o.width - 1 : 0, v = (k & 2) ? o.height - 1 : 0;
-    const double a = (u - o.cx) / o.fx, b = (v - o.cy) / o.fy;
-    rho = std::max(rho, std::sqrt(a * a + b * b + 1.0));
-  }
-  return rho;
-}
-static double stream_reach(const drf_options_t &o, double depth) {
-  const double s3 = std::sqrt(3.0), vs = o.voxel_size;
-  const double rho = corner_rho(o);
-  const double scan = std::max(depth * rho + (double)o.truncation_distance + 4.5 * s3 * vs, 12.5 * s3 * vs);
-  return scan + 8.0 * s3 * vs + vs;
-}
-static bool stream_options_ok(const drf_options_t &o) {
-  auto pos = [](double x) { return std::isfinite(x) && x > 0.0; };
-  return pos(o.voxel_size) && pos(o.fx) && pos(o.fy) && std::isfinite(o.cx) && std::isfinite(o.cy) && o.width > 0 && o.height > 0 &&
-         pos(o.max_sensor_depth) && std::isfinite(o.truncation_distance) && o.truncation_distance >= 0.0f;
-}
-static float streaming_min_radius(const drf_options_t &o) { return (float)stream_reach(o, o.max_sensor_depth); }
-// Mesh update: farthest a block ORIGIN can lie from the camera centre of a scan that writes one of its voxels (DESIGN.md
-// "Incremental mesh"): the "voxel update" term above taken at the origin (voxels lie within 7 sqrt(3) vs of it) plus the same
-// block diagonal and voxel of margin.  Options the bound is not defined for leave k_cull's test alone in charge.
-static float mesh_update_reach2(const drf_options_t &o) {
-  if (!stream_options_ok(o)) return INFINITY;
-  const double s3 = std::sqrt(3.0), vs = o.voxel_size;
-  const double r = (double)o.max_sensor_depth * corner_rho(o) + (double)o.truncation_distance + 7.0 * s3 * vs + 8.0 * s3 * vs + vs;
-  const float r2 = (float)(r * r * (1.0 + 1e-5));
-  return std::isfinite(r2) ? r2 : INFINITY;
-}
-
-static inline void unpack_key_host(unsigned long long k, int c[3]) {
-  const int B = 1 << 20;
-  c[0] = (int)((k >> 42) & 0x1fffff) - B;
-  c[1] = (int)((k >> 21) & 0x1fffff) - B;
-  c[2] = (int)(k & 0x1fffff) - B;
-}
-static inline bool pack_key_host(const int c[3], unsigned long long &k) {
-  const int B = 1 << 20;
-  for (int a = 0; a < 3; ++a)
-    if (c[a] < -B || c[a] >= B) return false;
-  k = ((unsigned long long)(unsigned)(c[0] + B) << 42) | ((unsigned long long)(unsigned)(c[1] + B) << 21) | (unsigned long long)(unsigned)(c[2] + B);
-  return true;
-}
-static inline float blk_origin_host(int c, float vs) { return (float)(c * kBS) * vs; }
-static inline double blk_centre_host(int c, float vs) { return ((double)(c * kBS) + 3.5) * vs; }
-
-// The host half of the map: block key -> 4 KB, in slabs of 1024 blocks, with a coarse spatial index (cells of 8^3 blocks)
-// so that the per-scan "stored blocks within the radius" query visits cells near the camera only.
-class HostBlockStore {
+// ------------------------------------------------------------------ engine
+// Owner of what the engine takes from the runtime for its lifetime: device and pinned buffers, events, streams.  All of it is
+// released with the owner -- buffers first, then the events and streams that work on them used -- also when the engine's
+// constructor throws half way.  The raw pointers and handles go where they are used (FusionDev, StreamDev, McArgs: by value).
+class HipOwner {
  public:
-  size_t size() const { return slot_.size(); }
-  bool empty() const { return slot_.empty(); }
-  void put(unsigned long long key, const void *vox) {
-    unsigned s;
-    if (!free_.empty()) { s = free_.back(); free_.pop_back(); }
-    else {
-      s = next_++;
-      if ((s >> kSlabShift) >= slabs_.size()) slabs_.emplace_back(new uint8_t[(size_t)4096 << kSlabShift]);
-    }
-    memcpy(at(s), vox, 4096);
-    slot_[key] = s;
-    cells_[cell_of(key)].push_back(key);
+  HipOwner() = default;
+  HipOwner(const HipOwner &) = delete;
+  void operator=(const HipOwner &) = delete;
+  ~HipOwner() {
+    if (dev_.empty() && pin_.empty() && ev_.empty() && st_.empty()) return;  // nothing taken: no device of ours to wait for
+    (void)hipDeviceSynchronize();
+    for (void *p : dev_) (void)hipFree(p);
+    for (void *p : pin_) (void)hipHostFree(p);
+    for (hipEvent_t e : ev_) (void)hipEventDestroy(e);
+    for (hipStream_t s : st_) (void)hipStreamDestroy(s);
   }
-  const uint8_t *get(unsigned long long key) const { return at(slot_.at(key)); }
-  bool contains(unsigned long long key) const { return slot_.count(key) != 0; }
-  void erase(unsigned long long key) {
-    auto it = slot_.find(key);
-    free_.push_back(it->second);
-    slot_.erase(it);
-    auto c = cells_.find(cell_of(key));
-    auto &v = c->second;
-    for (size_t i = 0; i < v.size(); ++i)
-      if (v[i] == key) { v[i] = v.back(); v.pop_back(); break; }
-    if (v.empty()) cells_.erase(c);
+  // device memory, cleared on stream `zero_on` if one is given
+  template <class T> T *device(size_t n, hipStream_t zero_on = nullptr) {
+    T *p = (T *)take(dev_, [&](void **q) { *q = dalloc<T>(n); });
+    if (zero_on) DR_HIP(hipMemsetAsync(p, 0, n * sizeof(T), zero_on));
+    return p;
   }
-  template <class F> void for_each(F f) const { for (auto &kv : slot_) f(kv.first, at(kv.second)); }
-  // keys of the stored blocks whose streaming centre lies within r of p
-  void query_sphere(const double p[3], double r, float vs, std::vector<unsigned long long> &out) const {
-    if (slot_.empty()) return;
-    const double cell = 64.0 * vs;  // 8 blocks
-    long lo[3], hi[3];
-    double span = 1.0;
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = (long)std::floor((p[a] - r) / cell) - 1;
-      hi[a] = (long)std::floor((p[a] + r) / cell) + 1;
-      span *= (double)(hi[a] - lo[a] + 1);
-    }
-    auto test_cell = [&](const std::vector<unsigned long long> &v) {
-      for (unsigned long long k : v) {
-        int c[3]; unpack_key_host(k, c);
-        const double dx = blk_centre_host(c[0], vs) - p[0], dy = blk_centre_host(c[1], vs) - p[1], dz = blk_centre_host(c[2], vs) - p[2];
-        if (dx * dx + dy * dy + dz * dz <= r * r) out.push_back(k);
-      }
-    };
-    if (span > (double)cells_.size()) {  // fewer occupied cells than cells in range: walk the occupied ones
-      for (auto &kv : cells_) {
-        const long cx = cell_coord(kv.first, 0), cy = cell_coord(kv.first, 1), cz = cell_coord(kv.first, 2);
-        if (cx >= lo[0] && cx <= hi[0] && cy >= lo[1] && cy <= hi[1] && cz >= lo[2] && cz <= hi[2]) test_cell(kv.second);
-      }
-      return;
-    }
-    for (long x = lo[0]; x <= hi[0]; ++x)
-      for (long y = lo[1]; y <= hi[1]; ++y)
-        for (long z = lo[2]; z <= hi[2]; ++z) {
-          auto it = cells_.find(pack_cell(x, y, z));
-          if (it != cells_.end()) test_cell(it->second);
-        }
+  // page-locked host memory; as_device: the address the kernels use for it
+  template <class T> T *pinned(size_t n, T **as_device = nullptr) {
+    T *p = (T *)take(pin_, [&](void **q) { DR_HIP(hipHostMalloc(q, n * sizeof(T), hipHostMallocDefault)); });
+    if (as_device) DR_HIP(hipHostGetDevicePointer((void **)as_device, p, 0));
+    return p;
+  }
+  hipEvent_t event(unsigned flags = hipEventDisableTiming) {
+    return take(ev_, [&](hipEvent_t *e) { DR_HIP(hipEventCreateWithFlags(e, flags)); });
+  }
+  hipStream_t stream(int priority = 0) {
+    return take(st_, [&](hipStream_t *q) { DR_HIP(hipStreamCreateWithPriority(q, hipStreamNonBlocking, priority)); });
   }
 
  private:
-  static constexpr int kSlabShift = 10;
-  uint8_t *at(unsigned s) const { return slabs_[s >> kSlabShift].get() + (size_t)(s & ((1u << kSlabShift) - 1)) * 4096; }
-  static unsigned long long pack_cell(long x, long y, long z) {
-    const long B = 1 << 20;
-    return ((unsigned long long)(x + B) << 42) | ((unsigned long long)(y + B) << 21) | (unsigned long long)(z + B);
+  // the slot first, then what goes into it: nothing is taken that could not be recorded
+  template <class H, class Make> H take(std::vector<H> &v, Make make) {
+    v.push_back(H());
+    make(&v.back());
+    return v.back();
   }
-  static long cell_coord(unsigned long long ck, int a) { return (long)((ck >> (42 - 21 * a)) & 0x1fffff) - (1 << 20); }
-  static unsigned long long cell_of(unsigned long long key) {
-    int c[3]; unpack_key_host(key, c);
-    return pack_cell(c[0] >> 3, c[1] >> 3, c[2] >> 3);  // arithmetic shift = floor division by 8
+  std::vector<void *> dev_, pin_;
+  std::vector<hipEvent_t> ev_;
+  std::vector<hipStream_t> st_;
+};
+// Device scratch that grows with its use; contents are not kept.  `st`: the stream whose work may still read the old allocation.
+template <class T>
+class DeviceBuf {
+ public:
+  DeviceBuf() = default;
+  DeviceBuf(const DeviceBuf &) = delete;
+  void operator=(const DeviceBuf &) = delete;
+  ~DeviceBuf() { (void)hipFree(p_); }
+  void reserve(size_t n, hipStream_t st) {
+    if (n <= cap_) return;
+    DR_HIP(hipStreamSynchronize(st));
+    if (p_) DR_HIP(hipFree(p_));
+    p_ = nullptr; cap_ = 0;
+    p_ = dalloc<T>(n);
+    cap_ = n;
   }
-  std::unordered_map<unsigned long long, unsigned> slot_;
-  std::unordered_map<unsigned long long, std::vector<unsigned long long>> cells_;
-  std::vector<std::unique_ptr<uint8_t[]>> slabs_;
-  std::vector<unsigned> free_;
-  unsigned next_ = 0;
+  T *get() const { return p_; }
+  size_t capacity() const { return cap_; }
+
+ private:
+  T *p_ = nullptr;
+  size_t cap_ = 0;
 };
 
-// ------------------------------------------------------------------ engine
 constexpr int kDefaultFusionPriority = 1;  // 0 least (the reference's), 1 normal (measured best in the TandemBackend loop), 2 greatest
 class FusionEngine {
  public:
@@ -1271,100 +1199,65 @@ class FusionEngine {
     DR_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
     int lo = kDefaultFusionPriority == 2 ? greatest : (kDefaultFusionPriority == 1 ? 0 : least);
     if (const char *e = getenv("DR_FUSION_PRIORITY")) lo = !strcmp(e, "high") ? greatest : (!strcmp(e, "normal") ? 0 : (!strcmp(e, "low") ? least : lo));
-    DR_HIP(hipStreamCreateWithPriority(&int_stream_, hipStreamNonBlocking, lo));
+    int_stream_ = own_.stream(lo);
     npix_ = (size_t)o.height * o.width;
     size_t cap = 1024;
     const size_t want = std::max((size_t)o.num_buckets * (size_t)o.bucket_size, (size_t)2 * o.num_blocks);
     while (cap < want) cap <<= 1;
     d_.o = o;
-    d_.keys = dalloc<unsigned long long>(cap);
-    d_.vals = dalloc<int>(cap);
+    d_.keys = own_.device<unsigned long long>(cap);
+    d_.vals = own_.device<int>(cap);
     // -1 everywhere: an insert publishes the key (CAS) BEFORE it stores the pool index, so a concurrent reader -- the ray-cast of scan k
     // beside the allocation of scan k + 1 (enqueue_scan) -- may match a key whose value is not there yet; it then reads -1 = absent, which
     // is the state the block was in a moment ago (its voxels are still all unobserved: the same ray-cast result either way)
     DR_HIP(hipMemsetAsync(d_.vals, 0xFF, cap * sizeof(int), int_stream_));
     d_.cmask = (unsigned)(cap - 1);
-    d_.blk_key = dalloc<unsigned long long>(o.num_blocks);
-    d_.vox = dalloc<Voxel>((size_t)o.num_blocks * 512);
-    d_.n_alloc = dalloc<int>(4);
+    d_.blk_key = own_.device<unsigned long long>(o.num_blocks);
+    d_.vox = own_.device<Voxel>((size_t)o.num_blocks * 512, int_stream_);  // hash_table.cu:28-32
+    d_.n_alloc = own_.device<int>(4, int_stream_);
     d_.err = d_.n_alloc + 1;
-    d_.cnt = dalloc<unsigned long long>(8);
-    d_.sd = dalloc<float>(npix_);
-    d_.pix = dalloc<PixRec>(npix_);
-    for (int l = 0; l < kSuperLevels; ++l) d_.super[l] = dalloc<unsigned char>((size_t)1 << (3 * (kGridBits - kSuperShift[l])));
-    d_.present = dalloc<unsigned>((size_t)1 << (3 * kPresentBits - 5));
-    DR_HIP(hipMemsetAsync(d_.present, 0, (size_t)1 << (3 * kPresentBits - 3), int_stream_));
-    d_.grid = dalloc<int>((size_t)1 << (3 * kGridBits));
-    DR_HIP(hipMemsetAsync(d_.grid, 0, sizeof(int) << (3 * kGridBits), int_stream_));
-    for (int l = 0; l < kSuperLevels; ++l) DR_HIP(hipMemsetAsync(d_.super[l], 0, (size_t)1 << (3 * (kGridBits - kSuperShift[l])), int_stream_));
-    d_.req = dalloc<unsigned>(o.num_blocks);
-    d_.req_count = dalloc<int>(4);
+    d_.cnt = own_.device<unsigned long long>(8, int_stream_);
+    d_.sd = own_.device<float>(npix_);
+    d_.pix = own_.device<PixRec>(npix_);
+    for (int l = 0; l < kSuperLevels; ++l) d_.super[l] = own_.device<unsigned char>((size_t)1 << (3 * (kGridBits - kSuperShift[l])), int_stream_);
+    d_.present = own_.device<unsigned>((size_t)1 << (3 * kPresentBits - 5), int_stream_);
+    d_.grid = own_.device<int>((size_t)1 << (3 * kGridBits), int_stream_);
+    d_.req = own_.device<unsigned>(o.num_blocks);
+    d_.req_count = own_.device<int>(4, int_stream_);
     d_.vis_count = d_.req_count + 1;
-    d_.vis = dalloc<int>(o.num_blocks);
-    d_.wg_upd = dalloc<unsigned>(65536);
-    DR_HIP(hipMemsetAsync(d_.req_count, 0, 16, int_stream_));
+    d_.vis = own_.device<int>(o.num_blocks);
+    d_.wg_upd = own_.device<unsigned>(65536);
     setup_fast_div();
     hipLaunchKernelGGL(k_fill_keys, dim3(1024), dim3(256), 0, int_stream_, d_.keys, cap);
-    DR_HIP(hipMemsetAsync(d_.vox, 0, (size_t)o.num_blocks * 512 * sizeof(Voxel), int_stream_));  // hash_table.cu:28-32
-    DR_HIP(hipMemsetAsync(d_.n_alloc, 0, 16, int_stream_));
-    DR_HIP(hipMemsetAsync(d_.cnt, 0, 64, int_stream_));
-    d_bgr_in_ = dalloc<unsigned char>(npix_ * 3);
-    d_depth_in_ = dalloc<float>(npix_);
-    DR_HIP(hipHostMalloc((void **)&h_bgr_in_, npix_ * 3, hipHostMallocDefault));
-    DR_HIP(hipHostMalloc((void **)&h_depth_in_, npix_ * 4, hipHostMallocDefault));
+    d_bgr_in_ = own_.device<unsigned char>(npix_ * 3);
+    d_depth_in_ = own_.device<float>(npix_);
+    h_bgr_in_ = own_.pinned<unsigned char>(npix_ * 3);
+    h_depth_in_ = own_.pinned<float>(npix_);
     // 12 workgroups per CU: enough to keep every SIMD's 4 resident waves busy, few enough that the blocks being worked on
     // at any moment are neighbours in the pool (sweep on the bench map: 1024 / 3072 / 4096 / 6144 / 8192 / 16384
     // workgroups -> 0.341 / 0.327 / 0.329 / 0.363 / 0.443 / 0.697 ms per scan)
     integrate_grid_ = std::min(cdiv(o.num_blocks, 4), 3072);
     if (const char *e = hook_env("DR_INT_GRID")) integrate_grid_ = std::min(65536, std::max(1, atoi(e)));  // tuning hook
-    DR_HIP(hipEventCreateWithFlags(&int_done_, hipEventDisableTiming));
+    int_done_ = own_.event();
     for (int i = 0; i < o.num_render_streams; ++i) {
       Render r;
-      DR_HIP(hipStreamCreateWithPriority(&r.stream, hipStreamNonBlocking, lo));
-      r.d_bgr = dalloc<unsigned char>(npix_ * 3);
-      r.d_depth = dalloc<float>(npix_);
-      r.d_flag = dalloc<int>(4);
+      r.stream = own_.stream(lo);
+      r.d_bgr = own_.device<unsigned char>(npix_ * 3);
+      r.d_depth = own_.device<float>(npix_);
+      r.d_flag = own_.device<int>(4);
       for (int k = 0; k < 2; ++k) {  // double-buffered host results ("blocked"/"free", tsdf_volume.cu:846-872)
-        DR_HIP(hipHostMalloc((void **)&r.h_bgr[k], npix_ * 3, hipHostMallocDefault));
-        DR_HIP(hipHostMalloc((void **)&r.h_depth[k], npix_ * 4, hipHostMallocDefault));
-        DR_HIP(hipHostGetDevicePointer((void **)&r.hd_bgr[k], r.h_bgr[k], 0));
-        DR_HIP(hipHostGetDevicePointer((void **)&r.hd_depth[k], r.h_depth[k], 0));
+        r.h_bgr[k] = own_.pinned<unsigned char>(npix_ * 3, &r.hd_bgr[k]);
+        r.h_depth[k] = own_.pinned<float>(npix_, &r.hd_depth[k]);
       }
-      DR_HIP(hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
-      DR_HIP(hipEventCreateWithFlags(&r.cast, hipEventDisableTiming));
+      r.done = own_.event();
+      r.cast = own_.event();
       renders_.push_back(r);
     }
     DR_HIP(hipStreamSynchronize(int_stream_));
   }
-  ~FusionEngine() {
+  ~FusionEngine() {  // the device idle before the growable scratch goes; own_ (declared first, so released last) frees the rest
     (void)hipSetDevice(device_);
     (void)hipDeviceSynchronize();
-    (void)hipFree(d_.keys); (void)hipFree(d_.vals); (void)hipFree(d_.blk_key); (void)hipFree(d_.vox);
-    (void)hipFree(d_.n_alloc); (void)hipFree(d_.cnt); (void)hipFree(d_.sd); (void)hipFree(d_.pix); (void)hipFree(d_.super[0]); (void)hipFree(d_.super[1]); (void)hipFree(d_.present); (void)hipFree(d_.grid); (void)hipFree(d_.req); (void)hipFree(d_.req_count); (void)hipFree(d_.vis); (void)hipFree(d_.wg_upd); (void)hipFree(d_bgr_in_); (void)hipFree(d_depth_in_);
-    (void)hipHostFree(h_bgr_in_); (void)hipHostFree(h_depth_in_);
-    for (auto &r : renders_) {
-      (void)hipFree(r.d_bgr); (void)hipFree(r.d_depth); (void)hipFree(r.d_flag);
-      for (int k = 0; k < 2; ++k) { (void)hipHostFree(r.h_bgr[k]); (void)hipHostFree(r.h_depth[k]); }
-      (void)hipEventDestroy(r.done); (void)hipEventDestroy(r.cast); (void)hipStreamDestroy(r.stream);
-    }
-    (void)hipEventDestroy(int_done_);
-    (void)hipStreamDestroy(int_stream_);
-    (void)hipFree(mesh_axis_); (void)hipFree(mesh_keys_); (void)hipFree(mesh_total_); (void)hipFree(mesh_counts_);
-    (void)hipFree(mesh_offsets_); (void)hipFree(mesh_tmp_); (void)hipFree(mesh_vert_); (void)hipFree(mesh_cols_);
-    if (mesh_done_) (void)hipEventDestroy(mesh_done_);
-    (void)hipFree(mu_flags_); (void)hipFree(mu_pos_); (void)hipFree(mu_sel_); (void)hipFree(mu_scope_); (void)hipFree(mu_first_);
-    (void)hipFree(mu_nsel_); (void)hipFree(mu_coords_);
-    for (int b = 0; b < 2; ++b) {
-      (void)hipFree(ms_dev_[b]); (void)hipHostFree(ms_host_[b]);
-      if (ms_copied_[b]) (void)hipEventDestroy(ms_copied_[b]);
-      if (ms_used_[b]) (void)hipEventDestroy(ms_used_[b]);
-    }
-    if (ms_copy_stream_) (void)hipStreamDestroy(ms_copy_stream_);
-    if (st_cap_) {
-      (void)hipFree(sd_.ctl); (void)hipFree(sd_.list); (void)hipFree(sd_.mv_dst); (void)hipFree(sd_.mv_src);
-      (void)hipHostFree(h_ev_keys_); (void)hipHostFree(h_ev_vox_); (void)hipHostFree(sd_.h_out); (void)hipHostFree(h_in_keys_); (void)hipHostFree(h_in_vox_);
-      for (auto &e : st_ev_) (void)hipEventDestroy(e);
-    }
   }
 
   // tsdf_volume.cu:515-598
@@ -1374,16 +1267,21 @@ class FusionEngine {
     if (st_radius_ <= 0.0f && !store_.empty()) fail(DR_ERR_PROTOCOL, "IntegrateScanAsync: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", store_.size());
     next_ = kRender;
     DR_HIP(hipSetDevice(device_));
-    DR_HIP(hipEventSynchronize(int_done_));  // previous scan's use of the pinned staging buffers
-    if (st_radius_ > 0.0f) {
-      stream_before_scan(pose16, max_valid_depth(depth));
-    }
-    memcpy(h_bgr_in_, bgr, npix_ * 3);
-    memcpy(h_depth_in_, depth, npix_ * 4);
-    DR_HIP(hipMemcpyAsync(d_bgr_in_, h_bgr_in_, npix_ * 3, hipMemcpyHostToDevice, int_stream_));
-    DR_HIP(hipMemcpyAsync(d_depth_in_, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
-    // the ray-casts read the volume; their result copies do not (the reference waits for the copies, tsdf_volume.cu:553-556)
-    enqueue_scan(d_bgr_in_, d_depth_in_, pose16, true);
+    const float depth_bound = st_radius_ > 0.0f ? max_valid_depth(depth, npix_, o_.min_sensor_depth, o_.max_sensor_depth) : 0.0f;
+    scan_between_streaming(pose16, depth_bound, [&] {
+      memcpy(h_bgr_in_, bgr, npix_ * 3);
+      memcpy(h_depth_in_, depth, npix_ * 4);
+      DR_HIP(hipMemcpyAsync(d_bgr_in_, h_bgr_in_, npix_ * 3, hipMemcpyHostToDevice, int_stream_));
+      DR_HIP(hipMemcpyAsync(d_depth_in_, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
+      // the ray-casts read the volume; their result copies do not (the reference waits for the copies, tsdf_volume.cu:553-556)
+      enqueue_scan(d_bgr_in_, d_depth_in_, pose16, true);
+    });
+  }
+  // One scan: the previous scan's use of the pinned buffers awaited, blocks streamed in before and out after, int_done_ behind it
+  template <class Enqueue> void scan_between_streaming(const float *pose16, float depth_bound, Enqueue enqueue) {
+    DR_HIP(hipEventSynchronize(int_done_));
+    if (st_radius_ > 0.0f) stream_before_scan(pose16, depth_bound);
+    enqueue();
     if (st_radius_ > 0.0f) stream_after_scan(pose16);
     DR_HIP(hipEventRecord(int_done_, int_stream_));
   }
@@ -1397,7 +1295,7 @@ class FusionEngine {
     if (raycast_no_skip_) dv.super[0] = nullptr;  // DR_RAYCAST_NO_SKIP=1: every sample is looked up (A/B and parity hook)
 #ifdef DR_PARITY_HOOKS
     if (raycast_stats_ && d_.fast_div) {  // DR_RAYCAST_STATS=1: a synchronous, counting launch of the same loop (prints to stderr)
-      if (!d_rstats_) d_rstats_ = dalloc<unsigned long long>(32);
+      if (!d_rstats_) d_rstats_ = own_.device<unsigned long long>(32);
       DR_HIP(hipMemsetAsync(d_rstats_, 0, 32 * 8, st));
       hipLaunchKernelGGL((k_raycast2<true, true>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, d_rstats_);
       unsigned long long h[32];
@@ -1487,10 +1385,9 @@ class FusionEngine {
   void stats(uint64_t out[4]) {
     DR_HIP(hipSetDevice(device_));
     DR_HIP(hipDeviceSynchronize());
-    unsigned long long c[4]; int na[2];
+    unsigned long long c[4];
     DR_HIP(hipMemcpy(c, d_.cnt, 32, hipMemcpyDeviceToHost));
-    DR_HIP(hipMemcpy(na, d_.n_alloc, 8, hipMemcpyDeviceToHost));
-    out[0] = (uint64_t)std::min(na[0], o_.num_blocks); out[1] = c[3]; out[2] = c[1]; out[3] = c[2];
+    out[0] = (uint64_t)pool_blocks(); out[1] = c[3]; out[2] = c[1]; out[3] = c[2];
   }
   // blocks k_integrate has read since the engine was created (one 4 KB read each, whether or not any voxel of the block was updated): with
   // `updated_total` this gives the kernel's HBM bytes exactly -- 4096 x visited + 8 x updated -- for the counter calibration in DESIGN.md
@@ -1504,31 +1401,23 @@ class FusionEngine {
   void export_blocks(int max_blocks, int32_t *coords, uint8_t *voxels, int *n) {
     DR_HIP(hipSetDevice(device_));
     DR_HIP(hipDeviceSynchronize());
-    int na = 0;
-    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
-    na = std::min(std::min(na, o_.num_blocks), max_blocks);
+    const int na = std::min(pool_blocks(), max_blocks);
     std::vector<unsigned long long> keys(na);
     DR_HIP(hipMemcpy(keys.data(), d_.blk_key, (size_t)na * 8, hipMemcpyDeviceToHost));
-    const int B = 1 << 20;
-    for (int i = 0; i < na; ++i) {
-      coords[3 * i] = (int)((keys[i] >> 42) & 0x1fffff) - B;
-      coords[3 * i + 1] = (int)((keys[i] >> 21) & 0x1fffff) - B;
-      coords[3 * i + 2] = (int)(keys[i] & 0x1fffff) - B;
-    }
+    for (int i = 0; i < na; ++i) unpack_key_host(keys[i], coords + 3 * i);
     DR_HIP(hipMemcpy(voxels, d_.vox, (size_t)na * 4096, hipMemcpyDeviceToHost));
     if (n) *n = na;
   }
   void fast_div_status(int *enabled, unsigned long long *mismatches) const { if (enabled) *enabled = d_.fast_div; if (mismatches) *mismatches = fast_div_mismatches_; }
   void test_combine(size_t n, const uint8_t *a, const uint8_t *b, int max_weight, uint8_t *out) {
     DR_HIP(hipSetDevice(device_));
-    Voxel *da = nullptr, *db = nullptr, *dout = nullptr;
-    DR_HIP(hipMalloc(&da, n * 8)); DR_HIP(hipMalloc(&db, n * 8)); DR_HIP(hipMalloc(&dout, n * 8));
-    DR_HIP(hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice));
-    DR_HIP(hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_test_combine, dim3(2048), dim3(256), 0, int_stream_, da, db, dout, n, max_weight);
+    DeviceBuf<Voxel> da, db, dout;
+    da.reserve(n, int_stream_); db.reserve(n, int_stream_); dout.reserve(n, int_stream_);
+    DR_HIP(hipMemcpy(da.get(), a, n * 8, hipMemcpyHostToDevice));
+    DR_HIP(hipMemcpy(db.get(), b, n * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_test_combine, dim3(2048), dim3(256), 0, int_stream_, da.get(), db.get(), dout.get(), n, max_weight);
     DR_HIP(hipStreamSynchronize(int_stream_));
-    DR_HIP(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
-    DR_HIP(hipFree(da)); DR_HIP(hipFree(db)); DR_HIP(hipFree(dout));
+    DR_HIP(hipMemcpy(out, dout.get(), n * 8, hipMemcpyDeviceToHost));
   }
   // ---- marching cubes: TsdfVolume::ExtractMeshAsync / GetMeshSync (tsdf_volume.cu:759-838) ----
   void extract_mesh_async(const float *lower, const float *upper) {
@@ -1550,8 +1439,7 @@ class FusionEngine {
     if (!num || !vert || !cols) fail(DR_ERR_ARG, "GetMeshSync: null argument");
     const size_t ntri = mesh_num_triangles();
     if (num_max < 3 * ntri) fail(DR_ERR_CAPACITY, "Did not provide enough storage for mesh (%zu vertices > %zu).", 3 * ntri, num_max);
-    DR_HIP(hipMemcpy(vert, mesh_vert_, ntri * 36, hipMemcpyDeviceToHost));
-    DR_HIP(hipMemcpy(cols, mesh_cols_, ntri * 36, hipMemcpyDeviceToHost));
+    fetch_mesh(ntri, vert, cols);
     *num = 3 * ntri;  // 1 triangle = 3 vert (tsdf_volume.cu:800)
     mesh_pending_ = false;
   }
@@ -1563,8 +1451,7 @@ class FusionEngine {
     launch_extraction(lower, upper);
     const size_t ntri = finish_mesh();
     std::vector<float> v(ntri * 9), c(ntri * 9);
-    DR_HIP(hipMemcpy(v.data(), mesh_vert_, ntri * 36, hipMemcpyDeviceToHost));
-    DR_HIP(hipMemcpy(c.data(), mesh_cols_, ntri * 36, hipMemcpyDeviceToHost));
+    fetch_mesh(ntri, v.data(), c.data());
     FILE *f = fopen(filename, "w");
     if (!f) fail(DR_ERR_IO, "SaveMeshToFile: cannot open %s", filename);
     for (size_t i = 0; i < ntri * 3; ++i)
@@ -1592,16 +1479,16 @@ class FusionEngine {
     settle();  // in either scope: what the host store holds decides below
     if (mesh_scope_ == DRF_MESH_RESIDENT && !store_.empty())
       fail(DR_ERR_PROTOCOL, "drf_extract_mesh_update_async: %zu blocks are in the host store; the resident view changes by eviction, which an update does not track (use DRF_MESH_MAP)", store_.size());
-    unsigned long long redirects = 0;  // a round-trip mismatch writes a block that is not on the visible list (k_integrate)
-    DR_HIP(hipMemcpy(&redirects, d_.cnt + 2, 8, hipMemcpyDeviceToHost));
-    float box[6];
-    memcpy(box, lower, 12); memcpy(box + 3, upper, 12);
-    const bool full = !mu_valid_ || mu_force_full_ || mu_overflow_ || memcmp(box, mu_box_, 24) != 0 || redirects != mu_redirects_;
-    if (store_.empty()) launch_mesh_update(lower, upper, full);
-    else launch_mesh_map(lower, upper, true, full);
+    MeshUpdate next;
+    next.valid = true;
+    // a round-trip mismatch writes a block that is not on the visible list (k_integrate)
+    DR_HIP(hipMemcpy(&next.redirects, d_.cnt + 2, 8, hipMemcpyDeviceToHost));
+    memcpy(next.box, lower, 12); memcpy(next.box + 3, upper, 12);
+    next.full = !mu_base_.valid || mu_force_full_ || mu_overflow_ || memcmp(next.box, mu_base_.box, 24) != 0 || next.redirects != mu_base_.redirects;
+    mu_next_ = next;  // (before the launch, which may throw: mu_next_ is read only while mesh_pending_update_ is set)
+    if (store_.empty()) launch_mesh_update(lower, upper);
+    else launch_mesh_map(lower, upper, true);
     // launched: the scans recorded so far belong to this update, later ones to the next
-    memcpy(mu_l_box_, box, 24);
-    mu_l_full_ = full; mu_l_redirects_ = redirects;
     mu_force_full_ = false; mu_overflow_ = false;
     mu_poses_.clear();
     mesh_pending_ = mesh_pending_update_ = true;
@@ -1609,27 +1496,23 @@ class FusionEngine {
   void mesh_update_size(size_t *nblk, size_t *ntri, int *full) {
     if (!nblk || !ntri || !full) fail(DR_ERR_ARG, "drf_mesh_update_size: null argument");
     if (!mesh_pending_ || !mesh_pending_update_) fail(DR_ERR_PROTOCOL, "drf_mesh_update_size: no mesh update is pending");
-    *ntri = finish_mesh(); *nblk = mu_l_nblk_; *full = mu_l_full_ ? 1 : 0;
+    *ntri = finish_mesh(); *nblk = mu_next_.nblk; *full = mu_next_.full ? 1 : 0;
   }
   void get_mesh_update_sync(size_t max_blocks, size_t num_max, size_t *nblk, int32_t *coords, uint64_t *first, size_t *num, float *vert,
                             float *cols, int *full) {
     if (!nblk || !coords || !first || !num || !vert || !cols || !full) fail(DR_ERR_ARG, "drf_get_mesh_update_sync: null argument");
     if (!mesh_pending_ || !mesh_pending_update_) fail(DR_ERR_PROTOCOL, "drf_get_mesh_update_sync: no mesh update is pending");
-    const size_t ntri = finish_mesh(), nb = mu_l_nblk_;
+    const size_t ntri = finish_mesh(), nb = mu_next_.nblk;
     if (max_blocks < nb) fail(DR_ERR_CAPACITY, "Did not provide enough storage for the patch table (%zu blocks > %zu).", nb, max_blocks);
     if (num_max < 3 * ntri) fail(DR_ERR_CAPACITY, "Did not provide enough storage for mesh (%zu vertices > %zu).", 3 * ntri, num_max);
     first[0] = 0;
     if (nb > 0) {
-      DR_HIP(hipMemcpy(coords, mu_coords_, nb * 12, hipMemcpyDeviceToHost));
-      DR_HIP(hipMemcpy(first, mu_first_, (nb + 1) * 8, hipMemcpyDeviceToHost));
-      DR_HIP(hipMemcpy(vert, mesh_vert_, ntri * 36, hipMemcpyDeviceToHost));
-      DR_HIP(hipMemcpy(cols, mesh_cols_, ntri * 36, hipMemcpyDeviceToHost));
+      DR_HIP(hipMemcpy(coords, mu_coords_.get(), nb * 12, hipMemcpyDeviceToHost));
+      DR_HIP(hipMemcpy(first, mu_first_.get(), (nb + 1) * 8, hipMemcpyDeviceToHost));
+      fetch_mesh(ntri, vert, cols);
     }
-    *nblk = nb; *num = 3 * ntri; *full = mu_l_full_ ? 1 : 0;
-    // the baseline advances: this box, the voxel state at the launch
-    memcpy(mu_box_, mu_l_box_, 24);
-    mu_redirects_ = mu_l_redirects_;
-    mu_valid_ = true;
+    *nblk = nb; *num = 3 * ntri; *full = mu_next_.full ? 1 : 0;
+    mu_base_ = mu_next_;  // the baseline advances: this box, the voxel state at the launch
     mesh_pending_ = mesh_pending_update_ = false;
   }
   void mesh_update_reset() { mu_force_full_ = true; }
@@ -1644,12 +1527,7 @@ class FusionEngine {
     DR_HIP(hipSetDevice(device_));
     if (st_radius_ > 0.0f) {  // the depths are on the device: bound the scan by max_sensor_depth
       if (!d_bgr || !d_depth || !pose16) fail(DR_ERR_ARG, "drf_integrate_device: null argument");
-      DR_HIP(hipEventSynchronize(int_done_));
-      stream_before_scan(pose16, o_.max_sensor_depth);
-      enqueue_scan((const unsigned char *)d_bgr, (const float *)d_depth, pose16);
-      stream_after_scan(pose16);
-      DR_HIP(hipEventRecord(int_done_, int_stream_));
-      return;
+      return scan_between_streaming(pose16, o_.max_sensor_depth, [&] { enqueue_scan((const unsigned char *)d_bgr, (const float *)d_depth, pose16); });
     }
     if (!store_.empty()) fail(DR_ERR_PROTOCOL, "drf_integrate_device: blocks are in the host store while streaming is off");
     enqueue_scan((const unsigned char *)d_bgr, (const float *)d_depth, pose16);
@@ -1746,9 +1624,10 @@ class FusionEngine {
     if (radius > 0.0f) ensure_staging();
     st_radius_ = radius;
     st_host_cap_ = host_capacity_blocks ? host_capacity_blocks : (size_t)-1;
-    reach_.clear();
+    reach_.reset();
     // blocks integrated before now are bounded by nothing the host knows: the first scan runs the selection pass
-    if (radius > 0.0f) reach_.push_back({0.0, 0.0, 0.0, HUGE_VAL});
+    const double origin[3] = {0.0, 0.0, 0.0};
+    if (radius > 0.0f) reach_.push(origin, HUGE_VAL);
   }
   void stream_out_region(const float *lower, const float *upper) {
     if (!lower || !upper) fail(DR_ERR_ARG, "drf_stream_out_region: null argument");
@@ -1792,15 +1671,13 @@ class FusionEngine {
     if (st_radius_ > 0.0f) {  // the ball around the uploaded centres bounds them for the selection skip
       double c[3], r = 0.0;
       for (int a = 0; a < 3; ++a) { c[a] = 0.5 * (bl[a] + bh[a]); r += (bh[a] - bl[a]) * (bh[a] - bl[a]); }
-      reach_.push_back({c[0], c[1], c[2], 0.5 * std::sqrt(r) + o_.voxel_size});
+      reach_.push(c, 0.5 * std::sqrt(r) + o_.voxel_size);
     }
   }
   // out: resident blocks, blocks in the host store, blocks streamed out / in (totals), bytes moved, last scan's streaming time (us)
   void streaming_stats(uint64_t out[6]) {
     settle();
-    int na = 0;
-    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
-    out[0] = (uint64_t)std::min(na, o_.num_blocks); out[1] = store_.size(); out[2] = st_out_total_; out[3] = st_in_total_;
+    out[0] = (uint64_t)pool_blocks(); out[1] = store_.size(); out[2] = st_out_total_; out[3] = st_in_total_;
     out[4] = 4096 * (st_out_total_ + st_in_total_); out[5] = (uint64_t)std::llround(st_last_us_);
   }
   void export_host_blocks(int max_blocks, int32_t *coords, uint8_t *voxels, int *n) {
@@ -1820,6 +1697,11 @@ class FusionEngine {
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
   size_t host_free() const { return st_host_cap_ - std::min(st_host_cap_, store_.size()); }
+  int pool_blocks() {  // blocks in the pool; the count lives on the device
+    int na = 0;
+    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
+    return std::min(na, o_.num_blocks);
+  }
   // every pending eviction folded into the host store, the device idle
   void settle() {
     DR_HIP(hipSetDevice(device_));
@@ -1829,22 +1711,18 @@ class FusionEngine {
   void ensure_staging() {
     if (st_cap_) return;
     st_cap_ = std::min(o_.num_blocks, kStageBlocks);
-    sd_.ctl = dalloc<int>(8);
+    sd_.ctl = own_.device<int>(8);
     DR_HIP(hipMemset(sd_.ctl, 0, 32));
-    sd_.list = dalloc<int>(st_cap_);
-    sd_.mv_dst = dalloc<int>(st_cap_);
-    sd_.mv_src = dalloc<int>(st_cap_);
-    DR_HIP(hipHostMalloc((void **)&h_ev_keys_, (size_t)st_cap_ * 8, hipHostMallocDefault));
-    DR_HIP(hipHostMalloc((void **)&h_ev_vox_, (size_t)st_cap_ * 4096, hipHostMallocDefault));
-    DR_HIP(hipHostMalloc((void **)&sd_.h_out, 16, hipHostMallocDefault));  // 4 ints
+    sd_.list = own_.device<int>(st_cap_);
+    sd_.mv_dst = own_.device<int>(st_cap_);
+    sd_.mv_src = own_.device<int>(st_cap_);
+    h_ev_keys_ = own_.pinned<unsigned long long>(st_cap_, &sd_.h_keys);
+    h_ev_vox_ = (uint8_t *)own_.pinned<uint4>((size_t)st_cap_ * 256, &sd_.h_vox);
+    sd_.h_out = own_.pinned<int>(4);
     memset(sd_.h_out, 0, 16);
-    DR_HIP(hipHostGetDevicePointer((void **)&sd_.h_keys, h_ev_keys_, 0));
-    DR_HIP(hipHostGetDevicePointer((void **)&sd_.h_vox, h_ev_vox_, 0));
-    DR_HIP(hipHostMalloc((void **)&h_in_keys_, (size_t)st_cap_ * 8, hipHostMallocDefault));
-    DR_HIP(hipHostMalloc((void **)&h_in_vox_, (size_t)st_cap_ * 4096, hipHostMallocDefault));
-    DR_HIP(hipHostGetDevicePointer((void **)&hd_in_keys_, h_in_keys_, 0));
-    DR_HIP(hipHostGetDevicePointer((void **)&hd_in_vox_, h_in_vox_, 0));
-    for (auto &e : st_ev_) DR_HIP(hipEventCreate(&e));
+    h_in_keys_ = own_.pinned<unsigned long long>(st_cap_, &hd_in_keys_);
+    h_in_vox_ = own_.pinned<uint8_t>((size_t)st_cap_ * 4096, &hd_in_vox_);
+    for (auto &e : st_ev_) e = own_.event(hipEventDefault);
   }
   // Enqueue the eviction chain on int_stream_ behind every render stream's last ray-cast (blocks move).  box = 0: blocks whose
   // centre lies beyond sqrt(r2) of p; box = 1: blocks whose origin lies in [lo, hi].  cap = 0 only counts (sd_.h_out[1]).
@@ -1887,7 +1765,8 @@ class FusionEngine {
       float kept2;
       memcpy(&kept2, &sd_.h_out[3], 4);
       const double r = std::min((double)st_radius_ + hysteresis(), std::sqrt((double)kept2) + o_.voxel_size);
-      reach_.assign(1, {ev_p_[0], ev_p_[1], ev_p_[2], r});
+      reach_.reset();
+      reach_.push(ev_p_, r);
     }
     ev_auto_ = false;
   }
@@ -1895,9 +1774,7 @@ class FusionEngine {
   // if they do not fit.
   void upload(const std::vector<unsigned long long> &keys) {
     ensure_staging();
-    int na = 0;
-    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
-    na = std::min(na, o_.num_blocks);
+    const int na = pool_blocks();
     if ((size_t)na + keys.size() > (size_t)o_.num_blocks)
       fail(DR_ERR_CAPACITY, "stream-in of %zu blocks does not fit in the pool (%d of num_blocks=%d in use)", keys.size(), na, o_.num_blocks);
     for (auto &r : renders_) DR_HIP(hipStreamWaitEvent(int_stream_, r.cast, 0));
@@ -1916,30 +1793,13 @@ class FusionEngine {
     st_in_total_ += keys.size();
   }
   double hysteresis() const { return (double)kBS * o_.voxel_size; }  // one block edge
-  // the scan's largest valid depth bounds what it touches (stream_reach); eight branch-free running maxima so that the host
-  // compiler vectorises the pass over the image
-  float max_valid_depth(const float *depth) const {
-    const float lo = o_.min_sensor_depth, hi = o_.max_sensor_depth;
-    float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, r = 0.f;
-    size_t i = 0;
-    for (; i + 8 <= npix_; i += 8)
-      for (int k = 0; k < 8; ++k) {
-        const float z = depth[i + k], v = (z >= lo && z <= hi) ? z : 0.f;
-        m[k] = v > m[k] ? v : m[k];
-      }
-    for (; i < npix_; ++i) {
-      const float z = depth[i];
-      if (z >= lo && z <= hi && z > r) r = z;
-    }
-    for (int k = 0; k < 8; ++k) r = m[k] > r ? m[k] : r;
-    return r;
-  }
   // Automatic mode, before k_allocate: fold the previous scan's evictions, bring back every stored block whose centre lies
   // within the radius of this scan's camera centre.  No launch and no wait when nothing comes in.
   void stream_before_scan(const float *pose16, float depth_bound) {
     DR_HIP(hipStreamSynchronize(int_stream_));
     fold_evicted();
-    const double p[3] = {pose16[3], pose16[7], pose16[11]};
+    double p[3];
+    camera_centre(pose16, p);
     std::vector<unsigned long long> in;
     store_.query_sphere(p, st_radius_, o_.voxel_size, in);
     double r = stream_reach(o_, depth_bound);
@@ -1950,42 +1810,25 @@ class FusionEngine {
       st_timed_ |= 1;
       r = std::max(r, (double)st_radius_);
     }
-    add_reach(p, r);
+    reach_.add(p, r);
   }
   // After the scan: select resident blocks beyond radius + hysteresis, unless the host can tell that there are none -- every
-  // block centre lies within reach_[j].r of some reach_[j].p, so if max_j |p - p_j| + r_j <= radius + hysteresis nothing is launched.
+  // block centre lies in one of the reach balls, so if none of them reaches beyond radius + hysteresis of p nothing is launched.
   void stream_after_scan(const float *pose16) {
-    const double p[3] = {pose16[3], pose16[7], pose16[11]};
+    double p[3];
+    camera_centre(pose16, p);
     const double lim = (double)st_radius_ + hysteresis();
-    double far = 0.0;
-    for (auto &b : reach_) far = std::max(far, std::sqrt((p[0] - b[0]) * (p[0] - b[0]) + (p[1] - b[1]) * (p[1] - b[1]) + (p[2] - b[2]) * (p[2] - b[2])) + b[3]);
     const int cap = (int)std::min((size_t)st_cap_, host_free());
     st_scan_done_ = true;
-    if (far <= lim || cap == 0) return;
-    F3 pf; pf.x = pose16[3]; pf.y = pose16[7]; pf.z = pose16[11];
+    if (reach_.farthest(p) <= lim || cap == 0) return;
+    F3 pf; pf.x = (float)p[0]; pf.y = (float)p[1]; pf.z = (float)p[2];
     const float r2 = (float)(lim * lim);
     DR_HIP(hipEventRecord(st_ev_[2], int_stream_));
     launch_eviction(pf, r2, pf, pf, 0, cap);
     DR_HIP(hipEventRecord(st_ev_[3], int_stream_));
     st_timed_ |= 2;
     ev_auto_ = true;
-    ev_p_[0] = p[0]; ev_p_[1] = p[1]; ev_p_[2] = p[2];
-  }
-  // reach_: balls that hold every block centre of the map; a new ball drops the ones it contains, and a long list collapses into
-  // one ball around the newest centre
-  void add_reach(const double p[3], double r) {
-    std::vector<std::array<double, 4>> keep;
-    for (auto &b : reach_) {
-      const double d = std::sqrt((p[0] - b[0]) * (p[0] - b[0]) + (p[1] - b[1]) * (p[1] - b[1]) + (p[2] - b[2]) * (p[2] - b[2]));
-      if (d + b[3] > r) keep.push_back(b);
-    }
-    keep.push_back({p[0], p[1], p[2], r});
-    if (keep.size() > 256) {
-      double R = 0.0;
-      for (auto &b : keep) R = std::max(R, std::sqrt((p[0] - b[0]) * (p[0] - b[0]) + (p[1] - b[1]) * (p[1] - b[1]) + (p[2] - b[2]) * (p[2] - b[2])) + b[3]);
-      keep.assign(1, {p[0], p[1], p[2], R});
-    }
-    reach_.swap(keep);
+    memcpy(ev_p_, p, sizeof p);
   }
   void expect(Next want, const char *msg) {
     static const char *names[] = {"IntegrateScanAsync", "RenderAsync", "GetRenderResult"};
@@ -2014,56 +1857,72 @@ class FusionEngine {
     hipLaunchKernelGGL(k_fold_counter, dim3(1), dim3(256), 0, int_stream_, d_.cnt, d_.req_count, d_.wg_upd, integrate_grid_);
     DR_HIP(hipGetLastError());
   }
-  static int f2i_host(float f) {  // make_int3(float...) on CUDA: cvt.rzi (saturating, NaN -> 0)
-    if (f != f) return 0;
-    if (f >= 2147483648.0f) return 2147483647;
-    if (f <= -2147483648.0f) return -2147483647 - 1;
-    return (int)f;
-  }
-  // Lattice cells per axis (ExtractMeshKernel, mesh_extractor.cu:241-245); returns the axis table length.
-  size_t mesh_lattice(const float *lower, const float *upper, int n[3]) {
-    const float vs = o_.voxel_size;
-    size_t ntab = 0;
-    for (int a = 0; a < 3; ++a) {
-      n[a] = f2i_host(fabsf(lower[a] - upper[a]) / vs);
-      if (n[a] > (1 << 22)) fail(DR_ERR_ARG, "ExtractMesh: %d lattice cells along axis %d (box too large for voxel_size %g)", n[a], a, vs);
-      ntab += (size_t)std::max(n[a], 0);
-    }
-    if (!mesh_total_) mesh_total_ = dalloc<unsigned long long>(1);
-    return ntab;
-  }
+  // ---- the mesh pass, shared by every extraction ----
   void mesh_empty() {
     DR_HIP(hipMemsetAsync(mesh_total_, 0, 8, int_stream_));
     DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
   }
-  // the axis tables, the per-block arrays and the 20 M-triangle output (allocated with the first extraction), then k_mc_axes
-  void mesh_prepare(const float *lower, const int n[3], size_t ntab, McArgs &a) {
-    if (ntab > mesh_axis_cap_) {
-      if (mesh_axis_) DR_HIP(hipFree(mesh_axis_));
-      mesh_axis_ = dalloc<McAxis>(ntab);
-      mesh_axis_cap_ = ntab;
+  // Prologue of every extraction (int_stream_ idle): the lattice into a.n, the statistics cleared; returns the pool's block count.
+  // Nothing is launched yet: the caller enqueues the empty result (mesh_empty) or goes on with mesh_tables.
+  int mesh_begin(const float *lower, const float *upper, McArgs &a) {
+    for (int k = 0; k < 3; ++k) {  // lattice cells per axis (ExtractMeshKernel, mesh_extractor.cu:241-245)
+      a.n[k] = f2i_host(fabsf(lower[k] - upper[k]) / o_.voxel_size);
+      if (a.n[k] > (1 << 22))
+        fail(DR_ERR_ARG, "ExtractMesh: %d lattice cells along axis %d (box too large for voxel_size %g)", a.n[k], k, o_.voxel_size);
     }
+    if (!mesh_total_) mesh_total_ = own_.device<unsigned long long>(1);
+    mesh_stats_[0] = mesh_stats_[1] = mesh_stats_[2] = 0;
+    return pool_blocks();
+  }
+  static bool box_empty(const McArgs &a) { return a.n[0] <= 0 || a.n[1] <= 0 || a.n[2] <= 0; }
+  // The axis tables, the per-block arrays and the 20 M-triangle output (allocated with the first extraction), then k_mc_axes and
+  // the pool's nblk keys sorted into mesh_keys_.  The box is not empty.
+  void mesh_tables(const float *lower, McArgs &a, int nblk) {
+    const float vs = o_.voxel_size;
+    mesh_axis_.reserve((size_t)a.n[0] + a.n[1] + a.n[2], int_stream_);
     if (!mesh_keys_) {
-      mesh_keys_ = dalloc<unsigned long long>(o_.num_blocks);
-      mesh_counts_ = dalloc<unsigned>(o_.num_blocks);
-      mesh_offsets_ = dalloc<unsigned>(o_.num_blocks);
+      mesh_keys_ = own_.device<unsigned long long>(o_.num_blocks);
+      mesh_counts_ = own_.device<unsigned>(o_.num_blocks);
+      mesh_offsets_ = own_.device<unsigned>(o_.num_blocks);
       size_t t1 = 0, t2 = 0;
       DR_HIP(rocprim::radix_sort_keys(nullptr, t1, d_.blk_key, mesh_keys_, (size_t)o_.num_blocks, 0, 63, int_stream_));
       DR_HIP(rocprim::exclusive_scan(nullptr, t2, mesh_counts_, mesh_offsets_, 0u, (size_t)o_.num_blocks, rocprim::plus<unsigned>(), int_stream_));
-      mesh_tmp_bytes_ = std::max(t1, t2);
-      mesh_tmp_ = dalloc<unsigned char>(mesh_tmp_bytes_);
+      mesh_tmp_.reserve(std::max(t1, t2), int_stream_);
       // the reference's MeshExtractor::Init(20000000, ...) (tsdf_volume.cu:776): 72 B per triangle, 1.44 GB of HBM
-      mesh_vert_ = dalloc<float>((size_t)kMeshMaxTriangles * 9);
-      mesh_cols_ = dalloc<float>((size_t)kMeshMaxTriangles * 9);
+      mesh_vert_ = own_.device<float>((size_t)kMeshMaxTriangles * 9);
+      mesh_cols_ = own_.device<float>((size_t)kMeshMaxTriangles * 9);
     }
-    McAxis *p = mesh_axis_;
+    McAxis *p = mesh_axis_.get();
     for (int k = 0; k < 3; ++k) {
-      hipLaunchKernelGGL(k_mc_axes, dim3(cdiv(n[k], 256)), dim3(256), 0, int_stream_, p, n[k], lower[k], o_.voxel_size);
-      a.ax[k] = p; a.n[k] = n[k];
-      p += n[k];
+      hipLaunchKernelGGL(k_mc_axes, dim3(cdiv(a.n[k], 256)), dim3(256), 0, int_stream_, p, a.n[k], lower[k], vs);
+      a.ax[k] = p;
+      p += a.n[k];
     }
     a.counts = mesh_counts_; a.offsets = mesh_offsets_;
     a.vert = mesh_vert_; a.cols = mesh_cols_; a.cap_tri = kMeshMaxTriangles;
+    size_t tb = mesh_tmp_.capacity();
+    if (nblk > 0) DR_HIP(rocprim::radix_sort_keys(mesh_tmp_.get(), tb, d_.blk_key, mesh_keys_, (size_t)nblk, 0, 63, int_stream_));
+  }
+  // Count, scan, emit for the blocks a.sorted_keys[0, a.nblk).  Resident form: the result is these triangles (k_mc_total).
+  // STAGED (one chunk of the map pass): emitted at the running total a.base, which then advances.
+  // table: rows [row0, row0 + a.nblk) of the mesh update's patch table.
+  template <bool STAGED> void mesh_pass(const McArgs &a, bool table, size_t row0 = 0) {
+    const dim3 grid((unsigned)a.nblk), block(256);
+    hipLaunchKernelGGL((k_mc_cells<false, STAGED>), grid, block, 0, int_stream_, d_, a);
+    size_t tb = mesh_tmp_.capacity();
+    DR_HIP(rocprim::exclusive_scan(mesh_tmp_.get(), tb, mesh_counts_, mesh_offsets_, 0u, (size_t)a.nblk, rocprim::plus<unsigned>(), int_stream_));
+    hipLaunchKernelGGL((k_mc_cells<true, STAGED>), grid, block, 0, int_stream_, d_, a);
+    if (!STAGED) hipLaunchKernelGGL(k_mc_total, dim3(1), dim3(1), 0, int_stream_, mesh_counts_, mesh_offsets_, a.nblk, mesh_total_);
+    if (table)
+      hipLaunchKernelGGL(k_mu_table, dim3(cdiv(a.nblk + 1, 256)), dim3(256), 0, int_stream_, a.sorted_keys, a.nblk, mesh_counts_, mesh_offsets_,
+                         a.base, row0, mu_coords_.get(), mu_first_.get());
+    if (STAGED) hipLaunchKernelGGL(k_mc_advance, dim3(1), dim3(1), 0, int_stream_, mesh_counts_, mesh_offsets_, a.nblk, mesh_total_);
+  }
+  // the extraction is enqueued: blocks meshed, host blocks uploaded (once per chunk that stages them), chunks
+  void mesh_end(size_t blocks, size_t uploads, size_t chunks) {
+    DR_HIP(hipGetLastError());
+    DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
+    mesh_stats_[0] = blocks; mesh_stats_[1] = uploads; mesh_stats_[2] = chunks;
   }
   // DRF_MESH_MAP folds pending evictions first; with an empty host store it is the resident pass
   void launch_extraction(const float *lower, const float *upper) {
@@ -2077,26 +1936,13 @@ class FusionEngine {
   void launch_mesh(const float *lower, const float *upper) {
     DR_HIP(hipSetDevice(device_));
     DR_HIP(hipStreamSynchronize(int_stream_));  // the block count lives on the device
-    int na = 0;
-    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
-    const int nblk = std::min(na, o_.num_blocks);
-    int n[3];
-    const size_t ntab = mesh_lattice(lower, upper, n);
-    mesh_stats_[0] = mesh_stats_[1] = mesh_stats_[2] = 0;
-    if (nblk <= 0 || n[0] <= 0 || n[1] <= 0 || n[2] <= 0) return mesh_empty();
     McArgs a{};
-    mesh_prepare(lower, n, ntab, a);
-    size_t tb = mesh_tmp_bytes_;
-    DR_HIP(rocprim::radix_sort_keys(mesh_tmp_, tb, d_.blk_key, mesh_keys_, (size_t)nblk, 0, 63, int_stream_));
+    const int nblk = mesh_begin(lower, upper, a);
+    if (box_empty(a) || nblk <= 0) return mesh_empty();
+    mesh_tables(lower, a, nblk);
     a.sorted_keys = mesh_keys_; a.nblk = nblk;
-    hipLaunchKernelGGL((k_mc_cells<false>), dim3(nblk), dim3(256), 0, int_stream_, d_, a);
-    tb = mesh_tmp_bytes_;
-    DR_HIP(rocprim::exclusive_scan(mesh_tmp_, tb, mesh_counts_, mesh_offsets_, 0u, (size_t)nblk, rocprim::plus<unsigned>(), int_stream_));
-    hipLaunchKernelGGL((k_mc_cells<true>), dim3(nblk), dim3(256), 0, int_stream_, d_, a);
-    hipLaunchKernelGGL(k_mc_total, dim3(1), dim3(1), 0, int_stream_, mesh_counts_, mesh_offsets_, nblk, mesh_total_);
-    DR_HIP(hipGetLastError());
-    DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
-    mesh_stats_[0] = (uint64_t)nblk; mesh_stats_[2] = 1;
+    mesh_pass<false>(a, false);
+    mesh_end((size_t)nblk, 0, 1);
   }
   // ---- mesh update: selection and the resident form ----
   // every entry point that integrates comes through enqueue_scan.  A pose that is not a finite rigid motion (the reach bound
@@ -2114,223 +1960,107 @@ class FusionEngine {
     memcpy(p.m, Ti.m, 48);
     mu_poses_.push_back(p);
   }
-  // scan scratch for n items (the mesh path's is sized for the pool; a map's scope may be longer)
-  void mesh_tmp_reserve(size_t n) {
-    size_t t = 0;
-    DR_HIP(rocprim::exclusive_scan(nullptr, t, mesh_counts_, mesh_offsets_, 0u, n, rocprim::plus<unsigned>(), int_stream_));
-    if (t <= mesh_tmp_bytes_) return;
-    DR_HIP(hipStreamSynchronize(int_stream_));
-    DR_HIP(hipFree(mesh_tmp_));
-    mesh_tmp_ = nullptr;
-    mesh_tmp_ = dalloc<unsigned char>(t);
-    mesh_tmp_bytes_ = t;
-  }
-  template <class T> void mu_grow(T *&p, size_t &cap, size_t n) {
-    if (n <= cap) return;
-    DR_HIP(hipStreamSynchronize(int_stream_));
-    if (p) DR_HIP(hipFree(p));
-    p = nullptr; cap = 0;
-    p = dalloc<T>(n);
-    cap = n;
-  }
   // Blocks of keys[0, n) (device, ascending) to mesh again after the recorded scans, compacted in order into mu_sel_; returns
   // their number (one 4-byte read back: the mesh kernels' grid).
   int mu_select(const unsigned long long *keys, int n) {
-    mu_grow(mu_flags_, mu_flags_cap_, (size_t)n);
-    mu_grow(mu_pos_, mu_pos_cap_, (size_t)n);
-    mu_grow(mu_sel_, mu_sel_cap_, (size_t)n);
-    if (!mu_nsel_) mu_nsel_ = dalloc<int>(1);
-    mesh_tmp_reserve((size_t)n);
+    mu_flags_.reserve((size_t)n, int_stream_); mu_pos_.reserve((size_t)n, int_stream_); mu_sel_.reserve((size_t)n, int_stream_);
+    if (!mu_nsel_) mu_nsel_ = own_.device<int>(1);
+    size_t tb = 0;  // scan scratch for n items (the mesh path's is sized for the pool; a map's scope may be longer)
+    DR_HIP(rocprim::exclusive_scan(nullptr, tb, mesh_counts_, mesh_offsets_, 0u, (size_t)n, rocprim::plus<unsigned>(), int_stream_));
+    mesh_tmp_.reserve(tb, int_stream_);
     MuArgs m{};
-    m.keys = keys; m.n = n; m.nposes = (int)mu_poses_.size(); m.reach2 = mesh_update_reach2(o_); m.flags = mu_flags_;
+    m.keys = keys; m.n = n; m.nposes = (int)mu_poses_.size(); m.reach2 = mesh_update_reach2(o_); m.flags = mu_flags_.get();
     memcpy(m.Ti, mu_poses_.data(), mu_poses_.size() * sizeof(MuPose));
     hipLaunchKernelGGL(k_mu_select, dim3(cdiv(n, 256)), dim3(256), 0, int_stream_, o_, m);
-    size_t tb = mesh_tmp_bytes_;
-    DR_HIP(rocprim::exclusive_scan(mesh_tmp_, tb, mu_flags_, mu_pos_, 0u, (size_t)n, rocprim::plus<unsigned>(), int_stream_));
-    hipLaunchKernelGGL(k_mu_compact, dim3(cdiv(n, 256)), dim3(256), 0, int_stream_, keys, mu_flags_, mu_pos_, n, mu_sel_, mu_nsel_);
+    tb = mesh_tmp_.capacity();
+    DR_HIP(rocprim::exclusive_scan(mesh_tmp_.get(), tb, mu_flags_.get(), mu_pos_.get(), 0u, (size_t)n, rocprim::plus<unsigned>(), int_stream_));
+    hipLaunchKernelGGL(k_mu_compact, dim3(cdiv(n, 256)), dim3(256), 0, int_stream_, keys, mu_flags_.get(), mu_pos_.get(), n, mu_sel_.get(), mu_nsel_);
     DR_HIP(hipGetLastError());
     int nsel = 0;
     DR_HIP(hipMemcpyAsync(&nsel, mu_nsel_, 4, hipMemcpyDeviceToHost, int_stream_));
     DR_HIP(hipStreamSynchronize(int_stream_));
     return std::max(0, std::min(nsel, n));
   }
-  void mu_table_reserve(size_t nblk) {
-    mu_grow(mu_coords_, mu_coords_cap_, 3 * nblk);
-    mu_grow(mu_first_, mu_first_cap_, nblk + 1);
-  }
-  // The resident pass of launch_mesh over the selected blocks only (all of them when full), plus the patch table.
-  void launch_mesh_update(const float *lower, const float *upper, bool full) {
-    int na = 0;
-    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
-    const int nblk = std::min(na, o_.num_blocks);
-    int n[3];
-    const size_t ntab = mesh_lattice(lower, upper, n);
-    mesh_stats_[0] = mesh_stats_[1] = mesh_stats_[2] = 0;
-    mu_stats_[0] = (uint64_t)std::max(nblk, 0); mu_stats_[1] = 0; mu_stats_[2] = mu_poses_.size(); mu_stats_[3] = full;
-    mu_l_nblk_ = 0;
-    if (nblk <= 0 || n[0] <= 0 || n[1] <= 0 || n[2] <= 0 || (!full && mu_poses_.empty())) return mesh_empty();
+  void mu_table_reserve(size_t nblk) { mu_coords_.reserve(3 * nblk, int_stream_); mu_first_.reserve(nblk + 1, int_stream_); }
+  // The resident pass of launch_mesh over the selected blocks only (all of them when mu_next_.full), plus the patch table.
+  void launch_mesh_update(const float *lower, const float *upper) {
     McArgs a{};
-    mesh_prepare(lower, n, ntab, a);
-    size_t tb = mesh_tmp_bytes_;
-    DR_HIP(rocprim::radix_sort_keys(mesh_tmp_, tb, d_.blk_key, mesh_keys_, (size_t)nblk, 0, 63, int_stream_));
-    const unsigned long long *sel = mesh_keys_;
-    int nsel = nblk;
-    if (!full) { nsel = mu_select(mesh_keys_, nblk); sel = mu_sel_; }
-    if (nsel == 0) return mesh_empty();
-    mu_table_reserve((size_t)nsel);
-    a.sorted_keys = sel; a.nblk = nsel;
-    hipLaunchKernelGGL((k_mc_cells<false>), dim3(nsel), dim3(256), 0, int_stream_, d_, a);
-    tb = mesh_tmp_bytes_;
-    DR_HIP(rocprim::exclusive_scan(mesh_tmp_, tb, mesh_counts_, mesh_offsets_, 0u, (size_t)nsel, rocprim::plus<unsigned>(), int_stream_));
-    hipLaunchKernelGGL((k_mc_cells<true>), dim3(nsel), dim3(256), 0, int_stream_, d_, a);
-    hipLaunchKernelGGL(k_mc_total, dim3(1), dim3(1), 0, int_stream_, mesh_counts_, mesh_offsets_, nsel, mesh_total_);
-    hipLaunchKernelGGL(k_mu_table, dim3(cdiv(nsel + 1, 256)), dim3(256), 0, int_stream_, sel, nsel, mesh_counts_, mesh_offsets_,
-                       (const unsigned long long *)nullptr, (size_t)0, mu_coords_, mu_first_);
-    DR_HIP(hipGetLastError());
-    DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
-    mesh_stats_[0] = (uint64_t)nsel; mesh_stats_[2] = 1;
-    mu_stats_[1] = (uint64_t)nsel; mu_l_nblk_ = (size_t)nsel;
+    const int nblk = mesh_begin(lower, upper, a);
+    mu_stats_[0] = (uint64_t)std::max(nblk, 0); mu_stats_[1] = 0; mu_stats_[2] = mu_poses_.size(); mu_stats_[3] = mu_next_.full;
+    if (box_empty(a) || nblk <= 0 || (!mu_next_.full && mu_poses_.empty())) return mesh_empty();
+    mesh_tables(lower, a, nblk);
+    a.sorted_keys = mesh_keys_; a.nblk = nblk;
+    if (!mu_next_.full) { a.nblk = mu_select(mesh_keys_, nblk); a.sorted_keys = mu_sel_.get(); }
+    if (a.nblk == 0) return mesh_empty();
+    mu_table_reserve((size_t)a.nblk);
+    mesh_pass<false>(a, true);
+    mesh_end((size_t)a.nblk, 0, 1);
+    mu_stats_[1] = (uint64_t)a.nblk; mu_next_.nblk = (size_t)a.nblk;
   }
   // ---- the map pass (DRF_MESH_MAP with blocks in the host store; DESIGN.md §7c "Meshing the whole map") ----
   // Global order = ascending key over resident and stored blocks, as the resident pass orders the pool.  The merged list is cut
-  // into chunks; a chunk stages its own stored blocks and every stored block among the 26 neighbours of its blocks (at most
-  // ms_stage_cap() of them), packed with the chunk's keys into pinned memory and copied to one of two device buffers on a copy
-  // stream, so that packing and copying chunk k + 1 overlap the kernels of chunk k.  Per chunk: count pass, scan, emit pass at
-  // the running base (mesh_total_), advance.  Neither the pool nor the host store changes.
+  // into chunks (plan_mesh_chunks); a chunk's keys and the stored blocks it stages are packed into pinned memory and copied to
+  // one of two device buffers on a copy stream, so that packing and copying chunk k + 1 overlap the kernels of chunk k.  Per chunk:
+  // mesh_pass at the running base (mesh_total_).  Neither the pool nor the host store changes.
   int ms_own_cap() const { return std::min(o_.num_blocks, kStageBlocks); }
   int ms_stage_cap() const { return std::max(ms_own_cap(), 27); }  // one block's 27 neighbours always fit
   void ensure_mesh_staging() {
     if (ms_dev_[0]) return;
     ms_bytes_ = (size_t)ms_own_cap() * 8 + (size_t)ms_stage_cap() * (8 + 4096);
-    DR_HIP(hipStreamCreateWithFlags(&ms_copy_stream_, hipStreamNonBlocking));
+    ms_copy_stream_ = own_.stream();
     for (int b = 0; b < 2; ++b) {
-      ms_dev_[b] = dalloc<unsigned char>(ms_bytes_);
-      DR_HIP(hipHostMalloc((void **)&ms_host_[b], ms_bytes_, hipHostMallocDefault));
-      DR_HIP(hipEventCreateWithFlags(&ms_copied_[b], hipEventDisableTiming));
-      DR_HIP(hipEventCreateWithFlags(&ms_used_[b], hipEventDisableTiming));
+      ms_dev_[b] = own_.device<unsigned char>(ms_bytes_);
+      ms_host_[b] = own_.pinned<unsigned char>(ms_bytes_);
+      ms_copied_[b] = own_.event();
+      ms_used_[b] = own_.event();
       DR_HIP(hipEventRecord(ms_copied_[b], ms_copy_stream_));
       DR_HIP(hipEventRecord(ms_used_[b], int_stream_));
     }
   }
   // update: the mesh-update form (drf_extract_mesh_update_async) -- only the blocks the selection kernel keeps (all of the scope
-  // when full) are planned into chunks, staged and meshed, and each chunk adds its rows to the patch table.
-  void launch_mesh_map(const float *lower, const float *upper, bool update = false, bool full = true) {
-    int na = 0;
-    DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
-    const int nblk = std::min(na, o_.num_blocks);
-    int n[3];
-    const size_t ntab = mesh_lattice(lower, upper, n);
-    mesh_stats_[0] = mesh_stats_[1] = mesh_stats_[2] = 0;
-    if (update) {
-      mu_stats_[0] = mu_stats_[1] = 0; mu_stats_[2] = mu_poses_.size(); mu_stats_[3] = full;
-      mu_l_nblk_ = 0;
-    }
-    if (n[0] <= 0 || n[1] <= 0 || n[2] <= 0) return mesh_empty();
+  // when mu_next_.full) are planned into chunks, staged and meshed, and each chunk adds its rows to the patch table.
+  void launch_mesh_map(const float *lower, const float *upper, bool update = false) {
     McArgs a{};
-    mesh_prepare(lower, n, ntab, a);
-    std::vector<unsigned long long> res(nblk), sto;
-    if (nblk > 0) {
-      size_t tb = mesh_tmp_bytes_;
-      DR_HIP(rocprim::radix_sort_keys(mesh_tmp_, tb, d_.blk_key, mesh_keys_, (size_t)nblk, 0, 63, int_stream_));
-      DR_HIP(hipMemcpyAsync(res.data(), mesh_keys_, (size_t)nblk * 8, hipMemcpyDeviceToHost, int_stream_));
-    }
-    sto.reserve(store_.size());
-    store_.for_each([&](unsigned long long k, const uint8_t *) { sto.push_back(k); });
-    std::sort(sto.begin(), sto.end());
-    // blocks that can own cells of the lattice: floor(mc / 8) between those of the first and last cell per axis (k_mc_axes'
-    // expression restated on the host), widened by one block -- the kernel finds the exact range, this only skips the rest
-    int blo[3], bhi[3];
-    for (int k = 0; k < 3; ++k) {
-      int m[2];
-      for (int e = 0; e < 2; ++e) {
-        const float pa = (float)(e ? n[k] - 1 : 0) * o_.voxel_size + lower[k];
-        m[e] = f2i_host(pa / o_.voxel_size + (float)((pa > 0) - (pa < 0)) * 0.5f);
-      }
-      auto fdiv = [](int v) { return v < 0 ? (v - kBS + 1) / kBS : v / kBS; };
-      blo[k] = fdiv(std::min(m[0], m[1])) - 1;
-      bhi[k] = fdiv(std::max(m[0], m[1])) + 1;
-    }
-    auto in_range = [&](unsigned long long key) {
-      int c[3]; unpack_key_host(key, c);
-      return c[0] >= blo[0] && c[0] <= bhi[0] && c[1] >= blo[1] && c[1] <= bhi[1] && c[2] >= blo[2] && c[2] <= bhi[2];
-    };
+    const int nblk = mesh_begin(lower, upper, a);
+    if (update) { mu_stats_[0] = mu_stats_[1] = 0; mu_stats_[2] = mu_poses_.size(); mu_stats_[3] = mu_next_.full; }
+    if (box_empty(a)) return mesh_empty();  // (an empty pool is no reason: the host store holds blocks)
+    mesh_tables(lower, a, nblk);
+    std::vector<unsigned long long> res(std::max(nblk, 0));
+    if (nblk > 0) DR_HIP(hipMemcpyAsync(res.data(), mesh_keys_, (size_t)nblk * 8, hipMemcpyDeviceToHost, int_stream_));
+    const std::vector<unsigned long long> sto = store_.sorted_keys();
+    const BlockRange range = lattice_block_range(lower, a.n, o_.voxel_size);
     DR_HIP(hipStreamSynchronize(int_stream_));
-    // plan: own[] = the chunks' blocks in global order, stg[] = each chunk's staged keys (ascending), chunk c = own[ob[c], ob[c+1]),
-    // stg[sb[c], sb[c+1])
-    const size_t own_cap = (size_t)ms_own_cap(), stage_cap = (size_t)ms_stage_cap();
-    std::vector<unsigned long long> own, stg, cur;
-    std::vector<size_t> ob{0}, sb{0};
-    std::unordered_set<unsigned long long> in_cur;
-    auto close_chunk = [&]() {
-      std::sort(cur.begin(), cur.end());
-      stg.insert(stg.end(), cur.begin(), cur.end());
-      ob.push_back(own.size()); sb.push_back(stg.size());
-      cur.clear(); in_cur.clear();
-    };
     // update: the scope is the merged list within the range; the selection kernel runs over it and the survivors come back
     std::vector<unsigned long long> picked;
     if (update) {
-      std::vector<unsigned long long> scope;
-      scope.reserve(res.size() + sto.size());
-      for (size_t i = 0, j = 0; i < res.size() || j < sto.size();) {
-        const bool stored = j < sto.size() && (i >= res.size() || sto[j] < res[i]);
-        const unsigned long long key = stored ? sto[j++] : res[i++];
-        if (in_range(key)) scope.push_back(key);
-      }
-      mu_stats_[0] = scope.size();
-      if (scope.empty() || (!full && mu_poses_.empty())) return mesh_empty();
-      if (scope.size() > (size_t)INT_MAX) fail(DR_ERR_CAPACITY, "mesh update: %zu blocks in scope", scope.size());
-      if (full) picked.swap(scope);
-      else {
-        mu_grow(mu_scope_, mu_scope_cap_, scope.size());
-        DR_HIP(hipMemcpyAsync(mu_scope_, scope.data(), scope.size() * 8, hipMemcpyHostToDevice, int_stream_));
-        const int nsel = mu_select(mu_scope_, (int)scope.size());
+      picked.reserve(res.size() + sto.size());
+      for_each_in_range(res, sto, range, [&](unsigned long long key, bool) { picked.push_back(key); });
+      mu_stats_[0] = picked.size();
+      if (picked.empty() || (!mu_next_.full && mu_poses_.empty())) return mesh_empty();
+      if (picked.size() > (size_t)INT_MAX) fail(DR_ERR_CAPACITY, "mesh update: %zu blocks in scope", picked.size());
+      if (!mu_next_.full) {
+        mu_scope_.reserve(picked.size(), int_stream_);
+        DR_HIP(hipMemcpyAsync(mu_scope_.get(), picked.data(), picked.size() * 8, hipMemcpyHostToDevice, int_stream_));
+        const int nsel = mu_select(mu_scope_.get(), (int)picked.size());
         if (nsel == 0) return mesh_empty();
         picked.resize((size_t)nsel);
-        DR_HIP(hipMemcpy(picked.data(), mu_sel_, (size_t)nsel * 8, hipMemcpyDeviceToHost));
+        DR_HIP(hipMemcpy(picked.data(), mu_sel_.get(), (size_t)nsel * 8, hipMemcpyDeviceToHost));
       }
       mu_table_reserve(picked.size());
     }
-    size_t i = 0, j = 0, pk = 0;
-    unsigned long long need[27];
-    while (i < res.size() || j < sto.size()) {
-      const bool stored = j < sto.size() && (i >= res.size() || sto[j] < res[i]);
-      const unsigned long long key = stored ? sto[j++] : res[i++];
-      if (!in_range(key)) continue;
-      if (update) {  // picked is a subsequence of the merged list
-        if (pk == picked.size() || picked[pk] != key) continue;
-        ++pk;
-      }
-      int c[3]; unpack_key_host(key, c);
-      int nn = 0, fresh = 0;  // stored blocks this block reads / those not staged for the chunk yet
-      for (int k = 0; k < 27; ++k) {
-        const int q[3] = {c[0] + k / 9 - 1, c[1] + (k / 3) % 3 - 1, c[2] + k % 3 - 1};
-        unsigned long long qk;
-        if (k == 13 ? stored : (pack_key_host(q, qk) && store_.contains(qk))) {
-          need[nn++] = k == 13 ? key : qk;
-          fresh += !in_cur.count(need[nn - 1]);
-        }
-      }
-      if (own.size() - ob.back() == own_cap || cur.size() + fresh > stage_cap) {
-        close_chunk();
-      }
-      own.push_back(key);
-      for (int k = 0; k < nn; ++k)
-        if (in_cur.insert(need[k]).second) cur.push_back(need[k]);
-    }
-    if (own.size() > ob.back()) close_chunk();
-    const int nchunk = (int)ob.size() - 1;
+    const MeshPlan plan = plan_mesh_chunks(res, sto, store_, range, (size_t)ms_own_cap(), (size_t)ms_stage_cap(), update ? &picked : nullptr);
     DR_HIP(hipMemsetAsync(mesh_total_, 0, 8, int_stream_));
-    if (nchunk > 0) ensure_mesh_staging();
-    for (int ch = 0; ch < nchunk; ++ch) {
+    if (plan.chunks() > 0) ensure_mesh_staging();
+    a.base = mesh_total_;
+    for (size_t ch = 0; ch < plan.chunks(); ++ch) {
       const int b = ch & 1;
-      const size_t no = ob[ch + 1] - ob[ch], ns = sb[ch + 1] - sb[ch];
+      const size_t no = plan.ob[ch + 1] - plan.ob[ch], ns = plan.sb[ch + 1] - plan.sb[ch];
       DR_HIP(hipEventSynchronize(ms_copied_[b]));  // the copy of chunk ch - 2 has left this pinned buffer
       unsigned char *h = ms_host_[b];
-      memcpy(h, own.data() + ob[ch], no * 8);
-      memcpy(h + no * 8, stg.data() + sb[ch], ns * 8);
+      memcpy(h, plan.own.data() + plan.ob[ch], no * 8);
+      memcpy(h + no * 8, plan.stg.data() + plan.sb[ch], ns * 8);
       unsigned char *hv = h + (no + ns) * 8;
-      for (size_t k = 0; k < ns; ++k) memcpy(hv + k * 4096, store_.get(stg[sb[ch] + k]), 4096);
+      for (size_t k = 0; k < ns; ++k) memcpy(hv + k * 4096, store_.get(plan.stg[plan.sb[ch] + k]), 4096);
       DR_HIP(hipStreamWaitEvent(ms_copy_stream_, ms_used_[b], 0));  // the kernels of chunk ch - 2 have read this device buffer
       DR_HIP(hipMemcpyAsync(ms_dev_[b], h, (no + ns) * 8 + ns * 4096, hipMemcpyHostToDevice, ms_copy_stream_));
       DR_HIP(hipEventRecord(ms_copied_[b], ms_copy_stream_));
@@ -2338,25 +2068,19 @@ class FusionEngine {
       const unsigned long long *dk = (const unsigned long long *)ms_dev_[b];
       a.sorted_keys = dk; a.nblk = (int)no;
       a.st_keys = dk + no; a.st_n = (int)ns; a.st_vox = (const Voxel *)(dk + no + ns);
-      a.base = mesh_total_;
-      hipLaunchKernelGGL((k_mc_cells<false, true>), dim3((unsigned)no), dim3(256), 0, int_stream_, d_, a);
-      size_t tb = mesh_tmp_bytes_;
-      DR_HIP(rocprim::exclusive_scan(mesh_tmp_, tb, mesh_counts_, mesh_offsets_, 0u, no, rocprim::plus<unsigned>(), int_stream_));
-      hipLaunchKernelGGL((k_mc_cells<true, true>), dim3((unsigned)no), dim3(256), 0, int_stream_, d_, a);
-      if (update)
-        hipLaunchKernelGGL(k_mu_table, dim3(cdiv((int)no + 1, 256)), dim3(256), 0, int_stream_, dk, (int)no, mesh_counts_, mesh_offsets_,
-                           (const unsigned long long *)mesh_total_, ob[ch], mu_coords_, mu_first_);
-      hipLaunchKernelGGL(k_mc_advance, dim3(1), dim3(1), 0, int_stream_, mesh_counts_, mesh_offsets_, (int)no, mesh_total_);
+      mesh_pass<true>(a, update, plan.ob[ch]);
       DR_HIP(hipEventRecord(ms_used_[b], int_stream_));
     }
-    DR_HIP(hipGetLastError());
-    DR_HIP(hipEventRecord(mesh_done_ev(), int_stream_));
-    mesh_stats_[0] = own.size(); mesh_stats_[1] = stg.size(); mesh_stats_[2] = (uint64_t)nchunk;
-    if (update) { mu_stats_[1] = own.size(); mu_l_nblk_ = own.size(); }
+    mesh_end(plan.own.size(), plan.stg.size(), plan.chunks());
+    if (update) { mu_stats_[1] = plan.own.size(); mu_next_.nblk = plan.own.size(); }
   }
   hipEvent_t mesh_done_ev() {
-    if (!mesh_done_) DR_HIP(hipEventCreateWithFlags(&mesh_done_, hipEventDisableTiming));
+    if (!mesh_done_) mesh_done_ = own_.event();
     return mesh_done_;
+  }
+  void fetch_mesh(size_t ntri, float *vert, float *cols) {
+    DR_HIP(hipMemcpy(vert, mesh_vert_, ntri * 36, hipMemcpyDeviceToHost));
+    DR_HIP(hipMemcpy(cols, mesh_cols_, ntri * 36, hipMemcpyDeviceToHost));
   }
   size_t finish_mesh() {
     DR_HIP(hipSetDevice(device_));
@@ -2373,7 +2097,9 @@ class FusionEngine {
     d_.vs_rcp = rcp_rn(o_.voxel_size); d_.fx_rcp = rcp_rn(o_.fx); d_.fy_rcp = rcp_rn(o_.fy);
     d_.fast_div = 0;
     if (hook_env("DR_FUSION_IEEE_DIV")) return;
-    unsigned long long *bad = dalloc<unsigned long long>(1), h = 0;
+    DeviceBuf<unsigned long long> counter;  // freed when the check is done
+    counter.reserve(1, int_stream_);
+    unsigned long long *bad = counter.get(), h = 0;
     DR_HIP(hipMemsetAsync(bad, 0, 8, int_stream_));
     const float b[3] = {o_.voxel_size, o_.fx, o_.fy}, y[3] = {d_.vs_rcp, d_.fx_rcp, d_.fy_rcp};
     for (int k = 0; k < 3; ++k)
@@ -2381,7 +2107,6 @@ class FusionEngine {
       else h = 1;
     DR_HIP(hipMemcpyAsync(&fast_div_mismatches_, bad, 8, hipMemcpyDeviceToHost, int_stream_));
     DR_HIP(hipStreamSynchronize(int_stream_));
-    DR_HIP(hipFree(bad));
     fast_div_mismatches_ += h;
     d_.fast_div = fast_div_mismatches_ == 0 ? 1 : 0;
   }
@@ -2398,6 +2123,7 @@ class FusionEngine {
     int *d_flag;  // pixels the fast ray-caster handed to the literal pass
     hipEvent_t done, cast;  // result on the host / ray-cast kernels finished (the volume may be written again)
   };
+  HipOwner own_;  // first: released after every other member
   int device_;
   drf_options_t o_;
   FusionDev d_{};
@@ -2429,28 +2155,30 @@ class FusionEngine {
   static constexpr unsigned kMeshMaxTriangles = 20000000;
   bool mesh_pending_ = false;
   hipEvent_t mesh_done_ = nullptr;
-  McAxis *mesh_axis_ = nullptr;
-  size_t mesh_axis_cap_ = 0, mesh_tmp_bytes_ = 0;
+  DeviceBuf<McAxis> mesh_axis_;
+  DeviceBuf<unsigned char> mesh_tmp_;  // radix sort / scan scratch
   unsigned long long *mesh_keys_ = nullptr, *mesh_total_ = nullptr;
   unsigned *mesh_counts_ = nullptr, *mesh_offsets_ = nullptr;
-  unsigned char *mesh_tmp_ = nullptr;
   float *mesh_vert_ = nullptr, *mesh_cols_ = nullptr;
   int mesh_scope_ = DRF_MESH_RESIDENT;
   uint64_t mesh_stats_[3] = {0, 0, 0};
-  // mesh update (incremental mesh).  Baseline = the last update fetched: its box, the round-trip redirect count at its launch;
-  // mu_poses_ = Ti of the scans since the last update was LAUNCHED (they belong to the next one).  mu_l_* describe the pending
-  // update and become the baseline when it is fetched.  Device scratch grows with the scope.
+  // mesh update (incremental mesh).  mu_base_ = the baseline, i.e. the last update fetched: its box, the round-trip redirect
+  // count at its launch; mu_next_ = the pending update, which becomes the baseline when it is fetched; mu_poses_ = Ti of the
+  // scans since the last update was LAUNCHED (they belong to the next one).  Device scratch grows with the scope.
+  struct MeshUpdate {
+    bool valid = false, full = false;
+    float box[6] = {0, 0, 0, 0, 0, 0};
+    unsigned long long redirects = 0; size_t nblk = 0;  // nblk: rows of its patch table
+  };
   bool mesh_pending_update_ = false;
-  bool mu_valid_ = false, mu_force_full_ = false, mu_overflow_ = false, mu_l_full_ = false;
-  float mu_box_[6] = {0, 0, 0, 0, 0, 0}, mu_l_box_[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long mu_redirects_ = 0, mu_l_redirects_ = 0;
+  bool mu_force_full_ = false, mu_overflow_ = false;
+  MeshUpdate mu_base_, mu_next_;
   std::vector<MuPose> mu_poses_;
-  size_t mu_l_nblk_ = 0;
   uint64_t mu_stats_[4] = {0, 0, 0, 0};
-  unsigned *mu_flags_ = nullptr, *mu_pos_ = nullptr;
-  unsigned long long *mu_sel_ = nullptr, *mu_scope_ = nullptr, *mu_first_ = nullptr;
-  int *mu_nsel_ = nullptr, *mu_coords_ = nullptr;
-  size_t mu_flags_cap_ = 0, mu_pos_cap_ = 0, mu_sel_cap_ = 0, mu_scope_cap_ = 0, mu_first_cap_ = 0, mu_coords_cap_ = 0;
+  DeviceBuf<unsigned> mu_flags_, mu_pos_;
+  DeviceBuf<unsigned long long> mu_sel_, mu_scope_, mu_first_;
+  DeviceBuf<int> mu_coords_;
+  int *mu_nsel_ = nullptr;
   // map pass staging (allocated with the first map-scope extraction that meets a non-empty host store): two pinned / device
   // buffer pairs of ms_bytes_ = own keys + staged keys + staged voxels, a copy stream and the events that order the reuse
   size_t ms_bytes_ = 0;
@@ -2471,7 +2199,7 @@ class FusionEngine {
   double st_last_us_ = 0.0;
   bool ev_pending_ = false, ev_auto_ = false;  // an eviction chain awaits folding; it was the automatic one (centre ev_p_)
   double ev_p_[3] = {0.0, 0.0, 0.0};
-  std::vector<std::array<double, 4>> reach_;  // balls (centre, radius) that hold every block centre of the map
+  ReachBalls reach_;  // balls that hold every block centre of the map
   uint64_t st_out_total_ = 0, st_in_total_ = 0;
 };
 

@@ -1,0 +1,301 @@
+// fusion_host.h -- the host half of DrFusion's map: block keys, streaming reach bounds, the host block store, the reach balls
+// and the planner of the map-scope mesh pass.  No device state and no HIP header: plain C++17, so that all of it runs in the
+// CPU tests (tests/cpp/fusion_host_check.cpp).  The engine (dr_fusion.hip) keeps everything that throws or touches the GPU.
+#pragma once
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <memory>
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+#include "../../include/dr_mi355x.h"
+
+namespace dr {
+
+constexpr int kBS = 8;  // voxel block edge (DrFusionOptions::block_size must be 8, as TANDEM sets it)
+// ---- block key: 21 bits per axis, biased by 2^20, x in the high bits (ascending key = ascending (x, y, z)).  The one host
+// definition; the kernels' pack_key / unpack_key (dr_fusion.hip) stay a device pair on I3 so that the device code is untouched.
+constexpr int kKeyBias = 1 << 20;
+inline unsigned long long pack_biased(long x, long y, long z) {
+  return ((unsigned long long)(x + kKeyBias) << 42) | ((unsigned long long)(y + kKeyBias) << 21) | (unsigned long long)(z + kKeyBias);
+}
+inline void unpack_key_host(unsigned long long k, int c[3]) {
+  c[0] = (int)((k >> 42) & 0x1fffff) - kKeyBias;
+  c[1] = (int)((k >> 21) & 0x1fffff) - kKeyBias;
+  c[2] = (int)(k & 0x1fffff) - kKeyBias;
+}
+inline bool pack_key_host(const int c[3], unsigned long long &k) {
+  for (int a = 0; a < 3; ++a)
+    if (c[a] < -kKeyBias || c[a] >= kKeyBias) return false;
+  k = pack_biased(c[0], c[1], c[2]);
+  return true;
+}
+// the store's spatial index: cells of 8^3 blocks, keyed like blocks
+inline unsigned long long cell_key(unsigned long long key) {
+  int c[3]; unpack_key_host(key, c);
+  return pack_biased(c[0] >> 3, c[1] >> 3, c[2] >> 3);  // arithmetic shift = floor division by 8
+}
+
+inline float blk_origin_host(int c, float vs) { return (float)(c * kBS) * vs; }
+inline double blk_centre_host(int c, float vs) { return ((double)(c * kBS) + 3.5) * vs; }
+inline int f2i_host(float f) {  // make_int3(float...) on CUDA: cvt.rzi (saturating, NaN -> 0)
+  if (f != f) return 0;
+  if (f >= 2147483648.0f) return 2147483647;
+  if (f <= -2147483648.0f) return -2147483647 - 1;
+  return (int)f;
+}
+inline void camera_centre(const float *pose16, double p[3]) { p[0] = pose16[3]; p[1] = pose16[7]; p[2] = pose16[11]; }
+inline double dist3(const double a[3], const double b[3]) {
+  return std::sqrt((a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]));
+}
+
+// Farthest a block centre can lie from the camera centre of a scan whose valid depths do not exceed `depth` and still be
+// read or written by that scan (DESIGN.md "Streaming voxel blocks" derives each term):
+//   allocation DDA  depth*rho + trunc + 4.5*sqrt(3)*vs    (points of the ray up to surf + trunc; block centre within 4.5 sqrt(3) vs)
+//                   12.5*sqrt(3)*vs                       (the start block shifted one block back on negative axes)
+//   voxel update    depth*rho + trunc + 3.5*sqrt(3)*vs    (updated voxels have vd < sd + trunc)
+//   ray-cast        depth*rho + 4.5*sqrt(3)*vs            (samples at cur < max_sensor_depth, trilinear corners within sqrt(3) vs)
+// plus one block diagonal (8 sqrt(3) vs) and one voxel of margin.  rho = the largest |((u - cx)/fx, (v - cy)/fy, 1)| over
+// the image corners.  Evaluated in double.
+inline double corner_rho(const drf_options_t &o) {
+  double rho = 0.0;
+  for (int k = 0; k < 4; ++k) {
+    const double u = (k & 1) ? o.width - 1 : 0, v = (k & 2) ? o.height - 1 : 0;
+    const double a = (u - o.cx) / o.fx, b = (v - o.cy) / o.fy;
+    rho = std::max(rho, std::sqrt(a * a + b * b + 1.0));
+  }
+  return rho;
+}
+inline double stream_reach(const drf_options_t &o, double depth) {
+  const double s3 = std::sqrt(3.0), vs = o.voxel_size;
+  const double rho = corner_rho(o);
+  const double scan = std::max(depth * rho + (double)o.truncation_distance + 4.5 * s3 * vs, 12.5 * s3 * vs);
+  return scan + 8.0 * s3 * vs + vs;
+}
+inline bool stream_options_ok(const drf_options_t &o) {
+  auto pos = [](double x) { return std::isfinite(x) && x > 0.0; };
+  return pos(o.voxel_size) && pos(o.fx) && pos(o.fy) && std::isfinite(o.cx) && std::isfinite(o.cy) && o.width > 0 && o.height > 0 &&
+         pos(o.max_sensor_depth) && std::isfinite(o.truncation_distance) && o.truncation_distance >= 0.0f;
+}
+inline float streaming_min_radius(const drf_options_t &o) { return (float)stream_reach(o, o.max_sensor_depth); }
+// Mesh update: farthest a block ORIGIN can lie from the camera centre of a scan that writes one of its voxels (DESIGN.md
+// "Incremental mesh"): the "voxel update" term above taken at the origin (voxels lie within 7 sqrt(3) vs of it) plus the same
+// block diagonal and voxel of margin.  Options the bound is not defined for leave k_cull's test alone in charge.
+inline float mesh_update_reach2(const drf_options_t &o) {
+  if (!stream_options_ok(o)) return INFINITY;
+  const double s3 = std::sqrt(3.0), vs = o.voxel_size;
+  const double r = (double)o.max_sensor_depth * corner_rho(o) + (double)o.truncation_distance + 7.0 * s3 * vs + 8.0 * s3 * vs + vs;
+  const float r2 = (float)(r * r * (1.0 + 1e-5));
+  return std::isfinite(r2) ? r2 : INFINITY;
+}
+// the scan's largest valid depth bounds what it touches (stream_reach); eight branch-free running maxima so that the host
+// compiler vectorises the pass over the image
+inline float max_valid_depth(const float *depth, size_t npix, float lo, float hi) {
+  float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, r = 0.f;
+  size_t i = 0;
+  for (; i + 8 <= npix; i += 8)
+    for (int k = 0; k < 8; ++k) {
+      const float z = depth[i + k], v = (z >= lo && z <= hi) ? z : 0.f;
+      m[k] = v > m[k] ? v : m[k];
+    }
+  for (; i < npix; ++i) {
+    const float z = depth[i];
+    if (z >= lo && z <= hi && z > r) r = z;
+  }
+  for (int k = 0; k < 8; ++k) r = m[k] > r ? m[k] : r;
+  return r;
+}
+
+// The host half of the map: block key -> 4 KB, in slabs of 1024 blocks, with a coarse spatial index (cells of 8^3 blocks)
+// so that the per-scan "stored blocks within the radius" query visits cells near the camera only.
+class HostBlockStore {
+ public:
+  size_t size() const { return slot_.size(); }
+  bool empty() const { return slot_.empty(); }
+  void put(unsigned long long key, const void *vox) {
+    unsigned s;
+    if (!free_.empty()) { s = free_.back(); free_.pop_back(); }
+    else {
+      s = next_++;
+      if ((s >> kSlabShift) >= slabs_.size()) slabs_.emplace_back(new uint8_t[(size_t)4096 << kSlabShift]);
+    }
+    memcpy(at(s), vox, 4096);
+    slot_[key] = s;
+    cells_[cell_key(key)].push_back(key);
+  }
+  const uint8_t *get(unsigned long long key) const { return at(slot_.at(key)); }
+  bool contains(unsigned long long key) const { return slot_.count(key) != 0; }
+  void erase(unsigned long long key) {  // the key must be there
+    auto it = slot_.find(key);
+    free_.push_back(it->second);
+    slot_.erase(it);
+    auto c = cells_.find(cell_key(key));
+    auto &v = c->second;
+    for (size_t i = 0; i < v.size(); ++i)
+      if (v[i] == key) { v[i] = v.back(); v.pop_back(); break; }
+    if (v.empty()) cells_.erase(c);
+  }
+  template <class F> void for_each(F f) const { for (auto &kv : slot_) f(kv.first, at(kv.second)); }
+  std::vector<unsigned long long> sorted_keys() const {
+    std::vector<unsigned long long> k; k.reserve(slot_.size());
+    for (auto &kv : slot_) k.push_back(kv.first);
+    std::sort(k.begin(), k.end());
+    return k;
+  }
+  // keys of the stored blocks whose streaming centre lies within r of p
+  void query_sphere(const double p[3], double r, float vs, std::vector<unsigned long long> &out) const {
+    if (slot_.empty()) return;
+    const double cell = 64.0 * vs;  // 8 blocks
+    long lo[3], hi[3];
+    double span = 1.0;
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = (long)std::floor((p[a] - r) / cell) - 1;
+      hi[a] = (long)std::floor((p[a] + r) / cell) + 1;
+      span *= (double)(hi[a] - lo[a] + 1);
+    }
+    auto test_cell = [&](const std::vector<unsigned long long> &v) {
+      for (unsigned long long k : v) {
+        int c[3]; unpack_key_host(k, c);
+        const double dx = blk_centre_host(c[0], vs) - p[0], dy = blk_centre_host(c[1], vs) - p[1], dz = blk_centre_host(c[2], vs) - p[2];
+        if (dx * dx + dy * dy + dz * dz <= r * r) out.push_back(k);
+      }
+    };
+    if (span > (double)cells_.size()) {  // fewer occupied cells than cells in range: walk the occupied ones
+      for (auto &kv : cells_) {
+        int c[3]; unpack_key_host(kv.first, c);
+        if (c[0] >= lo[0] && c[0] <= hi[0] && c[1] >= lo[1] && c[1] <= hi[1] && c[2] >= lo[2] && c[2] <= hi[2]) test_cell(kv.second);
+      }
+      return;
+    }
+    for (long x = lo[0]; x <= hi[0]; ++x)
+      for (long y = lo[1]; y <= hi[1]; ++y)
+        for (long z = lo[2]; z <= hi[2]; ++z) {
+          auto it = cells_.find(pack_biased(x, y, z));
+          if (it != cells_.end()) test_cell(it->second);
+        }
+  }
+
+ private:
+  static constexpr int kSlabShift = 10;
+  uint8_t *at(unsigned s) const { return slabs_[s >> kSlabShift].get() + (size_t)(s & ((1u << kSlabShift) - 1)) * 4096; }
+  std::unordered_map<unsigned long long, unsigned> slot_;
+  std::unordered_map<unsigned long long, std::vector<unsigned long long>> cells_;
+  std::vector<std::unique_ptr<uint8_t[]>> slabs_;
+  std::vector<unsigned> free_;
+  unsigned next_ = 0;
+};
+
+// Balls (centre, radius) that together hold every block centre of the map: what lets a scan tell on the host that no resident
+// block can lie beyond the streaming radius.
+class ReachBalls {
+ public:
+  void reset() { b_.clear(); }
+  const std::vector<std::array<double, 4>> &balls() const { return b_; }
+  void push(const double p[3], double r) { b_.push_back({p[0], p[1], p[2], r}); }  // kept as given
+  // largest |p - centre| + radius: no point of any ball lies farther from p (0 for an empty list)
+  double farthest(const double p[3]) const {
+    double far = 0.0;
+    for (auto &b : b_) far = std::max(far, dist3(p, b.data()) + b[3]);
+    return far;
+  }
+  // a new ball drops the ones it contains, and a long list collapses into one ball around the newest centre
+  void add(const double p[3], double r) {
+    std::vector<std::array<double, 4>> keep;
+    for (auto &b : b_)
+      if (dist3(p, b.data()) + b[3] > r) keep.push_back(b);
+    keep.push_back({p[0], p[1], p[2], r});
+    b_.swap(keep);
+    if (b_.size() > 256) b_.assign(1, {p[0], p[1], p[2], farthest(p)});
+  }
+
+ private:
+  std::vector<std::array<double, 4>> b_;
+};
+
+// ---- the map-scope mesh pass (DESIGN.md §7c "Meshing the whole map")
+// Blocks that can own cells of the lattice (lower, n cells per axis): floor(mc / 8) between those of the first and last cell
+// per axis (k_mc_axes' expression restated on the host), widened by one block -- the kernel finds the exact range, this only
+// skips the rest.
+struct BlockRange {
+  int lo[3], hi[3];
+  bool holds(unsigned long long key) const {
+    int c[3]; unpack_key_host(key, c);
+    return c[0] >= lo[0] && c[0] <= hi[0] && c[1] >= lo[1] && c[1] <= hi[1] && c[2] >= lo[2] && c[2] <= hi[2];
+  }
+};
+inline BlockRange lattice_block_range(const float *lower, const int n[3], float vs) {
+  BlockRange r;
+  for (int k = 0; k < 3; ++k) {
+    int m[2];
+    for (int e = 0; e < 2; ++e) {
+      const float pa = (float)(e ? n[k] - 1 : 0) * vs + lower[k];
+      m[e] = f2i_host(pa / vs + (float)((pa > 0) - (pa < 0)) * 0.5f);
+    }
+    auto fdiv = [](int v) { return v < 0 ? (v - kBS + 1) / kBS : v / kBS; };
+    r.lo[k] = fdiv(std::min(m[0], m[1])) - 1;
+    r.hi[k] = fdiv(std::max(m[0], m[1])) + 1;
+  }
+  return r;
+}
+// The global order of a map: ascending key over resident (res) and stored (sto) blocks, both sorted; f(key, stored) for those
+// within the range.
+template <class F>
+inline void for_each_in_range(const std::vector<unsigned long long> &res, const std::vector<unsigned long long> &sto, const BlockRange &range, F f) {
+  for (size_t i = 0, j = 0; i < res.size() || j < sto.size();) {
+    const bool stored = j < sto.size() && (i >= res.size() || sto[j] < res[i]);
+    const unsigned long long key = stored ? sto[j++] : res[i++];
+    if (range.holds(key)) f(key, stored);
+  }
+}
+// The merged list cut into chunks: chunk c meshes own[ob[c], ob[c+1]) (global order) and stages stg[sb[c], sb[c+1]) (ascending):
+// its own stored blocks and every stored block among the 26 neighbours of its blocks.
+struct MeshPlan {
+  std::vector<unsigned long long> own, stg;
+  std::vector<size_t> ob{0}, sb{0};
+  size_t chunks() const { return ob.size() - 1; }
+};
+// Greedy: a chunk closes when it owns own_cap blocks or the next block would take its staged set beyond stage_cap (>= 27, so
+// that one block's neighbourhood always fits).  sto = store.sorted_keys(); picked, if given, is a subsequence of the merged
+// in-range list and only its blocks are planned.
+inline MeshPlan plan_mesh_chunks(const std::vector<unsigned long long> &res, const std::vector<unsigned long long> &sto, const HostBlockStore &store,
+                                 const BlockRange &range, size_t own_cap, size_t stage_cap, const std::vector<unsigned long long> *picked = nullptr) {
+  MeshPlan p;
+  std::vector<unsigned long long> cur;
+  std::unordered_set<unsigned long long> in_cur;
+  auto close_chunk = [&]() {
+    std::sort(cur.begin(), cur.end());
+    p.stg.insert(p.stg.end(), cur.begin(), cur.end());
+    p.ob.push_back(p.own.size()); p.sb.push_back(p.stg.size());
+    cur.clear(); in_cur.clear();
+  };
+  size_t pk = 0;
+  unsigned long long need[27];
+  for_each_in_range(res, sto, range, [&](unsigned long long key, bool stored) {
+    if (picked) {
+      if (pk == picked->size() || (*picked)[pk] != key) return;
+      ++pk;
+    }
+    int c[3]; unpack_key_host(key, c);
+    int nn = 0, fresh = 0;  // stored blocks this block reads / those not staged for the chunk yet
+    for (int k = 0; k < 27; ++k) {
+      const int q[3] = {c[0] + k / 9 - 1, c[1] + (k / 3) % 3 - 1, c[2] + k % 3 - 1};
+      unsigned long long qk;
+      if (k == 13 ? stored : (pack_key_host(q, qk) && store.contains(qk))) {
+        need[nn++] = k == 13 ? key : qk;
+        fresh += !in_cur.count(need[nn - 1]);
+      }
+    }
+    if (p.own.size() - p.ob.back() == own_cap || cur.size() + fresh > stage_cap) close_chunk();
+    p.own.push_back(key);
+    for (int k = 0; k < nn; ++k)
+      if (in_cur.insert(need[k]).second) cur.push_back(need[k]);
+  });
+  if (p.own.size() > p.ob.back()) close_chunk();
+  return p;
+}
+
+}  // namespace dr
