@@ -257,10 +257,12 @@ int drf_bench_render_host(drf_t *h, int stream, int back, const uint8_t **bgr, c
  *   centre ((8 b + 3.5) voxel_size per axis) lies within `radius` of p -- before the allocation pass --, (3) integrates
  *   unchanged, (4) evicts the resident blocks whose centre lies beyond radius + one block edge (8 voxel_size) of p.
  * Exactness contract: with radius >= drf_streaming_min_radius, the voxel state of the map (resident blocks plus host store)
- *   after every scan is bit-identical to an engine whose pool never runs out, and so are the update counts.  A ray-cast
- *   equals that engine's when its pose lies within radius - drf_streaming_min_radius of the last scan's camera centre (the
- *   scan pose itself always qualifies).  Farther renders see the resident blocks only.
- * drf_export_blocks and rendering cover the RESIDENT blocks.  Mesh extraction covers them too by default; after
+ *   after every scan is bit-identical to an engine whose pool never runs out, and so are the update counts.
+ * Renders read the RESIDENT blocks by default: a ray-cast then equals that engine's when its pose lies within
+ *   radius - drf_streaming_min_radius of the last scan's camera centre (the scan pose itself always qualifies), and a farther
+ *   one misses what is stored on the host.  After drf_set_render_scope(h, DRF_RENDER_MAP, ...) a ray-cast at ANY pose equals
+ *   the unbounded engine's in depth and colour, without moving a block.
+ * drf_export_blocks covers the RESIDENT blocks.  Mesh extraction covers them too by default; after
  *   drf_set_mesh_scope(h, DRF_MESH_MAP) it covers resident blocks and host store together, without moving a block.
  *   drf_bench_* return DR_ERR_UNSUPPORTED while streaming is on or the host store holds blocks, and integrating with
  *   streaming off while the host store holds blocks is DR_ERR_PROTOCOL. */
@@ -293,6 +295,24 @@ int drf_export_host_blocks(drf_t *h, int max_blocks, int32_t *coords, uint8_t *v
  * A scope other than the two is DR_ERR_ARG; changing it while an extraction is pending is DR_ERR_PROTOCOL. */
 enum { DRF_MESH_RESIDENT = 0, DRF_MESH_MAP = 1 };
 int drf_set_mesh_scope(drf_t *h, int scope);
+/* What drf_render_async ray-casts.  DRF_RENDER_RESIDENT (the default): the pool's blocks, exactly as without this call.
+ * DRF_RENDER_MAP: the pool and the host store together -- every render equals, bit for bit in depth and colour, the one an
+ *   engine whose pool never ran out returns for the same scans and pose.  Each drf_render_async selects the stored blocks its
+ *   poses can read (the sphere of the ray-cast reach around each camera centre, cut by the view frustum; a pose that is not a
+ *   finite rigid motion selects the whole store), stages their union through a device scratch of stage_capacity_blocks blocks
+ *   (0 = min(num_blocks, 8192); 4104 bytes per block, twice) and ray-casts pool and staging together.  No block moves: pool,
+ *   slot order, host store and streaming state stay as they were.  A union beyond the capacity makes drf_render_async return
+ *   DR_ERR_CAPACITY with nothing changed (except that evictions the last scan left pending may already be folded into the host
+ *   store, as every call that reads the store does) -- the call sequence still expects drf_render_async, which may be retried after a
+ *   drf_set_render_scope with a larger capacity or in resident scope.  A render that cannot reach a block the last scan
+ *   evicted does not wait for that scan; with no stored block in reach (an engine without streaming, the scan pose) the
+ *   resident kernels run and nothing is copied.  DESIGN.md §7c "Rendering the whole map".
+ * scope other than the two: DR_ERR_ARG; between drf_render_async and drf_get_render_result: DR_ERR_PROTOCOL */
+enum { DRF_RENDER_RESIDENT = 0, DRF_RENDER_MAP = 1 };
+int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks);
+/* last drf_render_async: [0] stored blocks staged (union over its poses), [1] bytes uploaded,
+   [2] poses that selected the whole store (not rigid), [3] 1 if it waited for the scan to fold evictions */
+int drf_render_stats(drf_t *h, uint64_t out[4]);
 /* Last extraction: [0] blocks meshed (resident + stored), [1] host blocks uploaded (a block staged by k chunks counts k
  * times), [2] chunks (1 for a resident pass over a non-empty pool). */
 int drf_mesh_stats(drf_t *h, uint64_t out[3]);

@@ -640,17 +640,28 @@ __global__ __launch_bounds__(256, DR_INTEGRATE_WAVES) void k_integrate(const Fus
 }
 
 // ------------------------------------------------------------------ raycast
-__device__ inline Voxel get_voxel(const FusionDev &d, F3 p) {  // tsdf_volume.cu:147-160
+}  // namespace dr
+#include "render_stage_kernels.h"  // STAGED = true: blocks absent from the pool resolve among the host blocks staged for the render
+namespace dr {
+
+template <bool STAGED = false>
+__device__ inline Voxel get_voxel(const FusionDev &d, F3 p, const StageArg<STAGED> &sg = {}) {  // tsdf_volume.cu:147-160
   Voxel z; z.sdf = 0.f; z.c[0] = z.c[1] = z.c[2] = 0; z.weight = 0;
   I3 blk; int local;
   world_to_block_local(d.o, p, blk, local);
   const int b = find_block(d, blk);
+  if constexpr (STAGED) {  // the literal pass resolves through the pool, then the staging
+    const int s = b < 0 ? stage_find_sorted(sg, blk) : -1;
+    if (b < 0 && s < 0) return z;
+    return *(b >= 0 ? d.vox + (size_t)b * (kBS * kBS * kBS) + local : sg.vox + (size_t)s * (kBS * kBS * kBS) + local);
+  }
   if (b < 0) return z;
   return d.vox[(size_t)b * (kBS * kBS * kBS) + local];
 }
 
-__device__ inline Voxel get_interpolated_voxel(const FusionDev &d, F3 pos) {  // tsdf_volume.cu:161-289
-  const Voxel v0 = get_voxel(d, pos);
+template <bool STAGED = false>
+__device__ inline Voxel get_interpolated_voxel(const FusionDev &d, F3 pos, const StageArg<STAGED> &sg = {}) {  // tsdf_volume.cu:161-289
+  const Voxel v0 = get_voxel<STAGED>(d, pos, sg);
   if (v0.weight == 0) return v0;
   const float vs = d.o.voxel_size, hv = vs / 2.0f;
   F3 pd; pd.x = pos.x - hv; pd.y = pos.y - hv; pd.z = pos.z - hv;
@@ -664,7 +675,7 @@ __device__ inline Voxel get_interpolated_voxel(const FusionDev &d, F3 pos) {  //
   for (int k = 0; k < 8; ++k) {
     const int c = order[k];
     F3 q; q.x = pd.x + ((c & 1) ? vs : 0.0f); q.y = pd.y + ((c & 2) ? vs : 0.0f); q.z = pd.z + ((c & 4) ? vs : 0.0f);
-    v = get_voxel(d, q);
+    v = get_voxel<STAGED>(d, q, sg);
     const float a = (c & 1) ? w.x : (1.0f - w.x), b = (c & 2) ? w.y : (1.0f - w.y), cc = (c & 4) ? w.z : (1.0f - w.z);
     const float wt = a * b * cc;
     const Voxel &src = v.weight == 0 ? v0 : v;
@@ -830,8 +841,10 @@ __device__ inline Voxel interp_voxel(const FusionDev &d, F3 pos, bool far_blocks
 // (centre block -> centre voxel -> neighbour blocks -> corner voxels); here every block look-up (centre + the 2x2x2 corner
 // blocks, computed from the position alone) is issued at once, then every voxel load (centre + 8 corners, unconditional
 // 8-byte loads from a clamped address, masked afterwards) at once.  Same values, same arithmetic, same result.
-template <bool FAST, bool COLOUR>
-__device__ inline Voxel interp_voxel2(const FusionDev &d, F3 pos, bool far_blocks, bool &bail, int *empty_cell = nullptr) {
+// STAGED = true (map-scope renders): interp_voxel2_staged, render_stage_kernels.h -- the same two round trips over pool and staging.
+template <bool FAST, bool COLOUR, bool STAGED = false>
+__device__ inline Voxel interp_voxel2(const FusionDev &d, F3 pos, bool far_blocks, bool &bail, int *empty_cell = nullptr, const StageArg<STAGED> &sg = {}) {
+  if constexpr (STAGED) return interp_voxel2_staged<FAST, COLOUR>(d, sg, pos, far_blocks, bail, empty_cell);
   const float vs = d.o.voxel_size, hv = vs / 2.0f, y = d.vs_rcp;
   Voxel zero; zero.sdf = 0.f; zero.c[0] = zero.c[1] = zero.c[2] = 0; zero.weight = 0;
   const float qx = div_by<FAST>(pos.x, vs, y), qy = div_by<FAST>(pos.y, vs, y), qz = div_by<FAST>(pos.z, vs, y);
@@ -929,12 +942,21 @@ __device__ inline int skip_steps(unsigned cell, F3 q, F3 dirw, F3 inv_dir, float
 // centre block does not exist, [4] skip events, [5] skipped steps, [6] samples with weight != 0, [7] waves, [8..] histogram
 // of the waves' longest rays in buckets of 16 iterations.
 // SAMPLER: 1 = interp_voxel2 (9 + 9 gathers in two round trips; the product's), 0 = interp_voxel (round 2's four stages; parity build)
-template <bool FAST, bool STATS = false, int SAMPLER = 1>
+// STAGED: the map-scope form (render_stage_kernels.h) -- look-ups fall through to the staged host blocks, a superblock is skipped
+// only if neither the pool nor the staging holds a block in it, and a staged block outside the dense grid sends the pixel to the
+// literal pass like a table block does.  The product's sampler only.
+// The staging is a trailing parameter PACK -- one RenderStage when STAGED, nothing otherwise -- so that the resident instances keep
+// their kernel arguments, and with them their instructions, exactly.
+template <bool FAST, bool STATS = false, int SAMPLER = 1, bool STAGED = false, class... SG>
 __global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat pose, unsigned char *__restrict__ bgr,
-                                                 float *__restrict__ depth_out, int *__restrict__ n_flagged, unsigned long long *st = nullptr) {
+                                                 float *__restrict__ depth_out, int *__restrict__ n_flagged, unsigned long long *st,
+                                                 const SG... stage) {
+  static_assert(!STAGED || (SAMPLER == 1 && !STATS), "the staged ray-cast exists for the product's sampler");
+  static_assert(sizeof...(SG) == (STAGED ? 1 : 0), "one RenderStage for the staged form, none otherwise");
+  const StageArg<STAGED> &sg = stage_arg(stage...);
   const drf_options_t &o = d.o;
   const int size = o.height * o.width;
-  const bool far_blocks = d.n_alloc[3] != 0;
+  const bool far_blocks = d.n_alloc[3] != 0 || stage_far(sg);
   // one wave = one 8x8 pixel tile, tiles dealt to the 8 XCDs in bands of rows (see k_raycast)
   const bool tiled = (o.width % 8 == 0) && (o.height % 8 == 0) && blockDim.x == 64;
   const int ntile = tiled ? size / 64 : 0, per_xcd = (ntile + 7) >> 3;
@@ -983,16 +1005,17 @@ __global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat po
     while (cur < o.max_sensor_depth) {
       const F3 q = sample_pos(cur);
       int cell = -1;
-      const Voxel v = SAMPLER == 1 ? interp_voxel2<FAST, false>(d, q, far_blocks, bail, d.super[0] ? &cell : nullptr)
+      const Voxel v = SAMPLER == 1 ? interp_voxel2<FAST, false, STAGED>(d, q, far_blocks, bail, (STAGED || d.super[0]) ? &cell : nullptr, sg)
                                    : interp_voxel<FAST, false>(d, q, far_blocks, bail, d.super[0] ? &cell : nullptr);
+      if (STAGED && !d.super[0]) cell = -1;  // (the staged sampler always reports the cell: its pointer stays a plain local)
       if (bail) break;
       if (STATS) { ++n_it; n_miss += cell >= 0; n_full += v.weight != 0; }
       if (v.weight == 0) {
         cur += o.truncation_distance;
         if (cell >= 0) {
           int k = 0;
-          if (d.super[0][super_index<kSuperShift[0]>((unsigned)cell)] == 0) k = skip_steps<kSuperShift[0]>((unsigned)cell, q, dirw, inv_dir, vs, inv_trunc);
-          else if (d.super[1][super_index<kSuperShift[1]>((unsigned)cell)] == 0) k = skip_steps<kSuperShift[1]>((unsigned)cell, q, dirw, inv_dir, vs, inv_trunc);
+          if (d.super[0][super_index<kSuperShift[0]>((unsigned)cell)] == 0 && stage_super_empty<0>(sg, (unsigned)cell)) k = skip_steps<kSuperShift[0]>((unsigned)cell, q, dirw, inv_dir, vs, inv_trunc);
+          else if (d.super[1][super_index<kSuperShift[1]>((unsigned)cell)] == 0 && stage_super_empty<1>(sg, (unsigned)cell)) k = skip_steps<kSuperShift[1]>((unsigned)cell, q, dirw, inv_dir, vs, inv_trunc);
           if (STATS && k > 0) { ++n_skip; n_skipped += k; }
           for (; k > 0 && cur < o.max_sensor_depth; --k) cur += o.truncation_distance;
         }
@@ -1013,7 +1036,7 @@ __global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat po
     }
     if (!bail && cur < o.max_sensor_depth) {
       const F3 qf = sample_pos(cur);
-      const Voxel v = SAMPLER == 1 ? interp_voxel2<FAST, true>(d, qf, far_blocks, bail) : interp_voxel<FAST, true>(d, qf, far_blocks, bail);
+      const Voxel v = SAMPLER == 1 ? interp_voxel2<FAST, true, STAGED>(d, qf, far_blocks, bail, nullptr, sg) : interp_voxel<FAST, true>(d, qf, far_blocks, bail);
       bgr[3 * i] = v.c[0]; bgr[3 * i + 1] = v.c[1]; bgr[3 * i + 2] = v.c[2];
       depth_out[i] = cur;
     } else {
@@ -1024,8 +1047,11 @@ __global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat po
   }
 }
 // The literal ray-caster for the pixels k_raycast2 flagged; exits at once when there are none.
+template <bool STAGED = false, class... SG>
 __global__ __launch_bounds__(64) void k_raycast_fix(const FusionDev d, const Mat pose, unsigned char *__restrict__ bgr,
-                                                    float *__restrict__ depth_out, int *__restrict__ n_flagged) {
+                                                    float *__restrict__ depth_out, int *__restrict__ n_flagged, const SG... stage) {
+  static_assert(sizeof...(SG) == (STAGED ? 1 : 0), "one RenderStage for the staged form, none otherwise");
+  const StageArg<STAGED> &sg = stage_arg(stage...);
   if (*n_flagged == 0) return;
   const drf_options_t &o = d.o;
   const int size = o.height * o.width;
@@ -1033,12 +1059,12 @@ __global__ __launch_bounds__(64) void k_raycast_fix(const FusionDev d, const Mat
     if (!(depth_out[i] == -1.0f)) continue;
     float cur = 0.f;
     while (cur < o.max_sensor_depth) {
-      const Voxel v = get_interpolated_voxel(d, xform(pose, point3d(o, i, cur)));
+      const Voxel v = get_interpolated_voxel<STAGED>(d, xform(pose, point3d(o, i, cur)), sg);
       if (v.weight == 0) cur += o.truncation_distance; else cur += v.sdf;
       if (v.weight != 0 && v.sdf < o.voxel_size) break;
     }
     if (cur < o.max_sensor_depth) {
-      const Voxel v = get_interpolated_voxel(d, xform(pose, point3d(o, i, cur)));
+      const Voxel v = get_interpolated_voxel<STAGED>(d, xform(pose, point3d(o, i, cur)), sg);
       bgr[3 * i] = v.c[0]; bgr[3 * i + 1] = v.c[1]; bgr[3 * i + 2] = v.c[2];
       depth_out[i] = cur;
     } else {
@@ -1181,6 +1207,28 @@ class DeviceBuf {
   size_t cap_ = 0;
 };
 
+// Page-locked host scratch that grows with its use; contents are not kept.  The caller makes sure no copy still reads the old allocation.
+template <class T>
+class PinnedBuf {
+ public:
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  void operator=(const PinnedBuf &) = delete;
+  ~PinnedBuf() { (void)hipHostFree(p_); }
+  void reserve(size_t n) {
+    if (n <= cap_) return;
+    if (p_) DR_HIP(hipHostFree(p_));
+    p_ = nullptr; cap_ = 0;
+    DR_HIP(hipHostMalloc((void **)&p_, n * sizeof(T), hipHostMallocDefault));
+    cap_ = n;
+  }
+  T *get() const { return p_; }
+
+ private:
+  T *p_ = nullptr;
+  size_t cap_ = 0;
+};
+
 constexpr int kDefaultFusionPriority = 1;  // 0 least (the reference's), 1 normal (measured best in the TandemBackend loop), 2 greatest
 class FusionEngine {
  public:
@@ -1285,8 +1333,18 @@ class FusionEngine {
     if (st_radius_ > 0.0f) stream_after_scan(pose16);
     DR_HIP(hipEventRecord(int_done_, int_stream_));
   }
-  void launch_raycast(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P) {
+  // sg: the host blocks staged for this render (map scope with stored blocks in reach), nullptr = the resident kernels
+  void launch_raycast(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P, const RenderStage *sg = nullptr) {
     const dim3 grid(8 * cdiv(cdiv((int)npix_, 64), 8)), block(64);
+    if (sg) {
+      hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, d_flag);
+      FusionDev dv = d_;
+      if (raycast_no_skip_) dv.super[0] = nullptr;
+      if (d_.fast_div) hipLaunchKernelGGL((k_raycast2<true, false, 1, true>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, *sg);
+      else hipLaunchKernelGGL((k_raycast2<false, false, 1, true>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, *sg);
+      hipLaunchKernelGGL(k_raycast_fix<true>, dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag, *sg);
+      return;
+    }
 #ifdef DR_PARITY_HOOKS
     if (raycast_v1_) { hipLaunchKernelGGL(k_raycast, grid, block, 0, st, d_, P, d_bgr, d_depth); return; }
 #endif
@@ -1313,7 +1371,7 @@ class FusionEngine {
 #endif
     if (d_.fast_div) hipLaunchKernelGGL((k_raycast2<true, false, 1>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr);
     else hipLaunchKernelGGL((k_raycast2<false, false, 1>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(k_raycast_fix, dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag);
+    hipLaunchKernelGGL(k_raycast_fix<false>, dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag);
   }
   // render -> host (k_publish); DR_RENDER_D2H=copy: the two hipMemcpyAsync of round 2 (A/B hook)
   void publish_render(int i) {
@@ -1330,18 +1388,50 @@ class FusionEngine {
   void render_async(const float *const *poses, int n) {
     expect(kRender, "Please call the functions like IntegrateScanAsync -> RenderAsync -> GetRenderResult.");
     if (n != (int)renders_.size()) fail(DR_ERR_PROTOCOL, "Can only render exactly as many poses as streams. Streams: %zu, Poses: %d.", renders_.size(), n);
-    next_ = kGetRender;
     DR_HIP(hipSetDevice(device_));
+    // map scope: the stored blocks these poses can read, decided before anything changes (DR_ERR_CAPACITY leaves all as it was)
+    RenderStagePlan plan;
+    bool waited = false;
+    if (render_scope_ == DRF_RENDER_MAP) {
+      for (int i = 0; i < n; ++i) if (!poses[i]) fail(DR_ERR_ARG, "RenderAsync: null pose");
+      plan = plan_render(poses, n, waited);
+      if (!render_stage_fits(plan, rs_capacity()))
+        fail(DR_ERR_CAPACITY, "RenderAsync: the poses can read %zu stored blocks, the render staging holds %zu (drf_set_render_scope)", plan.keys.size(), rs_capacity());
+#ifdef DR_PARITY_HOOKS
+      if (!plan.keys.empty() && (raycast_v1_ || raycast_stats_ || raycast_sampler_ == 0))
+        fail(DR_ERR_UNSUPPORTED, "RenderAsync: the superseded ray-cast generations have no staged form (DRF_RENDER_MAP with stored blocks in reach)");
+#endif
+    }
+    next_ = kGetRender;
     free_slot_ ^= 1;  // write into the buffers NOT handed out by the last GetRenderResult
+    RenderStage sg{};
+    const bool staged = !plan.keys.empty();  // nothing to stage: exactly the resident launches
+    if (staged) sg = stage_render(plan.keys);
     for (int i = 0; i < n; ++i) {
       Render &r = renders_[i];
       Mat P; memcpy(P.m, poses[i], 64);
       DR_HIP(hipStreamWaitEvent(r.stream, int_done_, 0));
-      launch_raycast(r.stream, r.d_bgr, r.d_depth, r.d_flag, P);
+      if (staged) DR_HIP(hipStreamWaitEvent(r.stream, rs_[rs_cur_].copied, 0));
+      launch_raycast(r.stream, r.d_bgr, r.d_depth, r.d_flag, P, staged ? &sg : nullptr);
       DR_HIP(hipEventRecord(r.cast, r.stream));
       publish_render(i);
       DR_HIP(hipEventRecord(r.done, r.stream));
     }
+    if (staged) release_render_stage(sg);
+    render_stats_[0] = plan.keys.size(); render_stats_[1] = plan.keys.size() * (size_t)(8 + 4096);
+    render_stats_[2] = (uint64_t)plan.whole; render_stats_[3] = waited ? 1 : 0;
+  }
+  // DRF_RENDER_RESIDENT: renders read the pool (the default); DRF_RENDER_MAP: the pool and the host store together.
+  // stage_capacity_blocks bounds the staging (0 = min(num_blocks, kStageBlocks)).
+  void set_render_scope(int scope, size_t stage_capacity_blocks) {
+    if (scope != DRF_RENDER_RESIDENT && scope != DRF_RENDER_MAP) fail(DR_ERR_ARG, "drf_set_render_scope: unknown scope %d", scope);
+    if (next_ == kGetRender) fail(DR_ERR_PROTOCOL, "drf_set_render_scope: a render is pending, call GetRenderResult first");
+    render_scope_ = scope;
+    rs_cap_req_ = stage_capacity_blocks;
+  }
+  void render_stats(uint64_t out[4]) const {
+    if (!out) fail(DR_ERR_ARG, "drf_render_stats: null argument");
+    for (int i = 0; i < 4; ++i) out[i] = render_stats_[i];
   }
   // tsdf_volume.cu:702-737
   void get_render_result(uint8_t **bgr, float **depth, int n) {
@@ -1830,6 +1920,84 @@ class FusionEngine {
     ev_auto_ = true;
     memcpy(ev_p_, p, sizeof p);
   }
+  // ---- the render scope (DRF_RENDER_MAP; DESIGN.md §7c "Rendering the whole map") ----
+  size_t rs_capacity() const { return rs_cap_req_ ? rs_cap_req_ : (size_t)std::min(o_.num_blocks, kStageBlocks); }
+  // The union of stored blocks the poses can read.  Blocks the last scan's eviction chain gathered are not in the store yet: only
+  // a pose that could reach one (render_needs_fold) waits for the scan and folds them first.
+  RenderStagePlan plan_render(const float *const *poses, int n, bool &waited) {
+    if (ev_pending_) {
+      bool far = !ev_auto_;
+      for (int i = 0; i < n && !far; ++i) far = render_needs_fold(o_, poses[i], ev_p_, (double)st_radius_);
+      if (far) {
+        DR_HIP(hipEventSynchronize(int_done_));
+        fold_evicted();
+        waited = true;
+      }
+    }
+    return plan_render_stage(store_, o_, poses, n);
+  }
+  // Two staging buffers, each a pinned / device pair of [keys | voxels] with its table and its staged superblock flags.  Everything
+  // that touches buffer b on the device is ordered on rs_stream_: copy, table clear, k_rs_build, and -- behind the cast events of
+  // the renders that read it -- k_rs_clear.  The host waits for `copied` before it packs into the pinned half again.
+  void ensure_render_staging(size_t n) {
+    if (!rs_stream_) {
+      rs_stream_ = own_.stream();
+      for (auto &b : rs_) {
+        for (int l = 0; l < kSuperLevels; ++l) b.super[l] = own_.device<unsigned char>((size_t)1 << (3 * (kGridBits - kSuperShift[l])), rs_stream_);
+        b.copied = own_.event();
+        DR_HIP(hipEventRecord(b.copied, rs_stream_));
+      }
+    }
+    if (n <= rs_blocks_) return;
+    const size_t want = std::min(rs_capacity(), std::max(2 * rs_blocks_, (n + 1023) & ~(size_t)1023));
+    DR_HIP(hipDeviceSynchronize());  // no copy or kernel reads the old allocations
+    size_t slots = 1024;
+    while (slots < 2 * want) slots <<= 1;
+    for (auto &b : rs_) {
+      b.dev.reserve((want + 1) * 8 + want * 4096, rs_stream_);
+      b.host.reserve((want + 1) * 8 + want * 4096);
+      b.table.reserve(slots, rs_stream_);
+    }
+    rs_blocks_ = want;
+  }
+  RenderStage stage_render(const std::vector<unsigned long long> &keys) {
+    const size_t n = keys.size(), nk = (n + 1) & ~(size_t)1;  // voxels start 16-byte aligned
+    ensure_render_staging(n);
+    rs_cur_ ^= 1;
+    RenderStageBuf &b = rs_[rs_cur_];
+    DR_HIP(hipEventSynchronize(b.copied));
+    unsigned char *h = b.host.get();
+    memcpy(h, keys.data(), n * 8);
+    if (nk > n) memset(h + n * 8, 0xFF, 8);
+    int far = 0;
+    for (size_t k = 0; k < n; ++k) {
+      memcpy(h + nk * 8 + k * 4096, store_.get(keys[k]), 4096);
+      int c[3]; unpack_key_host(keys[k], c);
+      constexpr int G = 1 << (kGridBits - 1);
+      for (int a = 0; a < 3; ++a) if (c[a] < -G || c[a] >= G) far = 1;
+    }
+    size_t slots = 1024;
+    while (slots < 2 * n) slots <<= 1;
+    DR_HIP(hipMemcpyAsync(b.dev.get(), h, nk * 8 + n * 4096, hipMemcpyHostToDevice, rs_stream_));
+    DR_HIP(hipMemsetAsync(b.table.get(), 0, slots * 8, rs_stream_));
+    RenderStage sg{};
+    sg.keys = (const unsigned long long *)b.dev.get();
+    sg.vox = (const Voxel *)(b.dev.get() + nk * 8);
+    sg.table = b.table.get(); sg.tmask = (unsigned)(slots - 1);
+    sg.super[0] = b.super[0]; sg.super[1] = b.super[1];
+    sg.n = (int)n; sg.far = far;
+    hipLaunchKernelGGL(k_rs_build, dim3(cdiv((int)n, 256)), dim3(256), 0, rs_stream_, sg.keys, sg.n, b.table.get(), sg.tmask, b.super[0], b.super[1]);
+    DR_HIP(hipGetLastError());
+    DR_HIP(hipEventRecord(b.copied, rs_stream_));
+    return sg;
+  }
+  // behind every ray-cast that read the buffer: its flags go back to zero
+  void release_render_stage(const RenderStage &sg) {
+    RenderStageBuf &b = rs_[rs_cur_];
+    for (auto &r : renders_) DR_HIP(hipStreamWaitEvent(rs_stream_, r.cast, 0));
+    hipLaunchKernelGGL(k_rs_clear, dim3(cdiv(sg.n, 256)), dim3(256), 0, rs_stream_, sg.keys, sg.n, b.super[0], b.super[1]);
+    DR_HIP(hipGetLastError());
+  }
   void expect(Next want, const char *msg) {
     static const char *names[] = {"IntegrateScanAsync", "RenderAsync", "GetRenderResult"};
     if (next_ != want) fail(DR_ERR_PROTOCOL, "%s You should have called %s", msg, names[next_]);
@@ -1948,13 +2116,7 @@ class FusionEngine {
   // every entry point that integrates comes through enqueue_scan.  A pose that is not a finite rigid motion (the reach bound
   // assumes one) or one scan too many makes the next update full.
   void record_scan_pose(const Mat &Ti) {
-    bool rigid = true;
-    for (int i = 0; i < 3 && rigid; ++i)
-      for (int j = i; j < 3; ++j) {
-        const double dot = (double)Ti.m[4 * i] * Ti.m[4 * j] + (double)Ti.m[4 * i + 1] * Ti.m[4 * j + 1] + (double)Ti.m[4 * i + 2] * Ti.m[4 * j + 2];
-        if (!(std::fabs(dot - (i == j ? 1.0 : 0.0)) < 1e-3)) rigid = false;
-      }
-    for (int i = 0; i < 12; ++i) rigid = rigid && std::isfinite(Ti.m[i]);
+    const bool rigid = pose_is_rigid(Ti.m);  // (fusion_host.h: the one statement of the rule, shared with the render scope)
     if (!rigid || mu_poses_.size() == (size_t)DRF_MESH_UPDATE_MAX_SCANS) { mu_overflow_ = true; return; }
     MuPose p;
     memcpy(p.m, Ti.m, 48);
@@ -2185,6 +2347,20 @@ class FusionEngine {
   unsigned char *ms_dev_[2] = {nullptr, nullptr}, *ms_host_[2] = {nullptr, nullptr};
   hipEvent_t ms_copied_[2] = {nullptr, nullptr}, ms_used_[2] = {nullptr, nullptr};
   hipStream_t ms_copy_stream_ = nullptr;
+  // render scope: staging allocated with the first map-scope render that has stored blocks in reach, grown up to rs_capacity()
+  struct RenderStageBuf {
+    DeviceBuf<unsigned char> dev;
+    PinnedBuf<unsigned char> host;
+    DeviceBuf<unsigned long long> table;
+    unsigned char *super[2] = {nullptr, nullptr};
+    hipEvent_t copied = nullptr;
+  };
+  int render_scope_ = DRF_RENDER_RESIDENT;
+  size_t rs_cap_req_ = 0, rs_blocks_ = 0;
+  RenderStageBuf rs_[2];
+  int rs_cur_ = 0;
+  hipStream_t rs_stream_ = nullptr;
+  uint64_t render_stats_[4] = {0, 0, 0, 0};
   // streaming state (staging allocated with the first drf_set_streaming / region call)
   float st_radius_ = 0.0f;                  // 0 = off
   size_t st_host_cap_ = (size_t)-1;         // host store capacity in blocks
@@ -2316,6 +2492,8 @@ int drf_streaming_stats(drf_t *h, uint64_t out[6]) {
 int drf_export_host_blocks(drf_t *h, int max_blocks, int32_t *coords, uint8_t *voxels, int *n) {
   return guarded([&] { eng(h)->export_host_blocks(max_blocks, coords, voxels, n); });
 }
+int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }
+int drf_render_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->render_stats(out); }); }
 int drf_set_mesh_scope(drf_t *h, int scope) { return guarded([&] { eng(h)->set_mesh_scope(scope); }); }
 int drf_mesh_stats(drf_t *h, uint64_t out[3]) { return guarded([&] { eng(h)->mesh_stats(out); }); }
 int drf_extract_mesh_update_async(drf_t *h, const float *lower, const float *upper) {

@@ -216,6 +216,95 @@ class ReachBalls {
   std::vector<std::array<double, 4>> b_;
 };
 
+// ---- the render scope (DRF_RENDER_MAP; DESIGN.md §7c "Rendering the whole map"): which stored blocks a ray-cast can read
+// Farthest a block centre can lie from the camera centre of a ray-cast and still be read by it: the ray-cast term of
+// stream_reach with the same block diagonal and voxel of margin.  Equals stream_reach(o, max_sensor_depth) minus the truncation
+// distance whenever the depth term of that bound is the larger one, so at a scan pose no stored block is within it.
+inline double render_margin(const drf_options_t &o) {
+  const double s3 = std::sqrt(3.0), vs = o.voxel_size;
+  return 4.5 * s3 * vs + 8.0 * s3 * vs + vs;
+}
+inline double render_reach(const drf_options_t &o) { return (double)o.max_sensor_depth * corner_rho(o) + render_margin(o); }
+// A finite rigid motion, as far as the reach bounds need it: the twelve entries finite, |R R^T - I| < 1e-3 per entry.  The one
+// statement of the rule: the mesh update applies it to a scan's world-to-camera matrix (record_scan_pose), the render scope to
+// a render's camera-to-world matrix
+inline bool pose_is_rigid(const float *pose16) {
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(pose16[i])) return false;
+  for (int i = 0; i < 3; ++i)
+    for (int j = i; j < 3; ++j) {
+      const double dot = (double)pose16[4 * i] * pose16[4 * j] + (double)pose16[4 * i + 1] * pose16[4 * j + 1] + (double)pose16[4 * i + 2] * pose16[4 * j + 2];
+      if (!(std::fabs(dot - (i == j ? 1.0 : 0.0)) < 1e-3)) return false;
+    }
+  return true;
+}
+// Stored blocks a ray-cast from pose16 can read, appended to out (any order): the sphere of render_reach around the camera
+// centre, cut by the six half-spaces that hold the pyramid of sample points {z (lx, ly, 1)}, z in [0, D], each widened by
+// render_margin.  A superset by construction.  Returns false -- and appends the whole store -- for a pose that is not a
+// finite rigid motion, or options the bound is not defined for.
+inline bool select_render_blocks(const HostBlockStore &store, const drf_options_t &o, const float *pose16, std::vector<unsigned long long> &out) {
+  const double reach = stream_options_ok(o) ? render_reach(o) : HUGE_VAL;
+  if (!pose_is_rigid(pose16) || !std::isfinite(reach)) {
+    store.for_each([&](unsigned long long k, const uint8_t *) { out.push_back(k); });
+    return false;
+  }
+  double p[3];
+  camera_centre(pose16, p);
+  const size_t first = out.size();
+  const double m = render_margin(o), vs = o.voxel_size, D = o.max_sensor_depth;
+  // R R^T differs from I by < 1e-3 per entry (norm < 3e-3): R scales lengths by at most 1.5e-3, and b = R^T (c - t), which
+  // stands in for the inverse below, is off by less than 4e-3 |c - t|.  Where the 8 s + vs of margin covers that, sphere and cut
+  // stand as derived; where it does not (depth above ~10^4 voxels) the sphere grows by the error and the cut is not applied.
+  if (4e-3 * reach > 8.0 * std::sqrt(3.0) * vs + vs) {
+    store.query_sphere(p, reach * (1.0 + 4e-3), o.voxel_size, out);
+    return true;
+  }
+  store.query_sphere(p, reach, o.voxel_size, out);
+  const double lx[2] = {(0.0 - o.cx) / o.fx, ((double)o.width - 1.0 - o.cx) / o.fx};
+  const double ly[2] = {(0.0 - o.cy) / o.fy, ((double)o.height - 1.0 - o.cy) / o.fy};
+  // unit inward normals of the four side planes through the camera centre: x >= lx0 z, x <= lx1 z, y >= ly0 z, y <= ly1 z
+  const double n[4][3] = {{1.0, 0.0, -lx[0]}, {-1.0, 0.0, lx[1]}, {0.0, 1.0, -ly[0]}, {0.0, -1.0, ly[1]}};
+  size_t keep = first;
+  for (size_t i = first; i < out.size(); ++i) {
+    int c[3]; unpack_key_host(out[i], c);
+    const double w[3] = {blk_centre_host(c[0], o.voxel_size) - p[0], blk_centre_host(c[1], o.voxel_size) - p[1], blk_centre_host(c[2], o.voxel_size) - p[2]};
+    double b[3];
+    for (int a = 0; a < 3; ++a) b[a] = (double)pose16[a] * w[0] + (double)pose16[4 + a] * w[1] + (double)pose16[8 + a] * w[2];
+    bool in = b[2] >= -m && D - b[2] >= -m;
+    for (int k = 0; k < 4 && in; ++k) {
+      const double len = std::sqrt(n[k][0] * n[k][0] + n[k][1] * n[k][1] + n[k][2] * n[k][2]);
+      in = (n[k][0] * b[0] + n[k][1] * b[1] + n[k][2] * b[2]) / len >= -m;
+    }
+    if (in) out[keep++] = out[i];
+  }
+  out.resize(keep);
+  return true;
+}
+// What one RenderAsync stages: the union over its poses, ascending and de-duplicated; whole = poses that selected the whole store
+struct RenderStagePlan {
+  std::vector<unsigned long long> keys;
+  int whole = 0;
+};
+inline RenderStagePlan plan_render_stage(const HostBlockStore &store, const drf_options_t &o, const float *const *poses16, int n) {
+  RenderStagePlan p;
+  if (store.empty()) return p;
+  for (int i = 0; i < n; ++i)
+    if (!select_render_blocks(store, o, poses16[i], p.keys)) ++p.whole;
+  std::sort(p.keys.begin(), p.keys.end());
+  p.keys.erase(std::unique(p.keys.begin(), p.keys.end()), p.keys.end());
+  return p;
+}
+// the capacity decision of a RenderAsync: the union is what is staged, however many poses share a block
+inline bool render_stage_fits(const RenderStagePlan &p, size_t capacity_blocks) { return p.keys.size() <= capacity_blocks; }
+// Blocks the last scan's eviction chain gathered (not in the store until folded) lie beyond radius + 8 vs of that scan's
+// camera centre p.  A render from q with |q - p| + render_reach <= radius + 8 vs cannot read one: it need not wait for the scan.
+inline bool render_needs_fold(const drf_options_t &o, const float *pose16, const double scan_centre[3], double radius) {
+  if (!pose_is_rigid(pose16) || !stream_options_ok(o)) return true;
+  double q[3];
+  camera_centre(pose16, q);
+  return !(dist3(q, scan_centre) + render_reach(o) <= radius + (double)kBS * o.voxel_size);
+}
+
 // ---- the map-scope mesh pass (DESIGN.md §7c "Meshing the whole map")
 // Blocks that can own cells of the lattice (lower, n cells per axis): floor(mc / 8) between those of the first and last cell
 // per axis (k_mc_axes' expression restated on the host), widened by one block -- the kernel finds the exact range, this only

@@ -20,6 +20,8 @@ def DrFusionOptions(**kw):
 
 # drf_set_mesh_scope: what the mesh calls cover (include/dr_mi355x.h)
 MESH_RESIDENT, MESH_MAP = 0, 1
+# drf_set_render_scope: what RenderAsync ray-casts
+RENDER_RESIDENT, RENDER_MAP = 0, 1
 
 
 MESH_UPDATE_MAX_SCANS = 16  # DRF_MESH_UPDATE_MAX_SCANS: one scan more between two updates makes the next one full
@@ -241,6 +243,18 @@ class DrFusion:
         got = C.c_int()
         check(self._L.drf_export_host_blocks(self._h, n, coords.ctypes.data_as(C.POINTER(C.c_int32)), vox.ctypes.data_as(u8p), C.byref(got)))
         return {tuple(int(v) for v in coords[i]): vox[i] for i in range(got.value)}
+
+    def set_render_scope(self, scope, stage_capacity_blocks=0):
+        """RENDER_RESIDENT (default): renders read the pool; RENDER_MAP: the pool and the host store -- any pose renders as on an
+        engine whose pool never ran out, the stored blocks in reach staged through stage_capacity_blocks blocks of device scratch
+        (0 = min(num_blocks, 8192)); a RenderAsync that needs more raises DrError DR_ERR_CAPACITY and changes nothing."""
+        check(self._L.drf_set_render_scope(self._h, int(scope), int(stage_capacity_blocks)))
+
+    def render_stats(self):
+        """Last RenderAsync: (stored blocks staged, bytes uploaded, poses that selected the whole store, 1 if it waited for the scan)."""
+        out = (C.c_uint64 * 4)()
+        check(self._L.drf_render_stats(self._h, out))
+        return tuple(int(v) for v in out)
 
     def set_mesh_scope(self, scope):
         """MESH_RESIDENT (default): meshes cover the pool; MESH_MAP: the pool and the host store, without moving a block."""

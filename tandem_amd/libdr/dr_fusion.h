@@ -89,6 +89,8 @@ public:
   void StreamInRegion(float lower_corner[3], float upper_corner[3]) { check(drf_stream_in_region(impl, lower_corner, upper_corner)); }
   // DRF_MESH_MAP: SaveMeshToFile / ExtractMeshAsync / GetMeshSync / GetMesh cover the host store too (DRF_MESH_RESIDENT: the pool only)
   void SetMeshScope(int scope) { check(drf_set_mesh_scope(impl, scope)); }
+  // DRF_RENDER_MAP: RenderAsync at any pose reads resident and host-stored blocks together (capacity 0 = the default staging)
+  void SetRenderScope(int scope, size_t capacity = 0) { check(drf_set_render_scope(impl, scope, capacity)); }
 
   // Incremental mesh (dr_mi355x.h "incremental mesh", INTEGRATION.md "Incremental mesh"): GetMeshUpdateSync fills dr_mesh_num /
   // dr_mesh_vert / dr_mesh_cols with the triangles of the listed blocks only, and the members below name the blocks: block i has

@@ -38,6 +38,10 @@ def run_leg(leg, frames, poses, args):
         radius = rmin + args.margin
     if radius:
         f.set_streaming(radius, 0)
+    if args.render_scope == "map":  # renders at the scan pose: nothing may be staged and no render may wait for its scan
+        from tandem_amd.dr_fusion import RENDER_MAP
+        f.set_render_scope(RENDER_MAP)
+    staged_frames = 0
     ms, st_us, resident, moved = [], [], [], []
     last = dict(streamed_out=0, streamed_in=0)
     n = len(poses)
@@ -48,6 +52,8 @@ def run_leg(leg, frames, poses, args):
         f.RenderAsync([poses[k]])
         f.GetRenderResult(copy=False)
         ms.append(1e3 * (time.perf_counter() - t0))
+        if args.render_scope == "map":
+            staged_frames += f.render_stats() != (0, 0, 0, 0)
         if radius or k % 50 == 0 or k == n - 1:
             s = f.streaming_stats()
             resident.append((k, s["resident"]))
@@ -58,7 +64,7 @@ def run_leg(leg, frames, poses, args):
     f.close()
     w = args.warmup
     t = np.array(ms[w:])
-    out = dict(leg=leg, frames=n, max_sensor_depth=depth_max, radius=radius, min_radius=rmin, ms_per_frame_median=float(np.median(t)),
+    out = dict(leg=leg, render_scope=args.render_scope, frames_with_render_stats_nonzero=staged_frames, frames=n, max_sensor_depth=depth_max, radius=radius, min_radius=rmin, ms_per_frame_median=float(np.median(t)),
                ms_per_frame_mean=float(t.mean()), ms_per_frame_p90=float(np.percentile(t, 90)),
                ms_first_100=float(np.median(ms[w:100])), ms_last_100=float(np.median(ms[-100:])),
                streaming_us_per_frame_mean=float(np.mean(st_us)) if radius else 0.0,
@@ -80,6 +86,7 @@ def main():
     ap.add_argument("--margin", type=float, default=0.1, help="metres above drf_streaming_min_radius for the `move` leg")
     ap.add_argument("--num-blocks", type=int, default=400000)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--render-scope", default="resident", choices=("resident", "map"), help="drf_set_render_scope of every leg's engine")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
