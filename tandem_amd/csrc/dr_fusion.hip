@@ -37,6 +37,7 @@
 
 #include "dr_common.h"
 #include "fusion_host.h"  // the host half of the map: block keys (kBS), reach bounds, host store, chunk planner
+#include "hip_owner.h"    // HipOwner, DeviceBuf, PinnedBuf: what the engine takes from the runtime
 #define DR_MC_CONST __device__ static const
 #include "mc_tables.h"
 
@@ -162,6 +163,14 @@ __device__ inline bool pack_key(I3 p, unsigned long long &k) {
   if (p.x < -B || p.x >= B || p.y < -B || p.y >= B || p.z < -B || p.z >= B) return false;
   k = ((unsigned long long)(unsigned)(p.x + B) << 42) | ((unsigned long long)(unsigned)(p.y + B) << 21) | (unsigned long long)(unsigned)(p.z + B);
   return true;
+}
+// index of block p among the n ascending packed keys (binary search), -1 if it is not there
+__device__ inline int find_sorted_key(const unsigned long long *keys, int n, I3 p) {
+  unsigned long long key;
+  if (!pack_key(p, key)) return -1;
+  int lo = 0, hi = n;
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (keys[mid] < key) lo = mid + 1; else hi = mid; }
+  return lo < n && keys[lo] == key ? lo : -1;
 }
 __device__ inline I3 unpack_key(unsigned long long k) {
   const int B = 1 << 20;
@@ -641,438 +650,9 @@ __global__ __launch_bounds__(256, DR_INTEGRATE_WAVES) void k_integrate(const Fus
 
 // ------------------------------------------------------------------ raycast
 }  // namespace dr
-#include "render_stage_kernels.h"  // STAGED = true: blocks absent from the pool resolve among the host blocks staged for the render
+#include "raycast_kernels.h"  // k_raycast2 / k_raycast_fix (k_raycast: parity build), resident and STAGED (map-scope renders)
 namespace dr {
 
-template <bool STAGED = false>
-__device__ inline Voxel get_voxel(const FusionDev &d, F3 p, const StageArg<STAGED> &sg = {}) {  // tsdf_volume.cu:147-160
-  Voxel z; z.sdf = 0.f; z.c[0] = z.c[1] = z.c[2] = 0; z.weight = 0;
-  I3 blk; int local;
-  world_to_block_local(d.o, p, blk, local);
-  const int b = find_block(d, blk);
-  if constexpr (STAGED) {  // the literal pass resolves through the pool, then the staging
-    const int s = b < 0 ? stage_find_sorted(sg, blk) : -1;
-    if (b < 0 && s < 0) return z;
-    return *(b >= 0 ? d.vox + (size_t)b * (kBS * kBS * kBS) + local : sg.vox + (size_t)s * (kBS * kBS * kBS) + local);
-  }
-  if (b < 0) return z;
-  return d.vox[(size_t)b * (kBS * kBS * kBS) + local];
-}
-
-template <bool STAGED = false>
-__device__ inline Voxel get_interpolated_voxel(const FusionDev &d, F3 pos, const StageArg<STAGED> &sg = {}) {  // tsdf_volume.cu:161-289
-  const Voxel v0 = get_voxel<STAGED>(d, pos, sg);
-  if (v0.weight == 0) return v0;
-  const float vs = d.o.voxel_size, hv = vs / 2.0f;
-  F3 pd; pd.x = pos.x - hv; pd.y = pos.y - hv; pd.z = pos.z - hv;
-  F3 vp; vp.x = pos.x / vs; vp.y = pos.y / vs; vp.z = pos.z / vs;
-  F3 w; w.x = vp.x - floorf(vp.x); w.y = vp.y - floorf(vp.y); w.z = vp.z - floorf(vp.z);
-  float dist = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f;
-  Voxel v = v0;
-  // corner order of the reference: 000 100 010 001 110 011 101 111
-  const int order[8] = {0, 1, 2, 4, 3, 6, 5, 7};  // bit0 = x, bit1 = y, bit2 = z
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int c = order[k];
-    F3 q; q.x = pd.x + ((c & 1) ? vs : 0.0f); q.y = pd.y + ((c & 2) ? vs : 0.0f); q.z = pd.z + ((c & 4) ? vs : 0.0f);
-    v = get_voxel<STAGED>(d, q, sg);
-    const float a = (c & 1) ? w.x : (1.0f - w.x), b = (c & 2) ? w.y : (1.0f - w.y), cc = (c & 4) ? w.z : (1.0f - w.z);
-    const float wt = a * b * cc;
-    const Voxel &src = v.weight == 0 ? v0 : v;
-    dist += wt * src.sdf;
-    cx = cx + (float)src.c[0] * wt;
-    cy = cy + (float)src.c[1] * wt;
-    cz = cz + (float)src.c[2] * wt;
-  }
-  v.c[0] = f2u8(cx); v.c[1] = f2u8(cy); v.c[2] = f2u8(cz);
-  v.weight = v0.weight;
-  v.sdf = dist;
-  return v;
-}
-
-#ifdef DR_PARITY_HOOKS  // the literal first generation as a whole-image kernel (DR_RAYCAST_V1); k_raycast_fix below is its per-pixel form
-__global__ __launch_bounds__(64) void k_raycast(const FusionDev d, const Mat pose, unsigned char *__restrict__ bgr,
-                                                float *__restrict__ depth_out) {
-  const drf_options_t &o = d.o;
-  const int size = o.height * o.width;
-  // One wave = one 8x8 pixel tile (a row of 64 pixels fans out over ~6 voxel blocks at 2 m, a tile over 1-2, and
-  // PMC showed 4.5 GB of L2 misses per 640x480 render with row-wise waves); tiles are dealt to the 8 XCDs in bands of
-  // rows so that neighbouring tiles share an L2.  Sizes that are not multiples of 8 keep the row-wise order.
-  const bool tiled = (o.width % 8 == 0) && (o.height % 8 == 0) && blockDim.x == 64;
-  const int ntile = tiled ? size / 64 : 0, per_xcd = (ntile + 7) >> 3;
-  for (int w0 = blockIdx.x; w0 < (tiled ? 8 * per_xcd : (size + 63) / 64); w0 += gridDim.x) {
-    int i;
-    if (tiled) {
-      const int t = (w0 & 7) * per_xcd + (w0 >> 3);
-      if (t >= ntile) continue;
-      const int tw = o.width / 8, tx = t % tw, ty = t / tw;
-      i = (ty * 8 + (threadIdx.x >> 3)) * o.width + tx * 8 + (threadIdx.x & 7);
-    } else {
-      i = w0 * 64 + threadIdx.x;
-      if (i >= size) continue;
-    }
-    float cur = 0.f;
-    while (cur < o.max_sensor_depth) {
-      const Voxel v = get_interpolated_voxel(d, xform(pose, point3d(o, i, cur)));
-      if (v.weight == 0) cur += o.truncation_distance; else cur += v.sdf;
-      if (v.weight != 0 && v.sdf < o.voxel_size) break;
-    }
-    if (cur < o.max_sensor_depth) {
-      const Voxel v = get_interpolated_voxel(d, xform(pose, point3d(o, i, cur)));
-      bgr[3 * i] = v.c[0]; bgr[3 * i + 1] = v.c[1]; bgr[3 * i + 2] = v.c[2];
-      depth_out[i] = cur;
-    } else {
-      bgr[3 * i] = bgr[3 * i + 1] = bgr[3 * i + 2] = 0;
-      depth_out[i] = 0.0f;
-    }
-  }
-}
-
-#endif  // DR_PARITY_HOOKS
-
-// ---- ray-cast, second generation: same arithmetic, a fraction of the instructions and of the dependent loads ----
-// What GetInterpolatedVoxel costs when it is written out literally (above): 9 GetVoxel calls = 27 IEEE divisions by
-// voxel_size + 3 for the weights, and 9 block look-ups, each a probe chain into the hash table -- per sphere-tracing step,
-// ~100 steps per pixel.  Here:
-//   * every division by voxel_size / fx / fy is div_exact (3 instructions, verified equal to the IEEE quotient);
-//   * the 8 dual-grid corners differ per axis in ONE of two coordinates, so 6 voxel coordinates are computed, not 24
-//     (each coordinate goes through exactly the expression the reference evaluates for it);
-//   * blocks are looked up in the dense grid (one load), once per distinct block of the 2x2x2 corner set (almost
-//     always one) and shared with the centre voxel's look-up; the 8 corner loads are then independent of each other;
-//   * colour is only interpolated for the final sample of a ray.
-template <bool FAST>
-__device__ inline float div_by(float a, float b, float y) { return FAST ? div_exact(a, b, y) : a / b; }
-
-// Block look-up of the fast ray-caster: dense grid only.  A coordinate outside the grid is absent if the table holds no
-// block at all (d.n_alloc[3] counts table inserts; the usual case), otherwise the pixel bails out to the literal pass.
-__device__ inline int find_block_xyz(const FusionDev &d, int x, int y, int z, bool far_blocks, bool &bail) {
-  I3 p; p.x = x; p.y = y; p.z = z;
-  unsigned idx;
-  if (grid_index(p, idx)) return d.grid[idx] - 1;
-  if (far_blocks) bail = true;
-  return -1;
-}
-
-template <bool FAST, bool COLOUR>
-__device__ inline Voxel interp_voxel(const FusionDev &d, F3 pos, bool far_blocks, bool &bail, int *empty_cell = nullptr) {  // == get_interpolated_voxel(d, pos), tsdf_volume.cu:161-289
-  const float vs = d.o.voxel_size, hv = vs / 2.0f, y = d.vs_rcp;
-  Voxel zero; zero.sdf = 0.f; zero.c[0] = zero.c[1] = zero.c[2] = 0; zero.weight = 0;
-  // GetVoxel(position): WorldToGlobalVoxel (tsdf_volume.cu:109-113), then block = floor(g / 8), local = g mod 8
-  const float qx = div_by<FAST>(pos.x, vs, y), qy = div_by<FAST>(pos.y, vs, y), qz = div_by<FAST>(pos.z, vs, y);
-  const int g0x = f2i(qx + signf_(pos.x) * 0.5f), g0y = f2i(qy + signf_(pos.y) * 0.5f), g0z = f2i(qz + signf_(pos.z) * 0.5f);
-  const int c0x = g0x >> 3, c0y = g0y >> 3, c0z = g0z >> 3;
-  const int b0 = find_block_xyz(d, c0x, c0y, c0z, far_blocks, bail);
-  if (empty_cell) {  // dense-grid cell of the centre voxel's block when that block does not exist (else -1)
-    I3 c; c.x = c0x; c.y = c0y; c.z = c0z;
-    unsigned ci;
-    *empty_cell = (b0 < 0 && grid_index(c, ci)) ? (int)ci : -1;
-  }
-  Voxel v0 = zero;
-  if (b0 >= 0) v0 = load_voxel(d.vox + (size_t)b0 * 512 + (((g0x & 7) << 6) | ((g0y & 7) << 3) | (g0z & 7)));
-  if (v0.weight == 0) return v0;
-  const float pdx = pos.x - hv, pdy = pos.y - hv, pdz = pos.z - hv;
-  const float wx = qx - floorf(qx), wy = qy - floorf(qy), wz = qz - floorf(qz);  // voxel_position = position / voxel_size is q
-  // per-axis corner coordinates: pos_dual + 0.0f and pos_dual + voxel_size
-  int gx[2], gy[2], gz[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const float ax = pdx + (j ? vs : 0.0f), ay = pdy + (j ? vs : 0.0f), az = pdz + (j ? vs : 0.0f);
-    gx[j] = f2i(div_by<FAST>(ax, vs, y) + signf_(ax) * 0.5f);
-    gy[j] = f2i(div_by<FAST>(ay, vs, y) + signf_(ay) * 0.5f);
-    gz[j] = f2i(div_by<FAST>(az, vs, y) + signf_(az) * 0.5f);
-  }
-  const int bx0 = gx[0] >> 3, bx1 = gx[1] >> 3, by0 = gy[0] >> 3, by1 = gy[1] >> 3, bz0 = gz[0] >> 3, bz1 = gz[1] >> 3;
-  auto look = [&](int x, int yy, int z) { return (x == c0x && yy == c0y && z == c0z) ? b0 : find_block_xyz(d, x, yy, z, far_blocks, bail); };
-  int P[8];  // pool block of corner c (bit0 = x, bit1 = y, bit2 = z)
-  P[0] = look(bx0, by0, bz0);
-  P[1] = bx1 == bx0 ? P[0] : look(bx1, by0, bz0);
-  P[2] = by1 == by0 ? P[0] : look(bx0, by1, bz0);
-  P[3] = bx1 == bx0 ? P[2] : (by1 == by0 ? P[1] : look(bx1, by1, bz0));
-  P[4] = bz1 == bz0 ? P[0] : look(bx0, by0, bz1);
-  P[5] = bz1 == bz0 ? P[1] : (bx1 == bx0 ? P[4] : look(bx1, by0, bz1));
-  P[6] = bz1 == bz0 ? P[2] : (by1 == by0 ? P[4] : look(bx0, by1, bz1));
-  P[7] = bz1 == bz0 ? P[3] : (bx1 == bx0 ? P[6] : (by1 == by0 ? P[5] : look(bx1, by1, bz1)));
-  Voxel cv[8];
-  // The two z-corners of an (x, y) pair are neighbours in memory (z is the fastest voxel index) whenever they lie in the
-  // same block: one 16-byte load then brings both -- 4 gathers per sample instead of 8 for 7 lanes in 8.
-  if (bz1 == bz0 && gz[1] == gz[0] + 1) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int local = ((gx[c & 1] & 7) << 6) | ((gy[(c >> 1) & 1] & 7) << 3) | (gz[0] & 7);
-      cv[c] = zero; cv[c | 4] = zero;
-      if (P[c] >= 0) {
-        const Voxel16 t = *reinterpret_cast<const Voxel16 *>(d.vox + (size_t)P[c] * 512 + local);
-        cv[c] = unpack_voxel(t.a, t.b); cv[c | 4] = unpack_voxel(t.c, t.d);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      const int local = ((gx[c & 1] & 7) << 6) | ((gy[(c >> 1) & 1] & 7) << 3) | (gz[(c >> 2) & 1] & 7);
-      cv[c] = zero;
-      if (P[c] >= 0) cv[c] = load_voxel(d.vox + (size_t)P[c] * 512 + local);
-    }
-  }
-  float dist = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f;
-  const int order[8] = {0, 1, 2, 4, 3, 6, 5, 7};  // the reference's corner order: 000 100 010 001 110 011 101 111
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int c = order[k];
-    const float a = (c & 1) ? wx : (1.0f - wx), b = (c & 2) ? wy : (1.0f - wy), cc = (c & 4) ? wz : (1.0f - wz);
-    const float wt = a * b * cc;
-    const Voxel &src = cv[c].weight == 0 ? v0 : cv[c];
-    dist += wt * src.sdf;
-    if (COLOUR) {
-      cx = cx + (float)src.c[0] * wt;
-      cy = cy + (float)src.c[1] * wt;
-      cz = cz + (float)src.c[2] * wt;
-    }
-  }
-  Voxel v;
-  v.c[0] = f2u8(cx); v.c[1] = f2u8(cy); v.c[2] = f2u8(cz);
-  v.weight = v0.weight;
-  v.sdf = dist;
-  return v;
-}
-// interp_voxel in TWO memory round trips.  The statistics of the bench loop (DR_RAYCAST_STATS, r3): a ray takes ~62
-// samples, 52 of them inside allocated, carved space (the reference allocates every block between the camera and the
-// surface), and all lanes of a wave need about the same number -- the kernel is a chain of dependent gathers, each as slow
-// as the slowest of a wave's 64 lanes (some lane always misses L2).  interp_voxel has four dependent stages per sample
-// (centre block -> centre voxel -> neighbour blocks -> corner voxels); here every block look-up (centre + the 2x2x2 corner
-// blocks, computed from the position alone) is issued at once, then every voxel load (centre + 8 corners, unconditional
-// 8-byte loads from a clamped address, masked afterwards) at once.  Same values, same arithmetic, same result.
-// STAGED = true (map-scope renders): interp_voxel2_staged, render_stage_kernels.h -- the same two round trips over pool and staging.
-template <bool FAST, bool COLOUR, bool STAGED = false>
-__device__ inline Voxel interp_voxel2(const FusionDev &d, F3 pos, bool far_blocks, bool &bail, int *empty_cell = nullptr, const StageArg<STAGED> &sg = {}) {
-  if constexpr (STAGED) return interp_voxel2_staged<FAST, COLOUR>(d, sg, pos, far_blocks, bail, empty_cell);
-  const float vs = d.o.voxel_size, hv = vs / 2.0f, y = d.vs_rcp;
-  Voxel zero; zero.sdf = 0.f; zero.c[0] = zero.c[1] = zero.c[2] = 0; zero.weight = 0;
-  const float qx = div_by<FAST>(pos.x, vs, y), qy = div_by<FAST>(pos.y, vs, y), qz = div_by<FAST>(pos.z, vs, y);
-  const int g0x = f2i(qx + signf_(pos.x) * 0.5f), g0y = f2i(qy + signf_(pos.y) * 0.5f), g0z = f2i(qz + signf_(pos.z) * 0.5f);
-  const float pdx = pos.x - hv, pdy = pos.y - hv, pdz = pos.z - hv;
-  int gx[2], gy[2], gz[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const float ax = pdx + (j ? vs : 0.0f), ay = pdy + (j ? vs : 0.0f), az = pdz + (j ? vs : 0.0f);
-    gx[j] = f2i(div_by<FAST>(ax, vs, y) + signf_(ax) * 0.5f);
-    gy[j] = f2i(div_by<FAST>(ay, vs, y) + signf_(ay) * 0.5f);
-    gz[j] = f2i(div_by<FAST>(az, vs, y) + signf_(az) * 0.5f);
-  }
-  // ---- round trip 1: nine block look-ups (identical addresses coalesce in the load unit) ----
-  auto cell_of = [&](int x, int yy, int z, bool &ok) { I3 p; p.x = x; p.y = yy; p.z = z; unsigned idx = 0; ok = grid_index(p, idx); return ok ? idx : 0u; };
-  bool ok0, okc[8];
-  const unsigned i0 = cell_of(g0x >> 3, g0y >> 3, g0z >> 3, ok0);
-  unsigned ic[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) ic[c] = cell_of(gx[c & 1] >> 3, gy[(c >> 1) & 1] >> 3, gz[(c >> 2) & 1] >> 3, okc[c]);
-  int b0 = d.grid[i0];
-  int P[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) P[c] = d.grid[ic[c]];
-  b0 = ok0 ? b0 - 1 : -1;
-  if (!ok0 && far_blocks) bail = true;
-  if (empty_cell) *empty_cell = (b0 < 0 && ok0) ? (int)i0 : -1;
-  if (b0 < 0) return zero;  // (weight 0: the corner look-ups above were speculative)
-#pragma unroll
-  for (int c = 0; c < 8; ++c) P[c] = okc[c] ? P[c] - 1 : -1;
-  // ---- round trip 2: the centre voxel and the eight corners ----
-  const Voxel8 t0 = *reinterpret_cast<const Voxel8 *>(d.vox + (size_t)b0 * 512 + (((g0x & 7) << 6) | ((g0y & 7) << 3) | (g0z & 7)));
-  Voxel8 tc[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const int local = ((gx[c & 1] & 7) << 6) | ((gy[(c >> 1) & 1] & 7) << 3) | (gz[(c >> 2) & 1] & 7);
-    tc[c] = *reinterpret_cast<const Voxel8 *>(d.vox + (size_t)(P[c] >= 0 ? P[c] : b0) * 512 + local);
-  }
-  const Voxel v0 = unpack_voxel(t0.lo, t0.hi);
-  if (v0.weight == 0) return v0;
-  // the far-block bail of the literal order: a corner outside the dense grid only matters once the centre voxel has weight
-#pragma unroll
-  for (int c = 0; c < 8; ++c) if (!okc[c] && far_blocks) bail = true;
-  const float wx = qx - floorf(qx), wy = qy - floorf(qy), wz = qz - floorf(qz);
-  float dist = 0.0f, cx = 0.0f, cy = 0.0f, cz = 0.0f;
-  const int order[8] = {0, 1, 2, 4, 3, 6, 5, 7};  // the reference's corner order: 000 100 010 001 110 011 101 111
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int c = order[k];
-    const float a = (c & 1) ? wx : (1.0f - wx), b = (c & 2) ? wy : (1.0f - wy), cc = (c & 4) ? wz : (1.0f - wz);
-    const float wt = a * b * cc;
-    Voxel cvx = unpack_voxel(tc[c].lo, tc[c].hi);
-    if (P[c] < 0) cvx = zero;
-    const Voxel &src = cvx.weight == 0 ? v0 : cvx;
-    dist += wt * src.sdf;
-    if (COLOUR) {
-      cx = cx + (float)src.c[0] * wt;
-      cy = cy + (float)src.c[1] * wt;
-      cz = cz + (float)src.c[2] * wt;
-    }
-  }
-  Voxel v;
-  v.c[0] = f2u8(cx); v.c[1] = f2u8(cy); v.c[2] = f2u8(cz);
-  v.weight = v0.weight;
-  v.sdf = dist;
-  return v;
-}
-// Round 4 measured two more samplers against this one on the bench map (profiles/r04_experiments.txt, 2) and removed both: PAIRED
-// gathers (one 8-byte load for the two grid cells and one 16-byte load for the two voxels of a z-corner pair: 4 + 4 gathers, half of
-// them not naturally aligned) and the centre voxel SELECTED from the eight corners instead of fetched (8 + 8 gathers, 14 more selects):
-// 0.43 ms per render against 0.34 for this sampler.  The kernel is bound by the L1's tag path (PMC, r3: 131.6 M line accesses per
-// render, 20 per gather instruction -- the 64 rays of a tile sit in 64 different z-columns of a block), and neither variant lowers the
-// number of distinct lines a sample touches; both add instructions.
-// Pixels are flagged for the literal pass (k_raycast_fix) with depth -1 when a sample leaves the range div_exact was
-// verified on, or needs a block outside the dense grid while the table is not empty.  Neither happens in a room-sized map.
-// How many further samples q + j * trunc * dir (j = 1..k) stay inside the superblock of `cell`, shrunk by one voxel on
-// every side.  Approximate float arithmetic on purpose: it only has to be conservative (the margin is 5 mm against
-// errors of ~1e-5 m), the samples' own positions are never used.
-template <int SH>
-__device__ inline int skip_steps(unsigned cell, F3 q, F3 dirw, F3 inv_dir, float vs, float inv_trunc) {
-  constexpr int H = 1 << (kGridBits - 1);
-  constexpr unsigned M = (1u << kGridBits) - 1, SM = ~((1u << SH) - 1u);
-  constexpr float hi_off = (float)(kBS << SH) - 1.5f;  // the superblock's n = 8 << SH voxels cover [(g - 0.5) vs, (g + n - 0.5) vs)
-  const float gx = (float)((int)(((cell >> (2 * kGridBits)) & SM) - H) * kBS);
-  const float gy = (float)((int)((((cell >> kGridBits) & M) & SM) - H) * kBS);
-  const float gz = (float)((int)(((cell & M) & SM) - H) * kBS);
-  float t = 1e30f;
-  if (dirw.x != 0.f) t = fminf(t, ((gx + (dirw.x > 0.f ? hi_off : 0.5f)) * vs - q.x) * inv_dir.x);
-  if (dirw.y != 0.f) t = fminf(t, ((gy + (dirw.y > 0.f ? hi_off : 0.5f)) * vs - q.y) * inv_dir.y);
-  if (dirw.z != 0.f) t = fminf(t, ((gz + (dirw.z > 0.f ? hi_off : 0.5f)) * vs - q.z) * inv_dir.z);
-  return (int)fminf(t * inv_trunc - 0.5f, 256.f);
-}
-// STATS (DR_RAYCAST_STATS=1, a measuring build of the same loop): per-launch totals of the ray loop in st[] --
-// [0] lane iterations, [1] longest ray, [2] sum over waves of their longest ray (what the wave pays), [3] samples whose
-// centre block does not exist, [4] skip events, [5] skipped steps, [6] samples with weight != 0, [7] waves, [8..] histogram
-// of the waves' longest rays in buckets of 16 iterations.
-// SAMPLER: 1 = interp_voxel2 (9 + 9 gathers in two round trips; the product's), 0 = interp_voxel (round 2's four stages; parity build)
-// STAGED: the map-scope form (render_stage_kernels.h) -- look-ups fall through to the staged host blocks, a superblock is skipped
-// only if neither the pool nor the staging holds a block in it, and a staged block outside the dense grid sends the pixel to the
-// literal pass like a table block does.  The product's sampler only.
-// The staging is a trailing parameter PACK -- one RenderStage when STAGED, nothing otherwise -- so that the resident instances keep
-// their kernel arguments, and with them their instructions, exactly.
-template <bool FAST, bool STATS = false, int SAMPLER = 1, bool STAGED = false, class... SG>
-__global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat pose, unsigned char *__restrict__ bgr,
-                                                 float *__restrict__ depth_out, int *__restrict__ n_flagged, unsigned long long *st,
-                                                 const SG... stage) {
-  static_assert(!STAGED || (SAMPLER == 1 && !STATS), "the staged ray-cast exists for the product's sampler");
-  static_assert(sizeof...(SG) == (STAGED ? 1 : 0), "one RenderStage for the staged form, none otherwise");
-  const StageArg<STAGED> &sg = stage_arg(stage...);
-  const drf_options_t &o = d.o;
-  const int size = o.height * o.width;
-  const bool far_blocks = d.n_alloc[3] != 0 || stage_far(sg);
-  // one wave = one 8x8 pixel tile, tiles dealt to the 8 XCDs in bands of rows (see k_raycast)
-  const bool tiled = (o.width % 8 == 0) && (o.height % 8 == 0) && blockDim.x == 64;
-  const int ntile = tiled ? size / 64 : 0, per_xcd = (ntile + 7) >> 3;
-  for (int w0 = blockIdx.x; w0 < (tiled ? 8 * per_xcd : (size + 63) / 64); w0 += gridDim.x) {
-    int i;
-    if (tiled) {
-      const int t = (w0 & 7) * per_xcd + (w0 >> 3);
-      if (t >= ntile) continue;
-      const int tw = o.width / 8, tx = t % tw, ty = t / tw;
-      i = (ty * 8 + (threadIdx.x >> 3)) * o.width + tx * 8 + (threadIdx.x & 7);
-    } else {
-      i = w0 * 64 + threadIdx.x;
-      if (i >= size) continue;
-    }
-    // GetPoint3d(i, cur, sensor) (utils.h:93-101): x = (u - cx) * z / fx, the pixel part is constant along the ray
-    const int pv = i / o.width, pu = i - o.width * pv;
-    const float ucx = (float)pu - o.cx, vcy = (float)pv - o.cy;
-    bool bail = false;
-    auto sample_pos = [&](float cur) {
-      F3 p;
-      p.z = cur;
-      const float tx = ucx * cur, ty = vcy * cur;
-      p.x = div_by<FAST>(tx, o.fx, d.fx_rcp);
-      p.y = div_by<FAST>(ty, o.fy, d.fy_rcp);
-      const F3 q = xform(pose, p);
-      if (FAST && !(in_fast_range(q.x) && in_fast_range(q.y) && in_fast_range(q.z) && in_fast_range(tx) && in_fast_range(ty))) bail = true;
-      return q;
-    };
-    // Empty-space skip.  A sample whose centre voxel lies in a block that does not exist returns weight 0 and the ray
-    // advances by the truncation distance (2 cm at TANDEM's settings: ~150 look-ups across a room).  d.super[] marks the
-    // superblocks (32^3 and 8^3 blocks) of the dense grid that hold any block at all; while the ray stays inside an empty one
-    // (shrunk by a voxel on every side: three orders of magnitude above the float error of the approximate ray used
-    // here) every sample is known to return weight 0, so `cur` takes the same sequence of float additions -- the
-    // result is bit-identical -- without transforming, dividing or loading anything.  DR_RAYCAST_NO_SKIP=1 turns it off.
-    F3 dirw, inv_dir;
-    {
-      const float lx = ucx / o.fx, ly = vcy / o.fy;
-      dirw.x = pose.m[0] * lx + pose.m[1] * ly + pose.m[2];
-      dirw.y = pose.m[4] * lx + pose.m[5] * ly + pose.m[6];
-      dirw.z = pose.m[8] * lx + pose.m[9] * ly + pose.m[10];
-      inv_dir.x = 1.0f / dirw.x; inv_dir.y = 1.0f / dirw.y; inv_dir.z = 1.0f / dirw.z;
-    }
-    const float inv_trunc = 1.0f / o.truncation_distance, vs = o.voxel_size;
-    float cur = 0.f;
-    unsigned n_it = 0, n_miss = 0, n_skip = 0, n_skipped = 0, n_full = 0;
-    while (cur < o.max_sensor_depth) {
-      const F3 q = sample_pos(cur);
-      int cell = -1;
-      const Voxel v = SAMPLER == 1 ? interp_voxel2<FAST, false, STAGED>(d, q, far_blocks, bail, (STAGED || d.super[0]) ? &cell : nullptr, sg)
-                                   : interp_voxel<FAST, false>(d, q, far_blocks, bail, d.super[0] ? &cell : nullptr);
-      if (STAGED && !d.super[0]) cell = -1;  // (the staged sampler always reports the cell: its pointer stays a plain local)
-      if (bail) break;
-      if (STATS) { ++n_it; n_miss += cell >= 0; n_full += v.weight != 0; }
-      if (v.weight == 0) {
-        cur += o.truncation_distance;
-        if (cell >= 0) {
-          int k = 0;
-          if (d.super[0][super_index<kSuperShift[0]>((unsigned)cell)] == 0 && stage_super_empty<0>(sg, (unsigned)cell)) k = skip_steps<kSuperShift[0]>((unsigned)cell, q, dirw, inv_dir, vs, inv_trunc);
-          else if (d.super[1][super_index<kSuperShift[1]>((unsigned)cell)] == 0 && stage_super_empty<1>(sg, (unsigned)cell)) k = skip_steps<kSuperShift[1]>((unsigned)cell, q, dirw, inv_dir, vs, inv_trunc);
-          if (STATS && k > 0) { ++n_skip; n_skipped += k; }
-          for (; k > 0 && cur < o.max_sensor_depth; --k) cur += o.truncation_distance;
-        }
-      } else cur += v.sdf;
-      if (v.weight != 0 && v.sdf < o.voxel_size) break;
-    }
-    if (STATS) {
-      unsigned mx = n_it, sum = n_it, sm = n_miss, ss = n_skip, sk = n_skipped, sf = n_full;
-      for (int off = 32; off; off >>= 1) {
-        mx = max(mx, (unsigned)__shfl_xor((int)mx, off)); sum += __shfl_xor((int)sum, off); sm += __shfl_xor((int)sm, off);
-        ss += __shfl_xor((int)ss, off); sk += __shfl_xor((int)sk, off); sf += __shfl_xor((int)sf, off);
-      }
-      if (threadIdx.x == 0) {
-        atomicAdd(&st[0], (unsigned long long)sum); atomicMax(&st[1], (unsigned long long)mx); atomicAdd(&st[2], (unsigned long long)mx);
-        atomicAdd(&st[3], (unsigned long long)sm); atomicAdd(&st[4], (unsigned long long)ss); atomicAdd(&st[5], (unsigned long long)sk);
-        atomicAdd(&st[6], (unsigned long long)sf); atomicAdd(&st[7], 1ull); atomicAdd(&st[8 + min(mx / 16u, 23u)], 1ull);
-      }
-    }
-    if (!bail && cur < o.max_sensor_depth) {
-      const F3 qf = sample_pos(cur);
-      const Voxel v = SAMPLER == 1 ? interp_voxel2<FAST, true, STAGED>(d, qf, far_blocks, bail, nullptr, sg) : interp_voxel<FAST, true>(d, qf, far_blocks, bail);
-      bgr[3 * i] = v.c[0]; bgr[3 * i + 1] = v.c[1]; bgr[3 * i + 2] = v.c[2];
-      depth_out[i] = cur;
-    } else {
-      bgr[3 * i] = bgr[3 * i + 1] = bgr[3 * i + 2] = 0;
-      depth_out[i] = 0.0f;
-    }
-    if (bail) { depth_out[i] = -1.0f; atomicAdd(n_flagged, 1); }
-  }
-}
-// The literal ray-caster for the pixels k_raycast2 flagged; exits at once when there are none.
-template <bool STAGED = false, class... SG>
-__global__ __launch_bounds__(64) void k_raycast_fix(const FusionDev d, const Mat pose, unsigned char *__restrict__ bgr,
-                                                    float *__restrict__ depth_out, int *__restrict__ n_flagged, const SG... stage) {
-  static_assert(sizeof...(SG) == (STAGED ? 1 : 0), "one RenderStage for the staged form, none otherwise");
-  const StageArg<STAGED> &sg = stage_arg(stage...);
-  if (*n_flagged == 0) return;
-  const drf_options_t &o = d.o;
-  const int size = o.height * o.width;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < size; i += gridDim.x * blockDim.x) {
-    if (!(depth_out[i] == -1.0f)) continue;
-    float cur = 0.f;
-    while (cur < o.max_sensor_depth) {
-      const Voxel v = get_interpolated_voxel<STAGED>(d, xform(pose, point3d(o, i, cur)), sg);
-      if (v.weight == 0) cur += o.truncation_distance; else cur += v.sdf;
-      if (v.weight != 0 && v.sdf < o.voxel_size) break;
-    }
-    if (cur < o.max_sensor_depth) {
-      const Voxel v = get_interpolated_voxel<STAGED>(d, xform(pose, point3d(o, i, cur)), sg);
-      bgr[3 * i] = v.c[0]; bgr[3 * i + 1] = v.c[1]; bgr[3 * i + 2] = v.c[2];
-      depth_out[i] = cur;
-    } else {
-      bgr[3 * i] = bgr[3 * i + 1] = bgr[3 * i + 2] = 0;
-      depth_out[i] = 0.0f;
-    }
-  }
-}
 __global__ void k_zero_int(int *p) { if (threadIdx.x == 0 && blockIdx.x == 0) *p = 0; }
 
 __global__ __launch_bounds__(256) void k_fold_counter(unsigned long long *cnt, int *req_count, const unsigned *wg_upd, int n_wg) {
@@ -1137,100 +717,16 @@ __global__ __launch_bounds__(256) void k_publish(const unsigned char *__restrict
 }
 
 // ------------------------------------------------------------------ engine
-// Owner of what the engine takes from the runtime for its lifetime: device and pinned buffers, events, streams.  All of it is
-// released with the owner -- buffers first, then the events and streams that work on them used -- also when the engine's
-// constructor throws half way.  The raw pointers and handles go where they are used (FusionDev, StreamDev, McArgs: by value).
-class HipOwner {
- public:
-  HipOwner() = default;
-  HipOwner(const HipOwner &) = delete;
-  void operator=(const HipOwner &) = delete;
-  ~HipOwner() {
-    if (dev_.empty() && pin_.empty() && ev_.empty() && st_.empty()) return;  // nothing taken: no device of ours to wait for
-    (void)hipDeviceSynchronize();
-    for (void *p : dev_) (void)hipFree(p);
-    for (void *p : pin_) (void)hipHostFree(p);
-    for (hipEvent_t e : ev_) (void)hipEventDestroy(e);
-    for (hipStream_t s : st_) (void)hipStreamDestroy(s);
-  }
-  // device memory, cleared on stream `zero_on` if one is given
-  template <class T> T *device(size_t n, hipStream_t zero_on = nullptr) {
-    T *p = (T *)take(dev_, [&](void **q) { *q = dalloc<T>(n); });
-    if (zero_on) DR_HIP(hipMemsetAsync(p, 0, n * sizeof(T), zero_on));
-    return p;
-  }
-  // page-locked host memory; as_device: the address the kernels use for it
-  template <class T> T *pinned(size_t n, T **as_device = nullptr) {
-    T *p = (T *)take(pin_, [&](void **q) { DR_HIP(hipHostMalloc(q, n * sizeof(T), hipHostMallocDefault)); });
-    if (as_device) DR_HIP(hipHostGetDevicePointer((void **)as_device, p, 0));
-    return p;
-  }
-  hipEvent_t event(unsigned flags = hipEventDisableTiming) {
-    return take(ev_, [&](hipEvent_t *e) { DR_HIP(hipEventCreateWithFlags(e, flags)); });
-  }
-  hipStream_t stream(int priority = 0) {
-    return take(st_, [&](hipStream_t *q) { DR_HIP(hipStreamCreateWithPriority(q, hipStreamNonBlocking, priority)); });
-  }
-
- private:
-  // the slot first, then what goes into it: nothing is taken that could not be recorded
-  template <class H, class Make> H take(std::vector<H> &v, Make make) {
-    v.push_back(H());
-    make(&v.back());
-    return v.back();
-  }
-  std::vector<void *> dev_, pin_;
-  std::vector<hipEvent_t> ev_;
-  std::vector<hipStream_t> st_;
-};
-// Device scratch that grows with its use; contents are not kept.  `st`: the stream whose work may still read the old allocation.
-template <class T>
-class DeviceBuf {
- public:
-  DeviceBuf() = default;
-  DeviceBuf(const DeviceBuf &) = delete;
-  void operator=(const DeviceBuf &) = delete;
-  ~DeviceBuf() { (void)hipFree(p_); }
-  void reserve(size_t n, hipStream_t st) {
-    if (n <= cap_) return;
-    DR_HIP(hipStreamSynchronize(st));
-    if (p_) DR_HIP(hipFree(p_));
-    p_ = nullptr; cap_ = 0;
-    p_ = dalloc<T>(n);
-    cap_ = n;
-  }
-  T *get() const { return p_; }
-  size_t capacity() const { return cap_; }
-
- private:
-  T *p_ = nullptr;
-  size_t cap_ = 0;
-};
-
-// Page-locked host scratch that grows with its use; contents are not kept.  The caller makes sure no copy still reads the old allocation.
-template <class T>
-class PinnedBuf {
- public:
-  PinnedBuf() = default;
-  PinnedBuf(const PinnedBuf &) = delete;
-  void operator=(const PinnedBuf &) = delete;
-  ~PinnedBuf() { (void)hipHostFree(p_); }
-  void reserve(size_t n) {
-    if (n <= cap_) return;
-    if (p_) DR_HIP(hipHostFree(p_));
-    p_ = nullptr; cap_ = 0;
-    DR_HIP(hipHostMalloc((void **)&p_, n * sizeof(T), hipHostMallocDefault));
-    cap_ = n;
-  }
-  T *get() const { return p_; }
-
- private:
-  T *p_ = nullptr;
-  size_t cap_ = 0;
-};
-
 constexpr int kDefaultFusionPriority = 1;  // 0 least (the reference's), 1 normal (measured best in the TandemBackend loop), 2 greatest
 class FusionEngine {
+  struct Render {
+    hipStream_t stream;
+    unsigned char *d_bgr, *h_bgr[2], *hd_bgr[2];   // hd_*: the pinned result buffers as the device addresses them
+    float *d_depth, *h_depth[2], *hd_depth[2];
+    int *d_flag;  // pixels the fast ray-caster handed to the literal pass
+    hipEvent_t done, cast;  // result on the host / ray-cast kernels finished (the volume may be written again)
+  };
+
  public:
   FusionEngine(const drf_options_t &o, int device) : device_(device), o_(o) {
     int n = 0;
@@ -1333,26 +829,28 @@ class FusionEngine {
     if (st_radius_ > 0.0f) stream_after_scan(pose16);
     DR_HIP(hipEventRecord(int_done_, int_stream_));
   }
-  // sg: the host blocks staged for this render (map scope with stored blocks in reach), nullptr = the resident kernels
-  void launch_raycast(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P, const RenderStage *sg = nullptr) {
+  // The product's ray-cast: the flag counter cleared, the two-round-trip sampler (SAMPLER 0: round 2's, parity build), the literal pass
+  // for the pixels it flagged.  The staging is a trailing pack as in the kernels: none = resident, one RenderStage = staged.
+  template <int SAMPLER, class... SG>
+  void raycast_pass(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P, const SG &...stage) {
+    constexpr bool STAGED = sizeof...(SG) != 0;
     const dim3 grid(8 * cdiv(cdiv((int)npix_, 64), 8)), block(64);
-    if (sg) {
-      hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, d_flag);
-      FusionDev dv = d_;
-      if (raycast_no_skip_) dv.super[0] = nullptr;
-      if (d_.fast_div) hipLaunchKernelGGL((k_raycast2<true, false, 1, true>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, *sg);
-      else hipLaunchKernelGGL((k_raycast2<false, false, 1, true>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, *sg);
-      hipLaunchKernelGGL(k_raycast_fix<true>, dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag, *sg);
-      return;
-    }
-#ifdef DR_PARITY_HOOKS
-    if (raycast_v1_) { hipLaunchKernelGGL(k_raycast, grid, block, 0, st, d_, P, d_bgr, d_depth); return; }
-#endif
     hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, d_flag);
     FusionDev dv = d_;
     if (raycast_no_skip_) dv.super[0] = nullptr;  // DR_RAYCAST_NO_SKIP=1: every sample is looked up (A/B and parity hook)
-#ifdef DR_PARITY_HOOKS
+    if (d_.fast_div) hipLaunchKernelGGL((k_raycast2<true, false, SAMPLER, STAGED>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, stage...);
+    else hipLaunchKernelGGL((k_raycast2<false, false, SAMPLER, STAGED>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, stage...);
+    hipLaunchKernelGGL(k_raycast_fix<STAGED>, dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag, stage...);
+  }
+  // sg: the host blocks staged for this render (map scope with stored blocks in reach), nullptr = the resident kernels
+  void launch_raycast(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P, const RenderStage *sg = nullptr) {
+#ifdef DR_PARITY_HOOKS  // the superseded generations have no staged form (render_async refuses them)
+    const dim3 grid(8 * cdiv(cdiv((int)npix_, 64), 8)), block(64);
+    if (raycast_v1_) { hipLaunchKernelGGL(k_raycast, grid, block, 0, st, d_, P, d_bgr, d_depth); return; }
     if (raycast_stats_ && d_.fast_div) {  // DR_RAYCAST_STATS=1: a synchronous, counting launch of the same loop (prints to stderr)
+      hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, d_flag);
+      FusionDev dv = d_;
+      if (raycast_no_skip_) dv.super[0] = nullptr;
       if (!d_rstats_) d_rstats_ = own_.device<unsigned long long>(32);
       DR_HIP(hipMemsetAsync(d_rstats_, 0, 32 * 8, st));
       hipLaunchKernelGGL((k_raycast2<true, true>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, d_rstats_);
@@ -1363,26 +861,32 @@ class FusionEngine {
               h[7], (double)h[0] / (64.0 * h[7]), h[1], (double)h[2] / h[7], (double)h[3] / (64.0 * h[7]), (double)h[6] / (64.0 * h[7]), (double)h[4] / (64.0 * h[7]), (double)h[5] / (64.0 * h[7]));
       for (int i = 0; i < 24; ++i) fprintf(stderr, " %llu", h[8 + i]);
       fprintf(stderr, "\n");
-    } else
-    if (raycast_sampler_ == 0) {  // DR_RAYCAST_SAMPLER=0: the four-stage sampler of round 2 (parity hook)
-      if (d_.fast_div) hipLaunchKernelGGL((k_raycast2<true, false, 0>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr);
-      else hipLaunchKernelGGL((k_raycast2<false, false, 0>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr);
-    } else
-#endif
-    if (d_.fast_div) hipLaunchKernelGGL((k_raycast2<true, false, 1>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr);
-    else hipLaunchKernelGGL((k_raycast2<false, false, 1>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(k_raycast_fix<false>, dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag);
-  }
-  // render -> host (k_publish); DR_RENDER_D2H=copy: the two hipMemcpyAsync of round 2 (A/B hook)
-  void publish_render(int i) {
-    auto &r = renders_[i];
-    if (render_copy_) {  // (parity build only)
-      DR_HIP(hipMemcpyAsync(r.h_bgr[free_slot_], r.d_bgr, npix_ * 3, hipMemcpyDeviceToHost, r.stream));
-      DR_HIP(hipMemcpyAsync(r.h_depth[free_slot_], r.d_depth, npix_ * 4, hipMemcpyDeviceToHost, r.stream));
+      hipLaunchKernelGGL(k_raycast_fix<false>, dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag);
       return;
     }
-    hipLaunchKernelGGL(k_publish, dim3(128), dim3(256), 0, r.stream, (const unsigned char *)r.d_depth, (unsigned char *)r.hd_depth[free_slot_], npix_ * 4,
-                       (const unsigned char *)r.d_bgr, r.hd_bgr[free_slot_], npix_ * 3);
+    if (raycast_sampler_ == 0) return raycast_pass<0>(st, d_bgr, d_depth, d_flag, P);  // DR_RAYCAST_SAMPLER=0: the four-stage sampler of round 2
+#endif
+    if (sg) raycast_pass<1>(st, d_bgr, d_depth, d_flag, P, *sg);
+    else raycast_pass<1>(st, d_bgr, d_depth, d_flag, P);
+  }
+  // One render on its stream, behind the scan: ray-cast (sg: the staged host blocks it also reads, behind their staging), `cast`,
+  // hand-off to the host (k_publish; DR_RENDER_D2H=copy, parity build: the two hipMemcpyAsync of round 2), `done`.
+  // timing: three events around the ray-cast and the hand-off (bench_sequence).
+  void submit_render(Render &r, const Mat &P, const RenderStage *sg, hipEvent_t *timing = nullptr) {
+    DR_HIP(hipStreamWaitEvent(r.stream, int_done_, 0));
+    if (sg) rs_.wait_ready(r.stream);
+    if (timing) DR_HIP(hipEventRecord(timing[0], r.stream));
+    launch_raycast(r.stream, r.d_bgr, r.d_depth, r.d_flag, P, sg);
+    if (timing) DR_HIP(hipEventRecord(timing[1], r.stream));
+    DR_HIP(hipEventRecord(r.cast, r.stream));
+    if (render_copy_) {
+      DR_HIP(hipMemcpyAsync(r.h_bgr[free_slot_], r.d_bgr, npix_ * 3, hipMemcpyDeviceToHost, r.stream));
+      DR_HIP(hipMemcpyAsync(r.h_depth[free_slot_], r.d_depth, npix_ * 4, hipMemcpyDeviceToHost, r.stream));
+    } else
+      hipLaunchKernelGGL(k_publish, dim3(128), dim3(256), 0, r.stream, (const unsigned char *)r.d_depth, (unsigned char *)r.hd_depth[free_slot_], npix_ * 4,
+                         (const unsigned char *)r.d_bgr, r.hd_bgr[free_slot_], npix_ * 3);
+    if (timing) DR_HIP(hipEventRecord(timing[2], r.stream));
+    DR_HIP(hipEventRecord(r.done, r.stream));
   }
   // tsdf_volume.cu:634-700
   void render_async(const float *const *poses, int n) {
@@ -1408,16 +912,14 @@ class FusionEngine {
     const bool staged = !plan.keys.empty();  // nothing to stage: exactly the resident launches
     if (staged) sg = stage_render(plan.keys);
     for (int i = 0; i < n; ++i) {
-      Render &r = renders_[i];
       Mat P; memcpy(P.m, poses[i], 64);
-      DR_HIP(hipStreamWaitEvent(r.stream, int_done_, 0));
-      if (staged) DR_HIP(hipStreamWaitEvent(r.stream, rs_[rs_cur_].copied, 0));
-      launch_raycast(r.stream, r.d_bgr, r.d_depth, r.d_flag, P, staged ? &sg : nullptr);
-      DR_HIP(hipEventRecord(r.cast, r.stream));
-      publish_render(i);
-      DR_HIP(hipEventRecord(r.done, r.stream));
+      submit_render(renders_[i], P, staged ? &sg : nullptr);
     }
-    if (staged) release_render_stage(sg);
+    if (staged) {  // behind every ray-cast that read the slot: its flags go back to zero
+      for (auto &r : renders_) rs_.wait_for(r.cast);
+      hipLaunchKernelGGL(k_rs_clear, dim3(cdiv(sg.n, 256)), dim3(256), 0, rs_.stream(), sg.keys, sg.n, rs_super_[rs_.slot()][0], rs_super_[rs_.slot()][1]);
+      DR_HIP(hipGetLastError());
+    }
     render_stats_[0] = plan.keys.size(); render_stats_[1] = plan.keys.size() * (size_t)(8 + 4096);
     render_stats_[2] = (uint64_t)plan.whole; render_stats_[3] = waited ? 1 : 0;
   }
@@ -1673,16 +1175,8 @@ class FusionEngine {
       DR_HIP(hipEventRecord(int_done_, int_stream_));
       free_slot_ ^= 1;
       for (int i = 0; i < nr; ++i) {
-        Render &r = renders_[i];
         Mat P; memcpy(P.m, poses + 16 * s, 64);
-        DR_HIP(hipStreamWaitEvent(r.stream, int_done_, 0));
-        DR_HIP(hipEventRecord(e[4 + 3 * i], r.stream));
-        launch_raycast(r.stream, r.d_bgr, r.d_depth, r.d_flag, P);
-        DR_HIP(hipEventRecord(e[5 + 3 * i], r.stream));
-        DR_HIP(hipEventRecord(r.cast, r.stream));
-        publish_render(i);
-        DR_HIP(hipEventRecord(e[6 + 3 * i], r.stream));
-        DR_HIP(hipEventRecord(r.done, r.stream));
+        submit_render(renders_[i], P, nullptr, e + 4 + 3 * i);
       }
     }
     DR_HIP(hipDeviceSynchronize());
@@ -1860,6 +1354,13 @@ class FusionEngine {
     }
     ev_auto_ = false;
   }
+  // n stored blocks as the staging kernels read them: their keys to kdst, their voxels (4096 bytes each, in the keys' order) to vdst
+  void pack_stored(const unsigned long long *keys, size_t n, void *kdst, unsigned char *vdst) const {
+    memcpy(kdst, keys, n * 8);
+    for (size_t k = 0; k < n; ++k) memcpy(vdst + k * 4096, store_.get(keys[k]), 4096);
+  }
+  // slots of an open-addressing table over n staged blocks: a power of two, at least twice their number
+  static size_t stage_table_slots(size_t n) { size_t s = 1024; while (s < 2 * n) s <<= 1; return s; }
   // stored blocks -> the end of the pool (behind every render stream's last ray-cast).  DR_ERR_CAPACITY before anything moves
   // if they do not fit.
   void upload(const std::vector<unsigned long long> &keys) {
@@ -1871,11 +1372,8 @@ class FusionEngine {
     for (size_t b = 0; b < keys.size(); b += st_cap_) {
       if (b) DR_HIP(hipStreamSynchronize(int_stream_));  // the pinned upload is reused
       const int n = (int)std::min(keys.size() - b, (size_t)st_cap_);
-      for (int i = 0; i < n; ++i) {
-        h_in_keys_[i] = keys[b + i];
-        memcpy(h_in_vox_ + (size_t)i * 4096, store_.get(keys[b + i]), 4096);
-        store_.erase(keys[b + i]);
-      }
+      pack_stored(keys.data() + b, (size_t)n, h_in_keys_, h_in_vox_);
+      for (int i = 0; i < n; ++i) store_.erase(keys[b + i]);
       hipLaunchKernelGGL(k_in_place, dim3(std::min(cdiv(n, 4), 1024)), dim3(256), 0, int_stream_, d_, hd_in_keys_, (const uint4 *)hd_in_vox_, n);
       hipLaunchKernelGGL(k_in_finish, dim3(1), dim3(64), 0, int_stream_, d_.n_alloc, n);
       DR_HIP(hipGetLastError());
@@ -1936,67 +1434,46 @@ class FusionEngine {
     }
     return plan_render_stage(store_, o_, poses, n);
   }
-  // Two staging buffers, each a pinned / device pair of [keys | voxels] with its table and its staged superblock flags.  Everything
-  // that touches buffer b on the device is ordered on rs_stream_: copy, table clear, k_rs_build, and -- behind the cast events of
-  // the renders that read it -- k_rs_clear.  The host waits for `copied` before it packs into the pinned half again.
+  // rs_ carries [keys | voxels]; each of its two slots has a table and staged superblock flags of its own.  Everything that touches a
+  // slot on the device is ordered on rs_'s stream: copy, table clear, k_rs_build, and -- behind the cast events of the renders that
+  // read it -- k_rs_clear.
   void ensure_render_staging(size_t n) {
-    if (!rs_stream_) {
-      rs_stream_ = own_.stream();
-      for (auto &b : rs_) {
-        for (int l = 0; l < kSuperLevels; ++l) b.super[l] = own_.device<unsigned char>((size_t)1 << (3 * (kGridBits - kSuperShift[l])), rs_stream_);
-        b.copied = own_.event();
-        DR_HIP(hipEventRecord(b.copied, rs_stream_));
-      }
+    if (!rs_.stream()) {
+      rs_.open(own_);
+      for (auto &f : rs_super_)
+        for (int l = 0; l < kSuperLevels; ++l) f[l] = own_.device<unsigned char>((size_t)1 << (3 * (kGridBits - kSuperShift[l])), rs_.stream());
     }
     if (n <= rs_blocks_) return;
     const size_t want = std::min(rs_capacity(), std::max(2 * rs_blocks_, (n + 1023) & ~(size_t)1023));
     DR_HIP(hipDeviceSynchronize());  // no copy or kernel reads the old allocations
-    size_t slots = 1024;
-    while (slots < 2 * want) slots <<= 1;
-    for (auto &b : rs_) {
-      b.dev.reserve((want + 1) * 8 + want * 4096, rs_stream_);
-      b.host.reserve((want + 1) * 8 + want * 4096);
-      b.table.reserve(slots, rs_stream_);
-    }
+    rs_.reserve((want + 1) * 8 + want * 4096);
+    for (auto &t : rs_table_) t.reserve(stage_table_slots(want), rs_.stream());
     rs_blocks_ = want;
   }
   RenderStage stage_render(const std::vector<unsigned long long> &keys) {
     const size_t n = keys.size(), nk = (n + 1) & ~(size_t)1;  // voxels start 16-byte aligned
     ensure_render_staging(n);
-    rs_cur_ ^= 1;
-    RenderStageBuf &b = rs_[rs_cur_];
-    DR_HIP(hipEventSynchronize(b.copied));
-    unsigned char *h = b.host.get();
-    memcpy(h, keys.data(), n * 8);
+    unsigned char *h = rs_.next();
+    pack_stored(keys.data(), n, h, h + nk * 8);
     if (nk > n) memset(h + n * 8, 0xFF, 8);
-    int far = 0;
+    RenderStage sg{};
+    sg.keys = (const unsigned long long *)rs_.dev();
+    sg.vox = (const Voxel *)(rs_.dev() + nk * 8);
+    sg.table = rs_table_[rs_.slot()].get(); sg.tmask = (unsigned)(stage_table_slots(n) - 1);
+    sg.super[0] = rs_super_[rs_.slot()][0]; sg.super[1] = rs_super_[rs_.slot()][1];
+    sg.n = (int)n;
     for (size_t k = 0; k < n; ++k) {
-      memcpy(h + nk * 8 + k * 4096, store_.get(keys[k]), 4096);
       int c[3]; unpack_key_host(keys[k], c);
       constexpr int G = 1 << (kGridBits - 1);
-      for (int a = 0; a < 3; ++a) if (c[a] < -G || c[a] >= G) far = 1;
+      for (int a = 0; a < 3; ++a) if (c[a] < -G || c[a] >= G) sg.far = 1;
     }
-    size_t slots = 1024;
-    while (slots < 2 * n) slots <<= 1;
-    DR_HIP(hipMemcpyAsync(b.dev.get(), h, nk * 8 + n * 4096, hipMemcpyHostToDevice, rs_stream_));
-    DR_HIP(hipMemsetAsync(b.table.get(), 0, slots * 8, rs_stream_));
-    RenderStage sg{};
-    sg.keys = (const unsigned long long *)b.dev.get();
-    sg.vox = (const Voxel *)(b.dev.get() + nk * 8);
-    sg.table = b.table.get(); sg.tmask = (unsigned)(slots - 1);
-    sg.super[0] = b.super[0]; sg.super[1] = b.super[1];
-    sg.n = (int)n; sg.far = far;
-    hipLaunchKernelGGL(k_rs_build, dim3(cdiv((int)n, 256)), dim3(256), 0, rs_stream_, sg.keys, sg.n, b.table.get(), sg.tmask, b.super[0], b.super[1]);
+    rs_.copy(nk * 8 + n * 4096);
+    DR_HIP(hipMemsetAsync(rs_table_[rs_.slot()].get(), 0, ((size_t)sg.tmask + 1) * 8, rs_.stream()));
+    hipLaunchKernelGGL(k_rs_build, dim3(cdiv(sg.n, 256)), dim3(256), 0, rs_.stream(), sg.keys, sg.n, rs_table_[rs_.slot()].get(), sg.tmask,
+                       rs_super_[rs_.slot()][0], rs_super_[rs_.slot()][1]);
     DR_HIP(hipGetLastError());
-    DR_HIP(hipEventRecord(b.copied, rs_stream_));
+    rs_.record_ready();
     return sg;
-  }
-  // behind every ray-cast that read the buffer: its flags go back to zero
-  void release_render_stage(const RenderStage &sg) {
-    RenderStageBuf &b = rs_[rs_cur_];
-    for (auto &r : renders_) DR_HIP(hipStreamWaitEvent(rs_stream_, r.cast, 0));
-    hipLaunchKernelGGL(k_rs_clear, dim3(cdiv(sg.n, 256)), dim3(256), 0, rs_stream_, sg.keys, sg.n, b.super[0], b.super[1]);
-    DR_HIP(hipGetLastError());
   }
   void expect(Next want, const char *msg) {
     static const char *names[] = {"IntegrateScanAsync", "RenderAsync", "GetRenderResult"};
@@ -2166,19 +1643,6 @@ class FusionEngine {
   // mesh_pass at the running base (mesh_total_).  Neither the pool nor the host store changes.
   int ms_own_cap() const { return std::min(o_.num_blocks, kStageBlocks); }
   int ms_stage_cap() const { return std::max(ms_own_cap(), 27); }  // one block's 27 neighbours always fit
-  void ensure_mesh_staging() {
-    if (ms_dev_[0]) return;
-    ms_bytes_ = (size_t)ms_own_cap() * 8 + (size_t)ms_stage_cap() * (8 + 4096);
-    ms_copy_stream_ = own_.stream();
-    for (int b = 0; b < 2; ++b) {
-      ms_dev_[b] = own_.device<unsigned char>(ms_bytes_);
-      ms_host_[b] = own_.pinned<unsigned char>(ms_bytes_);
-      ms_copied_[b] = own_.event();
-      ms_used_[b] = own_.event();
-      DR_HIP(hipEventRecord(ms_copied_[b], ms_copy_stream_));
-      DR_HIP(hipEventRecord(ms_used_[b], int_stream_));
-    }
-  }
   // update: the mesh-update form (drf_extract_mesh_update_async) -- only the blocks the selection kernel keeps (all of the scope
   // when mu_next_.full) are planned into chunks, staged and meshed, and each chunk adds its rows to the patch table.
   void launch_mesh_map(const float *lower, const float *upper, bool update = false) {
@@ -2212,26 +1676,25 @@ class FusionEngine {
     }
     const MeshPlan plan = plan_mesh_chunks(res, sto, store_, range, (size_t)ms_own_cap(), (size_t)ms_stage_cap(), update ? &picked : nullptr);
     DR_HIP(hipMemsetAsync(mesh_total_, 0, 8, int_stream_));
-    if (plan.chunks() > 0) ensure_mesh_staging();
+    if (plan.chunks() > 0 && !ms_.stream()) {
+      ms_.open(own_);
+      ms_.reserve((size_t)ms_own_cap() * 8 + (size_t)ms_stage_cap() * (8 + 4096));
+    }
     a.base = mesh_total_;
     for (size_t ch = 0; ch < plan.chunks(); ++ch) {
-      const int b = ch & 1;
       const size_t no = plan.ob[ch + 1] - plan.ob[ch], ns = plan.sb[ch + 1] - plan.sb[ch];
-      DR_HIP(hipEventSynchronize(ms_copied_[b]));  // the copy of chunk ch - 2 has left this pinned buffer
-      unsigned char *h = ms_host_[b];
+      unsigned char *h = ms_.next();  // the copy of chunk ch - 2 has left this pinned buffer
       memcpy(h, plan.own.data() + plan.ob[ch], no * 8);
-      memcpy(h + no * 8, plan.stg.data() + plan.sb[ch], ns * 8);
-      unsigned char *hv = h + (no + ns) * 8;
-      for (size_t k = 0; k < ns; ++k) memcpy(hv + k * 4096, store_.get(plan.stg[plan.sb[ch] + k]), 4096);
-      DR_HIP(hipStreamWaitEvent(ms_copy_stream_, ms_used_[b], 0));  // the kernels of chunk ch - 2 have read this device buffer
-      DR_HIP(hipMemcpyAsync(ms_dev_[b], h, (no + ns) * 8 + ns * 4096, hipMemcpyHostToDevice, ms_copy_stream_));
-      DR_HIP(hipEventRecord(ms_copied_[b], ms_copy_stream_));
-      DR_HIP(hipStreamWaitEvent(int_stream_, ms_copied_[b], 0));
-      const unsigned long long *dk = (const unsigned long long *)ms_dev_[b];
+      pack_stored(plan.stg.data() + plan.sb[ch], ns, h + no * 8, h + (no + ns) * 8);
+      ms_.wait_for(ms_.used());  // the kernels of chunk ch - 2 have read this device buffer
+      ms_.copy((no + ns) * 8 + ns * 4096);
+      ms_.record_ready();
+      ms_.wait_ready(int_stream_);
+      const unsigned long long *dk = (const unsigned long long *)ms_.dev();
       a.sorted_keys = dk; a.nblk = (int)no;
       a.st_keys = dk + no; a.st_n = (int)ns; a.st_vox = (const Voxel *)(dk + no + ns);
       mesh_pass<true>(a, update, plan.ob[ch]);
-      DR_HIP(hipEventRecord(ms_used_[b], int_stream_));
+      DR_HIP(hipEventRecord(ms_.used(), int_stream_));
     }
     mesh_end(plan.own.size(), plan.stg.size(), plan.chunks());
     if (update) { mu_stats_[1] = plan.own.size(); mu_next_.nblk = plan.own.size(); }
@@ -2278,13 +1741,6 @@ class FusionEngine {
     if (f[1] || f[2]) fail(DR_ERR_CAPACITY, "DrFusion: block pool exhausted (num_blocks=%d) or block coordinate out of range", o_.num_blocks);
   }
 
-  struct Render {
-    hipStream_t stream;
-    unsigned char *d_bgr, *h_bgr[2], *hd_bgr[2];   // hd_*: the pinned result buffers as the device addresses them
-    float *d_depth, *h_depth[2], *hd_depth[2];
-    int *d_flag;  // pixels the fast ray-caster handed to the literal pass
-    hipEvent_t done, cast;  // result on the host / ray-cast kernels finished (the volume may be written again)
-  };
   HipOwner own_;  // first: released after every other member
   int device_;
   drf_options_t o_;
@@ -2341,25 +1797,14 @@ class FusionEngine {
   DeviceBuf<unsigned long long> mu_sel_, mu_scope_, mu_first_;
   DeviceBuf<int> mu_coords_;
   int *mu_nsel_ = nullptr;
-  // map pass staging (allocated with the first map-scope extraction that meets a non-empty host store): two pinned / device
-  // buffer pairs of ms_bytes_ = own keys + staged keys + staged voxels, a copy stream and the events that order the reuse
-  size_t ms_bytes_ = 0;
-  unsigned char *ms_dev_[2] = {nullptr, nullptr}, *ms_host_[2] = {nullptr, nullptr};
-  hipEvent_t ms_copied_[2] = {nullptr, nullptr}, ms_used_[2] = {nullptr, nullptr};
-  hipStream_t ms_copy_stream_ = nullptr;
-  // render scope: staging allocated with the first map-scope render that has stored blocks in reach, grown up to rs_capacity()
-  struct RenderStageBuf {
-    DeviceBuf<unsigned char> dev;
-    PinnedBuf<unsigned char> host;
-    DeviceBuf<unsigned long long> table;
-    unsigned char *super[2] = {nullptr, nullptr};
-    hipEvent_t copied = nullptr;
-  };
+  // map pass staging (opened by the first map-scope extraction that meets a non-empty host store): own keys + staged keys + staged voxels
+  BlockStaging ms_;
+  // render scope: staging opened by the first map-scope render that has stored blocks in reach, grown up to rs_capacity()
+  BlockStaging rs_;
+  DeviceBuf<unsigned long long> rs_table_[2];  // per slot of rs_: the open-addressing table and the two staged superblock flag arrays
+  unsigned char *rs_super_[2][2] = {};
   int render_scope_ = DRF_RENDER_RESIDENT;
   size_t rs_cap_req_ = 0, rs_blocks_ = 0;
-  RenderStageBuf rs_[2];
-  int rs_cur_ = 0;
-  hipStream_t rs_stream_ = nullptr;
   uint64_t render_stats_[4] = {0, 0, 0, 0};
   // streaming state (staging allocated with the first drf_set_streaming / region call)
   float st_radius_ = 0.0f;                  // 0 = off

@@ -72,14 +72,6 @@ __device__ inline Voxel voxel_at(const FusionDev &d, int vx, int vy, int vz) {  
   return d.vox[(size_t)p * 512 + pos_mod(vx, kBS) * 64 + pos_mod(vy, kBS) * 8 + pos_mod(vz, kBS)];
 }
 
-// Staged form: index of block p among the chunk's staged host blocks (binary search of the ascending keys), -1 if absent.
-__device__ inline int staged_block(const McArgs &a, I3 p) {
-  unsigned long long key;
-  if (!pack_key(p, key)) return -1;
-  int lo = 0, hi = a.st_n;
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (a.st_keys[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo < a.st_n && a.st_keys[lo] == key ? lo : -1;
-}
 // voxel_at through both levels: the pool first, then the staged host blocks.  The fallback samples it serves lie in the
 // 27 blocks around the cell's block, and the chunk stages every stored block among those.
 __device__ inline Voxel voxel_at_staged(const FusionDev &d, const McArgs &a, int vx, int vy, int vz) {
@@ -88,7 +80,7 @@ __device__ inline Voxel voxel_at_staged(const FusionDev &d, const McArgs &a, int
   const int off = pos_mod(vx, kBS) * 64 + pos_mod(vy, kBS) * 8 + pos_mod(vz, kBS);
   const int p = find_block(d, b);
   if (p >= 0) return d.vox[(size_t)p * 512 + off];
-  const int s = staged_block(a, b);
+  const int s = find_sorted_key(a.st_keys, a.st_n, b);
   if (s >= 0) return a.st_vox[(size_t)s * 512 + off];
   return z;
 }
@@ -135,7 +127,7 @@ __global__ __launch_bounds__(256) void k_mc_cells(const FusionDev d, const McArg
     I3 q; q.x = B.x + k / 9 - 1; q.y = B.y + (k / 3) % 3 - 1; q.z = B.z + k % 3 - 1;
     int p = find_block(d, q);
     if constexpr (STAGED) {
-      if (p < 0) { const int st = staged_block(a, q); p = st >= 0 ? -2 - st : -1; }
+      if (p < 0) { const int st = find_sorted_key(a.st_keys, a.st_n, q); p = st >= 0 ? -2 - st : -1; }
     }
     nbptr[k] = p;
   }

@@ -4,15 +4,9 @@ weight), bit-exact ray-cast depth and colour, identical update counts."""
 import numpy as np
 import pytest
 
+from fusion_helpers import options
+
 pytestmark = pytest.mark.gpu
-
-
-def options(sc, H, W, vs, **kw):
-    d = dict(voxel_size=vs, num_buckets=40000, bucket_size=10, num_blocks=40000, block_size=8, max_sdf_weight=64,
-             truncation_distance=4 * vs, max_sensor_depth=10.0, min_sensor_depth=0.1, num_render_streams=1,
-             fx=sc["fx"], fy=sc["fy"], cx=sc["cx"], cy=sc["cy"], height=H, width=W)
-    d.update(kw)
-    return d
 
 
 def assert_same_volume(f, o):

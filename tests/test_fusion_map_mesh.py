@@ -7,26 +7,19 @@ import subprocess
 
 import pytest
 
+from fusion_helpers import abi_module, check_symbols
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("drf_set_mesh_scope", "drf_mesh_stats")
 
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as g
-    if not os.path.isfile(os.path.join(ROOT, "tandem_amd", "libdr_mi355x.so")):
-        g.build()
-    from tandem_amd import _lib
-    return _lib
+    return abi_module()
 
 
 def test_symbols_declared_exported_and_typed(L):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dr_mi355x.h")).read(), flags=re.S)
-    lib = C.CDLL(L.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"\b%s\s*\(" % name, src), name
-        assert hasattr(lib, name), name
-        assert name in L.SIGNATURES, name
+    src = check_symbols(L, NEW)
     assert re.search(r"DRF_MESH_RESIDENT\s*=\s*0\s*,\s*DRF_MESH_MAP\s*=\s*1", src)
     from tandem_amd import dr_fusion
     assert (dr_fusion.MESH_RESIDENT, dr_fusion.MESH_MAP) == (0, 1)

@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from fusion_helpers import abi_module, check_symbols
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("drf_extract_mesh_update_async", "drf_mesh_update_size", "drf_get_mesh_update_sync", "drf_mesh_update_reset",
        "drf_mesh_update_stats")
@@ -17,15 +19,7 @@ NEW = ("drf_extract_mesh_update_async", "drf_mesh_update_size", "drf_get_mesh_up
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as g
-    if not os.path.isfile(os.path.join(ROOT, "tandem_amd", "libdr_mi355x.so")):
-        g.build()
-    from tandem_amd import _lib
-    return _lib
-
-
-def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dr_mi355x.h")).read(), flags=re.S)
+    return abi_module()
 
 
 CTYPE_OF = {"drf_t *": C.c_void_p, "const float": C.POINTER(C.c_float), "float *": C.POINTER(C.c_float), "size_t": C.c_size_t,
@@ -53,12 +47,8 @@ def declared_argtypes(src, name):
 
 
 def test_symbols_declared_exported_and_typed(L):
-    src = header()
-    lib = C.CDLL(L.LIB_PATH)
+    src = check_symbols(L, NEW)
     for name in NEW:
-        assert re.search(r"\b%s\s*\(" % name, src), name
-        assert hasattr(lib, name), name
-        assert name in L.SIGNATURES, name
         res, args = L.SIGNATURES[name]
         assert res is C.c_int
         assert args == declared_argtypes(src, name), name

@@ -2,50 +2,16 @@
 engine's full extraction (ExtractMeshAsync + GetMeshSync) over the same box at the same moment -- and, in map scope, an
 unbounded engine fed the same scans, which tests/test_fusion_map_mesh_gpu.py ties to the CPU oracle: the patches, kept in a
 MeshPatches store and assembled in packed-key order, must equal it byte for byte, triangle order included.
-DESIGN.md §7c "Incremental mesh".  Scenes and helpers as in tests/test_fusion_map_mesh_gpu.py."""
+DESIGN.md §7c "Incremental mesh".  Scenes as in tests/test_fusion_map_mesh_gpu.py, helpers from tests/fusion_helpers.py."""
 import numpy as np
 import pytest
 
+import fusion_helpers
+from fusion_helpers import assert_same_mesh, box_of, feed, options, places, shifted, unbounded
+
 pytestmark = pytest.mark.gpu
 
-BIG = 100000  # blocks of the reference engines: their pools never run out
 ROOM_LO, ROOM_HI = (-3.6, -2.6, -2.1), (3.6, 2.6, 2.1)  # synth.room is a 6 x 4 x 3 m box around the origin
-
-
-def options(sc, H, W, vs, **kw):
-    d = dict(voxel_size=vs, num_buckets=40000, bucket_size=10, num_blocks=40000, block_size=8, max_sdf_weight=64,
-             truncation_distance=4 * vs, max_sensor_depth=10.0, min_sensor_depth=0.1, num_render_streams=1,
-             fx=sc["fx"], fy=sc["fy"], cx=sc["cx"], cy=sc["cy"], height=H, width=W)
-    d.update(kw)
-    return d
-
-
-def unbounded(opt):
-    return dict(opt, num_blocks=BIG, num_buckets=BIG)
-
-
-def feed(f, bgr, depth, pose):
-    f.IntegrateScanAsync(bgr, depth, pose)
-    f.RenderAsync([pose])
-    f.GetRenderResult()
-
-
-def rows(vert, cols):
-    """(ntri, 18) uint32: the triangle's 9 coordinates and 9 colour values, bit patterns, in the order returned."""
-    return np.concatenate([vert.reshape(-1, 9), cols.reshape(-1, 9)], axis=1).view(np.uint32)
-
-
-def assert_same_mesh(a, b, what):
-    """Byte for byte, triangle order included."""
-    ra, rb = rows(*a), rows(*b)
-    assert ra.shape == rb.shape, f"{what}: {len(ra)} vs {len(rb)} triangles"
-    bad = np.flatnonzero((ra != rb).any(axis=1))
-    assert bad.size == 0, f"{what}: {bad.size} of {len(ra)} triangles differ, first at {bad[0]}"
-
-
-def box_of(blocks, vs):
-    c = np.array(list(blocks), np.int64)
-    return tuple(float(v) for v in (c.min(0) * 8 - 2) * vs), tuple(float(v) for v in ((c.max(0) + 1) * 8 + 2) * vs)
 
 
 def assert_box_holds(blocks, vs, lo, hi):
@@ -53,31 +19,9 @@ def assert_box_holds(blocks, vs, lo, hi):
     assert (c.min(0) * 8 * vs > np.array(lo) + 2 * vs).all() and ((c.max(0) + 1) * 8 * vs < np.array(hi) - 2 * vs).all(), "the fixed box does not hold the map"
 
 
-def shifted(scans, S):
-    return [(b, d, (S @ p).astype(np.float32)) for b, d, p in scans]
-
-
-def places(n_places, scans_per_place=2, seed=3, spacing=20.0, **kw):
-    from synth import scene
-    H, W = 96, 128
-    sc = scene.make_scans(scans_per_place, H, W, seed=seed)
-    out = []
-    for p in range(n_places):
-        S = np.eye(4, dtype=np.float32)
-        S[:3, 3] = (spacing * p, 0.0, 0.0)
-        out.append(shifted(sc["scans"], S))
-    return out, options(sc, H, W, 0.02, **dict(dict(max_sensor_depth=6.0), **kw))
-
-
 @pytest.fixture(scope="module")
 def room_frames():
-    import torch  # noqa: F401  (synth.room renders with torch)
-    from synth import room
-    H, W, N = 96, 128, 60
-    poses = room.loop_poses(N, seed=0)
-    fr = room.render_frames(poses, H, W)
-    frames = [(fr["bgr"][k].numpy(), fr["depth"][k].numpy(), np.asarray(poses[k], np.float32)) for k in range(N)]
-    return fr, frames, H, W
+    return fusion_helpers.room_frames()
 
 
 def check_update(upd, patches, want, what, full=None):

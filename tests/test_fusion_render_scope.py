@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from fusion_helpers import abi_module, check_symbols
 from test_fusion_streaming import f32, opts, restated_min_radius
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -284,16 +285,8 @@ def test_a_render_waits_for_the_scan_only_beyond_the_derived_distance(R, kw):
 
 # ------------------------------------------------------------------ C ABI surface
 def test_render_scope_symbols_are_declared_exported_typed_and_refuse_null():
-    import __graft_entry__ as g
-    if not os.path.isfile(os.path.join(ROOT, "tandem_amd", "libdr_mi355x.so")):
-        g.build()
-    from tandem_amd import _lib as L
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dr_mi355x.h")).read(), flags=re.S)
-    lib = C.CDLL(L.LIB_PATH)
-    for name in ("drf_set_render_scope", "drf_render_stats"):
-        assert re.search(r"\b%s\s*\(" % name, src), name
-        assert hasattr(lib, name), name
-        assert name in L.SIGNATURES, name
+    L = abi_module()
+    src = check_symbols(L, ("drf_set_render_scope", "drf_render_stats"))
     assert re.search(r"DRF_RENDER_RESIDENT\s*=\s*0\s*,\s*DRF_RENDER_MAP\s*=\s*1", src)
     from tandem_amd import dr_fusion
     assert (dr_fusion.RENDER_RESIDENT, dr_fusion.RENDER_MAP) == (0, 1)

@@ -4,11 +4,11 @@ DESIGN.md §7c "Rendering the whole map"."""
 import numpy as np
 import pytest
 
-from test_fusion_streaming_gpu import assert_same_blocks, canon, options, shifted, two_places
+import fusion_helpers
+from fusion_helpers import BIG, box_of, canon, options, shifted
+from test_fusion_streaming_gpu import assert_same_blocks, two_places
 
 pytestmark = pytest.mark.gpu
-
-BIG = 100000  # blocks of the oracle: its pool never runs out
 
 
 def same_render(got_bgr, got_depth, want, what):
@@ -18,7 +18,7 @@ def same_render(got_bgr, got_depth, want, what):
 
 
 def step(f, o, bgr, depth, pose, render_poses, what):
-    """The step() of the streaming test with the poses to render given: every render and the update count must agree."""
+    """The step() of tests/fusion_helpers.py with the poses to render given: every render and the update count must agree."""
     f.IntegrateScanAsync(bgr, depth, pose)
     f.RenderAsync(render_poses)
     rb, rd = f.GetRenderResult()
@@ -44,24 +44,15 @@ def hit_blocks(opt, pose, depth):
     return [tuple(int(c) for c in b) for b in np.stack(out, -1)]
 
 
-def box_of(blocks, vs):
-    c = np.array(list(blocks), np.int64)
-    return tuple(float(v) for v in (c.min(0) * 8 - 2) * vs), tuple(float(v) for v in ((c.max(0) + 1) * 8 + 2) * vs)
-
-
 @pytest.fixture(scope="module")
 def room():
     """The room loop of tests/test_fusion_streaming_gpu.py (60 frames, 96x128, 2 cm, 2 m, a pool of 5600 blocks, minimum radius)
     with three render streams in map scope: frame k renders poses k, max(k - 30, 0) and max(k - 38, 0).  What the loop saw is
     recorded here and asserted by the first test; the later tests go on from its end state."""
-    import torch  # noqa: F401  (synth.room renders with torch)
-    from synth import room as room_scene
     from oracle.tsdf_oracle import TsdfOracle
     from tandem_amd.dr_fusion import RENDER_MAP, DrFusion, DrFusionOptions, streaming_min_radius
-    H, W, N = 96, 128, 60
-    poses = room_scene.loop_poses(N, seed=0)
-    fr = room_scene.render_frames(poses, H, W)
-    frames = [(fr["bgr"][k].numpy(), fr["depth"][k].numpy(), np.asarray(poses[k], np.float32)) for k in range(N)]
+    fr, frames, H, W = fusion_helpers.room_frames()
+    N = len(frames)
     opt = options(fr, H, W, 0.02, max_sensor_depth=2.0, num_blocks=5600, num_buckets=5600, num_render_streams=3)
     f, o = DrFusion(DrFusionOptions(**opt)), TsdfOracle(**dict(opt, num_blocks=BIG, num_buckets=BIG))
     g = DrFusion(DrFusionOptions(**dict(opt, num_render_streams=1)))  # the default: resident scope

@@ -4,9 +4,10 @@ derives; null and invalid arguments are refused without a device."""
 import ctypes as C
 import math
 import os
-import re
 
 import pytest
+
+from fusion_helpers import abi_module, check_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("drf_streaming_min_radius", "drf_set_streaming", "drf_stream_out_region", "drf_stream_in_region", "drf_streaming_stats",
@@ -15,11 +16,7 @@ NEW = ("drf_streaming_min_radius", "drf_set_streaming", "drf_stream_out_region",
 
 @pytest.fixture(scope="module")
 def L():
-    import __graft_entry__ as g
-    if not os.path.isfile(os.path.join(ROOT, "tandem_amd", "libdr_mi355x.so")):
-        g.build()
-    from tandem_amd import _lib
-    return _lib
+    return abi_module()
 
 
 def restated_min_radius(o):
@@ -43,12 +40,7 @@ def f32(x):
 
 
 def test_symbols_declared_exported_and_typed(L):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dr_mi355x.h")).read(), flags=re.S)
-    lib = C.CDLL(L.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"\b%s\s*\(" % name, src), name
-        assert hasattr(lib, name), name
-        assert name in L.SIGNATURES, name
+    check_symbols(L, NEW)
 
 
 @pytest.mark.parametrize("kw", [

@@ -4,17 +4,11 @@ update counts, and bit-identical ray-casts at the scan pose.  DESIGN.md "Streami
 import numpy as np
 import pytest
 
+from fusion_helpers import canon, options, shifted, step
+
 pytestmark = pytest.mark.gpu
 
 ALL_LO, ALL_HI = (-1e4, -1e4, -1e4), (1e4, 1e4, 1e4)
-
-
-def options(sc, H, W, vs, **kw):
-    d = dict(voxel_size=vs, num_buckets=40000, bucket_size=10, num_blocks=40000, block_size=8, max_sdf_weight=64,
-             truncation_distance=4 * vs, max_sensor_depth=10.0, min_sensor_depth=0.1, num_render_streams=1,
-             fx=sc["fx"], fy=sc["fy"], cx=sc["cx"], cy=sc["cy"], height=H, width=W)
-    d.update(kw)
-    return d
 
 
 def assert_same_blocks(a, b, what=""):
@@ -22,29 +16,6 @@ def assert_same_blocks(a, b, what=""):
     assert a.keys() == b.keys(), f"{what}: block sets differ: {len(a)} vs {len(b)}, e.g. {sorted(a.keys() ^ b.keys())[:3]}"
     bad = [k for k in a if not np.array_equal(a[k], b[k])]
     assert not bad, f"{what}: {len(bad)} of {len(a)} blocks differ, e.g. {bad[:3]}"
-
-
-def step(f, o, bgr, depth, pose, what):
-    """One operator round on both sides; the ray-cast at the scan pose and the update count must agree."""
-    f.IntegrateScanAsync(bgr, depth, pose)
-    f.RenderAsync([pose])
-    rb, rd = f.GetRenderResult()
-    assert o.integrate(bgr, depth, pose) == 0
-    ob, od = o.render(pose)
-    assert np.array_equal(rd[0].view(np.uint32), od.view(np.uint32)), f"{what}: ray-cast depth differs at {(rd[0] != od).sum()} px"
-    assert np.array_equal(rb[0], ob), f"{what}: ray-cast colour differs"
-    assert f.stats()["updated_last"] == o.stats()["updated_last"], what
-    return od
-
-
-def canon(vert, cols):
-    """(ntri, 18) uint32 rows, sorted (as tests/test_mesh_gpu.py compares meshes)."""
-    t = np.concatenate([vert.reshape(-1, 9), cols.reshape(-1, 9)], axis=1).view(np.uint32)
-    return t[np.lexsort(t.T[::-1])]
-
-
-def shifted(scans, S):
-    return [(b, d, (S @ p).astype(np.float32)) for b, d, p in scans]
 
 
 def test_round_trip_out_and_in_is_exact():

@@ -20,15 +20,13 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
+from _timing import fusion_options, room_loop  # noqa: E402
 
 
 def run_leg(leg, frames, poses, args):
-    from tandem_amd.dr_fusion import DrFusion, DrFusionOptions, streaming_min_radius
+    from tandem_amd.dr_fusion import DrFusion, streaming_min_radius
     depth_max = args.short_depth if leg in ("move", "off_short") else 10.0
-    opt = DrFusionOptions(voxel_size=0.01, num_buckets=args.num_blocks, bucket_size=10, num_blocks=args.num_blocks, block_size=8,
-                          max_sdf_weight=64, truncation_distance=0.04, max_sensor_depth=depth_max, min_sensor_depth=0.1,
-                          num_render_streams=1, fx=frames["fx"], fy=frames["fy"], cx=frames["cx"], cy=frames["cy"], height=args.height,
-                          width=args.width)
+    opt = fusion_options(frames, args.num_blocks, depth_max, args.height, args.width)
     f = DrFusion(opt)
     rmin = streaming_min_radius(opt)
     radius = 0.0
@@ -90,16 +88,7 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
-    from synth import room
-    poses = room.loop_poses(args.frames, seed=0)
-    dev = "cuda" if torch.cuda.is_available() else "cpu"
-    bgr, depth = [], []
-    for i in range(0, args.frames, 100):  # rendered on the device in chunks, kept in host memory (the operator takes host images)
-        fr = room.render_frames(poses[i:i + 100], args.height, args.width, device=dev, seed=i)
-        bgr.append(fr["bgr"].cpu().numpy())
-        depth.append(fr["depth"].cpu().numpy())
-    frames = dict(bgr=np.concatenate(bgr), depth=np.concatenate(depth), fx=fr["fx"], fy=fr["fy"], cx=fr["cx"], cy=fr["cy"])
-    del bgr, depth
+    poses, frames = room_loop(args.frames, args.height, args.width, device="cuda" if torch.cuda.is_available() else "cpu")
     results = []
     for leg in args.legs.split(","):
         out, series = run_leg(leg, frames, poses, args)

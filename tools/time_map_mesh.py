@@ -19,13 +19,13 @@ Run:  rocprofv3 --kernel-trace --stats -d DIR -o mesh -- python tools/time_map_m
 import argparse
 import json
 import os
-import re
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
+from _timing import fusion_options, merge_kernel_stats, room_loop  # noqa: E402
 
 
 def time_extraction(f, lo, hi, reps):
@@ -59,31 +59,22 @@ def h2d_gbps():
     return 10 * (32 << 20) / (e0.elapsed_time(e1) * 1e-3) / 1e9
 
 
-def merge_kernel_stats(path, out):
-    """Adds the per-extraction device time of the map pass (staged k_mc_cells, k_mc_advance) and of the resident pass."""
-    with open(out) as fh:
-        res = json.load(fh)
+def add_kernel_stats(res, rows):
+    """The per-extraction device time of the map pass (staged k_mc_cells, k_mc_advance) and of the resident pass."""
     staged = resident = 0.0
     calls = {}
-    for line in open(path):
-        m = re.match(r"(.*?)\s+(\d+)\s+([\d.]+)\s+([\d.]+)\s+[\d.]+%$", line.rstrip())
-        if not m:
-            continue
-        name, n, tot = m.group(1), int(m.group(2)), float(m.group(3))
+    for name, n, tot, _ in rows:
         if "k_mc_cells<" in name and ", true>" in name or "k_mc_advance" in name:
             staged += tot
         elif "k_mc_cells<" in name:
             resident += tot
         if "k_mc_" in name:
-            calls[name.strip()] = n
+            calls[name] = n
     res["map_kernels_us"] = staged / res["reps"]
     # the resident pass runs reps times on the streaming engine and reps times on the unbounded one
     res["resident_kernels_us_both_engines"] = resident / res["reps"]
     res["kernel_calls"] = calls
-    res["kernel_stats"] = os.path.basename(path)
-    with open(out, "w") as fh:
-        json.dump(res, fh, indent=1)
-    print(json.dumps({k: res[k] for k in ("map_kernels_us", "resident_kernels_us_both_engines")}))
+    return {k: res[k] for k in ("map_kernels_us", "resident_kernels_us_both_engines")}
 
 
 def main():
@@ -99,30 +90,20 @@ def main():
     ap.add_argument("--merge-kernel-stats", default=None, help="add the mesh kernels of this rocprof summary to --out and exit")
     args = ap.parse_args()
     if args.merge_kernel_stats:
-        return merge_kernel_stats(args.merge_kernel_stats, args.out)
+        return merge_kernel_stats(args.merge_kernel_stats, args.out, add_kernel_stats)
     import torch
-    from synth import room
-    from tandem_amd.dr_fusion import DrFusion, DrFusionOptions, MESH_MAP, MESH_RESIDENT, streaming_min_radius
-    poses = room.loop_poses(args.frames, seed=0)
-    bgr, depth = [], []
-    for i in range(0, args.frames, 100):  # as tools/time_fusion_streaming.py renders them
-        fr = room.render_frames(poses[i:i + 100], args.height, args.width, device="cuda", seed=i)
-        bgr.append(fr["bgr"].cpu().numpy())
-        depth.append(fr["depth"].cpu().numpy())
-    bgr, depth = np.concatenate(bgr), np.concatenate(depth)
-
-    def opts(n):
-        return DrFusionOptions(voxel_size=0.01, num_buckets=n, bucket_size=10, num_blocks=n, block_size=8, max_sdf_weight=64,
-                               truncation_distance=0.04, max_sensor_depth=args.depth, min_sensor_depth=0.1, num_render_streams=1,
-                               fx=fr["fx"], fy=fr["fy"], cx=fr["cx"], cy=fr["cy"], height=args.height, width=args.width)
-    f, u = DrFusion(opts(args.num_blocks)), DrFusion(opts(args.num_blocks))
+    from tandem_amd.dr_fusion import DrFusion, MESH_MAP, MESH_RESIDENT, streaming_min_radius
+    poses, frames = room_loop(args.frames, args.height, args.width)
+    bgr, depth = frames["bgr"], frames["depth"]
+    opt = fusion_options(frames, args.num_blocks, args.depth, args.height, args.width)
+    f, u = DrFusion(opt), DrFusion(opt)
     f.set_streaming(streaming_min_radius(f.options) + args.margin, 0)
     for k in range(args.frames):
         for e in (f, u):
             e.IntegrateScanAsync(bgr[k], depth[k], poses[k])
             e.RenderAsync([poses[k]])
             e.GetRenderResult(copy=False)
-    del bgr, depth
+    del bgr, depth, frames["bgr"], frames["depth"]
     st = f.streaming_stats()
     c = np.array(list(f.export_all_blocks().keys()), np.int64)
     lo = tuple(float(v) for v in (c.min(0) * 8 - 2) * 0.01)

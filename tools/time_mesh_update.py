@@ -29,6 +29,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
+from _timing import fusion_options, merge_kernel_stats, room_loop  # noqa: E402
 
 
 def feed(e, frames, poses, k):
@@ -90,21 +91,12 @@ def run_leg(e, frames, poses, lo, hi, k, reps, cursor, patches):
     return out, cursor
 
 
-def merge_kernel_stats(path, out):
-    with open(out) as fh:
-        res = json.load(fh)
-    picked = {}
-    for line in open(path):
-        m = re.match(r"(.*?)\s+(\d+)\s+([\d.]+)\s+([\d.]+)\s+[\d.]+%$", line.rstrip())
-        if m and re.search(r"k_mu_|k_mc_cells|k_cull", m.group(1)):
-            picked[m.group(1).strip()] = dict(calls=int(m.group(2)), total_us=float(m.group(3)), avg_us=float(m.group(4)))
+def add_kernel_stats(res, rows):
+    picked = {name: dict(calls=n, total_us=tot, avg_us=avg) for name, n, tot, avg in rows if re.search(r"k_mu_|k_mc_cells|k_cull", name)}
     res["kernels"] = picked
     sel = [v for k, v in picked.items() if "k_mu_select" in k]
     res["select_kernel_us"] = sel[0]["avg_us"] if sel else None
-    res["kernel_stats"] = os.path.basename(path)
-    with open(out, "w") as fh:
-        json.dump(res, fh, indent=1)
-    print(json.dumps(dict(select_kernel_us=res["select_kernel_us"])))
+    return dict(select_kernel_us=res["select_kernel_us"])
 
 
 def main():
@@ -121,25 +113,13 @@ def main():
     ap.add_argument("--merge-kernel-stats", default=None, help="add the update's kernels of this rocprof summary to --out and exit")
     args = ap.parse_args()
     if args.merge_kernel_stats:
-        return merge_kernel_stats(args.merge_kernel_stats, args.out)
+        return merge_kernel_stats(args.merge_kernel_stats, args.out, add_kernel_stats)
     import torch
-    from synth import room
-    from tandem_amd.dr_fusion import DrFusion, DrFusionOptions, MeshPatches, MESH_MAP, streaming_min_radius
+    from tandem_amd.dr_fusion import DrFusion, MeshPatches, MESH_MAP, streaming_min_radius
     assert torch.cuda.is_available(), "needs a GPU"
-    poses = room.loop_poses(args.frames, seed=0)
-    bgr, depth = [], []
-    for i in range(0, args.frames, 100):  # as tools/time_fusion_streaming.py renders them
-        fr = room.render_frames(poses[i:i + 100], args.height, args.width, device="cuda", seed=i)
-        bgr.append(fr["bgr"].cpu().numpy())
-        depth.append(fr["depth"].cpu().numpy())
-    frames = dict(bgr=np.concatenate(bgr), depth=np.concatenate(depth))
-    del bgr, depth
-
-    def opts(n):
-        return DrFusionOptions(voxel_size=0.01, num_buckets=n, bucket_size=10, num_blocks=n, block_size=8, max_sdf_weight=64,
-                               truncation_distance=0.04, max_sensor_depth=args.depth, min_sensor_depth=0.1, num_render_streams=1,
-                               fx=fr["fx"], fy=fr["fy"], cx=fr["cx"], cy=fr["cy"], height=args.height, width=args.width)
-    f, u = DrFusion(opts(args.num_blocks)), DrFusion(opts(args.num_blocks))
+    poses, frames = room_loop(args.frames, args.height, args.width)
+    opt = fusion_options(frames, args.num_blocks, args.depth, args.height, args.width)
+    f, u = DrFusion(opt), DrFusion(opt)
     f.set_streaming(streaming_min_radius(f.options) + args.margin, 0)
     f.set_mesh_scope(MESH_MAP)
     for k in range(args.frames):

@@ -20,13 +20,13 @@ Run:  rocprofv3 --kernel-trace --stats -d DIR -o rs -- python tools/time_render_
 import argparse
 import json
 import os
-import re
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
+from _timing import fusion_options, merge_kernel_stats, room_loop  # noqa: E402
 
 
 def time_render(f, pose, reps, warmup):
@@ -48,22 +48,10 @@ def time_render(f, pose, reps, warmup):
     return float(np.median(tot)), float(np.median(call)), img
 
 
-def merge_kernel_stats(path, out):
-    with open(out) as fh:
-        res = json.load(fh)
-    k = {}
-    for line in open(path):
-        m = re.match(r"(.*?)\s+(\d+)\s+([\d.]+)\s+([\d.]+)\s+[\d.]+%$", line.rstrip())
-        if not m:
-            continue
-        name, n, tot = m.group(1).strip(), int(m.group(2)), float(m.group(3))
-        if "k_raycast" in name or "k_rs_" in name or "k_publish" in name:
-            k[name] = dict(calls=n, total_us=tot, us_per_call=tot / max(n, 1))
-    res["kernels_us"] = k
-    res["kernel_stats"] = os.path.basename(path)
-    with open(out, "w") as fh:
-        json.dump(res, fh, indent=1)
-    print(json.dumps(k, indent=1))
+def add_kernel_stats(res, rows):
+    res["kernels_us"] = {name: dict(calls=n, total_us=tot, us_per_call=tot / max(n, 1)) for name, n, tot, _ in rows
+                         if "k_raycast" in name or "k_rs_" in name or "k_publish" in name}
+    return res["kernels_us"]
 
 
 def main():
@@ -82,24 +70,14 @@ def main():
     ap.add_argument("--merge-kernel-stats", default=None, help="add the ray-cast kernels of this rocprof summary to --out and exit")
     args = ap.parse_args()
     if args.merge_kernel_stats:
-        return merge_kernel_stats(args.merge_kernel_stats, args.out)
+        return merge_kernel_stats(args.merge_kernel_stats, args.out, add_kernel_stats, indent=1)
     import torch
     assert torch.cuda.is_available(), "tools/time_render_scope.py needs a GPU"
-    from synth import room
-    from tandem_amd.dr_fusion import DrFusion, DrFusionOptions, RENDER_MAP, RENDER_RESIDENT, streaming_min_radius
-    poses = room.loop_poses(args.frames, seed=0)
-    bgr, depth = [], []
-    for i in range(0, args.frames, 100):  # as tools/time_fusion_streaming.py renders them
-        fr = room.render_frames(poses[i:i + 100], args.height, args.width, device="cuda", seed=i)
-        bgr.append(fr["bgr"].cpu().numpy())
-        depth.append(fr["depth"].cpu().numpy())
-    bgr, depth = np.concatenate(bgr), np.concatenate(depth)
-
-    def opts(n):
-        return DrFusionOptions(voxel_size=0.01, num_buckets=n, bucket_size=10, num_blocks=n, block_size=8, max_sdf_weight=64,
-                               truncation_distance=0.04, max_sensor_depth=args.depth, min_sensor_depth=0.1, num_render_streams=1,
-                               fx=fr["fx"], fy=fr["fy"], cx=fr["cx"], cy=fr["cy"], height=args.height, width=args.width)
-    f, u = DrFusion(opts(args.num_blocks)), DrFusion(opts(args.num_blocks))
+    from tandem_amd.dr_fusion import DrFusion, RENDER_MAP, RENDER_RESIDENT, streaming_min_radius
+    poses, frames = room_loop(args.frames, args.height, args.width)
+    bgr, depth = frames["bgr"], frames["depth"]
+    opt = fusion_options(frames, args.num_blocks, args.depth, args.height, args.width)
+    f, u = DrFusion(opt), DrFusion(opt)
     f.set_streaming(streaming_min_radius(f.options) + args.margin, 0)
     f.set_render_scope(RENDER_MAP, args.capacity)
     loop_stats = np.zeros(4, np.int64)
@@ -111,7 +89,7 @@ def main():
         loop_stats += np.array(f.render_stats(), np.int64)
     time_render.blank = (np.zeros_like(bgr[0]), np.zeros_like(depth[0]))
     time_render.scan_pose = poses[args.frames - 1]
-    del bgr, depth
+    del bgr, depth, frames["bgr"], frames["depth"]
     st = f.streaming_stats()
     for e in (f, u):  # leave both where RenderAsync is legal
         e.IntegrateScanAsync(time_render.blank[0], time_render.blank[1], time_render.scan_pose)
