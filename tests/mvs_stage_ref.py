@@ -1,0 +1,303 @@
+"""Float64 restatements of the DrMvsnet stages between FeatureNet and the edge filter -- TEST INFRASTRUCTURE.
+
+One function per stage operation (hypothesis planes, cost volume, prob head, regression, FeatureNet), each a plain
+numpy / torch float64 statement of the reference's arithmetic, written independently of oracle/mvsnet_oracle.py: the cost
+volume gathers its four taps from a zero-padded map (no grid_sample), the homography comes from double inverses.  They
+are imported by
+  tests/test_mvs_stage_ref.py    (CPU: the fp32 oracle against these = the reference's own rounding error, and what a
+                                  one-line mistake moves)
+  tests/test_mvs_stages_gpu.py   (GPU: every stage tensor of the engine against these, fed the engine's own stage input).
+
+Layouts are the engine's logical ones (DrMvsnet.tensor): feature maps (V, h, w, C), volumes (D, h, w, C), x11 (D, h, w, 8),
+logits (D, h, w), planes (D, h, w); views in model order [ref, the others in window order].
+
+THE RECORDED REFERENCE ERRORS (E_*).  The fp32 oracle against the float64 restatement given the oracle's own stage
+inputs, maximum over CPU_WINDOWS, as a fraction of the float64 tensor's range max - min (depth: relative; confidence:
+absolute, its range is 1).  Produced by
+    python -m pytest tests/test_mvs_stage_ref.py -q -s -k reference_error
+which prints the block below; tests/test_mvs_stage_ref.py asserts the oracle stays within 1.5 x of it.  The GPU test
+holds every kernel to BOUND_FACTOR x these figures: the kernel's coordinate passes a 1-ulp reciprocal and an fp32 matrix
+rounded from double, each worth about one more rounding of the size of the reference's own normalise / denormalise round
+trip -- a margin over the reference's error, not a number fitted to the kernels.
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+BOUND_FACTOR = 4.0
+CONV_BOUND = 2e-5        # the project's convolution bound (tests/test_conv_gpu.py): of the output's range
+EK_INTEGER_BAND = 1e-4   # trunc(E[k]) is discontinuous: within this distance of an integer either neighbouring index is accepted
+                         # (the fp32 sum of <= 48 terms p * k errs by about 48 * 2^-23 * a few = 2e-5)
+
+# --- recorded by the command above (see the module docstring) ---
+E_VOL = {1: 4.53e-06, 2: 9.62e-06, 3: 2.87e-05}
+E_VOL_MEAN = {1: 8.31e-08, 2: 1.80e-07, 3: 2.47e-07}
+E_VOL_PLAIN = {1: 5.20e-06, 2: 1.31e-05, 3: 2.45e-05}       # the plain-variance model (no view aggregation): another operation, its own reference error
+E_VOL_PLAIN_MEAN = {1: 8.68e-08, 2: 1.95e-07, 3: 3.69e-07}  # (maximum over test_mvs_stage_ref.PLAIN_WINDOWS)
+E_DEPTH = 4.77e-07
+E_CONF = 5.64e-07
+E_FEAT = {1: 9.23e-07, 2: 9.44e-07, 3: 9.16e-07}
+# ---
+
+MUTANTS = ("border", "no_behind_mask", "shift", "no_gate", "drop_last_view", "divisor_V", "spacing_Dm1")
+BN_EPS = 1e-5
+
+
+# ------------------------------------------------------------------ windows
+def _rot(axis, a):
+    c, s = np.cos(a), np.sin(a)
+    R = np.eye(4)
+    i, j = {"x": (1, 2), "y": (2, 0), "z": (0, 1)}[axis]
+    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+    return R
+
+
+POSES = ("scene", "narrow", "behind", "rotated")
+
+
+def make_case(height, width, views, pose, seed=3):
+    """A synth.scene window in one of the four pose / range settings:
+      scene    the scene's own poses, depth range 0.5 .. 5
+      narrow   the same poses, 0.3 .. 1.2 (sub-pixel steps between planes)
+      behind   0.01 .. 10 with the first source camera moved 0.05 m AHEAD of the reference along its z axis: the first
+               hypothesis plane (and every adaptive plane clamped at 1e-3) lies behind that camera, pz < 0.001; with three
+               views or more the second source stands 1.4 m ahead, which puts stage-3 planes behind a camera too
+      rotated  the reference camera rolled by 0.5 rad about its optical axis and yawed by 0.12 rad: about a quarter of the
+               samples leave the source images, through all four borders
+    (the images stay those of the scene: parity does not need consistent geometry).  Returns the window dict with
+    depth_min / depth_max set."""
+    from synth import scene
+    win = dict(scene.make_window(height, width, views, seed=seed))
+    c2ws = np.array(win["c2ws"], np.float64)
+    ref = win["ref_index"]
+    dmin, dmax = 0.5, 5.0
+    if pose == "narrow":
+        dmin, dmax = 0.3, 1.2
+    elif pose == "behind":
+        dmin, dmax = 0.01, 10.0
+        srcs = [i for i in range(views) if i != ref]
+        c2ws[srcs[0], :3, 3] = c2ws[ref, :3, 3] + c2ws[ref, :3, :3] @ np.array([0.01, -0.005, 0.05])
+        if len(srcs) > 1:  # stage 3's planes lie within 0.2 m of the stage-2 depth (1.3 .. 2.4 m in this scene): a camera between the slab and the wall
+            c2ws[srcs[1], :3, 3] = c2ws[ref, :3, 3] + c2ws[ref, :3, :3] @ np.array([0.02, 0.01, 1.4])
+    elif pose == "rotated":
+        c2ws[ref] = c2ws[ref] @ _rot("z", 0.5) @ _rot("y", 0.12)
+    elif pose != "scene":
+        raise ValueError(pose)
+    win["c2ws"] = c2ws.astype(np.float32)
+    win["depth_min"], win["depth_max"] = dmin, dmax
+    return win
+
+
+# the windows the E_* constants are the maximum over, and the sensitivity test runs on: (height, width, views, pose)
+# (the oracle's coordinate rounding grows with the coordinate: the largest shape of the GPU test is among them)
+CPU_WINDOWS = ((64, 96, 4, "scene"), (64, 96, 3, "narrow"), (64, 96, 4, "behind"), (64, 96, 3, "rotated"), (96, 64, 2, "scene"),
+               (96, 160, 4, "rotated"))
+
+
+def model_order(views, ref_index):
+    return [ref_index] + [i for i in range(views) if i != ref_index]
+
+
+def stage_K(K, stage):
+    """Rows 0-1 of the full-resolution K times 0.25 / 0.5 / 1, the product taken in double and stored as float."""
+    k = np.asarray(K, np.float32).reshape(3, 3).astype(np.float64)
+    k[:2] = (np.float64((0.25, 0.5, 1.0)[stage - 1]) * k[:2]).astype(np.float32)
+    return k
+
+
+def gate_weights(tensors, stage):
+    p = "volume_gates.stage%d." % stage
+    return {k[len(p):]: np.asarray(v, np.float64) for k, v in tensors.items() if k.startswith(p)}
+
+
+# ------------------------------------------------------------------ hypothesis planes
+def _up2(prev, h, w):
+    """x2 bilinear upsampling, align_corners=False: src = max(0.5 (dst + 0.5) - 0.5, 0), the far tap clamped to the last row / column."""
+    prev = np.asarray(prev, np.float64)
+    hp, wp = prev.shape
+    assert (h, w) == (2 * hp, 2 * wp)
+    sy = np.maximum(0.5 * (np.arange(h) + 0.5) - 0.5, 0.0)
+    sx = np.maximum(0.5 * (np.arange(w) + 0.5) - 0.5, 0.0)
+    y0, x0 = np.floor(sy).astype(int), np.floor(sx).astype(int)
+    y1, x1 = np.minimum(y0 + 1, hp - 1), np.minimum(x0 + 1, wp - 1)
+    ly, lx = (sy - y0)[:, None], (sx - x0)[None, :]
+    top = (1 - lx) * prev[y0][:, x0] + lx * prev[y0][:, x1]
+    bot = (1 - lx) * prev[y1][:, x0] + lx * prev[y1][:, x1]
+    return (1 - ly) * top + ly * bot
+
+
+def planes64(stage, engine_prev_depth, dmin, dmax, meta, h, w):
+    """(D, h, w) hypothesis depths.  Stage 1: D uniform planes dmin .. dmax.  Later stages: around the x2 upsampled previous-stage
+    depth (the caller passes the ENGINE's), lo = max(cur - D/2 Delta, 1e-3), d_k = lo + (hi - lo) k / D with hi = lo + D Delta and
+    Delta = interval_ratio[stage] * (dmax - dmin) / (D_1 - 1).  dmin, dmax are the float values the operator receives."""
+    dmin, dmax = float(np.float32(dmin)), float(np.float32(dmax))
+    D = int(meta["depth_num"][stage - 1])
+    base = (dmax - dmin) / (int(meta["depth_num"][0]) - 1)
+    k = np.arange(D, dtype=np.float64).reshape(D, 1, 1)
+    if stage == 1:
+        return np.broadcast_to(dmin + base * k, (D, h, w)).copy()
+    delta = float(np.float32(meta["interval_ratio"][stage - 1])) * base
+    cur = _up2(engine_prev_depth, h, w)
+    lo = np.maximum(cur - (D / 2.0) * delta, 1e-3)
+    hi = lo + D * delta
+    return lo[None] + (hi - lo)[None] * (k / D)
+
+
+# ------------------------------------------------------------------ cost volume
+def _inv_h(c2w):
+    return np.linalg.inv(np.asarray(c2w, np.float64).reshape(4, 4))
+
+
+def homography(K_stage, c2w_ref, c2w_src):
+    """Reference pixel (x, y, 1) * depth -> source pixel: M = [K w2c_src] [K w2c_ref]^-1, every inverse in double."""
+    K = np.asarray(K_stage, np.float64).reshape(3, 3)
+
+    def w2p(c2w):
+        m = _inv_h(c2w)
+        m[:3, :4] = K @ m[:3, :4]
+        return m
+    return w2p(c2w_src) @ np.linalg.inv(w2p(c2w_ref))
+
+
+def _bn1(x, g, p):
+    return (x - g[p + ".running_mean"][0]) / np.sqrt(g[p + ".running_var"][0] + BN_EPS) * g[p + ".weight"][0] + g[p + ".bias"][0]
+
+
+def cost_volume64(feats, planes, K_stage, c2w, gate_w, view_aggregation, nsrc_divisor=None, mutant=None, return_stats=False):
+    """feats (V, h, w, C), planes (D, h, w), c2w (V, 4, 4) in model order -> volume (D, h, w, C).
+    A source sample is valid iff pz >= 0.001 and -1 < u < w and -1 < v < h; it is the bilinear mix of its four taps read from the
+    source map with a one-pixel zero border, else 0.  View aggregation: mean over the sources of (g + 1) d^2 with d = warped - ref
+    and g = relu(BN(conv1x1(relu(BN(conv1x1(d^2))))))); otherwise the variance over all views, s2 / V - (s / V)^2.
+    nsrc_divisor: the divisor of the mean where it is not V - 1 (a view shard).
+    mutant: one of MUTANTS, a deliberate one-line mistake (tests/test_mvs_stage_ref.py shows each moves the volume beyond the bound
+    the GPU test sets); `spacing_Dm1` re-spaces the given planes from k / D to k / (D - 1) about plane 0.
+    return_stats: also dict(behind=share of samples with pz < 0.001, outside=share of the others outside the source image)."""
+    assert mutant is None or mutant in MUTANTS, mutant
+    feats = np.asarray(feats, np.float64)
+    planes = np.asarray(planes, np.float64)
+    V, h, w, C = feats.shape
+    D = planes.shape[0]
+    if mutant == "spacing_Dm1":
+        k = np.arange(D, dtype=np.float64).reshape(D, 1, 1)
+        planes = planes[0][None] + (planes[1] - planes[0])[None] * D * (k / (D - 1))
+    ys, xs = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    ref = feats[0][None]  # (1, h, w, C)
+    nsrc = V - 1
+    last = nsrc - 1 if mutant == "drop_last_view" else nsrc
+    acc = np.zeros((D, h, w, C))
+    s1 = np.broadcast_to(ref, (D, h, w, C)).copy()
+    s2 = s1 ** 2
+    n_behind = n_outside = 0
+    for v in range(1, 1 + last):
+        M = homography(K_stage, c2w[0], c2w[v])
+        rx = M[0, 0] * xs + M[0, 1] * ys + M[0, 2]
+        ry = M[1, 0] * xs + M[1, 1] * ys + M[1, 2]
+        rz = M[2, 0] * xs + M[2, 1] * ys + M[2, 2]
+        px, py, pz = rx[None] * planes + M[0, 3], ry[None] * planes + M[1, 3], rz[None] * planes + M[2, 3]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            u, vv = px / pz, py / pz
+        if mutant == "shift":
+            u = u + 1e-3
+        front = pz >= 0.001
+        if mutant == "border":
+            inside = (u >= 0) & (u <= w - 1) & (vv >= 0) & (vv <= h - 1)
+        else:
+            inside = (u > -1) & (u < w) & (vv > -1) & (vv < h)  # (NaN fails)
+        valid = inside if mutant == "no_behind_mask" else (front & inside)
+        n_behind += int((~front).sum())
+        n_outside += int((front & ~inside).sum())
+        uc, vc = np.where(valid, u, -1.0), np.where(valid, vv, -1.0)
+        x0, y0 = np.floor(uc), np.floor(vc)
+        ax, ay = (uc - x0)[..., None], (vc - y0)[..., None]
+        xi, yi = x0.astype(np.int64) + 1, y0.astype(np.int64) + 1  # indices into the bordered map: 0 .. w, 0 .. h
+        src = np.zeros((h + 2, w + 2, C))
+        src[1:-1, 1:-1] = feats[v]
+        warped = ((1 - ax) * (1 - ay) * src[yi, xi] + ax * (1 - ay) * src[yi, xi + 1] +
+                  (1 - ax) * ay * src[yi + 1, xi] + ax * ay * src[yi + 1, xi + 1]) * valid[..., None]
+        if view_aggregation:
+            d2 = (warped - ref) ** 2
+            if mutant == "no_gate":
+                g = 0.0
+            else:
+                z = d2 @ gate_w["0.weight"].reshape(C) + gate_w["0.bias"][0]
+                z = np.maximum(_bn1(z, gate_w, "1"), 0.0)
+                z = z * gate_w["3.weight"].reshape(()) + gate_w["3.bias"][0]
+                g = np.maximum(_bn1(z, gate_w, "4"), 0.0)[..., None]
+            acc += (g + 1.0) * d2
+        else:
+            s1 += warped
+            s2 += warped ** 2
+    if view_aggregation:
+        div = float(nsrc_divisor if nsrc_divisor is not None else nsrc)
+        vol = acc / (div + 1.0 if mutant == "divisor_V" else div)
+    else:
+        n = float(V + 1 if mutant == "divisor_V" else V)
+        vol = s2 / n - (s1 / n) ** 2
+    if return_stats:
+        total = float(max(last, 1) * D * h * w)
+        return vol, dict(behind=n_behind / total, outside=n_outside / total)
+    return vol
+
+
+# ------------------------------------------------------------------ prob head, regression, FeatureNet
+def prob64(x11, prob_weight):
+    """x11 (D, h, w, 8), weight (1, 8, 3, 3, 3) -> logits (D, h, w): conv3d, padding 1."""
+    x = torch.from_numpy(np.ascontiguousarray(np.asarray(x11, np.float64))).permute(3, 0, 1, 2)[None]
+    wt = torch.from_numpy(np.asarray(prob_weight, np.float64))
+    return F.conv3d(x, wt, None, 1, 1)[0, 0].numpy()
+
+
+def regress64(logits, planes):
+    """Returns (depth (h, w), E[k] (h, w), sum4 (D, h, w)): softmax over D, its expectation over the planes and over the plane index,
+    and sum4[i] = p[i-1] + p[i] + p[i+1] + p[i+2] (planes outside 0 .. D-1 count 0): the confidence is sum4 at i = clamp(trunc(E[k]))."""
+    lg = np.asarray(logits, np.float64)
+    D = lg.shape[0]
+    e = np.exp(lg - lg.max(axis=0, keepdims=True))
+    p = e / e.sum(axis=0, keepdims=True)
+    depth = (p * np.asarray(planes, np.float64)).sum(axis=0)
+    ek = (p * np.arange(D, dtype=np.float64).reshape(D, 1, 1)).sum(axis=0)
+    pp = np.concatenate([np.zeros((1,) + p.shape[1:]), p, np.zeros((2,) + p.shape[1:])])
+    sum4 = pp[0:D] + pp[1:D + 1] + pp[2:D + 2] + pp[3:D + 3]
+    return depth, ek, sum4
+
+
+def conf_at(sum4, idx):
+    D = sum4.shape[0]
+    return np.take_along_axis(sum4, np.clip(idx, 0, D - 1)[None].astype(np.int64), axis=0)[0]
+
+
+def conf_error(conf, ek, sum4):
+    """|conf - sum4[trunc(E[k])]| per pixel; where E[k] lies within EK_INTEGER_BAND of an integer r, the smaller of the errors at r - 1 and r."""
+    r = np.rint(ek)
+    near = np.abs(ek - r) <= EK_INTEGER_BAND
+    err = np.abs(conf - conf_at(sum4, np.trunc(ek)))
+    alt = np.minimum(np.abs(conf - conf_at(sum4, r - 1)), np.abs(conf - conf_at(sum4, r)))
+    return np.where(near, np.minimum(err, alt), err), near
+
+
+class _W64:
+    def __init__(self, tensors):
+        self.t = {k: torch.from_numpy(np.ascontiguousarray(v)).double() for k, v in tensors.items() if k.startswith("feature_net.")}
+
+    def __getitem__(self, k):
+        return self.t[k]
+
+
+def features64(bgrs, tensors, ref_index=0):
+    """The oracle's preprocess + feature_net with double weights and a double image (the u8 -> float image itself is the input: its
+    float values, exactly).  Returns [feat1, feat2, feat3], each (V, h, w, C) in model order."""
+    from oracle import mvsnet_oracle as O
+    K = np.eye(3, dtype=np.float32)
+    image, _, _ = O.preprocess(bgrs, K, [np.eye(4, dtype=np.float32)] * len(bgrs), ref_index)
+    with torch.no_grad():
+        feats = O.feature_net(image.double(), _W64(tensors))
+    return [f.permute(0, 2, 3, 1).contiguous().numpy() for f in feats]
+
+
+def rng_of(x):
+    return float(np.max(x) - np.min(x))
+
+
+def border_slices():
+    """The four image borders of a (D, h, w, ...) tensor, named."""
+    return (("row 0", np.s_[:, 0]), ("row h-1", np.s_[:, -1]), ("column 0", np.s_[:, :, 0]), ("column w-1", np.s_[:, :, -1]))

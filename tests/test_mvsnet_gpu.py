@@ -563,8 +563,10 @@ def test_view_outer_cost_volume_is_bit_identical(trained_blob, monkeypatch, view
     """k_costvol5 (round 6: view outer, the planes of a depth chunk inner, one float4 accumulator per plane in registers, the view's matrix
     in scalar registers, the pixel's ray hoisted out of the plane loop) against k_costvol3 (plane outer, view inner, one accumulator):
     per voxel the views are added in the same order with the same products, so the three cost volumes -- and everything behind them --
-    are equal bit for bit.  Depth ranges as in the LDS-staged kernel's test (samples behind the camera, outside every view, sub-pixel
-    steps); 1 to 7 source views; depth chunks of 4 planes (the product's choice) and of 8 (DR_CV_DCHUNK*); and the kernel's two A/B forms of
+    are equal bit for bit.  Depth ranges as in the LDS-staged kernel's test (samples outside every view, sub-pixel steps; at 0.01 .. 10 about
+    1 % of the samples of stages 1 and 2 lie behind a source camera, but with the scene's poses every one of them falls outside the source image
+    as well, so the pz < 0.001 mask itself decides nothing in these windows -- tests/test_mvs_stage_ref.py shows it, tests/test_mvs_stages_gpu.py
+    has the windows where it does); 1 to 7 source views; depth chunks of 4 planes (the product's choice) and of 8 (DR_CV_DCHUNK*); and the kernel's two A/B forms of
     the parity build: every sample gathering its taps (DR_CV5_REUSE=0: the product skips a sample's gathers where its footprint is the
     previous plane's and copies the taps), one-row and four-row workgroup tiles at every stage (DR_CV5_ROWS)."""
     from synth import scene
@@ -615,7 +617,8 @@ def test_lds_staged_cost_volume_is_bit_identical(trained_blob, monkeypatch, view
     against k_costvol3 (every tap a gather from global memory): the same arithmetic on the same tap values in the same view order, so the
     three cost volumes are equal bit for bit.  The depth ranges make the kernel take every path: boxes that fit (the scene's own range),
     steps whose planes lie metres apart or in front of the cameras so that the box does not fit or no sample falls inside the view
-    (0.01 .. 10 as the headline runs it, 2 .. 40), a narrow range (sub-pixel steps), 1 to 6 source views, two shapes."""
+    (0.01 .. 10 as the headline runs it, 2 .. 40; the samples that 0.01 .. 10 puts behind a source camera are all outside its image too: the
+    behind-camera mask is not what these windows exercise, see tests/test_mvs_stage_ref.py), a narrow range (sub-pixel steps), 1 to 6 source views, two shapes."""
     from synth import scene
     from tandem_amd.dr_mvsnet import DrMvsnet
     vols = []
