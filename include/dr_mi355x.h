@@ -27,7 +27,7 @@ enum {
   DR_ERR_ARG = 1,       /* bad argument (null pointer, aliasing views, unsupported size) */
   DR_ERR_PROTOCOL = 2,  /* call-order violation (reference: exit(EXIT_FAILURE)) */
   DR_ERR_DEVICE = 3,    /* HIP error / no GPU */
-  DR_ERR_IO = 4,        /* weight blob missing or malformed */
+  DR_ERR_IO = 4,        /* a file is missing, malformed or cannot be written (weight blob, mesh, map file) */
   DR_ERR_CAPACITY = 5,  /* hash table / block pool exhausted (reference: KERNEL_ABORT trap, heap.cu:16) */
   DR_ERR_UNSUPPORTED = 6
 };
@@ -316,6 +316,52 @@ int drf_render_stats(drf_t *h, uint64_t out[4]);
 /* Last extraction: [0] blocks meshed (resident + stored), [1] host blocks uploaded (a block staged by k chunks counts k
  * times), [2] chunks (1 for a resident pass over a non-empty pool). */
 int drf_mesh_stats(drf_t *h, uint64_t out[3]);
+
+/* --- map files: the whole map -- resident blocks and host store -- saved to a file and loaded into a new engine (no reference
+ * counterpart; DESIGN.md §7c "Saving and loading the map", INTEGRATION.md "Map files").
+ * The file is a function of the map alone: every block of the map keyed by coordinate, blocks that were allocated and never
+ * updated included, and nothing about the pool, slot order, streaming state, counters or options except voxel_size.  A bounded
+ * streaming engine and an unbounded one write the same bytes after the same scans, and an engine that loads the file goes on
+ * exactly where the saving engine stood: integration, update counts, ray-casts and meshes agree bit for bit.  Those
+ * statements assume that the loading engine's other options (truncation distance, weights, depths, intrinsics) equal the
+ * saving engine's: only voxel_size is recorded and checked.
+ * Layout, little-endian, 72 + 4104 n bytes:
+ *   offset 0          8 bytes magic "DRFMAP01"
+ *          8          u32 header size = 64
+ *          12         u32 block edge = 8
+ *          16         u32 bytes per voxel = 8
+ *          20         f32 voxel_size, stored as its bit pattern
+ *          24         u64 n = number of blocks
+ *          32         32 reserved bytes, all zero
+ *          64         n x u64 packed block keys, STRICTLY ASCENDING: 21 bits per axis, each coordinate biased by 2^20, x in the
+ *                     high bits -- ((x + 2^20) << 42) | ((y + 2^20) << 21) | (z + 2^20)
+ *          64 + 8 n   n x 4096 bytes of voxels in the keys' order: per block 512 voxels {f32 sdf, u8 b, g, r, u8 weight} in
+ *                     index order x*64 + y*8 + z, exactly what drf_export_blocks returns
+ *          64 + 4104n u64 checksum over the key table and the voxel bytes, 8 bytes at a time: h = 0xcbf29ce484222325, then for
+ *                     every little-endian u64 word w in file order h = (h ^ w) * 0x100000001b3 mod 2^64
+ * chunk_blocks = blocks per transfer chunk (0 = min(num_blocks, 8192); never more than the map holds or 2^20): it bounds the
+ * page-locked staging, two buffers of chunk_blocks * 4096 bytes.  Any file failure is DR_ERR_IO with the path in
+ * dr_last_error(); a null argument is DR_ERR_ARG. */
+/* Host-only, needs no device (like drf_streaming_min_radius): validates the WHOLE file -- size against n, magic, header size,
+ * block edge, voxel bytes, reserved bytes, key order (and keys below 2^63), checksum -- and returns its voxel_size and n. */
+int drf_map_info(const char *path, float *voxel_size, uint64_t *n_blocks);
+/* Legal where drf_integrate_scan_async is (otherwise DR_ERR_PROTOCOL); a pending mesh extraction stays pending.  Like the
+ * map-scope mesh pass it folds pending evictions first and is otherwise read-only: pool, slot order, host store, streaming
+ * state, mesh-update baseline and all counters stay as they were.  Writes <path>.part and renames it on success, so a failed
+ * save never leaves a truncated file under the requested name.  An empty map gives a valid 72-byte file. */
+int drf_save_map(drf_t *h, const char *path, size_t chunk_blocks);
+/* Legal where drf_integrate_scan_async is, on an engine whose map is EMPTY: a non-empty pool or host store, or a pending
+ * eviction, is DR_ERR_PROTOCOL.  The whole file is validated first (DR_ERR_IO); a voxel_size whose bits differ from the
+ * engine's is DR_ERR_ARG.  Streaming off: every block goes into the pool, slot i holding the block with the i-th key; more
+ * blocks than num_blocks is DR_ERR_CAPACITY.  Streaming on: every block goes into the host store (more than
+ * host_capacity_blocks: DR_ERR_CAPACITY) and the next scan brings in what lies within the radius, so the exactness contract
+ * holds from the first scan; until then a resident-scope render sees nothing and a map-scope render (DRF_RENDER_MAP, and
+ * likewise DRF_MESH_MAP) sees everything.  After a successful load, and until the next drf_integrate_scan_async,
+ * drf_render_async is legal wherever drf_integrate_scan_async is, so a loaded map can be ray-cast from any pose before (or
+ * without) a scan.  A failed load leaves the engine empty and usable.  A load makes the next mesh
+ * update full, does not count as streamed in or out in drf_streaming_stats, and leaves the update counters of drf_stats at
+ * zero ([0] reports the pool as always). */
+int drf_load_map(drf_t *h, const char *path, size_t chunk_blocks);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

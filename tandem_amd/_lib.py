@@ -126,6 +126,9 @@ SIGNATURES = {
                                            C.POINTER(C.c_size_t), f32p, f32p, C.POINTER(C.c_int)]),
     "drf_mesh_update_reset": (C.c_int, [vp]),
     "drf_mesh_update_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_map_info": (C.c_int, [C.c_char_p, f32p, C.POINTER(C.c_uint64)]),
+    "drf_save_map": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
+    "drf_load_map": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
 }
 
 

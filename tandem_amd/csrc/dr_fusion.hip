@@ -38,6 +38,7 @@
 #include "dr_common.h"
 #include "fusion_host.h"  // the host half of the map: block keys (kBS), reach bounds, host store, chunk planner
 #include "hip_owner.h"    // HipOwner, DeviceBuf, PinnedBuf: what the engine takes from the runtime
+#include "map_file.h"     // the map file: MapWriter, MapReader (host only)
 #define DR_MC_CONST __device__ static const
 #include "mc_tables.h"
 
@@ -809,7 +810,7 @@ class FusionEngine {
     if (!bgr || !depth || !pose16) fail(DR_ERR_ARG, "IntegrateScanAsync: null argument");
     expect(kIntegrate, "Please call the functions like Integration -> RenderAsync -> GetRenderResults.");
     if (st_radius_ <= 0.0f && !store_.empty()) fail(DR_ERR_PROTOCOL, "IntegrateScanAsync: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", store_.size());
-    next_ = kRender;
+    next_ = kRender; loaded_ = false;
     DR_HIP(hipSetDevice(device_));
     const float depth_bound = st_radius_ > 0.0f ? max_valid_depth(depth, npix_, o_.min_sensor_depth, o_.max_sensor_depth) : 0.0f;
     scan_between_streaming(pose16, depth_bound, [&] {
@@ -890,7 +891,8 @@ class FusionEngine {
   }
   // tsdf_volume.cu:634-700
   void render_async(const float *const *poses, int n) {
-    expect(kRender, "Please call the functions like IntegrateScanAsync -> RenderAsync -> GetRenderResult.");
+    // (a map that was loaded may be rendered before its first scan: drf_load_map)
+    if (!(loaded_ && next_ == kIntegrate)) expect(kRender, "Please call the functions like IntegrateScanAsync -> RenderAsync -> GetRenderResult.");
     if (n != (int)renders_.size()) fail(DR_ERR_PROTOCOL, "Can only render exactly as many poses as streams. Streams: %zu, Poses: %d.", renders_.size(), n);
     DR_HIP(hipSetDevice(device_));
     // map scope: the stored blocks these poses can read, decided before anything changes (DR_ERR_CAPACITY leaves all as it was)
@@ -1277,6 +1279,132 @@ class FusionEngine {
     if (n) *n = i;
   }
 
+  // ---- the map file (include/dr_mi355x.h "map files"; DESIGN.md §7c "Saving and loading the map") ----
+  // Resident and stored blocks merged in ascending key order, chunk by chunk: k_map_gather writes a chunk's resident blocks
+  // straight into one of two pinned buffers while the host copies the stored ones into their positions of it, appends the
+  // other buffer to the file and folds it into the checksum.  Folds pending evictions first; beyond that nothing changes.
+  void save_map(const char *path, size_t chunk_blocks) {
+    if (!path) fail(DR_ERR_ARG, "drf_save_map: null argument");
+    expect(kIntegrate, "drf_save_map: call it where IntegrateScanAsync may be called.");
+    settle();
+    const int nres = pool_blocks();
+    std::vector<unsigned long long> res((size_t)nres);
+    if (nres > 0) {  // the resident order: (blk_key, slot) pairs sorted by key, as mesh_tables sorts the keys
+      std::vector<int> iota((size_t)nres);
+      for (int i = 0; i < nres; ++i) iota[i] = i;
+      mio_keys_.reserve((size_t)nres, int_stream_); mio_slot_in_.reserve((size_t)nres, int_stream_);
+      mio_slot_.reserve((size_t)nres, int_stream_); mio_dst_.reserve((size_t)nres, int_stream_);
+      DR_HIP(hipMemcpy(mio_slot_in_.get(), iota.data(), (size_t)nres * 4, hipMemcpyHostToDevice));
+      size_t tb = 0;
+      DR_HIP(rocprim::radix_sort_pairs(nullptr, tb, d_.blk_key, mio_keys_.get(), mio_slot_in_.get(), mio_slot_.get(), (size_t)nres, 0, 63, int_stream_));
+      mio_tmp_.reserve(std::max<size_t>(tb, 256), int_stream_);  // (never null: a null scratch is rocprim's size query)
+      tb = mio_tmp_.capacity();
+      DR_HIP(rocprim::radix_sort_pairs(mio_tmp_.get(), tb, d_.blk_key, mio_keys_.get(), mio_slot_in_.get(), mio_slot_.get(), (size_t)nres, 0, 63, int_stream_));
+      DR_HIP(hipMemcpyAsync(res.data(), mio_keys_.get(), (size_t)nres * 8, hipMemcpyDeviceToHost, int_stream_));
+      DR_HIP(hipStreamSynchronize(int_stream_));
+    }
+    const std::vector<unsigned long long> sto = store_.sorted_keys();
+    const size_t n = res.size() + sto.size();
+    std::vector<unsigned long long> keys;
+    std::vector<unsigned char> stored;
+    keys.reserve(n); stored.reserve(n);
+    const BlockRange all{{INT_MIN, INT_MIN, INT_MIN}, {INT_MAX, INT_MAX, INT_MAX}};
+    for_each_in_range(res, sto, all, [&](unsigned long long key, bool st) { keys.push_back(key); stored.push_back(st ? 1 : 0); });
+    const size_t chunk = map_chunk(chunk_blocks, n), nc = (n + chunk - 1) / chunk;
+    // per chunk the resident blocks rb[c] .. rb[c + 1] of the sorted pairs; each one's position within its chunk
+    std::vector<size_t> rb(nc + 1, 0);
+    std::vector<int> dst;
+    dst.reserve((size_t)nres);
+    for (size_t i = 0; i < n; ++i)
+      if (!stored[i]) { ++rb[i / chunk + 1]; dst.push_back((int)(i % chunk)); }
+    for (size_t c = 0; c < nc; ++c) rb[c + 1] += rb[c];
+    if (nres > 0) DR_HIP(hipMemcpy(mio_dst_.get(), dst.data(), (size_t)nres * 4, hipMemcpyHostToDevice));
+    ensure_map_io(chunk);
+    std::string err;
+    MapWriter w;
+    if (!w.open(path, o_.voxel_size, keys.data(), n, err)) fail(DR_ERR_IO, "drf_save_map: %s", err.c_str());
+    auto gather = [&](size_t c) {  // chunk c's resident blocks into the current buffer; nothing is launched for none
+      const int m = (int)(rb[c + 1] - rb[c]);
+      if (m == 0) return;
+      hipLaunchKernelGGL(k_map_gather, dim3(std::min(cdiv(m, 4), 1024)), dim3(256), 0, int_stream_, d_.vox, mio_slot_.get() + rb[c], mio_dst_.get() + rb[c], m,
+                         (uint4 *)mio_.dev());
+      DR_HIP(hipGetLastError());
+      mio_.record(int_stream_);
+    };
+    bool ok = true;
+    if (nc > 0) gather(0);
+    for (size_t c = 0; c < nc && ok; ++c) {
+      const size_t b = c * chunk, m = std::min(chunk, n - b);
+      if (c + 1 < nc) { mio_.flip(); gather(c + 1); mio_.flip(); }  // runs while the host finishes chunk c
+      unsigned char *h = mio_.host();
+      for (size_t i = 0; i < m; ++i)
+        if (stored[b + i]) memcpy(h + i * 4096, store_.get(keys[b + i]), 4096);
+      mio_.wait();
+      ok = w.append(h, m, err);
+      mio_.flip();
+    }
+    ok = ok && w.close(err);
+    DR_HIP(hipStreamSynchronize(int_stream_));  // (a failed write leaves the next chunk's gather in flight)
+    if (!ok) fail(DR_ERR_IO, "drf_save_map: %s", err.c_str());
+  }
+  // The file validated as a whole first, then its blocks placed: into the pool in the keys' order (streaming off; k_in_place
+  // reads one pinned buffer while the host reads the file into the other) or into the host store (streaming on).  A failure
+  // leaves the map empty.
+  void load_map(const char *path, size_t chunk_blocks) {
+    if (!path) fail(DR_ERR_ARG, "drf_load_map: null argument");
+    expect(kIntegrate, "drf_load_map: call it where IntegrateScanAsync may be called.");
+    const bool pending = ev_pending_;
+    settle();
+    const int nres = pool_blocks();
+    if (pending || nres != 0 || !store_.empty())
+      fail(DR_ERR_PROTOCOL, "drf_load_map: the map is not empty (%d resident blocks, %zu in the host store%s)", nres, store_.size(), pending ? ", an eviction was pending" : "");
+    std::string err;
+    MapReader rd;
+    if (!rd.open(path, err)) fail(DR_ERR_IO, "drf_load_map: %s", err.c_str());
+    const float vs = rd.voxel_size();
+    if (memcmp(&vs, &o_.voxel_size, 4) != 0) fail(DR_ERR_ARG, "drf_load_map: %s has voxel_size %.9g, the engine %.9g", path, vs, o_.voxel_size);
+    const uint64_t n = rd.blocks();
+    const bool to_store = st_radius_ > 0.0f;
+    if (to_store ? n > (uint64_t)st_host_cap_ : n > (uint64_t)o_.num_blocks)
+      fail(DR_ERR_CAPACITY, "drf_load_map: %llu blocks do not fit in the %s (%llu)", (unsigned long long)n, to_store ? "host store" : "pool",
+           (unsigned long long)(to_store ? st_host_cap_ : (size_t)o_.num_blocks));
+    mu_force_full_ = true;
+    if (n == 0) { loaded_ = true; return; }
+    const std::vector<unsigned long long> &keys = rd.keys();
+    const size_t chunk = map_chunk(chunk_blocks, (size_t)n);
+    ensure_map_io(chunk);
+    bool ok = true;
+    if (to_store) {  // the next scan's stream_before_scan brings in what lies within the radius
+      for (size_t b = 0; b < n && ok; b += chunk) {
+        const size_t m = std::min(chunk, (size_t)n - b);
+        ok = rd.read(mio_.host(), m, err);
+        for (size_t i = 0; i < m && ok; ++i) store_.put(keys[b + i], mio_.host() + i * 4096);
+      }
+    } else {
+      mio_keys_.reserve((size_t)n, int_stream_);
+      DR_HIP(hipMemcpy(mio_keys_.get(), keys.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+      for (auto &r : renders_) DR_HIP(hipStreamWaitEvent(int_stream_, r.cast, 0));  // blocks are added
+      for (size_t b = 0; b < n && ok; b += chunk) {
+        const size_t m = std::min(chunk, (size_t)n - b);
+        mio_.wait();  // the placement of two chunks ago has read this buffer
+        ok = rd.read(mio_.host(), m, err);
+        if (!ok) break;
+        hipLaunchKernelGGL(k_in_place, dim3(std::min(cdiv((int)m, 4), 1024)), dim3(256), 0, int_stream_, d_, mio_keys_.get() + b, (const uint4 *)mio_.dev(), (int)m);
+        hipLaunchKernelGGL(k_in_finish, dim3(1), dim3(64), 0, int_stream_, d_.n_alloc, (int)m);
+        DR_HIP(hipGetLastError());
+        mio_.record(int_stream_);
+        mio_.flip();
+      }
+      DR_HIP(hipStreamSynchronize(int_stream_));
+    }
+    if (ok && !rd.verified()) { ok = false; err = std::string("map file ") + path + " changed while it was read"; }
+    if (!ok) {
+      clear_map();
+      fail(DR_ERR_IO, "drf_load_map: %s", err.c_str());
+    }
+    loaded_ = true;
+  }
+
  private:
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
@@ -1285,6 +1413,30 @@ class FusionEngine {
     int na = 0;
     DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
     return std::min(na, o_.num_blocks);
+  }
+  // blocks per chunk of a map file of n blocks: the caller's, or min(num_blocks, 8192); never more than the file has or 2^20
+  size_t map_chunk(size_t chunk_blocks, size_t n) const {
+    const size_t want = chunk_blocks ? chunk_blocks : (size_t)std::min(o_.num_blocks, kStageBlocks);
+    return std::max<size_t>(1, std::min({want, n, (size_t)1 << 20}));
+  }
+  void ensure_map_io(size_t chunk) {  // after settle(): no kernel uses the old buffers
+    if (!mio_.opened()) mio_.open(own_);
+    mio_.reserve(chunk * 4096);
+  }
+  // a load that failed half way: pool, block index and host store as a new engine has them (the counters were not touched)
+  void clear_map() {
+    store_ = HostBlockStore();
+    const int placed = pool_blocks();
+    if (placed == 0) return;
+    const size_t cap = (size_t)d_.cmask + 1;
+    DR_HIP(hipMemsetAsync(d_.vals, 0xFF, cap * sizeof(int), int_stream_));
+    hipLaunchKernelGGL(k_fill_keys, dim3(1024), dim3(256), 0, int_stream_, d_.keys, cap);
+    DR_HIP(hipMemsetAsync(d_.vox, 0, (size_t)placed * 4096, int_stream_));
+    for (int l = 0; l < kSuperLevels; ++l) DR_HIP(hipMemsetAsync(d_.super[l], 0, (size_t)1 << (3 * (kGridBits - kSuperShift[l])), int_stream_));
+    DR_HIP(hipMemsetAsync(d_.present, 0, ((size_t)1 << (3 * kPresentBits - 5)) * sizeof(unsigned), int_stream_));
+    DR_HIP(hipMemsetAsync(d_.grid, 0, ((size_t)1 << (3 * kGridBits)) * sizeof(int), int_stream_));
+    DR_HIP(hipMemsetAsync(d_.n_alloc, 0, 4 * sizeof(int), int_stream_));
+    DR_HIP(hipStreamSynchronize(int_stream_));
   }
   // every pending eviction folded into the host store, the device idle
   void settle() {
@@ -1769,6 +1921,7 @@ class FusionEngine {
   std::vector<Render> renders_;
   int free_slot_ = 0;
   Next next_ = kIntegrate;
+  bool loaded_ = false;  // the map came from drf_load_map and no scan followed yet: RenderAsync is legal where IntegrateScanAsync is
   // mesh extraction state (allocated with the first ExtractMeshAsync)
   static constexpr unsigned kMeshMaxTriangles = 20000000;
   bool mesh_pending_ = false;
@@ -1822,6 +1975,11 @@ class FusionEngine {
   double ev_p_[3] = {0.0, 0.0, 0.0};
   ReachBalls reach_;  // balls that hold every block centre of the map
   uint64_t st_out_total_ = 0, st_in_total_ = 0;
+  // map file transport (allocated with the first drf_save_map / drf_load_map): two pinned chunk buffers, the sorted (key, slot) pairs
+  PinnedPair mio_;
+  DeviceBuf<unsigned long long> mio_keys_;
+  DeviceBuf<int> mio_slot_in_, mio_slot_, mio_dst_;
+  DeviceBuf<unsigned char> mio_tmp_;
 };
 
 }  // namespace dr
@@ -1937,6 +2095,15 @@ int drf_streaming_stats(drf_t *h, uint64_t out[6]) {
 int drf_export_host_blocks(drf_t *h, int max_blocks, int32_t *coords, uint8_t *voxels, int *n) {
   return guarded([&] { eng(h)->export_host_blocks(max_blocks, coords, voxels, n); });
 }
+int drf_map_info(const char *path, float *voxel_size, uint64_t *n_blocks) {
+  return guarded([&] {
+    if (!path || !voxel_size || !n_blocks) dr::fail(DR_ERR_ARG, "drf_map_info: null argument");
+    std::string err;
+    if (!dr::map_file_info(path, voxel_size, n_blocks, err)) dr::fail(DR_ERR_IO, "drf_map_info: %s", err.c_str());
+  });
+}
+int drf_save_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->save_map(path, chunk_blocks); }); }
+int drf_load_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->load_map(path, chunk_blocks); }); }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }
 int drf_render_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->render_stats(out); }); }
 int drf_set_mesh_scope(drf_t *h, int scope) { return guarded([&] { eng(h)->set_mesh_scope(scope); }); }

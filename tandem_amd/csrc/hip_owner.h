@@ -1,5 +1,6 @@
 // What the DrFusion engine takes from the HIP runtime (included by dr_fusion.hip): HipOwner for what lives as long as the engine, DeviceBuf /
-// PinnedBuf for scratch that grows with its use, BlockStaging for the double-buffered transport of stored voxel blocks to the device.
+// PinnedBuf for scratch that grows with its use, BlockStaging for the double-buffered transport of stored voxel blocks to the device,
+// PinnedPair for the two page-locked chunk buffers of the map file.
 #pragma once
 #include <vector>
 
@@ -134,6 +135,43 @@ class BlockStaging {
   } slot_[2];
   int cur_ = 0;
   hipStream_t stream_ = nullptr;
+};
+
+// Two page-locked buffers that kernels address directly, used in turn: the host fills or drains one while a kernel reads or
+// writes the other (the map file's chunks, dr_fusion.hip save_map / load_map).  No device twin and no stream of its own, which
+// is what sets it apart from BlockStaging: the kernels run on the caller's stream, and per slot ONE event says that the kernel
+// given that slot has finished with it.
+class PinnedPair {
+ public:
+  void open(HipOwner &own) { for (auto &s : slot_) s.done = own.event(); }
+  bool opened() const { return slot_[0].done != nullptr; }
+  // both slots hold `bytes`; contents are not kept.  The caller makes sure that no kernel still uses the old allocations.
+  void reserve(size_t bytes) {
+    for (auto &s : slot_) {
+      s.host.reserve(bytes);
+      DR_HIP(hipHostGetDevicePointer((void **)&s.dev, s.host.get(), 0));
+    }
+  }
+  // the other slot becomes the current one
+  void flip() { cur_ ^= 1; }
+  unsigned char *host() const { return slot_[cur_].host.get(); }
+  unsigned char *dev() const { return slot_[cur_].dev; }  // the same bytes as the kernels address them
+  // the current slot's kernel is the last thing enqueued on st / the host waits for it (at once if the slot never had one)
+  void record(hipStream_t st) { DR_HIP(hipEventRecord(slot_[cur_].done, st)); slot_[cur_].busy = true; }
+  void wait() {
+    if (!slot_[cur_].busy) return;
+    DR_HIP(hipEventSynchronize(slot_[cur_].done));
+    slot_[cur_].busy = false;
+  }
+
+ private:
+  struct Slot {
+    PinnedBuf<unsigned char> host;
+    unsigned char *dev = nullptr;
+    hipEvent_t done = nullptr;
+    bool busy = false;
+  } slot_[2];
+  int cur_ = 0;
 };
 
 }  // namespace dr

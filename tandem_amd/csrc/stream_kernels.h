@@ -13,7 +13,9 @@
 //   k_ev_reindex   rebuilt from the surviving blocks [0, new n_alloc)
 //   k_ev_finish    n_alloc (and the table's block count) updated, the counts published to pinned memory
 // Every kernel after k_ev_select exits at once when the selection is empty.  Stream-in (k_in_place + k_in_finish) appends
-// blocks from a pinned upload to the pool and publishes them the way k_alloc_commit does.
+// blocks from a pinned upload to the pool and publishes them the way k_alloc_commit does.  The map file (drf_save_map /
+// drf_load_map) uses the same two moves: k_map_gather copies pool blocks into a chunk of the file without touching the map,
+// and a load places the file's chunks with k_in_place + k_in_finish.
 
 struct StreamDev {
   int *ctl;                    // [0] blocks selected (uncapped), [1] holes, [2] tail survivors, [3] table blocks re-inserted,
@@ -222,4 +224,17 @@ __global__ __launch_bounds__(256) void k_in_place(const FusionDev d, const unsig
 }
 __global__ void k_in_finish(int *n_alloc, int n) {
   if (threadIdx.x == 0 && blockIdx.x == 0) n_alloc[0] += n;
+}
+
+// Map save: pool block src[i] -> position dst[i] of the chunk buffer `out` (mapped pinned memory the file is written from),
+// i in [0, n): one wave per block, four uint4 per lane.  Writes nothing else -- grid, presence bits and blk_key stay as they are.
+__global__ __launch_bounds__(256) void k_map_gather(const Voxel *__restrict__ vox, const int *__restrict__ src, const int *__restrict__ dst, int n,
+                                                    uint4 *__restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+    const uint4 *a = reinterpret_cast<const uint4 *>(vox + (size_t)src[i] * 512);
+    uint4 *b = out + (size_t)dst[i] * 256;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[lane + 64 * k] = a[lane + 64 * k];
+  }
 }

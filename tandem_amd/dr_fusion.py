@@ -2,6 +2,7 @@
 on top of the C ABI of libdr_mi355x.so: same method names, call order contract and argument meaning.
 Protocol violations raise DrError (the reference prints and exit()s)."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -75,6 +76,13 @@ def streaming_min_radius(options):
     r = C.c_float()
     check(_lib.lib().drf_streaming_min_radius(C.byref(options), C.byref(r)))
     return float(r.value)
+
+
+def map_info(path):
+    """drf_map_info: validates the whole map file (host-only) and returns (voxel_size, number of blocks)."""
+    vs, n = C.c_float(), C.c_uint64()
+    check(_lib.lib().drf_map_info(os.fsencode(path), C.byref(vs), C.byref(n)))
+    return float(vs.value), int(n.value)
 
 
 class DrFusion:
@@ -243,6 +251,18 @@ class DrFusion:
         got = C.c_int()
         check(self._L.drf_export_host_blocks(self._h, n, coords.ctypes.data_as(C.POINTER(C.c_int32)), vox.ctypes.data_as(u8p), C.byref(got)))
         return {tuple(int(v) for v in coords[i]): vox[i] for i in range(got.value)}
+
+    # ---- map files (include/dr_mi355x.h "map files", DESIGN.md "Saving and loading the map") ----
+    def save_map(self, path, chunk_blocks=0):
+        """The whole map -- resident blocks and host store -- to a file that depends on the map alone (tandem_amd.map_file
+        reads it).  Changes nothing in the engine.  chunk_blocks bounds the pinned staging (0 = min(num_blocks, 8192))."""
+        check(self._L.drf_save_map(self._h, os.fsencode(path), int(chunk_blocks)))
+
+    def load_map(self, path, chunk_blocks=0):
+        """A saved map into this engine, whose map must be empty: into the pool in key order (streaming off) or into the host
+        store (streaming on).  DrError on a bad file (DR_ERR_IO), another voxel_size (DR_ERR_ARG), too many blocks
+        (DR_ERR_CAPACITY) or a non-empty map (DR_ERR_PROTOCOL); the engine then stays empty and usable."""
+        check(self._L.drf_load_map(self._h, os.fsencode(path), int(chunk_blocks)))
 
     def set_render_scope(self, scope, stage_capacity_blocks=0):
         """RENDER_RESIDENT (default): renders read the pool; RENDER_MAP: the pool and the host store -- any pose renders as on an

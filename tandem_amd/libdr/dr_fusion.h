@@ -92,6 +92,11 @@ public:
   // DRF_RENDER_MAP: RenderAsync at any pose reads resident and host-stored blocks together (capacity 0 = the default staging)
   void SetRenderScope(int scope, size_t capacity = 0) { check(drf_set_render_scope(impl, scope, capacity)); }
 
+  // Map files (dr_mi355x.h "map files", INTEGRATION.md "Map files"): the whole map, host store included, to a file and into a
+  // DrFusion whose map is empty.  Failures exit like every other member.
+  void SaveMapToFile(std::string const &filename) { check(drf_save_map(impl, filename.c_str(), 0)); }
+  void LoadMapFromFile(std::string const &filename) { check(drf_load_map(impl, filename.c_str(), 0)); }
+
   // Incremental mesh (dr_mi355x.h "incremental mesh", INTEGRATION.md "Incremental mesh"): GetMeshUpdateSync fills dr_mesh_num /
   // dr_mesh_vert / dr_mesh_cols with the triangles of the listed blocks only, and the members below name the blocks: block i has
   // coordinates dr_mesh_update_coords[3 i ..] and owns triangles [dr_mesh_update_first[i], dr_mesh_update_first[i + 1]).
