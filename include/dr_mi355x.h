@@ -313,6 +313,20 @@ int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks);
 /* last drf_render_async: [0] stored blocks staged (union over its poses), [1] bytes uploaded,
    [2] poses that selected the whole store (not rigid), [3] 1 if it waited for the scan to fold evictions */
 int drf_render_stats(drf_t *h, uint64_t out[4]);
+/* Depth bands for map-scope renders whose union exceeds the staging (DESIGN.md §7c "Rendering beyond the staging").
+ * max_passes 0 or 1: off (the default) -- every call behaves and launches as without this function.  2..64: such a
+ *   drf_render_async stages and ray-casts up to max_passes consecutive slabs of camera depth one after the other, each within
+ *   stage_capacity_blocks, the rays pausing at a slab's far side and resuming in the next pass.  The result equals the
+ *   one-pass render bit for bit in depth and colour, and the same nothing moves.  A union that fits runs in one pass as before.
+ *   DR_ERR_CAPACITY remains, with nothing changed, when the plan needs more than max_passes passes, when the thinnest possible
+ *   band (about 2 x 12.5 sqrt(3) voxels + truncation_distance of depth) holds more blocks than the capacity, or when a pose that
+ *   selects without the frustum cut (not a finite rigid motion; a reach beyond ~10^4 voxels) exceeds it on its own.
+ * negative or above 64: DR_ERR_ARG; between drf_render_async and drf_get_render_result: DR_ERR_PROTOCOL */
+int drf_set_render_bands(drf_t *h, int max_passes);
+/* last drf_render_async: [0] passes (1 for an unbanded staged render, 0 when nothing was staged), [1] blocks staged by its
+   largest pass, [2] blocks staged over all passes (a block staged by k passes counts k times; drf_render_stats [1] is
+   4104 x this), [3] 1 if the render was banded */
+int drf_render_band_stats(drf_t *h, uint64_t out[4]);
 /* Last extraction: [0] blocks meshed (resident + stored), [1] host blocks uploaded (a block staged by k chunks counts k
  * times), [2] chunks (1 for a resident pass over a non-empty pool). */
 int drf_mesh_stats(drf_t *h, uint64_t out[3]);

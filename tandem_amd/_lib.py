@@ -118,6 +118,8 @@ SIGNATURES = {
     "drf_export_host_blocks": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int32), u8p, C.POINTER(C.c_int)]),
     "drf_set_render_scope": (C.c_int, [vp, C.c_int, C.c_size_t]),
     "drf_render_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_set_render_bands": (C.c_int, [vp, C.c_int]),
+    "drf_render_band_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "drf_set_mesh_scope": (C.c_int, [vp, C.c_int]),
     "drf_mesh_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "drf_extract_mesh_update_async": (C.c_int, [vp, f32p, f32p]),

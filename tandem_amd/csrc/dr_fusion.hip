@@ -725,6 +725,7 @@ class FusionEngine {
     unsigned char *d_bgr, *h_bgr[2], *hd_bgr[2];   // hd_*: the pinned result buffers as the device addresses them
     float *d_depth, *h_depth[2], *hd_depth[2];
     int *d_flag;  // pixels the fast ray-caster handed to the literal pass
+    RayState *d_band = nullptr;  // per-pixel state of a depth-banded render (allocated by the first one)
     hipEvent_t done, cast;  // result on the host / ray-cast kernels finished (the volume may be written again)
   };
 
@@ -831,20 +832,23 @@ class FusionEngine {
     DR_HIP(hipEventRecord(int_done_, int_stream_));
   }
   // The product's ray-cast: the flag counter cleared, the two-round-trip sampler (SAMPLER 0: round 2's, parity build), the literal pass
-  // for the pixels it flagged.  The staging is a trailing pack as in the kernels: none = resident, one RenderStage = staged.
+  // for the pixels it flagged.  The staging is a trailing pack as in the kernels: none = resident, one RenderStage = staged, a
+  // RenderBand behind it = one depth band of a staged render (the flag counter is cleared before the first band only).
   template <int SAMPLER, class... SG>
-  void raycast_pass(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P, const SG &...stage) {
-    constexpr bool STAGED = sizeof...(SG) != 0;
+  void raycast_pass(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P, bool zero_flag, const SG &...stage) {
+    constexpr bool STAGED = sizeof...(SG) != 0, BANDED = sizeof...(SG) == 2;
     const dim3 grid(8 * cdiv(cdiv((int)npix_, 64), 8)), block(64);
-    hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, d_flag);
+    if (zero_flag) hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, st, d_flag);
     FusionDev dv = d_;
     if (raycast_no_skip_) dv.super[0] = nullptr;  // DR_RAYCAST_NO_SKIP=1: every sample is looked up (A/B and parity hook)
-    if (d_.fast_div) hipLaunchKernelGGL((k_raycast2<true, false, SAMPLER, STAGED>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, stage...);
-    else hipLaunchKernelGGL((k_raycast2<false, false, SAMPLER, STAGED>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, stage...);
-    hipLaunchKernelGGL(k_raycast_fix<STAGED>, dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag, stage...);
+    if (d_.fast_div) hipLaunchKernelGGL((k_raycast2<true, false, SAMPLER, STAGED, BANDED>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, stage...);
+    else hipLaunchKernelGGL((k_raycast2<false, false, SAMPLER, STAGED, BANDED>), grid, block, 0, st, dv, P, d_bgr, d_depth, d_flag, (unsigned long long *)nullptr, stage...);
+    hipLaunchKernelGGL((k_raycast_fix<STAGED, BANDED>), dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag, stage...);
   }
-  // sg: the host blocks staged for this render (map scope with stored blocks in reach), nullptr = the resident kernels
-  void launch_raycast(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P, const RenderStage *sg = nullptr) {
+  // sg: the host blocks staged for this render (map scope with stored blocks in reach), nullptr = the resident kernels;
+  // band: this launch is one depth band of the render (sg is then that band's staging)
+  void launch_raycast(hipStream_t st, unsigned char *d_bgr, float *d_depth, int *d_flag, const Mat &P, const RenderStage *sg = nullptr,
+                      const RenderBand *band = nullptr) {
 #ifdef DR_PARITY_HOOKS  // the superseded generations have no staged form (render_async refuses them)
     const dim3 grid(8 * cdiv(cdiv((int)npix_, 64), 8)), block(64);
     if (raycast_v1_) { hipLaunchKernelGGL(k_raycast, grid, block, 0, st, d_, P, d_bgr, d_depth); return; }
@@ -865,21 +869,31 @@ class FusionEngine {
       hipLaunchKernelGGL(k_raycast_fix<false>, dim3(512), dim3(64), 0, st, d_, P, d_bgr, d_depth, d_flag);
       return;
     }
-    if (raycast_sampler_ == 0) return raycast_pass<0>(st, d_bgr, d_depth, d_flag, P);  // DR_RAYCAST_SAMPLER=0: the four-stage sampler of round 2
+    if (raycast_sampler_ == 0) return raycast_pass<0>(st, d_bgr, d_depth, d_flag, P, true);  // DR_RAYCAST_SAMPLER=0: the four-stage sampler of round 2
 #endif
-    if (sg) raycast_pass<1>(st, d_bgr, d_depth, d_flag, P, *sg);
-    else raycast_pass<1>(st, d_bgr, d_depth, d_flag, P);
+    if (band) raycast_pass<1>(st, d_bgr, d_depth, d_flag, P, band->first != 0, *sg, *band);
+    else if (sg) raycast_pass<1>(st, d_bgr, d_depth, d_flag, P, true, *sg);
+    else raycast_pass<1>(st, d_bgr, d_depth, d_flag, P, true);
   }
   // One render on its stream, behind the scan: ray-cast (sg: the staged host blocks it also reads, behind their staging), `cast`,
   // hand-off to the host (k_publish; DR_RENDER_D2H=copy, parity build: the two hipMemcpyAsync of round 2), `done`.
   // timing: three events around the ray-cast and the hand-off (bench_sequence).
-  void submit_render(Render &r, const Mat &P, const RenderStage *sg, hipEvent_t *timing = nullptr) {
-    DR_HIP(hipStreamWaitEvent(r.stream, int_done_, 0));
+  // band: one depth band of the render -- z_hi and `first` given, the stream's state filled in here; the hand-off follows the
+  // last band only (`cast` is recorded behind every band: the staging stream waits for it before it takes the band's flags back).
+  void submit_render(Render &r, const Mat &P, const RenderStage *sg, hipEvent_t *timing = nullptr, const RenderBand *band = nullptr, bool last = true) {
+    if (!band || band->first) DR_HIP(hipStreamWaitEvent(r.stream, int_done_, 0));
     if (sg) rs_.wait_ready(r.stream);
     if (timing) DR_HIP(hipEventRecord(timing[0], r.stream));
-    launch_raycast(r.stream, r.d_bgr, r.d_depth, r.d_flag, P, sg);
+    if (band) {
+      if (!r.d_band) r.d_band = own_.device<RayState>(npix_);
+      RenderBand b = *band;
+      b.state = r.d_band;
+      launch_raycast(r.stream, r.d_bgr, r.d_depth, r.d_flag, P, sg, &b);
+    } else
+      launch_raycast(r.stream, r.d_bgr, r.d_depth, r.d_flag, P, sg);
     if (timing) DR_HIP(hipEventRecord(timing[1], r.stream));
     DR_HIP(hipEventRecord(r.cast, r.stream));
+    if (!last) return;
     if (render_copy_) {
       DR_HIP(hipMemcpyAsync(r.h_bgr[free_slot_], r.d_bgr, npix_ * 3, hipMemcpyDeviceToHost, r.stream));
       DR_HIP(hipMemcpyAsync(r.h_depth[free_slot_], r.d_depth, npix_ * 4, hipMemcpyDeviceToHost, r.stream));
@@ -897,12 +911,18 @@ class FusionEngine {
     DR_HIP(hipSetDevice(device_));
     // map scope: the stored blocks these poses can read, decided before anything changes (DR_ERR_CAPACITY leaves all as it was)
     RenderStagePlan plan;
+    RenderBandPlan bands;
     bool waited = false;
     if (render_scope_ == DRF_RENDER_MAP) {
       for (int i = 0; i < n; ++i) if (!poses[i]) fail(DR_ERR_ARG, "RenderAsync: null pose");
       plan = plan_render(poses, n, waited);
-      if (!render_stage_fits(plan, rs_capacity()))
-        fail(DR_ERR_CAPACITY, "RenderAsync: the poses can read %zu stored blocks, the render staging holds %zu (drf_set_render_scope)", plan.keys.size(), rs_capacity());
+      if (!render_stage_fits(plan, rs_capacity())) {
+        // depth bands (drf_set_render_bands): the union may exceed the staging as long as every band fits it
+        if (render_bands_ >= 2) bands = plan_render_bands(store_, o_, poses, n, rs_capacity(), render_bands_);
+        if (!bands.ok)
+          fail(DR_ERR_CAPACITY, "RenderAsync: the poses can read %zu stored blocks, the render staging holds %zu (drf_set_render_scope%s)", plan.keys.size(), rs_capacity(),
+               render_bands_ >= 2 ? "; no plan of depth bands within drf_set_render_bands either" : "");
+      }
 #ifdef DR_PARITY_HOOKS
       if (!plan.keys.empty() && (raycast_v1_ || raycast_stats_ || raycast_sampler_ == 0))
         fail(DR_ERR_UNSUPPORTED, "RenderAsync: the superseded ray-cast generations have no staged form (DRF_RENDER_MAP with stored blocks in reach)");
@@ -910,20 +930,47 @@ class FusionEngine {
     }
     next_ = kGetRender;
     free_slot_ ^= 1;  // write into the buffers NOT handed out by the last GetRenderResult
-    RenderStage sg{};
     const bool staged = !plan.keys.empty();  // nothing to stage: exactly the resident launches
-    if (staged) sg = stage_render(plan.keys);
-    for (int i = 0; i < n; ++i) {
-      Mat P; memcpy(P.m, poses[i], 64);
-      submit_render(renders_[i], P, staged ? &sg : nullptr);
+    // One pass stages the union; a banded render one depth band after the other.  The two slots of rs_ alternate, so band j + 1 is
+    // packed and copied while band j ray-casts; all render streams take a band together and share its staging.
+    const size_t passes = bands.ok ? bands.keys.size() : 1;
+    size_t largest = 0, total = 0;
+    for (size_t j = 0; j < passes; ++j) {
+      const std::vector<unsigned long long> &keys = bands.ok ? bands.keys[j] : plan.keys;
+      largest = std::max(largest, keys.size());
+      total += keys.size();
     }
-    if (staged) {  // behind every ray-cast that read the slot: its flags go back to zero
-      for (auto &r : renders_) rs_.wait_for(r.cast);
-      hipLaunchKernelGGL(k_rs_clear, dim3(cdiv(sg.n, 256)), dim3(256), 0, rs_.stream(), sg.keys, sg.n, rs_super_[rs_.slot()][0], rs_super_[rs_.slot()][1]);
-      DR_HIP(hipGetLastError());
+    if (bands.ok) ensure_render_staging(largest);  // (grown once, before the first band is in flight)
+    for (size_t j = 0; j < passes; ++j) {
+      RenderStage sg{};
+      if (staged) sg = stage_render(bands.ok ? bands.keys[j] : plan.keys);
+      RenderBand band{};
+      band.z_hi = bands.ok ? bands.z[j + 1] : 0.0f;
+      band.first = j == 0;
+      for (int i = 0; i < n; ++i) {
+        Mat P; memcpy(P.m, poses[i], 64);
+        submit_render(renders_[i], P, staged ? &sg : nullptr, nullptr, bands.ok ? &band : nullptr, j + 1 == passes);
+      }
+      if (staged) {  // behind every ray-cast that read the slot: its flags go back to zero
+        for (auto &r : renders_) rs_.wait_for(r.cast);
+        hipLaunchKernelGGL(k_rs_clear, dim3(cdiv(sg.n, 256)), dim3(256), 0, rs_.stream(), sg.keys, sg.n, rs_super_[rs_.slot()][0], rs_super_[rs_.slot()][1]);
+        DR_HIP(hipGetLastError());  // (per band: the launches of its ray-casts included)
+      }
     }
-    render_stats_[0] = plan.keys.size(); render_stats_[1] = plan.keys.size() * (size_t)(8 + 4096);
+    render_stats_[0] = plan.keys.size(); render_stats_[1] = total * (size_t)(8 + 4096);
     render_stats_[2] = (uint64_t)plan.whole; render_stats_[3] = waited ? 1 : 0;
+    band_stats_[0] = staged ? passes : 0; band_stats_[1] = largest; band_stats_[2] = total; band_stats_[3] = bands.ok ? 1 : 0;
+  }
+  // Depth bands of map-scope renders: max_passes 0 or 1 = off (the default), 2..64 = a RenderAsync whose union exceeds the
+  // staging may run in up to that many bands.
+  void set_render_bands(int max_passes) {
+    if (max_passes < 0 || max_passes > 64) fail(DR_ERR_ARG, "drf_set_render_bands: max_passes %d is not within 0..64", max_passes);
+    if (next_ == kGetRender) fail(DR_ERR_PROTOCOL, "drf_set_render_bands: a render is pending, call GetRenderResult first");
+    render_bands_ = max_passes;
+  }
+  void render_band_stats(uint64_t out[4]) const {
+    if (!out) fail(DR_ERR_ARG, "drf_render_band_stats: null argument");
+    for (int i = 0; i < 4; ++i) out[i] = band_stats_[i];
   }
   // DRF_RENDER_RESIDENT: renders read the pool (the default); DRF_RENDER_MAP: the pool and the host store together.
   // stage_capacity_blocks bounds the staging (0 = min(num_blocks, kStageBlocks)).
@@ -1959,6 +2006,8 @@ class FusionEngine {
   int render_scope_ = DRF_RENDER_RESIDENT;
   size_t rs_cap_req_ = 0, rs_blocks_ = 0;
   uint64_t render_stats_[4] = {0, 0, 0, 0};
+  int render_bands_ = 0;  // drf_set_render_bands
+  uint64_t band_stats_[4] = {0, 0, 0, 0};
   // streaming state (staging allocated with the first drf_set_streaming / region call)
   float st_radius_ = 0.0f;                  // 0 = off
   size_t st_host_cap_ = (size_t)-1;         // host store capacity in blocks
@@ -2106,6 +2155,8 @@ int drf_save_map(drf_t *h, const char *path, size_t chunk_blocks) { return guard
 int drf_load_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->load_map(path, chunk_blocks); }); }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }
 int drf_render_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->render_stats(out); }); }
+int drf_set_render_bands(drf_t *h, int max_passes) { return guarded([&] { eng(h)->set_render_bands(max_passes); }); }
+int drf_render_band_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->render_band_stats(out); }); }
 int drf_set_mesh_scope(drf_t *h, int scope) { return guarded([&] { eng(h)->set_mesh_scope(scope); }); }
 int drf_mesh_stats(drf_t *h, uint64_t out[3]) { return guarded([&] { eng(h)->mesh_stats(out); }); }
 int drf_extract_mesh_update_async(drf_t *h, const float *lower, const float *upper) {

@@ -242,10 +242,14 @@ inline bool pose_is_rigid(const float *pose16) {
 // centre, cut by the six half-spaces that hold the pyramid of sample points {z (lx, ly, 1)}, z in [0, D], each widened by
 // render_margin.  A superset by construction.  Returns false -- and appends the whole store -- for a pose that is not a
 // finite rigid motion, or options the bound is not defined for.
-inline bool select_render_blocks(const HostBlockStore &store, const drf_options_t &o, const float *pose16, std::vector<unsigned long long> &out) {
+// bz, if given, receives per appended block its camera-frame depth b_z (the third coordinate of R^T (centre - t)), or NaN where the
+// cut was not applied: what plan_render_bands slices the selection by.
+inline bool select_render_blocks(const HostBlockStore &store, const drf_options_t &o, const float *pose16, std::vector<unsigned long long> &out,
+                                 std::vector<double> *bz = nullptr) {
   const double reach = stream_options_ok(o) ? render_reach(o) : HUGE_VAL;
   if (!pose_is_rigid(pose16) || !std::isfinite(reach)) {
     store.for_each([&](unsigned long long k, const uint8_t *) { out.push_back(k); });
+    if (bz) bz->resize(bz->size() + store.size(), (double)NAN);
     return false;
   }
   double p[3];
@@ -257,6 +261,7 @@ inline bool select_render_blocks(const HostBlockStore &store, const drf_options_
   // stand as derived; where it does not (depth above ~10^4 voxels) the sphere grows by the error and the cut is not applied.
   if (4e-3 * reach > 8.0 * std::sqrt(3.0) * vs + vs) {
     store.query_sphere(p, reach * (1.0 + 4e-3), o.voxel_size, out);
+    if (bz) bz->resize(bz->size() + (out.size() - first), (double)NAN);
     return true;
   }
   store.query_sphere(p, reach, o.voxel_size, out);
@@ -275,7 +280,10 @@ inline bool select_render_blocks(const HostBlockStore &store, const drf_options_
       const double len = std::sqrt(n[k][0] * n[k][0] + n[k][1] * n[k][1] + n[k][2] * n[k][2]);
       in = (n[k][0] * b[0] + n[k][1] * b[1] + n[k][2] * b[2]) / len >= -m;
     }
-    if (in) out[keep++] = out[i];
+    if (in) {
+      out[keep++] = out[i];
+      if (bz) bz->push_back(b[2]);
+    }
   }
   out.resize(keep);
   return true;
@@ -296,6 +304,69 @@ inline RenderStagePlan plan_render_stage(const HostBlockStore &store, const drf_
 }
 // the capacity decision of a RenderAsync: the union is what is staged, however many poses share a block
 inline bool render_stage_fits(const RenderStagePlan &p, size_t capacity_blocks) { return p.keys.size() <= capacity_blocks; }
+// ---- depth bands (drf_set_render_bands; DESIGN.md §7c "Rendering beyond the staging"): a union that exceeds the staging is
+// ray-cast in passes over consecutive slabs of camera-frame depth [z_j, z_j+1), common to all poses of the call.  A loop sample
+// of pass j lies at depth cur in [z_j, z_j+1), its final colour sample in [cur - trunc, cur + vs), and a sample at depth z reads
+// only blocks with |b_z - z| <= render_margin.  So of a pose's selection pass j needs the blocks with
+//   b_z + trunc + margin >= z_j   and   b_z - margin - vs < z_j+1
+// (a superset by construction; a block whose pose did not take the cut belongs to every pass).
+struct RenderBandPlan {
+  bool ok = false;                                     // false: no plan within capacity and max_passes
+  std::vector<float> z;                                // P + 1 boundaries, 0 = z[0] < ... < z[P] = max_sensor_depth (fp32: the kernels compare cur against them)
+  std::vector<std::vector<unsigned long long>> keys;   // per pass: ascending, de-duplicated
+};
+// Greedy sweep: each pass reaches as far as the union over the poses stays within `capacity`.  A further block enters at
+// z = b_z - margin - vs, so a pass ends at the entry depth of the first block that does not fit (rounded down to fp32: still
+// short of that block).  A pass that cannot advance past its start, or a plan of more than max_passes passes, fails.  A pass
+// takes every block up to its capacity, so none stages nothing unless nothing is staged at all (one empty pass).
+inline RenderBandPlan plan_render_bands(const HostBlockStore &store, const drf_options_t &o, const float *const *poses16, int n, size_t capacity,
+                                        int max_passes) {
+  struct Item { double enter, leave; unsigned long long key; };
+  std::vector<Item> items;
+  {
+    std::vector<unsigned long long> k;
+    std::vector<double> bz;
+    const double m = render_margin(o), vs = o.voxel_size, tr = o.truncation_distance;
+    for (int i = 0; i < n && !store.empty(); ++i) {
+      k.clear(); bz.clear();
+      select_render_blocks(store, o, poses16[i], k, &bz);
+      for (size_t j = 0; j < k.size(); ++j)
+        items.push_back(std::isnan(bz[j]) ? Item{-HUGE_VAL, HUGE_VAL, k[j]} : Item{bz[j] - m - vs, bz[j] + tr + m, k[j]});
+    }
+  }
+  std::sort(items.begin(), items.end(), [](const Item &a, const Item &b) { return a.enter != b.enter ? a.enter < b.enter : a.key < b.key; });
+  RenderBandPlan p;
+  const float D = o.max_sensor_depth;
+  if (!(D > 0.0f) || !std::isfinite(D)) return p;
+  float zs = 0.0f;
+  p.z.push_back(zs);
+  for (;;) {
+    if ((int)p.keys.size() >= max_passes) return RenderBandPlan();
+    float ze = D;
+    std::unordered_set<unsigned long long> in;
+    for (const Item &it : items) {
+      if (it.leave < (double)zs || in.count(it.key)) continue;
+      if (in.size() < capacity) { in.insert(it.key); continue; }
+      // the first block that does not fit: the pass ends where it enters
+      if (!(it.enter > (double)zs)) return RenderBandPlan();
+      ze = (float)it.enter;
+      if ((double)ze > it.enter) ze = std::nextafterf(ze, -INFINITY);
+      if (!(ze > zs)) return RenderBandPlan();
+      break;
+    }
+    std::vector<unsigned long long> keys;
+    for (const Item &it : items)
+      if (it.leave >= (double)zs && it.enter < (double)ze) keys.push_back(it.key);
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    p.keys.push_back(std::move(keys));
+    p.z.push_back(ze);
+    if (ze >= D) break;
+    zs = ze;
+  }
+  p.ok = true;
+  return p;
+}
 // Blocks the last scan's eviction chain gathered (not in the store until folded) lie beyond radius + 8 vs of that scan's
 // camera centre p.  A render from q with |q - p| + render_reach <= radius + 8 vs cannot read one: it need not wait for the scan.
 inline bool render_needs_fold(const drf_options_t &o, const float *pose16, const double scan_centre[3], double radius) {

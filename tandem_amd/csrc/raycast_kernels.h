@@ -43,6 +43,32 @@ template <int L> __device__ inline bool stage_super_empty(const RenderStage &s, 
 __device__ inline NoStage stage_arg() { return {}; }
 __device__ inline const RenderStage &stage_arg(const RenderStage &s) { return s; }
 
+// ---- depth bands (BANDED = true; drf_set_render_bands, DESIGN.md §7c "Rendering beyond the staging"): a map-scope render whose
+// staged blocks exceed the staging runs in passes over consecutive slabs of camera depth, each with its own staging.  A ray
+// pauses at the end of a slab and resumes in the next pass from the `cur` it stored, so `cur` takes the additions of the
+// one-pass loop in the same order.  Per pixel and render stream: `cur` and where the ray stands.
+enum : unsigned {
+  kRayPending = 0,       // in the fast loop; cur = the next sample
+  kRayFinal = 1,         // depth and colour are written
+  kRayLiteral = 2,       // handed to k_raycast_fix (bail); cur = the sample that bailed, not consumed yet
+  kRayLiteralColour = 3  // the loop hit, the colour sample at cur bailed: k_raycast_fix takes that sample alone
+};
+struct RayState { float cur; unsigned status; };  // one 8-byte load and store per pixel and pass, outside the ray loop
+struct RenderBand {  // passed by value behind the RenderStage
+  RayState *state;   // [height * width] of this render stream
+  float z_hi;        // this pass samples cur < min(max_sensor_depth, z_hi)
+  int first;         // 1: the first pass -- every ray starts at cur = 0, nothing is read from state
+};
+struct NoBand {};
+template <bool BANDED> using BandArg = std::conditional_t<BANDED, RenderBand, NoBand>;
+__device__ inline const RenderStage &stage_arg(const RenderStage &s, const RenderBand &) { return s; }
+__device__ inline NoBand band_arg() { return {}; }
+__device__ inline NoBand band_arg(const RenderStage &) { return {}; }
+__device__ inline const RenderBand &band_arg(const RenderStage &, const RenderBand &b) { return b; }
+// where the ray loop of a pass ends
+__device__ inline float band_limit(float max_depth, const NoBand &) { return max_depth; }
+__device__ inline float band_limit(float max_depth, const RenderBand &b) { return fminf(max_depth, b.z_hi); }
+
 __device__ inline unsigned stage_hash(unsigned cell) {
   unsigned h = cell * 0x9E3779B1u;
   return h ^ (h >> 15);
@@ -471,15 +497,23 @@ __device__ inline int skip_steps(unsigned cell, F3 q, F3 dirw, F3 inv_dir, float
 // literal pass like a table block does.  The product's sampler only.
 // The staging is a trailing parameter PACK -- one RenderStage when STAGED, nothing otherwise -- so that the resident instances keep
 // their kernel arguments, and with them their instructions, exactly.
-template <bool FAST, bool STATS = false, int SAMPLER = 1, bool STAGED = false, class... SG>
+// BANDED: one depth band of a staged render (above) -- a RenderBand follows the RenderStage in the pack.  The loop and the
+// empty-space skip stop at the band's far side: the staged superblock flags describe this pass's blocks only, so a skip is
+// proven only below z_hi (stopping early and resuming by sampling gives the same `cur` sequence).  A ray that hits takes its
+// colour sample in the same pass and is final; a ray that neither hit nor left the depth range stores `cur` and stays pending;
+// a ray that bails becomes literal at the sample that bailed and is k_raycast_fix's from then on.
+template <bool FAST, bool STATS = false, int SAMPLER = 1, bool STAGED = false, bool BANDED = false, class... SG>
 __global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat pose, unsigned char *__restrict__ bgr,
                                                  float *__restrict__ depth_out, int *__restrict__ n_flagged, unsigned long long *st,
                                                  const SG... stage) {
   static_assert(!STAGED || (SAMPLER == 1 && !STATS), "the staged ray-cast exists for the product's sampler");
-  static_assert(sizeof...(SG) == (STAGED ? 1 : 0), "one RenderStage for the staged form, none otherwise");
+  static_assert(!BANDED || STAGED, "bands exist for the staged form");
+  static_assert(sizeof...(SG) == (STAGED ? 1 : 0) + (BANDED ? 1 : 0), "one RenderStage for the staged form, a RenderBand behind it for the banded one");
   const StageArg<STAGED> &sg = stage_arg(stage...);
+  const BandArg<BANDED> &band = band_arg(stage...);
   const drf_options_t &o = d.o;
   const int size = o.height * o.width;
+  const float z_end = band_limit(o.max_sensor_depth, band);
   const bool far_blocks = d.n_alloc[3] != 0 || stage_far(sg);
   // one wave = one 8x8 pixel tile, tiles dealt to the 8 XCDs in bands of rows (see k_raycast)
   const bool tiled = (o.width % 8 == 0) && (o.height % 8 == 0) && blockDim.x == 64;
@@ -525,8 +559,16 @@ __global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat po
     }
     const float inv_trunc = 1.0f / o.truncation_distance, vs = o.voxel_size;
     float cur = 0.f;
+    bool hit = false;  // (BANDED: the loop ended at a surface, not at the band's far side)
+    if constexpr (BANDED) {
+      if (!band.first) {
+        const RayState s = band.state[i];
+        if (s.status != kRayPending) continue;  // final, or the literal pass's
+        cur = s.cur;
+      }
+    }
     unsigned n_it = 0, n_miss = 0, n_skip = 0, n_skipped = 0, n_full = 0;
-    while (cur < o.max_sensor_depth) {
+    while (cur < z_end) {
       const F3 q = sample_pos(cur);
       int cell = -1;
       const Voxel v = SAMPLER == 1 ? interp_voxel2<FAST, false, STAGED>(d, q, far_blocks, bail, (STAGED || d.super[0]) ? &cell : nullptr, sg)
@@ -541,10 +583,10 @@ __global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat po
           if (d.super[0][super_index<kSuperShift[0]>((unsigned)cell)] == 0 && stage_super_empty<0>(sg, (unsigned)cell)) k = skip_steps<kSuperShift[0]>((unsigned)cell, q, dirw, inv_dir, vs, inv_trunc);
           else if (d.super[1][super_index<kSuperShift[1]>((unsigned)cell)] == 0 && stage_super_empty<1>(sg, (unsigned)cell)) k = skip_steps<kSuperShift[1]>((unsigned)cell, q, dirw, inv_dir, vs, inv_trunc);
           if (STATS && k > 0) { ++n_skip; n_skipped += k; }
-          for (; k > 0 && cur < o.max_sensor_depth; --k) cur += o.truncation_distance;
+          for (; k > 0 && cur < z_end; --k) cur += o.truncation_distance;
         }
       } else cur += v.sdf;
-      if (v.weight != 0 && v.sdf < o.voxel_size) break;
+      if (v.weight != 0 && v.sdf < o.voxel_size) { hit = true; break; }
     }
     if (STATS) {
       unsigned mx = n_it, sum = n_it, sm = n_miss, ss = n_skip, sk = n_skipped, sf = n_full;
@@ -557,6 +599,31 @@ __global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat po
         atomicAdd(&st[3], (unsigned long long)sm); atomicAdd(&st[4], (unsigned long long)ss); atomicAdd(&st[5], (unsigned long long)sk);
         atomicAdd(&st[6], (unsigned long long)sf); atomicAdd(&st[7], 1ull); atomicAdd(&st[8 + min(mx / 16u, 23u)], 1ull);
       }
+    }
+    if constexpr (BANDED) {
+      RayState s;
+      s.cur = cur;
+      s.status = kRayLiteral;
+      if (!bail) {
+        s.status = kRayPending;
+        if (hit && cur < o.max_sensor_depth) {
+          const F3 qf = sample_pos(cur);
+          const Voxel v = interp_voxel2<FAST, true, STAGED>(d, qf, far_blocks, bail, nullptr, sg);
+          if (bail) s.status = kRayLiteralColour;
+          else {
+            bgr[3 * i] = v.c[0]; bgr[3 * i + 1] = v.c[1]; bgr[3 * i + 2] = v.c[2];
+            depth_out[i] = cur;
+            s.status = kRayFinal;
+          }
+        } else if (hit || !(cur < o.max_sensor_depth)) {
+          bgr[3 * i] = bgr[3 * i + 1] = bgr[3 * i + 2] = 0;
+          depth_out[i] = 0.0f;
+          s.status = kRayFinal;
+        }
+      }
+      band.state[i] = s;
+      if (bail) atomicAdd(n_flagged, 1);
+      continue;
     }
     if (!bail && cur < o.max_sensor_depth) {
       const F3 qf = sample_pos(cur);
@@ -571,21 +638,45 @@ __global__ __launch_bounds__(64) void k_raycast2(const FusionDev d, const Mat po
   }
 }
 // The literal ray-caster for the pixels k_raycast2 flagged; exits at once when there are none.
-template <bool STAGED = false, class... SG>
+// BANDED: the literal rays of this and of earlier passes (n_flagged counts them over the whole render) go on from their stored
+// `cur` to the band's far side; the fast sampler and this one agree bit for bit on every sample that does not bail.
+template <bool STAGED = false, bool BANDED = false, class... SG>
 __global__ __launch_bounds__(64) void k_raycast_fix(const FusionDev d, const Mat pose, unsigned char *__restrict__ bgr,
                                                     float *__restrict__ depth_out, int *__restrict__ n_flagged, const SG... stage) {
-  static_assert(sizeof...(SG) == (STAGED ? 1 : 0), "one RenderStage for the staged form, none otherwise");
+  static_assert(!BANDED || STAGED, "bands exist for the staged form");
+  static_assert(sizeof...(SG) == (STAGED ? 1 : 0) + (BANDED ? 1 : 0), "one RenderStage for the staged form, a RenderBand behind it for the banded one");
   const StageArg<STAGED> &sg = stage_arg(stage...);
+  const BandArg<BANDED> &band = band_arg(stage...);
   if (*n_flagged == 0) return;
   const drf_options_t &o = d.o;
   const int size = o.height * o.width;
+  const float z_end = band_limit(o.max_sensor_depth, band);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < size; i += gridDim.x * blockDim.x) {
-    if (!(depth_out[i] == -1.0f)) continue;
     float cur = 0.f;
-    while (cur < o.max_sensor_depth) {
+    bool hit = false;
+    if constexpr (BANDED) {
+      const RayState s = band.state[i];  // (written by this pass's k_raycast2 or an earlier pass: never stale)
+      if (s.status != kRayLiteral && s.status != kRayLiteralColour) continue;
+      cur = s.cur;
+      hit = s.status == kRayLiteralColour;
+    } else {
+      if (!(depth_out[i] == -1.0f)) continue;
+    }
+    while (!hit && cur < z_end) {
       const Voxel v = get_interpolated_voxel<STAGED>(d, xform(pose, point3d(o, i, cur)), sg);
       if (v.weight == 0) cur += o.truncation_distance; else cur += v.sdf;
-      if (v.weight != 0 && v.sdf < o.voxel_size) break;
+      if (v.weight != 0 && v.sdf < o.voxel_size) { hit = true; break; }
+    }
+    if constexpr (BANDED) {
+      if (!hit && cur < o.max_sensor_depth) {  // the band's far side: literal in the next pass as well
+        RayState s;
+        s.cur = cur; s.status = kRayLiteral;
+        band.state[i] = s;
+        continue;
+      }
+      RayState s;
+      s.cur = cur; s.status = kRayFinal;
+      band.state[i] = s;
     }
     if (cur < o.max_sensor_depth) {
       const Voxel v = get_interpolated_voxel<STAGED>(d, xform(pose, point3d(o, i, cur)), sg);

@@ -276,6 +276,18 @@ class DrFusion:
         check(self._L.drf_render_stats(self._h, out))
         return tuple(int(v) for v in out)
 
+    def set_render_bands(self, max_passes):
+        """0 or 1 (default): off.  2..64: a RENDER_MAP RenderAsync whose stored blocks exceed the staging runs in up to max_passes
+        depth bands, staged and ray-cast one after the other -- the same images bit for bit; DR_ERR_CAPACITY only if no such
+        plan exists."""
+        check(self._L.drf_set_render_bands(self._h, int(max_passes)))
+
+    def render_band_stats(self):
+        """Last RenderAsync: (passes, blocks staged by the largest pass, blocks staged over all passes, 1 if it was banded)."""
+        out = (C.c_uint64 * 4)()
+        check(self._L.drf_render_band_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
     def set_mesh_scope(self, scope):
         """MESH_RESIDENT (default): meshes cover the pool; MESH_MAP: the pool and the host store, without moving a block."""
         check(self._L.drf_set_mesh_scope(self._h, int(scope)))

@@ -91,6 +91,8 @@ public:
   void SetMeshScope(int scope) { check(drf_set_mesh_scope(impl, scope)); }
   // DRF_RENDER_MAP: RenderAsync at any pose reads resident and host-stored blocks together (capacity 0 = the default staging)
   void SetRenderScope(int scope, size_t capacity = 0) { check(drf_set_render_scope(impl, scope, capacity)); }
+  // 2..64: a DRF_RENDER_MAP render that exceeds the staging runs in up to max_passes depth bands (0: off, the default)
+  void SetRenderBands(int max_passes) { check(drf_set_render_bands(impl, max_passes)); }
 
   // Map files (dr_mi355x.h "map files", INTEGRATION.md "Map files"): the whole map, host store included, to a file and into a
   // DrFusion whose map is empty.  Failures exit like every other member.

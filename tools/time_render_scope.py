@@ -14,6 +14,11 @@ Reported (profiles/render_scope_time.json), per pose and as medians over the pos
   kernels_us       (--merge-kernel-stats) device time per launch of the staged and the resident ray-cast kernels and of
                    k_rs_build / k_rs_clear, from a `rocprofv3 --kernel-trace --stats` summary of this script
 
+Depth bands (drf_set_render_bands; --bands-out profiles/render_bands_time.json): the far pose --bands-pose rendered one pass
+with --capacity, banded with the capacity cut to a half, a third and a tenth of the stored blocks that pass staged and to the
+smallest capacity the planner accepts (found by bisection: a refused RenderAsync changes nothing), and on the unbounded engine:
+medians, passes, largest pass, blocks and bytes staged per leg (a leg the planner refuses is recorded as such).
+
 Run:  rocprofv3 --kernel-trace --stats -d DIR -o rs -- python tools/time_render_scope.py --out profiles/render_scope_time.json
       python tools/rocprof_summary.py DIR/.../rs_results.db > profiles/render_scope_kernel_stats.txt
       python tools/time_render_scope.py --merge-kernel-stats profiles/render_scope_kernel_stats.txt --out profiles/render_scope_time.json"""
@@ -67,12 +72,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--poses", default="300,400,500,600,700", help="frames of the loop whose poses are rendered at the end")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bands-out", default=None, help="run the depth-band legs and write them here")
+    ap.add_argument("--bands-pose", type=int, default=300, help="frame of the loop whose pose the depth-band legs render")
     ap.add_argument("--merge-kernel-stats", default=None, help="add the ray-cast kernels of this rocprof summary to --out and exit")
     args = ap.parse_args()
     if args.merge_kernel_stats:
         return merge_kernel_stats(args.merge_kernel_stats, args.out, add_kernel_stats, indent=1)
     import torch
     assert torch.cuda.is_available(), "tools/time_render_scope.py needs a GPU"
+    from tandem_amd._lib import DrError
     from tandem_amd.dr_fusion import DrFusion, RENDER_MAP, RENDER_RESIDENT, streaming_min_radius
     poses, frames = room_loop(args.frames, args.height, args.width)
     bgr, depth = frames["bgr"], frames["depth"]
@@ -123,6 +131,47 @@ def main():
                scan_pose=dict(map_ms=scan_ms, map_call_ms=scan_call, unbounded_ms=unb_scan_ms, render_stats=list(scan_stats)),
                streaming_stats_after={k: v for k, v in f.streaming_stats().items() if k != "last_scan_us"} ==
                {k: v for k, v in st.items() if k != "last_scan_us"})
+    if args.bands_out:
+        pose = poses[args.bands_pose]
+        unb_ms, _, unb_img = time_render(u, pose, args.reps, args.warmup)
+        legs, n = [], None
+        def accepted(cap):
+            f.set_render_scope(RENDER_MAP, cap)
+            try:
+                f.RenderAsync([pose])
+            except DrError:
+                return False
+            f.GetRenderResult(copy=False)
+            f.IntegrateScanAsync(time_render.blank[0], time_render.blank[1], time_render.scan_pose)
+            f.Synchronize()
+            return True
+        for name, div in (("one_pass", 0), ("half", 2), ("third", 3), ("tenth", 10), ("smallest", -1)):
+            if div < 0:
+                f.set_render_bands(64)
+                lo, hi = 0, n  # lo is refused, hi accepted
+                while hi - lo > 1:
+                    mid = (lo + hi) // 2
+                    lo, hi = (lo, mid) if accepted(mid) else (mid, hi)
+                cap = hi
+            else:
+                cap = args.capacity if not div else -(-n // div)
+            f.set_render_scope(RENDER_MAP, cap)
+            f.set_render_bands(64 if div else 0)
+            try:
+                ms, call, img = time_render(f, pose, args.reps, args.warmup)
+            except DrError as e:  # no plan of bands within this capacity: recorded, not timed
+                legs.append(dict(leg=name, capacity=cap, refused=e.code))
+                continue
+            rs, bs = f.render_stats(), f.render_band_stats()
+            n = rs[0] if n is None else n
+            legs.append(dict(leg=name, capacity=cap, ms=ms, call_ms=call, ratio_to_unbounded=ms / unb_ms, union_blocks=rs[0], bytes=rs[1],
+                             passes=bs[0], largest_pass_blocks=bs[1], staged_blocks=bs[2], banded=bs[3],
+                             equal=bool(np.array_equal(img[1].view(np.uint32), unb_img[1].view(np.uint32)) and np.array_equal(img[0], unb_img[0]))))
+            print(json.dumps(legs[-1]), flush=True)
+        f.set_render_bands(0)
+        with open(args.bands_out, "w") as fh:
+            json.dump(dict(frames=args.frames, height=args.height, width=args.width, voxel_size=0.01, max_sensor_depth=args.depth, pose=args.bands_pose,
+                           reps=args.reps, warmup=args.warmup, unbounded_ms=unb_ms, legs=legs), fh, indent=1)
     f.close()
     u.close()
     print(json.dumps({k: v for k, v in out.items() if k != "poses"}), flush=True)
