@@ -1,26 +1,21 @@
 // dr_mvsnet.hip -- MI355X engine behind the DrMvsnet operator API (C ABI: include/dr_mi355x.h).
 //
 // Replaces tandem/libdr/dr_mvsnet/src/dr_mvsnet.cpp (libtorch TorchScript interpreter + cuDNN)
-// with a fixed launch plan of hand-written gfx950 kernels (conv_mfma.h, mvs_kernels.h):
+// with a fixed launch plan of hand-written gfx950 kernels (conv_mfma.h, mvs_kernels.h; launchers: mvs_launch.h; host logic: mvs_host.h):
 //   CallAsync   dr_mvsnet.cpp:125-283  -> MvsEngine::stage_inputs + worker thread
 //   forward     dr_mvsnet.cpp:285-331  -> MvsEngine::forward (cva_mvsnet.py:98-184 as ~75 launches)
 //   GetResult   dr_mvsnet.cpp:95-107   -> drm_get_result
 // The threading contract is the reference's: one worker thread, one mutex, two condition variables;
 // CallAsync blocks only while the previous input is still unprocessed.
-#include <cmath>
 #include <atomic>
-#include <condition_variable>
-#include <functional>
-#include <map>
 #include <memory>
-#include <mutex>
-#include <thread>
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and prototypes only: the library is bound with dlopen when a communicator is asked for
 
 #include "conv_mfma.h"
-#include "mvs_kernels.h"
+#include "mvs_host.h"
+#include "mvs_launch.h"
 #ifdef DR_PARITY_HOOKS  // conv11 + prob in one launch: built twice in round 5, correct, slower than the two-kernel path (profiles/r05_tail.txt): parity build only
 #include "tail_kernels.h"
 #endif
@@ -32,77 +27,6 @@ namespace dr {
 std::string &last_error_slot() {
   thread_local std::string s;
   return s;
-}
-
-// ------------------------------------------------------------------ TDMW blob (tandem_amd/weights.py)
-struct HostTensor {
-  std::vector<int> dims;
-  std::vector<float> data;
-};
-struct Blob {
-  int depth_num[3];
-  float ratio[3];
-  int view_aggregation, base;
-  std::map<std::string, HostTensor> t;
-  const HostTensor &at(const std::string &k) const {
-    auto it = t.find(k);
-    if (it == t.end()) fail(DR_ERR_IO, "weight blob: missing tensor %s", k.c_str());
-    return it->second;
-  }
-};
-
-static Blob load_blob(const char *path) {
-  FILE *f = fopen(path, "rb");
-  if (!f) fail(DR_ERR_IO, "cannot open weight blob %s", path);
-  Blob b;
-  char magic[8];
-  auto rd = [&](void *p, size_t n) {
-    if (fread(p, 1, n, f) != n) { fclose(f); fail(DR_ERR_IO, "weight blob %s truncated", path); }
-  };
-  rd(magic, 8);
-  if (memcmp(magic, "TDMW0001", 8)) { fclose(f); fail(DR_ERR_IO, "%s is not a TDMW blob", path); }
-  rd(b.depth_num, 12); rd(b.ratio, 12); rd(&b.view_aggregation, 4); rd(&b.base, 4);
-  uint32_t n;
-  rd(&n, 4);
-  for (uint32_t i = 0; i < n; ++i) {
-    uint32_t ln, nd;
-    rd(&ln, 4);
-    std::string name(ln, '\0');
-    rd(&name[0], ln);
-    rd(&nd, 4);
-    HostTensor t;
-    size_t cnt = 1;
-    for (uint32_t k = 0; k < nd; ++k) { uint32_t d; rd(&d, 4); t.dims.push_back((int)d); cnt *= d; }
-    t.data.resize(cnt);
-    rd(t.data.data(), cnt * 4);
-    b.t[name] = std::move(t);
-  }
-  fclose(f);
-  if (b.base != 8) fail(DR_ERR_UNSUPPORTED, "only feature_net_base_channels=8 is supported (got %d)", b.base);
-  return b;
-}
-
-// ------------------------------------------------------------------ small host math (double)
-static void inv4(const double *m, double *o) {  // Gauss-Jordan with partial pivoting
-  double a[4][8];
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { a[i][j] = m[4 * i + j]; a[i][4 + j] = i == j; }
-  for (int c = 0; c < 4; ++c) {
-    int piv = c;
-    for (int r = c + 1; r < 4; ++r) if (std::fabs(a[r][c]) > std::fabs(a[piv][c])) piv = r;
-    if (piv != c) for (int j = 0; j < 8; ++j) std::swap(a[c][j], a[piv][j]);
-    const double d = a[c][c];
-    for (int j = 0; j < 8; ++j) a[c][j] /= d;
-    for (int r = 0; r < 4; ++r) if (r != c) { const double f = a[r][c]; for (int j = 0; j < 8; ++j) a[r][j] -= f * a[c][j]; }
-  }
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) o[4 * i + j] = a[i][4 + j];
-}
-static void mul4(const double *a, const double *b, double *o) {
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) { double s = 0; for (int k = 0; k < 4; ++k) s += a[4 * i + k] * b[4 * k + j]; o[4 * i + j] = s; }
-}
-// world->pixel 4x4 = [K * W2C(3x4); 0 0 0 1]   (module.py:798-804)
-static void world_to_pixel(const float *K9, const double *w2c, double *o) {
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 4; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += (double)K9[3 * i + k] * w2c[4 * k + j]; o[4 * i + j] = s; }
-  o[12] = w2c[12]; o[13] = w2c[13]; o[14] = w2c[14]; o[15] = w2c[15];
 }
 
 // ------------------------------------------------------------------ engine
@@ -127,6 +51,7 @@ struct Op {
 #endif
   FrontArgs front{};                      // FRONT only: preprocess + conv0.0 + conv0.1 in one launch (fn_front.h)
   Head3Args head3{};                      // HEAD3 only: FeatureNet's folded stage-3 head in one launch (fn_head3.h)
+  PreprocessArgs pre{};                   // PREPROCESS only
   std::function<ConvLaunch(int)> replan;  // CONV only: build candidate `rank` of the planner's ranking
   std::string sig;                        // CONV only: layer signature in conv_tuned.h's column order
   int ncand = 0;
@@ -176,120 +101,6 @@ struct Rccl {
   void check(ncclResult_t e, const char *what) const {
     if (e != ncclSuccess) fail(DR_ERR_DEVICE, "RCCL %s: %s", what, GetErrorString(e));
   }
-};
-
-// The four result maps of a window go to the pinned host block in ONE kernel (16-byte stores over PCIe) instead of four
-// copy-engine transfers: 4 x (launch + completion latency) is most of the time those take for 1.2 MB each.
-__global__ __launch_bounds__(256) void k_publish4(const float4 *__restrict__ a, const float4 *__restrict__ b, const float4 *__restrict__ c,
-                                                  const float4 *__restrict__ d, float4 *__restrict__ host, size_t n4) {
-  const size_t nt = (size_t)gridDim.x * blockDim.x;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < 4 * n4; i += nt) {
-    const size_t k = i / n4, j = i - k * n4;
-    host[i] = (k == 0 ? a : (k == 1 ? b : (k == 2 ? c : d)))[j];
-  }
-}
-
-// Every DR_* switch of the engine, read ONCE when the engine is created (nothing on the launch path calls getenv).  The product library reads
-// six of them (profiling, printing, tuning knobs: listed in INTEGRATION.md); every switch that selects a superseded kernel generation, the losing side of a
-// settled A/B or a forced fallback is read through hook_env(), i.e. only in the parity build (-DDR_PARITY_HOOKS, libdr_mi355x_hooks.so: what the tests
-// that compare generations load) -- in the product those members are constants.
-struct MvsSwitches {
-  static int num(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
-  static bool on(const char *name) { return getenv(name) != nullptr; }
-  static int hnum(const char *name, int dflt) { const char *e = hook_env(name); return e ? atoi(e) : dflt; }  // parity build only (dr_common.h): the product returns dflt
-  static bool hon(const char *name) { return hook_env(name) != nullptr; }
-  // ---- read by the product library ("Environment switches"): profiling, printing, tuning knobs
-  bool side_stream = !on("DR_MVS_NO_SIDE_STREAM");       // FeatureNet's stage-2/3 heads on a second stream (off: strictly sequential kernels, for profiles)
-  int conv_print = num("DR_CONV_PRINT", 0);              // autotune / debug printing
-  std::string autotune_only = getenv("DR_AUTOTUNE_ONLY") ? getenv("DR_AUTOTUNE_ONLY") : "";  // tuning: restrict autotune to layers whose name contains this
-  int cv_dchunk[3] = {num("DR_CV_DCHUNK1", 0), num("DR_CV_DCHUNK2", 0), num("DR_CV_DCHUNK3", 0)};  // tuning: depth planes per cost-volume workgroup (0: default)
-  int prob_zchunk = num("DR_PROB_ZCHUNK", 0);            // tuning: z-march chunk of k_prob2 (0: default)
-  int hist_blocks = std::max(1, num("DR_HIST_BLOCKS", 128));  // tuning: workgroups of a histogram level (each flushes its bins with atomics on a few hot addresses)
-  // ---- parity build only: the other side of every settled A/B, superseded generations, forced fallbacks (constants in the product)
-  int prob_rows = hnum("DR_PROB_ROWS", 0);               // logits per lane of k_prob2 (2 or 4: measured slower; default 1)
-  bool costvol_v2 = hon("DR_COSTVOL_V2");                // k_costvol2 (the product's fallback for depth chunks that are not multiples of 4) everywhere
-  bool regress_generic = hon("DR_REGRESS_GENERIC");      // k_regress (the product's fallback for other plane counts) everywhere
-  bool shard_allreduce = hon("DR_SHARD_ALLREDUCE");      // view shard: round 2's all-reduce form instead of reduce + broadcast
-  // CostRegNet's conv11 + prob as ONE launch (tail_kernels.h): both forms are correct (tests/test_tail_gpu.py) and the memory side of the fusion works
-  // (the 78.6 MB tensor between the two layers is gone), but the transposed convolution x 1.8 (halo) and the prob stencil share the same issue slots -- fp32
-  // MFMAs and vector work serialise on a SIMD -- and nothing overlaps the kernel's memory side: 0.128 / 0.113 ms (matrix pipe) and 0.118 / 0.109 (vector pipe)
-  // at stages 2 / 3 against the two-kernel path's 0.100 / 0.096 (profiles/r05_tail.txt)
-  int tail_fused = hnum("DR_TAIL_FUSED", 0);             // 0: the two-kernel path; 1: k_tail_m (transposed convolution on the matrix pipe); 2: k_tail (on the vector pipe)
-  int tail_qy = hnum("DR_TAIL_QY", 0), tail_zchunk = hnum("DR_TAIL_ZCHUNK", 0);  // k_tail's tile (quad rows: 4, 8, 16, 32) and depth planes per workgroup (0: chosen by size)
-  bool fn_front = hnum("DR_FN_FRONT", 1) != 0;           // 1: FeatureNet's first block (u8 -> float, conv0.0, conv0.1) in one launch (k_fn_front); 0: the three launches
-  bool fn_head3 = hnum("DR_FN_HEAD3", 1) != 0;           // 1: the folded stage-3 head of FeatureNet (fn.out3a..d) in one launch (k_fn_head3); 0: the four launches
-  bool filter_fused = hnum("DR_FILTER_FUSED", 1) != 0;   // 1: the radix select's scans run as the prologue of the kernels that follow them (5 launches); 0: a k_scan launch per level (8)
-  bool prob_regress = hnum("DR_PROB_REGRESS", 1) != 0;   // 1: where a stage's planes are one depth chunk of k_prob2 (D = 8), the regression runs in the same launch (k_prob2_regress)
-  bool vol_split = !hon("DR_VOL_NO_SPLIT");              // stage 1's 32-channel cost volume as two 16-channel halves (DevTensor::split); off: one (D,h,w,32) tensor
-  bool costvol_v1 = hon("DR_COSTVOL_V1");                // round 2's k_costvol on unpadded feature maps
-  bool costvol_v3 = hon("DR_COSTVOL_V3");                // k_costvol3 everywhere: also where the product runs k_costvol5 and where DR_CV4_STAGES selects the LDS-staged k_costvol4
-  int costvol_cpl = hnum("DR_COSTVOL_CPL", 4) == 8 ? 8 : 4;
-  bool prob_v1 = hon("DR_PROB_V1");                      // round 2's k_prob (L1 gathers)
-  int prob_block = std::max(64, std::min(256, hnum("DR_PROB_BLOCK", 256) / 64 * 64)), prob_xo = hnum("DR_PROB_XO", 1);
-  bool prob_launch_order = hon("DR_PROB_LAUNCH_ORDER"), prob_on_conv = hon("DR_PROB_ON_CONV");
-  bool skip_on_conv = hon("DR_SKIP_ON_CONV"), no_skip_fusion = hon("DR_NO_SKIP_FUSION");
-  bool out3_folded = hnum("DR_OUT3_FOLDED", 1) != 0;     // 0: FeatureNet's stage-3 head in its literal order (fused-skip kernel)
-  bool d2h_copy = hook_env("DR_MVS_D2H") && !strcmp(hook_env("DR_MVS_D2H"), "copy");  // four copy-engine transfers instead of k_publish4
-  // k_costvol5's two choices (round 6, profiles/r06_costvol_ab.txt): a sample whose footprint is the previous plane's issues no gathers (0.109 / 0.172 / 0.120 ->
-  // 0.084 / 0.150 / 0.117 ms at depth chunks of 4 / 8 / 8 planes; 0.078 / 0.126 / 0.099 in the single-set form); the workgroup tile is four rows of a quarter segment
-  // (0.108 -> 0.099 ms at stage 3, 0.126 -> 0.122 at stage 2, nothing at stage 1)
-  int cv5_rows = hnum("DR_CV5_ROWS", 0);                 // 0: the product's rule (4 rows); 1 / 4: that tile at every stage
-  bool cv5_reuse = hnum("DR_CV5_REUSE", 1) != 0;         // 0: every sample gathers its four taps
-  int cv5_abl = hnum("DR_CV5_ABL", 0);                   // measuring hook: k_costvol5 without its gathers (1), stores (2), tap arithmetic (4)
-  // k_costvol4 (round 4: source taps staged through LDS -- north_star's "LDS staging of per-pixel feature slices"): bit-identical to
-  // k_costvol3 and measured 8-15 % SLOWER (0.121 / 0.163 / 0.105 against 0.106 / 0.150 / 0.099 ms per stage), so it is not in the product
-  int cv4_stages = hnum("DR_CV4_STAGES", 0);             // bit s-1 set = stage s builds its cost volume with k_costvol4 where it applies
-  int cv4_sp8 = hnum("DR_CV4_SP8", 0);                   // bit s-1 set = 8 planes per k_costvol4 step at stage s (else 4)
-};
-
-// One helper thread that takes half of the operator boundary's host copies (the window into the staging block, the result maps out of
-// the pinned block): a single core moves them at ~25 GB/s, i.e. 0.27 + 0.2 ms per 640 x 480 x 7 call on the critical path of TANDEM's
-// one-window-in-flight loop.  run() hands it a job, wait() returns when the job is done; the caller does its own half in between.
-class HostCopier {
- public:
-  HostCopier() : th_(&HostCopier::loop, this) {}
-  ~HostCopier() {
-    { std::lock_guard<std::mutex> lk(mu_); quit_ = true; }
-    cv_.notify_all();
-    th_.join();
-  }
-  void run(std::function<void()> job) {
-    { std::lock_guard<std::mutex> lk(mu_); job_ = std::move(job); busy_ = true; }
-    cv_.notify_all();
-  }
-  void wait() {
-    std::unique_lock<std::mutex> lk(mu_);
-    done_.wait(lk, [&] { return !busy_; });
-    if (!error_.empty()) { std::string e = error_; error_.clear(); fail(DR_ERR_DEVICE, "%s", e.c_str()); }
-  }
-  void wait_quiet() {
-    std::unique_lock<std::mutex> lk(mu_);
-    done_.wait(lk, [&] { return !busy_; });
-    error_.clear();
-  }
-
- private:
-  void loop() {
-    std::unique_lock<std::mutex> lk(mu_);
-    for (;;) {
-      cv_.wait(lk, [&] { return busy_ || quit_; });
-      if (quit_) return;
-      std::function<void()> job = std::move(job_);
-      lk.unlock();
-      std::string err;
-      try { job(); } catch (const std::exception &e) { err = e.what(); }
-      lk.lock();
-      error_ = err;
-      busy_ = false;
-      done_.notify_all();
-    }
-  }
-  std::mutex mu_;
-  std::condition_variable cv_, done_;
-  std::function<void()> job_;
-  std::string error_;
-  bool busy_ = false, quit_ = false;
-  std::thread th_;
 };
 
 static const char *conv_kind_name(const ConvLaunch &c) {
@@ -358,30 +169,22 @@ class MvsEngine {
   }
   void get_result(float *depth, float *conf, float *depth_dense, float *conf_dense) {
     std::unique_lock<std::mutex> lk(mu_);
-    done_cv_.wait(lk, [&] { return !unprocessed_; });
-    rethrow_worker_error();
-    if (!has_output_) fail(DR_ERR_PROTOCOL, "Output should be valid. Maybe you called GetResult more than once?");
+    const float *src = take_result(lk);
     const size_t n = (size_t)H_ * W_;
-    const float *src = h_out_[out_cur_];
     copier_.run([=] { memcpy(depth_dense, src + 2 * n, n * 4); memcpy(conf_dense, src + 3 * n, n * 4); });  // two maps each
     memcpy(depth, src, n * 4); memcpy(conf, src + n, n * 4);
     copier_.wait();
-    has_output_ = false;
   }
   // The same result WITHOUT the 4.9 MB host copy: pointers into the page-locked block the device wrote it to.  Two blocks alternate,
   // so the maps stay valid while the NEXT call is processed and die when the call after that one starts.
   void get_result_view(const float **depth, const float **conf, const float **depth_dense, const float **conf_dense) {
     std::unique_lock<std::mutex> lk(mu_);
-    done_cv_.wait(lk, [&] { return !unprocessed_; });
-    rethrow_worker_error();
-    if (!has_output_) fail(DR_ERR_PROTOCOL, "Output should be valid. Maybe you called GetResult more than once?");
+    const float *src = take_result(lk);
     const size_t n = (size_t)H_ * W_;
-    const float *src = h_out_[out_cur_];
     if (depth) *depth = src;
     if (conf) *conf = src + n;
     if (depth_dense) *depth_dense = src + 2 * n;
     if (conf_dense) *conf_dense = src + 3 * n;
-    has_output_ = false;
   }
 
   // --- key-frame feature cache (extension; see build_fn1) ----------------------------------------
@@ -401,7 +204,7 @@ class MvsEngine {
   }
   void feature_cache_stats(uint64_t out[6]) {
     std::unique_lock<std::mutex> lk(mu_);
-    out[0] = fc_hits_; out[1] = fc_misses_; out[2] = fc_batch_windows_; out[3] = fc_collisions_; out[4] = fn1_ok_ ? 1 : 0; out[5] = (uint64_t)fcache_.size();
+    out[0] = fc_.hits; out[1] = fc_.misses; out[2] = fc_.batch_windows; out[3] = fc_.collisions; out[4] = fn1_ok_ ? 1 : 0; out[5] = (uint64_t)fc_.size();
   }
 
   // --- device-resident hooks -------------------------------------------------------------------
@@ -483,7 +286,7 @@ class MvsEngine {
     check_march();
     if (before_ms) *before_ms = (float)t_before;
     if (after_ms) *after_ms = (float)t_after;
-    if (fn1_ok_ && !match_fn1()) { fn1_ok_ = false; fc_fast_ = false; }  // (the feature cache's single-view plan follows the batch plan's instances, or stands down)
+    if (fn1_ok_ && !match_fn1()) { fn1_ok_ = false; fc_.fast = false; }  // (the feature cache's single-view plan follows the batch plan's instances, or stands down)
   }
 
   // ---- view sharding hooks (SURVEY 8e / BASELINE configs[2]; no reference counterpart) ----
@@ -611,19 +414,8 @@ class MvsEngine {
       else if (o.kind == Op::CONV && o.conv.bf3) snprintf(kn, sizeof kn, "k_conv_b<%d,%d,%d>", o.conv.ci, o.conv.ct, o.conv.pt);
       else if (o.kind == Op::CONV && o.conv.args.class_loop > 0) snprintf(kn, sizeof kn, "k_conv_c<%d,%d,%d>", o.conv.ci, o.conv.ct, o.conv.pt);
       else if (o.kind == Op::CONV) snprintf(kn, sizeof kn, "k_conv<%d,%d,%d,%d>", o.conv.ci, o.conv.ct, o.conv.pt, o.conv.fz);
-      else if (o.kind == Op::COSTVOL) {
-        const CostVolArgs &ca = cv_[o.stage - 1];
-        const int Cc = 32 >> (o.stage - 1), dch = ca.planes.D >= 8 ? 8 : 4;
-        const bool v4 = cv4_applies(o.stage);
-        if (v4) snprintf(kn, sizeof kn, "k_costvol4<%d,%d>", Cc, dch);
-        else if (cv5_applies(o.stage)) snprintf(kn, sizeof kn, "k_costvol5<%d,%d>", Cc, cv_[o.stage - 1].dchunk);
-        else snprintf(kn, sizeof kn, sw_.costvol_v1 ? "k_costvol<%d>" : (sw_.costvol_v2 ? "k_costvol2<%d>" : "k_costvol3<%d>"), Cc);
-      }
-      else if (o.kind == Op::PROB) {
-        if (sw_.prob_v1) snprintf(kn, sizeof kn, "k_prob");
-        else if (o.stage >= 1 && o.stage <= 3 && prob_fused_last_[o.stage - 1]) snprintf(kn, sizeof kn, "k_prob2_regress<8>");
-        else snprintf(kn, sizeof kn, "k_prob2<%d>", sw_.prob_rows == 2 || sw_.prob_rows == 4 ? sw_.prob_rows : 1);
-      }
+      else if (o.kind == Op::COSTVOL) choose_costvol(costvol_shape(cv_[o.stage - 1]), sw_, o.stage).name(kn, sizeof kn);
+      else if (o.kind == Op::PROB) choose_prob(prob_shape(pr_[o.stage - 1]), sw_, o.stage).name(kn, sizeof kn);
 #ifdef DR_PARITY_HOOKS
       else if (o.kind == Op::TAIL) snprintf(kn, sizeof kn, o.tail.wmf ? "k_tail_m<%d>" : "k_tail<%d>", std::max(3, tail_nout(o.tail.QY, o.tail.QX)));
 #endif
@@ -665,6 +457,14 @@ class MvsEngine {
   void rethrow_worker_error() {
     if (!worker_error_.empty()) { std::string e = worker_error_; worker_error_.clear(); fail(DR_ERR_DEVICE, "%s", e.c_str()); }
   }
+  // GetResult's first half: waits for the window, rethrows what its worker threw and hands the pinned block of four maps out ONCE
+  const float *take_result(std::unique_lock<std::mutex> &lk) {
+    done_cv_.wait(lk, [&] { return !unprocessed_; });
+    rethrow_worker_error();
+    if (!has_output_) fail(DR_ERR_PROTOCOL, "Output should be valid. Maybe you called GetResult more than once?");
+    has_output_ = false;
+    return h_out_[out_cur_];
+  }
   // windows whose kernels are enqueued or running, per device, over all engines of the process (forward() forks onto its side stream only when it is alone)
   static std::atomic<int> &windows_in_flight(int device) {
     static std::atomic<int> n[16];
@@ -684,24 +484,9 @@ class MvsEngine {
           InFlight window(device_, prelaunched_);  // (counted from here, or from CallAsync's own launch, to the end of this block)
           if (prelaunched_) prelaunched_ = false;  // (CallAsync enqueued this window's forward itself: stage_inputs)
           else forward(nullptr);
-          const size_t n = (size_t)H_ * W_ * 4;
           const int blk = out_cur_ ^ 1;  // the block the previous result does NOT live in (drm_get_result_view: that one may still be read)
-          float *ho = h_out_[blk];
-          if (sw_.d2h_copy) {  // DR_MVS_D2H=copy: the four copy-engine transfers of round 2 (A/B hook)
-            DR_HIP(hipMemcpyAsync(ho, T("depth").d, n, hipMemcpyDeviceToHost, stream_));
-            DR_HIP(hipMemcpyAsync(ho + n / 4, T("confidence").d, n, hipMemcpyDeviceToHost, stream_));
-            DR_HIP(hipMemcpyAsync(ho + 2 * (n / 4), T("depth3").d, n, hipMemcpyDeviceToHost, stream_));
-            DR_HIP(hipMemcpyAsync(ho + 3 * (n / 4), T("conf3").d, n, hipMemcpyDeviceToHost, stream_));
-          } else {  // (H and W are multiples of 32: whole float4s)
-            hipLaunchKernelGGL(k_publish4, dim3(256), dim3(256), 0, stream_, (const float4 *)T("depth").d, (const float4 *)T("confidence").d,
-                               (const float4 *)T("depth3").d, (const float4 *)T("conf3").d, (float4 *)h_out_dev_[blk], n / 16);
-          }
-          DR_HIP(hipStreamSynchronize(stream_));
-          if (cache_mismatch_recovered()) {  // a cache hit that was a key collision: the window ran again without the cache; publish THAT result
-            hipLaunchKernelGGL(k_publish4, dim3(256), dim3(256), 0, stream_, (const float4 *)T("depth").d, (const float4 *)T("confidence").d,
-                               (const float4 *)T("depth3").d, (const float4 *)T("conf3").d, (float4 *)h_out_dev_[blk], n / 16);
-            DR_HIP(hipStreamSynchronize(stream_));
-          }
+          publish(blk);
+          if (cache_mismatch_recovered()) publish(blk);  // a cache hit that was a key collision: the window ran again without the cache; publish THAT result
           check_march();
           out_cur_ = blk;
           has_output_ = true;
@@ -711,6 +496,19 @@ class MvsEngine {
       }
       input_cv_.wait(lk, [&] { return unprocessed_ || !running_; });
     }
+  }
+
+  // the four result maps into pinned block `blk`, and the wait for them
+  void publish(int blk) {
+    const size_t n = (size_t)H_ * W_ * 4;
+    float *ho = h_out_[blk];
+    if (sw_.d2h_copy) {  // DR_MVS_D2H=copy: the four copy-engine transfers of round 2 (A/B hook)
+      DR_HIP(hipMemcpyAsync(ho, filt_.depth, n, hipMemcpyDeviceToHost, stream_));
+      DR_HIP(hipMemcpyAsync(ho + n / 4, filt_.conf, n, hipMemcpyDeviceToHost, stream_));
+      DR_HIP(hipMemcpyAsync(ho + 2 * (n / 4), filt_.depth3, n, hipMemcpyDeviceToHost, stream_));
+      DR_HIP(hipMemcpyAsync(ho + 3 * (n / 4), filt_.conf3, n, hipMemcpyDeviceToHost, stream_));
+    } else launch_publish4(filt_.depth, filt_.conf, filt_.depth3, filt_.conf3, h_out_dev_[blk], n / 16, stream_);
+    DR_HIP(hipStreamSynchronize(stream_));
   }
 
   DevTensor &T(const std::string &name) {
@@ -730,23 +528,13 @@ class MvsEngine {
     for (auto &kv : tensors_) (void)hipFree(kv.second.d);
     tensors_.clear();
     ops_.clear();
-    ops1_.clear(); fcache_.clear(); fn1_ok_ = false; fc_fast_ = fc_fill_ = false;  // (a new window shape evicts everything: the entries' buffers are in misc_)
+    ops1_.clear(); fcache_.clear(); fc_.clear(); fn1_ok_ = false; fc_.fast = fc_.fill = false;  // (a new window shape evicts everything: the entries' buffers are in misc_)
     plan_arena_.reset();
     for (void *p : misc_) (void)hipFree(p);
     misc_.clear();
   }
 
   // ---------------------------------------------------------------- layer construction
-  void fold_bn(const std::string &p, int C, std::vector<float> &sc, std::vector<float> &bi) {
-    const auto &g = blob_.at(p + ".weight").data, &b = blob_.at(p + ".bias").data;
-    const auto &m = blob_.at(p + ".running_mean").data, &v = blob_.at(p + ".running_var").data;
-    sc.resize(C); bi.resize(C);
-    for (int c = 0; c < C; ++c) {
-      const double s = (double)g[c] / std::sqrt((double)v[c] + 1e-5);
-      sc[c] = (float)s;
-      bi[c] = (float)((double)b[c] - (double)m[c] * s);
-    }
-  }
   // FeatureNet's skip connection (1x1 conv + bias + nearest-upsampled coarser level) on the streaming kernel k_skip_up;
   // DR_SKIP_ON_CONV=1 keeps it on the MFMA convolution kernel (A/B hook, and the path for other channel counts).
   DevTensor &add_skip(const std::string &opname, const std::string &wname, const DevTensor &in, const std::string &outname, const DevTensor &coarse) {
@@ -777,13 +565,10 @@ class MvsEngine {
     std::vector<float> padded;
     if (c_in_real != in.C) {  // RGB -> RGB0: zero-pad the input-channel axis of the weights
       if (transposed || c_in_real > in.C) fail(DR_ERR_ARG, "%s: channel mismatch", opname.c_str());
-      const int taps = k3d * kh * kw;
-      padded.assign((size_t)c_out * in.C * taps, 0.f);
-      for (int co = 0; co < c_out; ++co) for (int ci = 0; ci < c_in_real; ++ci) for (int t = 0; t < taps; ++t)
-        padded[((size_t)co * in.C + ci) * taps + t] = w.data[((size_t)co * c_in_real + ci) * taps + t];
+      padded = pad_cin(w.data, c_out, c_in_real, in.C, k3d * kh * kw);
       L.weight = padded.data();
     } else L.weight = w.data.data();
-    if (!bnname.empty()) fold_bn(bnname, c_out, L.scale, L.bias);
+    if (!bnname.empty()) fold_bn(blob_, bnname, c_out, L.scale, L.bias);
     else if (conv_bias) L.bias = blob_.at(wname + ".bias").data;
     ConvPlanOut P0;  // dims first
     {
@@ -848,7 +633,7 @@ class MvsEngine {
     const bool fits32 = (double)V * H * W * 32.0 < 2147483648.0 && ((uintptr_t)d_bgr_ & 3) == 0;  // (the kernel addresses both tensors with 32-bit byte offsets from an aligned base)
     if (!sw_.fn_front || conv_bf3_policy() || !shape_ok || !fits32 || !lds_fits(kFrontLdsBytes)) {
       DevTensor &img = alloc("image", V, H, W, 4);
-      { Op o; o.kind = Op::PREPROCESS; o.name = "preprocess"; o.bytes = (double)V * H * W * (3 + 16); ops_.push_back(o); }
+      { Op o; o.kind = Op::PREPROCESS; o.name = "preprocess"; o.bytes = (double)V * H * W * (3 + 16); o.pre = {d_bgr_, reinterpret_cast<float4 *>(img.d), lut_, (size_t)V * H * W}; ops_.push_back(o); }
       DevTensor &c3a = cbr2("fn.conv0.0", fn + "conv0.0", img, 3, 1, CONV_XPAIR);
       return cbr2("fn.conv0.1", fn + "conv0.1", c3a, 3, 1, CONV_XPAIR);
     }
@@ -860,7 +645,7 @@ class MvsEngine {
     a.w2 = reinterpret_cast<const float4 *>(plan_arena_->upload(front_pack(wb.data.data(), 8, 8)));
     auto affine = [&](const std::string &bn) {  // 16 scales, 16 biases: XPAIR row r = 8 * (x of the pair) + channel
       std::vector<float> sc, bi, sb(32);
-      fold_bn(bn, 8, sc, bi);
+      fold_bn(blob_, bn, 8, sc, bi);
       for (int r = 0; r < 16; ++r) { sb[r] = sc[r & 7]; sb[16 + r] = bi[r & 7]; }
       return plan_arena_->upload(sb);
     };
@@ -892,6 +677,7 @@ class MvsEngine {
     H_ = W_ = V_ = 0;
     memset(cv_, 0, sizeof cv_);
     memset(rg_, 0, sizeof rg_);
+    memset(pr_, 0, sizeof pr_);
     try {
       build_plan(H, W, V);
     } catch (...) {
@@ -929,20 +715,8 @@ class MvsEngine {
     // feat3 then differs from the literal order by fp32 reassociation (2e-6 of its range).  DR_OUT3_FOLDED=0: the fused-skip form.
     if (sw_.out3_folded && !sw_.no_skip_fusion && !sw_.skip_on_conv && w3.dims[0] == 32 && w3.dims[1] == 8 && c3.C == 8 &&
         i2.C == 32 && wo3.dims[0] == 8 && wo3.dims[1] == 32 && i2.H * 2 == c3.H && i2.W * 2 == c3.W) {
-      const std::vector<float> &b3 = blob_.at(fn + "skip.stage3.bias").data;
-      std::vector<float> wa((size_t)8 * 8 * 9), T(9 * 8), bint(8, 0.f);
-      for (int co = 0; co < 8; ++co)
-        for (int t = 0; t < 9; ++t) {
-          for (int c8 = 0; c8 < 8; ++c8) {
-            double acc = 0;
-            for (int c = 0; c < 32; ++c) acc += (double)wo3.data[((size_t)co * 32 + c) * 9 + t] * (double)w3.data[(size_t)c * 8 + c8];
-            wa[((size_t)co * 8 + c8) * 9 + t] = (float)acc;
-          }
-          double tb = 0;
-          for (int c = 0; c < 32; ++c) tb += (double)wo3.data[((size_t)co * 32 + c) * 9 + t] * (double)b3[c];
-          T[t * 8 + co] = (float)tb;
-        }
-      for (int co = 0; co < 8; ++co) { double b = 0; for (int t = 0; t < 9; ++t) b += (double)T[t * 8 + co]; bint[co] = (float)b; }
+      const Out3Fold fold = compose_out3(wo3.data, w3.data, blob_.at(fn + "skip.stage3.bias").data);
+      const std::vector<float> &wa = fold.wa, &T = fold.T, &bint = fold.bint;
       DevTensor &f3 = alloc("feat3", c3.D, c3.H, c3.W, 8, fpad);
       if (sw_.fn_head3 && !conv_bf3_policy() && (double)f3.n() * 4.0 < 2147483648.0 && (double)i2.n() * 4.0 < 2147483648.0 && lds_fits(kH3LdsBytes)) {  // one launch: the three terms meet in one accumulator (fn_head3.h)
         Op o; o.kind = Op::HEAD3; o.name = "fn.head3";
@@ -996,13 +770,13 @@ class MvsEngine {
   //    -- the products and their order per output value do not depend on the tile shape or the batch size (tests: test_feature_cache_is_bit_identical);
   //  * OFF by default and in every leg of bench.py that feeds `value` / `single_window_ms` (they repeat one window: every image would hit).
   struct FnOut { size_t op; int stage; size_t offset; };  // launch `op` of the single-view plan stores into feat<stage + 1> at this float offset
-  struct FcEntry { uint64_t key[2] = {0, 0}; float *feat[3] = {nullptr, nullptr, nullptr}; uint8_t *bgr = nullptr; uint64_t used = 0; bool valid = false; };
+  struct FcBuffers { float *feat[3] = {nullptr, nullptr, nullptr}; uint8_t *bgr = nullptr; };  // entry e of the index (fc_, mvs_host.h): its three bordered feature maps and its image
   static bool same_instance(const ConvLaunch &a, const ConvLaunch &b) {
     return a.async == b.async && a.ci == b.ci && a.ct == b.ct && a.pt == b.pt && a.fz == b.fz && a.bf3 == b.bf3 && a.nup == b.nup && a.ncw == b.ncw &&
            a.march.wino == b.march.wino && a.march.rm == b.march.rm;
   }
   void build_fn1(int H, int W) {
-    fn1_ok_ = false; ops1_.clear(); fcache_.clear();
+    fn1_ok_ = false; ops1_.clear(); fcache_.clear(); fc_.clear();
     if (ops_.empty() || ops_[0].kind != Op::FRONT || sw_.costvol_v1 || shard_nsrc_) return;  // (the single-view plan patches k_fn_front's image pointer per call)
     const size_t lo = fork_lo_, hi = fork_hi_, f2 = feat2_op_;
     std::vector<Op> batch;
@@ -1015,8 +789,8 @@ class MvsEngine {
     if (!match_fn1()) { ops1_.clear(); return; }
     // the entries: three bordered feature maps + the image, per cached key frame
     const size_t img_bytes = (size_t)H * W * 3;
-    fcache_.resize(fcache_cap_);
-    for (FcEntry &e : fcache_) {
+    fcache_.resize(fcache_cap_); fc_.resize(fcache_cap_);
+    for (FcBuffers &e : fcache_) {
       for (int s = 0; s < 3; ++s) {
         const DevTensor &t = T("c1.feat" + std::to_string(s + 1));
         e.feat[s] = dalloc<float>(t.n()); misc_.push_back(e.feat[s]);
@@ -1036,7 +810,7 @@ class MvsEngine {
         if (out >= t.d && out < t.d + t.n()) fn1_out_.push_back({i, s, (size_t)(out - t.d)});
       }
     }
-    if (fn1_out_.size() != 3) { ops1_.clear(); fcache_.clear(); return; }
+    if (fn1_out_.size() != 3) { ops1_.clear(); fcache_.clear(); fc_.clear(); return; }
     fn1_ok_ = true;
   }
   // every launch of the single-view plan becomes the batch plan's own kernel instance for that layer (the planner ranks candidates by a cost model that sees
@@ -1059,66 +833,19 @@ class MvsEngine {
     }
     return true;
   }
-  static void image_key(const uint8_t *p, size_t n, int H, int W, uint64_t key[2]) {
-    uint64_t a = 0xcbf29ce484222325ull ^ (uint64_t)H, b = 0x9e3779b97f4a7c15ull ^ (uint64_t)W;
-    auto mix = [&](uint64_t w) { a = (a ^ w) * 0x100000001b3ull; b = (b + w) * 0xff51afd7ed558ccdull; b ^= b >> 29; };
-    auto word = [&](size_t off) { uint64_t w; memcpy(&w, p + off, 8); return w; };
-    for (size_t o = 0; o < 64; o += 8) { mix(word(o)); mix(word(n - 64 + o)); }
-    const size_t step = (n / 512) & ~(size_t)7;
-    for (size_t k = 1; k < 512 && step; ++k) mix(word(k * step));
-    key[0] = a; key[1] = b;
-  }
-  // decides, for the window being staged, which views the cache answers.  fc_slot_[v]: the entry that holds (or will hold) view v's features.
-  void plan_cache_use(int H, int W, int V, const uint8_t *const *bgrs, const std::vector<int> &order) {
-    fc_fast_ = false; fc_fill_ = false; fc_miss_ = -1;
-    if (!fn1_ok_ || (int)fcache_.size() < V + 1 || shard_nsrc_ || comm_ || phase_mode_) return;  // (a view-shard rank computes its own views every time)
-    for (int s = 1; s <= 3; ++s) if (!cv5_applies(s)) return;  // (only k_costvol5 reads the views by pointer)
-    const size_t img_bytes = (size_t)H * W * 3;
-    uint64_t keys[8][2];
-    int nmiss = 0;
-    ++fc_clock_;
-    for (int v = 0; v < V; ++v) {
-      image_key(bgrs[order[v]], img_bytes, H, W, keys[v]);
-      fc_slot_[v] = -1;
-      for (size_t e = 0; e < fcache_.size(); ++e)
-        if (fcache_[e].valid && fcache_[e].key[0] == keys[v][0] && fcache_[e].key[1] == keys[v][1]) { fc_slot_[v] = (int)e; break; }
-      for (int u = 0; u < v; ++u) if (fc_slot_[v] >= 0 && fc_slot_[u] == fc_slot_[v]) fc_slot_[v] = -1;  // (two views with one key: only one may own the entry)
-      if (fc_slot_[v] < 0) { ++nmiss; fc_miss_ = v; } else fcache_[fc_slot_[v]].used = fc_clock_;
-    }
-    auto evict = [&]() {  // the least recently used entry that this window does not use
-      int best = -1;
-      for (size_t e = 0; e < fcache_.size(); ++e) {
-        bool in_window = false;
-        for (int v = 0; v < V; ++v) in_window |= fc_slot_[v] == (int)e;
-        if (!in_window && (best < 0 || !fcache_[e].valid || (fcache_[best].valid && fcache_[e].used < fcache_[best].used))) best = (int)e;
-        if (best >= 0 && !fcache_[best].valid) break;
-      }
-      return best;
-    };
-    if (nmiss <= 1) {
-      fc_fast_ = true;
-      if (nmiss == 1) {
-        const int e = evict();
-        fcache_[e].valid = false;  // (valid again once a forward has enqueued its fill)
-        fcache_[e].key[0] = keys[fc_miss_][0]; fcache_[e].key[1] = keys[fc_miss_][1]; fcache_[e].used = fc_clock_;
-        fc_slot_[fc_miss_] = e;
-      }
-      fc_hits_ += V - nmiss; fc_misses_ += nmiss;
-    } else {  // the batch path computes every view; its outputs fill the cache
-      fc_fill_ = true; fc_miss_ = -1;
-      for (int v = 0; v < V; ++v) {
-        if (fc_slot_[v] >= 0) continue;
-        const int e = evict();
-        fcache_[e].valid = false;
-        fcache_[e].key[0] = keys[v][0]; fcache_[e].key[1] = keys[v][1]; fcache_[e].used = fc_clock_;
-        fc_slot_[v] = e;
-      }
-      fc_misses_ += V; ++fc_batch_windows_;
-    }
+  // decides, for the window being staged, which views the cache answers (FeatureIndex::plan); the guards that need engine state are here
+  void plan_cache_use(int H, int W, int V, const uint8_t *const *bgrs, const int *order) {
+    fc_.stand_down();
+    if (!fn1_ok_ || shard_nsrc_ || comm_ || phase_mode_) return;  // (a view-shard rank computes its own views every time)
+    for (int s = 1; s <= 3; ++s)
+      if (choose_costvol(costvol_shape(cv_[s - 1]), sw_, s).family != CostVolChoice::V5) return;  // (only k_costvol5 reads the views by pointer)
+    uint64_t keys[kMaxSrc + 1][2];
+    for (int v = 0; v < V; ++v) image_key(bgrs[order[v]], (size_t)H * W * 3, H, W, keys[v]);
+    fc_.plan(V, keys);
     // where the plane sweep finds each view
     for (int s = 0; s < 3; ++s)
       for (int v = 0; v < V; ++v)
-        if (fc_fast_) cv_[s].vfeat[v] = fcache_[fc_slot_[v]].feat[s];
+        if (fc_.fast) cv_[s].vfeat[v] = fcache_[fc_.slot[v]].feat[s];
   }
   void launch_fn_op(const Op &o, hipStream_t st) {
     if (o.kind == Op::CONV) launch_conv(o.conv, st);
@@ -1127,22 +854,22 @@ class MvsEngine {
     else fail(DR_ERR_UNSUPPORTED, "feature cache: op kind %d in the single-view plan", (int)o.kind);
   }
   // one launch: the hits compared with their entries' images, the new image filed in its entry
-  void launch_cache_io() {
+  void enqueue_cache_io() {
     const size_t img_bytes = (size_t)H_ * W_ * 3;
     CacheIoArgs io{};
     for (int v = 0; v < V_; ++v) {
       io.img[v] = reinterpret_cast<const uint4 *>(d_bgr_ + v * img_bytes);
-      io.entry[v] = reinterpret_cast<uint4 *>(fcache_[fc_slot_[v]].bgr);
+      io.entry[v] = reinterpret_cast<uint4 *>(fcache_[fc_.slot[v]].bgr);
     }
-    io.miss = fc_miss_; io.flag = fc_flag_dev(); io.n16 = img_bytes / 16;
-    hipLaunchKernelGGL(k_cache_io, dim3(32, V_), dim3(256), 0, stream_, io);
+    io.miss = fc_.miss; io.flag = fc_flag_dev(); io.n16 = img_bytes / 16;
+    launch_cache_io(io, V_, stream_);
   }
   // fast path of a forward: verify the hits, FeatureNet on the one uncached view, its outputs (and image) into the entry
   void forward_cached_features() {
     const size_t img_bytes = (size_t)H_ * W_ * 3;
-    if (!defer_cache_io_) launch_cache_io();
-    if (fc_miss_ >= 0) {
-      FcEntry &e = fcache_[fc_slot_[fc_miss_]];
+    if (!defer_cache_io_) enqueue_cache_io();
+    if (fc_.miss >= 0) {
+      const FcBuffers &e = fcache_[fc_.slot[fc_.miss]];
       for (const FnOut &p : fn1_out_) {
         Op &o = ops1_[p.op];
         (o.kind == Op::CONV ? o.conv.args.out : o.head3.out) = e.feat[p.stage] + p.offset;
@@ -1150,25 +877,25 @@ class MvsEngine {
       // (the heads on the side stream, as the batch path runs them, were measured: device time 1.821 -> 1.825 ms, the sliding loop x 1.10 instead of x 1.12-1.15 --
       // two cross-stream waits cost what the overlap of three small launches wins; not kept)
       for (Op &o : ops1_) {
-        if (o.kind == Op::FRONT) o.front.bgr = d_bgr_ + fc_miss_ * img_bytes;
+        if (o.kind == Op::FRONT) o.front.bgr = d_bgr_ + fc_.miss * img_bytes;
         launch_fn_op(o, stream_);
       }
-      e.valid = true;
+      fc_.set_valid(fc_.slot[fc_.miss]);
     }
   }
   // batch path with the cache on: every view's features (and image) into its entry, behind the forward that produced them
   void fill_cache_from_batch() {
     const size_t img_bytes = (size_t)H_ * W_ * 3;
     for (int v = 0; v < V_; ++v) {
-      FcEntry &e = fcache_[fc_slot_[v]];
-      if (e.valid) continue;
+      const FcBuffers &e = fcache_[fc_.slot[v]];
+      if (fc_.valid(fc_.slot[v])) continue;
       for (int s = 0; s < 3; ++s) {
         const DevTensor &t = T("feat" + std::to_string(s + 1));
         const size_t n1 = t.n() / t.D;
         DR_HIP(hipMemcpyAsync(e.feat[s], t.d + v * n1, n1 * 4, hipMemcpyDeviceToDevice, stream_));
       }
       DR_HIP(hipMemcpyAsync(e.bgr, d_bgr_ + v * img_bytes, img_bytes, hipMemcpyDeviceToDevice, stream_));
-      e.valid = true;
+      fc_.set_valid(fc_.slot[v]);
     }
   }
   int *fc_flag_dev() { int *d = nullptr; DR_HIP(hipHostGetDevicePointer((void **)&d, fc_flag_, 0)); return d; }
@@ -1176,9 +903,9 @@ class MvsEngine {
   bool cache_mismatch_recovered() {
     if (!fc_flag_ || !*fc_flag_) return false;
     *fc_flag_ = 0;
-    ++fc_collisions_;
-    for (FcEntry &e : fcache_) e.valid = false;
-    fc_fast_ = false; fc_fill_ = false;
+    ++fc_.collisions;
+    fc_.invalidate_all();
+    fc_.fast = false; fc_.fill = false;
     for (int s = 0; s < 3; ++s) set_batch_vfeat(s);
     forward(nullptr);
     DR_HIP(hipStreamSynchronize(stream_));
@@ -1240,7 +967,7 @@ class MvsEngine {
         // conv11 (ConvTranspose3d 16 -> 8 + BN + ReLU, + conv0) and prob (8 -> 1) in one z-marching launch: the 8-channel full-resolution tensor
         // between them (78.6 MB at stages 2 and 3) is never written or read (tail_kernels.h)
         std::vector<float> sc, bi;
-        fold_bn(cr + "conv11.bn", 8, sc, bi);
+        fold_bn(blob_, cr + "conv11.bn", 8, sc, bi);
         sc.insert(sc.end(), bi.begin(), bi.end());
         DevTensor &lg = alloc("logits" + S, D, h, w, 1);
         Op o; o.kind = Op::TAIL; o.stage = s; o.name = pre + "tail";
@@ -1251,9 +978,7 @@ class MvsEngine {
         t.wp = plan_arena_->upload(tail_pack_prob(wpr.data.data()));
         const bool mf = sw_.tail_fused == 1;
         t.wmf = mf ? plan_arena_->upload(tail_pack_deconv_mfma(w11.data.data())) : nullptr;
-        tail_pick_tile(h, w, t.QY, t.QX, mf);
-        if (sw_.tail_qy == 4 || sw_.tail_qy == 8 || sw_.tail_qy == 16 || (sw_.tail_qy == 32 && !mf)) { t.QY = sw_.tail_qy; t.QX = 256 / t.QY; }
-        t.zchunk = sw_.tail_zchunk > 0 ? std::min(D, sw_.tail_zchunk) : tail_pick_zchunk(D, h, w, t.QY, t.QX);
+        tail_set_tile(t, sw_.tail_qy, sw_.tail_zchunk, mf);
         const double N = (double)D * h * w;
         o.flops = 2.0 * 3.375 * 16 * 8 * N + 2.0 * 216 * N;  // the algorithmic MACs of both layers (halo recomputation not counted)
         o.bytes = 4.0 * (x9.n() + c0.n() + lg.n());
@@ -1267,12 +992,9 @@ class MvsEngine {
         // measured against k_prob in profiles/r02_experiments.txt
         add_conv(pre + "prob", cr + "prob", "", false, false, x11, "logits" + S, 3, 3, 3, 1, 1, 1, false, CONV_X8, nullptr, 0);
       } else {
-        const HostTensor &pw = blob_.at(cr + "prob.weight");  // (1,8,3,3,3) -> [tap][cin]
-        std::vector<float> wt(27 * 8);
-        for (int ci = 0; ci < 8; ++ci) for (int t = 0; t < 27; ++t) wt[t * 8 + ci] = pw.data[ci * 27 + t];
         DevTensor &lg = alloc("logits" + S, D, h, w, 1);
         Op o; o.kind = Op::PROB; o.stage = s; o.name = pre + "prob";
-        o.p0 = x11.d; o.p1 = plan_arena_->upload(wt); o.p2 = lg.d; o.d0 = D; o.d1 = h; o.d2 = w;
+        pr_[s - 1] = {x11.d, plan_arena_->upload(prob_taps(blob_.at(cr + "prob.weight").data)), lg.d, D, h, w};
         o.flops = 2.0 * 216 * D * h * w; o.bytes = 4.0 * (x11.n() + lg.n());
         ops_.push_back(o);
       }
@@ -1281,9 +1003,8 @@ class MvsEngine {
       alloc("conf" + S, 1, h, w, 1);
       { Op o; o.kind = Op::REGRESS; o.stage = s; o.name = pre + "regress"; o.bytes = 4.0 * ((double)D * h * w + 2.0 * h * w); o.flops = 8.0 * D * h * w; ops_.push_back(o); }
     }
-    alloc("edge", 1, H, W, 1);
-    alloc("depth", 1, H, W, 1);
-    alloc("confidence", 1, H, W, 1);
+    filt_ = {T("depth3").d, T("conf3").d, alloc("edge", 1, H, W, 1).d, alloc("depth", 1, H, W, 1).d, alloc("confidence", 1, H, W, 1).d, d_state_, d_hist_,
+             H * W, H, W, sw_.hist_blocks, sw_.filter_fused};
     { Op o; o.kind = Op::EDGE; o.name = "filter.edge"; o.bytes = 8.0 * H * W; ops_.push_back(o); }
     const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
     for (int i = 0; i < 3; ++i) {
@@ -1302,9 +1023,8 @@ class MvsEngine {
     DR_HIP(hipSetDevice(device_));
     configure(H, W, V);
     const size_t img_bytes = (size_t)H * W * 3;
-    std::vector<int> order;
-    order.push_back(ref);
-    for (int i = 0; i < V; ++i) if (i != ref) order.push_back(i);
+    const WindowGeometry geo = plan_geometry(H, W, V, ref, K9, c2ws, dmin, dmax, disc, blob_, shard_nsrc_);  // cameras, plane ranges, filter rank (mvs_host.h)
+    const int *order = geo.order;  // model order [ref, others]
     // view by view: the copy engine moves view v to the device while the host gathers view v + 1 into the pinned block (one 6.45 MB
     // transfer behind seven memcpys cost their sum: 0.3 + 0.2 ms at 640 x 480 x 7 on the operator boundary's critical path)
     // Images that already live in page-locked memory (drm_host_alloc, hipHostMalloc, hipHostRegister) go to the device straight from
@@ -1326,94 +1046,50 @@ class MvsEngine {
         pinned = p >= lo && p + img_bytes <= lo + span;
       }
     }
-    // stage intrinsics: rows 0-1 x 0.25 / 0.5 / 1 (the C++ rule, dr_mvsnet.cpp:226-247)
-    double w2c[8][16];
-    for (int v = 0; v < V; ++v) {
-      double c2w[16];
-      for (int i = 0; i < 16; ++i) c2w[i] = c2ws[order[v]][i];
-      inv4(c2w, w2c[v]);
-    }
-    const float base_interval = (dmax - dmin) / (float)(blob_.depth_num[0] - 1);  // module.py:1493
     for (int s = 1; s <= 3; ++s) {
-      const float f = s == 1 ? 0.25f : (s == 2 ? 0.5f : 1.f);
-      float Ks[9];
-      for (int i = 0; i < 9; ++i) Ks[i] = i < 6 ? (float)((double)f * (double)K9[i]) : K9[i];
-      const int sc = 1 << (3 - s), h = H / sc, w = W / sc, D = blob_.depth_num[s - 1], C = 32 >> (s - 1);
+      const StageGeometry &g = geo.stage[s - 1];
+      const int sc = 1 << (3 - s), h = H / sc, w = W / sc, D = g.D, C = 32 >> (s - 1);
+      const std::string S = std::to_string(s);
+      const DevTensor &feat = T("feat" + S), &vol = T("volume" + S);
       CostVolArgs &a = cv_[s - 1];
       memset(&a, 0, sizeof a);
-      a.feat = T("feat" + std::to_string(s)).d;
-      a.fpad = T("feat" + std::to_string(s)).pad;
-      a.vol = T("volume" + std::to_string(s)).d;
-      a.split = T("volume" + std::to_string(s)).split;
+      a.feat = feat.d; a.fpad = feat.pad;
+      a.vol = vol.d; a.split = vol.split;
       a.V = V; a.h = h; a.w = w;
-      a.dchunk = s == 1 ? 4 : (D >= 16 ? 8 : D);  // enough workgroups to fill 256 CUs at every stage
       a.view_aggregation = blob_.view_aggregation;
-      // k_costvol5 holds a chunk's planes in registers: 4 planes leave room for six waves per SIMD (0.150 -> 0.131 ms at stage 2, 0.117 -> 0.106 at stage 3)
-      if (a.view_aggregation && a.fpad && D % 4 == 0 && !sw_.costvol_v2 && !sw_.costvol_v3 && !sw_.cv4_stages) a.dchunk = 4;
-      if (sw_.cv_dchunk[s - 1] > 0) a.dchunk = std::min(D, sw_.cv_dchunk[s - 1]);  // tuning hook
-      // view sharding: this rank's window holds a subset of the source views, the divisor stays the whole window's
-      if (shard_nsrc_ && !blob_.view_aggregation) fail(DR_ERR_UNSUPPORTED, "view sharding needs a view-aggregation model (the variance volume is not a sum over views)");
-      a.nsrc_f = shard_nsrc_ ? (float)shard_nsrc_ : (float)(V - 1);
+      a.dchunk = costvol_dchunk(s, D, a.view_aggregation, a.fpad, sw_);
+      a.nsrc_f = g.nsrc_f;
+      memcpy(a.M, g.M, sizeof a.M);
       PlaneArgs &p = a.planes;
-      p.D = D; p.dmin = dmin; p.interval = base_interval;
-      if (s > 1) {
-        p.prev = T("depth" + std::to_string(s - 1)).d; p.hp = h / 2; p.wp = w / 2;
-        const float delta = blob_.ratio[s - 1] * base_interval;  // cva_mvsnet.py:151
-        p.half_range = ((float)D / 2.f) * delta;                  // module.py:1518
-        p.full_range = (float)D * delta;                          // module.py:1526
-      }
-      double r_w2p[16], r_p2w[16];
-      world_to_pixel(Ks, w2c[0], r_w2p);
-      inv4(r_w2p, r_p2w);
-      for (int v = 1; v < V; ++v) {
-        double s_w2p[16], M[16];
-        world_to_pixel(Ks, w2c[v], s_w2p);
-        mul4(s_w2p, r_p2w, M);
-        for (int i = 0; i < 12; ++i) a.M[v - 1][i] = (float)M[i];
-      }
+      p.D = D; p.dmin = g.dmin; p.interval = g.interval;
+      p.half_range = g.half_range; p.full_range = g.full_range;
+      if (s > 1) { p.prev = T("depth" + std::to_string(s - 1)).d; p.hp = h / 2; p.wp = w / 2; }
       if (blob_.view_aggregation) {
-        const std::string g = "volume_gates.stage" + std::to_string(s) + ".";
-        const auto &w0 = blob_.at(g + "0.weight").data;
-        for (int c = 0; c < C; ++c) a.gw[c] = w0[c];
-        auto bnf = [&](const std::string &bn, double &A, double &B) {
-          const double ga = blob_.at(bn + ".weight").data[0], be = blob_.at(bn + ".bias").data[0];
-          const double mu = blob_.at(bn + ".running_mean").data[0], var = blob_.at(bn + ".running_var").data[0];
-          A = ga / std::sqrt(var + 1e-5); B = be - mu * A;
-        };
-        double A1, B1, A2, B2;
-        bnf(g + "1", A1, B1); bnf(g + "4", A2, B2);
-        const double b0 = blob_.at(g + "0.bias").data[0], w3 = blob_.at(g + "3.weight").data[0], b3 = blob_.at(g + "3.bias").data[0];
-        a.gA1 = (float)A1; a.gB1 = (float)(b0 * A1 + B1);
-        a.gA2 = (float)(w3 * A2); a.gB2 = (float)(b3 * A2 + B2);
+        const GateFold gf = fold_gate(blob_, s, C);
+        memcpy(a.gw, gf.gw, sizeof a.gw);
+        a.gA1 = gf.gA1; a.gB1 = gf.gB1; a.gA2 = gf.gA2; a.gB2 = gf.gB2;
       }
       RegressArgs &r = rg_[s - 1];
-      r.logits = T("logits" + std::to_string(s)).d;
-      r.depth = T("depth" + std::to_string(s)).d;
-      r.conf = T("conf" + std::to_string(s)).d;
+      r.logits = T("logits" + S).d;
+      r.depth = T("depth" + S).d;
+      r.conf = T("conf" + S).d;
       r.planes = p; r.h = h; r.w = w;
     }
     for (int s = 0; s < 3; ++s) set_batch_vfeat(s);
     if (fcache_cap_ > 0) plan_cache_use(H, W, V, bgrs, order);
-    // quantile rank, computed in float32 like module.py:1348-1349
-    const float hw = (float)(H * W);
-    float cut = hw * (100.f - disc);
-    cut = cut / 100.f;
-    long long ci = (long long)cut;
-    if (ci < 0) ci = 0;
-    if (ci > (long long)H * W - 1) ci = (long long)H * W - 1;
-    filter_rank_ = (unsigned)ci;
+    filter_rank_ = geo.filter_rank;
     prelaunched_ = false;
     // PRELAUNCH (CallAsync with the feature cache answering the window): the device needs ONE image -- the new one -- to start; the other six are only compared
     // with their cache entries, which can happen last.  So the new image goes up first, the helper thread stages and uploads the rest on a second stream, and
     // THIS thread enqueues the whole forward meanwhile; the comparison (k_cache_io) is enqueued behind it once the uploads are in flight.  The device starts
     // ~0.3 ms earlier in TandemBackend's loop (it idles while a window is staged); the call still returns only when every image has been copied.
-    if (may_prelaunch && fc_fast_ && up_stream_) {
+    if (may_prelaunch && fc_.fast && up_stream_) {
       auto up_one = [&, pinned](int v, hipStream_t st) {
         const uint8_t *src = bgrs[order[v]];
         if (!pinned) { memcpy(h_in_ + v * img_bytes, src, img_bytes); src = h_in_ + v * img_bytes; }
         DR_HIP(hipMemcpyAsync(d_bgr_ + v * img_bytes, src, img_bytes, hipMemcpyHostToDevice, st));
       };
-      const int miss = fc_miss_;
+      const int miss = fc_.miss;
       if (miss >= 0) {
         up_one(miss, stream_);
         if (pinned) {  // (read in place from the caller's page-locked image: waited for before the call returns)
@@ -1438,7 +1114,7 @@ class MvsEngine {
       } catch (...) { defer_cache_io_ = false; copier_.wait_quiet(); throw; }
       copier_.wait();
       DR_HIP(hipStreamWaitEvent(stream_, ev_hits_, 0));
-      launch_cache_io();
+      enqueue_cache_io();
       if (pinned) {  // uploaded in place from the caller's page-locked images: they must have been read before the call returns
         DR_HIP(hipEventSynchronize(ev_hits_));
         if (miss >= 0) DR_HIP(hipEventSynchronize(ev_h2d_));
@@ -1479,11 +1155,11 @@ class MvsEngine {
   // regularisation, whose coarse UNet levels leave most CUs idle; stage 2 / 3's cost volume waits for feat2 / feat3.
   // The next forward's main-stream work is ordered after those waits, so the side stream never runs ahead of a reader.
   void forward(std::vector<hipEvent_t> *ev, size_t first = 0, size_t last = ~(size_t)0) {
-    if ((fc_fast_ || fc_fill_) && !(first == 0 && last >= ops_.size())) {  // a partial forward (phases, one op) cannot skip FeatureNet: the window goes back to the batch path
-      fc_fast_ = fc_fill_ = false;
+    if ((fc_.fast || fc_.fill) && !(first == 0 && last >= ops_.size())) {  // a partial forward (phases, one op) cannot skip FeatureNet: the window goes back to the batch path
+      fc_.fast = fc_.fill = false;
       for (int s = 0; s < 3; ++s) set_batch_vfeat(s);
     }
-    const bool cached = fc_fast_;  // FeatureNet answered by the feature cache: its ops are skipped
+    const bool cached = fc_.fast;  // FeatureNet answered by the feature cache: its ops are skipped
     // ... unless other engines of this process have windows in flight on the device: their kernels already fill the idle CUs, and a second stream per
     // engine only adds queue contention (4 engines: 580 depth maps/s without the fork against 570 with it, profiles/r06_queues_side_stream.txt; alone: 2.150 ms
     // with it against 2.165).  Same kernels in the same per-stream order either way: the result does not depend on it.
@@ -1493,7 +1169,6 @@ class MvsEngine {
     // view shard, reduce-to-root form: between a stage's cost volume and its regression only rank 0 works
     const bool rooted = comm_ && shard_nsrc_ && !phase_mode_ && !sw_.shard_allreduce;
     bool idle_stage = false;
-    for (bool &f : regress_done_) f = false;  // (a PROB op and the REGRESS op it may answer for always lie in the same call; nothing is carried over from a call that threw)
     size_t i = 0;
     for (const Op &o : ops_) {
       if (ev) DR_HIP(hipEventRecord((*ev)[i], stream_));
@@ -1505,239 +1180,67 @@ class MvsEngine {
       if (fork && i - 1 == fork_lo_) { DR_HIP(hipEventRecord(ev_fork_, stream_)); DR_HIP(hipStreamWaitEvent(side_, ev_fork_, 0)); }
       if (fork && o.kind == Op::COSTVOL && o.stage == 2) DR_HIP(hipStreamWaitEvent(stream_, ev_feat2_, 0));
       if (fork && o.kind == Op::COSTVOL && o.stage == 3) DR_HIP(hipStreamWaitEvent(stream_, ev_feat3_, 0));
-      hipStream_t stream_ = on_side ? side_ : this->stream_;  // shadows the member for the launches below
+      const hipStream_t st = on_side ? side_ : stream_;
       switch (o.kind) {
-        case Op::PREPROCESS: {
-          const size_t npix = (size_t)V_ * H_ * W_;
-          hipLaunchKernelGGL(k_preprocess, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream_, d_bgr_,
-                             reinterpret_cast<float4 *>(T("image").d), lut_, npix);
-          break;
-        }
-        case Op::CONV:
-          launch_conv(o.conv, stream_);
-          break;
-        case Op::BORDERFIX: {
-          const int per = 2 * (o.d1 + o.d2) - 4, n = o.d0 * per * 8;
-          const int rs = (o.d2 + 2 * o.stage) * 8;
-          hipLaunchKernelGGL(k_out3_border, dim3(cdiv(n, 256)), dim3(256), 0, stream_, o.p2, o.p1, o.d0, o.d1, o.d2, rs, (size_t)(o.d1 + 2 * o.stage) * rs);
-          break;
-        }
-        case Op::SKIPUP: {
-#ifdef DR_PARITY_HOOKS
-          const size_t npix = (size_t)o.d0 * o.d1 * o.d2;
-          const dim3 grid((unsigned)std::min<size_t>((npix + 31) / 32, 8192));
-          hipLaunchKernelGGL(k_skip_up<8>, grid, dim3(256), 0, stream_, o.p0, o.p1, o.p3, o.p4, o.p2, o.d0, o.d1, o.d2);
-#endif
-          break;
-        }
-        case Op::PROB: {
-          // z-march chunk: long chunks amortise the 2 halo planes, but the launch needs ~1000 waves to fill the chip
-          // (round-2 sweep: 48x120x160 -> 4, 32x240x320 -> 8, 8x480x640 -> 8)
-#ifdef DR_PARITY_HOOKS
-          if (sw_.prob_v1) {  // round 2's L1-gather kernel: one output column per lane (r2 sweep: 4x the waves beats the 4-column variant)
-            int zchunk = std::min(o.d0, 8);
-            while (zchunk > 2 && cdiv(o.d1 * (o.d2 / 4), 64) * cdiv(o.d0, zchunk) < 800) zchunk /= 2;
-            if (sw_.prob_zchunk > 0) zchunk = std::min(o.d0, sw_.prob_zchunk);
-            const int pb = sw_.prob_block, xo = sw_.prob_xo == 2 ? 2 : (sw_.prob_xo == 4 ? 4 : 1);
-            dim3 grid(cdiv(o.d1 * (o.d2 / xo), pb), cdiv(o.d0, zchunk));
-            int gz = 0, nwg = 0;
-            if (!sw_.prob_launch_order) {  // XCD-band workgroup order (A/B hook: the plain 2-D launch order)
-              gz = (int)grid.y; nwg = (int)(grid.x * grid.y);
-              grid = dim3(8 * cdiv(nwg, 8));
-            }
-            if (xo == 4) hipLaunchKernelGGL(k_prob<4>, grid, dim3(pb), 0, stream_, o.p0, o.p1, o.p2, o.d0, o.d1, o.d2, zchunk, gz, nwg);
-            else if (xo == 2) hipLaunchKernelGGL(k_prob<2>, grid, dim3(pb), 0, stream_, o.p0, o.p1, o.p2, o.d0, o.d1, o.d2, zchunk, gz, nwg);
-            else hipLaunchKernelGGL(k_prob<1>, grid, dim3(pb), 0, stream_, o.p0, o.p1, o.p2, o.d0, o.d1, o.d2, zchunk, gz, nwg);
-            break;
-          }
-#endif
-          // LDS-staged plane tiles (k_prob2<NR>: NR rows per lane, tile 4 NR x 64)
-          const int NR = sw_.prob_rows == 2 || sw_.prob_rows == 4 ? sw_.prob_rows : 1;  // (measured: 0.028 / 0.044 / 0.084 ms at stage 2 for 1 / 2 / 4 rows per lane -- fewer, fatter workgroups lose more than the shared reads win)
-          const int tyr = kProbTY * NR;
-          int zc = std::min(o.d0, 8);
-          while (zc > 2 && cdiv(o.d1, tyr) * cdiv(o.d2, kProbTX) * cdiv(o.d0, zc) < (NR == 1 ? 1024 : 512)) zc /= 2;  // enough workgroups for every CU's LDS
-          if (sw_.prob_zchunk > 0) zc = std::min(o.d0, sw_.prob_zchunk);
-          const int gxp = cdiv(o.d2, kProbTX), gyp = cdiv(o.d1, tyr), gzp = cdiv(o.d0, zc), nw = gxp * gyp * gzp;
-          const size_t pl = prob2_lds_bytes(NR);
-          if (NR == 4) {
-            static std::atomic<int> big{0};
-            if (!big.load()) { DR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_prob2<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); big.store(1); }
-            hipLaunchKernelGGL(k_prob2<4>, dim3(8 * cdiv(nw, 8)), dim3(256), pl, stream_, o.p0, o.p1, o.p2, o.d0, o.d1, o.d2, zc, gxp, gyp, gzp, nw);
-          } else if (NR == 2) hipLaunchKernelGGL(k_prob2<2>, dim3(8 * cdiv(nw, 8)), dim3(256), pl, stream_, o.p0, o.p1, o.p2, o.d0, o.d1, o.d2, zc, gxp, gyp, gzp, nw);
-          else if (sw_.prob_regress && gzp == 1 && o.d0 == 8 && o.stage >= 1 && o.stage <= 3 && !sw_.regress_generic && !idle_stage) {
-            // all planes are one depth chunk: the regression follows in the lane that produced the logits (k_prob2_regress); the REGRESS op of this stage then has nothing to launch
-            hipLaunchKernelGGL(k_prob2_regress<8>, dim3(8 * cdiv(nw, 8)), dim3(256), pl, stream_, o.p0, o.p1, o.p2, o.d1, o.d2, gxp, gyp, nw, rg_[o.stage - 1]);
-            regress_done_[o.stage - 1] = true; prob_fused_last_[o.stage - 1] = true;
-          } else {
-            hipLaunchKernelGGL(k_prob2<1>, dim3(8 * cdiv(nw, 8)), dim3(256), pl, stream_, o.p0, o.p1, o.p2, o.d0, o.d1, o.d2, zc, gxp, gyp, gzp, nw);
-            if (o.stage >= 1 && o.stage <= 3) prob_fused_last_[o.stage - 1] = false;
-          }
-          break;
-        }
-        case Op::TAIL:
-#ifdef DR_PARITY_HOOKS
-          launch_tail(o.tail, stream_);
-#endif
-          break;
-        case Op::FRONT:
-          launch_fn_front(o.front, stream_);
-          break;
-        case Op::HEAD3:
-          launch_fn_head3(o.head3, stream_);
-          break;
+        case Op::PREPROCESS: launch_preprocess(o.pre, st); break;
+        case Op::CONV: launch_conv(o.conv, st); break;
+        case Op::BORDERFIX: launch_out3_border(o.p2, o.p1, o.d0, o.d1, o.d2, o.stage, st); break;
+        case Op::SKIPUP: launch_skip_up(o.p0, o.p1, o.p3, o.p4, o.p2, o.d0, o.d1, o.d2, st); break;
+        case Op::PROB: launch_prob(pr_[o.stage - 1], rg_[o.stage - 1], sw_, o.stage, st); break;
+        case Op::TAIL: launch_tail_op(o, st); break;
+        case Op::FRONT: launch_fn_front(o.front, st); break;
+        case Op::HEAD3: launch_fn_head3(o.head3, st); break;
         case Op::COSTVOL: {
           const CostVolArgs &a = cv_[o.stage - 1];
-          const int C = 32 >> (o.stage - 1);
-          if (a.V - 1 <= 0) {  // a view-shard rank that holds the reference view only: its partial volume is the empty sum (the kernels return without storing)
-            const DevTensor &vol0 = T("volume" + std::to_string(o.stage));
-            DR_HIP(hipMemsetAsync(vol0.d, 0, vol0.n() * 4, stream_));
-          }
-          CostVolArgs b = a;
-          b.gz = cdiv(a.planes.D, a.dchunk);
-          b.abl = sw_.cv5_abl;
-#ifdef DR_PARITY_HOOKS
-          if (!a.fpad) {  // DR_COSTVOL_V1: round 2's kernel on unpadded feature maps; channels per lane 4 (fewest L1 line accesses per byte) or 8
-            const int cpl = C >= 16 ? sw_.costvol_cpl : 4, pxb = 256 / (C / cpl);
-            b.gx = cdiv(a.w, pxb); b.nwg = b.gx * b.gz * a.h;
-            const dim3 grid1(8 * cdiv(b.nwg, 8));
-            if (C == 32 && cpl == 8) hipLaunchKernelGGL((k_costvol<32, 8>), grid1, dim3(256), 0, stream_, b);
-            else if (C == 32) hipLaunchKernelGGL((k_costvol<32, 4>), grid1, dim3(256), 0, stream_, b);
-            else if (C == 16 && cpl == 8) hipLaunchKernelGGL((k_costvol<16, 8>), grid1, dim3(256), 0, stream_, b);
-            else if (C == 16) hipLaunchKernelGGL((k_costvol<16, 4>), grid1, dim3(256), 0, stream_, b);
-            else hipLaunchKernelGGL((k_costvol<8, 4>), grid1, dim3(256), 0, stream_, b);
-          } else
-#endif
-          {  // bordered feature maps: 4 channels per lane, no per-tap validity logic
-            b.gx = cdiv(a.w, 1024 / C); b.nwg = b.gx * b.gz * a.h;
-            const dim3 grid(8 * cdiv(b.nwg, 8));
-#ifdef DR_PARITY_HOOKS  // k_costvol4 (source taps staged through LDS): view-aggregation models, whole pixel tiles, depth chunks of 8 (4 when D = 4)
-            const int dch = a.planes.D >= 8 ? 8 : 4;
-            const int tw = C == 8 ? 16 : 8, th = (1024 / C) / tw;
-            if (cv4_applies(o.stage)) {
-              CostVolArgs c4 = a;
-              c4.gx = a.w / tw; c4.gz = a.planes.D / dch; c4.nwg = c4.gx * (a.h / th) * c4.gz;
-              const dim3 g4(8 * cdiv(c4.nwg, 8));
-              // planes per step: 8 where neighbouring planes move a sample by a fraction of a pixel (the box hardly grows), else 4
-              const bool sp8 = dch == 8 && C != 32 && ((sw_.cv4_sp8 >> (o.stage - 1)) & 1);
-              if (C == 32 && dch == 8) hipLaunchKernelGGL((k_costvol4<32, 8, 4>), g4, dim3(256), 0, stream_, c4);
-              else if (C == 32) hipLaunchKernelGGL((k_costvol4<32, 4, 4>), g4, dim3(256), 0, stream_, c4);
-              else if (C == 16 && sp8) hipLaunchKernelGGL((k_costvol4<16, 8, 8>), g4, dim3(256), 0, stream_, c4);
-              else if (C == 16 && dch == 8) hipLaunchKernelGGL((k_costvol4<16, 8, 4>), g4, dim3(256), 0, stream_, c4);
-              else if (C == 16) hipLaunchKernelGGL((k_costvol4<16, 4, 4>), g4, dim3(256), 0, stream_, c4);
-              else if (sp8) hipLaunchKernelGGL((k_costvol4<8, 8, 8>), g4, dim3(256), 0, stream_, c4);
-              else if (dch == 8) hipLaunchKernelGGL((k_costvol4<8, 8, 4>), g4, dim3(256), 0, stream_, c4);
-              else hipLaunchKernelGGL((k_costvol4<8, 4, 4>), g4, dim3(256), 0, stream_, c4);
-            } else
-#endif
-            if (cv5_applies(o.stage)) {  // view-outer / plane-inner sweep, the chunk's planes accumulate in registers (bit-identical to k_costvol3)
-              const bool d8 = a.dchunk == 8;
-              CostVolArgs b4 = b;  // the four-row tile: x segments of a quarter of the pixels, four rows per workgroup
-              b4.gx = cdiv(a.w, 256 / C); b4.nwg = b4.gx * b4.gz * cdiv(a.h, 4);
-              const dim3 grid4(8 * cdiv(b4.nwg, 8));
-              [[maybe_unused]] const bool rows4 = sw_.cv5_rows ? sw_.cv5_rows == 4 : true;  // (four-row tiles at every stage since the single-set form: 0.126 -> 0.122 ms at stage 2, stage 1 unchanged)
-#ifdef DR_PARITY_HOOKS
-#define DR_CV5(CC, DD) do { if (!sw_.cv5_reuse) hipLaunchKernelGGL((k_costvol5<CC, DD, 0, 1>), grid, dim3(256), 0, stream_, b); \
-                            else if (rows4) hipLaunchKernelGGL((k_costvol5<CC, DD, 1, 4>), grid4, dim3(256), 0, stream_, b4); \
-                            else hipLaunchKernelGGL((k_costvol5<CC, DD, 1, 1>), grid, dim3(256), 0, stream_, b); } while (0)
-#else
-#define DR_CV5(CC, DD) hipLaunchKernelGGL((k_costvol5<CC, DD, 1, 4>), grid4, dim3(256), 0, stream_, b4)
-#endif
-              if (C == 32 && d8) DR_CV5(32, 8);
-              else if (C == 32) DR_CV5(32, 4);
-              else if (C == 16 && d8) DR_CV5(16, 8);
-              else if (C == 16) DR_CV5(16, 4);
-              else if (d8) DR_CV5(8, 8);
-              else DR_CV5(8, 4);
-#undef DR_CV5
-            } else {
-            // k_costvol3 (the lanes of a pixel share the per-sample set-up) needs whole batches of 4 iterations per depth chunk
-            const bool v3 = !sw_.costvol_v2 && a.dchunk % 4 == 0 && a.planes.D % 4 == 0;
-            if (v3 && C == 32) hipLaunchKernelGGL((k_costvol3<32>), grid, dim3(256), 0, stream_, b);
-            else if (v3 && C == 16) hipLaunchKernelGGL((k_costvol3<16>), grid, dim3(256), 0, stream_, b);
-            else if (v3) hipLaunchKernelGGL((k_costvol3<8>), grid, dim3(256), 0, stream_, b);
-            else if (C == 32) hipLaunchKernelGGL((k_costvol2<32>), grid, dim3(256), 0, stream_, b);
-            else if (C == 16) hipLaunchKernelGGL((k_costvol2<16>), grid, dim3(256), 0, stream_, b);
-            else hipLaunchKernelGGL((k_costvol2<8>), grid, dim3(256), 0, stream_, b);
-            }
-          }
+          // a view-shard rank that holds the reference view only: its partial volume is the empty sum (the kernels return without storing)
+          if (a.V - 1 <= 0) { const DevTensor &vol = T("volume" + std::to_string(o.stage)); DR_HIP(hipMemsetAsync(vol.d, 0, vol.n() * 4, st)); }
+          launch_costvol(a, sw_, o.stage, st);
           if (comm_ && shard_nsrc_ && !phase_mode_) {  // view shard: sum the partial volumes of all ranks, in place, in stream order
             const DevTensor &vol = T("volume" + std::to_string(o.stage));
             Rccl &r = Rccl::get();
             if (rooted) {
-              r.check(r.Reduce(vol.d, vol.d, vol.n(), ncclFloat, ncclSum, 0, comm_, stream_), "ncclReduce");
+              r.check(r.Reduce(vol.d, vol.d, vol.n(), ncclFloat, ncclSum, 0, comm_, st), "ncclReduce");
               idle_stage = comm_rank_ != 0;
-            } else r.check(r.AllReduce(vol.d, vol.d, vol.n(), ncclFloat, ncclSum, comm_, stream_), "ncclAllReduce");
+            } else r.check(r.AllReduce(vol.d, vol.d, vol.n(), ncclFloat, ncclSum, comm_, st), "ncclAllReduce");
           }
           break;
         }
         case Op::REGRESS: {
-          const RegressArgs &r = rg_[o.stage - 1];
-          const bool done = regress_done_[o.stage - 1];  // (k_prob2_regress did it)
-          regress_done_[o.stage - 1] = false;
-          if (!idle_stage && !done) {
-            const dim3 grid(cdiv(r.h * r.w, 256)), block(256);
-            const int D = sw_.regress_generic ? 0 : r.planes.D;  // DR_REGRESS_GENERIC=1: the three-pass kernel for every plane count (A/B and parity hook)
-            if (D == 48) hipLaunchKernelGGL(k_regress_r<48>, grid, block, 0, stream_, r);
-            else if (D == 32) hipLaunchKernelGGL(k_regress_r<32>, grid, block, 0, stream_, r);
-            else if (D == 8) hipLaunchKernelGGL(k_regress_r<8>, grid, block, 0, stream_, r);
-            else if (D == 4) hipLaunchKernelGGL(k_regress_r<4>, grid, block, 0, stream_, r);
-            else hipLaunchKernelGGL(k_regress, grid, block, 0, stream_, r);
-          }
+          // (where the stage's PROB op ran k_prob2_regress, the regression is done: the same choice function says so here and there)
+          const ProbArgs &pr = pr_[o.stage - 1];
+          const bool done = pr.x && choose_prob(prob_shape(pr), sw_, o.stage).regresses();
+          if (!idle_stage && !done) launch_regress(rg_[o.stage - 1], sw_, st);
           if (rooted) {  // the stage's depth map goes back to every rank: stage s + 1 centres its hypotheses on it; stage 3's
             Rccl &c = Rccl::get();  // depth and confidence are the result (the edge filter then runs on every rank: 0.08 ms)
             const DevTensor &dep = T("depth" + std::to_string(o.stage));
-            c.check(c.Broadcast(dep.d, dep.d, dep.n(), ncclFloat, 0, comm_, stream_), "ncclBroadcast");
+            c.check(c.Broadcast(dep.d, dep.d, dep.n(), ncclFloat, 0, comm_, st), "ncclBroadcast");
             if (o.stage == 3) {
               const DevTensor &cf = T("conf3");
-              c.check(c.Broadcast(cf.d, cf.d, cf.n(), ncclFloat, 0, comm_, stream_), "ncclBroadcast");
+              c.check(c.Broadcast(cf.d, cf.d, cf.n(), ncclFloat, 0, comm_, st), "ncclBroadcast");
             }
             idle_stage = false;
           }
           break;
         }
-        case Op::EDGE:
-          if (sw_.filter_fused) hipLaunchKernelGGL(k_edge2, dim3(cdiv(H_ * W_, 256)), dim3(256), 0, stream_, T("depth3").d, T("edge").d, H_, W_, d_state_, d_hist_, filter_rank_);
-          else hipLaunchKernelGGL(k_edge, dim3(cdiv(H_ * W_, 256)), dim3(256), 0, stream_, T("depth3").d, T("edge").d, H_, W_, d_state_, filter_rank_);
-          break;
-        case Op::HIST:
-          if (sw_.filter_fused && o.stage > 0)
-            hipLaunchKernelGGL(k_hist_s, dim3(std::min(cdiv(H_ * W_, 256), sw_.hist_blocks)), dim3(256), 0, stream_, T("edge").d, H_ * W_, o.d0, o.d1, o.shift, o.bits, o.stage,
-                               d_state_, d_hist_);
-          else hipLaunchKernelGGL(k_hist, dim3(std::min(cdiv(H_ * W_, 256), sw_.hist_blocks)), dim3(256), 0, stream_, T("edge").d, H_ * W_, o.shift, o.bits, d_state_, d_hist_);
-          break;
-        case Op::SCAN:
-          hipLaunchKernelGGL(k_scan, dim3(1), dim3(256), 0, stream_, d_state_, d_hist_, o.shift, o.bits);
-          break;
-        case Op::APPLY:
-          if (sw_.filter_fused)
-            hipLaunchKernelGGL(k_apply_s, dim3(cdiv(H_ * W_, 256)), dim3(256), 0, stream_, T("edge").d, d_state_, d_hist_, o.shift, o.bits, T("depth3").d, T("conf3").d,
-                               T("depth").d, T("confidence").d, H_ * W_);
-          else hipLaunchKernelGGL(k_apply, dim3(cdiv(H_ * W_, 256)), dim3(256), 0, stream_, T("edge").d, d_state_, T("depth3").d, T("conf3").d,
-                                  T("depth").d, T("confidence").d, H_ * W_);
-          break;
+        case Op::EDGE: launch_edge(filt_, filter_rank_, st); break;
+        case Op::HIST: launch_hist(filt_, o.stage, o.d0, o.d1, o.shift, o.bits, st); break;
+        case Op::SCAN: launch_scan(filt_, o.shift, o.bits, st); break;
+        case Op::APPLY: launch_apply(filt_, o.shift, o.bits, st); break;
       }
       // the side stream's results are published after whichever op ends them (fn.out2; the LAST op of the fork range: a
       // convolution in the fused-skip form, the border kernel in the folded form) -- independent of the op kind
       if (on_side && i - 1 == feat2_op_) DR_HIP(hipEventRecord(ev_feat2_, side_));
       if (on_side && i - 1 == fork_hi_ - 1) DR_HIP(hipEventRecord(ev_feat3_, side_));
     }
-    if (fc_fill_ && first == 0 && last >= ops_.size()) fill_cache_from_batch();
+    if (fc_.fill && first == 0 && last >= ops_.size()) fill_cache_from_batch();
     if (ev) DR_HIP(hipEventRecord((*ev)[i], stream_));
     DR_HIP(hipGetLastError());
   }
 
-  // k_costvol5 (view-outer / plane-inner sweep): view-aggregation models, bordered feature maps, depth chunks of exactly 4 or 8 planes
-  bool cv5_applies(int stage) const {
-    const CostVolArgs &a = cv_[stage - 1];
-    return !sw_.costvol_v1 && !sw_.costvol_v2 && !sw_.costvol_v3 && a.fpad && a.view_aggregation && a.V > 1 && (a.dchunk == 4 || a.dchunk == 8) &&
-           a.planes.D % a.dchunk == 0;
-  }
-  // k_costvol4 (taps staged through LDS): view-aggregation models, bordered feature maps, whole pixel tiles, whole depth chunks
-  bool cv4_applies(int stage) const {
-    const CostVolArgs &a = cv_[stage - 1];
-    const int C = 32 >> (stage - 1), tw = C == 8 ? 16 : 8, th = (1024 / C) / tw, dch = a.planes.D >= 8 ? 8 : 4;
-    return !sw_.costvol_v1 && !sw_.costvol_v2 && !sw_.costvol_v3 && ((sw_.cv4_stages >> (stage - 1)) & 1) && a.fpad && a.view_aggregation && a.V > 1 &&
-           a.w % tw == 0 && a.h % th == 0 && a.planes.D % dch == 0;
+  void launch_tail_op([[maybe_unused]] const Op &o, [[maybe_unused]] hipStream_t st) {
+#ifdef DR_PARITY_HOOKS
+    launch_tail(o.tail, st);
+#endif  // (the product plans no TAIL op)
   }
   hipStream_t side_ = nullptr;
   hipEvent_t ev_fork_ = nullptr, ev_feat2_ = nullptr, ev_feat3_ = nullptr;
@@ -1745,19 +1248,17 @@ class MvsEngine {
   size_t fork_lo_ = 0, fork_hi_ = 0, feat2_op_ = 0;  // ops [fork_lo_, fork_hi_) = fn.skip2 .. fn.out3
   // key-frame feature cache (build_fn1 .. set_batch_vfeat)
   int fcache_cap_ = 0;             // entries (0: off, the default)
-  std::vector<FcEntry> fcache_;
+  std::vector<FcBuffers> fcache_;  // the entries' device buffers, parallel to the index
+  FeatureIndex fc_;                // which entry answers which view of the staged window; LRU; counters (mvs_host.h)
   std::vector<Op> ops1_;           // FeatureNet for ONE view
   std::vector<FnOut> fn1_out_;
   std::string tprefix_;            // tensor-name prefix while ops1_ is built
   bool fn1_ok_ = false;            // the single-view plan exists and matches the batch plan's instances
-  bool fc_fast_ = false, fc_fill_ = false;  // the staged window: answered by the cache (at most one view computed) / computed as a batch whose outputs fill the cache
-  int fc_miss_ = -1, fc_slot_[kMaxSrc + 1] = {};
   int *fc_flag_ = nullptr;         // page-locked: raised by k_cache_io
   hipStream_t up_stream_ = nullptr;  // uploads of the images the cache answers (prelaunch, stage_inputs)
   hipEvent_t ev_hits_ = nullptr;
   bool prelaunched_ = false;       // the staged window's forward is already on the stream (the worker only publishes)
   bool defer_cache_io_ = false;    // ... and its image comparison follows once the uploads are in flight
-  uint64_t fc_clock_ = 0, fc_hits_ = 0, fc_misses_ = 0, fc_batch_windows_ = 0, fc_collisions_ = 0;
 
   const MvsSwitches sw_;  // read once, here
 #ifdef DR_PARITY_HOOKS
@@ -1781,14 +1282,14 @@ class MvsEngine {
   std::vector<void *> misc_;
   CostVolArgs cv_[3];
   RegressArgs rg_[3];
+  ProbArgs pr_[3];    // per stage; x == nullptr where the plan has no PROB op
+  FilterArgs filt_{};
   uint8_t *d_bgr_ = nullptr, *h_in_ = nullptr;
   float *h_out_[2] = {nullptr, nullptr}, *h_out_dev_[2] = {nullptr, nullptr};  // two pinned result blocks (4 maps each), used alternately, and the addresses the device uses for them
   int out_cur_ = 0;                // the block the last result is in
   hipEvent_t ev_h2d_ = nullptr;    // completion of a window uploaded straight from the caller's page-locked images
   unsigned *d_state_ = nullptr, *d_hist_ = nullptr;
   unsigned filter_rank_ = 0;
-  bool prob_fused_last_[3] = {false, false, false};  // (reporting: the last forward ran this stage's prob as k_prob2_regress)
-  bool regress_done_[3] = {false, false, false};  // set by a PROB op that also ran its stage's regression, consumed by the REGRESS op behind it
   int H_ = 0, W_ = 0, V_ = 0;
   int shard_nsrc_ = 0;  // > 0: view-shard rank, cost-volume divisor = source views of the whole window
   ncclComm_t comm_ = nullptr;  // view-shard communicator (drm_comm_init); the volumes are reduced in stream order when set
@@ -1959,7 +1460,7 @@ int drm_debug_conv(int device, const float *in, int D, int H, int W, int Cin, co
     if (march_err) fail(DR_ERR_DEVICE, "k_conv_m: a ring wait gave up (code %d)", march_err);
     if (getenv("DR_CONV_PRINT")) {
       const ConvLaunch &c = P.launches.at(0);
-      fprintf(stderr, "debug_conv: %s<%d,%d,%d> nup %d tile %dx%dx%d lds %zu grid %ux%u (%d candidates)%s\n", (c.async == 2 ? (c.march.rm ? "rowmarch" : (c.march.wino ? "winomarch" : "march")) : (c.async == 4 ? "wino" : (c.async ? "async" : (c.bf3 ? "bf16x3" : "sync")))), c.ci, c.ct, c.pt,
+      fprintf(stderr, "debug_conv: %s<%d,%d,%d> nup %d tile %dx%dx%d lds %zu grid %ux%u (%d candidates)%s\n", *conv_kind_name(c) ? conv_kind_name(c) : (c.bf3 ? "bf16x3" : "sync"), c.ci, c.ct, c.pt,
               c.nup, c.args.TZ, c.args.TY, c.args.TXT * 16, c.lds_bytes, c.grid.x, c.grid.z, P.ncand, c.args.class_loop ? ", class loop" : "");
     }
     DR_HIP(hipMemcpy(out, d_out, on * 4, hipMemcpyDeviceToHost));
@@ -1994,9 +1495,7 @@ int drm_debug_tail(int device, const float *x, const float *skip, const float *w
     t.out = d_out; t.D = D; t.h = h; t.w = w;
     const bool mf = form == 1;  // 1: k_tail_m (matrix pipe), else k_tail (vector pipe)
     t.wmf = mf ? arena.upload(tail_pack_deconv_mfma(w_deconv)) : nullptr;
-    tail_pick_tile(h, w, t.QY, t.QX, mf);
-    if (qy == 4 || qy == 8 || qy == 16 || (qy == 32 && !mf)) { t.QY = qy; t.QX = 256 / qy; }
-    t.zchunk = zchunk > 0 ? std::min(D, zchunk) : tail_pick_zchunk(D, h, w, t.QY, t.QX);
+    tail_set_tile(t, qy, zchunk, mf);
     launch_tail(t, nullptr);
     DR_HIP(hipDeviceSynchronize());
     DR_HIP(hipGetLastError());

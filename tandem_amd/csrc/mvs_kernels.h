@@ -16,10 +16,9 @@
 #include <utility>
 
 #include "dr_common.h"
+#include "mvs_host.h"  // kMaxSrc, kProbTY / kProbTX: constants the host half shares with the kernels
 
 namespace dr {
-
-constexpr int kMaxSrc = 7;  // view_num <= 8
 
 // ------------------------------------------------------------------ pre-processing
 // lut[b] = float(double(float(b)) / 255.0)  (the reference divides in double, dr_mvsnet.cpp:212-214)
@@ -981,7 +980,7 @@ __global__ __launch_bounds__(256) void k_prob(const float *__restrict__ x, const
 // plane is being consumed, registers -> the other LDS buffer afterwards, one barrier per plane -- and serves the nine
 // taps of all 256 lanes and the three output planes it contributes to.  The products are k_prob's; they are summed in two
 // interleaved chains (even and odd channels) instead of one.
-constexpr int kProbTY = 4, kProbTX = 64, kProbPos = (kProbTY + 2) * (kProbTX + 2);  // 396 staged positions per plane (NR = 1)
+constexpr int kProbPos = (kProbTY + 2) * (kProbTX + 2);  // 396 staged positions per plane (NR = 1)
 // NR (round 5): rows per lane.  A lane that owns NR vertically adjacent logits reads the NR + 2 rows around them once (9 LDS reads per logit at NR = 4
 // against 18), the 24 wave-uniform weights of a tap are fetched once for all of them (the scalar loads and their s_waitcnt were what the NR = 1 kernel waited
 // for: 20 waits per 108 packed FMAs), and the tile's halo shrinks from 1.55 to 1.16 of its interior.  Per logit the products and their order are unchanged:

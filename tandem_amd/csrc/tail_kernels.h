@@ -474,6 +474,12 @@ inline int tail_pick_zchunk(int D, int h, int w, int QY, int QX) {
   while (zc > 4 && tiles * cdiv(D, zc) < 400) zc = (zc + 1) / 2;
   return zc;
 }
+// the tile and the z chunk of a launch whose D, h, w are set: chosen by size unless asked for (qy: quad rows 4, 8, 16, 32; zchunk > 0)
+inline void tail_set_tile(TailArgs &t, int qy, int zchunk, bool mfma) {
+  tail_pick_tile(t.h, t.w, t.QY, t.QX, mfma);
+  if (qy == 4 || qy == 8 || qy == 16 || (qy == 32 && !mfma)) { t.QY = qy; t.QX = 256 / qy; }
+  t.zchunk = zchunk > 0 ? std::min(t.D, zchunk) : tail_pick_zchunk(t.D, t.h, t.w, t.QY, t.QX);
+}
 
 inline void launch_tail(TailArgs a, hipStream_t st) {
   const int TY = 2 * a.QY - 4, TX = 2 * a.QX - 4;

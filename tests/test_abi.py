@@ -84,7 +84,7 @@ def test_product_path_never_imports_the_oracle():
 
 def test_product_library_reads_only_the_documented_switches():
     """every DR_* name the PRODUCT library can pass to getenv is one of the sixteen INTEGRATION.md lists; the superseded
-    generations and settled A/Bs are read through hook_env() (csrc/dr_common.h), i.e. by the parity build only, and their kernels
+    generations and settled A/Bs are read through hook_env() (csrc/dr_host.h), i.e. by the parity build only, and their kernels
     (k_tail, k_tail_m, k_conv_b, k_costvol / k_costvol4, ...) are not in the product's code object at all."""
     import subprocess
     lib = os.path.join(ROOT, "tandem_amd", "libdr_mi355x.so")
