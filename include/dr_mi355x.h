@@ -376,6 +376,42 @@ int drf_save_map(drf_t *h, const char *path, size_t chunk_blocks);
  * update full, does not count as streamed in or out in drf_streaming_stats, and leaves the update counters of drf_stats at
  * zero ([0] reports the pool as always). */
 int drf_load_map(drf_t *h, const char *path, size_t chunk_blocks);
+/* Merges a map file into the map the engine holds, voxel by voxel (DESIGN.md §7c "Merging a map file"): two maps of the same
+ * world -- same voxel_size, same world frame -- become one.  The rule:
+ *   blocks  the merged map holds the union of the two block sets.  A file block whose key the map does not hold is placed
+ *           verbatim, 4096 bytes unchanged, exactly as drf_load_map places it; one whose key the map holds is combined with the
+ *           map's block voxel by voxel, index by index.
+ *   voxels  a = the map's voxel, b = the file's, W = (unsigned char)max_sdf_weight, fp32 without contraction:
+ *           1. b.weight == 0: a stays as it is, all 8 bytes.
+ *           2. otherwise, a.weight == 0: a.sdf = b.sdf, a.colour = b.colour, a.weight = min(b.weight, W).
+ *           3. otherwise, with wa = (float)a.weight, wb = (float)b.weight: each colour channel becomes
+ *              (unsigned char)(((float)a.c * wa + (float)b.c * wb) / (wa + wb)), a.sdf = (a.sdf * wa + b.sdf * wb) / (wa + wb),
+ *              a.weight = min((int)a.weight + (int)b.weight, (int)W).
+ *           Case 3 is the reference's Voxel::Combine, except that the weight sum is formed in int (two unsigned chars would wrap
+ *           above 255; integration adds 1 at a time and never gets there, a merge can).  Cases 1 and 2 keep 0/0 out of the map and
+ *           make an absent block and an allocated block that was never updated behave the same.
+ * Legal where drf_integrate_scan_async is (otherwise DR_ERR_PROTOCOL); a null argument is DR_ERR_ARG.  Folds pending evictions
+ * first.  The whole file is validated before anything changes (DR_ERR_IO); a voxel_size whose bits differ from the engine's is
+ * DR_ERR_ARG.  Capacity is decided before anything changes as well -- streaming off: resident blocks + added blocks must not
+ * exceed num_blocks; streaming on: host-store blocks + added blocks must not exceed host_capacity_blocks when that is non-zero --
+ * and DR_ERR_CAPACITY leaves pool, slot order, host store, counters and mesh baseline exactly as they were.
+ * Streaming off: blocks whose key is resident are combined in their pool slots, blocks whose key is in the host store (after
+ * drf_stream_out_region) are combined there, added blocks are appended behind the existing ones in ascending key order; the
+ * order of the existing slots does not change.  Streaming on: resident keys are combined in the pool, stored keys in the host
+ * store, new blocks go into the host store and the next scan brings in what lies within the radius, as after a load.
+ * The merged map is a function of the two maps alone: whatever the pool size, the streaming state and chunk_blocks, engines
+ * that held the same map and merge the same file save the same bytes, and an engine that merged goes on exactly like one that
+ * loaded a file holding the merged map.  Merging into an empty engine is drf_load_map.
+ * Afterwards the next mesh update is full; drf_stats [1] to [3] and the streaming counters do not move; a pending mesh
+ * extraction stays pending and describes the map before the merge; until the next scan drf_render_async is legal wherever
+ * drf_integrate_scan_async is, as after a load.
+ * If the file changes between the validation and the second pass (a read fails or the checksum of what was read differs) the
+ * call returns DR_ERR_IO and the map is a valid MIXTURE: every file block is either fully merged or untouched, drf_merge_stats
+ * says how far it got, and the engine stays usable.  No rollback is attempted: it would need a copy of the map. */
+int drf_merge_map(drf_t *h, const char *path, size_t chunk_blocks);
+/* last drf_merge_map: [0] blocks in the file, [1] blocks added (key was not in the map), [2] blocks combined in the pool,
+ * [3] blocks combined in the host store, [4] voxels of combined blocks taken verbatim (case 2), [5] voxels averaged (case 3) */
+int drf_merge_stats(drf_t *h, uint64_t out[6]);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

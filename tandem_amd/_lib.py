@@ -131,6 +131,8 @@ SIGNATURES = {
     "drf_map_info": (C.c_int, [C.c_char_p, f32p, C.POINTER(C.c_uint64)]),
     "drf_save_map": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
     "drf_load_map": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
+    "drf_merge_map": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
+    "drf_merge_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
 
 

@@ -905,7 +905,7 @@ class FusionEngine {
   }
   // tsdf_volume.cu:634-700
   void render_async(const float *const *poses, int n) {
-    // (a map that was loaded may be rendered before its first scan: drf_load_map)
+    // (a map that was loaded or merged may be rendered before its next scan: drf_load_map, drf_merge_map)
     if (!(loaded_ && next_ == kIntegrate)) expect(kRender, "Please call the functions like IntegrateScanAsync -> RenderAsync -> GetRenderResult.");
     if (n != (int)renders_.size()) fail(DR_ERR_PROTOCOL, "Can only render exactly as many poses as streams. Streams: %zu, Poses: %d.", renders_.size(), n);
     DR_HIP(hipSetDevice(device_));
@@ -1336,20 +1336,7 @@ class FusionEngine {
     settle();
     const int nres = pool_blocks();
     std::vector<unsigned long long> res((size_t)nres);
-    if (nres > 0) {  // the resident order: (blk_key, slot) pairs sorted by key, as mesh_tables sorts the keys
-      std::vector<int> iota((size_t)nres);
-      for (int i = 0; i < nres; ++i) iota[i] = i;
-      mio_keys_.reserve((size_t)nres, int_stream_); mio_slot_in_.reserve((size_t)nres, int_stream_);
-      mio_slot_.reserve((size_t)nres, int_stream_); mio_dst_.reserve((size_t)nres, int_stream_);
-      DR_HIP(hipMemcpy(mio_slot_in_.get(), iota.data(), (size_t)nres * 4, hipMemcpyHostToDevice));
-      size_t tb = 0;
-      DR_HIP(rocprim::radix_sort_pairs(nullptr, tb, d_.blk_key, mio_keys_.get(), mio_slot_in_.get(), mio_slot_.get(), (size_t)nres, 0, 63, int_stream_));
-      mio_tmp_.reserve(std::max<size_t>(tb, 256), int_stream_);  // (never null: a null scratch is rocprim's size query)
-      tb = mio_tmp_.capacity();
-      DR_HIP(rocprim::radix_sort_pairs(mio_tmp_.get(), tb, d_.blk_key, mio_keys_.get(), mio_slot_in_.get(), mio_slot_.get(), (size_t)nres, 0, 63, int_stream_));
-      DR_HIP(hipMemcpyAsync(res.data(), mio_keys_.get(), (size_t)nres * 8, hipMemcpyDeviceToHost, int_stream_));
-      DR_HIP(hipStreamSynchronize(int_stream_));
-    }
+    sort_resident(nres, res);
     const std::vector<unsigned long long> sto = store_.sorted_keys();
     const size_t n = res.size() + sto.size();
     std::vector<unsigned long long> keys;
@@ -1452,6 +1439,93 @@ class FusionEngine {
     loaded_ = true;
   }
 
+  // A map file merged into the map (the rule: fusion_host.h merge_voxel).  The file validated and every block classified against
+  // the map (plan_merge) before anything changes; then chunk by chunk through the two pinned buffers: k_map_merge combines the
+  // blocks whose key is resident in place, k_in_place_at appends the new ones (streaming off) while the host combines the
+  // chunk's stored blocks into the store, puts the new ones there (streaming on) and reads the next chunk.  A file that changes
+  // under the second pass leaves a mixture of merged and untouched blocks (DR_ERR_IO; merge_stats tells how far it got).
+  void merge_map(const char *path, size_t chunk_blocks) {
+    if (!path) fail(DR_ERR_ARG, "drf_merge_map: null argument");
+    expect(kIntegrate, "drf_merge_map: call it where IntegrateScanAsync may be called.");
+    settle();
+    std::string err;
+    MapReader rd;
+    if (!rd.open(path, err)) fail(DR_ERR_IO, "drf_merge_map: %s", err.c_str());
+    const float vs = rd.voxel_size();
+    if (memcmp(&vs, &o_.voxel_size, 4) != 0) fail(DR_ERR_ARG, "drf_merge_map: %s has voxel_size %.9g, the engine %.9g", path, vs, o_.voxel_size);
+    const size_t n = (size_t)rd.blocks();
+    const std::vector<unsigned long long> &keys = rd.keys();
+    const int nres = pool_blocks();
+    std::vector<unsigned long long> res((size_t)nres);
+    std::vector<int> slots((size_t)nres);
+    sort_resident(nres, res);
+    if (nres > 0) DR_HIP(hipMemcpy(slots.data(), mio_slot_.get(), (size_t)nres * 4, hipMemcpyDeviceToHost));
+    const size_t chunk = map_chunk(chunk_blocks, n);
+    const MergePlan p = plan_merge(res, slots, store_.sorted_keys(), keys, chunk);
+    const bool to_store = st_radius_ > 0.0f;
+    const size_t n_add = p.add_key.size(), n_res = p.res_slot.size();
+    if (to_store ? store_.size() + n_add > st_host_cap_ : (size_t)nres + n_add > (size_t)o_.num_blocks)
+      fail(DR_ERR_CAPACITY, "drf_merge_map: %zu new blocks do not fit in the %s (%zu of %llu in use)", n_add, to_store ? "host store" : "pool",
+           to_store ? store_.size() : (size_t)nres, (unsigned long long)(to_store ? st_host_cap_ : (size_t)o_.num_blocks));
+    for (auto &v : mg_stats_) v = 0;
+    mg_stats_[0] = n;
+    mu_force_full_ = true;
+    if (n == 0) { loaded_ = true; return; }
+    ensure_map_io(chunk);
+    // the per-chunk index lists, in the sort's buffers (their contents are on the host now)
+    const size_t n_dev = to_store ? 0 : n_add;
+    mio_slot_in_.reserve(std::max<size_t>(n_res, 1), int_stream_); mio_slot_.reserve(std::max<size_t>(n_res, 1), int_stream_);
+    mio_dst_.reserve(std::max<size_t>(n_dev, 1), int_stream_); mio_keys_.reserve(std::max<size_t>(n_dev, 1), int_stream_);
+    mg_counts_.reserve(2, int_stream_);
+    if (n_res > 0) {
+      DR_HIP(hipMemcpy(mio_slot_in_.get(), p.res_src.data(), n_res * 4, hipMemcpyHostToDevice));
+      DR_HIP(hipMemcpy(mio_slot_.get(), p.res_slot.data(), n_res * 4, hipMemcpyHostToDevice));
+    }
+    if (n_dev > 0) {
+      DR_HIP(hipMemcpy(mio_dst_.get(), p.add_src.data(), n_dev * 4, hipMemcpyHostToDevice));
+      DR_HIP(hipMemcpy(mio_keys_.get(), p.add_key.data(), n_dev * 8, hipMemcpyHostToDevice));
+    }
+    DR_HIP(hipMemset(mg_counts_.get(), 0, 16));
+    for (auto &r : renders_) DR_HIP(hipStreamWaitEvent(int_stream_, r.cast, 0));  // blocks change
+    const unsigned char W = (unsigned char)o_.max_sdf_weight;
+    uint64_t host_counts[2] = {0, 0};
+    bool ok = true;
+    for (size_t c = 0; c < p.chunks() && ok; ++c) {
+      const size_t m = std::min(chunk, n - c * chunk);
+      mio_.wait();  // the kernels of two chunks ago have read this buffer
+      ok = rd.read(mio_.host(), m, err);
+      if (!ok) break;
+      const int mr = (int)(p.rb[c + 1] - p.rb[c]), ma = to_store ? 0 : (int)(p.ab[c + 1] - p.ab[c]);
+      if (mr > 0)
+        hipLaunchKernelGGL(k_map_merge, dim3(std::min(cdiv(mr, 4), 1024)), dim3(256), 0, int_stream_, d_.vox, mio_slot_in_.get() + p.rb[c], mio_slot_.get() + p.rb[c],
+                           mr, (const uint4 *)mio_.dev(), W, mg_counts_.get());
+      if (ma > 0) {
+        hipLaunchKernelGGL(k_in_place_at, dim3(std::min(cdiv(ma, 4), 1024)), dim3(256), 0, int_stream_, d_, mio_keys_.get() + p.ab[c], mio_dst_.get() + p.ab[c],
+                           (const uint4 *)mio_.dev(), ma);
+        hipLaunchKernelGGL(k_in_finish, dim3(1), dim3(64), 0, int_stream_, d_.n_alloc, ma);
+      }
+      if (mr > 0 || ma > 0) {
+        DR_HIP(hipGetLastError());
+        mio_.record(int_stream_);
+      }
+      // the host half of the chunk, from the same buffer, while the kernels read it
+      const unsigned char *h = mio_.host();
+      for (size_t i = p.sb[c]; i < p.sb[c + 1]; ++i) merge_block(store_.get_mut(p.sto_key[i]), h + (size_t)p.sto_src[i] * 4096, W, host_counts);
+      if (to_store)
+        for (size_t i = p.ab[c]; i < p.ab[c + 1]; ++i) store_.put(p.add_key[i], h + (size_t)p.add_src[i] * 4096);
+      mg_stats_[1] += p.ab[c + 1] - p.ab[c]; mg_stats_[2] += (uint64_t)mr; mg_stats_[3] += p.sb[c + 1] - p.sb[c];
+      mio_.flip();
+    }
+    DR_HIP(hipStreamSynchronize(int_stream_));
+    unsigned long long dev_counts[2];
+    DR_HIP(hipMemcpy(dev_counts, mg_counts_.get(), 16, hipMemcpyDeviceToHost));
+    mg_stats_[4] = host_counts[0] + dev_counts[0]; mg_stats_[5] = host_counts[1] + dev_counts[1];
+    if (ok && !rd.verified()) { ok = false; err = std::string("map file ") + path + " changed while it was read"; }
+    if (!ok) fail(DR_ERR_IO, "drf_merge_map: %s (the blocks merged so far stay merged: drf_merge_stats)", err.c_str());
+    loaded_ = true;
+  }
+  void merge_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = mg_stats_[i]; }
+
  private:
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
@@ -1460,6 +1534,23 @@ class FusionEngine {
     int na = 0;
     DR_HIP(hipMemcpy(&na, d_.n_alloc, 4, hipMemcpyDeviceToHost));
     return std::min(na, o_.num_blocks);
+  }
+  // the resident order: (blk_key, slot) pairs sorted by key, as mesh_tables sorts the keys -- the keys to res, keys and slots
+  // left in mio_keys_ / mio_slot_ (drf_save_map, drf_merge_map)
+  void sort_resident(int nres, std::vector<unsigned long long> &res) {
+    if (nres <= 0) return;
+    std::vector<int> iota((size_t)nres);
+    for (int i = 0; i < nres; ++i) iota[i] = i;
+    mio_keys_.reserve((size_t)nres, int_stream_); mio_slot_in_.reserve((size_t)nres, int_stream_);
+    mio_slot_.reserve((size_t)nres, int_stream_); mio_dst_.reserve((size_t)nres, int_stream_);
+    DR_HIP(hipMemcpy(mio_slot_in_.get(), iota.data(), (size_t)nres * 4, hipMemcpyHostToDevice));
+    size_t tb = 0;
+    DR_HIP(rocprim::radix_sort_pairs(nullptr, tb, d_.blk_key, mio_keys_.get(), mio_slot_in_.get(), mio_slot_.get(), (size_t)nres, 0, 63, int_stream_));
+    mio_tmp_.reserve(std::max<size_t>(tb, 256), int_stream_);  // (never null: a null scratch is rocprim's size query)
+    tb = mio_tmp_.capacity();
+    DR_HIP(rocprim::radix_sort_pairs(mio_tmp_.get(), tb, d_.blk_key, mio_keys_.get(), mio_slot_in_.get(), mio_slot_.get(), (size_t)nres, 0, 63, int_stream_));
+    DR_HIP(hipMemcpyAsync(res.data(), mio_keys_.get(), (size_t)nres * 8, hipMemcpyDeviceToHost, int_stream_));
+    DR_HIP(hipStreamSynchronize(int_stream_));
   }
   // blocks per chunk of a map file of n blocks: the caller's, or min(num_blocks, 8192); never more than the file has or 2^20
   size_t map_chunk(size_t chunk_blocks, size_t n) const {
@@ -1968,7 +2059,7 @@ class FusionEngine {
   std::vector<Render> renders_;
   int free_slot_ = 0;
   Next next_ = kIntegrate;
-  bool loaded_ = false;  // the map came from drf_load_map and no scan followed yet: RenderAsync is legal where IntegrateScanAsync is
+  bool loaded_ = false;  // the map came from drf_load_map / drf_merge_map and no scan followed yet: RenderAsync is legal where IntegrateScanAsync is
   // mesh extraction state (allocated with the first ExtractMeshAsync)
   static constexpr unsigned kMeshMaxTriangles = 20000000;
   bool mesh_pending_ = false;
@@ -2024,11 +2115,13 @@ class FusionEngine {
   double ev_p_[3] = {0.0, 0.0, 0.0};
   ReachBalls reach_;  // balls that hold every block centre of the map
   uint64_t st_out_total_ = 0, st_in_total_ = 0;
-  // map file transport (allocated with the first drf_save_map / drf_load_map): two pinned chunk buffers, the sorted (key, slot) pairs
+  // map file transport (allocated with the first drf_save_map / drf_load_map / drf_merge_map): two pinned chunk buffers, the sorted (key, slot) pairs
   PinnedPair mio_;
   DeviceBuf<unsigned long long> mio_keys_;
   DeviceBuf<int> mio_slot_in_, mio_slot_, mio_dst_;
   DeviceBuf<unsigned char> mio_tmp_;
+  DeviceBuf<unsigned long long> mg_counts_;  // drf_merge_map: voxels of case 2 and case 3 counted by k_map_merge
+  uint64_t mg_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_merge_stats
 };
 
 }  // namespace dr
@@ -2153,6 +2246,10 @@ int drf_map_info(const char *path, float *voxel_size, uint64_t *n_blocks) {
 }
 int drf_save_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->save_map(path, chunk_blocks); }); }
 int drf_load_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->load_map(path, chunk_blocks); }); }
+int drf_merge_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->merge_map(path, chunk_blocks); }); }
+int drf_merge_stats(drf_t *h, uint64_t out[6]) {
+  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_merge_stats: null argument"); eng(h)->merge_stats(out); });
+}
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }
 int drf_render_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->render_stats(out); }); }
 int drf_set_render_bands(drf_t *h, int max_passes) { return guarded([&] { eng(h)->set_render_bands(max_passes); }); }

@@ -1,6 +1,7 @@
-// fusion_host.h -- the host half of DrFusion's map: block keys, streaming reach bounds, the host block store, the reach balls
-// and the planner of the map-scope mesh pass.  No device state and no HIP header: plain C++17, so that all of it runs in the
-// CPU tests (tests/cpp/fusion_host_check.cpp).  The engine (dr_fusion.hip) keeps everything that throws or touches the GPU.
+// fusion_host.h -- the host half of DrFusion's map: block keys, streaming reach bounds, the host block store, the reach balls,
+// the planner of the map-scope mesh pass, and the rule and planner of a map merge.  No device state and no HIP header: plain
+// C++17, so that all of it runs in the CPU tests (tests/cpp/fusion_host_check.cpp, tests/cpp/map_merge_check.cpp).  The engine
+// (dr_fusion.hip) keeps everything that throws or touches the GPU.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -128,6 +129,7 @@ class HostBlockStore {
     cells_[cell_key(key)].push_back(key);
   }
   const uint8_t *get(unsigned long long key) const { return at(slot_.at(key)); }
+  uint8_t *get_mut(unsigned long long key) { return at(slot_.at(key)); }  // the block changed in place (merge_block)
   bool contains(unsigned long long key) const { return slot_.count(key) != 0; }
   void erase(unsigned long long key) {  // the key must be there
     auto it = slot_.find(key);
@@ -455,6 +457,93 @@ inline MeshPlan plan_mesh_chunks(const std::vector<unsigned long long> &res, con
       if (in_cur.insert(need[k]).second) cur.push_back(need[k]);
   });
   if (p.own.size() > p.ob.back()) close_chunk();
+  return p;
+}
+
+// ---- merging a map file into the map (drf_merge_map; DESIGN.md §7c "Merging a map file")
+// The rule, stated once for the host store and the kernel (k_map_merge compiles this very function for the device).  Blocks: the
+// merged map holds the union of the two block sets; a file block whose key the map lacks is placed verbatim, one whose key it
+// holds is combined with the map's block voxel by voxel, index by index.  Voxels: a = the map's, b = the file's,
+// W = (unsigned char)max_sdf_weight, fp32 without contraction:
+//   1  b.weight == 0:          a stays as it is, all 8 bytes
+//   2  else a.weight == 0:     a.sdf = b.sdf, a.colour = b.colour, a.weight = min(b.weight, W)
+//   3  else, wa = (float)a.weight, wb = (float)b.weight:
+//        each colour channel  (unsigned char)(((float)a.c * wa + (float)b.c * wb) / (wa + wb))
+//        a.sdf = (a.sdf * wa + b.sdf * wb) / (wa + wb)
+//        a.weight = min((int)a.weight + (int)b.weight, (int)W)
+// Case 3 is Voxel::Combine (tsdfvh/voxel.h) with any second weight, except that the weight sum is formed in int: two unsigned
+// chars would wrap above 255, which integration (always + 1, clamped) never reaches and a merge does.  Cases 1 and 2 keep 0/0
+// out of the map and make an absent block and an allocated, never updated one behave alike.
+// A voxel here is its two little-endian words: [0] the sdf's bits, [1] b | g << 8 | r << 16 | weight << 24.  Returns the case.
+#if defined(__HIPCC__)
+#define DR_HOST_DEVICE __host__ __device__
+#else
+#define DR_HOST_DEVICE
+#endif
+DR_HOST_DEVICE inline int merge_voxel(uint32_t a[2], const uint32_t b[2], unsigned char W) {
+  const unsigned wai = a[1] >> 24, wbi = b[1] >> 24;
+  if (wbi == 0) return 1;
+  if (wai == 0) {
+    a[0] = b[0];
+    a[1] = (b[1] & 0xffffffu) | ((wbi < W ? wbi : (unsigned)W) << 24);
+    return 2;
+  }
+  const float wa = (float)wai, wb = (float)wbi, den = wa + wb;
+  unsigned cw = 0;
+  for (int k = 0; k < 24; k += 8) {
+    const float ca = (float)((a[1] >> k) & 255u), cb = (float)((b[1] >> k) & 255u);
+    // integer-valued operands below 2^24: products and sum exact, the quotient a correctly rounded value in [0, 255]
+    cw |= (unsigned)(unsigned char)(int)((ca * wa + cb * wb) / den) << k;
+  }
+  float sa, sb;
+  memcpy(&sa, &a[0], 4); memcpy(&sb, &b[0], 4);
+  const float s = (sa * wa + sb * wb) / den;
+  memcpy(&a[0], &s, 4);
+  const unsigned ws = wai + wbi;
+  a[1] = cw | ((ws < W ? ws : (unsigned)W) << 24);
+  return 3;
+}
+// 512 voxels of src merged into dst; counts[0] += voxels of case 2 (taken verbatim), counts[1] += voxels of case 3 (averaged)
+inline void merge_block(uint8_t *dst4096, const uint8_t *src4096, unsigned char W, uint64_t counts[2]) {
+  for (int v = 0; v < kBS * kBS * kBS; ++v) {
+    uint32_t a[2], b[2];
+    memcpy(a, dst4096 + 8 * v, 8); memcpy(b, src4096 + 8 * v, 8);
+    const int c = merge_voxel(a, b, W);
+    if (c == 1) continue;
+    memcpy(dst4096 + 8 * v, a, 8);
+    ++counts[c - 2];
+  }
+}
+// Every file block classified against the map in one walk over three ascending key lists: the resident keys with their pool
+// slots (the sorted pairs drf_save_map works from), the host store's keys, the file's keys.  ADDED = the map lacks the key,
+// RESIDENT = combined in its pool slot, STORED = combined in the host store.  The file is cut into chunks of `chunk` blocks (one
+// pinned buffer each); per class the lists below are in file order, chunk c owning [xb[c], xb[c + 1]), and *_src is the block's
+// position within its chunk's buffer -- what k_map_merge and k_in_place_at index by.
+struct MergePlan {
+  size_t chunk = 1;
+  std::vector<int> res_src, res_slot;
+  std::vector<int> add_src;
+  std::vector<unsigned long long> add_key;
+  std::vector<int> sto_src;
+  std::vector<unsigned long long> sto_key;
+  std::vector<size_t> rb{0}, ab{0}, sb{0};
+  size_t chunks() const { return rb.size() - 1; }
+};
+inline MergePlan plan_merge(const std::vector<unsigned long long> &res, const std::vector<int> &res_slot, const std::vector<unsigned long long> &sto,
+                            const std::vector<unsigned long long> &file, size_t chunk) {
+  MergePlan p;
+  p.chunk = std::max<size_t>(chunk, 1);
+  size_t i = 0, j = 0;
+  for (size_t f = 0; f < file.size(); ++f) {
+    const unsigned long long key = file[f];
+    const int at = (int)(f % p.chunk);
+    while (i < res.size() && res[i] < key) ++i;
+    while (j < sto.size() && sto[j] < key) ++j;
+    if (i < res.size() && res[i] == key) { p.res_src.push_back(at); p.res_slot.push_back(res_slot[i]); }
+    else if (j < sto.size() && sto[j] == key) { p.sto_src.push_back(at); p.sto_key.push_back(key); }
+    else { p.add_src.push_back(at); p.add_key.push_back(key); }
+    if (at + 1 == (int)p.chunk || f + 1 == file.size()) { p.rb.push_back(p.res_src.size()); p.ab.push_back(p.add_src.size()); p.sb.push_back(p.sto_src.size()); }
+  }
   return p;
 }
 

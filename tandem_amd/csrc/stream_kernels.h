@@ -15,7 +15,8 @@
 // Every kernel after k_ev_select exits at once when the selection is empty.  Stream-in (k_in_place + k_in_finish) appends
 // blocks from a pinned upload to the pool and publishes them the way k_alloc_commit does.  The map file (drf_save_map /
 // drf_load_map) uses the same two moves: k_map_gather copies pool blocks into a chunk of the file without touching the map,
-// and a load places the file's chunks with k_in_place + k_in_finish.
+// and a load places the file's chunks with k_in_place + k_in_finish.  A merge (drf_merge_map) combines the file's blocks whose
+// key is resident into their pool slots (k_map_merge) and appends those the map lacks (k_in_place_at + k_in_finish).
 
 struct StreamDev {
   int *ctl;                    // [0] blocks selected (uncapped), [1] holes, [2] tail survivors, [3] table blocks re-inserted,
@@ -236,5 +237,63 @@ __global__ __launch_bounds__(256) void k_map_gather(const Voxel *__restrict__ vo
     uint4 *b = out + (size_t)dst[i] * 256;
 #pragma unroll
     for (int k = 0; k < 4; ++k) b[lane + 64 * k] = a[lane + 64 * k];
+  }
+}
+
+// Map merge: block src[i] of the chunk buffer (mapped pinned memory, read once) combined into pool slot slot[i], i in [0, n):
+// one wave per block, four uint4 = 8 voxels per lane, merge_voxel (fusion_host.h: the rule) on each.  A voxel of case 1 is
+// written back with the bytes it was read with.  counts[0] += voxels of case 2, counts[1] += voxels of case 3: summed across
+// the wave, one atomic each per wave.  Touches nothing but the voxels: keys, grid, presence bits stay as they are.
+__global__ __launch_bounds__(256) void k_map_merge(Voxel *__restrict__ vox, const int *__restrict__ src, const int *__restrict__ slot, int n,
+                                                   const uint4 *__restrict__ chunk, unsigned char W, unsigned long long *__restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  unsigned n2 = 0, n3 = 0;
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+    const uint4 *b = chunk + (size_t)src[i] * 256;
+    uint4 *a = reinterpret_cast<uint4 *>(vox + (size_t)slot[i] * 512);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint4 vb = b[lane + 64 * k];
+      uint4 va = a[lane + 64 * k];
+      uint32_t p[2] = {va.x, va.y}, q[2] = {va.z, va.w};
+      const uint32_t pb[2] = {vb.x, vb.y}, qb[2] = {vb.z, vb.w};
+      const int c0 = merge_voxel(p, pb, W), c1 = merge_voxel(q, qb, W);
+      n2 += (c0 == 2) + (c1 == 2);
+      n3 += (c0 == 3) + (c1 == 3);
+      a[lane + 64 * k] = make_uint4(p[0], p[1], q[0], q[1]);
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) { n2 += __shfl_xor(n2, off); n3 += __shfl_xor(n3, off); }
+  if (lane == 0) {
+    if (n2) atomicAdd(&counts[0], (unsigned long long)n2);
+    if (n3) atomicAdd(&counts[1], (unsigned long long)n3);
+  }
+}
+
+// k_in_place with a source index list: key keys[i] and block src[i] of the chunk buffer -> pool slot n_alloc + i.  A chunk's
+// added blocks are not contiguous in its buffer.  Followed by k_in_finish like k_in_place.
+__global__ __launch_bounds__(256) void k_in_place_at(const FusionDev d, const unsigned long long *__restrict__ keys, const int *__restrict__ src,
+                                                     const uint4 *__restrict__ vox, int n) {
+  const int base = pool_count(d);
+  const int lane = threadIdx.x & 63;
+  for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += gridDim.x * 4) {
+    const int p = base + i;
+    const uint4 *a = vox + (size_t)src[i] * 256;
+    uint4 *b = reinterpret_cast<uint4 *>(d.vox + (size_t)p * 512);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[lane + 64 * k] = a[lane + 64 * k];
+    if (lane == 0) {
+      const unsigned long long key = keys[i];
+      d.blk_key[p] = key;
+      unsigned idx;
+      if (grid_index(unpack_key(key), idx)) {
+        d.grid[idx] = p + 1;
+        atomicOr(&d.present[idx >> 5], 1u << (idx & 31));
+        set_super(d, idx);
+      } else {
+        table_insert(d, key, p);
+        atomicAdd(&d.n_alloc[3], 1);
+      }
+    }
   }
 }

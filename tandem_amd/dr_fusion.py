@@ -264,6 +264,20 @@ class DrFusion:
         (DR_ERR_CAPACITY) or a non-empty map (DR_ERR_PROTOCOL); the engine then stays empty and usable."""
         check(self._L.drf_load_map(self._h, os.fsencode(path), int(chunk_blocks)))
 
+    def merge_map(self, path, chunk_blocks=0):
+        """A saved map of the same world (same voxel_size and frame) merged into this engine's map: the union of the blocks, shared
+        blocks combined voxel by voxel as a weighted average (include/dr_mi355x.h drf_merge_map states the rule).  DrError on a
+        bad file (DR_ERR_IO), another voxel_size (DR_ERR_ARG) or too many new blocks (DR_ERR_CAPACITY); then nothing changed,
+        except after a file that changed while it was read (DR_ERR_IO, merge_stats() tells how far the merge got)."""
+        check(self._L.drf_merge_map(self._h, os.fsencode(path), int(chunk_blocks)))
+
+    def merge_stats(self):
+        """Last merge_map: (blocks in the file, blocks added, blocks combined in the pool, blocks combined in the host store,
+        voxels taken verbatim, voxels averaged)."""
+        out = (C.c_uint64 * 6)()
+        check(self._L.drf_merge_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
     def set_render_scope(self, scope, stage_capacity_blocks=0):
         """RENDER_RESIDENT (default): renders read the pool; RENDER_MAP: the pool and the host store -- any pose renders as on an
         engine whose pool never ran out, the stored blocks in reach staged through stage_capacity_blocks blocks of device scratch

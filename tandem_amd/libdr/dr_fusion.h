@@ -98,6 +98,8 @@ public:
   // DrFusion whose map is empty.  Failures exit like every other member.
   void SaveMapToFile(std::string const &filename) { check(drf_save_map(impl, filename.c_str(), 0)); }
   void LoadMapFromFile(std::string const &filename) { check(drf_load_map(impl, filename.c_str(), 0)); }
+  // a saved map of the same world merged into the map this DrFusion holds, voxel by voxel (dr_mi355x.h drf_merge_map)
+  void MergeMapFromFile(std::string const &filename) { check(drf_merge_map(impl, filename.c_str(), 0)); }
 
   // Incremental mesh (dr_mi355x.h "incremental mesh", INTEGRATION.md "Incremental mesh"): GetMeshUpdateSync fills dr_mesh_num /
   // dr_mesh_vert / dr_mesh_cols with the triangles of the listed blocks only, and the members below name the blocks: block i has

@@ -3,6 +3,8 @@
     python -m tandem_amd.map_file info PATH                  header fields and the blocks' bounding box (needs no device)
     python -m tandem_amd.map_file mesh PATH OUT.obj [--lower x y z --upper x y z]
                                                              loads the map into an engine sized for it and meshes it
+    python -m tandem_amd.map_file merge OUT IN1 IN2 [IN3 ...] [--max-weight 64]
+                                                             IN1 loaded, the others merged into it in order (drf_merge_map), saved
 
 Layout, little-endian, 72 + 4104 n bytes: magic "DRFMAP01", u32 header size 64, u32 block edge 8, u32 bytes per voxel 8,
 f32 voxel_size, u64 n, 32 zero bytes; n ascending u64 packed keys; n x 4096 voxel bytes; u64 checksum."""
@@ -116,6 +118,27 @@ def mesh(path, out, lower=None, upper=None):
         f.close()
 
 
+def merge(out, inputs, max_weight=64):
+    """load_map(inputs[0]), merge_map of the rest in order, save_map(out), in an engine sized for the sum of the inputs' block
+    counts.  Returns the merge_stats() of every merge."""
+    from .dr_fusion import DrFusion, DrFusionOptions
+    infos = [info(p) for p in inputs]
+    vs = infos[0]["voxel_size"]
+    n = max(sum(d["blocks"] for d in infos), 1)
+    f = DrFusion(DrFusionOptions(voxel_size=vs, num_blocks=n, num_buckets=n, num_render_streams=0, height=8, width=8,
+                                 truncation_distance=4 * vs, max_sdf_weight=int(max_weight)))
+    try:
+        f.load_map(inputs[0])
+        stats = []
+        for p in inputs[1:]:
+            f.merge_map(p)
+            stats.append(f.merge_stats())
+        f.save_map(out)
+    finally:
+        f.close()
+    return stats
+
+
 def main(argv):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m tandem_amd.map_file")
@@ -126,10 +149,19 @@ def main(argv):
     m.add_argument("out")
     m.add_argument("--lower", type=float, nargs=3)
     m.add_argument("--upper", type=float, nargs=3)
+    g = sub.add_parser("merge")
+    g.add_argument("out")
+    g.add_argument("inputs", nargs="+")
+    g.add_argument("--max-weight", type=int, default=64)
     a = ap.parse_args(argv)
     if a.cmd == "info":
         for k, v in info(a.path).items():
             print("%-12s %s" % (k, v))
+    elif a.cmd == "merge":
+        if len(a.inputs) < 2:
+            ap.error("merge needs at least two input maps")
+        for p, st in zip(a.inputs[1:], merge(a.out, a.inputs, a.max_weight)):
+            print("%s: blocks %d added %d combined %d voxels_verbatim %d voxels_averaged %d" % (p, st[0], st[1], st[2] + st[3], st[4], st[5]))
     else:
         mesh(a.path, a.out, a.lower, a.upper)
     return 0
