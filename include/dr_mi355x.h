@@ -412,6 +412,42 @@ int drf_merge_map(drf_t *h, const char *path, size_t chunk_blocks);
 /* last drf_merge_map: [0] blocks in the file, [1] blocks added (key was not in the map), [2] blocks combined in the pool,
  * [3] blocks combined in the host store, [4] voxels of combined blocks taken verbatim (case 2), [5] voxels averaged (case 3) */
 int drf_merge_stats(drf_t *h, uint64_t out[6]);
+/* Moves a map file into another world frame (DESIGN.md §7c "Moving a map into another frame"): reads src_path, resamples its
+ * surface on the engine's voxel lattice under the rigid motion T16 and writes the result to dst_path as a map file, which
+ * drf_load_map and drf_merge_map then take like any other.  T16 is row-major and maps file-world to engine-world,
+ * p_engine = R p_file + t, the convention of the poses.  The engine lends its device, its streams, its pinned buffers and its
+ * voxel_size; its own map is neither read nor changed: pool, slot order, host store, streaming state, mesh baseline and every
+ * counter stay as they were, a pending mesh extraction stays pending, and drf_save_map writes the same bytes before and after.
+ * The rule, per destination lattice point g (a voxel with lattice coordinates g sits at g * voxel_size; block floor(g / 8),
+ * index (gx & 7) * 64 + (gy & 7) * 8 + (gz & 7)).  Once, in double: Rd[i][j] = T16[4 i + j], tv[j] = T16[4 j + 3] / voxel_size.
+ *   position  in double, without contraction: d = g - tv, u_k = (Rd[0][k] d_0 + Rd[1][k] d_1) + Rd[2][k] d_2 (= R^T d),
+ *             b_k = floor(u_k), f_k = (float)(u_k - b_k).
+ *   corners   c = 4 cx + 2 cy + cz with the fp32 weight w_c = (a_x(cx) * a_y(cy)) * a_z(cz), a_k(0) = 1.0f - f_k, a_k(1) = f_k.
+ *             A corner is USED iff w_c != 0 and reads the source voxel at lattice point b + (cx, cy, cz); an absent block, or one
+ *             outside the key range, counts as weight 0.
+ *   result    if any used corner has weight 0: 8 zero bytes.  Otherwise sdf = the sum of w_c * sdf_c over the used corners in
+ *             ascending c in fp32 (the first used term initialises the sum), each colour channel
+ *             (unsigned char)min(sum of w_c * (float)channel_c + 0.5f, 255.0f) in the same order, weight = the smallest of the
+ *             used corners' weights.  A partly weighted neighbourhood is refused, not renormalised.
+ *   blocks    a destination block is written iff one of its 512 voxels has weight > 0, with all 4096 bytes as computed; keys
+ *             strictly ascending.  The output is a function of the source file and T16 alone.
+ * So a signed permutation matrix with a translation of whole voxels (voxel_size a power of two) moves every weighted voxel with
+ * its 8 bytes unchanged, and the identity writes the source without its weight-0 voxels and its blocks that hold no other.
+ * Scale is not handled: T16 must be rigid.
+ * Legal where drf_integrate_scan_async is (otherwise DR_ERR_PROTOCOL).  DR_ERR_ARG: a null argument; src_path and dst_path the
+ * same string; T16 with a non-finite entry, a last row that is not exactly 0 0 0 1, R R^T differing from I by 1e-3 or more in an
+ * entry, or det R <= 0; a file whose voxel_size bits differ from the engine's; a motion that takes a candidate destination block
+ * outside the 21-bit key range.  DR_ERR_IO: the source fails the whole-file validation (before anything else is done with it),
+ * or any other file failure (the path is in dr_last_error()).  DR_ERR_CAPACITY: the source cannot be held on the device --
+ * it is uploaded whole for the duration of the call, key table and voxels, 4104 n bytes, and freed before the call returns;
+ * sources beyond the free device memory are out of scope and are refused with nothing written.  The output goes to <dst_path>.part and takes its name when it is complete: no failure leaves a partial file under
+ * dst_path.  It streams through the engine's pinned buffers in chunks of chunk_blocks blocks (0: as drf_save_map).  An empty
+ * source, or one that yields no weighted voxel, gives a valid file of 72 bytes. */
+int drf_transform_map(drf_t *h, const char *src_path, const float T16[16], const char *dst_path, size_t chunk_blocks);
+/* last drf_transform_map: [0] source blocks, [1] candidate destination blocks evaluated, [2] blocks written, [3] voxels written
+ * with weight > 0, [4] destination voxels refused because only part of their neighbourhood was weighted, [5] device bytes held
+ * for the source */
+int drf_transform_stats(drf_t *h, uint64_t out[6]);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

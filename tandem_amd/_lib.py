@@ -133,6 +133,8 @@ SIGNATURES = {
     "drf_load_map": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
     "drf_merge_map": (C.c_int, [vp, C.c_char_p, C.c_size_t]),
     "drf_merge_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_transform_map": (C.c_int, [vp, C.c_char_p, f32p, C.c_char_p, C.c_size_t]),
+    "drf_transform_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
 
 

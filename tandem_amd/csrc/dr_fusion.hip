@@ -1526,6 +1526,120 @@ class FusionEngine {
   }
   void merge_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = mg_stats_[i]; }
 
+  // A map file resampled on this engine's lattice in another world frame and written as a map file (the rule: fusion_host.h
+  // transform_voxel; DESIGN.md §7c "Moving a map into another frame").  The engine lends its device, int_stream_, the pinned pair
+  // and voxel_size; its own map is neither read nor changed and nothing is folded.  The source goes to the device whole (voxels,
+  // then the key table: 4104 n bytes, freed on every way out), plan_transform lists the candidate destination blocks, a count
+  // pass of k_map_transform tells which of them hold a weighted voxel -- MapWriter wants the key table first -- and a write pass
+  // over those fills the pinned buffers chunk by chunk while the host appends the other buffer to <dst>.part.
+  void transform_map(const char *src, const float *T16, const char *dst, size_t chunk_blocks) {
+    if (!src || !T16 || !dst) fail(DR_ERR_ARG, "drf_transform_map: null argument");
+    expect(kIntegrate, "drf_transform_map: call it where IntegrateScanAsync may be called.");
+    if (!strcmp(src, dst)) fail(DR_ERR_ARG, "drf_transform_map: source and destination are the same path (%s)", src);
+    if (const char *why = transform_pose_fault(T16)) fail(DR_ERR_ARG, "drf_transform_map: the motion %s", why);
+    std::string err;
+    MapReader rd;
+    if (!rd.open(src, err)) fail(DR_ERR_IO, "drf_transform_map: %s", err.c_str());
+    const float vs = rd.voxel_size();
+    if (memcmp(&vs, &o_.voxel_size, 4) != 0) fail(DR_ERR_ARG, "drf_transform_map: %s has voxel_size %.9g, the engine %.9g", src, vs, o_.voxel_size);
+    const size_t n = (size_t)rd.blocks();
+    const MapMotion m = map_motion(T16, o_.voxel_size);
+    bool in_range = true;
+    const std::vector<unsigned long long> cand = plan_transform(rd.keys(), m, &in_range);
+    if (!in_range) fail(DR_ERR_ARG, "drf_transform_map: the motion takes blocks of %s outside the key range (2^20 blocks per axis)", src);
+    if (n > (size_t)INT_MAX || cand.size() > (size_t)INT_MAX) fail(DR_ERR_CAPACITY, "drf_transform_map: %zu source and %zu candidate blocks exceed the index range", n, cand.size());
+    DR_HIP(hipSetDevice(device_));
+    // the source must fit on the device beside what is there (the parity build can lower the limit: the tests' way to this refusal)
+    const size_t src_bytes = n * 4104, side_bytes = cand.size() * 20 + 16;  // candidate keys, flags, kept keys; two counters
+    if (n > 0) {
+      size_t free_b = 0, total_b = 0;
+      DR_HIP(hipMemGetInfo(&free_b, &total_b));
+      if (const char *e = hook_env("DR_TRANSFORM_MAX_BYTES")) free_b = std::min(free_b, (size_t)strtoull(e, nullptr, 10));
+      if (src_bytes + side_bytes > free_b)
+        fail(DR_ERR_CAPACITY, "drf_transform_map: %s needs %zu bytes of device memory (%zu blocks), %zu are available", src, src_bytes + side_bytes, n, free_b);
+    }
+    struct Held {  // device memory of this call only
+      void *p = nullptr;
+      ~Held() { if (p) (void)hipFree(p); }
+      bool take(size_t bytes) { if (hipMalloc(&p, bytes) == hipSuccess) return true; p = nullptr; (void)hipGetLastError(); return false; }
+    } source, side;
+    for (auto &v : xf_stats_) v = 0;
+    xf_stats_[0] = n; xf_stats_[1] = cand.size();
+    std::vector<unsigned long long> kept;
+    const size_t nc = cand.size();
+    const size_t chunk = map_chunk(chunk_blocks, std::max(n, nc));
+    DR_HIP(hipStreamSynchronize(int_stream_));  // the pinned pair is idle: every user of it ends with this
+    unsigned long long *d_cand = nullptr, *d_kept = nullptr, *d_counts = nullptr;
+    if (n > 0 && nc > 0) {
+      if (!source.take(src_bytes) || !side.take(side_bytes))
+        fail(DR_ERR_CAPACITY, "drf_transform_map: %s needs %zu bytes of device memory (%zu blocks)", src, src_bytes + side_bytes, n);
+      xf_stats_[5] = src_bytes;
+      ensure_map_io(chunk);
+      unsigned char *d_vox = (unsigned char *)source.p;
+      unsigned long long *d_keys = (unsigned long long *)(d_vox + n * 4096);
+      d_counts = (unsigned long long *)side.p; d_cand = d_counts + 2; d_kept = d_cand + nc;
+      int *d_flags = (int *)(d_kept + nc);
+      DR_HIP(hipMemcpyAsync(d_keys, rd.keys().data(), n * 8, hipMemcpyHostToDevice, int_stream_));
+      DR_HIP(hipMemcpyAsync(d_cand, cand.data(), nc * 8, hipMemcpyHostToDevice, int_stream_));
+      DR_HIP(hipMemsetAsync(d_counts, 0, 16, int_stream_));
+      bool ok = true;
+      for (size_t b = 0; b < n && ok; b += chunk) {  // the file through the pinned pair to the device
+        const size_t cnt = std::min(chunk, n - b);
+        mio_.wait();  // the copy of two chunks ago has left this buffer
+        ok = rd.read(mio_.host(), cnt, err);
+        if (!ok) break;
+        DR_HIP(hipMemcpyAsync(d_vox + b * 4096, mio_.host(), cnt * 4096, hipMemcpyHostToDevice, int_stream_));
+        mio_.record(int_stream_);
+        mio_.flip();
+      }
+      if (ok && !rd.verified()) { ok = false; err = std::string("map file ") + src + " changed while it was read"; }
+      if (!ok) {
+        DR_HIP(hipStreamSynchronize(int_stream_));
+        fail(DR_ERR_IO, "drf_transform_map: %s", err.c_str());
+      }
+      hipLaunchKernelGGL(k_map_transform<false>, dim3(cdiv((int)nc, 4)), dim3(256), 0, int_stream_, d_keys, (const uint2 *)d_vox, (int)n, d_cand, (int)nc, m,
+                         (uint4 *)nullptr, d_flags, d_counts);
+      DR_HIP(hipGetLastError());
+      std::vector<int> flags(nc);
+      unsigned long long counts[2] = {0, 0};
+      DR_HIP(hipMemcpyAsync(flags.data(), d_flags, nc * 4, hipMemcpyDeviceToHost, int_stream_));
+      DR_HIP(hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, int_stream_));
+      DR_HIP(hipStreamSynchronize(int_stream_));
+      for (size_t i = 0; i < nc; ++i)
+        if (flags[i]) kept.push_back(cand[i]);
+      xf_stats_[3] = counts[0]; xf_stats_[4] = counts[1];
+      if (!kept.empty()) DR_HIP(hipMemcpyAsync(d_kept, kept.data(), kept.size() * 8, hipMemcpyHostToDevice, int_stream_));
+    }
+    const size_t nk = kept.size();
+    MapWriter w;
+    if (!w.open(dst, o_.voxel_size, kept.data(), nk, err)) fail(DR_ERR_IO, "drf_transform_map: %s", err.c_str());
+    bool ok = true;
+    if (nk > 0) {
+      unsigned char *d_vox = (unsigned char *)source.p;
+      const unsigned long long *d_keys = (const unsigned long long *)(d_vox + n * 4096);
+      const size_t chunks = (nk + chunk - 1) / chunk;
+      auto launch = [&](size_t c) {  // chunk c of the kept blocks into the current buffer
+        const int cnt = (int)std::min(chunk, nk - c * chunk);
+        hipLaunchKernelGGL(k_map_transform<true>, dim3(cdiv(cnt, 4)), dim3(256), 0, int_stream_, d_keys, (const uint2 *)d_vox, (int)n, d_kept + c * chunk, cnt, m,
+                           (uint4 *)mio_.dev(), (int *)nullptr, (unsigned long long *)nullptr);
+        DR_HIP(hipGetLastError());
+        mio_.record(int_stream_);
+      };
+      launch(0);
+      for (size_t c = 0; c < chunks && ok; ++c) {
+        if (c + 1 < chunks) { mio_.flip(); launch(c + 1); mio_.flip(); }  // runs while the host appends chunk c
+        mio_.wait();
+        ok = w.append(mio_.host(), std::min(chunk, nk - c * chunk), err);
+        mio_.flip();
+      }
+    }
+    ok = ok && w.close(err);
+    DR_HIP(hipStreamSynchronize(int_stream_));  // (a failed write leaves the next chunk's kernel in flight)
+    if (!ok) fail(DR_ERR_IO, "drf_transform_map: %s", err.c_str());
+    xf_stats_[2] = nk;
+  }
+  void transform_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = xf_stats_[i]; }
+
  private:
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
@@ -2122,6 +2236,7 @@ class FusionEngine {
   DeviceBuf<unsigned char> mio_tmp_;
   DeviceBuf<unsigned long long> mg_counts_;  // drf_merge_map: voxels of case 2 and case 3 counted by k_map_merge
   uint64_t mg_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_merge_stats
+  uint64_t xf_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_transform_stats
 };
 
 }  // namespace dr
@@ -2249,6 +2364,12 @@ int drf_load_map(drf_t *h, const char *path, size_t chunk_blocks) { return guard
 int drf_merge_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->merge_map(path, chunk_blocks); }); }
 int drf_merge_stats(drf_t *h, uint64_t out[6]) {
   return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_merge_stats: null argument"); eng(h)->merge_stats(out); });
+}
+int drf_transform_map(drf_t *h, const char *src_path, const float T16[16], const char *dst_path, size_t chunk_blocks) {
+  return guarded([&] { eng(h)->transform_map(src_path, T16, dst_path, chunk_blocks); });
+}
+int drf_transform_stats(drf_t *h, uint64_t out[6]) {
+  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_transform_stats: null argument"); eng(h)->transform_stats(out); });
 }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }
 int drf_render_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->render_stats(out); }); }

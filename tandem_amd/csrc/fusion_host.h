@@ -1,7 +1,8 @@
 // fusion_host.h -- the host half of DrFusion's map: block keys, streaming reach bounds, the host block store, the reach balls,
-// the planner of the map-scope mesh pass, and the rule and planner of a map merge.  No device state and no HIP header: plain
-// C++17, so that all of it runs in the CPU tests (tests/cpp/fusion_host_check.cpp, tests/cpp/map_merge_check.cpp).  The engine
-// (dr_fusion.hip) keeps everything that throws or touches the GPU.
+// the planner of the map-scope mesh pass, the rule and planner of a map merge, and the rule and planner of a rigid resample.  No
+// device state and no HIP header: plain C++17, so that all of it runs in the CPU tests (tests/cpp/fusion_host_check.cpp,
+// tests/cpp/map_merge_check.cpp, tests/cpp/map_transform_check.cpp).  The engine (dr_fusion.hip) keeps everything that throws or
+// touches the GPU.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -546,5 +547,166 @@ inline MergePlan plan_merge(const std::vector<unsigned long long> &res, const st
   }
   return p;
 }
+
+// ---- moving a map file into another world frame (drf_transform_map; DESIGN.md §7c "Moving a map into another frame")
+// T16 maps file-world to engine-world, p_engine = R p_file + t; both maps live on the lattice g * voxel_size.  The motion in
+// lattice units, once, in double: R[3 i + j] = (double)T16[4 i + j], tv[j] = (double)T16[4 j + 3] / (double)voxel_size.
+struct MapMotion {
+  double R[9];
+  double tv[3];
+};
+inline MapMotion map_motion(const float *T16, float voxel_size) {
+  MapMotion m;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) m.R[3 * i + j] = (double)T16[4 * i + j];
+    m.tv[i] = (double)T16[4 * i + 3] / (double)voxel_size;
+  }
+  return m;
+}
+inline double det3(const double R[9]) {
+  return R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+}
+// What drf_transform_map accepts: sixteen finite entries, a last row that is exactly 0 0 0 1, pose_is_rigid, det R > 0.  Returns
+// null, or what is wrong.
+inline const char *transform_pose_fault(const float *T16) {
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(T16[i])) return "has a non-finite entry";
+  if (T16[12] != 0.0f || T16[13] != 0.0f || T16[14] != 0.0f || T16[15] != 1.0f) return "has a last row other than 0 0 0 1";
+  if (!pose_is_rigid(T16)) return "is not a rigid motion (R R^T differs from I: scale is not handled)";
+  double R[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) R[3 * i + j] = (double)T16[4 * i + j];
+  if (!(det3(R) > 0.0)) return "is a reflection (det R <= 0)";
+  return nullptr;
+}
+// The rule, stated once for the host and the kernel (k_map_transform compiles this very function for the device): the voxel of the
+// destination lattice point g.  In double, without contraction: d = g - tv, u = R^T d as (R[0][k] d0 + R[1][k] d1) + R[2][k] d2,
+// b = floor(u), f = (float)(u - b).  Corner c = 4 cx + 2 cy + cz has the fp32 weight w_c = (a_x(cx) * a_y(cy)) * a_z(cz) with
+// a_k(0) = 1.0f - f_k, a_k(1) = f_k; it is USED iff w_c != 0 and then reads the source voxel at lattice point b + (cx, cy, cz)
+// through fetch(x, y, z, v[2]) (an absent block, or one outside the key range: weight 0).  If any used corner has weight 0 the
+// result is 8 zero bytes.  Otherwise sdf and each colour channel are the sums of w_c * value over the used corners in ascending c
+// (fp32, the first used term initialises the sum), a colour channel stored as (unsigned char)min(sum + 0.5f, 255.0f), and the
+// weight is the smallest of the used corners' weights.  A partly weighted neighbourhood is refused, not renormalised: DESIGN.md
+// says why.  A voxel is its two little-endian words, as for merge_voxel.
+// Returns 0: no used corner is weighted (empty), 1: written with weight > 0, 2: refused (some used corners weighted, some not).
+template <class Fetch>
+DR_HOST_DEVICE inline int transform_voxel(const MapMotion &m, int gx, int gy, int gz, Fetch &&fetch, uint32_t out[2]) {
+  out[0] = 0; out[1] = 0;
+  const double d0 = (double)gx - m.tv[0], d1 = (double)gy - m.tv[1], d2 = (double)gz - m.tv[2];
+  int b[3];
+  float f[3];
+  for (int k = 0; k < 3; ++k) {
+    const double u = (m.R[k] * d0 + m.R[3 + k] * d1) + m.R[6 + k] * d2;
+    if (!(u > -1073741824.0 && u < 1073741824.0)) return 0;  // far outside the key range (2^23 voxels): every corner is absent
+    const double fl = floor(u);
+    b[k] = (int)fl;
+    f[k] = (float)(u - fl);
+  }
+  const float ax[2] = {1.0f - f[0], f[0]}, ay[2] = {1.0f - f[1], f[1]}, az[2] = {1.0f - f[2], f[2]};
+  bool first = true, any = false, all = true;
+  float s = 0.0f, ch[3] = {0.0f, 0.0f, 0.0f};
+  unsigned wmin = 255u;
+  for (int c = 0; c < 8; ++c) {
+    const int cx = c >> 2, cy = (c >> 1) & 1, cz = c & 1;
+    const float w = (ax[cx] * ay[cy]) * az[cz];
+    if (w == 0.0f) continue;
+    uint32_t v[2];
+    fetch(b[0] + cx, b[1] + cy, b[2] + cz, v);
+    const unsigned wt = v[1] >> 24;
+    if (wt == 0u) { all = false; continue; }
+    any = true;
+    float sc;
+    memcpy(&sc, &v[0], 4);
+    const float ts = w * sc, t0 = w * (float)(v[1] & 255u), t1 = w * (float)((v[1] >> 8) & 255u), t2 = w * (float)((v[1] >> 16) & 255u);
+    if (first) { s = ts; ch[0] = t0; ch[1] = t1; ch[2] = t2; first = false; }
+    else { s = s + ts; ch[0] = ch[0] + t0; ch[1] = ch[1] + t1; ch[2] = ch[2] + t2; }
+    wmin = wt < wmin ? wt : wmin;
+  }
+  if (!all) return any ? 2 : 0;
+  unsigned word = wmin << 24;
+  for (int k = 0; k < 3; ++k) {
+    const float r = ch[k] + 0.5f;
+    word |= (unsigned)(unsigned char)(int)(r < 255.0f ? r : 255.0f) << (8 * k);
+  }
+  memcpy(&out[0], &s, 4);
+  out[1] = word;
+  return 1;
+}
+// The destination block at block coordinates blk: its 512 voxels to dst4096 (index x*64 + y*8 + z).  counts[0] += voxels
+// written with weight > 0, counts[1] += voxels refused.  Returns whether the block holds a weighted voxel (= is written).
+template <class Fetch>
+inline bool transform_block(const MapMotion &m, const int blk[3], Fetch &&fetch, uint8_t *dst4096, uint64_t counts[2]) {
+  bool keep = false;
+  for (int v = 0; v < kBS * kBS * kBS; ++v) {
+    uint32_t o[2];
+    const int r = transform_voxel(m, blk[0] * kBS + (v >> 6), blk[1] * kBS + ((v >> 3) & 7), blk[2] * kBS + (v & 7), fetch, o);
+    memcpy(dst4096 + 8 * v, o, 8);
+    if (r == 1) { keep = true; ++counts[0]; }
+    if (r == 2) ++counts[1];
+  }
+  return keep;
+}
+// Candidate destination blocks, ascending and unique: a superset of every block that can hold a voxel with a used corner inside a
+// source block.  Such a voxel g has u(g) = R^T (g - tv) within one voxel of a lattice point of the block, so u lies in the box
+// [8 b - 1, 8 b + 8]^3 and g = A u + tv in the image of that box, A the inverse of R^T (R itself for an orthogonal R; the inverse is
+// taken so that the argument holds for every R that pose_is_rigid lets through).  The image is convex: it lies within the
+// axis-aligned bounds of its eight corners, which are widened by one voxel for the rounding of either direction.  Blocks outside
+// the key range are left out and *in_range, if given, says whether there were any.  (DESIGN.md §7c writes the argument out.)
+inline std::vector<unsigned long long> plan_transform(const std::vector<unsigned long long> &src_keys, const MapMotion &m, bool *in_range = nullptr) {
+  std::vector<unsigned long long> out;
+  if (in_range) *in_range = true;
+  const double *R = m.R;
+  const double det = det3(R);
+  // A = (R^T)^-1 = cofactor matrix of R over det
+  const double A[9] = {(R[4] * R[8] - R[5] * R[7]) / det, (R[5] * R[6] - R[3] * R[8]) / det, (R[3] * R[7] - R[4] * R[6]) / det,
+                       (R[2] * R[7] - R[1] * R[8]) / det, (R[0] * R[8] - R[2] * R[6]) / det, (R[1] * R[6] - R[0] * R[7]) / det,
+                       (R[1] * R[5] - R[2] * R[4]) / det, (R[2] * R[3] - R[0] * R[5]) / det, (R[0] * R[4] - R[1] * R[3]) / det};
+  auto fdiv = [](long v) { return v < 0 ? (v - kBS + 1) / kBS : v / kBS; };
+  for (unsigned long long key : src_keys) {
+    int c[3]; unpack_key_host(key, c);
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (int e = 0; e < 8; ++e) {
+      const double u[3] = {(double)(c[0] * kBS) + ((e & 4) ? 8.0 : -1.0), (double)(c[1] * kBS) + ((e & 2) ? 8.0 : -1.0), (double)(c[2] * kBS) + ((e & 1) ? 8.0 : -1.0)};
+      for (int a = 0; a < 3; ++a) {
+        const double g = (A[3 * a] * u[0] + A[3 * a + 1] * u[1]) + A[3 * a + 2] * u[2] + m.tv[a];
+        lo[a] = std::min(lo[a], g); hi[a] = std::max(hi[a], g);
+      }
+    }
+    long bl[3], bh[3];
+    bool ok = true;
+    for (int a = 0; a < 3; ++a) {
+      if (!(lo[a] > -1e15 && hi[a] < 1e15)) { ok = false; break; }  // (long) of it would not be defined
+      bl[a] = fdiv((long)std::floor(lo[a]) - 1); bh[a] = fdiv((long)std::ceil(hi[a]) + 1);
+      if (bl[a] < -kKeyBias || bh[a] >= kKeyBias) ok = false;
+    }
+    if (!ok) {
+      if (in_range) *in_range = false;
+      continue;
+    }
+    for (long x = bl[0]; x <= bh[0]; ++x)
+      for (long y = bl[1]; y <= bh[1]; ++y)
+        for (long z = bl[2]; z <= bh[2]; ++z) out.push_back(pack_biased(x, y, z));
+  }
+  std::sort(out.begin(), out.end());
+  out.erase(std::unique(out.begin(), out.end()), out.end());
+  return out;
+}
+// The source as the host holds it for transform_voxel's fetch: key -> block index into voxels (n x 4096 bytes)
+struct HostMapSource {
+  std::unordered_map<unsigned long long, size_t> at;
+  const uint8_t *vox = nullptr;
+  HostMapSource(const std::vector<unsigned long long> &keys, const uint8_t *voxels) : vox(voxels) {
+    at.reserve(keys.size());
+    for (size_t i = 0; i < keys.size(); ++i) at[keys[i]] = i;
+  }
+  void operator()(int x, int y, int z, uint32_t v[2]) const {
+    v[0] = 0; v[1] = 0;
+    const int c[3] = {x >> 3, y >> 3, z >> 3};  // arithmetic shift = floor division by 8
+    unsigned long long k;
+    if (!pack_key_host(c, k)) return;
+    auto it = at.find(k);
+    if (it != at.end()) memcpy(v, vox + it->second * 4096 + (size_t)(((x & 7) << 6) | ((y & 7) << 3) | (z & 7)) * 8, 8);
+  }
+};
 
 }  // namespace dr

@@ -16,7 +16,9 @@
 // blocks from a pinned upload to the pool and publishes them the way k_alloc_commit does.  The map file (drf_save_map /
 // drf_load_map) uses the same two moves: k_map_gather copies pool blocks into a chunk of the file without touching the map,
 // and a load places the file's chunks with k_in_place + k_in_finish.  A merge (drf_merge_map) combines the file's blocks whose
-// key is resident into their pool slots (k_map_merge) and appends those the map lacks (k_in_place_at + k_in_finish).
+// key is resident into their pool slots (k_map_merge) and appends those the map lacks (k_in_place_at + k_in_finish).  A rigid
+// resample (drf_transform_map) does not touch the map at all: k_map_transform reads a source map uploaded for the call and writes
+// blocks of the destination lattice into a chunk of the output file.
 
 struct StreamDev {
   int *ctl;                    // [0] blocks selected (uncapped), [1] holes, [2] tail survivors, [3] table blocks re-inserted,
@@ -294,6 +296,99 @@ __global__ __launch_bounds__(256) void k_in_place_at(const FusionDev d, const un
         table_insert(d, key, p);
         atomicAdd(&d.n_alloc[3], 1);
       }
+    }
+  }
+}
+
+// ---- drf_transform_map: a map file resampled on the lattice of another world frame (the rule: fusion_host.h transform_voxel)
+// slot of block (bx, by, bz) in the ascending key table keys[0, n), or -1 (absent, or outside the key range)
+__device__ __forceinline__ int xf_find(const unsigned long long *__restrict__ keys, int n, int bx, int by, int bz) {
+  const int B = 1 << 20;
+  if (bx < -B || bx >= B || by < -B || by >= B || bz < -B || bz >= B) return -1;
+  const unsigned long long key = ((unsigned long long)(bx + B) << 42) | ((unsigned long long)(by + B) << 21) | (unsigned long long)(bz + B);
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return (lo < n && keys[lo] == key) ? lo : -1;
+}
+// transform_voxel's fetch on the device: the 3^3 source blocks from block nb0 on were resolved once per wave (near[27], LDS);
+// a corner outside them -- which the extent argument below rules out up to rounding -- searches the table itself
+struct XfFetch {
+  const unsigned long long *keys;
+  const uint2 *vox;
+  const int *near;
+  int n, nb0[3];
+  __device__ __forceinline__ void operator()(int x, int y, int z, uint32_t v[2]) const {
+    const int bx = x >> 3, by = y >> 3, bz = z >> 3;
+    const unsigned rx = (unsigned)(bx - nb0[0]), ry = (unsigned)(by - nb0[1]), rz = (unsigned)(bz - nb0[2]);
+    const int slot = (rx < 3u && ry < 3u && rz < 3u) ? near[rx * 9 + ry * 3 + rz] : xf_find(keys, n, bx, by, bz);
+    if (slot < 0) { v[0] = 0; v[1] = 0; return; }
+    const uint2 q = vox[(size_t)slot * 512 + (size_t)(((x & 7) << 6) | ((y & 7) << 3) | (z & 7))];
+    v[0] = q.x; v[1] = q.y;
+  }
+};
+// One wave per destination block dst_keys[i], i in [0, nd) (no grid stride: the workgroup's four waves meet at one barrier), four
+// uint4 = 8 voxels per lane.  The image of a destination block under u = R^T (g - tv) is a rotated 7-voxel cube, at most
+// 7 sqrt(3) + 1 voxels along an axis with its trilinear corners: it spans at most 3 source blocks per axis.  So 27 lanes first
+// resolve the blocks from nb0 = floor(min over the block's 8 corner voxels of floor(u) / 8) on, one binary search each in the
+// source's ascending key table, into LDS, and the 8 corner reads per voxel look blocks up there.
+// kWrite = false, the count pass: flags[i] = the block holds a weighted voxel, counts[0] += voxels with weight > 0,
+// counts[1] += voxels refused (summed across the wave, one atomic each per wave).  kWrite = true, the write pass over the blocks
+// the count pass kept: block i to out + i * 256 (a chunk of the file in mapped pinned memory, written once).
+template <bool kWrite>
+__global__ __launch_bounds__(256) void k_map_transform(const unsigned long long *__restrict__ src_keys, const uint2 *__restrict__ src_vox, int n,
+                                                       const unsigned long long *__restrict__ dst_keys, int nd, const MapMotion m,
+                                                       uint4 *__restrict__ out, int *__restrict__ flags, unsigned long long *__restrict__ counts) {
+  __shared__ int s_near[4][27];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * 4 + wave;
+  const bool live = i < nd;
+  int blk[3] = {0, 0, 0};
+  XfFetch fetch;
+  fetch.keys = src_keys; fetch.vox = src_vox; fetch.near = s_near[wave]; fetch.n = n;
+  fetch.nb0[0] = fetch.nb0[1] = fetch.nb0[2] = 0;
+  if (live) {
+    const unsigned long long key = dst_keys[i];
+    blk[0] = (int)((key >> 42) & 0x1fffff) - (1 << 20);
+    blk[1] = (int)((key >> 21) & 0x1fffff) - (1 << 20);
+    blk[2] = (int)(key & 0x1fffff) - (1 << 20);
+    double lo[3] = {1073741824.0, 1073741824.0, 1073741824.0};
+    for (int e = 0; e < 8; ++e) {
+      const double d0 = (double)(blk[0] * 8 + ((e & 4) ? 7 : 0)) - m.tv[0], d1 = (double)(blk[1] * 8 + ((e & 2) ? 7 : 0)) - m.tv[1],
+                   d2 = (double)(blk[2] * 8 + ((e & 1) ? 7 : 0)) - m.tv[2];
+      for (int k = 0; k < 3; ++k) {
+        const double u = (m.R[k] * d0 + m.R[3 + k] * d1) + m.R[6 + k] * d2;
+        lo[k] = u < lo[k] ? u : lo[k];
+      }
+    }
+    for (int k = 0; k < 3; ++k) {
+      const double c = lo[k] > -1073741824.0 ? lo[k] : -1073741824.0;  // (beyond it transform_voxel reads nothing)
+      fetch.nb0[k] = (int)floor(c) >> 3;
+    }
+    if (lane < 27) s_near[wave][lane] = xf_find(src_keys, n, fetch.nb0[0] + lane / 9, fetch.nb0[1] + (lane / 3) % 3, fetch.nb0[2] + lane % 3);
+  }
+  __syncthreads();
+  unsigned nw = 0, nr = 0;
+  if (live) {
+#pragma unroll 1
+    for (int k = 0; k < 4; ++k) {
+      const int v = 2 * (lane + 64 * k);  // voxels v and v + 1: neighbours along z
+      const int gx = blk[0] * 8 + (v >> 6), gy = blk[1] * 8 + ((v >> 3) & 7), gz = blk[2] * 8 + (v & 7);
+      uint32_t p[2], q[2];
+      const int c0 = transform_voxel(m, gx, gy, gz, fetch, p), c1 = transform_voxel(m, gx, gy, gz + 1, fetch, q);
+      nw += (c0 == 1) + (c1 == 1);
+      nr += (c0 == 2) + (c1 == 2);
+      if (kWrite) out[(size_t)i * 256 + lane + 64 * k] = make_uint4(p[0], p[1], q[0], q[1]);
+    }
+  }
+  if (!kWrite) {
+    for (int off = 32; off > 0; off >>= 1) { nw += __shfl_xor(nw, off); nr += __shfl_xor(nr, off); }
+    if (live && lane == 0) {
+      flags[i] = nw > 0;
+      if (nw) atomicAdd(&counts[0], (unsigned long long)nw);
+      if (nr) atomicAdd(&counts[1], (unsigned long long)nr);
     }
   }
 }

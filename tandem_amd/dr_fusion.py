@@ -278,6 +278,22 @@ class DrFusion:
         check(self._L.drf_merge_stats(self._h, out))
         return tuple(int(v) for v in out)
 
+    def transform_map(self, src, T, dst, chunk_blocks=0):
+        """The map file src moved into this engine's world frame and written to dst: T (4x4, row-major, rigid) maps file-world to
+        engine-world, p_engine = R p_file + t, and the surface is resampled on the engine's lattice (include/dr_mi355x.h
+        drf_transform_map states the rule).  The engine's own map is not touched; merge_map(dst) or load_map(dst) follow.  DrError
+        on a bad motion or another voxel_size (DR_ERR_ARG), a bad file (DR_ERR_IO) or a source that does not fit on the device
+        (DR_ERR_CAPACITY); no partial dst is left."""
+        T = np.ascontiguousarray(T, np.float32).reshape(16)
+        check(self._L.drf_transform_map(self._h, os.fsencode(src), T.ctypes.data_as(C.POINTER(C.c_float)), os.fsencode(dst), int(chunk_blocks)))
+
+    def transform_stats(self):
+        """Last transform_map: (source blocks, candidate destination blocks evaluated, blocks written, voxels written with
+        weight > 0, voxels refused for a partly weighted neighbourhood, device bytes held for the source)."""
+        out = (C.c_uint64 * 6)()
+        check(self._L.drf_transform_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
     def set_render_scope(self, scope, stage_capacity_blocks=0):
         """RENDER_RESIDENT (default): renders read the pool; RENDER_MAP: the pool and the host store -- any pose renders as on an
         engine whose pool never ran out, the stored blocks in reach staged through stage_capacity_blocks blocks of device scratch

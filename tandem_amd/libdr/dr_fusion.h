@@ -100,6 +100,9 @@ public:
   void LoadMapFromFile(std::string const &filename) { check(drf_load_map(impl, filename.c_str(), 0)); }
   // a saved map of the same world merged into the map this DrFusion holds, voxel by voxel (dr_mi355x.h drf_merge_map)
   void MergeMapFromFile(std::string const &filename) { check(drf_merge_map(impl, filename.c_str(), 0)); }
+  // the map file src resampled in this DrFusion's world frame and written to dst: T16 row-major, p_here = R p_file + t, rigid
+  // (dr_mi355x.h drf_transform_map); this DrFusion's own map is not touched, MergeMapFromFile(dst) or LoadMapFromFile(dst) follow
+  void TransformMapFile(std::string const &src, float const *T16, std::string const &dst) { check(drf_transform_map(impl, src.c_str(), T16, dst.c_str(), 0)); }
 
   // Incremental mesh (dr_mi355x.h "incremental mesh", INTEGRATION.md "Incremental mesh"): GetMeshUpdateSync fills dr_mesh_num /
   // dr_mesh_vert / dr_mesh_cols with the triangles of the listed blocks only, and the members below name the blocks: block i has

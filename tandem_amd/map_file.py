@@ -5,6 +5,8 @@
                                                              loads the map into an engine sized for it and meshes it
     python -m tandem_amd.map_file merge OUT IN1 IN2 [IN3 ...] [--max-weight 64]
                                                              IN1 loaded, the others merged into it in order (drf_merge_map), saved
+    python -m tandem_amd.map_file transform IN OUT --pose <16 floats>
+                                                             IN resampled in the frame p_out = R p_in + t (drf_transform_map)
 
 Layout, little-endian, 72 + 4104 n bytes: magic "DRFMAP01", u32 header size 64, u32 block edge 8, u32 bytes per voxel 8,
 f32 voxel_size, u64 n, 32 zero bytes; n ascending u64 packed keys; n x 4096 voxel bytes; u64 checksum."""
@@ -139,6 +141,20 @@ def merge(out, inputs, max_weight=64):
     return stats
 
 
+def transform(src, out, pose, chunk_blocks=0):
+    """transform_map(src, pose, out) in a small engine with src's voxel_size; pose: 16 floats, row-major, rigid.  Returns the
+    transform_stats()."""
+    from .dr_fusion import DrFusion, DrFusionOptions
+    vs = info(src)["voxel_size"]
+    f = DrFusion(DrFusionOptions(voxel_size=vs, num_blocks=8192, num_buckets=8192, num_render_streams=0, height=8, width=8,
+                                 truncation_distance=4 * vs))
+    try:
+        f.transform_map(src, np.asarray(pose, np.float32).reshape(4, 4), out, chunk_blocks)
+        return f.transform_stats()
+    finally:
+        f.close()
+
+
 def main(argv):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m tandem_amd.map_file")
@@ -153,6 +169,10 @@ def main(argv):
     g.add_argument("out")
     g.add_argument("inputs", nargs="+")
     g.add_argument("--max-weight", type=int, default=64)
+    t = sub.add_parser("transform")
+    t.add_argument("src")
+    t.add_argument("out")
+    t.add_argument("--pose", type=float, nargs=16, required=True)
     a = ap.parse_args(argv)
     if a.cmd == "info":
         for k, v in info(a.path).items():
@@ -162,6 +182,9 @@ def main(argv):
             ap.error("merge needs at least two input maps")
         for p, st in zip(a.inputs[1:], merge(a.out, a.inputs, a.max_weight)):
             print("%s: blocks %d added %d combined %d voxels_verbatim %d voxels_averaged %d" % (p, st[0], st[1], st[2] + st[3], st[4], st[5]))
+    elif a.cmd == "transform":
+        st = transform(a.src, a.out, a.pose)
+        print("%s: blocks %d candidates %d written %d voxels %d refused %d" % (a.src, st[0], st[1], st[2], st[3], st[4]))
     else:
         mesh(a.path, a.out, a.lower, a.upper)
     return 0
