@@ -448,6 +448,93 @@ int drf_transform_map(drf_t *h, const char *src_path, const float T16[16], const
  * with weight > 0, [4] destination voxels refused because only part of their neighbourhood was weighted, [5] device bytes held
  * for the source */
 int drf_transform_stats(drf_t *h, uint64_t out[6]);
+/* Registers one map file to another (DESIGN.md §7c "Registering two maps"): finds the rigid motion T, src-world to ref-world,
+ * p_ref = R p_src + t -- the convention of drf_transform_map, so T16_out goes straight into drf_transform_map(h, src, T16_out, dst)
+ * and the result into drf_merge_map of an engine that holds ref.  Both files are truncated signed distance fields of (partly) the
+ * same surface; the call minimises, over the source voxels near the surface, the difference between the source's sdf and the
+ * reference's sdf interpolated at the moved voxel (SDF-to-SDF, Gauss-Newton with Huber weights).  It REFINES: T_init must bring the
+ * source surface inside the reference's truncation band (a few voxels, a few degrees across the map).  There is no damping, no
+ * line search, no coarse-to-fine and no global search; a start outside the basin ends DRF_ALIGN_LOST or in a wrong minimum.
+ * The engine lends its device, its streams, its pinned buffers and its voxel_size; its own map is neither read nor changed, exactly
+ * as for drf_transform_map.  drf_align_system evaluates the system once at T16: the score of a pose hypothesis (sums[27] /
+ * counts[1] is the mean robust squared residual in voxels^2; counts[1] / counts[0] the overlap).
+ * The rule (one text, fusion_host.h, compiled for the host and for the kernel; double and fp32 without contraction):
+ *   motion    Rd[i][j] = T16[4 i + j], tv[j] = T16[4 j + 3] / voxel_size in double, as for drf_transform_map; during the iterations
+ *             the pose is held as (Rd, tv) in double.
+ *   centre    once, from the source's block coordinates, integers in double: c_src[k] = 4 (min_k + max_k + 1) (0 for an empty
+ *             source); per evaluation c_k = ((Rd[k][0] c_src0 + Rd[k][1] c_src1) + Rd[k][2] c_src2) + tv_k.
+ *   sample    a source voxel at lattice point g with weight >= min_weight and |sdf| <= band (fp32 compare).  In double:
+ *             q_k = ((Rd[k][0] g0 + Rd[k][1] g1) + Rd[k][2] g2) + tv_k, b = floor(q), f = (float)(q - b); a q_k that is not
+ *             within (-2^30, 2^30) makes the sample invalid.
+ *   validity  the eight reference voxels at b + (cx, cy, cz) are read (the gradient needs all eight even where f_k == 0); the
+ *             sample is VALID iff all eight have weight >= min_weight; an absent block, or one outside the key range, has weight
+ *             0.  An invalid sample adds nothing to the sums and is counted in counts[2].
+ *   field     fp32, s[cx][cy][cz] the eight sdf values, in this order:
+ *               z: h[cx][cy] = s[cx][cy][1] - s[cx][cy][0];  e[cx][cy] = s[cx][cy][0] + fz * h[cx][cy]
+ *               y: dy[cx] = e[cx][1] - e[cx][0];  d[cx] = e[cx][0] + fy * dy[cx];  hy[cx] = h[cx][0] + fy * (h[cx][1] - h[cx][0])
+ *               x: phi = d[0] + fx * (d[1] - d[0]);  gx = d[1] - d[0];  gy = dy[0] + fx * (dy[1] - dy[0]);
+ *                  gz = hy[0] + fx * (hy[1] - hy[0])
+ *   residual  double: r = ((double)phi - (double)s_src) / (double)voxel_size, n_k = (double)g_k / (double)voxel_size with
+ *             g = (gx, gy, gz) of the field, x = q - c, J = (x1 n2 - x2 n1, x2 n0 - x0 n2, x0 n1 - x1 n0, n0, n1, n2),
+ *             a = |r|, w = a <= (double)huber ? 1.0 : (double)huber / a.
+ *   sums      [0..20] += (w J_i) J_j for i <= j, row-major; [21..26] += (w J_i) r; [27] += (w r) r.
+ *             counts = {samples, valid, invalid}.
+ *   order     per source block, lane l of 64 adds its voxels v = 2 (l + 64 k) and v + 1 for k = 0..3 (voxel index
+ *             x * 64 + y * 8 + z), in that order, to 28 doubles that start at +0.0; then x = x + x[lane ^ off] for off = 32, 16, 8,
+ *             4, 2, 1; the block's 28 values are partial[i], i the block's index in the ascending key table.  Then per component
+ *             lane l adds partial[l], partial[l + 64], ... in ascending order from +0.0, and the same butterfly gives the sum.
+ *   step      H = the symmetric 6x6 of sums[0..20], b = sums[21..26].  Cholesky H = L L^T column by column: the pivot of column j
+ *             is p = H[j][j] - L[j][0]^2 - ... - L[j][j-1]^2 (subtracted in that order); p <= 1e-12 * max_j H[j][j] (or a maximum
+ *             that is not > 0) ends the call DRF_ALIGN_DEGENERATE.  L[j][j] = sqrt(p), L[i][j] = (H[i][j] - L[i][0] L[j][0] - ...
+ *             - L[i][j-1] L[j][j-1]) / L[j][j]; y_i = (-b_i - L[i][0] y_0 - ... - L[i][i-1] y_{i-1}) / L[i][i];
+ *             d_i = (y_i - L[i+1][i] d_{i+1} - ... - L[5][i] d_5) / L[i][i], i descending.  d = (omega, v).
+ *             |omega| = sqrt((o0 o0 + o1 o1) + o2 o2) < eps_rot and |v| < eps_trans (same form): DRF_ALIGN_CONVERGED, the step is
+ *             not applied.  Otherwise a = 1 / sqrt(1 + ((o0 o0 + o1 o1) + o2 o2) / 4), (qw, qx, qy, qz) = (a, (a o0) / 2,
+ *             (a o1) / 2, (a o2) / 2), Rq the rotation matrix of that unit quaternion
+ *               [1 - 2 (qy qy + qz qz), 2 (qx qy - qw qz), 2 (qx qz + qw qy); 2 (qx qy + qw qz), 1 - 2 (qx qx + qz qz),
+ *                2 (qy qz - qw qx); 2 (qx qz - qw qy), 2 (qy qz + qw qx), 1 - 2 (qx qx + qy qy)],
+ *             Rd' = Rq Rd with entries (Rq[i][0] Rd[0][j] + Rq[i][1] Rd[1][j]) + Rq[i][2] Rd[2][j], and with e = tv - c,
+ *             tv'_k = (c_k + ((Rq[k][0] e0 + Rq[k][1] e1) + Rq[k][2] e2)) + v_k: a rotation about the centre.
+ *   loop      evaluate; DRF_ALIGN_LOST if valid < min_valid * samples (in double) or valid < 6; else step; after max_iters
+ *             evaluations DRF_ALIGN_MAX_ITERS.  Only + - * / sqrt and floor are used: no library function whose rounding
+ *             could differ between hosts and the device.
+ * What ends where: CONVERGED and DEGENERATE end on the pose of the last evaluation.  LOST ends on the last pose whose evaluation
+ * was not lost (T_init if the first one was); sums, valid and cost then describe the lost evaluation.  MAX_ITERS applies the
+ * step of its last evaluation: T is one step past the pose that sums, valid and cost describe.
+ * Legality and refusals, in this order: a null argument (opt and res may be null) or an option that is negative or not finite,
+ * DR_ERR_ARG; not where drf_integrate_scan_async is legal, DR_ERR_PROTOCOL; a T that drf_transform_map would refuse, DR_ERR_ARG;
+ * a file that fails the whole-file validation, src first, DR_ERR_IO; a voxel_size whose bits differ from the engine's, src
+ * first, DR_ERR_ARG; DR_ERR_CAPACITY when both maps do not fit on the device together: they are uploaded whole, once per call,
+ * 4104 (n_src + n_ref) bytes plus 224 n_src + 32 for the partial sums and counters, and freed on every way out; a file that
+ * changed between validation and upload, DR_ERR_IO.  src_path == ref_path is allowed (a self-score).
+ * DR_OK means the call ran: a registration that ends DRF_ALIGN_DEGENERATE or DRF_ALIGN_LOST returns DR_OK with res->status set,
+ * T16_out as described above and a message in dr_last_error(). */
+typedef struct {
+  int    max_iters;   /* 0 -> 30 */
+  int    min_weight;  /* 0 -> 1; a voxel counts as observed iff weight >= min_weight */
+  float  band;        /* metres; 0 -> 2 * voxel_size (fp32 product); source voxels with |sdf| <= band are samples */
+  float  huber;       /* voxels; 0 -> 1.0 */
+  double eps_rot;     /* rad; 0 -> 1e-7 */
+  double eps_trans;   /* voxels; 0 -> 1e-5 */
+  double min_valid;   /* share of the samples that must be valid; 0 -> 0.25 */
+} drf_align_options_t;
+enum { DRF_ALIGN_CONVERGED = 0, DRF_ALIGN_MAX_ITERS = 1, DRF_ALIGN_DEGENERATE = 2, DRF_ALIGN_LOST = 3 };
+typedef struct {
+  double   T[16];         /* row-major, src-world -> ref-world, metres: Rd, t_k = tv_k * (double)voxel_size, last row 0 0 0 1 */
+  double   sums[28];      /* the last system evaluated */
+  uint64_t samples, valid0, valid;   /* in band; valid at T_init; valid at the last evaluation */
+  double   cost0, cost;   /* sums[27] / valid at T_init and at the last evaluation (0 where valid is 0) */
+  int      iterations, status;  /* evaluations made; DRF_ALIGN_* */
+} drf_align_result_t;
+/* the system at T16: sums[28] and counts = {samples, valid, invalid} */
+int drf_align_system(drf_t *h, const char *src_path, const char *ref_path, const float T16[16], const drf_align_options_t *opt,
+                     double sums[28], uint64_t counts[3]);
+/* the registration from T_init16; T16_out = res->T rounded to float (it passes drf_transform_map's test of a motion) */
+int drf_align_map(drf_t *h, const char *src_path, const char *ref_path, const float T_init16[16], const drf_align_options_t *opt,
+                  float T16_out[16], drf_align_result_t *res);
+/* last drf_align_system / drf_align_map: [0] source blocks, [1] reference blocks, [2] samples, [3] valid samples at the last
+ * evaluation, [4] system evaluations, [5] device bytes held during the call (all 0 after a call that was refused) */
+int drf_align_stats(drf_t *h, uint64_t out[6]);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

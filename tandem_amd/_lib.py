@@ -135,7 +135,22 @@ SIGNATURES = {
     "drf_merge_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "drf_transform_map": (C.c_int, [vp, C.c_char_p, f32p, C.c_char_p, C.c_size_t]),
     "drf_transform_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_align_system": (C.c_int, [vp, C.c_char_p, C.c_char_p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_align_map": (C.c_int, [vp, C.c_char_p, C.c_char_p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_align_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
+
+
+class AlignOptions(C.Structure):
+    """drf_align_options_t: a zero field means its default."""
+    _fields_ = [("max_iters", C.c_int), ("min_weight", C.c_int), ("band", C.c_float), ("huber", C.c_float),
+                ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("min_valid", C.c_double)]
+
+
+class AlignResultStruct(C.Structure):
+    """drf_align_result_t."""
+    _fields_ = [("T", C.c_double * 16), ("sums", C.c_double * 28), ("samples", C.c_uint64), ("valid0", C.c_uint64), ("valid", C.c_uint64),
+                ("cost0", C.c_double), ("cost", C.c_double), ("iterations", C.c_int), ("status", C.c_int)]
 
 
 HOOKS_LIB_PATH = os.path.join(_HERE, "libdr_mi355x_hooks.so")  # the PARITY build (-DDR_PARITY_HOOKS): superseded kernel generations selectable

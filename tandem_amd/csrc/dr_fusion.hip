@@ -671,6 +671,7 @@ __global__ void k_fill_keys(unsigned long long *keys, size_t n) {
 }
 
 #include "stream_kernels.h"
+#include "align_kernels.h"  // k_map_align / k_align_fold (drf_align_system, drf_align_map)
 
 }  // namespace dr
 #include "mesh_kernels.h"
@@ -1640,6 +1641,113 @@ class FusionEngine {
   }
   void transform_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = xf_stats_[i]; }
 
+  // Two map files registered to each other (the rule: fusion_host.h align_voxel / align_step; DESIGN.md §7c "Registering two maps").
+  // As for transform_map the engine lends its device, int_stream_, the pinned pair and voxel_size, and its own map is neither read
+  // nor changed.  with_align_maps does what both calls share -- the refusals in their order, both files to the device whole (one
+  // allocation: reference voxels and keys, source voxels and keys, partial sums, counters; freed on every way out) -- and hands
+  // body an evaluator: k_map_align + k_align_fold on int_stream_, 28 doubles and 3 counters back through the pinned pair.
+  template <class Body>
+  void with_align_maps(const char *who, const char *src, const char *ref, const float *T16, const drf_align_options_t *opt, Body &&body) {
+    for (auto &v : al_stats_) v = 0;
+    AlignOpt ao;
+    if (const char *bad = align_options(opt, o_.voxel_size, ao)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
+    expect(kIntegrate, (std::string(who) + ": call it where IntegrateScanAsync may be called.").c_str());
+    if (const char *why = transform_pose_fault(T16)) fail(DR_ERR_ARG, "%s: the motion %s", who, why);
+    std::string err;
+    MapReader rs, rr;
+    if (!rs.open(src, err) || !rr.open(ref, err)) fail(DR_ERR_IO, "%s: %s", who, err.c_str());
+    for (const auto *r : {&rs, &rr}) {
+      const float vs = r->voxel_size();
+      if (memcmp(&vs, &o_.voxel_size, 4) != 0) fail(DR_ERR_ARG, "%s: %s has voxel_size %.9g, the engine %.9g", who, r == &rs ? src : ref, vs, o_.voxel_size);
+    }
+    const size_t ns = (size_t)rs.blocks(), nr = (size_t)rr.blocks();
+    if (ns > (size_t)INT_MAX || nr > (size_t)INT_MAX) fail(DR_ERR_CAPACITY, "%s: %zu source and %zu reference blocks exceed the index range", who, ns, nr);
+    DR_HIP(hipSetDevice(device_));
+    // both maps must fit on the device beside what is there (the parity build can lower the limit: the tests' way to this refusal)
+    const size_t bytes = (ns + nr) * 4104 + ns * 224 + 32;
+    {
+      size_t free_b = 0, total_b = 0;
+      DR_HIP(hipMemGetInfo(&free_b, &total_b));
+      if (const char *e = hook_env("DR_TRANSFORM_MAX_BYTES")) free_b = std::min(free_b, (size_t)strtoull(e, nullptr, 10));
+      if (bytes > free_b)
+        fail(DR_ERR_CAPACITY, "%s: %zu bytes of device memory are needed (%zu + %zu blocks), %zu are available: %s and %s", who, bytes, ns, nr, free_b, src, ref);
+    }
+    struct Held {  // device memory of this call only
+      void *p = nullptr;
+      ~Held() { if (p) (void)hipFree(p); }
+    } held;
+    DR_HIP(hipStreamSynchronize(int_stream_));  // the pinned pair is idle: every user of it ends with this
+    if (hipMalloc(&held.p, bytes) != hipSuccess) {
+      held.p = nullptr; (void)hipGetLastError();
+      fail(DR_ERR_CAPACITY, "%s: %zu bytes of device memory are needed (%zu + %zu blocks): %s and %s", who, bytes, ns, nr, src, ref);
+    }
+    al_stats_[0] = ns; al_stats_[1] = nr; al_stats_[5] = bytes;
+    // layout, every part a multiple of 8 bytes: ref voxels, src voxels, ref keys, src keys, partial sums, 3 counters (+ 1 unused)
+    unsigned char *r_vox = (unsigned char *)held.p, *s_vox = r_vox + nr * 4096;
+    unsigned long long *r_keys = (unsigned long long *)(s_vox + ns * 4096), *s_keys = r_keys + nr;
+    double *partial = (double *)(s_keys + ns);
+    unsigned long long *counts = (unsigned long long *)(partial + ns * 28);
+    const size_t chunk = map_chunk(0, std::max(ns, nr));
+    ensure_map_io(chunk);
+    bool ok = true;
+    auto upload = [&](MapReader &rd, const char *path, unsigned char *d_vox, unsigned long long *d_keys) {
+      const size_t n = (size_t)rd.blocks();
+      if (n) DR_HIP(hipMemcpyAsync(d_keys, rd.keys().data(), n * 8, hipMemcpyHostToDevice, int_stream_));
+      for (size_t b = 0; b < n && ok; b += chunk) {  // the file through the pinned pair to the device
+        const size_t cnt = std::min(chunk, n - b);
+        mio_.wait();  // the copy of two chunks ago has left this buffer
+        ok = rd.read(mio_.host(), cnt, err);
+        if (!ok) break;
+        DR_HIP(hipMemcpyAsync(d_vox + b * 4096, mio_.host(), cnt * 4096, hipMemcpyHostToDevice, int_stream_));
+        mio_.record(int_stream_);
+        mio_.flip();
+      }
+      if (ok && !rd.verified()) { ok = false; err = std::string("map file ") + path + " changed while it was read"; }
+    };
+    upload(rs, src, s_vox, s_keys);
+    if (ok) upload(rr, ref, r_vox, r_keys);
+    DR_HIP(hipStreamSynchronize(int_stream_));  // (also: the key tables' host memory may go now, and both slots are idle)
+    if (!ok) { al_stats_[5] = 0; fail(DR_ERR_IO, "%s: %s", who, err.c_str()); }
+    double c_src[3];
+    align_centre_src(rs.keys(), c_src);
+    auto eval = [&](const AlignEval &e, double sums[28], uint64_t cnt[3]) {
+      DR_HIP(hipMemsetAsync(counts, 0, 32, int_stream_));
+      if (ns) {
+        hipLaunchKernelGGL(k_map_align, dim3(cdiv((int)ns, 4)), dim3(256), 0, int_stream_, s_keys, (const uint4 *)s_vox, (int)ns, r_keys, (const uint2 *)r_vox,
+                           (int)nr, e, partial, counts);
+        DR_HIP(hipGetLastError());
+      }
+      hipLaunchKernelGGL(k_align_fold, dim3(28), dim3(64), 0, int_stream_, partial, (int)ns, counts, (double *)mio_.dev());
+      DR_HIP(hipGetLastError());
+      DR_HIP(hipStreamSynchronize(int_stream_));
+      memcpy(sums, mio_.host(), 224);
+      memcpy(cnt, mio_.host() + 224, 24);
+      al_stats_[2] = cnt[0]; al_stats_[3] = cnt[1]; ++al_stats_[4];
+    };
+    body(ao, c_src, eval);
+  }
+  void align_system(const char *src, const char *ref, const float *T16, const drf_align_options_t *opt, double *sums, uint64_t *counts) {
+    if (!src || !ref || !T16 || !sums || !counts) fail(DR_ERR_ARG, "drf_align_system: null argument");
+    with_align_maps("drf_align_system", src, ref, T16, opt, [&](const AlignOpt &ao, const double c_src[3], auto &eval) {
+      eval(align_eval(map_motion(T16, o_.voxel_size), c_src, ao, o_.voxel_size), sums, counts);
+    });
+  }
+  // returns what dr_last_error() says after a registration that ran but found no pose (empty otherwise)
+  std::string align_map(const char *src, const char *ref, const float *T16, const drf_align_options_t *opt, float *T16_out, drf_align_result_t *res) {
+    if (!src || !ref || !T16 || !T16_out) fail(DR_ERR_ARG, "drf_align_map: null argument");
+    drf_align_result_t r;
+    with_align_maps("drf_align_map", src, ref, T16, opt, [&](const AlignOpt &ao, const double c_src[3], auto &eval) {
+      align_loop(eval, map_motion(T16, o_.voxel_size), c_src, ao, o_.voxel_size, r);
+    });
+    for (int i = 0; i < 16; ++i) T16_out[i] = (float)r.T[i];
+    if (res) *res = r;
+    if (r.status != DRF_ALIGN_DEGENERATE && r.status != DRF_ALIGN_LOST) return std::string();
+    // the reason first and no fixed buffer: two paths of any length must not cut it off
+    return std::string("drf_align_map: the registration ") + align_status_name(r.status) + " after " + std::to_string(r.iterations) + " evaluations (" +
+           std::to_string((unsigned long long)r.valid) + " of " + std::to_string((unsigned long long)r.samples) + " samples valid): " + src + " to " + ref;
+  }
+  void align_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = al_stats_[i]; }
+
  private:
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
@@ -2237,6 +2345,7 @@ class FusionEngine {
   DeviceBuf<unsigned long long> mg_counts_;  // drf_merge_map: voxels of case 2 and case 3 counted by k_map_merge
   uint64_t mg_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_merge_stats
   uint64_t xf_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_transform_stats
+  uint64_t al_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_align_stats
 };
 
 }  // namespace dr
@@ -2370,6 +2479,21 @@ int drf_transform_map(drf_t *h, const char *src_path, const float T16[16], const
 }
 int drf_transform_stats(drf_t *h, uint64_t out[6]) {
   return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_transform_stats: null argument"); eng(h)->transform_stats(out); });
+}
+int drf_align_system(drf_t *h, const char *src_path, const char *ref_path, const float T16[16], const drf_align_options_t *opt, double sums[28],
+                     uint64_t counts[3]) {
+  return guarded([&] { eng(h)->align_system(src_path, ref_path, T16, opt, sums, counts); });
+}
+int drf_align_map(drf_t *h, const char *src_path, const char *ref_path, const float T_init16[16], const drf_align_options_t *opt, float T16_out[16],
+                  drf_align_result_t *res) {
+  // DEGENERATE and LOST are results, not failures: DR_OK, with the reason where a failure's message would be
+  std::string note;
+  const int rc = guarded([&] { note = eng(h)->align_map(src_path, ref_path, T_init16, opt, T16_out, res); });
+  if (rc == DR_OK && !note.empty()) dr::last_error_slot() = note;
+  return rc;
+}
+int drf_align_stats(drf_t *h, uint64_t out[6]) {
+  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_align_stats: null argument"); eng(h)->align_stats(out); });
 }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }
 int drf_render_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->render_stats(out); }); }

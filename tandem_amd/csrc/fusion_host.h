@@ -1,8 +1,8 @@
 // fusion_host.h -- the host half of DrFusion's map: block keys, streaming reach bounds, the host block store, the reach balls,
-// the planner of the map-scope mesh pass, the rule and planner of a map merge, and the rule and planner of a rigid resample.  No
-// device state and no HIP header: plain C++17, so that all of it runs in the CPU tests (tests/cpp/fusion_host_check.cpp,
-// tests/cpp/map_merge_check.cpp, tests/cpp/map_transform_check.cpp).  The engine (dr_fusion.hip) keeps everything that throws or
-// touches the GPU.
+// the planner of the map-scope mesh pass, the rule and planner of a map merge, the rule and planner of a rigid resample, and the
+// rule, step and host driver of a map-to-map registration.  No device state and no HIP header: plain C++17, so that all of it runs
+// in the CPU tests (tests/cpp/fusion_host_check.cpp, tests/cpp/map_merge_check.cpp, tests/cpp/map_transform_check.cpp,
+// tests/cpp/map_align_check.cpp).  The engine (dr_fusion.hip) keeps everything that throws or touches the GPU.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -708,5 +708,278 @@ struct HostMapSource {
     if (it != at.end()) memcpy(v, vox + it->second * 4096 + (size_t)(((x & 7) << 6) | ((y & 7) << 3) | (z & 7)) * 8, 8);
   }
 };
+
+// ---- registering two map files (drf_align_system / drf_align_map; DESIGN.md §7c "Registering two maps")
+// T maps src-world to ref-world, p_ref = R p_src + t, held as a MapMotion in double: q = R g + tv takes a source lattice point to
+// reference lattice units.  The cost is the sum over the source's samples of rho(r), r = (phi_ref(q) - s_src) / voxel_size, phi_ref
+// the trilinear interpolation of the reference's sdf, rho Huber's function; one evaluation yields the Gauss-Newton system of it:
+// sums[0..20] = the upper triangle of H = sum w J J^T row-major, sums[21..26] = b = sum w J r, sums[27] = sum w r r.
+// The rule is stated once, here (the header of the C ABI restates it for users): align_voxel is compiled by g++ for the CPU tests
+// and by hipcc for k_map_align, both without contraction, and uses + - * / and floor only.
+#if defined(__HIPCC__)
+#define DR_UNROLL _Pragma("unroll")
+#else
+#define DR_UNROLL
+#endif
+struct AlignOpt {  // drf_align_options_t with its defaults resolved
+  int max_iters, min_weight;
+  float band, huber;
+  double eps_rot, eps_trans, min_valid;
+};
+// null: all defaults.  Returns null, or which option is negative or not finite
+inline const char *align_options(const drf_align_options_t *opt, float voxel_size, AlignOpt &o) {
+  static const drf_align_options_t zero = {0, 0, 0.0f, 0.0f, 0.0, 0.0, 0.0};
+  const drf_align_options_t &u = opt ? *opt : zero;
+  if (u.max_iters < 0) return "max_iters";
+  if (u.min_weight < 0) return "min_weight";
+  if (!(u.band >= 0.0f) || !std::isfinite(u.band)) return "band";
+  if (!(u.huber >= 0.0f) || !std::isfinite(u.huber)) return "huber";
+  if (!(u.eps_rot >= 0.0) || !std::isfinite(u.eps_rot)) return "eps_rot";
+  if (!(u.eps_trans >= 0.0) || !std::isfinite(u.eps_trans)) return "eps_trans";
+  if (!(u.min_valid >= 0.0) || !std::isfinite(u.min_valid)) return "min_valid";
+  o.max_iters = u.max_iters ? u.max_iters : 30;
+  o.min_weight = u.min_weight ? u.min_weight : 1;
+  o.band = u.band != 0.0f ? u.band : 2.0f * voxel_size;
+  o.huber = u.huber != 0.0f ? u.huber : 1.0f;
+  o.eps_rot = u.eps_rot != 0.0 ? u.eps_rot : 1e-7;
+  o.eps_trans = u.eps_trans != 0.0 ? u.eps_trans : 1e-5;
+  o.min_valid = u.min_valid != 0.0 ? u.min_valid : 0.25;
+  return nullptr;
+}
+// what a kernel launch and a host evaluation share besides the pose
+struct AlignEval {
+  MapMotion m;
+  double c[3];        // the centre at this pose: R c_src + tv
+  double huber, vs;   // (double)huber, (double)voxel_size
+  float band;
+  int min_weight;
+};
+// c_src[k] = 4 (min_k + max_k + 1) over the source's block coordinates: the middle of its lattice box, an integer (0 if empty)
+inline void align_centre_src(const std::vector<unsigned long long> &src_keys, double c_src[3]) {
+  c_src[0] = c_src[1] = c_src[2] = 0.0;
+  if (src_keys.empty()) return;
+  int lo[3] = {kKeyBias, kKeyBias, kKeyBias}, hi[3] = {-kKeyBias - 1, -kKeyBias - 1, -kKeyBias - 1};
+  for (unsigned long long k : src_keys) {
+    int c[3]; unpack_key_host(k, c);
+    for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], c[a]); hi[a] = std::max(hi[a], c[a]); }
+  }
+  for (int a = 0; a < 3; ++a) c_src[a] = (double)(4L * ((long)lo[a] + (long)hi[a] + 1L));
+}
+inline AlignEval align_eval(const MapMotion &m, const double c_src[3], const AlignOpt &o, float voxel_size) {
+  AlignEval e;
+  e.m = m;
+  for (int k = 0; k < 3; ++k) e.c[k] = ((m.R[3 * k] * c_src[0] + m.R[3 * k + 1] * c_src[1]) + m.R[3 * k + 2] * c_src[2]) + m.tv[k];
+  e.huber = (double)o.huber; e.vs = (double)voxel_size;
+  e.band = o.band; e.min_weight = o.min_weight;
+  return e;
+}
+// is the source voxel (its two words) a sample?
+DR_HOST_DEVICE inline bool align_is_sample(const uint32_t v[2], const AlignEval &e) {
+  float s;
+  memcpy(&s, &v[0], 4);
+  return (int)(v[1] >> 24) >= e.min_weight && (s < 0.0f ? -s : s) <= e.band;
+}
+// One sample: the source voxel at lattice point (gx, gy, gz) with sdf s_src.  Reads the eight reference voxels through
+// fetch(x, y, z, v[2]) (an absent block: weight 0), and if all eight are observed adds the sample's terms to acc[28] and returns
+// true.  The operations and their order are the rule; the header of the C ABI spells them out.
+template <class Fetch>
+DR_HOST_DEVICE inline bool align_voxel(const AlignEval &e, int gx, int gy, int gz, float s_src, Fetch &&fetch, double acc[28]) {
+  const double g0 = (double)gx, g1 = (double)gy, g2 = (double)gz;
+  double q[3];
+  int b[3];
+  float f[3];
+  DR_UNROLL
+  for (int k = 0; k < 3; ++k) {
+    q[k] = ((e.m.R[3 * k] * g0 + e.m.R[3 * k + 1] * g1) + e.m.R[3 * k + 2] * g2) + e.m.tv[k];
+    if (!(q[k] > -1073741824.0 && q[k] < 1073741824.0)) return false;
+    const double fl = floor(q[k]);
+    b[k] = (int)fl;
+    f[k] = (float)(q[k] - fl);
+  }
+  float s[8];  // index 4 cx + 2 cy + cz
+  DR_UNROLL
+  for (int c = 0; c < 8; ++c) {
+    uint32_t v[2];
+    fetch(b[0] + (c >> 2), b[1] + ((c >> 1) & 1), b[2] + (c & 1), v);
+    if ((int)(v[1] >> 24) < e.min_weight) return false;
+    memcpy(&s[c], &v[0], 4);
+  }
+  float h[4], ez[4];  // index 2 cx + cy
+  DR_UNROLL
+  for (int c = 0; c < 4; ++c) {
+    h[c] = s[2 * c + 1] - s[2 * c];
+    ez[c] = s[2 * c] + f[2] * h[c];
+  }
+  float dy[2], d[2], hy[2];
+  DR_UNROLL
+  for (int c = 0; c < 2; ++c) {
+    dy[c] = ez[2 * c + 1] - ez[2 * c];
+    d[c] = ez[2 * c] + f[1] * dy[c];
+    hy[c] = h[2 * c] + f[1] * (h[2 * c + 1] - h[2 * c]);
+  }
+  const float gxf = d[1] - d[0];
+  const float phi = d[0] + f[0] * gxf;
+  const float gyf = dy[0] + f[0] * (dy[1] - dy[0]);
+  const float gzf = hy[0] + f[0] * (hy[1] - hy[0]);
+  const double r = ((double)phi - (double)s_src) / e.vs;
+  const double n0 = (double)gxf / e.vs, n1 = (double)gyf / e.vs, n2 = (double)gzf / e.vs;
+  const double x0 = q[0] - e.c[0], x1 = q[1] - e.c[1], x2 = q[2] - e.c[2];
+  const double J[6] = {x1 * n2 - x2 * n1, x2 * n0 - x0 * n2, x0 * n1 - x1 * n0, n0, n1, n2};
+  const double a = r < 0.0 ? -r : r;
+  const double w = a <= e.huber ? 1.0 : e.huber / a;
+  int idx = 0;
+  DR_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    const double wj = w * J[i];
+    DR_UNROLL
+    for (int j = i; j < 6; ++j) { acc[idx] = acc[idx] + wj * J[j]; ++idx; }
+    acc[21 + i] = acc[21 + i] + wj * r;
+  }
+  acc[27] = acc[27] + (w * r) * r;
+  return true;
+}
+// x[l] = x[l] + x[l ^ off] for off = 32, 16, 8, 4, 2, 1 over 64 lanes of 28 values: afterwards every lane holds the same sum
+inline void align_butterfly(double x[64][28]) {
+  for (int off = 32; off > 0; off >>= 1) {
+    double y[64][28];
+    for (int l = 0; l < 64; ++l)
+      for (int i = 0; i < 28; ++i) y[l][i] = x[l][i] + x[l ^ off][i];
+    memcpy(x, y, sizeof y);
+  }
+}
+// One source block at block coordinates blk in the wave's order: lane l takes voxels 2 (l + 64 k) and the next, k = 0..3, then the
+// butterfly.  out[28] = the block's sums; counts += {samples, valid, invalid}.
+template <class Fetch>
+inline void align_block(const AlignEval &e, const int blk[3], const uint8_t *src4096, Fetch &&ref, double out[28], uint64_t counts[3]) {
+  double x[64][28];
+  for (int l = 0; l < 64; ++l) {
+    for (int i = 0; i < 28; ++i) x[l][i] = 0.0;
+    for (int k = 0; k < 4; ++k)
+      for (int t = 0; t < 2; ++t) {
+        const int v = 2 * (l + 64 * k) + t;
+        uint32_t w[2];
+        memcpy(w, src4096 + 8 * v, 8);
+        if (!align_is_sample(w, e)) continue;
+        float s;
+        memcpy(&s, &w[0], 4);
+        ++counts[0];
+        if (align_voxel(e, blk[0] * kBS + (v >> 6), blk[1] * kBS + ((v >> 3) & 7), blk[2] * kBS + (v & 7), s, ref, x[l])) ++counts[1];
+        else ++counts[2];
+      }
+  }
+  align_butterfly(x);
+  for (int i = 0; i < 28; ++i) out[i] = x[0][i];
+}
+// The system at one pose over the whole source (keys ascending, n x 4096 bytes): align_block per block into partial[i], then
+// per component lane l adds partial[l], partial[l + 64], ... from +0.0 and the butterfly folds the lanes.
+template <class Fetch>
+inline void align_system_host(const std::vector<unsigned long long> &src_keys, const uint8_t *src_vox, Fetch &&ref, const AlignEval &e, double sums[28],
+                              uint64_t counts[3]) {
+  counts[0] = counts[1] = counts[2] = 0;
+  const size_t n = src_keys.size();
+  std::vector<double> partial(n * 28);
+  for (size_t i = 0; i < n; ++i) {
+    int blk[3]; unpack_key_host(src_keys[i], blk);
+    align_block(e, blk, src_vox + i * 4096, ref, &partial[i * 28], counts);
+  }
+  double x[64][28];
+  for (int l = 0; l < 64; ++l)
+    for (int c = 0; c < 28; ++c) {
+      double a = 0.0;
+      for (size_t i = (size_t)l; i < n; i += 64) a = a + partial[i * 28 + c];
+      x[l][c] = a;
+    }
+  align_butterfly(x);
+  for (int c = 0; c < 28; ++c) sums[c] = x[0][c];
+}
+// One Gauss-Newton step from the system sums at pose m (centre c = e.c of that evaluation).  Returns DRF_ALIGN_DEGENERATE (m
+// unchanged), DRF_ALIGN_CONVERGED (the step is below both thresholds and is not applied) or -1 (m moved).  + - * / sqrt only.
+inline int align_step(const double sums[28], const double c[3], double eps_rot, double eps_trans, MapMotion &m) {
+  double H[6][6], L[6][6] = {{0.0}}, y[6] = {0.0}, d[6] = {0.0};
+  int idx = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { H[i][j] = sums[idx]; H[j][i] = sums[idx]; ++idx; }
+  double top = H[0][0];
+  for (int j = 1; j < 6; ++j) top = H[j][j] > top ? H[j][j] : top;
+  if (!(top > 0.0)) return DRF_ALIGN_DEGENERATE;
+  for (int j = 0; j < 6; ++j) {
+    double p = H[j][j];
+    for (int k = 0; k < j; ++k) p = p - L[j][k] * L[j][k];
+    if (!(p > 1e-12 * top)) return DRF_ALIGN_DEGENERATE;
+    L[j][j] = std::sqrt(p);
+    for (int i = j + 1; i < 6; ++i) {
+      double t = H[i][j];
+      for (int k = 0; k < j; ++k) t = t - L[i][k] * L[j][k];
+      L[i][j] = t / L[j][j];
+    }
+  }
+  for (int i = 0; i < 6; ++i) {
+    double t = -sums[21 + i];
+    for (int k = 0; k < i; ++k) t = t - L[i][k] * y[k];
+    y[i] = t / L[i][i];
+  }
+  for (int i = 5; i >= 0; --i) {
+    double t = y[i];
+    for (int k = i + 1; k < 6; ++k) t = t - L[k][i] * d[k];
+    d[i] = t / L[i][i];
+  }
+  const double oo = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2], vv = (d[3] * d[3] + d[4] * d[4]) + d[5] * d[5];
+  if (!(oo == oo) || !(vv == vv)) return DRF_ALIGN_DEGENERATE;  // a system that held a NaN
+  if (std::sqrt(oo) < eps_rot && std::sqrt(vv) < eps_trans) return DRF_ALIGN_CONVERGED;
+  const double a = 1.0 / std::sqrt(1.0 + oo / 4.0);
+  const double qw = a, qx = (a * d[0]) / 2.0, qy = (a * d[1]) / 2.0, qz = (a * d[2]) / 2.0;
+  const double Rq[9] = {1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qw * qz), 2.0 * (qx * qz + qw * qy),
+                        2.0 * (qx * qy + qw * qz), 1.0 - 2.0 * (qx * qx + qz * qz), 2.0 * (qy * qz - qw * qx),
+                        2.0 * (qx * qz - qw * qy), 2.0 * (qy * qz + qw * qx), 1.0 - 2.0 * (qx * qx + qy * qy)};
+  MapMotion o;
+  const double e[3] = {m.tv[0] - c[0], m.tv[1] - c[1], m.tv[2] - c[2]};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) o.R[3 * i + j] = (Rq[3 * i] * m.R[j] + Rq[3 * i + 1] * m.R[3 + j]) + Rq[3 * i + 2] * m.R[6 + j];
+    o.tv[i] = (c[i] + ((Rq[3 * i] * e[0] + Rq[3 * i + 1] * e[1]) + Rq[3 * i + 2] * e[2])) + d[3 + i];
+  }
+  m = o;
+  return -1;
+}
+// The loop of drf_align_map over any evaluator eval(const AlignEval &, double sums[28], uint64_t counts[3]): the host's
+// (align_maps_host) or the engine's (the kernels).  trace, if given, receives the sums of every evaluation.
+template <class Eval>
+inline void align_loop(Eval &&eval, const MapMotion &m0, const double c_src[3], const AlignOpt &o, float voxel_size, drf_align_result_t &res,
+                       std::vector<std::array<double, 28>> *trace = nullptr) {
+  MapMotion m = m0, good = m0;
+  memset(&res, 0, sizeof res);
+  res.status = DRF_ALIGN_MAX_ITERS;
+  for (int it = 0; it < o.max_iters; ++it) {
+    const AlignEval e = align_eval(m, c_src, o, voxel_size);
+    uint64_t counts[3];
+    eval(e, res.sums, counts);
+    if (trace) { std::array<double, 28> t; memcpy(t.data(), res.sums, sizeof res.sums); trace->push_back(t); }
+    res.iterations = it + 1;
+    res.samples = counts[0]; res.valid = counts[1];
+    res.cost = counts[1] ? res.sums[27] / (double)counts[1] : 0.0;
+    if (it == 0) { res.valid0 = res.valid; res.cost0 = res.cost; }
+    if ((double)counts[1] < o.min_valid * (double)counts[0] || counts[1] < 6) { res.status = DRF_ALIGN_LOST; m = good; break; }
+    good = m;
+    const int s = align_step(res.sums, e.c, o.eps_rot, o.eps_trans, m);
+    if (s >= 0) { res.status = s; break; }
+  }
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) res.T[4 * i + j] = m.R[3 * i + j];
+    res.T[4 * i + 3] = m.tv[i] * (double)voxel_size;
+  }
+  res.T[15] = 1.0;
+}
+inline const char *align_status_name(int s) {
+  static const char *names[] = {"converged", "reached max_iters", "is degenerate (the samples do not constrain all six degrees of freedom)",
+                                "is lost (too few samples have an observed neighbourhood in the reference)"};
+  return s >= 0 && s < 4 ? names[s] : "?";
+}
+// The whole registration on the CPU: the library's reference for drf_align_map, and what the sanitizer program runs.
+inline void align_maps_host(const std::vector<unsigned long long> &src_keys, const uint8_t *src_vox, const HostMapSource &ref, const MapMotion &m0,
+                            const AlignOpt &o, float voxel_size, drf_align_result_t &res, std::vector<std::array<double, 28>> *trace = nullptr) {
+  double c_src[3];
+  align_centre_src(src_keys, c_src);
+  align_loop([&](const AlignEval &e, double sums[28], uint64_t counts[3]) { align_system_host(src_keys, src_vox, ref, e, sums, counts); }, m0, c_src, o,
+             voxel_size, res, trace);
+}
 
 }  // namespace dr

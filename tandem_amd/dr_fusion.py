@@ -1,6 +1,7 @@
 """Python mirror of TANDEM's `DrFusion` operator (tandem/libdr/dr_fusion/src/dr_fusion/dr_fusion.h:18-73)
 on top of the C ABI of libdr_mi355x.so: same method names, call order contract and argument meaning.
 Protocol violations raise DrError (the reference prints and exit()s)."""
+import collections
 import ctypes as C
 import os
 
@@ -26,6 +27,23 @@ RENDER_RESIDENT, RENDER_MAP = 0, 1
 
 
 MESH_UPDATE_MAX_SCANS = 16  # DRF_MESH_UPDATE_MAX_SCANS: one scan more between two updates makes the next one full
+# drf_align_result_t.status
+ALIGN_CONVERGED, ALIGN_MAX_ITERS, ALIGN_DEGENERATE, ALIGN_LOST = 0, 1, 2, 3
+ALIGN_STATUS = ("converged", "max_iters", "degenerate", "lost")
+
+
+class AlignResult(collections.namedtuple("AlignResult", "T T32 sums samples valid0 valid cost0 cost iterations status")):
+    """drf_align_result_t: T (4, 4) float64 src-world to ref-world in metres, T32 the same rounded to float32 (what transform_map
+    takes), sums (28,) the last system evaluated, samples / valid0 / valid, cost0 / cost, iterations, status (ALIGN_*)."""
+    __slots__ = ()
+
+
+class AlignError(RuntimeError):
+    """A registration that ran but found no pose (ALIGN_DEGENERATE, ALIGN_LOST); .result is the AlignResult."""
+
+    def __init__(self, result, msg):
+        super().__init__(msg)
+        self.result = result
 
 
 def pack_block_key(coords):
@@ -292,6 +310,50 @@ class DrFusion:
         weight > 0, voxels refused for a partly weighted neighbourhood, device bytes held for the source)."""
         out = (C.c_uint64 * 6)()
         check(self._L.drf_transform_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    @staticmethod
+    def _align_options(opt):
+        if not opt:
+            return None
+        unknown = set(opt) - {f[0] for f in _lib.AlignOptions._fields_}
+        if unknown:
+            raise TypeError("unknown align option(s): %s" % ", ".join(sorted(unknown)))
+        return _lib.AlignOptions(**opt)
+
+    def align_system(self, src, ref, T, **opt):
+        """The registration's Gauss-Newton system at the pose T (4x4, row-major, rigid, src-world to ref-world): (sums (28,)
+        float64, (samples, valid, invalid)).  sums[27] / valid is the mean robust squared residual in voxels^2 -- the score of a
+        pose hypothesis -- and valid / samples the overlap.  opt: the fields of drf_align_options_t (include/dr_mi355x.h states
+        the rule).  The engine's own map is not touched."""
+        T = np.ascontiguousarray(T, np.float32).reshape(16)
+        o = self._align_options(opt)
+        sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 3)()
+        check(self._L.drf_align_system(self._h, os.fsencode(src), os.fsencode(ref), fptr(T), C.byref(o) if o else None,
+                                       sums.ctypes.data_as(_lib.f64p), counts))
+        return sums, tuple(int(v) for v in counts)
+
+    def align_map(self, src, ref, T_init=None, raise_on_failure=True, **opt):
+        """Registers the map file src to the map file ref from T_init (default: the identity) and returns an AlignResult; its T32
+        goes straight into transform_map(src, T32, dst), and merge_map(dst) into an engine that holds ref follows.  The call
+        refines: T_init must bring the source surface inside the reference's truncation band.  A registration that ends
+        ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the result) unless raise_on_failure is false."""
+        T = np.ascontiguousarray(np.eye(4) if T_init is None else T_init, np.float32).reshape(16)
+        o = self._align_options(opt)
+        T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
+        check(self._L.drf_align_map(self._h, os.fsencode(src), os.fsencode(ref), fptr(T), C.byref(o) if o else None, fptr(T32), C.byref(r)))
+        res = AlignResult(T=np.array(r.T, np.float64).reshape(4, 4), T32=T32.reshape(4, 4), sums=np.array(r.sums, np.float64), samples=int(r.samples),
+                          valid0=int(r.valid0), valid=int(r.valid), cost0=float(r.cost0), cost=float(r.cost), iterations=int(r.iterations),
+                          status=int(r.status))
+        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
+            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
+        return res
+
+    def align_stats(self):
+        """Last align_system / align_map: (source blocks, reference blocks, samples, valid samples at the last evaluation, system
+        evaluations, device bytes held during the call)."""
+        out = (C.c_uint64 * 6)()
+        check(self._L.drf_align_stats(self._h, out))
         return tuple(int(v) for v in out)
 
     def set_render_scope(self, scope, stage_capacity_blocks=0):

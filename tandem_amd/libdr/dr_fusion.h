@@ -103,6 +103,16 @@ public:
   // the map file src resampled in this DrFusion's world frame and written to dst: T16 row-major, p_here = R p_file + t, rigid
   // (dr_mi355x.h drf_transform_map); this DrFusion's own map is not touched, MergeMapFromFile(dst) or LoadMapFromFile(dst) follow
   void TransformMapFile(std::string const &src, float const *T16, std::string const &dst) { check(drf_transform_map(impl, src.c_str(), T16, dst.c_str(), 0)); }
+  // the map file src registered to the map file ref from T_init16 (null: the identity): T16_out, src-world to ref-world, goes
+  // straight into TransformMapFile(src, T16_out, dst) (dr_mi355x.h drf_align_map; it refines, T_init16 must be within a few voxels).
+  // A registration that finds no pose (degenerate, lost) exits like every other violation; returns the evaluations made.
+  int AlignMapFiles(std::string const &src, std::string const &ref, float const *T_init16, float *T16_out) {
+    static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    drf_align_result_t res;
+    check(drf_align_map(impl, src.c_str(), ref.c_str(), T_init16 ? T_init16 : identity, nullptr, T16_out, &res));
+    if (res.status == DRF_ALIGN_DEGENERATE || res.status == DRF_ALIGN_LOST) { fprintf(stderr, "%s\n", dr_last_error()); exit(EXIT_FAILURE); }
+    return res.iterations;
+  }
 
   // Incremental mesh (dr_mi355x.h "incremental mesh", INTEGRATION.md "Incremental mesh"): GetMeshUpdateSync fills dr_mesh_num /
   // dr_mesh_vert / dr_mesh_cols with the triangles of the listed blocks only, and the members below name the blocks: block i has

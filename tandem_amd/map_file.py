@@ -5,6 +5,10 @@
                                                              loads the map into an engine sized for it and meshes it
     python -m tandem_amd.map_file merge OUT IN1 IN2 [IN3 ...] [--max-weight 64]
                                                              IN1 loaded, the others merged into it in order (drf_merge_map), saved
+    python -m tandem_amd.map_file align SRC REF [--init <16 floats>] [--max-iters N]
+                                                             SRC registered to REF (drf_align_map): one JSON line with the pose
+                                                             SRC-world -> REF-world, status, iterations, samples, valid, costs;
+                                                             the exit status is non-zero unless it converged
     python -m tandem_amd.map_file transform IN OUT --pose <16 floats>
                                                              IN resampled in the frame p_out = R p_in + t (drf_transform_map)
 
@@ -155,6 +159,19 @@ def transform(src, out, pose, chunk_blocks=0):
         f.close()
 
 
+def align(src, ref, init=None, **opt):
+    """align_map(src, ref, init) in a small engine with src's voxel_size; init: 16 floats, row-major, rigid (default: the
+    identity).  Returns the AlignResult whatever its status."""
+    from .dr_fusion import DrFusion, DrFusionOptions
+    vs = info(src)["voxel_size"]
+    f = DrFusion(DrFusionOptions(voxel_size=vs, num_blocks=8192, num_buckets=8192, num_render_streams=0, height=8, width=8,
+                                 truncation_distance=4 * vs))
+    try:
+        return f.align_map(src, ref, None if init is None else np.asarray(init, np.float32).reshape(4, 4), raise_on_failure=False, **opt)
+    finally:
+        f.close()
+
+
 def main(argv):
     import argparse
     ap = argparse.ArgumentParser(prog="python -m tandem_amd.map_file")
@@ -173,6 +190,11 @@ def main(argv):
     t.add_argument("src")
     t.add_argument("out")
     t.add_argument("--pose", type=float, nargs=16, required=True)
+    al = sub.add_parser("align")
+    al.add_argument("src")
+    al.add_argument("ref")
+    al.add_argument("--init", type=float, nargs=16)
+    al.add_argument("--max-iters", type=int, default=0)
     a = ap.parse_args(argv)
     if a.cmd == "info":
         for k, v in info(a.path).items():
@@ -185,6 +207,13 @@ def main(argv):
     elif a.cmd == "transform":
         st = transform(a.src, a.out, a.pose)
         print("%s: blocks %d candidates %d written %d voxels %d refused %d" % (a.src, st[0], st[1], st[2], st[3], st[4]))
+    elif a.cmd == "align":
+        import json
+        from .dr_fusion import ALIGN_CONVERGED, ALIGN_STATUS
+        r = align(a.src, a.ref, a.init, max_iters=a.max_iters)
+        print(json.dumps(dict(pose=[float(v) for v in r.T32.reshape(16)], status=ALIGN_STATUS[r.status], iterations=r.iterations, samples=r.samples,
+                              valid=r.valid, cost0=r.cost0, cost=r.cost)))
+        return 0 if r.status == ALIGN_CONVERGED else 1
     else:
         mesh(a.path, a.out, a.lower, a.upper)
     return 0
