@@ -155,6 +155,19 @@ int drm_debug_conv(int device, const float *in, int D, int H, int W, int Cin, co
 int drm_debug_tail(int device, const float *x, const float *skip, const float *w_deconv, const float *scale8, const float *bias8, const float *w_prob, int D,
                    int h, int w, int qy, int zchunk, int form, float *out);
 
+/* Test hooks of the parity library (libdr_mi355x_hooks.so); in the product library all three return DR_ERR_UNSUPPORTED.  With guards on, every
+ * device allocation of the library (engine tensors, plan uploads, voxel pool, tracker arrays, dr_device_alloc, ...) lies between two guard bands of
+ * guard_bytes each, and guards and payload start as a poison pattern in which every aligned 32-bit word is a quiet NaN (csrc/guard_host.h).  A guard
+ * is compared with the pattern when its buffer is freed and by dr_guard_check; what differs is a violation: buffer label, payload bytes, side, first
+ * and last byte offset relative to the payload edge (front: -1 is the byte before the payload; back: +0 the byte behind it), count.
+ * dr_guard_set: guard_bytes a multiple of 4096, 0 = off; affects later allocations only.
+ * dr_guard_check: scans every live guarded buffer and adds the violations found at frees since the last clear.  out = {live guarded buffers, buffers
+ *   guarded since the last clear, violations, payload bytes of the live guarded buffers}; report (may be NULL): one line per violation, cut at cap.
+ * dr_guard_clear: forgets the violations found at frees and restarts the count of guarded buffers. */
+int dr_guard_set(size_t guard_bytes);
+int dr_guard_check(uint64_t out[4], char *report, size_t cap);
+int dr_guard_clear(void);
+
 /* ------------------------------------------------------------------ DrFusion */
 /* struct DrFusionOptions                                         dr_fusion.h:18-36 (same field order) */
 typedef struct {

@@ -104,6 +104,9 @@ SIGNATURES = {
     "dr_memcpy_d2d": (C.c_int, [vp, vp, C.c_size_t]),
     "dr_memcpy_h2d": (C.c_int, [vp, vp, C.c_size_t]),
     "dr_memcpy_d2h": (C.c_int, [vp, vp, C.c_size_t]),
+    "dr_guard_set": (C.c_int, [C.c_size_t]),
+    "dr_guard_check": (C.c_int, [C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
+    "dr_guard_clear": (C.c_int, []),
     "drm_set_feature_cache": (C.c_int, [vp, C.c_int]),
     "drm_feature_cache_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "drf_bench_sequence": (C.c_int, [vp, vp, vp, f32p, C.c_int, C.c_int, f32p]),

@@ -969,7 +969,7 @@ struct DeviceArena {  // owns small device buffers created while planning (weigh
     ptrs.push_back(d);
     return d;
   }
-  ~DeviceArena() { for (void *p : ptrs) { if (host_only) free(p); else (void)hipFree(p); } }
+  ~DeviceArena() { for (void *p : ptrs) { if (host_only) free(p); else dfree(p); } }
 };
 
 // Measured-best plans for known layer shapes (tools/tune_conv.sh -> conv_tuned.h); anything else uses the cost model.

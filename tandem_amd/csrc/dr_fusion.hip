@@ -1561,8 +1561,8 @@ class FusionEngine {
     }
     struct Held {  // device memory of this call only
       void *p = nullptr;
-      ~Held() { if (p) (void)hipFree(p); }
-      bool take(size_t bytes) { if (hipMalloc(&p, bytes) == hipSuccess) return true; p = nullptr; (void)hipGetLastError(); return false; }
+      ~Held() { dfree(p); }
+      bool take(size_t bytes) { if (device_alloc(&p, bytes) == hipSuccess) return true; p = nullptr; (void)hipGetLastError(); return false; }
     } source, side;
     for (auto &v : xf_stats_) v = 0;
     xf_stats_[0] = n; xf_stats_[1] = cand.size();
@@ -1674,10 +1674,10 @@ class FusionEngine {
     }
     struct Held {  // device memory of this call only
       void *p = nullptr;
-      ~Held() { if (p) (void)hipFree(p); }
+      ~Held() { dfree(p); }
     } held;
     DR_HIP(hipStreamSynchronize(int_stream_));  // the pinned pair is idle: every user of it ends with this
-    if (hipMalloc(&held.p, bytes) != hipSuccess) {
+    if (device_alloc(&held.p, bytes) != hipSuccess) {
       held.p = nullptr; (void)hipGetLastError();
       fail(DR_ERR_CAPACITY, "%s: %zu bytes of device memory are needed (%zu + %zu blocks): %s and %s", who, bytes, ns, nr, src, ref);
     }
@@ -2407,9 +2407,53 @@ int drf_integrate_device(drf_t *h, const void *d_bgr, const void *d_depth, const
   return guarded([&] { eng(h)->integrate_device(d_bgr, d_depth, pose16); });
 }
 int dr_device_alloc(int device, size_t bytes, void **dptr) {
-  return guarded([&] { DR_HIP(hipSetDevice(device)); DR_HIP(hipMalloc(dptr, bytes)); });
+  return guarded([&] { DR_HIP(hipSetDevice(device)); DR_HIP(dr::device_alloc(dptr, bytes, "dr_device_alloc")); });
 }
-int dr_device_free(void *dptr) { return guarded([&] { DR_HIP(hipFree(dptr)); }); }
+int dr_device_free(void *dptr) { return guarded([&] { DR_HIP(dr::device_free(dptr)); }); }
+// The guarded allocator's switch and its check (dr_common.h, guard_host.h): parity build only.
+int dr_guard_set(size_t guard_bytes) {
+  return guarded([&] {
+#ifndef DR_PARITY_HOOKS
+    (void)guard_bytes;
+    dr::fail(DR_ERR_UNSUPPORTED, "dr_guard_set: guarded allocation is built into the parity library (libdr_mi355x_hooks.so, -DDR_PARITY_HOOKS) only");
+#else
+    if (guard_bytes % dr::guard::kGranule) dr::fail(DR_ERR_ARG, "dr_guard_set: the guard size must be a multiple of %zu bytes (0: off)", dr::guard::kGranule);
+    dr::guard::Registry &r = dr::guard::registry();
+    std::lock_guard<std::mutex> lk(r.mu);
+    r.guard_bytes = guard_bytes;
+#endif
+  });
+}
+int dr_guard_check(uint64_t out[4], char *report, size_t cap) {
+  return guarded([&] {
+#ifndef DR_PARITY_HOOKS
+    (void)out; (void)report; (void)cap;
+    dr::fail(DR_ERR_UNSUPPORTED, "dr_guard_check: guarded allocation is built into the parity library (libdr_mi355x_hooks.so, -DDR_PARITY_HOOKS) only");
+#else
+    if (!out) dr::fail(DR_ERR_ARG, "dr_guard_check: null argument");
+    dr::guard::Registry &r = dr::guard::registry();
+    std::lock_guard<std::mutex> lk(r.mu);
+    std::vector<dr::guard::Violation> all = r.sticky;
+    uint64_t bytes = 0;
+    if (!r.live.empty()) DR_HIP(hipDeviceSynchronize());
+    for (auto &kv : r.live) { dr::guard::scan_entry(kv.first, kv.second, all); bytes += kv.second.bytes; }
+    out[0] = r.live.size(); out[1] = r.since_clear; out[2] = all.size(); out[3] = bytes;
+    dr::guard::report(all, report, cap);
+#endif
+  });
+}
+int dr_guard_clear(void) {
+  return guarded([&] {
+#ifndef DR_PARITY_HOOKS
+    dr::fail(DR_ERR_UNSUPPORTED, "dr_guard_clear: guarded allocation is built into the parity library (libdr_mi355x_hooks.so, -DDR_PARITY_HOOKS) only");
+#else
+    dr::guard::Registry &r = dr::guard::registry();
+    std::lock_guard<std::mutex> lk(r.mu);
+    r.sticky.clear();
+    r.since_clear = 0;
+#endif
+  });
+}
 int dr_memcpy_h2d(void *dptr, const void *src, size_t bytes) { return guarded([&] { DR_HIP(hipMemcpy(dptr, src, bytes, hipMemcpyHostToDevice)); }); }
 int dr_memcpy_d2d(void *dst, const void *src, size_t bytes) {
   // a device-to-device hipMemcpy may return before the copy has run, and the engines' streams are non-blocking:

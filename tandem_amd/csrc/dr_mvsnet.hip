@@ -518,19 +518,19 @@ class MvsEngine {
   }
   DevTensor &alloc(const std::string &name, int D, int H, int W, int C, int pad = 0) {
     DevTensor t; t.D = D; t.H = H; t.W = W; t.C = C; t.pad = pad;
-    t.d = dalloc<float>(t.n());
-    if (pad) DR_HIP(hipMemset(t.d, 0, t.n() * 4));  // the border is written once, here; producers only touch the interior
     const std::string key = tprefix_.empty() ? name : tprefix_ + name;  // (the single-view FeatureNet of the feature cache builds into its own names)
+    t.d = dalloc<float>(t.n(), key.c_str());
+    if (pad) DR_HIP(hipMemset(t.d, 0, t.n() * 4));  // the border is written once, here; producers only touch the interior
     tensors_[key] = t;
     return tensors_[key];
   }
   void release() {
-    for (auto &kv : tensors_) (void)hipFree(kv.second.d);
+    for (auto &kv : tensors_) dfree(kv.second.d);
     tensors_.clear();
     ops_.clear();
     ops1_.clear(); fcache_.clear(); fc_.clear(); fn1_ok_ = false; fc_.fast = fc_.fill = false;  // (a new window shape evicts everything: the entries' buffers are in misc_)
     plan_arena_.reset();
-    for (void *p : misc_) (void)hipFree(p);
+    for (void *p : misc_) dfree(p);
     misc_.clear();
   }
 
@@ -1437,8 +1437,9 @@ int drm_debug_conv(int device, const float *in, int D, int H, int W, int Cin, co
     std::vector<float> hin(in, in + (size_t)D * H * W * Cin);
     float *d_in = arena.upload(hin);
     const size_t on = (size_t)oD * oH * oW * Cout;
-    std::vector<float> zero(on, 0.f);
-    float *d_out = arena.upload(zero);
+    // the output starts as the poison pattern (guard_host.h), not as zeros: a position no launch writes is a NaN the caller sees
+    float poison; memcpy(&poison, &guard::kWord, 4);
+    float *d_out = arena.upload(std::vector<float>(on, poison));
     float *d_add = nullptr;
     if (add) {
       const size_t an = add_up2 ? (size_t)oD * (oH / 2) * (oW / 2) * Cout : on;
@@ -1491,7 +1492,8 @@ int drm_debug_tail(int device, const float *x, const float *skip, const float *w
     sb.insert(sb.end(), bias8, bias8 + 8);
     t.sb = arena.upload(sb);
     t.wp = arena.upload(tail_pack_prob(w_prob));
-    float *d_out = arena.upload(std::vector<float>((size_t)D * h * w, -12345.f));
+    float poison; memcpy(&poison, &guard::kWord, 4);  // (guard_host.h: a position the launch does not write stays a NaN)
+    float *d_out = arena.upload(std::vector<float>((size_t)D * h * w, poison));
     t.out = d_out; t.D = D; t.h = h; t.w = w;
     const bool mf = form == 1;  // 1: k_tail_m (matrix pipe), else k_tail (vector pipe)
     t.wmf = mf ? arena.upload(tail_pack_deconv_mfma(w_deconv)) : nullptr;

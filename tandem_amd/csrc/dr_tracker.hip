@@ -441,11 +441,11 @@ class TrackerEngine {
     return d;
   }
   void release() {
-    for (int k = 0; k < 4; ++k) { (void)hipFree(pc_[k]); if (h_pc_[k]) (void)hipHostFree(h_pc_[k]); }
-    for (int k = 0; k < 7; ++k) (void)hipFree(warped_[k]);
-    (void)hipFree(dInew_); if (h_dInew_) (void)hipHostFree(h_dInew_);
-    (void)hipFree(partial_); (void)hipFree(sums_); if (h_sums_) (void)hipHostFree(h_sums_);
-    (void)hipFree(zbuf_); (void)hipFree(rowcnt_); (void)hipFree(up_depth_); (void)hipFree(up_idepth_); (void)hipFree(up_dip_);
+    for (int k = 0; k < 4; ++k) { dfree(pc_[k]); if (h_pc_[k]) (void)hipHostFree(h_pc_[k]); }
+    for (int k = 0; k < 7; ++k) dfree(warped_[k]);
+    dfree(dInew_); if (h_dInew_) (void)hipHostFree(h_dInew_);
+    dfree(partial_); dfree(sums_); if (h_sums_) (void)hipHostFree(h_sums_);
+    dfree(zbuf_); dfree(rowcnt_); dfree(up_depth_); dfree(up_idepth_); dfree(up_dip_);
   }
   int device_, w_, h_;
   float huber_;

@@ -19,7 +19,7 @@ class HipOwner {
   ~HipOwner() {
     if (dev_.empty() && pin_.empty() && ev_.empty() && st_.empty()) return;  // nothing taken: no device of ours to wait for
     (void)hipDeviceSynchronize();
-    for (void *p : dev_) (void)hipFree(p);
+    for (void *p : dev_) dfree(p);
     for (void *p : pin_) (void)hipHostFree(p);
     for (hipEvent_t e : ev_) (void)hipEventDestroy(e);
     for (hipStream_t s : st_) (void)hipStreamDestroy(s);
@@ -61,11 +61,11 @@ class DeviceBuf {
   DeviceBuf() = default;
   DeviceBuf(const DeviceBuf &) = delete;
   void operator=(const DeviceBuf &) = delete;
-  ~DeviceBuf() { (void)hipFree(p_); }
+  ~DeviceBuf() { dfree(p_); }
   void reserve(size_t n, hipStream_t st) {
     if (n <= cap_) return;
     DR_HIP(hipStreamSynchronize(st));
-    if (p_) DR_HIP(hipFree(p_));
+    if (p_) DR_HIP(device_free(p_));
     p_ = nullptr; cap_ = 0;
     p_ = dalloc<T>(n);
     cap_ = n;
