@@ -548,6 +548,76 @@ int drf_align_map(drf_t *h, const char *src_path, const char *ref_path, const fl
 /* last drf_align_system / drf_align_map: [0] source blocks, [1] reference blocks, [2] samples, [3] valid samples at the last
  * evaluation, [4] system evaluations, [5] device bytes held during the call (all 0 after a call that was refused) */
 int drf_align_stats(drf_t *h, uint64_t out[6]);
+/* Locates a depth frame in the map the engine holds (DESIGN.md §7c "Locating a depth frame in the map"): the frame-to-model step.
+ * One depth image (height x width floats, metres, as drf_integrate_scan_async takes it: a sensor frame, a DrMvsnet depth map, a
+ * ray-cast) and a rough pose in, the refined pose in the map's frame out -- the pose16 that drf_integrate_scan_async needs to
+ * continue a map brought in by drf_load_map, the start from which drf_transform_map and drf_merge_map bring a second session over,
+ * and a per-frame drift check of a running session.  The call minimises, over the depth pixels, the map's sdf interpolated at the
+ * pixel's point (depth-to-SDF, Gauss-Newton with Huber weights); it REFINES, as drf_align_map does: pose_init must bring the
+ * points inside the truncation band.  No damping, no coarse-to-fine, no global search.  drf_locate_system evaluates the system
+ * once at pose16: the score of a pose hypothesis (sums[27] / counts[1], counts[1] / counts[0]).
+ * The map is read where it lives, through the dense grid and the far-block table: nothing is uploaded but the depth image (through
+ * the engine's pinned input buffer; the _device forms take a device pointer as drf_integrate_device does -- a rendered depth from
+ * drf_get_render_device, or the dense hand-off, never goes through the host).  The call runs on the integration stream, behind any
+ * pending scan, and returns when it is done.  It neither changes the map nor allocates a block: drf_stats, the export and the next
+ * render are bit-identical with and without it.
+ * SCOPE: the resident map only.  With streaming on, blocks in the host store read as absent (their samples are `unobserved`);
+ * drf_locate_stats()[5] tells how many there are, and drf_stream_in_region brings them back first.  A map-scope variant that
+ * stages stored blocks is not part of this call.
+ * The rule (one text, fusion_host.h, compiled for the host and for the kernel; double and fp32 without contraction; only + - * /
+ * sqrt and floor are used):
+ *   pose      pose16 is the engine's own convention: row-major, camera-to-world, metres.  Rd[i][j] = pose16[4 i + j],
+ *             tv[j] = pose16[4 j + 3] / voxel_size in double; during the iterations the pose is held as (Rd, tv) in double.
+ *   grid      step >= 1 is a pixel stride: Wg = ceil(width / step), Hg = ceil(height / step); grid position n = j * Wg + i is
+ *             pixel (u, v) = (step * i, step * j) with dep = depth[v * width + u].  It is a SAMPLE iff, in fp32 compares,
+ *             dep > 0, dep >= min_sensor_depth and dep <= max_sensor_depth (a NaN is no sample): the pixels k_integrate uses.
+ *   point     double, z = (double)dep, vs = (double)voxel_size: g0 = ((((double)u - (double)cx) / (double)fx) * z) / vs,
+ *             g1 = ((((double)v - (double)cy) / (double)fy) * z) / vs, g2 = z / vs: the camera-frame point in lattice units,
+ *             pixel centres at whole (u, v).  q_k = ((Rd[k][0] g0 + Rd[k][1] g1) + Rd[k][2] g2) + tv_k.  The lattice point g of
+ *             the map sits at world g * voxel_size (what drf_integrate_scan_async and drf_transform_map use): no half-voxel
+ *             offset, and not the ray-cast's dual-grid interpolation.
+ *   field, validity, residual, sums: drf_align_map's from q on, with s_src = 0 -- b = floor(q), f = (float)(q - b), the eight
+ *             voxels at b + (cx, cy, cz); a sample one of whose eight has weight < min_weight (an absent block: weight 0), or
+ *             whose q is not within (-2^30, 2^30), is UNOBSERVED.  One addition: a sample whose eight corners are observed but
+ *             whose fp32 |phi| < band is false is OUTSIDE (the flat region in front of a surface, where the gradient is zero).
+ *             Neither adds to the sums.  r = (double)phi / vs.  counts = {samples, valid, unobserved, outside},
+ *             samples = valid + unobserved + outside.
+ *   centre    c_src = (0, 0, (double)centre_depth / vs); per evaluation c_k = ((Rd[k][0] c_src0 + Rd[k][1] c_src1) +
+ *             Rd[k][2] c_src2) + tv_k.  centre_depth = 0 rotates about the camera centre; the scene's depth conditions the
+ *             system better.
+ *   order     group i covers grid positions 512 i .. 512 i + 511; lane l of 64 adds positions 512 i + l + 64 k, k = 0..7, in
+ *             that order, to 28 doubles from +0.0 (positions >= Wg * Hg are no samples); then x = x + x[lane ^ off] for
+ *             off = 32, 16, 8, 4, 2, 1 gives partial[i]; then drf_align_map's fold over the groups.
+ *   step, loop, statuses: drf_align_map's, unchanged (DRF_ALIGN_*), the loop given {samples, valid, unobserved + outside}; what
+ *             ends where is the same.  res->T is camera-to-world.
+ * Legality and refusals, in this order: a null argument (opt and res may be null) or an option that is negative or not finite,
+ * DR_ERR_ARG naming the option; not where drf_integrate_scan_async is legal, DR_ERR_PROTOCOL; a pose that drf_transform_map would
+ * refuse, DR_ERR_ARG.  DR_OK means the call ran: a refinement that ends DRF_ALIGN_DEGENERATE or DRF_ALIGN_LOST returns DR_OK with
+ * res->status set and a message in dr_last_error(). */
+typedef struct {
+  int    max_iters;     /* 0 -> 30 */
+  int    min_weight;    /* 0 -> 1; a voxel counts as observed iff weight >= min_weight */
+  int    step;          /* pixel stride of the sample grid; 0 -> 1 */
+  float  band;          /* metres; 0 -> truncation_distance; samples with |phi| < band are used */
+  float  huber;         /* voxels; 0 -> 1.0 */
+  float  centre_depth;  /* metres; the centre of rotation lies this far along the optical axis; 0 = the camera centre */
+  double eps_rot;       /* rad; 0 -> 1e-7 */
+  double eps_trans;     /* voxels; 0 -> 1e-5 */
+  double min_valid;     /* share of the samples that must be valid; 0 -> 0.25 */
+} drf_locate_options_t;
+/* the system at pose16: sums[28] and counts = {samples, valid, unobserved, outside} */
+int drf_locate_system(drf_t *h, const float *depth, const float pose16[16], const drf_locate_options_t *opt, double sums[28], uint64_t counts[4]);
+/* the refinement from pose_init16; pose16_out = res->T rounded to float */
+int drf_locate_frame(drf_t *h, const float *depth, const float pose_init16[16], const drf_locate_options_t *opt, float pose16_out[16],
+                     drf_align_result_t *res);
+/* the same with depth in device memory */
+int drf_locate_system_device(drf_t *h, const void *d_depth, const float pose16[16], const drf_locate_options_t *opt, double sums[28],
+                             uint64_t counts[4]);
+int drf_locate_frame_device(drf_t *h, const void *d_depth, const float pose_init16[16], const drf_locate_options_t *opt, float pose16_out[16],
+                            drf_align_result_t *res);
+/* last drf_locate_*: [0] grid positions, [1] samples, [2] valid samples at the last evaluation, [3] system evaluations, [4] device
+ * bytes held during the call, [5] blocks in the host store at the call (all 0 after a call that was refused) */
+int drf_locate_stats(drf_t *h, uint64_t out[6]);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

@@ -141,6 +141,11 @@ SIGNATURES = {
     "drf_align_system": (C.c_int, [vp, C.c_char_p, C.c_char_p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
     "drf_align_map": (C.c_int, [vp, C.c_char_p, C.c_char_p, f32p, C.c_void_p, f32p, C.c_void_p]),
     "drf_align_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_locate_system": (C.c_int, [vp, f32p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_locate_frame": (C.c_int, [vp, f32p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_locate_system_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_locate_frame_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_locate_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
 
 
@@ -148,6 +153,12 @@ class AlignOptions(C.Structure):
     """drf_align_options_t: a zero field means its default."""
     _fields_ = [("max_iters", C.c_int), ("min_weight", C.c_int), ("band", C.c_float), ("huber", C.c_float),
                 ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("min_valid", C.c_double)]
+
+
+class LocateOptions(C.Structure):
+    """drf_locate_options_t: a zero field means its default."""
+    _fields_ = [("max_iters", C.c_int), ("min_weight", C.c_int), ("step", C.c_int), ("band", C.c_float), ("huber", C.c_float),
+                ("centre_depth", C.c_float), ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("min_valid", C.c_double)]
 
 
 class AlignResultStruct(C.Structure):

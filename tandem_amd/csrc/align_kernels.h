@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void k_map_align(const unsigned long long *__r
 
 // The fold over blocks: workgroup c = one wave = component c of 28.  Lane l adds partial[l], partial[l + 64], ... in ascending order
 // from +0.0, then the same butterfly.  out (a pinned buffer the host reads after the stream's synchronisation) receives the 28 sums
-// and, behind them, the three counters.
+// and, behind them, four counters (the registration uses three, its fourth stays 0; k_map_locate all four).
 __global__ __launch_bounds__(64) void k_align_fold(const double *__restrict__ partial, int n, const unsigned long long *__restrict__ counts,
                                                    double *__restrict__ out) {
   const int lane = threadIdx.x, c = blockIdx.x;
@@ -103,5 +103,5 @@ __global__ __launch_bounds__(64) void k_align_fold(const double *__restrict__ pa
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) x = x + __shfl_xor(x, off);
   if (lane == 0) out[c] = x;
-  if (c == 0 && lane < 3) reinterpret_cast<unsigned long long *>(out + 28)[lane] = counts[lane];
+  if (c == 0 && lane < 4) reinterpret_cast<unsigned long long *>(out + 28)[lane] = counts[lane];
 }

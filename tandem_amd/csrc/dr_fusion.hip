@@ -672,6 +672,7 @@ __global__ void k_fill_keys(unsigned long long *keys, size_t n) {
 
 #include "stream_kernels.h"
 #include "align_kernels.h"  // k_map_align / k_align_fold (drf_align_system, drf_align_map)
+#include "locate_kernels.h"  // k_map_locate (drf_locate_system, drf_locate_frame)
 
 }  // namespace dr
 #include "mesh_kernels.h"
@@ -1748,6 +1749,83 @@ class FusionEngine {
   }
   void align_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = al_stats_[i]; }
 
+  // A depth frame located in the map this engine holds (the rule: fusion_host.h locate_pixel / align_point; DESIGN.md §7c "Locating a
+  // depth frame in the map").  The map is read where it lives, through find_block; nothing of it is uploaded, changed or allocated.
+  // with_locate does what both calls share -- the refusals in their order, pending work settled, a host depth image through the
+  // scan's pinned input buffer into device scratch that is sized once (partial sums, counters, the image) -- and hands body an
+  // evaluator: k_map_locate + k_align_fold on int_stream_, 28 doubles and 4 counters back through the pinned pair.
+  template <class Body>
+  void with_locate(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_locate_options_t *opt, Body &&body) {
+    for (auto &v : lc_stats_) v = 0;
+    LocateOpt lo;
+    if (const char *bad = locate_options(opt, o_.truncation_distance, lo)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
+    expect(kIntegrate, (std::string(who) + ": call it where IntegrateScanAsync may be called.").c_str());
+    if (st_radius_ <= 0.0f && !store_.empty())
+      fail(DR_ERR_PROTOCOL, "%s: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", who, store_.size());
+    if (const char *why = transform_pose_fault(pose16)) fail(DR_ERR_ARG, "%s: the pose %s", who, why);
+    settle();  // behind any pending scan; the pinned buffers are idle and every eviction is in the host store
+    const LocateGrid lg = locate_grid(o_, lo.step);
+    const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
+    const size_t max_groups = (npix_ + 511) / 512;  // step = 1
+    const size_t bytes = max_groups * 224 + 32 + npix_ * 4;
+    lc_buf_.reserve(bytes, int_stream_);
+    ensure_map_io(1);
+    double *partial = (double *)lc_buf_.get();
+    unsigned long long *counts = (unsigned long long *)(partial + max_groups * 28);
+    const float *depth = (const float *)d_depth;
+    if (h_depth) {
+      float *mine = (float *)(counts + 4);
+      memcpy(h_depth_in_, h_depth, npix_ * 4);
+      DR_HIP(hipMemcpyAsync(mine, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
+      depth = mine;
+    }
+    lc_stats_[0] = (uint64_t)total; lc_stats_[4] = lc_buf_.capacity(); lc_stats_[5] = store_.size();
+    auto eval = [&](const AlignEval &e, double sums[28], uint64_t c4[4]) {
+      DR_HIP(hipMemsetAsync(counts, 0, 32, int_stream_));
+      hipLaunchKernelGGL(k_map_locate, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, d_, depth, lg, e, groups, total, partial, counts);
+      DR_HIP(hipGetLastError());
+      hipLaunchKernelGGL(k_align_fold, dim3(28), dim3(64), 0, int_stream_, partial, groups, counts, (double *)mio_.dev());
+      DR_HIP(hipGetLastError());
+      DR_HIP(hipStreamSynchronize(int_stream_));
+      memcpy(sums, mio_.host(), 224);
+      memcpy(c4, mio_.host() + 224, 32);
+      lc_stats_[1] = c4[0]; lc_stats_[2] = c4[1]; ++lc_stats_[3];
+    };
+    try {
+      body(lo, eval);
+    } catch (...) {
+      for (auto &v : lc_stats_) v = 0;
+      throw;
+    }
+  }
+  void locate_system(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_locate_options_t *opt, double *sums,
+                     uint64_t *counts) {
+    for (auto &v : lc_stats_) v = 0;
+    if (!(h_depth || d_depth) || !pose16 || !sums || !counts) fail(DR_ERR_ARG, "%s: null argument", who);
+    with_locate(who, h_depth, d_depth, pose16, opt, [&](const LocateOpt &lo, auto &eval) {
+      double c_src[3];
+      locate_centre_src(lo.centre_depth, o_.voxel_size, c_src);
+      eval(align_eval(map_motion(pose16, o_.voxel_size), c_src, lo.a, o_.voxel_size), sums, counts);
+    });
+  }
+  // returns what dr_last_error() says after a refinement that ran but found no pose (empty otherwise)
+  std::string locate_frame(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_locate_options_t *opt, float *pose16_out,
+                           drf_align_result_t *res) {
+    for (auto &v : lc_stats_) v = 0;
+    if (!(h_depth || d_depth) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+    drf_align_result_t r;
+    uint64_t c4[4] = {0, 0, 0, 0};
+    with_locate(who, h_depth, d_depth, pose16, opt, [&](const LocateOpt &lo, auto &eval) { locate_loop(eval, map_motion(pose16, o_.voxel_size), lo, o_.voxel_size, r, c4); });
+    for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
+    if (res) *res = r;
+    if (r.status != DRF_ALIGN_DEGENERATE && r.status != DRF_ALIGN_LOST) return std::string();
+    return std::string(who) + ": the refinement " + align_status_name(r.status) + " after " + std::to_string(r.iterations) + " evaluations (" +
+           std::to_string((unsigned long long)r.valid) + " of " + std::to_string((unsigned long long)r.samples) + " samples valid, " +
+           std::to_string((unsigned long long)c4[2]) + " unobserved, " + std::to_string((unsigned long long)c4[3]) + " outside the band; " +
+           std::to_string(store_.size()) + " blocks are in the host store)";
+  }
+  void locate_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = lc_stats_[i]; }
+
  private:
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
@@ -2346,6 +2424,8 @@ class FusionEngine {
   uint64_t mg_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_merge_stats
   uint64_t xf_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_transform_stats
   uint64_t al_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_align_stats
+  DeviceBuf<unsigned char> lc_buf_;            // drf_locate_*: partial sums, counters and a host-given depth image (sized once)
+  uint64_t lc_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_locate_stats
 };
 
 }  // namespace dr
@@ -2538,6 +2618,30 @@ int drf_align_map(drf_t *h, const char *src_path, const char *ref_path, const fl
 }
 int drf_align_stats(drf_t *h, uint64_t out[6]) {
   return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_align_stats: null argument"); eng(h)->align_stats(out); });
+}
+int drf_locate_system(drf_t *h, const float *depth, const float pose16[16], const drf_locate_options_t *opt, double sums[28], uint64_t counts[4]) {
+  return guarded([&] { eng(h)->locate_system("drf_locate_system", depth, nullptr, pose16, opt, sums, counts); });
+}
+int drf_locate_system_device(drf_t *h, const void *d_depth, const float pose16[16], const drf_locate_options_t *opt, double sums[28], uint64_t counts[4]) {
+  return guarded([&] { eng(h)->locate_system("drf_locate_system_device", nullptr, d_depth, pose16, opt, sums, counts); });
+}
+// DEGENERATE and LOST are results, not failures: DR_OK, with the reason where a failure's message would be (as drf_align_map)
+static int locate_frame_call(drf_t *h, const char *who, const float *depth, const void *d_depth, const float *pose_init16, const drf_locate_options_t *opt,
+                             float *pose16_out, drf_align_result_t *res) {
+  std::string note;
+  const int rc = guarded([&] { note = eng(h)->locate_frame(who, depth, d_depth, pose_init16, opt, pose16_out, res); });
+  if (rc == DR_OK && !note.empty()) dr::last_error_slot() = note;
+  return rc;
+}
+int drf_locate_frame(drf_t *h, const float *depth, const float pose_init16[16], const drf_locate_options_t *opt, float pose16_out[16], drf_align_result_t *res) {
+  return locate_frame_call(h, "drf_locate_frame", depth, nullptr, pose_init16, opt, pose16_out, res);
+}
+int drf_locate_frame_device(drf_t *h, const void *d_depth, const float pose_init16[16], const drf_locate_options_t *opt, float pose16_out[16],
+                            drf_align_result_t *res) {
+  return locate_frame_call(h, "drf_locate_frame_device", nullptr, d_depth, pose_init16, opt, pose16_out, res);
+}
+int drf_locate_stats(drf_t *h, uint64_t out[6]) {
+  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_locate_stats: null argument"); eng(h)->locate_stats(out); });
 }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }
 int drf_render_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->render_stats(out); }); }

@@ -1,8 +1,8 @@
 // fusion_host.h -- the host half of DrFusion's map: block keys, streaming reach bounds, the host block store, the reach balls,
 // the planner of the map-scope mesh pass, the rule and planner of a map merge, the rule and planner of a rigid resample, and the
-// rule, step and host driver of a map-to-map registration.  No device state and no HIP header: plain C++17, so that all of it runs
-// in the CPU tests (tests/cpp/fusion_host_check.cpp, tests/cpp/map_merge_check.cpp, tests/cpp/map_transform_check.cpp,
-// tests/cpp/map_align_check.cpp).  The engine (dr_fusion.hip) keeps everything that throws or touches the GPU.
+// rule, step and host driver of a map-to-map registration and of a depth frame's localisation in the map.  No device state and no
+// HIP header: plain C++17, so that all of it runs in the CPU tests (tests/cpp/fusion_host_check.cpp, tests/cpp/map_merge_check.cpp,
+// tests/cpp/map_transform_check.cpp, tests/cpp/map_align_check.cpp, tests/cpp/map_locate_check.cpp).  The engine (dr_fusion.hip) keeps everything that throws or touches the GPU.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -779,19 +779,22 @@ DR_HOST_DEVICE inline bool align_is_sample(const uint32_t v[2], const AlignEval 
   memcpy(&s, &v[0], 4);
   return (int)(v[1] >> 24) >= e.min_weight && (s < 0.0f ? -s : s) <= e.band;
 }
-// One sample: the source voxel at lattice point (gx, gy, gz) with sdf s_src.  Reads the eight reference voxels through
-// fetch(x, y, z, v[2]) (an absent block: weight 0), and if all eight are observed adds the sample's terms to acc[28] and returns
-// true.  The operations and their order are the rule; the header of the C ABI spells them out.
-template <class Fetch>
-DR_HOST_DEVICE inline bool align_voxel(const AlignEval &e, int gx, int gy, int gz, float s_src, Fetch &&fetch, double acc[28]) {
-  const double g0 = (double)gx, g1 = (double)gy, g2 = (double)gz;
+// One sample at the point g (lattice units of the moving frame, three doubles) with sdf s_src: the body that the registration
+// (align_voxel: g a source lattice point) and the localisation (locate_group: g a depth pixel's point, s_src = 0) share.  Reads the
+// eight reference voxels through fetch(x, y, z, v[2]) (an absent block: weight 0); returns 0 if one of them is not observed (or q
+// lies outside the key range), and otherwise adds the sample's terms to acc[28] and returns 1.  BAND (the localisation only): a
+// sample whose eight corners are observed but whose fp32 |phi| < band is false adds nothing and returns 2 -- it lies in the flat
+// region in front of the surface, where the gradient is zero.  The operations and their order are the rule; the header of the C
+// ABI spells them out.
+template <bool BAND, class Fetch>
+DR_HOST_DEVICE inline int align_point(const AlignEval &e, double g0, double g1, double g2, float s_src, Fetch &&fetch, double acc[28]) {
   double q[3];
   int b[3];
   float f[3];
   DR_UNROLL
   for (int k = 0; k < 3; ++k) {
     q[k] = ((e.m.R[3 * k] * g0 + e.m.R[3 * k + 1] * g1) + e.m.R[3 * k + 2] * g2) + e.m.tv[k];
-    if (!(q[k] > -1073741824.0 && q[k] < 1073741824.0)) return false;
+    if (!(q[k] > -1073741824.0 && q[k] < 1073741824.0)) return 0;
     const double fl = floor(q[k]);
     b[k] = (int)fl;
     f[k] = (float)(q[k] - fl);
@@ -801,7 +804,7 @@ DR_HOST_DEVICE inline bool align_voxel(const AlignEval &e, int gx, int gy, int g
   for (int c = 0; c < 8; ++c) {
     uint32_t v[2];
     fetch(b[0] + (c >> 2), b[1] + ((c >> 1) & 1), b[2] + (c & 1), v);
-    if ((int)(v[1] >> 24) < e.min_weight) return false;
+    if ((int)(v[1] >> 24) < e.min_weight) return 0;
     memcpy(&s[c], &v[0], 4);
   }
   float h[4], ez[4];  // index 2 cx + cy
@@ -821,6 +824,10 @@ DR_HOST_DEVICE inline bool align_voxel(const AlignEval &e, int gx, int gy, int g
   const float phi = d[0] + f[0] * gxf;
   const float gyf = dy[0] + f[0] * (dy[1] - dy[0]);
   const float gzf = hy[0] + f[0] * (hy[1] - hy[0]);
+  if (BAND) {
+    const float ap = phi < 0.0f ? -phi : phi;
+    if (!(ap < e.band)) return 2;
+  }
   const double r = ((double)phi - (double)s_src) / e.vs;
   const double n0 = (double)gxf / e.vs, n1 = (double)gyf / e.vs, n2 = (double)gzf / e.vs;
   const double x0 = q[0] - e.c[0], x1 = q[1] - e.c[1], x2 = q[2] - e.c[2];
@@ -836,7 +843,12 @@ DR_HOST_DEVICE inline bool align_voxel(const AlignEval &e, int gx, int gy, int g
     acc[21 + i] = acc[21 + i] + wj * r;
   }
   acc[27] = acc[27] + (w * r) * r;
-  return true;
+  return 1;
+}
+// One sample of the registration: the source voxel at lattice point (gx, gy, gz) with sdf s_src; true if it was valid.
+template <class Fetch>
+DR_HOST_DEVICE inline bool align_voxel(const AlignEval &e, int gx, int gy, int gz, float s_src, Fetch &&fetch, double acc[28]) {
+  return align_point<false>(e, (double)gx, (double)gy, (double)gz, s_src, fetch, acc) == 1;
 }
 // x[l] = x[l] + x[l ^ off] for off = 32, 16, 8, 4, 2, 1 over 64 lanes of 28 values: afterwards every lane holds the same sum
 inline void align_butterfly(double x[64][28]) {
@@ -870,6 +882,18 @@ inline void align_block(const AlignEval &e, const int blk[3], const uint8_t *src
   align_butterfly(x);
   for (int i = 0; i < 28; ++i) out[i] = x[0][i];
 }
+// k_align_fold on the host: per component lane l adds partial[l], partial[l + 64], ... from +0.0 and the butterfly folds the lanes
+inline void align_fold_host(const double *partial, size_t n, double sums[28]) {
+  double x[64][28];
+  for (int l = 0; l < 64; ++l)
+    for (int c = 0; c < 28; ++c) {
+      double a = 0.0;
+      for (size_t i = (size_t)l; i < n; i += 64) a = a + partial[i * 28 + c];
+      x[l][c] = a;
+    }
+  align_butterfly(x);
+  for (int c = 0; c < 28; ++c) sums[c] = x[0][c];
+}
 // The system at one pose over the whole source (keys ascending, n x 4096 bytes): align_block per block into partial[i], then
 // per component lane l adds partial[l], partial[l + 64], ... from +0.0 and the butterfly folds the lanes.
 template <class Fetch>
@@ -882,15 +906,7 @@ inline void align_system_host(const std::vector<unsigned long long> &src_keys, c
     int blk[3]; unpack_key_host(src_keys[i], blk);
     align_block(e, blk, src_vox + i * 4096, ref, &partial[i * 28], counts);
   }
-  double x[64][28];
-  for (int l = 0; l < 64; ++l)
-    for (int c = 0; c < 28; ++c) {
-      double a = 0.0;
-      for (size_t i = (size_t)l; i < n; i += 64) a = a + partial[i * 28 + c];
-      x[l][c] = a;
-    }
-  align_butterfly(x);
-  for (int c = 0; c < 28; ++c) sums[c] = x[0][c];
+  align_fold_host(partial.data(), n, sums);
 }
 // One Gauss-Newton step from the system sums at pose m (centre c = e.c of that evaluation).  Returns DRF_ALIGN_DEGENERATE (m
 // unchanged), DRF_ALIGN_CONVERGED (the step is below both thresholds and is not applied) or -1 (m moved).  + - * / sqrt only.
@@ -980,6 +996,117 @@ inline void align_maps_host(const std::vector<unsigned long long> &src_keys, con
   align_centre_src(src_keys, c_src);
   align_loop([&](const AlignEval &e, double sums[28], uint64_t counts[3]) { align_system_host(src_keys, src_vox, ref, e, sums, counts); }, m0, c_src, o,
              voxel_size, res, trace);
+}
+
+// ---- locating a depth frame in the map (drf_locate_system / drf_locate_frame; DESIGN.md §7c "Locating a depth frame in the map")
+// T is the engine's pose16: camera-to-world, held as a MapMotion (Rd, tv = t / voxel_size).  The samples are the pixels of a depth
+// image on a grid of stride `step`, each the camera-frame point g = ((u - cx) / fx * z, (v - cy) / fy * z, z) / voxel_size in
+// double; from q = Rd g + tv on a sample is align_point's, with s_src = 0 and the band test on phi.  The lattice point g of the map
+// sits at world g * voxel_size, as for k_integrate and transform_voxel: no half-voxel offset.  Stated once, here; the header of
+// the C ABI restates it for users.  Compiled by g++ for the CPU tests and by hipcc for k_map_locate, both without contraction.
+struct LocateOpt {  // drf_locate_options_t with its defaults resolved
+  AlignOpt a;
+  int step;
+  float centre_depth;
+};
+// null: all defaults (band: the engine's truncation_distance).  Returns null, or which option is negative or not finite
+inline const char *locate_options(const drf_locate_options_t *opt, float truncation_distance, LocateOpt &o) {
+  static const drf_locate_options_t zero = {0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0, 0.0, 0.0};
+  const drf_locate_options_t &u = opt ? *opt : zero;
+  if (u.step < 0) return "step";
+  if (!(u.centre_depth >= 0.0f) || !std::isfinite(u.centre_depth)) return "centre_depth";
+  const drf_align_options_t a = {u.max_iters, u.min_weight, u.band, u.huber, u.eps_rot, u.eps_trans, u.min_valid};
+  if (const char *bad = align_options(&a, 1.0f, o.a)) return bad;
+  if (u.band == 0.0f) o.a.band = truncation_distance;
+  o.step = u.step ? u.step : 1;
+  o.centre_depth = u.centre_depth;
+  return nullptr;
+}
+// the sample grid and the camera: what a kernel launch and a host evaluation share besides AlignEval
+struct LocateGrid {
+  int W, H, step, Wg, Hg;  // Wg = ceil(W / step), Hg = ceil(H / step): Wg * Hg grid positions
+  float fx, fy, cx, cy, min_depth, max_depth;
+};
+inline LocateGrid locate_grid(const drf_options_t &o, int step) {
+  LocateGrid g;
+  g.W = o.width; g.H = o.height; g.step = step;
+  g.Wg = (o.width + step - 1) / step; g.Hg = (o.height + step - 1) / step;
+  g.fx = o.fx; g.fy = o.fy; g.cx = o.cx; g.cy = o.cy; g.min_depth = o.min_sensor_depth; g.max_depth = o.max_sensor_depth;
+  return g;
+}
+inline long locate_positions(const LocateGrid &g) { return (long)g.Wg * (long)g.Hg; }
+inline long locate_groups(const LocateGrid &g) { return (locate_positions(g) + 511) / 512; }
+inline void locate_centre_src(float centre_depth, float voxel_size, double c_src[3]) {
+  c_src[0] = 0.0; c_src[1] = 0.0; c_src[2] = (double)centre_depth / (double)voxel_size;
+}
+// Grid position n < Wg * Hg: is its pixel a sample (the conditions under which k_integrate uses a pixel; a NaN is none), and if
+// so its camera-frame point g in lattice units.
+DR_HOST_DEVICE inline bool locate_is_sample(const LocateGrid &lg, float dep) { return dep > 0.0f && dep >= lg.min_depth && dep <= lg.max_depth; }
+DR_HOST_DEVICE inline size_t locate_offset(const LocateGrid &lg, int n) {  // of grid position n's pixel in the depth image
+  const int j = n / lg.Wg, i = n - j * lg.Wg;
+  return (size_t)(lg.step * j) * (size_t)lg.W + (size_t)(lg.step * i);
+}
+DR_HOST_DEVICE inline bool locate_pixel(const LocateGrid &lg, double vs, int n, const float *depth, double g[3]) {
+  const int j = n / lg.Wg, i = n - j * lg.Wg;
+  const int u = lg.step * i, v = lg.step * j;
+  const float dep = depth[locate_offset(lg, n)];
+  if (!locate_is_sample(lg, dep)) return false;
+  const double z = (double)dep;
+  g[0] = ((((double)u - (double)lg.cx) / (double)lg.fx) * z) / vs;
+  g[1] = ((((double)v - (double)lg.cy) / (double)lg.fy) * z) / vs;
+  g[2] = z / vs;
+  return true;
+}
+// Group i in the wave's order: lane l takes grid positions 512 i + l + 64 k, k = 0..7 (those >= Wg * Hg are no samples), then the
+// butterfly.  out[28] = the group's sums; counts += {samples, valid, unobserved, outside}.
+template <class Fetch>
+inline void locate_group(const AlignEval &e, const LocateGrid &lg, const float *depth, long i, Fetch &&fetch, double out[28], uint64_t counts[4]) {
+  double x[64][28];
+  const long total = locate_positions(lg);
+  for (int l = 0; l < 64; ++l) {
+    for (int c = 0; c < 28; ++c) x[l][c] = 0.0;
+    for (int k = 0; k < 8; ++k) {
+      const long n = 512 * i + l + 64 * k;
+      double g[3];
+      if (n >= total || !locate_pixel(lg, e.vs, (int)n, depth, g)) continue;
+      ++counts[0];
+      const int r = align_point<true>(e, g[0], g[1], g[2], 0.0f, fetch, x[l]);
+      ++counts[r == 1 ? 1 : r == 0 ? 2 : 3];
+    }
+  }
+  align_butterfly(x);
+  for (int c = 0; c < 28; ++c) out[c] = x[0][c];
+}
+// The system at one pose over the whole sample grid: locate_group per group into partial[i], then k_align_fold's fold.
+template <class Fetch>
+inline void locate_system_host(const LocateGrid &lg, const float *depth, Fetch &&fetch, const AlignEval &e, double sums[28], uint64_t counts[4]) {
+  counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  const size_t n = (size_t)locate_groups(lg);
+  std::vector<double> partial(n * 28);
+  for (size_t i = 0; i < n; ++i) locate_group(e, lg, depth, (long)i, fetch, &partial[i * 28], counts);
+  align_fold_host(partial.data(), n, sums);
+}
+// align_loop over a localisation's evaluator eval(const AlignEval &, double sums[28], uint64_t counts[4]): the loop is given
+// {samples, valid, unobserved + outside}.  last4, if given, receives the four counters of the last evaluation.
+template <class Eval>
+inline void locate_loop(Eval &&eval, const MapMotion &m0, const LocateOpt &o, float voxel_size, drf_align_result_t &res, uint64_t *last4 = nullptr,
+                        std::vector<std::array<double, 28>> *trace = nullptr) {
+  double c_src[3];
+  locate_centre_src(o.centre_depth, voxel_size, c_src);
+  align_loop([&](const AlignEval &e, double sums[28], uint64_t counts[3]) {
+    uint64_t c4[4];
+    eval(e, sums, c4);
+    counts[0] = c4[0]; counts[1] = c4[1]; counts[2] = c4[2] + c4[3];
+    if (last4) memcpy(last4, c4, sizeof c4);
+  }, m0, c_src, o.a, voxel_size, res, trace);
+}
+// The whole refinement on the CPU over a HostMapSource or any fetch: the library's reference for drf_locate_frame, and what the
+// sanitizer program runs.
+template <class Fetch>
+inline void locate_frame_host(const LocateGrid &lg, const float *depth, Fetch &&fetch, const MapMotion &m0, const LocateOpt &o, float voxel_size,
+                              drf_align_result_t &res, std::vector<std::array<double, 28>> *trace = nullptr) {
+  locate_loop([&](const AlignEval &e, double sums[28], uint64_t c4[4]) { locate_system_host(lg, depth, fetch, e, sums, c4); }, m0, o, voxel_size, res,
+              nullptr, trace);
 }
 
 }  // namespace dr

@@ -356,6 +356,63 @@ class DrFusion:
         check(self._L.drf_align_stats(self._h, out))
         return tuple(int(v) for v in out)
 
+    # ---- locating a depth frame in the map (include/dr_mi355x.h drf_locate_frame, DESIGN.md "Locating a depth frame in the map") ----
+    @staticmethod
+    def _locate_options(opt):
+        if not opt:
+            return None
+        unknown = set(opt) - {f[0] for f in _lib.LocateOptions._fields_}
+        if unknown:
+            raise TypeError("unknown locate option(s): %s" % ", ".join(sorted(unknown)))
+        return _lib.LocateOptions(**opt)
+
+    def _locate_depth(self, depth):
+        """(is a device pointer, the argument, what keeps it alive)"""
+        if isinstance(depth, (int, np.integer)):
+            return True, C.c_void_p(int(depth)), None
+        depth = np.ascontiguousarray(depth, np.float32)
+        assert depth.size == self._hw[0] * self._hw[1]
+        return False, fptr(depth), depth
+
+    def locate_system(self, depth, pose, **opt):
+        """The localisation's Gauss-Newton system of the depth image (H*W float32 metres, or an integer device pointer to one) at
+        the pose (16 float32, row-major, camera-to-world) against the map this engine holds: (sums (28,) float64, (samples, valid,
+        unobserved, outside)).  sums[27] / valid is the mean robust squared residual in voxels^2, the score of a pose hypothesis.
+        opt: the fields of drf_locate_options_t.  The map is not touched."""
+        dev, d, keep = self._locate_depth(depth)
+        pose = np.ascontiguousarray(pose, np.float32).reshape(16)
+        o = self._locate_options(opt)
+        sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 4)()
+        call = self._L.drf_locate_system_device if dev else self._L.drf_locate_system
+        check(call(self._h, d, fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
+        return sums, tuple(int(v) for v in counts)
+
+    def locate_frame(self, depth, pose_init, raise_on_failure=True, **opt):
+        """Refines pose_init (camera-to-world) so that the depth image lies on the surface of the map this engine holds and returns
+        an AlignResult (T, T32: camera-to-world); T32 is the pose IntegrateScanAsync takes to continue the map.  The call refines:
+        pose_init must bring the points inside the truncation band.  Only resident blocks are read (locate_stats()[5] counts the
+        blocks in the host store).  A refinement that ends ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the
+        result) unless raise_on_failure is false."""
+        dev, d, keep = self._locate_depth(depth)
+        pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
+        o = self._locate_options(opt)
+        T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
+        call = self._L.drf_locate_frame_device if dev else self._L.drf_locate_frame
+        check(call(self._h, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
+        res = AlignResult(T=np.array(r.T, np.float64).reshape(4, 4), T32=T32.reshape(4, 4), sums=np.array(r.sums, np.float64), samples=int(r.samples),
+                          valid0=int(r.valid0), valid=int(r.valid), cost0=float(r.cost0), cost=float(r.cost), iterations=int(r.iterations),
+                          status=int(r.status))
+        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
+            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
+        return res
+
+    def locate_stats(self):
+        """Last locate_system / locate_frame: (grid positions, samples, valid samples at the last evaluation, system evaluations,
+        device bytes held during the call, blocks in the host store at the call)."""
+        out = (C.c_uint64 * 6)()
+        check(self._L.drf_locate_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
     def set_render_scope(self, scope, stage_capacity_blocks=0):
         """RENDER_RESIDENT (default): renders read the pool; RENDER_MAP: the pool and the host store -- any pose renders as on an
         engine whose pool never ran out, the stored blocks in reach staged through stage_capacity_blocks blocks of device scratch

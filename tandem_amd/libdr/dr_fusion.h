@@ -113,6 +113,16 @@ public:
     if (res.status == DRF_ALIGN_DEGENERATE || res.status == DRF_ALIGN_LOST) { fprintf(stderr, "%s\n", dr_last_error()); exit(EXIT_FAILURE); }
     return res.iterations;
   }
+  // a depth frame (height x width floats, metres) located in the map this object holds, from the rough camera-to-world pose
+  // pose_init16: pose16_out is the pose IntegrateScanAsync takes to continue the map (dr_mi355x.h drf_locate_frame; it refines,
+  // pose_init16 must bring the points inside the truncation band).  Returns the status, DRF_ALIGN_*: a frame that finds no pose
+  // (DRF_ALIGN_DEGENERATE, DRF_ALIGN_LOST: pose16_out is then no better than pose_init16, dr_last_error() says why) is an answer a
+  // tracker acts on, not a violation.
+  int LocateDepthFrame(float const *depth, float const *pose_init16, float *pose16_out) {
+    drf_align_result_t res;
+    check(drf_locate_frame(impl, depth, pose_init16, nullptr, pose16_out, &res));
+    return res.status;
+  }
 
   // Incremental mesh (dr_mi355x.h "incremental mesh", INTEGRATION.md "Incremental mesh"): GetMeshUpdateSync fills dr_mesh_num /
   // dr_mesh_vert / dr_mesh_cols with the triangles of the listed blocks only, and the members below name the blocks: block i has
