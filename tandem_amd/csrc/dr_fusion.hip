@@ -677,6 +677,7 @@ __global__ void k_fill_keys(unsigned long long *keys, size_t n) {
 }  // namespace dr
 #include "mesh_kernels.h"
 #include "mesh_update_kernels.h"
+#include "map_ops.h"  // MapIo: what the map-file operations share; drf_transform_map / drf_align_* whole
 namespace dr {
 
 // cofactor inverse on the host in the reference's term order (matrix_utils.h:958-1083), fp32, no contraction
@@ -732,7 +733,7 @@ class FusionEngine {
   };
 
  public:
-  FusionEngine(const drf_options_t &o, int device) : device_(device), o_(o) {
+  FusionEngine(const drf_options_t &o, int device) : device_(device), o_(o), mio_(own_, device, o.voxel_size, (size_t)std::min(o.num_blocks, kStageBlocks)) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= device) fail(DR_ERR_DEVICE, "DrFusion: no HIP device %d (found %d) -- the MI355X path has no CPU fallback", device, n);
     if (o.block_size != 8) fail(DR_ERR_UNSUPPORTED, "DrFusion: block_size must be 8 (got %d)", o.block_size);
@@ -747,7 +748,7 @@ class FusionEngine {
     DR_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
     int lo = kDefaultFusionPriority == 2 ? greatest : (kDefaultFusionPriority == 1 ? 0 : least);
     if (const char *e = getenv("DR_FUSION_PRIORITY")) lo = !strcmp(e, "high") ? greatest : (!strcmp(e, "normal") ? 0 : (!strcmp(e, "low") ? least : lo));
-    int_stream_ = own_.stream(lo);
+    int_stream_ = mio_.stream = own_.stream(lo);
     npix_ = (size_t)o.height * o.width;
     size_t cap = 1024;
     const size_t want = std::max((size_t)o.num_buckets * (size_t)o.bucket_size, (size_t)2 * o.num_blocks);
@@ -1346,7 +1347,7 @@ class FusionEngine {
     keys.reserve(n); stored.reserve(n);
     const BlockRange all{{INT_MIN, INT_MIN, INT_MIN}, {INT_MAX, INT_MAX, INT_MAX}};
     for_each_in_range(res, sto, all, [&](unsigned long long key, bool st) { keys.push_back(key); stored.push_back(st ? 1 : 0); });
-    const size_t chunk = map_chunk(chunk_blocks, n), nc = (n + chunk - 1) / chunk;
+    const size_t chunk = mio_.chunk(chunk_blocks, n), nc = (n + chunk - 1) / chunk;
     // per chunk the resident blocks rb[c] .. rb[c + 1] of the sorted pairs; each one's position within its chunk
     std::vector<size_t> rb(nc + 1, 0);
     std::vector<int> dst;
@@ -1354,34 +1355,25 @@ class FusionEngine {
     for (size_t i = 0; i < n; ++i)
       if (!stored[i]) { ++rb[i / chunk + 1]; dst.push_back((int)(i % chunk)); }
     for (size_t c = 0; c < nc; ++c) rb[c + 1] += rb[c];
-    if (nres > 0) DR_HIP(hipMemcpy(mio_dst_.get(), dst.data(), (size_t)nres * 4, hipMemcpyHostToDevice));
-    ensure_map_io(chunk);
+    if (nres > 0) DR_HIP(hipMemcpy(mio_.dst.get(), dst.data(), (size_t)nres * 4, hipMemcpyHostToDevice));
+    mio_.ensure(chunk);
     std::string err;
     MapWriter w;
     if (!w.open(path, o_.voxel_size, keys.data(), n, err)) fail(DR_ERR_IO, "drf_save_map: %s", err.c_str());
-    auto gather = [&](size_t c) {  // chunk c's resident blocks into the current buffer; nothing is launched for none
-      const int m = (int)(rb[c + 1] - rb[c]);
-      if (m == 0) return;
-      hipLaunchKernelGGL(k_map_gather, dim3(std::min(cdiv(m, 4), 1024)), dim3(256), 0, int_stream_, d_.vox, mio_slot_.get() + rb[c], mio_dst_.get() + rb[c], m,
-                         (uint4 *)mio_.dev());
-      DR_HIP(hipGetLastError());
-      mio_.record(int_stream_);
-    };
-    bool ok = true;
-    if (nc > 0) gather(0);
-    for (size_t c = 0; c < nc && ok; ++c) {
-      const size_t b = c * chunk, m = std::min(chunk, n - b);
-      if (c + 1 < nc) { mio_.flip(); gather(c + 1); mio_.flip(); }  // runs while the host finishes chunk c
-      unsigned char *h = mio_.host();
-      for (size_t i = 0; i < m; ++i)
-        if (stored[b + i]) memcpy(h + i * 4096, store_.get(keys[b + i]), 4096);
-      mio_.wait();
-      ok = w.append(h, m, err);
-      mio_.flip();
-    }
-    ok = ok && w.close(err);
-    DR_HIP(hipStreamSynchronize(int_stream_));  // (a failed write leaves the next chunk's gather in flight)
-    if (!ok) fail(DR_ERR_IO, "drf_save_map: %s", err.c_str());
+    mio_.write_chunks(
+        "drf_save_map", w, n, chunk,
+        [&](size_t c) {  // chunk c's resident blocks into the current buffer; nothing is launched for none
+          const int m = (int)(rb[c + 1] - rb[c]);
+          if (m == 0) return;
+          hipLaunchKernelGGL(k_map_gather, dim3(std::min(cdiv(m, 4), 1024)), dim3(256), 0, int_stream_, d_.vox, mio_.slot.get() + rb[c], mio_.dst.get() + rb[c], m,
+                             (uint4 *)mio_.pair.dev());
+          DR_HIP(hipGetLastError());
+        },
+        [&](size_t c, unsigned char *h) {  // and the stored ones, while that kernel runs
+          const size_t b = c * chunk, m = std::min(chunk, n - b);
+          for (size_t i = 0; i < m; ++i)
+            if (stored[b + i]) memcpy(h + i * 4096, store_.get(keys[b + i]), 4096);
+        });
   }
   // The file validated as a whole first, then its blocks placed: into the pool in the keys' order (streaming off; k_in_place
   // reads one pinned buffer while the host reads the file into the other) or into the host store (streaming on).  A failure
@@ -1396,9 +1388,7 @@ class FusionEngine {
       fail(DR_ERR_PROTOCOL, "drf_load_map: the map is not empty (%d resident blocks, %zu in the host store%s)", nres, store_.size(), pending ? ", an eviction was pending" : "");
     std::string err;
     MapReader rd;
-    if (!rd.open(path, err)) fail(DR_ERR_IO, "drf_load_map: %s", err.c_str());
-    const float vs = rd.voxel_size();
-    if (memcmp(&vs, &o_.voxel_size, 4) != 0) fail(DR_ERR_ARG, "drf_load_map: %s has voxel_size %.9g, the engine %.9g", path, vs, o_.voxel_size);
+    mio_.open_reader("drf_load_map", path, rd);
     const uint64_t n = rd.blocks();
     const bool to_store = st_radius_ > 0.0f;
     if (to_store ? n > (uint64_t)st_host_cap_ : n > (uint64_t)o_.num_blocks)
@@ -1407,33 +1397,24 @@ class FusionEngine {
     mu_force_full_ = true;
     if (n == 0) { loaded_ = true; return; }
     const std::vector<unsigned long long> &keys = rd.keys();
-    const size_t chunk = map_chunk(chunk_blocks, (size_t)n);
-    ensure_map_io(chunk);
-    bool ok = true;
+    const size_t chunk = mio_.chunk(chunk_blocks, (size_t)n);
+    mio_.ensure(chunk);
+    bool ok;
     if (to_store) {  // the next scan's stream_before_scan brings in what lies within the radius
-      for (size_t b = 0; b < n && ok; b += chunk) {
-        const size_t m = std::min(chunk, (size_t)n - b);
-        ok = rd.read(mio_.host(), m, err);
-        for (size_t i = 0; i < m && ok; ++i) store_.put(keys[b + i], mio_.host() + i * 4096);
-      }
-    } else {
-      mio_keys_.reserve((size_t)n, int_stream_);
-      DR_HIP(hipMemcpy(mio_keys_.get(), keys.data(), (size_t)n * 8, hipMemcpyHostToDevice));
+      ok = mio_.read_chunks(rd, chunk, err, [&](size_t b, size_t m, const unsigned char *h, const unsigned char *) {
+        for (size_t i = 0; i < m; ++i) store_.put(keys[b + i], h + i * 4096);
+      });
+    } else {  // k_in_place reads one pinned buffer while the host reads the file into the other
+      mio_.keys.reserve((size_t)n, int_stream_);
+      DR_HIP(hipMemcpy(mio_.keys.get(), keys.data(), (size_t)n * 8, hipMemcpyHostToDevice));
       for (auto &r : renders_) DR_HIP(hipStreamWaitEvent(int_stream_, r.cast, 0));  // blocks are added
-      for (size_t b = 0; b < n && ok; b += chunk) {
-        const size_t m = std::min(chunk, (size_t)n - b);
-        mio_.wait();  // the placement of two chunks ago has read this buffer
-        ok = rd.read(mio_.host(), m, err);
-        if (!ok) break;
-        hipLaunchKernelGGL(k_in_place, dim3(std::min(cdiv((int)m, 4), 1024)), dim3(256), 0, int_stream_, d_, mio_keys_.get() + b, (const uint4 *)mio_.dev(), (int)m);
+      ok = mio_.read_chunks(rd, chunk, err, [&](size_t b, size_t m, const unsigned char *, const unsigned char *d) {
+        hipLaunchKernelGGL(k_in_place, dim3(std::min(cdiv((int)m, 4), 1024)), dim3(256), 0, int_stream_, d_, mio_.keys.get() + b, (const uint4 *)d, (int)m);
         hipLaunchKernelGGL(k_in_finish, dim3(1), dim3(64), 0, int_stream_, d_.n_alloc, (int)m);
         DR_HIP(hipGetLastError());
-        mio_.record(int_stream_);
-        mio_.flip();
-      }
+      });
       DR_HIP(hipStreamSynchronize(int_stream_));
     }
-    if (ok && !rd.verified()) { ok = false; err = std::string("map file ") + path + " changed while it was read"; }
     if (!ok) {
       clear_map();
       fail(DR_ERR_IO, "drf_load_map: %s", err.c_str());
@@ -1452,17 +1433,15 @@ class FusionEngine {
     settle();
     std::string err;
     MapReader rd;
-    if (!rd.open(path, err)) fail(DR_ERR_IO, "drf_merge_map: %s", err.c_str());
-    const float vs = rd.voxel_size();
-    if (memcmp(&vs, &o_.voxel_size, 4) != 0) fail(DR_ERR_ARG, "drf_merge_map: %s has voxel_size %.9g, the engine %.9g", path, vs, o_.voxel_size);
+    mio_.open_reader("drf_merge_map", path, rd);
     const size_t n = (size_t)rd.blocks();
     const std::vector<unsigned long long> &keys = rd.keys();
     const int nres = pool_blocks();
     std::vector<unsigned long long> res((size_t)nres);
     std::vector<int> slots((size_t)nres);
     sort_resident(nres, res);
-    if (nres > 0) DR_HIP(hipMemcpy(slots.data(), mio_slot_.get(), (size_t)nres * 4, hipMemcpyDeviceToHost));
-    const size_t chunk = map_chunk(chunk_blocks, n);
+    if (nres > 0) DR_HIP(hipMemcpy(slots.data(), mio_.slot.get(), (size_t)nres * 4, hipMemcpyDeviceToHost));
+    const size_t chunk = mio_.chunk(chunk_blocks, n);
     const MergePlan p = plan_merge(res, slots, store_.sorted_keys(), keys, chunk);
     const bool to_store = st_radius_ > 0.0f;
     const size_t n_add = p.add_key.size(), n_res = p.res_slot.size();
@@ -1473,281 +1452,65 @@ class FusionEngine {
     mg_stats_[0] = n;
     mu_force_full_ = true;
     if (n == 0) { loaded_ = true; return; }
-    ensure_map_io(chunk);
+    mio_.ensure(chunk);
     // the per-chunk index lists, in the sort's buffers (their contents are on the host now)
     const size_t n_dev = to_store ? 0 : n_add;
-    mio_slot_in_.reserve(std::max<size_t>(n_res, 1), int_stream_); mio_slot_.reserve(std::max<size_t>(n_res, 1), int_stream_);
-    mio_dst_.reserve(std::max<size_t>(n_dev, 1), int_stream_); mio_keys_.reserve(std::max<size_t>(n_dev, 1), int_stream_);
+    mio_.slot_in.reserve(std::max<size_t>(n_res, 1), int_stream_); mio_.slot.reserve(std::max<size_t>(n_res, 1), int_stream_);
+    mio_.dst.reserve(std::max<size_t>(n_dev, 1), int_stream_); mio_.keys.reserve(std::max<size_t>(n_dev, 1), int_stream_);
     mg_counts_.reserve(2, int_stream_);
     if (n_res > 0) {
-      DR_HIP(hipMemcpy(mio_slot_in_.get(), p.res_src.data(), n_res * 4, hipMemcpyHostToDevice));
-      DR_HIP(hipMemcpy(mio_slot_.get(), p.res_slot.data(), n_res * 4, hipMemcpyHostToDevice));
+      DR_HIP(hipMemcpy(mio_.slot_in.get(), p.res_src.data(), n_res * 4, hipMemcpyHostToDevice));
+      DR_HIP(hipMemcpy(mio_.slot.get(), p.res_slot.data(), n_res * 4, hipMemcpyHostToDevice));
     }
     if (n_dev > 0) {
-      DR_HIP(hipMemcpy(mio_dst_.get(), p.add_src.data(), n_dev * 4, hipMemcpyHostToDevice));
-      DR_HIP(hipMemcpy(mio_keys_.get(), p.add_key.data(), n_dev * 8, hipMemcpyHostToDevice));
+      DR_HIP(hipMemcpy(mio_.dst.get(), p.add_src.data(), n_dev * 4, hipMemcpyHostToDevice));
+      DR_HIP(hipMemcpy(mio_.keys.get(), p.add_key.data(), n_dev * 8, hipMemcpyHostToDevice));
     }
     DR_HIP(hipMemset(mg_counts_.get(), 0, 16));
     for (auto &r : renders_) DR_HIP(hipStreamWaitEvent(int_stream_, r.cast, 0));  // blocks change
     const unsigned char W = (unsigned char)o_.max_sdf_weight;
     uint64_t host_counts[2] = {0, 0};
-    bool ok = true;
-    for (size_t c = 0; c < p.chunks() && ok; ++c) {
-      const size_t m = std::min(chunk, n - c * chunk);
-      mio_.wait();  // the kernels of two chunks ago have read this buffer
-      ok = rd.read(mio_.host(), m, err);
-      if (!ok) break;
+    const bool ok = mio_.read_chunks(rd, chunk, err, [&](size_t b, size_t, const unsigned char *h, const unsigned char *d) {
+      const size_t c = b / chunk;
       const int mr = (int)(p.rb[c + 1] - p.rb[c]), ma = to_store ? 0 : (int)(p.ab[c + 1] - p.ab[c]);
       if (mr > 0)
-        hipLaunchKernelGGL(k_map_merge, dim3(std::min(cdiv(mr, 4), 1024)), dim3(256), 0, int_stream_, d_.vox, mio_slot_in_.get() + p.rb[c], mio_slot_.get() + p.rb[c],
-                           mr, (const uint4 *)mio_.dev(), W, mg_counts_.get());
+        hipLaunchKernelGGL(k_map_merge, dim3(std::min(cdiv(mr, 4), 1024)), dim3(256), 0, int_stream_, d_.vox, mio_.slot_in.get() + p.rb[c], mio_.slot.get() + p.rb[c], mr,
+                           (const uint4 *)d, W, mg_counts_.get());
       if (ma > 0) {
-        hipLaunchKernelGGL(k_in_place_at, dim3(std::min(cdiv(ma, 4), 1024)), dim3(256), 0, int_stream_, d_, mio_keys_.get() + p.ab[c], mio_dst_.get() + p.ab[c],
-                           (const uint4 *)mio_.dev(), ma);
+        hipLaunchKernelGGL(k_in_place_at, dim3(std::min(cdiv(ma, 4), 1024)), dim3(256), 0, int_stream_, d_, mio_.keys.get() + p.ab[c], mio_.dst.get() + p.ab[c],
+                           (const uint4 *)d, ma);
         hipLaunchKernelGGL(k_in_finish, dim3(1), dim3(64), 0, int_stream_, d_.n_alloc, ma);
       }
-      if (mr > 0 || ma > 0) {
-        DR_HIP(hipGetLastError());
-        mio_.record(int_stream_);
-      }
+      if (mr > 0 || ma > 0) DR_HIP(hipGetLastError());
       // the host half of the chunk, from the same buffer, while the kernels read it
-      const unsigned char *h = mio_.host();
       for (size_t i = p.sb[c]; i < p.sb[c + 1]; ++i) merge_block(store_.get_mut(p.sto_key[i]), h + (size_t)p.sto_src[i] * 4096, W, host_counts);
       if (to_store)
         for (size_t i = p.ab[c]; i < p.ab[c + 1]; ++i) store_.put(p.add_key[i], h + (size_t)p.add_src[i] * 4096);
       mg_stats_[1] += p.ab[c + 1] - p.ab[c]; mg_stats_[2] += (uint64_t)mr; mg_stats_[3] += p.sb[c + 1] - p.sb[c];
-      mio_.flip();
-    }
+    });
     DR_HIP(hipStreamSynchronize(int_stream_));
     unsigned long long dev_counts[2];
     DR_HIP(hipMemcpy(dev_counts, mg_counts_.get(), 16, hipMemcpyDeviceToHost));
     mg_stats_[4] = host_counts[0] + dev_counts[0]; mg_stats_[5] = host_counts[1] + dev_counts[1];
-    if (ok && !rd.verified()) { ok = false; err = std::string("map file ") + path + " changed while it was read"; }
     if (!ok) fail(DR_ERR_IO, "drf_merge_map: %s (the blocks merged so far stay merged: drf_merge_stats)", err.c_str());
     loaded_ = true;
   }
   void merge_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = mg_stats_[i]; }
 
-  // A map file resampled on this engine's lattice in another world frame and written as a map file (the rule: fusion_host.h
-  // transform_voxel; DESIGN.md §7c "Moving a map into another frame").  The engine lends its device, int_stream_, the pinned pair
-  // and voxel_size; its own map is neither read nor changed and nothing is folded.  The source goes to the device whole (voxels,
-  // then the key table: 4104 n bytes, freed on every way out), plan_transform lists the candidate destination blocks, a count
-  // pass of k_map_transform tells which of them hold a weighted voxel -- MapWriter wants the key table first -- and a write pass
-  // over those fills the pinned buffers chunk by chunk while the host appends the other buffer to <dst>.part.
+  // Operations on map files alone (map_ops.h: map_transform, map_align_system, map_align).  The engine lends mio_ -- its device,
+  // int_stream_, the pinned pair, voxel_size -- and states where in its call order they may run; its own map is neither read nor changed.
   void transform_map(const char *src, const float *T16, const char *dst, size_t chunk_blocks) {
-    if (!src || !T16 || !dst) fail(DR_ERR_ARG, "drf_transform_map: null argument");
-    expect(kIntegrate, "drf_transform_map: call it where IntegrateScanAsync may be called.");
-    if (!strcmp(src, dst)) fail(DR_ERR_ARG, "drf_transform_map: source and destination are the same path (%s)", src);
-    if (const char *why = transform_pose_fault(T16)) fail(DR_ERR_ARG, "drf_transform_map: the motion %s", why);
-    std::string err;
-    MapReader rd;
-    if (!rd.open(src, err)) fail(DR_ERR_IO, "drf_transform_map: %s", err.c_str());
-    const float vs = rd.voxel_size();
-    if (memcmp(&vs, &o_.voxel_size, 4) != 0) fail(DR_ERR_ARG, "drf_transform_map: %s has voxel_size %.9g, the engine %.9g", src, vs, o_.voxel_size);
-    const size_t n = (size_t)rd.blocks();
-    const MapMotion m = map_motion(T16, o_.voxel_size);
-    bool in_range = true;
-    const std::vector<unsigned long long> cand = plan_transform(rd.keys(), m, &in_range);
-    if (!in_range) fail(DR_ERR_ARG, "drf_transform_map: the motion takes blocks of %s outside the key range (2^20 blocks per axis)", src);
-    if (n > (size_t)INT_MAX || cand.size() > (size_t)INT_MAX) fail(DR_ERR_CAPACITY, "drf_transform_map: %zu source and %zu candidate blocks exceed the index range", n, cand.size());
-    DR_HIP(hipSetDevice(device_));
-    // the source must fit on the device beside what is there (the parity build can lower the limit: the tests' way to this refusal)
-    const size_t src_bytes = n * 4104, side_bytes = cand.size() * 20 + 16;  // candidate keys, flags, kept keys; two counters
-    if (n > 0) {
-      size_t free_b = 0, total_b = 0;
-      DR_HIP(hipMemGetInfo(&free_b, &total_b));
-      if (const char *e = hook_env("DR_TRANSFORM_MAX_BYTES")) free_b = std::min(free_b, (size_t)strtoull(e, nullptr, 10));
-      if (src_bytes + side_bytes > free_b)
-        fail(DR_ERR_CAPACITY, "drf_transform_map: %s needs %zu bytes of device memory (%zu blocks), %zu are available", src, src_bytes + side_bytes, n, free_b);
-    }
-    struct Held {  // device memory of this call only
-      void *p = nullptr;
-      ~Held() { dfree(p); }
-      bool take(size_t bytes) { if (device_alloc(&p, bytes) == hipSuccess) return true; p = nullptr; (void)hipGetLastError(); return false; }
-    } source, side;
-    for (auto &v : xf_stats_) v = 0;
-    xf_stats_[0] = n; xf_stats_[1] = cand.size();
-    std::vector<unsigned long long> kept;
-    const size_t nc = cand.size();
-    const size_t chunk = map_chunk(chunk_blocks, std::max(n, nc));
-    DR_HIP(hipStreamSynchronize(int_stream_));  // the pinned pair is idle: every user of it ends with this
-    unsigned long long *d_cand = nullptr, *d_kept = nullptr, *d_counts = nullptr;
-    if (n > 0 && nc > 0) {
-      if (!source.take(src_bytes) || !side.take(side_bytes))
-        fail(DR_ERR_CAPACITY, "drf_transform_map: %s needs %zu bytes of device memory (%zu blocks)", src, src_bytes + side_bytes, n);
-      xf_stats_[5] = src_bytes;
-      ensure_map_io(chunk);
-      unsigned char *d_vox = (unsigned char *)source.p;
-      unsigned long long *d_keys = (unsigned long long *)(d_vox + n * 4096);
-      d_counts = (unsigned long long *)side.p; d_cand = d_counts + 2; d_kept = d_cand + nc;
-      int *d_flags = (int *)(d_kept + nc);
-      DR_HIP(hipMemcpyAsync(d_keys, rd.keys().data(), n * 8, hipMemcpyHostToDevice, int_stream_));
-      DR_HIP(hipMemcpyAsync(d_cand, cand.data(), nc * 8, hipMemcpyHostToDevice, int_stream_));
-      DR_HIP(hipMemsetAsync(d_counts, 0, 16, int_stream_));
-      bool ok = true;
-      for (size_t b = 0; b < n && ok; b += chunk) {  // the file through the pinned pair to the device
-        const size_t cnt = std::min(chunk, n - b);
-        mio_.wait();  // the copy of two chunks ago has left this buffer
-        ok = rd.read(mio_.host(), cnt, err);
-        if (!ok) break;
-        DR_HIP(hipMemcpyAsync(d_vox + b * 4096, mio_.host(), cnt * 4096, hipMemcpyHostToDevice, int_stream_));
-        mio_.record(int_stream_);
-        mio_.flip();
-      }
-      if (ok && !rd.verified()) { ok = false; err = std::string("map file ") + src + " changed while it was read"; }
-      if (!ok) {
-        DR_HIP(hipStreamSynchronize(int_stream_));
-        fail(DR_ERR_IO, "drf_transform_map: %s", err.c_str());
-      }
-      hipLaunchKernelGGL(k_map_transform<false>, dim3(cdiv((int)nc, 4)), dim3(256), 0, int_stream_, d_keys, (const uint2 *)d_vox, (int)n, d_cand, (int)nc, m,
-                         (uint4 *)nullptr, d_flags, d_counts);
-      DR_HIP(hipGetLastError());
-      std::vector<int> flags(nc);
-      unsigned long long counts[2] = {0, 0};
-      DR_HIP(hipMemcpyAsync(flags.data(), d_flags, nc * 4, hipMemcpyDeviceToHost, int_stream_));
-      DR_HIP(hipMemcpyAsync(counts, d_counts, 16, hipMemcpyDeviceToHost, int_stream_));
-      DR_HIP(hipStreamSynchronize(int_stream_));
-      for (size_t i = 0; i < nc; ++i)
-        if (flags[i]) kept.push_back(cand[i]);
-      xf_stats_[3] = counts[0]; xf_stats_[4] = counts[1];
-      if (!kept.empty()) DR_HIP(hipMemcpyAsync(d_kept, kept.data(), kept.size() * 8, hipMemcpyHostToDevice, int_stream_));
-    }
-    const size_t nk = kept.size();
-    MapWriter w;
-    if (!w.open(dst, o_.voxel_size, kept.data(), nk, err)) fail(DR_ERR_IO, "drf_transform_map: %s", err.c_str());
-    bool ok = true;
-    if (nk > 0) {
-      unsigned char *d_vox = (unsigned char *)source.p;
-      const unsigned long long *d_keys = (const unsigned long long *)(d_vox + n * 4096);
-      const size_t chunks = (nk + chunk - 1) / chunk;
-      auto launch = [&](size_t c) {  // chunk c of the kept blocks into the current buffer
-        const int cnt = (int)std::min(chunk, nk - c * chunk);
-        hipLaunchKernelGGL(k_map_transform<true>, dim3(cdiv(cnt, 4)), dim3(256), 0, int_stream_, d_keys, (const uint2 *)d_vox, (int)n, d_kept + c * chunk, cnt, m,
-                           (uint4 *)mio_.dev(), (int *)nullptr, (unsigned long long *)nullptr);
-        DR_HIP(hipGetLastError());
-        mio_.record(int_stream_);
-      };
-      launch(0);
-      for (size_t c = 0; c < chunks && ok; ++c) {
-        if (c + 1 < chunks) { mio_.flip(); launch(c + 1); mio_.flip(); }  // runs while the host appends chunk c
-        mio_.wait();
-        ok = w.append(mio_.host(), std::min(chunk, nk - c * chunk), err);
-        mio_.flip();
-      }
-    }
-    ok = ok && w.close(err);
-    DR_HIP(hipStreamSynchronize(int_stream_));  // (a failed write leaves the next chunk's kernel in flight)
-    if (!ok) fail(DR_ERR_IO, "drf_transform_map: %s", err.c_str());
-    xf_stats_[2] = nk;
+    map_transform(mio_, src, T16, dst, chunk_blocks, [&] { expect_integrate("drf_transform_map"); });
   }
-  void transform_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = xf_stats_[i]; }
-
-  // Two map files registered to each other (the rule: fusion_host.h align_voxel / align_step; DESIGN.md §7c "Registering two maps").
-  // As for transform_map the engine lends its device, int_stream_, the pinned pair and voxel_size, and its own map is neither read
-  // nor changed.  with_align_maps does what both calls share -- the refusals in their order, both files to the device whole (one
-  // allocation: reference voxels and keys, source voxels and keys, partial sums, counters; freed on every way out) -- and hands
-  // body an evaluator: k_map_align + k_align_fold on int_stream_, 28 doubles and 3 counters back through the pinned pair.
-  template <class Body>
-  void with_align_maps(const char *who, const char *src, const char *ref, const float *T16, const drf_align_options_t *opt, Body &&body) {
-    for (auto &v : al_stats_) v = 0;
-    AlignOpt ao;
-    if (const char *bad = align_options(opt, o_.voxel_size, ao)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
-    expect(kIntegrate, (std::string(who) + ": call it where IntegrateScanAsync may be called.").c_str());
-    if (const char *why = transform_pose_fault(T16)) fail(DR_ERR_ARG, "%s: the motion %s", who, why);
-    std::string err;
-    MapReader rs, rr;
-    if (!rs.open(src, err) || !rr.open(ref, err)) fail(DR_ERR_IO, "%s: %s", who, err.c_str());
-    for (const auto *r : {&rs, &rr}) {
-      const float vs = r->voxel_size();
-      if (memcmp(&vs, &o_.voxel_size, 4) != 0) fail(DR_ERR_ARG, "%s: %s has voxel_size %.9g, the engine %.9g", who, r == &rs ? src : ref, vs, o_.voxel_size);
-    }
-    const size_t ns = (size_t)rs.blocks(), nr = (size_t)rr.blocks();
-    if (ns > (size_t)INT_MAX || nr > (size_t)INT_MAX) fail(DR_ERR_CAPACITY, "%s: %zu source and %zu reference blocks exceed the index range", who, ns, nr);
-    DR_HIP(hipSetDevice(device_));
-    // both maps must fit on the device beside what is there (the parity build can lower the limit: the tests' way to this refusal)
-    const size_t bytes = (ns + nr) * 4104 + ns * 224 + 32;
-    {
-      size_t free_b = 0, total_b = 0;
-      DR_HIP(hipMemGetInfo(&free_b, &total_b));
-      if (const char *e = hook_env("DR_TRANSFORM_MAX_BYTES")) free_b = std::min(free_b, (size_t)strtoull(e, nullptr, 10));
-      if (bytes > free_b)
-        fail(DR_ERR_CAPACITY, "%s: %zu bytes of device memory are needed (%zu + %zu blocks), %zu are available: %s and %s", who, bytes, ns, nr, free_b, src, ref);
-    }
-    struct Held {  // device memory of this call only
-      void *p = nullptr;
-      ~Held() { dfree(p); }
-    } held;
-    DR_HIP(hipStreamSynchronize(int_stream_));  // the pinned pair is idle: every user of it ends with this
-    if (device_alloc(&held.p, bytes) != hipSuccess) {
-      held.p = nullptr; (void)hipGetLastError();
-      fail(DR_ERR_CAPACITY, "%s: %zu bytes of device memory are needed (%zu + %zu blocks): %s and %s", who, bytes, ns, nr, src, ref);
-    }
-    al_stats_[0] = ns; al_stats_[1] = nr; al_stats_[5] = bytes;
-    // layout, every part a multiple of 8 bytes: ref voxels, src voxels, ref keys, src keys, partial sums, 3 counters (+ 1 unused)
-    unsigned char *r_vox = (unsigned char *)held.p, *s_vox = r_vox + nr * 4096;
-    unsigned long long *r_keys = (unsigned long long *)(s_vox + ns * 4096), *s_keys = r_keys + nr;
-    double *partial = (double *)(s_keys + ns);
-    unsigned long long *counts = (unsigned long long *)(partial + ns * 28);
-    const size_t chunk = map_chunk(0, std::max(ns, nr));
-    ensure_map_io(chunk);
-    bool ok = true;
-    auto upload = [&](MapReader &rd, const char *path, unsigned char *d_vox, unsigned long long *d_keys) {
-      const size_t n = (size_t)rd.blocks();
-      if (n) DR_HIP(hipMemcpyAsync(d_keys, rd.keys().data(), n * 8, hipMemcpyHostToDevice, int_stream_));
-      for (size_t b = 0; b < n && ok; b += chunk) {  // the file through the pinned pair to the device
-        const size_t cnt = std::min(chunk, n - b);
-        mio_.wait();  // the copy of two chunks ago has left this buffer
-        ok = rd.read(mio_.host(), cnt, err);
-        if (!ok) break;
-        DR_HIP(hipMemcpyAsync(d_vox + b * 4096, mio_.host(), cnt * 4096, hipMemcpyHostToDevice, int_stream_));
-        mio_.record(int_stream_);
-        mio_.flip();
-      }
-      if (ok && !rd.verified()) { ok = false; err = std::string("map file ") + path + " changed while it was read"; }
-    };
-    upload(rs, src, s_vox, s_keys);
-    if (ok) upload(rr, ref, r_vox, r_keys);
-    DR_HIP(hipStreamSynchronize(int_stream_));  // (also: the key tables' host memory may go now, and both slots are idle)
-    if (!ok) { al_stats_[5] = 0; fail(DR_ERR_IO, "%s: %s", who, err.c_str()); }
-    double c_src[3];
-    align_centre_src(rs.keys(), c_src);
-    auto eval = [&](const AlignEval &e, double sums[28], uint64_t cnt[3]) {
-      DR_HIP(hipMemsetAsync(counts, 0, 32, int_stream_));
-      if (ns) {
-        hipLaunchKernelGGL(k_map_align, dim3(cdiv((int)ns, 4)), dim3(256), 0, int_stream_, s_keys, (const uint4 *)s_vox, (int)ns, r_keys, (const uint2 *)r_vox,
-                           (int)nr, e, partial, counts);
-        DR_HIP(hipGetLastError());
-      }
-      hipLaunchKernelGGL(k_align_fold, dim3(28), dim3(64), 0, int_stream_, partial, (int)ns, counts, (double *)mio_.dev());
-      DR_HIP(hipGetLastError());
-      DR_HIP(hipStreamSynchronize(int_stream_));
-      memcpy(sums, mio_.host(), 224);
-      memcpy(cnt, mio_.host() + 224, 24);
-      al_stats_[2] = cnt[0]; al_stats_[3] = cnt[1]; ++al_stats_[4];
-    };
-    body(ao, c_src, eval);
-  }
+  void transform_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = mio_.xf_stats[i]; }
   void align_system(const char *src, const char *ref, const float *T16, const drf_align_options_t *opt, double *sums, uint64_t *counts) {
-    if (!src || !ref || !T16 || !sums || !counts) fail(DR_ERR_ARG, "drf_align_system: null argument");
-    with_align_maps("drf_align_system", src, ref, T16, opt, [&](const AlignOpt &ao, const double c_src[3], auto &eval) {
-      eval(align_eval(map_motion(T16, o_.voxel_size), c_src, ao, o_.voxel_size), sums, counts);
-    });
+    map_align_system(mio_, src, ref, T16, opt, sums, counts, [&](const char *who) { expect_integrate(who); });
   }
   // returns what dr_last_error() says after a registration that ran but found no pose (empty otherwise)
   std::string align_map(const char *src, const char *ref, const float *T16, const drf_align_options_t *opt, float *T16_out, drf_align_result_t *res) {
-    if (!src || !ref || !T16 || !T16_out) fail(DR_ERR_ARG, "drf_align_map: null argument");
-    drf_align_result_t r;
-    with_align_maps("drf_align_map", src, ref, T16, opt, [&](const AlignOpt &ao, const double c_src[3], auto &eval) {
-      align_loop(eval, map_motion(T16, o_.voxel_size), c_src, ao, o_.voxel_size, r);
-    });
-    for (int i = 0; i < 16; ++i) T16_out[i] = (float)r.T[i];
-    if (res) *res = r;
-    if (r.status != DRF_ALIGN_DEGENERATE && r.status != DRF_ALIGN_LOST) return std::string();
-    // the reason first and no fixed buffer: two paths of any length must not cut it off
-    return std::string("drf_align_map: the registration ") + align_status_name(r.status) + " after " + std::to_string(r.iterations) + " evaluations (" +
-           std::to_string((unsigned long long)r.valid) + " of " + std::to_string((unsigned long long)r.samples) + " samples valid): " + src + " to " + ref;
+    return map_align(mio_, src, ref, T16, opt, T16_out, res, [&](const char *who) { expect_integrate(who); });
   }
-  void align_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = al_stats_[i]; }
+  void align_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = mio_.al_stats[i]; }
 
   // A depth frame located in the map this engine holds (the rule: fusion_host.h locate_pixel / align_point; DESIGN.md §7c "Locating a
   // depth frame in the map").  The map is read where it lives, through find_block; nothing of it is uploaded, changed or allocated.
@@ -1759,7 +1522,7 @@ class FusionEngine {
     for (auto &v : lc_stats_) v = 0;
     LocateOpt lo;
     if (const char *bad = locate_options(opt, o_.truncation_distance, lo)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
-    expect(kIntegrate, (std::string(who) + ": call it where IntegrateScanAsync may be called.").c_str());
+    expect_integrate(who);
     if (st_radius_ <= 0.0f && !store_.empty())
       fail(DR_ERR_PROTOCOL, "%s: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", who, store_.size());
     if (const char *why = transform_pose_fault(pose16)) fail(DR_ERR_ARG, "%s: the pose %s", who, why);
@@ -1769,7 +1532,7 @@ class FusionEngine {
     const size_t max_groups = (npix_ + 511) / 512;  // step = 1
     const size_t bytes = max_groups * 224 + 32 + npix_ * 4;
     lc_buf_.reserve(bytes, int_stream_);
-    ensure_map_io(1);
+    mio_.ensure(1);
     double *partial = (double *)lc_buf_.get();
     unsigned long long *counts = (unsigned long long *)(partial + max_groups * 28);
     const float *depth = (const float *)d_depth;
@@ -1781,14 +1544,10 @@ class FusionEngine {
     }
     lc_stats_[0] = (uint64_t)total; lc_stats_[4] = lc_buf_.capacity(); lc_stats_[5] = store_.size();
     auto eval = [&](const AlignEval &e, double sums[28], uint64_t c4[4]) {
-      DR_HIP(hipMemsetAsync(counts, 0, 32, int_stream_));
-      hipLaunchKernelGGL(k_map_locate, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, d_, depth, lg, e, groups, total, partial, counts);
-      DR_HIP(hipGetLastError());
-      hipLaunchKernelGGL(k_align_fold, dim3(28), dim3(64), 0, int_stream_, partial, groups, counts, (double *)mio_.dev());
-      DR_HIP(hipGetLastError());
-      DR_HIP(hipStreamSynchronize(int_stream_));
-      memcpy(sums, mio_.host(), 224);
-      memcpy(c4, mio_.host() + 224, 32);
+      mio_.evaluate(partial, groups, counts, 4, sums, c4, [&] {
+        hipLaunchKernelGGL(k_map_locate, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, d_, depth, lg, e, groups, total, partial, counts);
+        DR_HIP(hipGetLastError());
+      });
       lc_stats_[1] = c4[0]; lc_stats_[2] = c4[1]; ++lc_stats_[3];
     };
     try {
@@ -1818,11 +1577,9 @@ class FusionEngine {
     with_locate(who, h_depth, d_depth, pose16, opt, [&](const LocateOpt &lo, auto &eval) { locate_loop(eval, map_motion(pose16, o_.voxel_size), lo, o_.voxel_size, r, c4); });
     for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
     if (res) *res = r;
-    if (r.status != DRF_ALIGN_DEGENERATE && r.status != DRF_ALIGN_LOST) return std::string();
-    return std::string(who) + ": the refinement " + align_status_name(r.status) + " after " + std::to_string(r.iterations) + " evaluations (" +
-           std::to_string((unsigned long long)r.valid) + " of " + std::to_string((unsigned long long)r.samples) + " samples valid, " +
-           std::to_string((unsigned long long)c4[2]) + " unobserved, " + std::to_string((unsigned long long)c4[3]) + " outside the band; " +
-           std::to_string(store_.size()) + " blocks are in the host store)";
+    return no_pose_note(std::string(who) + ": the refinement", r,
+                        ", " + std::to_string((unsigned long long)c4[2]) + " unobserved, " + std::to_string((unsigned long long)c4[3]) + " outside the band; " +
+                            std::to_string(store_.size()) + " blocks are in the host store)");
   }
   void locate_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = lc_stats_[i]; }
 
@@ -1836,30 +1593,21 @@ class FusionEngine {
     return std::min(na, o_.num_blocks);
   }
   // the resident order: (blk_key, slot) pairs sorted by key, as mesh_tables sorts the keys -- the keys to res, keys and slots
-  // left in mio_keys_ / mio_slot_ (drf_save_map, drf_merge_map)
+  // left in mio_.keys / mio_.slot (drf_save_map, drf_merge_map)
   void sort_resident(int nres, std::vector<unsigned long long> &res) {
     if (nres <= 0) return;
     std::vector<int> iota((size_t)nres);
     for (int i = 0; i < nres; ++i) iota[i] = i;
-    mio_keys_.reserve((size_t)nres, int_stream_); mio_slot_in_.reserve((size_t)nres, int_stream_);
-    mio_slot_.reserve((size_t)nres, int_stream_); mio_dst_.reserve((size_t)nres, int_stream_);
-    DR_HIP(hipMemcpy(mio_slot_in_.get(), iota.data(), (size_t)nres * 4, hipMemcpyHostToDevice));
+    mio_.keys.reserve((size_t)nres, int_stream_); mio_.slot_in.reserve((size_t)nres, int_stream_);
+    mio_.slot.reserve((size_t)nres, int_stream_); mio_.dst.reserve((size_t)nres, int_stream_);
+    DR_HIP(hipMemcpy(mio_.slot_in.get(), iota.data(), (size_t)nres * 4, hipMemcpyHostToDevice));
     size_t tb = 0;
-    DR_HIP(rocprim::radix_sort_pairs(nullptr, tb, d_.blk_key, mio_keys_.get(), mio_slot_in_.get(), mio_slot_.get(), (size_t)nres, 0, 63, int_stream_));
-    mio_tmp_.reserve(std::max<size_t>(tb, 256), int_stream_);  // (never null: a null scratch is rocprim's size query)
-    tb = mio_tmp_.capacity();
-    DR_HIP(rocprim::radix_sort_pairs(mio_tmp_.get(), tb, d_.blk_key, mio_keys_.get(), mio_slot_in_.get(), mio_slot_.get(), (size_t)nres, 0, 63, int_stream_));
-    DR_HIP(hipMemcpyAsync(res.data(), mio_keys_.get(), (size_t)nres * 8, hipMemcpyDeviceToHost, int_stream_));
+    DR_HIP(rocprim::radix_sort_pairs(nullptr, tb, d_.blk_key, mio_.keys.get(), mio_.slot_in.get(), mio_.slot.get(), (size_t)nres, 0, 63, int_stream_));
+    mio_.tmp.reserve(std::max<size_t>(tb, 256), int_stream_);  // (never null: a null scratch is rocprim's size query)
+    tb = mio_.tmp.capacity();
+    DR_HIP(rocprim::radix_sort_pairs(mio_.tmp.get(), tb, d_.blk_key, mio_.keys.get(), mio_.slot_in.get(), mio_.slot.get(), (size_t)nres, 0, 63, int_stream_));
+    DR_HIP(hipMemcpyAsync(res.data(), mio_.keys.get(), (size_t)nres * 8, hipMemcpyDeviceToHost, int_stream_));
     DR_HIP(hipStreamSynchronize(int_stream_));
-  }
-  // blocks per chunk of a map file of n blocks: the caller's, or min(num_blocks, 8192); never more than the file has or 2^20
-  size_t map_chunk(size_t chunk_blocks, size_t n) const {
-    const size_t want = chunk_blocks ? chunk_blocks : (size_t)std::min(o_.num_blocks, kStageBlocks);
-    return std::max<size_t>(1, std::min({want, n, (size_t)1 << 20}));
-  }
-  void ensure_map_io(size_t chunk) {  // after settle(): no kernel uses the old buffers
-    if (!mio_.opened()) mio_.open(own_);
-    mio_.reserve(chunk * 4096);
   }
   // a load that failed half way: pool, block index and host store as a new engine has them (the counters were not touched)
   void clear_map() {
@@ -2069,6 +1817,7 @@ class FusionEngine {
     static const char *names[] = {"IntegrateScanAsync", "RenderAsync", "GetRenderResult"};
     if (next_ != want) fail(DR_ERR_PROTOCOL, "%s You should have called %s", msg, names[next_]);
   }
+  void expect_integrate(const char *who) { expect(kIntegrate, (std::string(who) + ": call it where IntegrateScanAsync may be called.").c_str()); }
   // allocate -> integrate on int_stream_, no host round trip: the number of allocated blocks lives on the
   // device, so the integrate grid is fixed (a few workgroups per CU) and strides over [0, *n_alloc).
   // wait_renders: order the voxel UPDATE behind the ray-casts of the previous scan (they read the voxels).  The allocation pass, the
@@ -2415,15 +2164,10 @@ class FusionEngine {
   double ev_p_[3] = {0.0, 0.0, 0.0};
   ReachBalls reach_;  // balls that hold every block centre of the map
   uint64_t st_out_total_ = 0, st_in_total_ = 0;
-  // map file transport (allocated with the first drf_save_map / drf_load_map / drf_merge_map): two pinned chunk buffers, the sorted (key, slot) pairs
-  PinnedPair mio_;
-  DeviceBuf<unsigned long long> mio_keys_;
-  DeviceBuf<int> mio_slot_in_, mio_slot_, mio_dst_;
-  DeviceBuf<unsigned char> mio_tmp_;
+  // map file transport (map_ops.h; allocated with the first use): two pinned chunk buffers, the sorted (key, slot) pairs
+  MapIo mio_;
   DeviceBuf<unsigned long long> mg_counts_;  // drf_merge_map: voxels of case 2 and case 3 counted by k_map_merge
   uint64_t mg_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_merge_stats
-  uint64_t xf_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_transform_stats
-  uint64_t al_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_align_stats
   DeviceBuf<unsigned char> lc_buf_;            // drf_locate_*: partial sums, counters and a host-given depth image (sized once)
   uint64_t lc_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_locate_stats
 };

@@ -1,4 +1,4 @@
-// What the DrFusion engine takes from the HIP runtime (included by dr_fusion.hip): HipOwner for what lives as long as the engine, DeviceBuf /
+// What the DrFusion engine takes from the HIP runtime (included by dr_fusion.hip and map_ops.h): HipOwner for what lives as long as the engine, DeviceBuf /
 // PinnedBuf for scratch that grows with its use, BlockStaging for the double-buffered transport of stored voxel blocks to the device,
 // PinnedPair for the two page-locked chunk buffers of the map file.
 #pragma once
@@ -138,7 +138,7 @@ class BlockStaging {
 };
 
 // Two page-locked buffers that kernels address directly, used in turn: the host fills or drains one while a kernel reads or
-// writes the other (the map file's chunks, dr_fusion.hip save_map / load_map).  No device twin and no stream of its own, which
+// writes the other (the map file's chunks: map_ops.h MapIo owns the pair and its two pumps use it).  No device twin and no stream of its own, which
 // is what sets it apart from BlockStaging: the kernels run on the caller's stream, and per slot ONE event says that the kernel
 // given that slot has finished with it.
 class PinnedPair {

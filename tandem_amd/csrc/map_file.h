@@ -177,6 +177,11 @@ class MapReader {
   }
   // every block has been handed out and they were the bytes open() validated
   bool verified() const { return next_ == n_ && hash_ == sum_; }
+  // verified(), with the reason in err when it is not
+  bool verify(std::string &err) const {
+    if (!verified()) err = "map file " + path_ + " changed while it was read";
+    return verified();
+  }
 
  private:
   bool refuse(std::string &err, const char *why) {

@@ -18,7 +18,8 @@
 // and a load places the file's chunks with k_in_place + k_in_finish.  A merge (drf_merge_map) combines the file's blocks whose
 // key is resident into their pool slots (k_map_merge) and appends those the map lacks (k_in_place_at + k_in_finish).  A rigid
 // resample (drf_transform_map) does not touch the map at all: k_map_transform reads a source map uploaded for the call and writes
-// blocks of the destination lattice into a chunk of the output file.
+// blocks of the destination lattice into a chunk of the output file.  The host side of the four map-file moves: save / load / merge
+// are FusionEngine's (dr_fusion.hip), the resample is map_ops.h map_transform; all of them go through MapIo's two chunk pumps.
 
 struct StreamDev {
   int *ctl;                    // [0] blocks selected (uncapped), [1] holes, [2] tail survivors, [3] table blocks re-inserted,

@@ -45,5 +45,29 @@ int mf_read(const char *path, size_t chunk, float *voxel_size, unsigned long lon
   if (r.read(vox, 1, g_err)) return 4;  // beyond the last block: refused
   return r.verified() ? 0 : 5;
 }
+// open() validates the file; then -- change != 0 -- a second handle flips one byte in the middle of the LAST block (far from
+// anything the validation pass may have left in a stdio buffer); then every block is read, one per read().  0 = every read
+// succeeded and verify() held, 5 = every read succeeded and verify() refused (its message in mf_last_error), else what failed.
+int mf_read_changed(const char *path, int change) {
+  dr::MapReader r;
+  if (!r.open(path, g_err)) return 1;
+  if (r.blocks() < 3) { g_err = "fewer than 3 blocks"; return 2; }
+  if (change) {
+    FILE *f = fopen(path, "r+b");
+    const long at = (long)(64 + r.blocks() * 8 + (r.blocks() - 1) * 4096 + 2048);
+    int c = EOF;
+    if (!f || fseek(f, at, SEEK_SET) != 0 || (c = fgetc(f)) == EOF || fseek(f, at, SEEK_SET) != 0 || fputc(c ^ 0x20, f) == EOF || fclose(f) != 0) {
+      g_err = "cannot change the file";
+      return 2;
+    }
+  }
+  std::vector<unsigned char> block(4096);
+  while (r.remaining())
+    if (!r.read(block.data(), 1, g_err)) return 3;
+  g_err.clear();
+  const bool same = r.verify(g_err);
+  if (same != r.verified() || same != g_err.empty()) return 4;
+  return same ? 0 : 5;
+}
 
 }  // extern "C"

@@ -138,6 +138,24 @@ static void round_trip(const std::string &dir, uint64_t n, unsigned seed) {
     CHECK(!exists(path + ".part") && slurp(path) == good);
   }
   CHECK(!refused(path));
+  if (n >= 3) {  // the file changes between open() and the reads: every read() succeeds, verify() says so; unchanged, it holds
+    for (int change = 0; change < 2; ++change) {
+      dr::MapReader r;
+      CHECK(r.open(path, err));
+      if (change) {  // one byte in the middle of the last block, through a second handle
+        const size_t at = 64 + 8 * (size_t)n + 4096 * ((size_t)n - 1) + 2048;
+        FILE *f = fopen(path.c_str(), "r+b");
+        CHECK(f && fseek(f, (long)at, SEEK_SET) == 0 && fputc(good[at] ^ 0x20, f) != EOF);
+        if (f) CHECK(fclose(f) == 0);
+      }
+      std::vector<unsigned char> block(4096);
+      while (r.remaining()) CHECK(r.read(block.data(), 1, err));
+      err.clear();
+      CHECK(r.verify(err) == !change && r.verified() == !change);
+      CHECK(err == (change ? "map file " + path + " changed while it was read" : std::string()));
+    }
+    CHECK(refused(path));
+  }
 }
 
 int main(int argc, char **argv) {

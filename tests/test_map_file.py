@@ -84,6 +84,7 @@ def H(tmp_path_factory):
     h.mf_write_abandoned.argtypes = [C.c_char_p, C.c_float, u64p, C.c_uint64]
     h.mf_info.argtypes = [C.c_char_p, C.POINTER(C.c_float), u64p]
     h.mf_read.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_float), u64p, u64p, u8p, C.c_uint64, u64p]
+    h.mf_read_changed.argtypes = [C.c_char_p, C.c_int]
     return h
 
 
@@ -175,6 +176,23 @@ def test_every_malformed_file_is_refused(H, tmp_path):
         q.write_bytes(data)
         assert cpp_refuses(H, q), what
         assert cpp_read(H, q, 7, 40)[0] == 1, what
+
+
+@pytest.mark.parametrize("n", [3, 40])
+def test_a_file_that_changes_between_validation_and_reading_fails_verify(H, tmp_path, n):
+    """MapReader::verify: the second pass over the file -- the one whose blocks are placed -- must meet the bytes open() validated."""
+    keys, vox = random_map(n, seed=21 + n)
+    p = tmp_path / "v.drfmap"
+    good = compose(VS, keys, vox)
+    p.write_bytes(good)
+    assert H.mf_read_changed(str(p).encode(), 0) == 0, H.mf_last_error()
+    assert H.mf_last_error() == b""
+    assert H.mf_read_changed(str(p).encode(), 1) == 5, H.mf_last_error()      # every read() succeeded, verify() did not
+    assert H.mf_last_error() == f"map file {p} changed while it was read".encode()
+    data = p.read_bytes()
+    at = 64 + 8 * n + 4096 * (n - 1) + 2048
+    assert data[at] == good[at] ^ 0x20 and data[:at] == good[:at] and data[at + 1:] == good[at + 1:]  # one byte, in the last block
+    assert cpp_refuses(H, p)                                                  # and a new open() sees it
 
 
 def test_a_failed_write_leaves_nothing_behind(H, tmp_path):
