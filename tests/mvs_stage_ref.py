@@ -19,13 +19,22 @@ which prints the block below; tests/test_mvs_stage_ref.py asserts the oracle sta
 holds every kernel to BOUND_FACTOR x these figures: the kernel's coordinate passes a 1-ulp reciprocal and an fp32 matrix
 rounded from double, each worth about one more rounding of the size of the reference's own normalise / denormalise round
 trip -- a margin over the reference's error, not a number fitted to the kernels.
+
+THE LAYER RESTATEMENTS (the last section).  One function per layer kind of CostRegNet (conv_bn_relu64,
+deconv_bn_relu_skip64) and one per FeatureNet tensor the engine keeps (feature_net_layers), each returning the float64 output AND
+the float64 value before the ReLU.  A layer's error is taken as a fraction of layer_scale() = max(max |value before the
+ReLU|, max |output|): a (6, 1, 1) level behind a ReLU can have a range near zero while its accumulations are O(1), so the
+output's range is not used.  The bound is CONV_BOUND of that scale; E_LAYER is the fp32 oracle's own layer against the
+restatement given the oracle's own input, in the same unit (tests/test_mvs_stage_ref.py asserts
+BOUND_FACTOR * E_LAYER <= CONV_BOUND).  The transposed layers are stated as zero insertion + a plain convolution with the
+flipped kernel (no conv_transpose), BatchNorm as its eval formula.  Imported by tests/test_mvs_layers_gpu.py as well.
 """
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 BOUND_FACTOR = 4.0
-CONV_BOUND = 2e-5        # the project's convolution bound (tests/test_conv_gpu.py): of the output's range
+CONV_BOUND = 2e-5        # the project's convolution bound (tests/test_conv_gpu.py): of the output's range (the logits), of layer_scale() (one layer)
 EK_INTEGER_BAND = 1e-4   # trunc(E[k]) is discontinuous: within this distance of an integer either neighbouring index is accepted
                          # (the fp32 sum of <= 48 terms p * k errs by about 48 * 2^-23 * a few = 2e-5)
 
@@ -37,6 +46,7 @@ E_VOL_PLAIN_MEAN = {1: 8.68e-08, 2: 1.95e-07, 3: 3.69e-07}  # (maximum over test
 E_DEPTH = 4.77e-07
 E_CONF = 5.64e-07
 E_FEAT = {1: 9.23e-07, 2: 9.44e-07, 3: 9.16e-07}
+E_LAYER = 1.72e-06  # one layer (THE LAYER RESTATEMENTS), of layer_scale(): the maximum over CPU_WINDOWS and SMALL_WINDOWS, every CostRegNet and FeatureNet layer
 # ---
 
 MUTANTS = ("border", "no_behind_mask", "shift", "no_gate", "drop_last_view", "divisor_V", "spacing_Dm1")
@@ -92,6 +102,11 @@ def make_case(height, width, views, pose, seed=3):
 # (the oracle's coordinate rounding grows with the coordinate: the largest shape of the GPU test is among them)
 CPU_WINDOWS = ((64, 96, 4, "scene"), (64, 96, 3, "narrow"), (64, 96, 4, "behind"), (64, 96, 3, "rotated"), (96, 64, 2, "scene"),
                (96, 160, 4, "rotated"))
+# the smallest windows the engine accepts (any positive multiple of 32) and the model each runs with in the CPU tests: stage 1 is an 8 x 8 map
+# whose CostRegNet bottoms out at (6, 1, 1); at 48/4/4 stage 3 bottoms out at ONE plane, (1, 4, 4).  Not part of the maxima E_VOL .. E_FEAT record.
+SMALL_WINDOWS = ((32, 32, 2, "scene"), (32, 32, 4, "behind"), (32, 64, 3, "rotated"), (64, 32, 8, "narrow"), (32, 96, 3, "rotated"),
+                 (96, 32, 2, "behind"))
+SMALL_MODELS = ("trained", (48, 4, 4), (16, 8, 8), "trained", (48, 4, 4), "trained")
 
 
 def model_order(views, ref_index):
@@ -301,3 +316,187 @@ def rng_of(x):
 def border_slices():
     """The four image borders of a (D, h, w, ...) tensor, named."""
     return (("row 0", np.s_[:, 0]), ("row h-1", np.s_[:, -1]), ("column 0", np.s_[:, :, 0]), ("column w-1", np.s_[:, :, -1]))
+
+
+# ------------------------------------------------------------------ layer restatements (CostRegNet, FeatureNet)
+# deliberate one-line mistakes of a LAYER (tests/test_mvs_stage_ref.py shows each moves some layer of some small window beyond 20 x the bound):
+#   skip_before_relu   relu(bn + skip) where the network computes relu(bn) + skip
+#   deconv_phase       a transposed layer's output padding placed at the front: the odd and the even output phases swap
+#   replicate_border   the zero padding replaced by the edge value
+#   stride_phase       a strided layer sampling the odd positions
+LAYER_MUTANTS = ("skip_before_relu", "deconv_phase", "replicate_border", "stride_phase")
+
+
+def _t64(a):
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64)))
+
+
+def _tup(v, nd):
+    return (int(v),) * nd if np.isscalar(v) else tuple(int(i) for i in v)
+
+
+def _bn64(y, tensors, prefix):
+    """Eval-mode BatchNorm over the last (channel) axis: (y - mean) / sqrt(var + eps) * weight + bias."""
+    mean, var, g, b = (_t64(tensors[prefix + "." + n]) for n in ("running_mean", "running_var", "weight", "bias"))
+    return (y - mean) / torch.sqrt(var + BN_EPS) * g + b
+
+
+def _conv64(x, weight, stride=1, bias=None, mutant=None):
+    """x channels-last, (D, h, w, Cin) for a 5-D weight and (V, h, w, Cin) for a 4-D one; padding k // 2, written out as an explicit border
+    around the input.  Returns channels-last float64 (torch)."""
+    w = _t64(weight)
+    nd = w.dim() - 2
+    x = _t64(x)
+    x = x.permute(3, 0, 1, 2)[None] if nd == 3 else x.permute(0, 3, 1, 2)
+    stride = _tup(stride, nd)
+    pads = []
+    for k in reversed(w.shape[2:]):
+        pads += [k // 2, k // 2]
+    if any(pads):
+        x = F.pad(x, pads, mode="replicate" if mutant == "replicate_border" else "constant")
+    if mutant == "stride_phase":
+        for ax, s in enumerate(stride):
+            n = x.shape[2 + ax] - 2 * (w.shape[2 + ax] // 2)
+            if s > 1 and n % s == 0:  # (an axis of one position has no odd position to sample)
+                x = x.narrow(2 + ax, 1, x.shape[2 + ax] - 1)
+    y = (F.conv3d if nd == 3 else F.conv2d)(x, w, None if bias is None else _t64(bias), stride, 0)
+    return y[0].permute(1, 2, 3, 0) if nd == 3 else y.permute(0, 2, 3, 1)
+
+
+def layer_scale(out, pre):
+    """The unit of a layer's error: max(max |value before the ReLU|, max |output|) of the float64 layer."""
+    return float(max(np.abs(pre).max(), np.abs(out).max()))
+
+
+def conv_bn_relu64(x, tensors, prefix, stride, mutant=None):
+    """Conv (no bias, padding k // 2: 1 for CostRegNet's Conv3d) + BatchNorm (eval, eps 1e-5) + ReLU.  x (D, h, w, Cin) with a 5-D weight, (V, h, w, Cin) with
+    a 4-D one.  Returns (output, value before the ReLU), float64 numpy."""
+    assert mutant is None or mutant in LAYER_MUTANTS, mutant
+    pre = _bn64(_conv64(x, tensors[prefix + ".conv.weight"], stride, None, mutant), tensors, prefix + ".bn")
+    return torch.relu(pre).numpy(), pre.numpy()
+
+
+def deconv_bn_relu_skip64(x, skip, tensors, prefix, stride, output_padding, mutant=None):
+    """ConvTranspose3d (k 3, padding 1) + BatchNorm + ReLU, THEN + skip.  The transposed convolution is written as: zeros inserted between the input
+    positions along the strided axes, a border of k - 1 - padding = 1 in front and 1 + output_padding behind, and a plain convolution with the kernel
+    flipped and its channel axes exchanged.  x (D, h, w, Cin), skip (D', h', w', Cout).  Returns (output, value before the ReLU)."""
+    assert mutant is None or mutant in LAYER_MUTANTS, mutant
+    w = _t64(tensors[prefix + ".conv.weight"])  # (Cin, Cout, 3, 3, 3)
+    assert tuple(w.shape[2:]) == (3, 3, 3)
+    x = _t64(x)
+    (sd, sh, sw), opad = _tup(stride, 3), _tup(output_padding, 3)
+    D, h, w_, C = x.shape
+    z = torch.zeros(((D - 1) * sd + 1, (h - 1) * sh + 1, (w_ - 1) * sw + 1, C), dtype=torch.float64)
+    z[::sd, ::sh, ::sw] = x
+    pads = []
+    for op in reversed(opad):
+        pads += [1 + op, 1] if mutant == "deconv_phase" else [1, 1 + op]
+    z = F.pad(z.permute(3, 0, 1, 2)[None], pads, mode="replicate" if mutant == "replicate_border" else "constant")
+    y = F.conv3d(z, w.flip(2, 3, 4).transpose(0, 1).contiguous())[0].permute(1, 2, 3, 0)
+    pre = _bn64(y, tensors, prefix + ".bn")
+    skip = _t64(skip)
+    assert skip.shape == pre.shape, (tuple(skip.shape), tuple(pre.shape))
+    out = torch.relu(pre + skip) if mutant == "skip_before_relu" else torch.relu(pre) + skip
+    return out.numpy(), pre.numpy()
+
+
+def image64(bgrs, ref_index):
+    """(V, H, W, 3) RGB in model order: the float values of u8 / 255 (the quotient taken in double, stored as float), exactly."""
+    order = model_order(len(bgrs), ref_index)
+    return np.stack([(np.asarray(bgrs[v])[..., ::-1].astype(np.float64) / 255.0).astype(np.float32).astype(np.float64) for v in order])
+
+
+def _up2_nearest(x):
+    return np.repeat(np.repeat(np.asarray(x, np.float64), 2, axis=1), 2, axis=2)
+
+
+_FN = "feature_net."
+
+
+def fn_conv0_1_64(image, tensors, mutant=None):
+    """fn.conv0.1 from the image: conv0.0 and conv0.1, both 3 x 3 + BN + ReLU (the engine's k_fn_front leaves no fn.conv0.0)."""
+    a, _ = conv_bn_relu64(image, tensors, _FN + "conv0.0", 1, mutant)
+    return conv_bn_relu64(a, tensors, _FN + "conv0.1", 1, mutant)
+
+
+def fn_cbr64(name):
+    """fn.conv1.0 .. fn.conv2.2 from the tensor before it: conv{1,2}.0 are 5 x 5 with stride 2, the others 3 x 3."""
+    stride = 2 if name.endswith(".0") else 1
+    return lambda x, tensors, mutant=None: conv_bn_relu64(x, tensors, _FN + name[len("fn."):], (stride, stride), mutant)
+
+
+def fn_feat1_64(c1, tensors, mutant=None):
+    """feat1 from fn.conv2.2: out.stage1, 1 x 1, no bias (no ReLU: the value `before` it is the output)."""
+    y = _conv64(c1, tensors[_FN + "out.stage1.weight"], 1, None, mutant).numpy()
+    return y, y
+
+
+def fn_inter2_64(c2, c1, tensors, mutant=None):
+    """inter2 from fn.conv1.2 and fn.conv2.2: the nearest x2 upsampling of conv2.2 + skip.stage2 (1 x 1, bias) of conv1.2."""
+    y = _up2_nearest(c1) + _conv64(c2, tensors[_FN + "skip.stage2.weight"], 1, tensors[_FN + "skip.stage2.bias"], mutant).numpy()
+    return y, y
+
+
+def fn_feat2_64(i2, tensors, mutant=None):
+    """feat2 from inter2: out.stage2, 3 x 3, no bias."""
+    y = _conv64(i2, tensors[_FN + "out.stage2.weight"], 1, None, mutant).numpy()
+    return y, y
+
+
+def fn_feat3_64(c3, i2, tensors, mutant=None):
+    """feat3 from fn.conv0.1 and inter2, in the literal order: inter3 = up(inter2) + skip.stage3 (1 x 1, bias) of conv0.1, then out.stage3 (3 x 3, no bias)."""
+    i3 = _up2_nearest(i2) + _conv64(c3, tensors[_FN + "skip.stage3.weight"], 1, tensors[_FN + "skip.stage3.bias"], mutant).numpy()
+    y = _conv64(i3, tensors[_FN + "out.stage3.weight"], 1, None, mutant).numpy()
+    return y, y
+
+
+class Layer:
+    """One engine tensor and the float64 statement of the layer(s) that produce it: fn(*inputs, tensors, mutant=) -> (output, value before the ReLU).
+    inputs: engine tensor names ("images": the window's u8 images, passed as image64)."""
+
+    def __init__(self, name, inputs, fn, strided=False, transposed=False):
+        self.name, self.inputs, self.fn, self.strided, self.transposed = name, tuple(inputs), fn, strided, transposed
+
+    def mutants(self):
+        return ("replicate_border",) + (("stride_phase",) if self.strided else ()) + (("deconv_phase", "skip_before_relu") if self.transposed else ())
+
+
+def feature_net_layers():
+    L = [Layer("fn.conv0.1", ("images",), fn_conv0_1_64)]
+    prev = "fn.conv0.1"
+    for n in ("fn.conv1.0", "fn.conv1.1", "fn.conv1.2", "fn.conv2.0", "fn.conv2.1", "fn.conv2.2"):
+        L.append(Layer(n, (prev,), fn_cbr64(n), strided=n.endswith(".0")))
+        prev = n
+    L += [Layer("feat1", ("fn.conv2.2",), fn_feat1_64), Layer("inter2", ("fn.conv1.2", "fn.conv2.2"), fn_inter2_64),
+          Layer("feat2", ("inter2",), fn_feat2_64), Layer("feat3", ("fn.conv0.1", "inter2"), fn_feat3_64)]
+    return L
+
+
+def cost_reg_layers(stage, D):
+    """CostRegNet of one stage as the engine names it: s{S}.conv0 .. conv6, the transposed conv7 / conv9 / conv11 with their skips conv4 / conv2 / conv0.
+    With D = 4 planes conv5 and conv7 keep the depth axis: stride (1, 2, 2), conv7's output padding (0, 1, 1)."""
+    s, p = "s%d." % stage, "cost_regularization_net.stage%d." % stage
+    s5, op7 = ((1, 2, 2), (0, 1, 1)) if D == 4 else ((2, 2, 2), (1, 1, 1))
+
+    def cbr(n, stride):
+        return lambda x, tensors, mutant=None: conv_bn_relu64(x, tensors, p + n, stride, mutant)
+
+    def dbr(n, stride, opad):
+        return lambda x, skip, tensors, mutant=None: deconv_bn_relu_skip64(x, skip, tensors, p + n, stride, opad, mutant)
+
+    L, prev = [], "volume%d" % stage
+    for n, stride in (("conv0", 1), ("conv1", 2), ("conv2", 1), ("conv3", 2), ("conv4", 1), ("conv5", s5), ("conv6", 1)):
+        L.append(Layer(s + n, (prev,), cbr(n, _tup(stride, 3)), strided=stride != 1))
+        prev = s + n
+    for n, skip, stride, opad in (("conv7", "conv4", s5, op7), ("conv9", "conv2", (2, 2, 2), (1, 1, 1)), ("conv11", "conv0", (2, 2, 2), (1, 1, 1))):
+        L.append(Layer(s + n, (prev, s + skip), dbr(n, stride, opad), transposed=True))
+        prev = s + n
+    return L
+
+
+def all_layers(meta):
+    """Every layer between the images and the three x11 tensors, in execution order."""
+    L = feature_net_layers()
+    for s in (1, 2, 3):
+        L += cost_reg_layers(s, int(meta["depth_num"][s - 1]))
+    return L

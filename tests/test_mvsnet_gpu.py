@@ -137,22 +137,47 @@ def test_pipelined_calls_keep_order(trained_blob):
     m.close()
 
 
-def test_edge_filter_is_exact_given_the_same_depth(trained_blob):
-    """The order-statistic filter is pure comparisons: fed the engine's own depth map, the oracle filter must
-    reproduce the engine's mask bit for bit (module.py:1320-1361)."""
+def _edge_filter_is_exact(m, H, W):
+    """Every discard percentage on one engine: the engine's edge measure, filtered depth and mask against the oracle filter on the engine's own depth."""
     import torch
     from oracle import mvsnet_oracle as O
     from synth import scene
-    from tandem_amd.dr_mvsnet import DrMvsnet
-    m = DrMvsnet(trained_blob)
-    win = scene.make_window(128, 160, 3, seed=4)
-    for disc in (2.5, 10.0, 37.5):
-        m.CallAsync(128, 160, 3, win["ref_index"], win["bgrs"], win["K"], list(win["c2ws"]), 0.5, 5.0, disc)
+    win = scene.make_window(H, W, 3, seed=4)
+    for disc in (0.0, 2.5, 10.0, 37.5, 100.0):
+        m.CallAsync(H, W, 3, win["ref_index"], win["bgrs"], win["K"], list(win["c2ws"]), 0.5, 5.0, disc)
         out = m.GetResult()
         filt, mask, edge, thr = O.filter_edges(torch.from_numpy(out.depth_dense.copy()), disc)
-        assert np.array_equal(m.tensor("edge")[0, :, :, 0], edge.numpy())
-        assert np.array_equal(out.depth, filt.numpy())
-        assert np.array_equal(out.depth == 0, mask.numpy() | (out.depth_dense == 0))
+        assert np.array_equal(m.tensor("edge")[0, :, :, 0], edge.numpy()), disc
+        assert np.array_equal(out.depth, filt.numpy()), disc
+        assert np.array_equal(out.depth == 0, mask.numpy() | (out.depth_dense == 0)), disc
+        print("edge filter %dx%d discard %5.1f: threshold %.6g, %d of %d pixels masked" % (H, W, disc, float(thr), int(mask.sum()), H * W))
+        if disc == 0.0:  # the rank clamps to n - 1: the threshold is the maximum and nothing is masked
+            assert float(thr) == float(edge.max()) and not mask.any() and np.array_equal(out.depth, out.depth_dense)
+        if disc == 100.0:  # rank 0: the threshold is the minimum
+            assert float(thr) == float(edge.min()) and np.array_equal(mask.numpy(), edge.numpy() > float(edge.min()))
+
+
+@pytest.mark.parametrize("H,W", [(32, 32), (32, 96), (128, 160)], ids=["32x32", "32x96", "128x160"])
+def test_edge_filter_is_exact_given_the_same_depth(trained_blob, H, W):
+    """The order-statistic filter is pure comparisons: fed the engine's own depth map, the oracle filter must
+    reproduce the engine's mask bit for bit (module.py:1320-1361).  Discard 0 and 100 are the two ends of the rank (n - 1 and 0); at 32 x 32 the select
+    runs on n = 1024: four workgroups of the histogram kernels, mostly empty bins for the fused scans."""
+    from tandem_amd.dr_mvsnet import DrMvsnet
+    m = DrMvsnet(trained_blob)
+    _edge_filter_is_exact(m, H, W)
+    m.close()
+
+
+@pytest.mark.parametrize("fused", ["0", "1"])
+def test_edge_filter_is_exact_with_and_without_fused_scans(trained_blob, monkeypatch, parity_hooks, fused):
+    """The same at 32 x 32 in both launch forms of the radix select (the parity build reads DR_FILTER_FUSED): a k_scan launch per level (8 launches) and
+    the scans as the prologue of the kernels that follow them (5)."""
+    from tandem_amd.dr_mvsnet import DrMvsnet
+    monkeypatch.setenv("DR_FILTER_FUSED", fused)
+    m = DrMvsnet(trained_blob)
+    _edge_filter_is_exact(m, 32, 32)
+    launches = [r["op"] for r in m.profile() if r["op"].startswith("filter.")]
+    assert len(launches) == (5 if fused == "1" else 8), launches
     m.close()
 
 
