@@ -45,7 +45,8 @@ struct MarchArgs {
   int depth;           // loads a producer wave keeps in flight (1: publish every load before issuing the next)
   int inHp;            // rows a plane has inside the tensor (inH, or 1 for the row march)
   int rm;              // row march
-  int wino;            // 1: the y axis in Winograd F(2,3) form (march_consumer_w): a position is a row PAIR, a.sy = 2, the in-plane tap table lists the x taps only
+  int wino;            // 1, 2: the y axis in Winograd F(2,3) form: a position is a row PAIR, a.sy = 2, the in-plane tap table lists the x taps only
+                       //       (1: march_consumer_w, one output plane per step; 2: march_consumer_ws, the same products in plane-major order)
   int *err;            // raised when a wait gave up (nullptr: not reported)
 };
 
@@ -383,12 +384,12 @@ __device__ inline void march_w_anchor(const MarchWSet<NRP, CT, PT> &o) {
 }
 DR_HD inline float march_w_u1(float g0, float g1h, float g2) { return fmaf(g0 + g2, 0.5f, g1h); }   // shared with the host emulation
 DR_HD inline float march_w_u2(float g0, float g1h, float g2) { return fmaf(g0 + g2, 0.5f, -g1h); }
-template <int NRP, int CT, int PT>
-__device__ inline void march_w_compute(MarchWSet<NRP, CT, PT> &o, floatx4 (&acc)[4][CT][PT]) {
-  float4 u[4][CT];
+// the four Winograd weight fragments of a chunk from its three raw rows (both consumer orders)
+template <int CT>
+__device__ inline void march_w_derive(const float4 (&g)[3][CT], float4 (&u)[4][CT]) {
 #pragma unroll
   for (int ct = 0; ct < CT; ++ct) {
-    const float4 g0 = o.g[0][ct], gh = o.g[1][ct], g2 = o.g[2][ct];
+    const float4 g0 = g[0][ct], gh = g[1][ct], g2 = g[2][ct];
     u[0][ct] = g0; u[3][ct] = g2;
 #ifdef DR_WABL_NO_WT  // timing ablation (results wrong by design): what the per-lane weight transform costs
     u[1][ct] = gh; u[2][ct] = gh;
@@ -397,6 +398,11 @@ __device__ inline void march_w_compute(MarchWSet<NRP, CT, PT> &o, floatx4 (&acc)
     u[2][ct] = make_float4(march_w_u2(g0.x, gh.x, g2.x), march_w_u2(g0.y, gh.y, g2.y), march_w_u2(g0.z, gh.z, g2.z), march_w_u2(g0.w, gh.w, g2.w));
 #endif
   }
+}
+template <int NRP, int CT, int PT>
+__device__ inline void march_w_compute(MarchWSet<NRP, CT, PT> &o, floatx4 (&acc)[4][CT][PT]) {
+  float4 u[4][CT];
+  march_w_derive<CT>(o.g, u);
 #ifndef DR_WABL_NO_IT  // timing ablation: what the input transform costs
   conv_w_transform<PT>(o.d);
 #endif
@@ -529,6 +535,198 @@ __device__ inline void march_consumer_w(const ConvArgs &a, const MarchArgs &m, f
         cur.next_step(m.geo, R);
       }
       L += sg.nl;
+      s += sg.zb - sg.za;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same consumer in SCATTER (plane-major) order.  march_consumer_w walks output planes: step z reads the three resident planes
+// z - 1, z, z + 1, so every input plane is read from LDS and put through the F(2,3) input transform three times, and all three ring
+// slots are live.  Here the loads are walked once, in the order the producers issue them: the four rows of a chunk of plane p are
+// read and transformed ONCE, and their products go to the three output planes p + 1 - dz the plane feeds (weight section dz,
+// march_plan.h march_plane_feeds), each with an accumulator set of its own.  After plane p output plane p - 1 has received everything:
+// its epilogue runs (march_epilogue_w, unchanged), then the sets move up by one plane (32 v_mov against 192 MFMAs; the plane loop
+// unrolled by three with the sets' roles as compile-time constants needed 30 to 70 registers of scratch under the 168 the ten
+// waves leave).  Only the slot of the current plane is live -- it is released after the plane's last ds_read, so the other R - 1
+// slots hold planes fetched ahead, across a change of column as well.
+// Per accumulator the MFMAs arrive in the gather form's order (plane = dz ascending, chunk ascending, the chunk's four k-steps), and
+// the weight derivation and the epilogue are the same functions: the results are bit-identical.
+// The operand pipeline (the next group's weight rows, the next chunk's input rows, fetched under the current 16 MFMAs) runs inside
+// a plane and is filled once per plane, as the gather form fills it once per step: carrying it across planes keeps 28 more
+// registers live through the epilogue and the loop edge, which does not fit either.
+template <int CT>
+struct MarchSG { float4 g[3][CT]; };  // three raw weight rows of one (section, chunk)
+template <int PT>
+struct MarchSD { float4 d[4][PT]; };  // the four rows of a pair's window of one chunk; transformed in place
+template <int K>
+struct MarchPath { static constexpr int value = K; };
+template <int CT>
+__device__ inline void march_s_load_g(const float4 *wsec, int r, MarchSG<CT> &o) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) o.g[k][ct] = wsec[((r * 3 + k) * CT + ct) * 64];
+}
+// (the lane's byte offsets inside a plane are below 48 KB: two to a register)
+template <int NRP, int PT>
+__device__ inline void march_s_load_d(const float4 *tile, const unsigned (&sw)[NRP][2][PT], int r, MarchSD<PT> &o) {
+  const char *tb = reinterpret_cast<const char *>(tile);
+#pragma unroll
+  for (int pt = 0; pt < PT; ++pt)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const unsigned x = sw[r][h][pt];
+      o.d[2 * h][pt] = *reinterpret_cast<const float4 *>(tb + (x & 0xffffu));
+      o.d[2 * h + 1][pt] = *reinterpret_cast<const float4 *>(tb + (x >> 16));
+    }
+}
+template <int CT>
+__device__ inline void march_s_anchor_g(const MarchSG<CT> &o) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) asm volatile("" ::"v"(o.g[k][ct].x), "v"(o.g[k][ct].y), "v"(o.g[k][ct].z), "v"(o.g[k][ct].w));
+}
+template <int PT>
+__device__ inline void march_s_anchor_d(const MarchSD<PT> &o) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt) asm volatile("" ::"v"(o.d[q][pt].x), "v"(o.d[q][pt].y), "v"(o.d[q][pt].z), "v"(o.d[q][pt].w));
+}
+
+template <int CI, int NUP, int CT, int PT, int NPW>
+__device__ inline void march_consumer_ws(const ConvArgs &a, const MarchArgs &m, float4 *lds4, march_flag_t *flags, const float4 *wl, int wave, int lane,
+                                         int s0, int s1) {
+  static_assert(NUP % 3 == 0 && NUP >= 6, "three kernel rows per chunk of x taps, at least two chunks per plane");
+  constexpr int TPC = 16 / CI, NRP = NUP / 3, NG = 3 * NRP;  // NG groups (chunk r, section dz) of 16 * CT * PT MFMAs per plane
+  constexpr int WSEC = NUP * CT * 64;                        // == m.wsec: the sections' offsets are immediates
+  const int j = lane & 15, g = lane >> 4;
+  const int sub = (4 * g) / CI, c4 = ((4 * g) % CI) / 4, ct0 = blockIdx.z * CT;
+  unsigned sw[NRP][2][PT];  // march_consumer_w's table as byte offsets, rows q and q + 1 of the window packed into one register
+#pragma unroll
+  for (int pt = 0; pt < PT; ++pt) {
+    const int bpos = march_bpos(a, wave, pt, PT, j);
+#pragma unroll
+    for (int r = 0; r < NRP; ++r)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const unsigned lo = 16u * (unsigned)conv_a_unit<CI>(bpos + m.tap2d[r * TPC + sub] + (2 * h) * a.TXI, c4);
+        const unsigned hi = 16u * (unsigned)conv_a_unit<CI>(bpos + m.tap2d[r * TPC + sub] + (2 * h + 1) * a.TXI, c4);
+        sw[r][h][pt] = lo | (hi << 16);
+        asm volatile("" : "+v"(sw[r][h][pt]));
+      }
+  }
+  const float4 *wp = wl + lane;
+  const int R = m.R, Dc = m.geo.Dc;
+  floatx4 acc[3][4][CT][PT];  // while plane p is walked: set 0 = output plane p - 1 (section dz = 2), set 1 = p (dz = 1), set 2 = p + 1 (dz = 0)
+  auto clear = [&](floatx4 (&s)[4][CT][PT]) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int pt = 0; pt < PT; ++pt) s[p][ct][pt] = floatx4{0.f, 0.f, 0.f, 0.f};
+  };
+  auto move = [&](floatx4 (&d)[4][CT][PT], const floatx4 (&s)[4][CT][PT]) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int pt = 0; pt < PT; ++pt) {
+          d[p][ct][pt] = s[p][ct][pt];
+        }
+  };
+  clear(acc[0]); clear(acc[1]); clear(acc[2]);
+  MarchSD<PT> dd[2];
+  MarchSG<CT> gg[2];
+  int cached = 0, idx = 0, slot = 0;  // load index of the walk (as the producers count it) and its ring slot
+  for (int po = 0; po < m.NPO; ++po) {
+    const int raw = m.NPO == 1 ? 0 : (po == 0 ? 1 : 2);
+    for (int s = s0; s < s1;) {
+      const MarchSeg sg = march_segment(m.geo, s, s1);
+      int zc, py0, px0;
+      march_tile_origin(a, m, sg.col, zc, py0, px0);
+      for (int i = 0; i < sg.nl; ++i) {
+        const int p = sg.p0 + i;
+        const bool more = i + 1 < sg.nl || s + (sg.zb - sg.za) < s1;  // another load of this channel pass follows (the next pass has other weights)
+        const bool on[3] = {march_plane_feeds(sg, p, 0), march_plane_feeds(sg, p, 1), march_plane_feeds(sg, p, 2)};
+        const float4 *tile = lds4 + (size_t)slot * m.PS;
+        // MAIN: an inner plane of a segment (all three output planes exist, another load follows) -- straight-line code, nothing
+        // conditional around the MFMAs; the planes at the ends of a segment take the guarded copy.
+        auto plane = [&](auto main_path) -> bool {
+          constexpr bool MAIN = decltype(main_path)::value != 0;
+          if (!march_wait_ready<NPW>(flags, idx, cached, m.err, lane)) return false;
+          asm volatile("" ::: "memory");
+          march_s_load_g<CT>(wp, 0, gg[0]);
+          march_s_load_d<NRP, PT>(tile, sw, 0, dd[0]);
+#pragma unroll
+          for (int r = 0; r < NRP; ++r) {
+#pragma unroll
+            for (int dz = 0; dz < 3; ++dz) {
+              const int t = r * 3 + dz;  // compile-time: the sets alternate
+              MarchSG<CT> &gn = gg[(t + 1) & 1];
+              MarchSD<PT> &dn = dd[(r + 1) & 1];
+              if (t + 1 < NG) {
+                march_s_load_g<CT>(wp + (size_t)((dz + 1) % 3) * WSEC, dz == 2 ? r + 1 : r, gn);
+                if (dz == 2) march_s_load_d<NRP, PT>(tile, sw, r + 1, dn);
+              }
+              __builtin_amdgcn_sched_barrier(0);
+              if (dz == 0) conv_w_transform<PT>(dd[r & 1].d);
+              if (MAIN || on[dz]) {
+                float4 u[4][CT];
+                march_w_derive<CT>(gg[t & 1].g, u);
+                conv_w_mfma<CT, PT>(u, dd[r & 1].d, acc[2 - dz]);
+              }
+              __builtin_amdgcn_sched_barrier(0);
+              if (t + 1 < NG) {
+                march_s_anchor_g<CT>(gn);
+                if (dz == 2) march_s_anchor_d<PT>(dn);
+              }
+              // the rows of the plane's last chunk were anchored just above: every ds_read of load idx has returned, nothing reads its slot again.
+              // The last load of a channel pass is released one group before the end instead, behind the last read of the WEIGHTS: the
+              // producers overwrite them for the next pass once every load of this one is released.
+              if ((MAIN || more) ? (r == NRP - 2 && dz == 2) : t == NG - 2) {
+                asm volatile("" ::: "memory");
+                if (lane == 0) flags[kMarchReleased + wave] = idx + 1;
+              }
+            }
+          }
+          // scale and bias are fetched where they are used (the lanes' pointer is laundered so that the loads stay here): eight registers
+          // that the K loop does not carry
+          const float *scp = a.scale, *bip = a.bias;
+          int el = lane;  // the same for the lane's part of the output addresses
+          asm volatile("" : "+s"(scp), "+s"(bip), "+v"(el));
+          const int j = el & 15, g = el >> 4;
+          float4 scv[CT], biv[CT];
+          if (MAIN || on[2] || on[1]) {
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+              scv[ct] = *reinterpret_cast<const float4 *>(scp + (ct0 + ct) * 16 + 4 * g);
+              biv[ct] = *reinterpret_cast<const float4 *>(bip + (ct0 + ct) * 16 + 4 * g);
+            }
+          }
+          if (MAIN || on[2]) {  // output plane p - 1 is complete
+            march_epilogue_w<CT, PT>(a, m, acc[0], scv, biv, raw, wave, j, g, ct0, zc, p - 1, py0, px0);
+          }
+          if (!MAIN && on[1] && p == Dc - 1) {  // and so is the last plane of the volume: nothing lies behind it
+            march_epilogue_w<CT, PT>(a, m, acc[1], scv, biv, raw, wave, j, g, ct0, zc, p, py0, px0);
+            clear(acc[1]);
+          }
+          __builtin_amdgcn_sched_barrier(0);  // (the moves stay behind the epilogue that reads acc[0])
+          move(acc[0], acc[1]);  // the sets move up by one plane
+          move(acc[1], acc[2]);
+          clear(acc[2]);
+          __builtin_amdgcn_sched_barrier(0);
+          return true;
+        };
+        const bool inner = more && on[0] && on[1] && on[2];
+        if (!(inner ? plane(MarchPath<1>{}) : plane(MarchPath<0>{}))) return;
+        ++idx;
+        slot = slot + 1 == R ? 0 : slot + 1;
+      }
       s += sg.zb - sg.za;
     }
   }
@@ -691,6 +889,7 @@ __device__ inline void march_producer_fz(const ConvArgs &a, const MarchArgs &m, 
 }
 
 // grid = (persistent workgroups (multiple of 8), 1, output-row groups); 8 consumer waves + 2 (DMA) or 4 (fused skip) producer waves.
+// W: 0 = direct form, 1 = Winograd form in gather order (march_consumer_w), 2 = Winograd form in scatter order (march_consumer_ws).
 template <int CI, int NUP, int CT, int PT, int FZ = 0, int NCW = 8, int W = 0>
 __global__ __launch_bounds__(64 * (NCW + (FZ ? kMarchFzProducers : kMarchProducers))) void k_conv_m(const ConvArgs a, const MarchArgs m) {
   extern __shared__ float4 lds4[];
@@ -706,7 +905,8 @@ __global__ __launch_bounds__(64 * (NCW + (FZ ? kMarchFzProducers : kMarchProduce
   march_range(m.steps, id, nwg, s0, s1);
   if (s0 >= s1) return;
   if (wave < NCW) {
-    if constexpr (W) march_consumer_w<CI, NUP, CT, PT, kMarchProducers>(a, m, lds4, flags, wl, wave, lane, s0, s1);
+    if constexpr (W == 2) march_consumer_ws<CI, NUP, CT, PT, kMarchProducers>(a, m, lds4, flags, wl, wave, lane, s0, s1);
+    else if constexpr (W) march_consumer_w<CI, NUP, CT, PT, kMarchProducers>(a, m, lds4, flags, wl, wave, lane, s0, s1);
     else march_consumer<CI, NUP, CT, PT, (FZ ? kMarchFzProducers : kMarchProducers)>(a, m, lds4, flags, wl, wave, lane, s0, s1);
   }
   else if constexpr (FZ > 0) march_producer_fz<FZ>(a, m, lds4, flags, wl, wave - NCW, lane, s0, s1, NUP, CT);

@@ -999,6 +999,13 @@ inline bool conv_a_instance_exists(int ci, int ct, int pt) {  // PT = 1 (round 4
   X(16, 3, 2, 1, 8) X(16, 3, 2, 2, 8) X(16, 3, 2, 1, 10) X(16, 3, 2, 2, 10)
 // the Winograd form of the 3-D instances (march_consumer_w): one position tile (16 x by a row pair) per wave
 #define DR_MARCH_W_INSTANCES(X) X(8, 6, 1, 1, 8) X(16, 12, 1, 1, 8) X(16, 9, 1, 1, 8)  // (twelve consumer waves leave 128 registers: the two operand sets spill)
+// Order in which an instance of the Winograd form walks its range: 2 = scatter (march_consumer_ws: every input plane read and transformed
+// once), 1 = gather (march_consumer_w).  DR_MARCH_W_ORDER forces one order on every instance (parity build only: the side-by-side tests and A/Bs).
+inline int conv_march_w_order(int ci, int nup) {
+  (void)ci; (void)nup;
+  if (const char *e = hook_env("DR_MARCH_W_ORDER")) return atoi(e) == 1 ? 1 : 2;
+  return 2;
+}
 inline bool conv_m_instance_exists(int ci, int nup, int ct, int pt, int ncw, bool wino = false) {
 #define DR_X(CI_, NUP_, CT_, PT_, NCW_) if (ci == CI_ && nup == NUP_ && ct == CT_ && pt == PT_ && ncw == NCW_) return true;
   if (wino) { DR_MARCH_W_INSTANCES(DR_X) return false; }
@@ -1257,7 +1264,8 @@ inline ConvPlanOut plan_conv(const ConvLayer &L, ConvMode mode, const float *in,
         for (int ty = 1; ty <= ncw; ++ty) {
           if (ncw % ty) continue;
           const int txt = ncw / ty;
-          if ((ty > 1 && ty / 2 >= nPHw) || (txt > 1 && (txt / 2) * 16 >= nPW)) continue;
+          // (DR_MARCH_ANY_TILE, parity build: tiles more than twice the layer as well -- the unit tests run the kernel on layers of a few rows)
+          if (!hook_env("DR_MARCH_ANY_TILE") && ((ty > 1 && ty / 2 >= nPHw) || (txt > 1 && (txt / 2) * 16 >= nPW))) continue;
           const MarchShape ms = march_shape(L.kd, march_ntp, L.Cin, ci, 1, 1, ty, txt, SX, exy, exx, nPD, nPHw, nPW, CTtot, false, true);
           if (!ms.ok) continue;
           const double spw = std::ceil((double)ms.steps / ms.grid);
@@ -1609,7 +1617,7 @@ inline ConvPlanOut plan_conv(const ConvLayer &L, ConvMode mode, const float *in,
     m.steps = (int)ms.steps;
     m.ncw = ms.ncw;
     m.rm = rm ? 1 : 0;
-    m.wino = wino_raw ? 1 : 0;
+    m.wino = wino_raw ? conv_march_w_order(CI, ms.nup) : 0;
     const long long iplane = (long long)a.inH * a.inW * a.inC, oplane = (long long)a.outH * a.outW * a.outC;
     if (iplane * std::max(1, a.inD) >= (1ll << 31) || oplane * std::max(1, a.outD) >= (1ll << 31)) fail(DR_ERR_ARG, "plan_conv: tensor too large for k_conv_m's 32-bit strides");
     m.i_sv = L.kd == 3 ? 0 : (int)iplane; m.i_sz = rm ? a.inW * a.inC : (L.kd == 3 ? (int)iplane : 0); m.i_sy = rm ? 0 : a.inW * a.inC;
@@ -1705,11 +1713,21 @@ inline void launch_conv(const ConvLaunch &c, hipStream_t st) {
     return;
   }
 #endif
+  if (c.async == 2 && c.march.wino == 2) {
+#define DR_X(CI_, NUP_, CT_, PT_, NCW_) \
+  if (c.ci == CI_ && c.nup == NUP_ && c.ct == CT_ && c.pt == PT_ && c.ncw == NCW_) { launch_conv_m_inst<CI_, NUP_, CT_, PT_, 0, NCW_, 2>(c, st); return; }
+    DR_MARCH_W_INSTANCES(DR_X)
+#undef DR_X
+  }
+#ifdef DR_PARITY_HOOKS  // the gather order: superseded on every instance (conv_march_w_order), kept for the side-by-side tests
   if (c.async == 2 && c.march.wino) {
 #define DR_X(CI_, NUP_, CT_, PT_, NCW_) \
   if (c.ci == CI_ && c.nup == NUP_ && c.ct == CT_ && c.pt == PT_ && c.ncw == NCW_) { launch_conv_m_inst<CI_, NUP_, CT_, PT_, 0, NCW_, 1>(c, st); return; }
     DR_MARCH_W_INSTANCES(DR_X)
 #undef DR_X
+  }
+#endif
+  if (c.async == 2 && c.march.wino) {
     fail(DR_ERR_ARG, "launch_conv: no Winograd marching instance CI=%d NUP=%d CT=%d PT=%d waves=%d", c.ci, c.nup, c.ct, c.pt, c.ncw);
   }
   if (c.async == 2) {

@@ -76,6 +76,19 @@ struct MarchCursor {
   }
 };
 
+// The SCATTER (plane-major) order of the 3-D Winograd consumer (march_consumer_ws; KZ = 3, NPI = 1): the loads of a segment are walked once,
+// in the producer's order, and input plane p feeds output plane p + 1 - dz through weight section dz -- the same (plane, section) pairs as
+// march_section_load, grouped by plane instead of by step.  Load idx is released after the walk over its plane: one live slot.
+DR_HD inline bool march_plane_feeds(const MarchSeg &sg, int p, int dz) {
+  const int zo = p + 1 - dz;
+  return zo >= sg.za && zo < sg.zb;
+}
+// Output planes [lo, hi) of the segment have received every product once plane p is done: p - 1, and p itself at the end of the volume.
+DR_HD inline void march_plane_completes(const MarchGeom &g, const MarchSeg &sg, int p, int &lo, int &hi) {
+  lo = p - 1 >= sg.za ? p - 1 : p;
+  hi = (p == g.Dc - 1 && p < sg.zb) ? p + 1 : p;
+}
+
 // Balanced step range of workgroup `id` of `n`.
 DR_HD inline void march_range(long long steps, int id, int n, int &s0, int &s1) {
   s0 = (int)(steps * id / n);
