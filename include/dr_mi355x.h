@@ -561,9 +561,27 @@ int drf_align_stats(drf_t *h, uint64_t out[6]);
  * drf_get_render_device, or the dense hand-off, never goes through the host).  The call runs on the integration stream, behind any
  * pending scan, and returns when it is done.  It neither changes the map nor allocates a block: drf_stats, the export and the next
  * render are bit-identical with and without it.
- * SCOPE: the resident map only.  With streaming on, blocks in the host store read as absent (their samples are `unobserved`);
- * drf_locate_stats()[5] tells how many there are, and drf_stream_in_region brings them back first.  A map-scope variant that
- * stages stored blocks is not part of this call.
+ * SCOPE (drf_set_locate_scope, below).  DRF_LOCATE_RESIDENT, the default: the resident map only.  With streaming on, blocks in the
+ * host store read as absent (their samples are `unobserved`); drf_locate_stats()[5] tells how many there are.
+ * DRF_LOCATE_MAP: the pool and the host store together -- sums, counts, result and pose are, bit for bit, those of an engine whose
+ * pool holds the whole map, whatever the split between pool and store.  No block moves: the map, the store, the pool and the
+ * streaming state are as the call found them (drf_stream_in_region, the other way to the stored blocks, moves them into the pool,
+ * can fail with DR_ERR_CAPACITY and changes what the next scan evicts).
+ *   selection  An evaluation at a pose reads, for each sample point p of the pixel pyramid (z <= max_sensor_depth), the eight
+ *              lattice corners around it: blocks whose centre lies within 4.5 sqrt(3) voxel_size of p.  The call stages, through
+ *              the staging of the map-scope render, the stored blocks that a DRF_RENDER_MAP render at that pose would stage: the
+ *              same pyramid and sphere widened by (4.5 sqrt(3) + 8 sqrt(3) + 1) voxel_size, a superset with 8 sqrt(3) voxels
+ *              to spare.  A block the pool holds is read from the pool; with an empty store or an empty selection nothing is
+ *              staged and the call is the resident one.
+ *   reuse      A staging made at pose A serves an evaluation at pose B while drift(A, B) = |tA - tB| + ||RA - RB||_F *
+ *              max_sensor_depth * rho <= slack = 8 sqrt(3) voxel_size - 4e-3 * (max_sensor_depth * rho + the widening), rho the
+ *              largest |((u - cx) / fx, (v - cy) / fy, 1)| over the image corners (fusion_host.h: locate_pose_drift,
+ *              locate_stage_slack; DESIGN.md derives both).  A refinement that moves farther selects and stages again at B.
+ *   capacity   stage_capacity_blocks of drf_set_locate_scope bounds one staging (0: min(num_blocks, 8192), the render's
+ *              default); the staging buffer grows to the larger need of its two users.  A selection above it is refused with
+ *              DR_ERR_CAPACITY before anything is evaluated (a later pose of a refinement whose selection exceeds it ends the
+ *              call the same way); the message gives both counts.  Raise the capacity, or use drf_stream_in_region.  Depth bands
+ *              (drf_set_render_bands) do not apply to this call.
  * The rule (one text, fusion_host.h, compiled for the host and for the kernel; double and fp32 without contraction; only + - * /
  * sqrt and floor are used):
  *   pose      pose16 is the engine's own convention: row-major, camera-to-world, metres.  Rd[i][j] = pose16[4 i + j],
@@ -592,8 +610,9 @@ int drf_align_stats(drf_t *h, uint64_t out[6]);
  *             ends where is the same.  res->T is camera-to-world.
  * Legality and refusals, in this order: a null argument (opt and res may be null) or an option that is negative or not finite,
  * DR_ERR_ARG naming the option; not where drf_integrate_scan_async is legal, DR_ERR_PROTOCOL; a pose that drf_transform_map would
- * refuse, DR_ERR_ARG.  DR_OK means the call ran: a refinement that ends DRF_ALIGN_DEGENERATE or DRF_ALIGN_LOST returns DR_OK with
- * res->status set and a message in dr_last_error(). */
+ * refuse, DR_ERR_ARG; in DRF_LOCATE_MAP a selection above the staging's capacity, DR_ERR_CAPACITY.  DR_OK means the call ran: a
+ * refinement that ends DRF_ALIGN_DEGENERATE or DRF_ALIGN_LOST returns DR_OK with res->status set and a message in dr_last_error()
+ * (in DRF_LOCATE_MAP it says how many of the stored blocks were staged). */
 typedef struct {
   int    max_iters;     /* 0 -> 30 */
   int    min_weight;    /* 0 -> 1; a voxel counts as observed iff weight >= min_weight */
@@ -618,6 +637,14 @@ int drf_locate_frame_device(drf_t *h, const void *d_depth, const float pose_init
 /* last drf_locate_*: [0] grid positions, [1] samples, [2] valid samples at the last evaluation, [3] system evaluations, [4] device
  * bytes held during the call, [5] blocks in the host store at the call (all 0 after a call that was refused) */
 int drf_locate_stats(drf_t *h, uint64_t out[6]);
+/* What drf_locate_* read (SCOPE above).  Unknown scope: DR_ERR_ARG; between RenderAsync and GetRenderResult: DR_ERR_PROTOCOL, as for
+ * drf_set_render_scope (the two share the staging). */
+#define DRF_LOCATE_RESIDENT 0   /* default */
+#define DRF_LOCATE_MAP      1
+int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks);
+/* last drf_locate_*: [0] stagings made, [1] blocks in the largest staging, [2] blocks staged in total, [3] evaluations that read a
+ * staging (all 0 in resident scope, with nothing to stage, or after a call that was refused) */
+int drf_locate_stage_stats(drf_t *h, uint64_t out[4]);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

@@ -146,6 +146,8 @@ SIGNATURES = {
     "drf_locate_system_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
     "drf_locate_frame_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
     "drf_locate_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_set_locate_scope": (C.c_int, [vp, C.c_int, C.c_size_t]),
+    "drf_locate_stage_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
 
 

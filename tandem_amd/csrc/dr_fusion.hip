@@ -1519,7 +1519,7 @@ class FusionEngine {
   // evaluator: k_map_locate + k_align_fold on int_stream_, 28 doubles and 4 counters back through the pinned pair.
   template <class Body>
   void with_locate(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_locate_options_t *opt, Body &&body) {
-    for (auto &v : lc_stats_) v = 0;
+    locate_reset();
     LocateOpt lo;
     if (const char *bad = locate_options(opt, o_.truncation_distance, lo)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
     expect_integrate(who);
@@ -1535,6 +1535,24 @@ class FusionEngine {
     mio_.ensure(1);
     double *partial = (double *)lc_buf_.get();
     unsigned long long *counts = (unsigned long long *)(partial + max_groups * 28);
+    // Map scope (drf_set_locate_scope): the stored blocks an evaluation at the pose can read go through the render's staging, rs_
+    // -- no render reads it here: the call is legal only where a scan is, and the device is idle.  A staging serves the poses that
+    // follow while locate_stage_serves says so; a pose beyond that selects and stages again.  With an empty store or an empty
+    // selection nothing is staged and the resident kernel is launched.
+    const bool map_scope = locate_scope_ == DRF_LOCATE_MAP && !store_.empty();
+    double slack = locate_stage_slack(o_);
+    if (const char *env = hook_env("DR_LOCATE_STAGE_SLACK")) slack = std::min(slack, std::max(0.0, atof(env)) * (double)o_.voxel_size);  // parity hook, in voxels
+    std::vector<unsigned long long> keys;  // the selection at sel_pose
+    float sel_pose[16];
+    RenderStage sg{};
+    bool staged = false, selected = false;
+    if (map_scope) {  // the refusal: decided at the first pose, before anything is evaluated
+      locate_pose16(map_motion(pose16, o_.voxel_size), o_.voxel_size, sel_pose);
+      keys = select_locate_blocks(store_, o_, sel_pose);
+      if (keys.size() > lc_capacity())
+        fail(DR_ERR_CAPACITY, "%s: the pose can read %zu stored blocks, the locate staging holds %zu (drf_set_locate_scope with a larger capacity, or drf_stream_in_region)",
+             who, keys.size(), lc_capacity());
+    }
     const float *depth = (const float *)d_depth;
     if (h_depth) {
       float *mine = (float *)(counts + 4);
@@ -1543,23 +1561,64 @@ class FusionEngine {
       depth = mine;
     }
     lc_stats_[0] = (uint64_t)total; lc_stats_[4] = lc_buf_.capacity(); lc_stats_[5] = store_.size();
+    // the slot's flags go back to zero behind the evaluations that read it (they are on int_stream_)
+    auto release = [&](bool may_throw) {
+      if (!staged) return;
+      staged = false;
+      hipError_t err = hipEventRecord(rs_.used(), int_stream_);
+      if (err == hipSuccess) err = hipStreamWaitEvent(rs_.stream(), rs_.used(), 0);
+      if (err == hipSuccess) {
+        hipLaunchKernelGGL(k_rs_clear, dim3(cdiv(sg.n, 256)), dim3(256), 0, rs_.stream(), sg.keys, sg.n, rs_super_[rs_.slot()][0], rs_super_[rs_.slot()][1]);
+        err = hipGetLastError();
+      }
+      if (may_throw) DR_HIP(err);
+    };
     auto eval = [&](const AlignEval &e, double sums[28], uint64_t c4[4]) {
+      if (map_scope) {
+        float p16[16];
+        locate_pose16(e.m, o_.voxel_size, p16);
+        if (selected && !locate_stage_serves(o_, sel_pose, p16, slack)) {
+          keys = select_locate_blocks(store_, o_, p16);
+          if (keys.size() > lc_capacity())
+            fail(DR_ERR_CAPACITY, "%s: a pose of the refinement can read %zu stored blocks, the locate staging holds %zu (drf_set_locate_scope with a larger capacity, or drf_stream_in_region)",
+                 who, keys.size(), lc_capacity());
+          memcpy(sel_pose, p16, sizeof p16);
+          selected = false;
+        }
+        if (!selected) {
+          release(true);
+          if (!keys.empty()) {
+            sg = stage_render(keys);
+            staged = true;
+            ++ls_stats_[0]; ls_stats_[1] = std::max<uint64_t>(ls_stats_[1], keys.size()); ls_stats_[2] += keys.size();
+          }
+          selected = true;
+        }
+      }
       mio_.evaluate(partial, groups, counts, 4, sums, c4, [&] {
-        hipLaunchKernelGGL(k_map_locate, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, d_, depth, lg, e, groups, total, partial, counts);
+        if (staged) {
+          rs_.wait_ready(int_stream_);
+          hipLaunchKernelGGL(k_map_locate_staged, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, d_, depth, lg, e, groups, total, partial, counts, sg);
+        } else {
+          hipLaunchKernelGGL(k_map_locate, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, d_, depth, lg, e, groups, total, partial, counts);
+        }
         DR_HIP(hipGetLastError());
       });
       lc_stats_[1] = c4[0]; lc_stats_[2] = c4[1]; ++lc_stats_[3];
+      if (staged) ++ls_stats_[3];
     };
     try {
       body(lo, eval);
     } catch (...) {
-      for (auto &v : lc_stats_) v = 0;
+      release(false);
+      locate_reset();
       throw;
     }
+    release(true);
   }
   void locate_system(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_locate_options_t *opt, double *sums,
                      uint64_t *counts) {
-    for (auto &v : lc_stats_) v = 0;
+    locate_reset();
     if (!(h_depth || d_depth) || !pose16 || !sums || !counts) fail(DR_ERR_ARG, "%s: null argument", who);
     with_locate(who, h_depth, d_depth, pose16, opt, [&](const LocateOpt &lo, auto &eval) {
       double c_src[3];
@@ -1570,7 +1629,7 @@ class FusionEngine {
   // returns what dr_last_error() says after a refinement that ran but found no pose (empty otherwise)
   std::string locate_frame(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_locate_options_t *opt, float *pose16_out,
                            drf_align_result_t *res) {
-    for (auto &v : lc_stats_) v = 0;
+    locate_reset();
     if (!(h_depth || d_depth) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
     drf_align_result_t r;
     uint64_t c4[4] = {0, 0, 0, 0};
@@ -1579,9 +1638,22 @@ class FusionEngine {
     if (res) *res = r;
     return no_pose_note(std::string(who) + ": the refinement", r,
                         ", " + std::to_string((unsigned long long)c4[2]) + " unobserved, " + std::to_string((unsigned long long)c4[3]) + " outside the band; " +
-                            std::to_string(store_.size()) + " blocks are in the host store)");
+                            std::to_string(store_.size()) + " blocks are in the host store" +
+                            (locate_scope_ == DRF_LOCATE_MAP ? ", " + std::to_string((unsigned long long)ls_stats_[1]) + " of them staged" : std::string()) + ")");
   }
   void locate_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = lc_stats_[i]; }
+  // DRF_LOCATE_RESIDENT: drf_locate_* read the pool (the default); DRF_LOCATE_MAP: the pool and the host store together.
+  // stage_capacity_blocks bounds what one evaluation may stage (0 = the render's default); rs_ holds the larger of the two needs.
+  void set_locate_scope(int scope, size_t stage_capacity_blocks) {
+    if (scope != DRF_LOCATE_RESIDENT && scope != DRF_LOCATE_MAP) fail(DR_ERR_ARG, "drf_set_locate_scope: unknown scope %d", scope);
+    if (next_ == kGetRender) fail(DR_ERR_PROTOCOL, "drf_set_locate_scope: a render is pending, call GetRenderResult first");
+    locate_scope_ = scope;
+    lc_cap_req_ = stage_capacity_blocks;
+  }
+  void locate_stage_stats(uint64_t out[4]) const {
+    if (!out) fail(DR_ERR_ARG, "drf_locate_stage_stats: null argument");
+    for (int i = 0; i < 4; ++i) out[i] = ls_stats_[i];
+  }
 
  private:
   enum Next { kIntegrate, kRender, kGetRender };
@@ -1758,6 +1830,11 @@ class FusionEngine {
   }
   // ---- the render scope (DRF_RENDER_MAP; DESIGN.md §7c "Rendering the whole map") ----
   size_t rs_capacity() const { return rs_cap_req_ ? rs_cap_req_ : (size_t)std::min(o_.num_blocks, kStageBlocks); }
+  size_t lc_capacity() const { return lc_cap_req_ ? lc_cap_req_ : (size_t)std::min(o_.num_blocks, kStageBlocks); }
+  void locate_reset() {
+    for (auto &v : lc_stats_) v = 0;
+    for (auto &v : ls_stats_) v = 0;
+  }
   // The union of stored blocks the poses can read.  Blocks the last scan's eviction chain gathered are not in the store yet: only
   // a pose that could reach one (render_needs_fold) waits for the scan and folds them first.
   RenderStagePlan plan_render(const float *const *poses, int n, bool &waited) {
@@ -1782,7 +1859,8 @@ class FusionEngine {
         for (int l = 0; l < kSuperLevels; ++l) f[l] = own_.device<unsigned char>((size_t)1 << (3 * (kGridBits - kSuperShift[l])), rs_.stream());
     }
     if (n <= rs_blocks_) return;
-    const size_t want = std::min(rs_capacity(), std::max(2 * rs_blocks_, (n + 1023) & ~(size_t)1023));
+    const size_t cap = locate_scope_ == DRF_LOCATE_MAP ? std::max(rs_capacity(), lc_capacity()) : rs_capacity();  // the larger need of its two users
+    const size_t want = std::min(cap, std::max(2 * rs_blocks_, (n + 1023) & ~(size_t)1023));
     DR_HIP(hipDeviceSynchronize());  // no copy or kernel reads the old allocations
     rs_.reserve((want + 1) * 8 + want * 4096);
     for (auto &t : rs_table_) t.reserve(stage_table_slots(want), rs_.stream());
@@ -2170,6 +2248,9 @@ class FusionEngine {
   uint64_t mg_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_merge_stats
   DeviceBuf<unsigned char> lc_buf_;            // drf_locate_*: partial sums, counters and a host-given depth image (sized once)
   uint64_t lc_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_locate_stats
+  int locate_scope_ = DRF_LOCATE_RESIDENT;     // drf_set_locate_scope
+  size_t lc_cap_req_ = 0;
+  uint64_t ls_stats_[4] = {0, 0, 0, 0};        // drf_locate_stage_stats
 };
 
 }  // namespace dr
@@ -2387,6 +2468,8 @@ int drf_locate_frame_device(drf_t *h, const void *d_depth, const float pose_init
 int drf_locate_stats(drf_t *h, uint64_t out[6]) {
   return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_locate_stats: null argument"); eng(h)->locate_stats(out); });
 }
+int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_locate_scope(scope, stage_capacity_blocks); }); }
+int drf_locate_stage_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->locate_stage_stats(out); }); }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }
 int drf_render_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->render_stats(out); }); }
 int drf_set_render_bands(drf_t *h, int max_passes) { return guarded([&] { eng(h)->set_render_bands(max_passes); }); }

@@ -307,6 +307,48 @@ inline RenderStagePlan plan_render_stage(const HostBlockStore &store, const drf_
 }
 // the capacity decision of a RenderAsync: the union is what is staged, however many poses share a block
 inline bool render_stage_fits(const RenderStagePlan &p, size_t capacity_blocks) { return p.keys.size() <= capacity_blocks; }
+// ---- the locate scope (DRF_LOCATE_MAP; DESIGN.md §7c "Locating in the whole map"): which stored blocks one evaluation of
+// drf_locate_* at a pose can read, and how long a staging of them serves the poses that follow.
+// A sample is a point R (z (lx, ly, 1)) + t of the pixel pyramid with z <= max_sensor_depth; its eight corners floor(q) + {0, 1}^3
+// lie within sqrt(3) voxels of it and a block's farthest voxel 3.5 sqrt(3) voxels from the block's centre: every block read has
+// its centre within 4.5 sqrt(3) vs of a sample point -- the ray-cast's own term.  select_render_blocks widens pyramid and sphere by
+// render_margin = 4.5 sqrt(3) vs + 8 sqrt(3) vs + vs, so its selection at the pose is a superset with 8 sqrt(3) vs + vs to spare.
+// Of that spare part, a pose that is rigid only within pose_is_rigid's 1e-3 takes up to 4e-3 render_reach (select_render_blocks
+// says how), and the vs covers the pose's rounding from the loop's doubles to the floats these functions take (below).  What is
+// left is the slack: how far every sample point may move while the selection still holds each block read.  It is 0 where
+// select_render_blocks drops the cut (then every moved pose stages again).
+inline double locate_stage_slack(const drf_options_t &o) {
+  if (!stream_options_ok(o)) return 0.0;
+  const double s = 8.0 * std::sqrt(3.0) * (double)o.voxel_size - 4e-3 * render_reach(o);
+  return s > 0.0 && std::isfinite(s) ? s : 0.0;
+}
+// An upper bound on how far any sample point moves between two poses: |(RA - RB) g + tA - tB| <= |tA - tB| + ||RA - RB||_2 |g|,
+// |g| <= max_sensor_depth * corner_rho, and the Frobenius norm bounds the spectral one.  Symmetric, and 0 for A = B.
+inline double locate_pose_drift(const drf_options_t &o, const float *poseA16, const float *poseB16) {
+  double t2 = 0.0, r2 = 0.0;
+  for (int i = 0; i < 3; ++i) {
+    const double dt = (double)poseA16[4 * i + 3] - (double)poseB16[4 * i + 3];
+    t2 += dt * dt;
+    for (int j = 0; j < 3; ++j) {
+      const double dr = (double)poseA16[4 * i + j] - (double)poseB16[4 * i + j];
+      r2 += dr * dr;
+    }
+  }
+  return std::sqrt(t2) + std::sqrt(r2) * (double)o.max_sensor_depth * corner_rho(o);
+}
+// The staging selected at pose A serves an evaluation at pose B iff this holds (NaN: it does not).
+inline bool locate_stage_serves(const drf_options_t &o, const float *poseA16, const float *poseB16, double slack) {
+  return locate_pose_drift(o, poseA16, poseB16) <= slack;
+}
+// What one evaluation stages: the render's selection at the pose, ascending (select_render_blocks appends each block once).
+inline std::vector<unsigned long long> select_locate_blocks(const HostBlockStore &store, const drf_options_t &o, const float *pose16) {
+  std::vector<unsigned long long> keys;
+  if (store.empty()) return keys;
+  select_render_blocks(store, o, pose16, keys);
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  return keys;
+}
 // ---- depth bands (drf_set_render_bands; DESIGN.md §7c "Rendering beyond the staging"): a union that exceeds the staging is
 // ray-cast in passes over consecutive slabs of camera-frame depth [z_j, z_j+1), common to all poses of the call.  A loop sample
 // of pass j lies at depth cur in [z_j, z_j+1), its final colour sample in [cur - trunc, cur + vs), and a sample at depth z reads
@@ -1056,6 +1098,18 @@ DR_HOST_DEVICE inline bool locate_pixel(const LocateGrid &lg, double vs, int n, 
   g[1] = ((((double)v - (double)lg.cy) / (double)lg.fy) * z) / vs;
   g[2] = z / vs;
   return true;
+}
+// The loop's pose (Rd, tv in lattice units, double) as the pose16 the two functions above and select_render_blocks take.  The
+// evaluation itself runs at the double pose: an entry of R moves by at most 2^-25 and t_k by 2^-25 |t_k| plus the product's own
+// rounding, so a sample point moves by less than 2^-24 (3 max_sensor_depth rho + |t|).  |t| is below 2^23 voxels wherever a block
+// has a key, and the depth range far below that: less than one voxel, the vs that locate_stage_slack leaves out of the slack.
+inline void locate_pose16(const MapMotion &m, float voxel_size, float pose16[16]) {
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) pose16[4 * i + j] = (float)m.R[3 * i + j];
+    pose16[4 * i + 3] = (float)(m.tv[i] * (double)voxel_size);
+  }
+  pose16[12] = pose16[13] = pose16[14] = 0.0f;
+  pose16[15] = 1.0f;
 }
 // Group i in the wave's order: lane l takes grid positions 512 i + l + 64 k, k = 0..7 (those >= Wg * Hg are no samples), then the
 // butterfly.  out[28] = the group's sums; counts += {samples, valid, unobserved, outside}.

@@ -24,6 +24,8 @@ def DrFusionOptions(**kw):
 MESH_RESIDENT, MESH_MAP = 0, 1
 # drf_set_render_scope: what RenderAsync ray-casts
 RENDER_RESIDENT, RENDER_MAP = 0, 1
+# drf_set_locate_scope: what locate_system / locate_frame read
+LOCATE_RESIDENT, LOCATE_MAP = 0, 1
 
 
 MESH_UPDATE_MAX_SCANS = 16  # DRF_MESH_UPDATE_MAX_SCANS: one scan more between two updates makes the next one full
@@ -391,7 +393,7 @@ class DrFusion:
         """Refines pose_init (camera-to-world) so that the depth image lies on the surface of the map this engine holds and returns
         an AlignResult (T, T32: camera-to-world); T32 is the pose IntegrateScanAsync takes to continue the map.  The call refines:
         pose_init must bring the points inside the truncation band.  Only resident blocks are read (locate_stats()[5] counts the
-        blocks in the host store).  A refinement that ends ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the
+        blocks in the host store) unless set_locate_scope(LOCATE_MAP) was called.  A refinement that ends ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the
         result) unless raise_on_failure is false."""
         dev, d, keep = self._locate_depth(depth)
         pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
@@ -411,6 +413,20 @@ class DrFusion:
         device bytes held during the call, blocks in the host store at the call)."""
         out = (C.c_uint64 * 6)()
         check(self._L.drf_locate_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def set_locate_scope(self, scope, stage_capacity_blocks=0):
+        """LOCATE_RESIDENT (default): locate_system / locate_frame read the pool; LOCATE_MAP: the pool and the host store -- the
+        same bits as on an engine whose pool holds the whole map, and no block moves.  The stored blocks an evaluation can read are
+        staged through stage_capacity_blocks blocks of device scratch (0 = min(num_blocks, 8192)); a call that needs more raises
+        DrError DR_ERR_CAPACITY and changes nothing."""
+        check(self._L.drf_set_locate_scope(self._h, int(scope), int(stage_capacity_blocks)))
+
+    def locate_stage_stats(self):
+        """Last locate_system / locate_frame: (stagings made, blocks in the largest staging, blocks staged in total, evaluations
+        that read a staging); all 0 in resident scope or with nothing to stage."""
+        out = (C.c_uint64 * 4)()
+        check(self._L.drf_locate_stage_stats(self._h, out))
         return tuple(int(v) for v in out)
 
     def set_render_scope(self, scope, stage_capacity_blocks=0):

@@ -123,6 +123,9 @@ public:
     check(drf_locate_frame(impl, depth, pose_init16, nullptr, pose16_out, &res));
     return res.status;
   }
+  // DRF_LOCATE_MAP: LocateDepthFrame reads resident and host-stored blocks together, without moving one (capacity 0 = the default
+  // staging); DRF_LOCATE_RESIDENT, the default: the pool only
+  void SetLocateScope(int scope, size_t capacity = 0) { check(drf_set_locate_scope(impl, scope, capacity)); }
 
   // Incremental mesh (dr_mi355x.h "incremental mesh", INTEGRATION.md "Incremental mesh"): GetMeshUpdateSync fills dr_mesh_num /
   // dr_mesh_vert / dr_mesh_cols with the triangles of the listed blocks only, and the members below name the blocks: block i has
