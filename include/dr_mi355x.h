@@ -554,7 +554,9 @@ int drf_align_stats(drf_t *h, uint64_t out[6]);
  * continue a map brought in by drf_load_map, the start from which drf_transform_map and drf_merge_map bring a second session over,
  * and a per-frame drift check of a running session.  The call minimises, over the depth pixels, the map's sdf interpolated at the
  * pixel's point (depth-to-SDF, Gauss-Newton with Huber weights); it REFINES, as drf_align_map does: pose_init must bring the
- * points inside the truncation band.  No damping, no coarse-to-fine, no global search.  drf_locate_system evaluates the system
+ * points inside the truncation band.  No damping, no coarse-to-fine, no global search (from a pose that is only good to decimetres
+ * and degrees call drf_track_frame, below, first: its basin is set by a projective association, not by the band, and it ends
+ * inside this call's).  drf_locate_system evaluates the system
  * once at pose16: the score of a pose hypothesis (sums[27] / counts[1], counts[1] / counts[0]).
  * The map is read where it lives, through the dense grid and the far-block table: nothing is uploaded but the depth image (through
  * the engine's pinned input buffer; the _device forms take a device pointer as drf_integrate_device does -- a rendered depth from
@@ -645,6 +647,84 @@ int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks);
 /* last drf_locate_*: [0] stagings made, [1] blocks in the largest staging, [2] blocks staged in total, [3] evaluations that read a
  * staging (all 0 in resident scope, with nothing to stage, or after a call that was refused) */
 int drf_locate_stage_stats(drf_t *h, uint64_t out[4]);
+/* Tracks a depth frame against the ray-cast model of the map the engine holds (DESIGN.md §7c "Tracking a depth frame against the
+ * ray-cast model"): the classical frame-to-model step, projective data association and point-to-plane Gauss-Newton.  Where
+ * drf_locate_frame needs a start inside the truncation band (a few centimetres), this call's basin is set by the association:
+ * decimetres and some ten degrees.  It ends close enough for drf_locate_frame to do the sub-voxel part -- the ray-cast stops up to
+ * one voxel in front of the surface, so this call alone is good to about a voxel.  From a rough pose: drf_track_frame, then
+ * drf_locate_frame from the pose it returns.  Out of scope: a global search, colour / photometric terms, a test that compares
+ * the frame's own normals with the model's, and an image pyramid.
+ * drf_track_frame renders the map at the current estimate into buffers of its own -- the engine's ray-cast, under
+ * drf_set_render_scope and drf_set_render_bands as drf_render_async plans it (DRF_RENDER_MAP reads the host store too, and a
+ * selection above the staging is DR_ERR_CAPACITY in the same way) -- builds the model map, runs a few evaluations against it and
+ * renders again.  The public render buffers, drf_get_render_device and the render protocol are not touched; the map is neither
+ * changed nor grown.  The call runs on the integration stream behind any pending scan and returns when it is done.
+ * drf_track_system is one evaluation against a model depth image the caller supplies (a ray-cast at model_pose16): it reads no map.
+ * The rule (one text, fusion_host.h, compiled for the host and for the kernels; double and fp32 without contraction; only + - * /
+ * sqrt and floor are used):
+ *   model map Per pixel (u, v) of the model depth image Dm (height x width floats, a ray-cast at the pose Pm) four fp32 values
+ *             (nx, ny, nz, z), all 0 where the pixel is INVALID.  A miss of the ray-cast is the 0.0f it writes for a ray that found
+ *             no surface; the test is !(z > 0), which a NaN and a negative value fail too.  Invalid: the pixel is a miss; it lies
+ *             on the image border (u = 0, v = 0, u = width - 1 or v = height - 1); one of its neighbours (u - 1, v), (u + 1, v),
+ *             (u, v - 1), (u, v + 1) is a miss; or |z_neighbour - z| > max_jump for one of them (fp32 subtraction and compare: a
+ *             depth discontinuity).  Otherwise, in fp32, X(u, v, z) = ((((float)u - cx) / fx) * z, (((float)v - cy) / fy) * z, z),
+ *             a = X(u + 1, v, Dm(u + 1, v)) - X(u - 1, v, Dm(u - 1, v)), b = X(u, v + 1, ..) - X(u, v - 1, ..) (each component
+ *             the difference of the two products), n = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0),
+ *             l2 = (n0 n0 + n1 n1) + n2 n2; !(l2 > 0) is invalid; n = n / sqrt(l2) component by component; and with
+ *             s = (n0 X0 + n1 X1) + n2 X2 at the centre pixel, s > 0 negates n, so that the normal looks at the camera.
+ *             z = Dm(u, v).
+ *   sample    drf_locate_*'s grid, test and point: grid position n = j * Wg + i with pixel stride step, a SAMPLE iff dep > 0,
+ *             dep >= min_sensor_depth and dep <= max_sensor_depth in fp32; g in double as there; q = Rd g + tv at the estimate.
+ *   association  in double.  (Rm, tvm) = model_pose16 as a pose is read above.  s = q - tvm, m_k = (Rm[0][k] s0 + Rm[1][k] s1) +
+ *             Rm[2][k] s2: the point in the model camera.  !(m2 > 0) is UNASSOCIATED.  u' = (double)fx * (m0 / m2) + (double)cx,
+ *             v' = (double)fy * (m1 / m2) + (double)cy, pu = floor(u' + 0.5), pv = floor(v' + 0.5); outside 0 <= pu <= width - 1,
+ *             0 <= pv <= height - 1, or at an invalid model pixel, is UNASSOCIATED.  z = (double)(the pixel's z),
+ *             vm = ((((pu - cx) / fx) * z) / vs, (((pv - cy) / fy) * z) / vs, z / vs), d = m - vm.  If
+ *             (d0 d0 + d1 d1) + d2 d2 <= lim * lim is false, lim = (double)dist_max / vs, the sample is REJECTED.
+ *   residual  n = the pixel's normal widened to double; r = (n0 d0 + n1 d1) + n2 d2, the point-to-plane distance in voxels;
+ *             nw_k = (Rm[k][0] n0 + Rm[k][1] n1) + Rm[k][2] n2; x = q - c; J = (x cross nw, nw).  From here Huber's weight and the
+ *             28 sums are drf_align_map's.  centre: drf_locate_*'s (centre_depth).
+ *   order     drf_locate_*'s groups, lanes, butterfly and fold.  counts = {samples, valid, unassociated, rejected}.
+ *   step, loop, statuses: drf_align_map's, the loop given {samples, valid, unassociated + rejected}.
+ *   outer loop  p16 = pose_init16.  A round renders the model at p16, builds the model map and runs the loop from that very pose
+ *             (Rd, tv read from p16; Pm = p16) for at most inner_iters evaluations.  A round that ends DRF_ALIGN_LOST or
+ *             DRF_ALIGN_DEGENERATE ends the call with that status, what ends where as for drf_locate_frame; a round that
+ *             converges at its first evaluation ends the call DRF_ALIGN_CONVERGED; after any other round p16 = the round's T
+ *             rounded to float (what a drf_render_async at that pose16 renders, bit for bit), and after max_renders rounds the
+ *             call is DRF_ALIGN_MAX_ITERS.  res: T, sums, samples, valid, cost of the last round, valid0 and cost0 of the
+ *             first, iterations = the evaluations of all rounds.
+ * Legality and refusals, in drf_locate_frame's order: a null argument (opt and res may be null) or an option that is negative or
+ * not finite, DR_ERR_ARG naming it; not where drf_integrate_scan_async is legal, DR_ERR_PROTOCOL; a pose (or model pose) that
+ * drf_transform_map would refuse, DR_ERR_ARG; the render's DR_ERR_CAPACITY.  drf_track_stats is all zero after a refused call.
+ * DR_OK means the call ran: DRF_ALIGN_DEGENERATE or DRF_ALIGN_LOST return DR_OK with res->status set and a message in
+ * dr_last_error().  Device memory is sized once per engine: 16 W H (model map) + 4 W H (model depth) + 4 W H (the frame) bytes, the
+ * groups' partial sums and 64 bytes of counters. */
+typedef struct {
+  int    max_renders;   /* 0 -> 10 */
+  int    inner_iters;   /* evaluations per render; 0 -> 4 */
+  int    step;          /* pixel stride of the sample grid; 0 -> 1 */
+  float  dist_max;      /* metres; 0 -> 25 * voxel_size; a sample farther than this from its model vertex is rejected */
+  float  max_jump;      /* metres; 0 -> 5 * voxel_size; neighbouring model depths that differ by more are a discontinuity */
+  float  huber;         /* voxels; 0 -> 1.0 */
+  float  centre_depth;  /* metres, as in drf_locate_options_t */
+  double eps_rot;       /* rad; 0 -> 1e-7 */
+  double eps_trans;     /* voxels; 0 -> 1e-5 */
+  double min_valid;     /* share of the samples that must be valid; 0 -> 0.25 */
+} drf_track_options_t;
+/* one evaluation at pose16 against the model depth ray-cast at model_pose16: sums[28], counts = {samples, valid, unassociated, rejected} */
+int drf_track_system(drf_t *h, const float *depth, const float *model_depth, const float model_pose16[16], const float pose16[16],
+                     const drf_track_options_t *opt, double sums[28], uint64_t counts[4]);
+/* the tracking from pose_init16; pose16_out = res->T rounded to float */
+int drf_track_frame(drf_t *h, const float *depth, const float pose_init16[16], const drf_track_options_t *opt, float pose16_out[16],
+                    drf_align_result_t *res);
+/* the same with the images in device memory */
+int drf_track_system_device(drf_t *h, const void *d_depth, const void *d_model_depth, const float model_pose16[16], const float pose16[16],
+                            const drf_track_options_t *opt, double sums[28], uint64_t counts[4]);
+int drf_track_frame_device(drf_t *h, const void *d_depth, const float pose_init16[16], const drf_track_options_t *opt, float pose16_out[16],
+                           drf_align_result_t *res);
+/* last drf_track_*: [0] grid positions, [1] samples, [2] valid samples at the last evaluation, [3] system evaluations, [4] renders,
+ * [5] device bytes held (all 0 after a call that was refused) */
+int drf_track_stats(drf_t *h, uint64_t out[6]);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

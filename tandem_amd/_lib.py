@@ -148,6 +148,11 @@ SIGNATURES = {
     "drf_locate_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "drf_set_locate_scope": (C.c_int, [vp, C.c_int, C.c_size_t]),
     "drf_locate_stage_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_track_system": (C.c_int, [vp, f32p, f32p, f32p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_track_frame": (C.c_int, [vp, f32p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_track_system_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_track_frame_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_track_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
 
 
@@ -161,6 +166,12 @@ class LocateOptions(C.Structure):
     """drf_locate_options_t: a zero field means its default."""
     _fields_ = [("max_iters", C.c_int), ("min_weight", C.c_int), ("step", C.c_int), ("band", C.c_float), ("huber", C.c_float),
                 ("centre_depth", C.c_float), ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("min_valid", C.c_double)]
+
+
+class TrackOptions(C.Structure):
+    """drf_track_options_t: a zero field means its default."""
+    _fields_ = [("max_renders", C.c_int), ("inner_iters", C.c_int), ("step", C.c_int), ("dist_max", C.c_float), ("max_jump", C.c_float),
+                ("huber", C.c_float), ("centre_depth", C.c_float), ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("min_valid", C.c_double)]
 
 
 class AlignResultStruct(C.Structure):

@@ -673,6 +673,7 @@ __global__ void k_fill_keys(unsigned long long *keys, size_t n) {
 #include "stream_kernels.h"
 #include "align_kernels.h"  // k_map_align / k_align_fold (drf_align_system, drf_align_map)
 #include "locate_kernels.h"  // k_map_locate (drf_locate_system, drf_locate_frame)
+#include "track_kernels.h"   // k_track_model, k_track (drf_track_system, drf_track_frame)
 
 }  // namespace dr
 #include "mesh_kernels.h"
@@ -918,21 +919,35 @@ class FusionEngine {
     bool waited = false;
     if (render_scope_ == DRF_RENDER_MAP) {
       for (int i = 0; i < n; ++i) if (!poses[i]) fail(DR_ERR_ARG, "RenderAsync: null pose");
-      plan = plan_render(poses, n, waited);
-      if (!render_stage_fits(plan, rs_capacity())) {
-        // depth bands (drf_set_render_bands): the union may exceed the staging as long as every band fits it
-        if (render_bands_ >= 2) bands = plan_render_bands(store_, o_, poses, n, rs_capacity(), render_bands_);
-        if (!bands.ok)
-          fail(DR_ERR_CAPACITY, "RenderAsync: the poses can read %zu stored blocks, the render staging holds %zu (drf_set_render_scope%s)", plan.keys.size(), rs_capacity(),
-               render_bands_ >= 2 ? "; no plan of depth bands within drf_set_render_bands either" : "");
-      }
-#ifdef DR_PARITY_HOOKS
-      if (!plan.keys.empty() && (raycast_v1_ || raycast_stats_ || raycast_sampler_ == 0))
-        fail(DR_ERR_UNSUPPORTED, "RenderAsync: the superseded ray-cast generations have no staged form (DRF_RENDER_MAP with stored blocks in reach)");
-#endif
+      plan_render_call("RenderAsync", poses, n, plan, bands, waited);
     }
     next_ = kGetRender;
     free_slot_ ^= 1;  // write into the buffers NOT handed out by the last GetRenderResult
+    const PassStats ps = render_passes(plan, bands, renders_.data(), poses, n, true);
+    render_stats_[0] = plan.keys.size(); render_stats_[1] = ps.total * (size_t)(8 + 4096);
+    render_stats_[2] = (uint64_t)plan.whole; render_stats_[3] = waited ? 1 : 0;
+    band_stats_[0] = ps.staged ? ps.passes : 0; band_stats_[1] = ps.largest; band_stats_[2] = ps.total; band_stats_[3] = bands.ok ? 1 : 0;
+  }
+  // What a map-scope render of these poses stages (drf_render_async, and drf_track_frame for its model): the union of the stored
+  // blocks in reach, or depth bands of it, or DR_ERR_CAPACITY before anything changes.
+  void plan_render_call(const char *who, const float *const *poses, int n, RenderStagePlan &plan, RenderBandPlan &bands, bool &waited) {
+    plan = plan_render(poses, n, waited);
+    if (!render_stage_fits(plan, rs_capacity())) {
+      // depth bands (drf_set_render_bands): the union may exceed the staging as long as every band fits it
+      if (render_bands_ >= 2) bands = plan_render_bands(store_, o_, poses, n, rs_capacity(), render_bands_);
+      if (!bands.ok)
+        fail(DR_ERR_CAPACITY, "%s: the poses can read %zu stored blocks, the render staging holds %zu (drf_set_render_scope%s)", who, plan.keys.size(), rs_capacity(),
+             render_bands_ >= 2 ? "; no plan of depth bands within drf_set_render_bands either" : "");
+    }
+#ifdef DR_PARITY_HOOKS
+    if (!plan.keys.empty() && (raycast_v1_ || raycast_stats_ || raycast_sampler_ == 0))
+      fail(DR_ERR_UNSUPPORTED, "%s: the superseded ray-cast generations have no staged form (DRF_RENDER_MAP with stored blocks in reach)", who);
+#endif
+  }
+  // The planned render on the n streams of rs, pose i on rs[i]; handoff: the result goes to the host behind the last pass
+  // (drf_render_async), otherwise it stays in rs[i]'s device buffers (drf_track_frame's model).
+  struct PassStats { size_t passes, largest, total; bool staged; };
+  PassStats render_passes(const RenderStagePlan &plan, const RenderBandPlan &bands, Render *rs, const float *const *poses, int n, bool handoff) {
     const bool staged = !plan.keys.empty();  // nothing to stage: exactly the resident launches
     // One pass stages the union; a banded render one depth band after the other.  The two slots of rs_ alternate, so band j + 1 is
     // packed and copied while band j ray-casts; all render streams take a band together and share its staging.
@@ -952,17 +967,15 @@ class FusionEngine {
       band.first = j == 0;
       for (int i = 0; i < n; ++i) {
         Mat P; memcpy(P.m, poses[i], 64);
-        submit_render(renders_[i], P, staged ? &sg : nullptr, nullptr, bands.ok ? &band : nullptr, j + 1 == passes);
+        submit_render(rs[i], P, staged ? &sg : nullptr, nullptr, bands.ok ? &band : nullptr, handoff && j + 1 == passes);
       }
       if (staged) {  // behind every ray-cast that read the slot: its flags go back to zero
-        for (auto &r : renders_) rs_.wait_for(r.cast);
+        for (int i = 0; i < n; ++i) rs_.wait_for(rs[i].cast);
         hipLaunchKernelGGL(k_rs_clear, dim3(cdiv(sg.n, 256)), dim3(256), 0, rs_.stream(), sg.keys, sg.n, rs_super_[rs_.slot()][0], rs_super_[rs_.slot()][1]);
         DR_HIP(hipGetLastError());  // (per band: the launches of its ray-casts included)
       }
     }
-    render_stats_[0] = plan.keys.size(); render_stats_[1] = total * (size_t)(8 + 4096);
-    render_stats_[2] = (uint64_t)plan.whole; render_stats_[3] = waited ? 1 : 0;
-    band_stats_[0] = staged ? passes : 0; band_stats_[1] = largest; band_stats_[2] = total; band_stats_[3] = bands.ok ? 1 : 0;
+    return PassStats{passes, largest, total, staged};
   }
   // Depth bands of map-scope renders: max_passes 0 or 1 = off (the default), 2..64 = a RenderAsync whose union exceeds the
   // staging may run in up to that many bands.
@@ -1655,7 +1668,118 @@ class FusionEngine {
     for (int i = 0; i < 4; ++i) out[i] = ls_stats_[i];
   }
 
+  // A depth frame tracked against the ray-cast model (the rule: fusion_host.h track_normal / track_point / track_loop; DESIGN.md §7c
+  // "Tracking a depth frame against the ray-cast model").  with_track does what the calls share -- the refusals in their order,
+  // pending work settled, device scratch that is sized once: partial sums | 4 counters | the ray-cast's flag counter | model map |
+  // model depth | the frame -- and hands body an evaluator: k_track + k_align_fold on int_stream_.  The model's render goes through
+  // the engine's one submit (render_passes) on int_stream_ into that scratch: depth into `model depth`; the colour image and, in a
+  // banded render, the per-pixel ray state, which nobody reads afterwards, into the bytes k_track_model then overwrites with the
+  // model map.  renders_, free_slot_, next_ and the render statistics are not touched.
+  struct TrackBufs { double *partial; unsigned long long *counts; int *flag; TrackPixel *map; float *model, *frame; const float *depth; };
+  template <class Body>
+  void with_track(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const float *model_pose16, const drf_track_options_t *opt,
+                  Body &&body) {
+    track_reset();
+    TrackOpt to;
+    if (const char *bad = track_options(opt, o_.voxel_size, to)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
+    expect_integrate(who);
+    if (st_radius_ <= 0.0f && !store_.empty())
+      fail(DR_ERR_PROTOCOL, "%s: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", who, store_.size());
+    if (const char *why = transform_pose_fault(pose16)) fail(DR_ERR_ARG, "%s: the pose %s", who, why);
+    if (model_pose16)
+      if (const char *why = transform_pose_fault(model_pose16)) fail(DR_ERR_ARG, "%s: the model pose %s", who, why);
+    settle();  // behind any pending scan; the pinned buffers are idle and every eviction is in the host store
+    const LocateGrid lg = locate_grid(o_, to.step);
+    const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
+    const size_t max_groups = (npix_ + 511) / 512;  // step = 1
+    const size_t head = max_groups * 224 + 32 + 32;  // a multiple of 32: the model map is 16-byte aligned
+    tk_buf_.reserve(head + npix_ * 24, int_stream_);
+    mio_.ensure(1);
+    TrackBufs b;
+    b.partial = (double *)tk_buf_.get();
+    b.counts = (unsigned long long *)(b.partial + max_groups * 28);
+    b.flag = (int *)(b.counts + 4);
+    b.map = (TrackPixel *)(tk_buf_.get() + head);
+    b.model = (float *)(b.map + npix_);
+    b.frame = b.model + npix_;
+    b.depth = (const float *)d_depth;
+    if (h_depth) {
+      memcpy(h_depth_in_, h_depth, npix_ * 4);
+      DR_HIP(hipMemcpyAsync(b.frame, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
+      b.depth = b.frame;
+    }
+    tk_stats_[0] = (uint64_t)total; tk_stats_[5] = tk_buf_.capacity();
+    auto eval = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t c4[4]) {
+      const TrackModel tm = track_model(mp16, to, o_.voxel_size, b.map);
+      mio_.evaluate(b.partial, groups, b.counts, 4, sums, c4, [&] {
+        hipLaunchKernelGGL(k_track, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, b.depth, lg, e, tm, groups, total, b.partial, b.counts);
+        DR_HIP(hipGetLastError());
+      });
+      tk_stats_[1] = c4[0]; tk_stats_[2] = c4[1]; ++tk_stats_[3];
+    };
+    try {
+      body(to, lg, b, eval);
+    } catch (...) {
+      track_reset();
+      throw;
+    }
+  }
+  void track_system(const char *who, const float *h_depth, const float *h_model, const void *d_depth, const void *d_model, const float *model_pose16,
+                    const float *pose16, const drf_track_options_t *opt, double *sums, uint64_t *counts) {
+    track_reset();
+    if (!(h_depth || d_depth) || !(h_model || d_model) || !model_pose16 || !pose16 || !sums || !counts) fail(DR_ERR_ARG, "%s: null argument", who);
+    with_track(who, h_depth, d_depth, pose16, model_pose16, opt, [&](const TrackOpt &to, const LocateGrid &lg, const TrackBufs &b, auto &eval) {
+      const float *model = (const float *)d_model;
+      if (h_model) {
+        DR_HIP(hipStreamSynchronize(int_stream_));  // the frame has left the pinned buffer
+        memcpy(h_depth_in_, h_model, npix_ * 4);
+        DR_HIP(hipMemcpyAsync(b.model, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
+        model = b.model;
+      }
+      hipLaunchKernelGGL(k_track_model, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, model, lg, to.max_jump, b.map);
+      DR_HIP(hipGetLastError());
+      double c_src[3];
+      locate_centre_src(to.centre_depth, o_.voxel_size, c_src);
+      eval(align_eval(map_motion(pose16, o_.voxel_size), c_src, to.a, o_.voxel_size), model_pose16, sums, counts);
+    });
+  }
+  // returns what dr_last_error() says after a tracking that ran but found no pose (empty otherwise)
+  std::string track_frame(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_track_options_t *opt, float *pose16_out,
+                          drf_align_result_t *res) {
+    track_reset();
+    if (!(h_depth || d_depth) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+    drf_align_result_t r;
+    uint64_t c4[4] = {0, 0, 0, 0};
+    with_track(who, h_depth, d_depth, pose16, nullptr, opt, [&](const TrackOpt &to, const LocateGrid &lg, const TrackBufs &b, auto &eval) {
+      if (!track_render_.cast) { track_render_.cast = own_.event(); track_render_.done = own_.event(); }
+      track_render_.stream = int_stream_;
+      track_render_.d_bgr = (unsigned char *)b.map;
+      track_render_.d_band = (RayState *)((unsigned char *)b.map + npix_ * 8);
+      track_render_.d_depth = b.model;
+      track_render_.d_flag = b.flag;
+      auto render = [&](const float *p16) {
+        RenderStagePlan plan;
+        RenderBandPlan bands;
+        bool waited = false;
+        const float *poses[1] = {p16};
+        if (render_scope_ == DRF_RENDER_MAP) plan_render_call(who, poses, 1, plan, bands, waited);
+        render_passes(plan, bands, &track_render_, poses, 1, false);
+        hipLaunchKernelGGL(k_track_model, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, (const float *)b.model, lg, to.max_jump, b.map);
+        DR_HIP(hipGetLastError());
+        ++tk_stats_[4];
+      };
+      track_loop(render, eval, pose16, to, o_.voxel_size, r, c4);
+    });
+    for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
+    if (res) *res = r;
+    return no_pose_note(std::string(who) + ": the tracking", r,
+                        ", " + std::to_string((unsigned long long)c4[2]) + " unassociated, " + std::to_string((unsigned long long)c4[3]) + " rejected; " +
+                            std::to_string((unsigned long long)tk_stats_[4]) + " renders; " + std::to_string(store_.size()) + " blocks are in the host store)");
+  }
+  void track_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = tk_stats_[i]; }
+
  private:
+  void track_reset() { for (auto &v : tk_stats_) v = 0; }
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
   size_t host_free() const { return st_host_cap_ - std::min(st_host_cap_, store_.size()); }
@@ -2248,6 +2372,9 @@ class FusionEngine {
   uint64_t mg_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_merge_stats
   DeviceBuf<unsigned char> lc_buf_;            // drf_locate_*: partial sums, counters and a host-given depth image (sized once)
   uint64_t lc_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_locate_stats
+  DeviceBuf<unsigned char> tk_buf_;            // drf_track_*: partial sums, counters, model map, model depth and a host-given frame (sized once)
+  uint64_t tk_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_track_stats
+  Render track_render_{};                      // drf_track_frame's model render: int_stream_ and pointers into tk_buf_
   int locate_scope_ = DRF_LOCATE_RESIDENT;     // drf_set_locate_scope
   size_t lc_cap_req_ = 0;
   uint64_t ls_stats_[4] = {0, 0, 0, 0};        // drf_locate_stage_stats
@@ -2467,6 +2594,31 @@ int drf_locate_frame_device(drf_t *h, const void *d_depth, const float pose_init
 }
 int drf_locate_stats(drf_t *h, uint64_t out[6]) {
   return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_locate_stats: null argument"); eng(h)->locate_stats(out); });
+}
+int drf_track_system(drf_t *h, const float *depth, const float *model_depth, const float model_pose16[16], const float pose16[16], const drf_track_options_t *opt,
+                     double sums[28], uint64_t counts[4]) {
+  return guarded([&] { eng(h)->track_system("drf_track_system", depth, model_depth, nullptr, nullptr, model_pose16, pose16, opt, sums, counts); });
+}
+int drf_track_system_device(drf_t *h, const void *d_depth, const void *d_model_depth, const float model_pose16[16], const float pose16[16],
+                            const drf_track_options_t *opt, double sums[28], uint64_t counts[4]) {
+  return guarded([&] { eng(h)->track_system("drf_track_system_device", nullptr, nullptr, d_depth, d_model_depth, model_pose16, pose16, opt, sums, counts); });
+}
+static int track_frame_call(drf_t *h, const char *who, const float *depth, const void *d_depth, const float *pose_init16, const drf_track_options_t *opt,
+                            float *pose16_out, drf_align_result_t *res) {
+  std::string note;
+  const int rc = guarded([&] { note = eng(h)->track_frame(who, depth, d_depth, pose_init16, opt, pose16_out, res); });
+  if (rc == DR_OK && !note.empty()) dr::last_error_slot() = note;
+  return rc;
+}
+int drf_track_frame(drf_t *h, const float *depth, const float pose_init16[16], const drf_track_options_t *opt, float pose16_out[16], drf_align_result_t *res) {
+  return track_frame_call(h, "drf_track_frame", depth, nullptr, pose_init16, opt, pose16_out, res);
+}
+int drf_track_frame_device(drf_t *h, const void *d_depth, const float pose_init16[16], const drf_track_options_t *opt, float pose16_out[16],
+                           drf_align_result_t *res) {
+  return track_frame_call(h, "drf_track_frame_device", nullptr, d_depth, pose_init16, opt, pose16_out, res);
+}
+int drf_track_stats(drf_t *h, uint64_t out[6]) {
+  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_track_stats: null argument"); eng(h)->track_stats(out); });
 }
 int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_locate_scope(scope, stage_capacity_blocks); }); }
 int drf_locate_stage_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->locate_stage_stats(out); }); }

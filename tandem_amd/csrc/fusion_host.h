@@ -821,6 +821,23 @@ DR_HOST_DEVICE inline bool align_is_sample(const uint32_t v[2], const AlignEval 
   memcpy(&s, &v[0], 4);
   return (int)(v[1] >> 24) >= e.min_weight && (s < 0.0f ? -s : s) <= e.band;
 }
+// The terms of one valid sample at q with residual r and gradient n (both in voxels): J = ((q - c) x n, n), Huber's weight, the 28
+// sums.  What align_point and track_point (below) end in: the same operations in the same order for all three callers.
+DR_HOST_DEVICE inline void align_accumulate(const AlignEval &e, double r, double n0, double n1, double n2, const double q[3], double acc[28]) {
+  const double x0 = q[0] - e.c[0], x1 = q[1] - e.c[1], x2 = q[2] - e.c[2];
+  const double J[6] = {x1 * n2 - x2 * n1, x2 * n0 - x0 * n2, x0 * n1 - x1 * n0, n0, n1, n2};
+  const double a = r < 0.0 ? -r : r;
+  const double w = a <= e.huber ? 1.0 : e.huber / a;
+  int idx = 0;
+  DR_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    const double wj = w * J[i];
+    DR_UNROLL
+    for (int j = i; j < 6; ++j) { acc[idx] = acc[idx] + wj * J[j]; ++idx; }
+    acc[21 + i] = acc[21 + i] + wj * r;
+  }
+  acc[27] = acc[27] + (w * r) * r;
+}
 // One sample at the point g (lattice units of the moving frame, three doubles) with sdf s_src: the body that the registration
 // (align_voxel: g a source lattice point) and the localisation (locate_group: g a depth pixel's point, s_src = 0) share.  Reads the
 // eight reference voxels through fetch(x, y, z, v[2]) (an absent block: weight 0); returns 0 if one of them is not observed (or q
@@ -872,19 +889,7 @@ DR_HOST_DEVICE inline int align_point(const AlignEval &e, double g0, double g1, 
   }
   const double r = ((double)phi - (double)s_src) / e.vs;
   const double n0 = (double)gxf / e.vs, n1 = (double)gyf / e.vs, n2 = (double)gzf / e.vs;
-  const double x0 = q[0] - e.c[0], x1 = q[1] - e.c[1], x2 = q[2] - e.c[2];
-  const double J[6] = {x1 * n2 - x2 * n1, x2 * n0 - x0 * n2, x0 * n1 - x1 * n0, n0, n1, n2};
-  const double a = r < 0.0 ? -r : r;
-  const double w = a <= e.huber ? 1.0 : e.huber / a;
-  int idx = 0;
-  DR_UNROLL
-  for (int i = 0; i < 6; ++i) {
-    const double wj = w * J[i];
-    DR_UNROLL
-    for (int j = i; j < 6; ++j) { acc[idx] = acc[idx] + wj * J[j]; ++idx; }
-    acc[21 + i] = acc[21 + i] + wj * r;
-  }
-  acc[27] = acc[27] + (w * r) * r;
+  align_accumulate(e, r, n0, n1, n2, q, acc);
   return 1;
 }
 // One sample of the registration: the source voxel at lattice point (gx, gy, gz) with sdf s_src; true if it was valid.
@@ -1161,6 +1166,201 @@ inline void locate_frame_host(const LocateGrid &lg, const float *depth, Fetch &&
                               drf_align_result_t &res, std::vector<std::array<double, 28>> *trace = nullptr) {
   locate_loop([&](const AlignEval &e, double sums[28], uint64_t c4[4]) { locate_system_host(lg, depth, fetch, e, sums, c4); }, m0, o, voxel_size, res,
               nullptr, trace);
+}
+
+// ---- tracking a depth frame against the ray-cast model (drf_track_system / drf_track_frame; DESIGN.md §7c "Tracking a depth frame
+// against the ray-cast model").  The frame's samples are drf_locate_*'s (locate_pixel, the same grid and test); each is associated
+// projectively with a pixel of the MODEL MAP -- per pixel of a depth image Dm ray-cast at the pose Pm its depth and the unit normal
+// of its back-projected neighbourhood -- and contributes the point-to-plane distance to that pixel's plane.  From the residual and
+// the normal on a sample is align_accumulate's, the step and the loop align_step's and align_loop's.  Stated once, here; the
+// header of the C ABI restates it for users.  Compiled by g++ and by hipcc (k_track_model, k_track), both without contraction;
+// + - * / sqrt and floor only.
+struct TrackOpt {  // drf_track_options_t with its defaults resolved; a.max_iters is inner_iters (a.band and a.min_weight are not read)
+  AlignOpt a;
+  int max_renders, step;
+  float centre_depth, dist_max, max_jump;
+};
+// null: all defaults.  Returns null, or which option is negative or not finite
+inline const char *track_options(const drf_track_options_t *opt, float voxel_size, TrackOpt &o) {
+  static const drf_track_options_t zero = {0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0, 0.0, 0.0};
+  const drf_track_options_t &u = opt ? *opt : zero;
+  if (u.max_renders < 0) return "max_renders";
+  if (u.inner_iters < 0) return "inner_iters";
+  if (u.step < 0) return "step";
+  if (!(u.dist_max >= 0.0f) || !std::isfinite(u.dist_max)) return "dist_max";
+  if (!(u.max_jump >= 0.0f) || !std::isfinite(u.max_jump)) return "max_jump";
+  if (!(u.centre_depth >= 0.0f) || !std::isfinite(u.centre_depth)) return "centre_depth";
+  const drf_align_options_t a = {u.inner_iters, 0, 0.0f, u.huber, u.eps_rot, u.eps_trans, u.min_valid};
+  if (const char *bad = align_options(&a, 1.0f, o.a)) return bad;
+  o.a.max_iters = u.inner_iters ? u.inner_iters : 4;
+  o.max_renders = u.max_renders ? u.max_renders : 10;
+  o.step = u.step ? u.step : 1;
+  o.dist_max = u.dist_max != 0.0f ? u.dist_max : 25.0f * voxel_size;
+  o.max_jump = u.max_jump != 0.0f ? u.max_jump : 5.0f * voxel_size;
+  o.centre_depth = u.centre_depth;
+  return nullptr;
+}
+// one pixel of the model map: the unit normal in the model camera's frame, towards the camera, and the depth; z = 0 is invalid
+struct alignas(16) TrackPixel { float nx, ny, nz, z; };
+// The model map's pixel (u, v) from the model depth image Dm (lg: the camera; its step is not read), all in fp32.  A MISS of the
+// ray-cast is the 0.0f that k_raycast2 / k_raycast_fix write for a ray that found no surface; the test is !(z > 0), which a NaN
+// and a negative depth fail too.  Invalid (all four floats 0): the centre is a miss; the pixel lies on the image border; one of its
+// four neighbours (u -+ 1, v), (u, v -+ 1) is a miss; |z_neighbour - z| > max_jump for one of them.  Otherwise, with
+// X(u, v, z) = ((((float)u - cx) / fx) * z, (((float)v - cy) / fy) * z, z): a = X(u + 1, v) - X(u - 1, v), b = X(u, v + 1) -
+// X(u, v - 1), n = a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0), l2 = (n0 n0 + n1 n1) + n2 n2; !(l2 > 0) is invalid;
+// n = n / sqrt(l2); and with s = (n0 X0 + n1 X1) + n2 X2 at the centre, s > 0 negates n: the normal looks at the camera.
+DR_HOST_DEVICE inline TrackPixel track_normal(const LocateGrid &lg, float max_jump, const float *Dm, int u, int v) {
+  TrackPixel p = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (u <= 0 || v <= 0 || u >= lg.W - 1 || v >= lg.H - 1) return p;
+  const size_t at = (size_t)v * (size_t)lg.W + (size_t)u;
+  const float z = Dm[at], zl = Dm[at - 1], zr = Dm[at + 1], zu = Dm[at - (size_t)lg.W], zd = Dm[at + (size_t)lg.W];
+  if (!(z > 0.0f) || !(zl > 0.0f) || !(zr > 0.0f) || !(zu > 0.0f) || !(zd > 0.0f)) return p;
+  const float jl = zl - z, jr = zr - z, ju = zu - z, jd = zd - z;
+  if ((jl < 0.0f ? -jl : jl) > max_jump || (jr < 0.0f ? -jr : jr) > max_jump || (ju < 0.0f ? -ju : ju) > max_jump || (jd < 0.0f ? -jd : jd) > max_jump) return p;
+  const float rx = ((float)u - lg.cx) / lg.fx, ry = ((float)v - lg.cy) / lg.fy;
+  const float rxl = ((float)(u - 1) - lg.cx) / lg.fx, rxr = ((float)(u + 1) - lg.cx) / lg.fx;
+  const float ryu = ((float)(v - 1) - lg.cy) / lg.fy, ryd = ((float)(v + 1) - lg.cy) / lg.fy;
+  const float a0 = rxr * zr - rxl * zl, a1 = ry * zr - ry * zl, a2 = zr - zl;
+  const float b0 = rx * zd - rx * zu, b1 = ryd * zd - ryu * zu, b2 = zd - zu;
+  float n0 = a1 * b2 - a2 * b1, n1 = a2 * b0 - a0 * b2, n2 = a0 * b1 - a1 * b0;
+  const float l2 = (n0 * n0 + n1 * n1) + n2 * n2;
+  if (!(l2 > 0.0f)) return p;
+  const float l = sqrtf(l2);
+  n0 = n0 / l; n1 = n1 / l; n2 = n2 / l;
+  const float s = (n0 * (rx * z) + n1 * (ry * z)) + n2 * z;
+  if (s > 0.0f) { n0 = -n0; n1 = -n1; n2 = -n2; }
+  p.nx = n0; p.ny = n1; p.nz = n2; p.z = z;
+  return p;
+}
+inline void track_model_host(const LocateGrid &lg, float max_jump, const float *Dm, TrackPixel *out) {
+  for (int v = 0; v < lg.H; ++v)
+    for (int u = 0; u < lg.W; ++u) out[(size_t)v * lg.W + u] = track_normal(lg, max_jump, Dm, u, v);
+}
+// the model of one evaluation: its pose Pm (camera-to-world, lattice units), (dist_max / voxel_size)^2, and the map
+struct TrackModel {
+  MapMotion m;
+  double lim2;
+  const TrackPixel *map;
+};
+inline TrackModel track_model(const float *model_pose16, const TrackOpt &o, float voxel_size, const TrackPixel *map) {
+  TrackModel t;
+  t.m = map_motion(model_pose16, voxel_size);
+  const double lim = (double)o.dist_max / (double)voxel_size;
+  t.lim2 = lim * lim;
+  t.map = map;
+  return t;
+}
+// One sample at the camera-frame point g (lattice units, locate_pixel's): q = Rd g + tv at the estimate; m = Rm^T (q - tvm), the
+// point in the model camera; !(m2 > 0) is UNASSOCIATED (behind the model camera, or a NaN); u' = fx (m0 / m2) + cx, v' likewise,
+// the pixel (floor(u' + 0.5), floor(v' + 0.5)); outside the image or an invalid model pixel is UNASSOCIATED (returns 0).  The model
+// vertex vm is that pixel's back-projection at its z, as locate_pixel computes a point; d = m - vm; a sample for which
+// |d|^2 <= lim2 is false is REJECTED (returns 2).  Otherwise r = (n0 d0 + n1 d1) + n2 d2 with the pixel's normal widened to
+// double, nw = Rm n, and align_accumulate adds the sample (returns 1).
+DR_HOST_DEVICE inline int track_point(const AlignEval &e, const TrackModel &t, const LocateGrid &lg, double g0, double g1, double g2, double acc[28]) {
+  double q[3], m[3];
+  DR_UNROLL
+  for (int k = 0; k < 3; ++k) q[k] = ((e.m.R[3 * k] * g0 + e.m.R[3 * k + 1] * g1) + e.m.R[3 * k + 2] * g2) + e.m.tv[k];
+  const double s0 = q[0] - t.m.tv[0], s1 = q[1] - t.m.tv[1], s2 = q[2] - t.m.tv[2];
+  DR_UNROLL
+  for (int k = 0; k < 3; ++k) m[k] = (t.m.R[k] * s0 + t.m.R[3 + k] * s1) + t.m.R[6 + k] * s2;
+  if (!(m[2] > 0.0)) return 0;
+  const double up = (double)lg.fx * (m[0] / m[2]) + (double)lg.cx, vp = (double)lg.fy * (m[1] / m[2]) + (double)lg.cy;
+  const double pu = floor(up + 0.5), pv = floor(vp + 0.5);
+  if (!(pu >= 0.0 && pu <= (double)(lg.W - 1) && pv >= 0.0 && pv <= (double)(lg.H - 1))) return 0;
+  const TrackPixel p = t.map[(size_t)(int)pv * (size_t)lg.W + (size_t)(int)pu];
+  if (!(p.z > 0.0f)) return 0;
+  const double z = (double)p.z;
+  const double d0 = m[0] - (((pu - (double)lg.cx) / (double)lg.fx) * z) / e.vs;
+  const double d1 = m[1] - (((pv - (double)lg.cy) / (double)lg.fy) * z) / e.vs;
+  const double d2 = m[2] - z / e.vs;
+  const double dd = (d0 * d0 + d1 * d1) + d2 * d2;
+  if (!(dd <= t.lim2)) return 2;
+  const double n0 = (double)p.nx, n1 = (double)p.ny, n2 = (double)p.nz;
+  const double r = (n0 * d0 + n1 * d1) + n2 * d2;
+  const double w0 = (t.m.R[0] * n0 + t.m.R[1] * n1) + t.m.R[2] * n2;
+  const double w1 = (t.m.R[3] * n0 + t.m.R[4] * n1) + t.m.R[5] * n2;
+  const double w2 = (t.m.R[6] * n0 + t.m.R[7] * n1) + t.m.R[8] * n2;
+  align_accumulate(e, r, w0, w1, w2, q, acc);
+  return 1;
+}
+// Group i in the wave's order (locate_group's); counts += {samples, valid, unassociated, rejected}.
+inline void track_group(const AlignEval &e, const TrackModel &t, const LocateGrid &lg, const float *depth, long i, double out[28], uint64_t counts[4]) {
+  double x[64][28];
+  const long total = locate_positions(lg);
+  for (int l = 0; l < 64; ++l) {
+    for (int c = 0; c < 28; ++c) x[l][c] = 0.0;
+    for (int k = 0; k < 8; ++k) {
+      const long n = 512 * i + l + 64 * k;
+      double g[3];
+      if (n >= total || !locate_pixel(lg, e.vs, (int)n, depth, g)) continue;
+      ++counts[0];
+      const int r = track_point(e, t, lg, g[0], g[1], g[2], x[l]);
+      ++counts[r == 1 ? 1 : r == 0 ? 2 : 3];
+    }
+  }
+  align_butterfly(x);
+  for (int c = 0; c < 28; ++c) out[c] = x[0][c];
+}
+// The system at one pose over the whole sample grid: track_group per group into partial[i], then k_align_fold's fold.
+inline void track_system_host(const LocateGrid &lg, const float *depth, const TrackModel &t, const AlignEval &e, double sums[28], uint64_t counts[4]) {
+  counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  const size_t n = (size_t)locate_groups(lg);
+  std::vector<double> partial(n * 28);
+  for (size_t i = 0; i < n; ++i) track_group(e, t, lg, depth, (long)i, &partial[i * 28], counts);
+  align_fold_host(partial.data(), n, sums);
+}
+// The outer loop of drf_track_frame over render(const float pose16[16]), which ray-casts the map at that pose and builds the model
+// map, and eval(const AlignEval &, const float model_pose16[16], double sums[28], uint64_t counts[4]), one evaluation against it.
+// Round r renders at p16 -- pose_init16, later the float pose16 the round before ended on (res.T rounded to float, what
+// drf_render_async would be given) -- and runs align_loop from that very pose, m = map_motion(p16), with max_iters = inner_iters
+// and {samples, valid, unassociated + rejected}.  A round that ends LOST or DEGENERATE ends the call with that status; one that
+// ends CONVERGED at its first evaluation ends it CONVERGED; any other round hands its pose on, and after max_renders rounds the
+// call is MAX_ITERS.  res: T, sums, samples, valid, cost of the last round; valid0, cost0 of the first; iterations = evaluations in
+// all.  stats2 = {evaluations, renders}; last4 the four counters of the last evaluation.
+template <class Render, class Eval>
+inline void track_loop(Render &&render, Eval &&eval, const float *pose_init16, const TrackOpt &o, float voxel_size, drf_align_result_t &res,
+                       uint64_t *last4 = nullptr, uint64_t *stats2 = nullptr, std::vector<std::array<double, 28>> *trace = nullptr) {
+  double c_src[3];
+  locate_centre_src(o.centre_depth, voxel_size, c_src);
+  float p16[16];
+  memcpy(p16, pose_init16, sizeof p16);
+  memset(&res, 0, sizeof res);
+  int evaluations = 0;
+  uint64_t valid0 = 0;
+  double cost0 = 0.0;
+  for (int r = 0; r < o.max_renders; ++r) {
+    render(p16);
+    if (stats2) ++stats2[1];
+    drf_align_result_t in;
+    align_loop([&](const AlignEval &e, double sums[28], uint64_t counts[3]) {
+      uint64_t c4[4];
+      eval(e, p16, sums, c4);
+      counts[0] = c4[0]; counts[1] = c4[1]; counts[2] = c4[2] + c4[3];
+      if (last4) memcpy(last4, c4, sizeof c4);
+      if (stats2) ++stats2[0];
+    }, map_motion(p16, voxel_size), c_src, o.a, voxel_size, in, trace);
+    evaluations += in.iterations;
+    if (r == 0) { valid0 = in.valid0; cost0 = in.cost0; }
+    res = in;
+    res.valid0 = valid0; res.cost0 = cost0; res.iterations = evaluations;
+    if (in.status == DRF_ALIGN_LOST || in.status == DRF_ALIGN_DEGENERATE) return;
+    if (in.status == DRF_ALIGN_CONVERGED && in.iterations == 1) return;
+    res.status = DRF_ALIGN_MAX_ITERS;
+    for (int i = 0; i < 16; ++i) p16[i] = (float)in.T[i];
+  }
+}
+// The whole tracking on the CPU over any renderer render_depth(const float pose16[16], float *Dm): the library's reference for
+// drf_track_frame, and what the sanitizer program runs.
+template <class RenderDepth>
+inline void track_frame_host(const LocateGrid &lg, const float *depth, RenderDepth &&render_depth, const float *pose_init16, const TrackOpt &o, float voxel_size,
+                             drf_align_result_t &res, uint64_t *last4 = nullptr, uint64_t *stats2 = nullptr, std::vector<std::array<double, 28>> *trace = nullptr) {
+  const size_t npix = (size_t)lg.W * (size_t)lg.H;
+  std::vector<float> Dm(npix);
+  std::vector<TrackPixel> map(npix);
+  track_loop([&](const float *p16) { render_depth(p16, Dm.data()); track_model_host(lg, o.max_jump, Dm.data(), map.data()); },
+             [&](const AlignEval &e, const float *p16, double sums[28], uint64_t c4[4]) {
+               track_system_host(lg, depth, track_model(p16, o, voxel_size, map.data()), e, sums, c4);
+             }, pose_init16, o, voxel_size, res, last4, stats2, trace);
 }
 
 }  // namespace dr

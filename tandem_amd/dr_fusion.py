@@ -392,7 +392,7 @@ class DrFusion:
     def locate_frame(self, depth, pose_init, raise_on_failure=True, **opt):
         """Refines pose_init (camera-to-world) so that the depth image lies on the surface of the map this engine holds and returns
         an AlignResult (T, T32: camera-to-world); T32 is the pose IntegrateScanAsync takes to continue the map.  The call refines:
-        pose_init must bring the points inside the truncation band.  Only resident blocks are read (locate_stats()[5] counts the
+        pose_init must bring the points inside the truncation band (from farther off, track_frame first).  Only resident blocks are read (locate_stats()[5] counts the
         blocks in the host store) unless set_locate_scope(LOCATE_MAP) was called.  A refinement that ends ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the
         result) unless raise_on_failure is false."""
         dev, d, keep = self._locate_depth(depth)
@@ -427,6 +427,57 @@ class DrFusion:
         that read a staging); all 0 in resident scope or with nothing to stage."""
         out = (C.c_uint64 * 4)()
         check(self._L.drf_locate_stage_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    # ---- tracking a depth frame against the ray-cast model (include/dr_mi355x.h drf_track_frame, DESIGN.md "Tracking a depth frame") ----
+    @staticmethod
+    def _track_options(opt):
+        if not opt:
+            return None
+        unknown = set(opt) - {f[0] for f in _lib.TrackOptions._fields_}
+        if unknown:
+            raise TypeError("unknown track option(s): %s" % ", ".join(sorted(unknown)))
+        return _lib.TrackOptions(**opt)
+
+    def track_system(self, depth, model_depth, model_pose, pose, **opt):
+        """One evaluation of the tracking's Gauss-Newton system: the depth image at the pose against model_depth, a ray-cast at
+        model_pose (both images H*W float32 metres, or both integer device pointers): (sums (28,) float64, (samples, valid,
+        unassociated, rejected)).  opt: the fields of drf_track_options_t.  No map is read."""
+        dev, d, keep = self._locate_depth(depth)
+        mdev, m, mkeep = self._locate_depth(model_depth)
+        assert dev == mdev, "both images on the host or both on the device"
+        pose = np.ascontiguousarray(pose, np.float32).reshape(16)
+        mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
+        o = self._track_options(opt)
+        sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 4)()
+        call = self._L.drf_track_system_device if dev else self._L.drf_track_system
+        check(call(self._h, d, m, fptr(mpose), fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
+        return sums, tuple(int(v) for v in counts)
+
+    def track_frame(self, depth, pose_init, raise_on_failure=True, **opt):
+        """Tracks the depth image against the ray-cast model of the map this engine holds from pose_init (camera-to-world), which
+        need only be good to decimetres and some ten degrees, and returns an AlignResult (T, T32: camera-to-world).  It ends within
+        locate_frame's reach: track first, then locate_frame(depth, result.T32) for the sub-voxel part.  The renders follow
+        set_render_scope and set_render_bands; the public render buffers and the map are not touched.  ALIGN_MAX_ITERS is a usable
+        pose; ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the result) unless raise_on_failure is false."""
+        dev, d, keep = self._locate_depth(depth)
+        pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
+        o = self._track_options(opt)
+        T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
+        call = self._L.drf_track_frame_device if dev else self._L.drf_track_frame
+        check(call(self._h, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
+        res = AlignResult(T=np.array(r.T, np.float64).reshape(4, 4), T32=T32.reshape(4, 4), sums=np.array(r.sums, np.float64), samples=int(r.samples),
+                          valid0=int(r.valid0), valid=int(r.valid), cost0=float(r.cost0), cost=float(r.cost), iterations=int(r.iterations),
+                          status=int(r.status))
+        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
+            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
+        return res
+
+    def track_stats(self):
+        """Last track_system / track_frame: (grid positions, samples, valid samples at the last evaluation, system evaluations,
+        renders, device bytes held)."""
+        out = (C.c_uint64 * 6)()
+        check(self._L.drf_track_stats(self._h, out))
         return tuple(int(v) for v in out)
 
     def set_render_scope(self, scope, stage_capacity_blocks=0):

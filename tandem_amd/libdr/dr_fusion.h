@@ -115,12 +115,21 @@ public:
   }
   // a depth frame (height x width floats, metres) located in the map this object holds, from the rough camera-to-world pose
   // pose_init16: pose16_out is the pose IntegrateScanAsync takes to continue the map (dr_mi355x.h drf_locate_frame; it refines,
-  // pose_init16 must bring the points inside the truncation band).  Returns the status, DRF_ALIGN_*: a frame that finds no pose
+  // pose_init16 must bring the points inside the truncation band; from farther off TrackDepthFrame goes first).  Returns the status, DRF_ALIGN_*: a frame that finds no pose
   // (DRF_ALIGN_DEGENERATE, DRF_ALIGN_LOST: pose16_out is then no better than pose_init16, dr_last_error() says why) is an answer a
   // tracker acts on, not a violation.
   int LocateDepthFrame(float const *depth, float const *pose_init16, float *pose16_out) {
     drf_align_result_t res;
     check(drf_locate_frame(impl, depth, pose_init16, nullptr, pose16_out, &res));
+    return res.status;
+  }
+  // a depth frame tracked against the ray-cast model of the map this object holds, from a pose that is only good to decimetres and
+  // degrees (dr_mi355x.h drf_track_frame: projective association, point-to-plane; opt null = its defaults).  It ends within
+  // LocateDepthFrame's reach: track first, then locate from pose16_out.  Returns the status, DRF_ALIGN_*; DRF_ALIGN_MAX_ITERS is a
+  // usable pose too.
+  int TrackDepthFrame(float const *depth, float const *pose_init16, float *pose16_out, drf_track_options_t const *opt = nullptr) {
+    drf_align_result_t res;
+    check(drf_track_frame(impl, depth, pose_init16, opt, pose16_out, &res));
     return res.status;
   }
   // DRF_LOCATE_MAP: LocateDepthFrame reads resident and host-stored blocks together, without moving one (capacity 0 = the default
