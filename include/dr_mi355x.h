@@ -652,8 +652,9 @@ int drf_locate_stage_stats(drf_t *h, uint64_t out[4]);
  * drf_locate_frame needs a start inside the truncation band (a few centimetres), this call's basin is set by the association:
  * decimetres and some ten degrees.  It ends close enough for drf_locate_frame to do the sub-voxel part -- the ray-cast stops up to
  * one voxel in front of the surface, so this call alone is good to about a voxel.  From a rough pose: drf_track_frame, then
- * drf_locate_frame from the pose it returns.  Out of scope: a global search, colour / photometric terms, a test that compares
- * the frame's own normals with the model's, and an image pyramid.
+ * drf_locate_frame from the pose it returns.  Out of scope: a global search, a test that compares
+ * the frame's own normals with the model's, and an image pyramid.  With the frame's colour image at hand call
+ * drf_track_colour_frame, below: its photometric term holds the motion inside a plane, which this call leaves open.
  * drf_track_frame renders the map at the current estimate into buffers of its own -- the engine's ray-cast, under
  * drf_set_render_scope and drf_set_render_bands as drf_render_async plans it (DRF_RENDER_MAP reads the host store too, and a
  * selection above the staging is DR_ERR_CAPACITY in the same way) -- builds the model map, runs a few evaluations against it and
@@ -725,6 +726,56 @@ int drf_track_frame_device(drf_t *h, const void *d_depth, const float pose_init1
 /* last drf_track_*: [0] grid positions, [1] samples, [2] valid samples at the last evaluation, [3] system evaluations, [4] renders,
  * [5] device bytes held (all 0 after a call that was refused) */
 int drf_track_stats(drf_t *h, uint64_t out[6]);
+/* Tracks a depth frame AND its colour image against the ray-cast model (DESIGN.md §7c "Tracking with colour").  drf_track_frame
+ * sees geometry only: on a map of planes -- most indoor maps -- the motion inside the planes is open, and on one plane the call is
+ * DRF_ALIGN_DEGENERATE.  Every voxel carries a colour and the ray-cast renders it, so these calls add, for every sample whose
+ * geometric term was added, a photometric term: the model's colour image, interpolated where the sample projects, against the
+ * frame's own pixel.  bgr is the frame's colour image as drf_integrate_scan_async takes it (height x width x 3 bytes, B G R),
+ * model_bgr the ray-cast's at model_pose16.  Everything that drf_track_* say above about the render, its scope and bands, the
+ * stream, the map left unchanged, the legality and the refusals (in that order, the colour images among the null checks) holds
+ * here.  Out of scope: an affine brightness or exposure model (frame and map are taken to share their exposure), an image
+ * pyramid, a global search, and photometric terms in drf_locate_*.
+ * The rule (the same text of fusion_host.h; double and fp32 without contraction; + - * / sqrt floor):
+ *   intensity   a BGR pixel is y = ((float)b + (float)g) + (float)r, a whole number in 0..765.
+ *   Ym          the model intensity map, one float per pixel of the model colour image Cm: Ym(u, v) = the pixel's y where the model
+ *               map's pixel is valid (its z > 0), -1.0f elsewhere: misses, the border and depth discontinuities carry no colour.
+ *   sample, association, geometric term: drf_track_*'s, unchanged, and added FIRST.  The photometric term is attempted only for a
+ *               sample whose geometric term was added, so the dist_max test is its occlusion test.
+ *   photometric term  in double, from the m, u', v' of the association.  u0 = floor(u'), v0 = floor(v'), a = u' - u0, b = v' - v0.
+ *               The term is SKIPPED unless 0 <= u0, u0 + 1 <= width - 1, 0 <= v0, v0 + 1 <= height - 1 and y00 = Ym(u0, v0),
+ *               y10 = Ym(u0 + 1, v0), y01 = Ym(u0, v0 + 1), y11 = Ym(u0 + 1, v0 + 1) (each widened to double) are all >= 0.
+ *               oa = 1 - a, ob = 1 - b;
+ *               I  = ob * (oa * y00 + a * y10) + b * (oa * y01 + a * y11);
+ *               Iu = ob * (y10 - y00) + b * (y11 - y01), Iv = oa * (y01 - y00) + a * (y11 - y10): the exact gradient of I;
+ *               gm0 = (Iu * (double)fx) / m2, gm1 = (Iv * (double)fy) / m2, gm2 = -((gm0 * m0 + gm1 * m1) / m2);
+ *               lambda = (double)photo_weight, yf = the intensity of the frame's pixel at the sample's own (u, v):
+ *               r = lambda * (I - (double)yf), n_k = lambda * ((Rm[k][0] gm0 + Rm[k][1] gm1) + Rm[k][2] gm2).
+ *               From (r, n) on the term is a sample of drf_align_map's like the geometric one: J = ((q - c) cross n, n), Huber's
+ *               weight on |r| (in voxels after the scaling), the same 28 sums, the geometric term's additions before it.
+ *   counts      {samples, valid, unassociated, rejected, photometric terms added}; the loop is given {samples, valid,
+ *               unassociated + rejected}.  res->cost = sums[27] / valid carries BOTH terms.
+ *   order, step, loop, statuses, outer loop: drf_track_*'s. */
+typedef struct {
+  drf_track_options_t track;
+  float photo_weight;   /* voxels per intensity unit; 0 -> (float)(1.0 / 27.0) * huber (fp32, huber resolved first): 27 units of the
+                           three-channel sum, 9 grey levels of 255, weigh what a geometric residual at Huber's threshold weighs */
+} drf_track_colour_options_t;
+/* one evaluation at pose16 against the model colour and depth ray-cast at model_pose16: sums[28], counts[5] as above */
+int drf_track_colour_system(drf_t *h, const uint8_t *bgr, const float *depth, const uint8_t *model_bgr, const float *model_depth,
+                            const float model_pose16[16], const float pose16[16], const drf_track_colour_options_t *opt, double sums[28], uint64_t counts[5]);
+/* the tracking from pose_init16; pose16_out = res->T rounded to float */
+int drf_track_colour_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float pose_init16[16], const drf_track_colour_options_t *opt,
+                           float pose16_out[16], drf_align_result_t *res);
+/* the same with the images in device memory */
+int drf_track_colour_system_device(drf_t *h, const void *d_bgr, const void *d_depth, const void *d_model_bgr, const void *d_model_depth,
+                                   const float model_pose16[16], const float pose16[16], const drf_track_colour_options_t *opt, double sums[28],
+                                   uint64_t counts[5]);
+int drf_track_colour_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float pose_init16[16], const drf_track_colour_options_t *opt,
+                                  float pose16_out[16], drf_align_result_t *res);
+/* last drf_track_colour_*: drf_track_stats' fields.  [5]: a buffer of these calls' own, sized once per engine at the first of them
+ * (the partial sums, 64 bytes of counters, 16 W H model map, 4 W H model depth, 3 W H model colour, 4 W H Ym, 4 W H + 3 W H for a
+ * frame given by host pointer); drf_track_stats()[5] does not change. */
+int drf_track_colour_stats(drf_t *h, uint64_t out[6]);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

@@ -153,6 +153,11 @@ SIGNATURES = {
     "drf_track_system_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
     "drf_track_frame_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
     "drf_track_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_track_colour_system": (C.c_int, [vp, C.c_void_p, f32p, C.c_void_p, f32p, f32p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_track_colour_frame": (C.c_int, [vp, C.c_void_p, f32p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_track_colour_system_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_track_colour_frame_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_track_colour_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
 
 
@@ -172,6 +177,11 @@ class TrackOptions(C.Structure):
     """drf_track_options_t: a zero field means its default."""
     _fields_ = [("max_renders", C.c_int), ("inner_iters", C.c_int), ("step", C.c_int), ("dist_max", C.c_float), ("max_jump", C.c_float),
                 ("huber", C.c_float), ("centre_depth", C.c_float), ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("min_valid", C.c_double)]
+
+
+class TrackColourOptions(C.Structure):
+    """drf_track_colour_options_t: a zero field means its default."""
+    _fields_ = [("track", TrackOptions), ("photo_weight", C.c_float)]
 
 
 class AlignResultStruct(C.Structure):

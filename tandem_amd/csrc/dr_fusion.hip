@@ -674,6 +674,7 @@ __global__ void k_fill_keys(unsigned long long *keys, size_t n) {
 #include "align_kernels.h"  // k_map_align / k_align_fold (drf_align_system, drf_align_map)
 #include "locate_kernels.h"  // k_map_locate (drf_locate_system, drf_locate_frame)
 #include "track_kernels.h"   // k_track_model, k_track (drf_track_system, drf_track_frame)
+#include "track_colour_kernels.h"  // k_track_model_colour, k_track_colour (drf_track_colour_system, drf_track_colour_frame)
 
 }  // namespace dr
 #include "mesh_kernels.h"
@@ -1778,8 +1779,141 @@ class FusionEngine {
   }
   void track_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = tk_stats_[i]; }
 
+  // The same with the photometric term (the rule: fusion_host.h track_photo_term / track_colour_point; DESIGN.md §7c "Tracking with
+  // colour").  with_track_colour is with_track for these calls: the same refusals in the same order, a scratch of its own that is
+  // sized once -- partial sums | 5 counters and the ray-cast's flag counter (64 bytes) | model map | model depth | Ym | the frame's
+  // depth | model colour | the frame's colour -- so that tk_buf_ and drf_track_stats stay what they were.  The render's colour image
+  // is read by k_track_model_colour and has bytes of its own; the banded render's ray state, which nobody reads afterwards, still
+  // goes where the model map is then written.  k_align_fold hands back four counters; the fifth leaves through a pinned word.
+  struct TrackColourBufs { double *partial; unsigned long long *counts; int *flag; TrackPixel *map; float *model, *Ym, *frame; unsigned char *model_bgr, *frame_bgr;
+                           const float *depth; const unsigned char *bgr; };
+  template <class Body>
+  void with_track_colour(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
+                         const float *model_pose16, const drf_track_colour_options_t *opt, Body &&body) {
+    track_colour_reset();
+    TrackColourOpt to;
+    if (const char *bad = track_colour_options(opt, o_.voxel_size, to)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
+    expect_integrate(who);
+    if (st_radius_ <= 0.0f && !store_.empty())
+      fail(DR_ERR_PROTOCOL, "%s: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", who, store_.size());
+    if (const char *why = transform_pose_fault(pose16)) fail(DR_ERR_ARG, "%s: the pose %s", who, why);
+    if (model_pose16)
+      if (const char *why = transform_pose_fault(model_pose16)) fail(DR_ERR_ARG, "%s: the model pose %s", who, why);
+    settle();  // behind any pending scan; the pinned buffers are idle and every eviction is in the host store
+    const LocateGrid lg = locate_grid(o_, to.t.step);
+    const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
+    const size_t max_groups = (npix_ + 511) / 512;  // step = 1
+    const size_t head = max_groups * 224 + 64;      // a multiple of 32: the model map is 16-byte aligned
+    tc_buf_.reserve(head + npix_ * 34, int_stream_);
+    if (!tc_fifth_) tc_fifth_ = own_.pinned<unsigned long long>(1);
+    mio_.ensure(1);
+    TrackColourBufs b;
+    b.partial = (double *)tc_buf_.get();
+    b.counts = (unsigned long long *)(b.partial + max_groups * 28);
+    b.flag = (int *)(b.counts + 6);
+    b.map = (TrackPixel *)(tc_buf_.get() + head);
+    b.model = (float *)(b.map + npix_);
+    b.Ym = b.model + npix_;
+    b.frame = b.Ym + npix_;
+    b.model_bgr = (unsigned char *)(b.frame + npix_);
+    b.frame_bgr = b.model_bgr + npix_ * 3;
+    b.depth = (const float *)d_depth;
+    b.bgr = (const unsigned char *)d_bgr;
+    if (h_depth) {  // the frame goes through the pinned input buffers as a scan's does
+      memcpy(h_bgr_in_, h_bgr, npix_ * 3);
+      memcpy(h_depth_in_, h_depth, npix_ * 4);
+      DR_HIP(hipMemcpyAsync(b.frame_bgr, h_bgr_in_, npix_ * 3, hipMemcpyHostToDevice, int_stream_));
+      DR_HIP(hipMemcpyAsync(b.frame, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
+      b.depth = b.frame;
+      b.bgr = b.frame_bgr;
+    }
+    tc_stats_[0] = (uint64_t)total; tc_stats_[5] = tc_buf_.capacity();
+    auto eval = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t c5[5]) {
+      const TrackModel tm = track_model(mp16, to.t, o_.voxel_size, b.map);
+      const TrackColour tc = track_colour(to, b.Ym);
+      mio_.evaluate(b.partial, groups, b.counts, 4, sums, c5, [&] {
+        DR_HIP(hipMemsetAsync(b.counts + 4, 0, 8, int_stream_));
+        hipLaunchKernelGGL(k_track_colour, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, b.depth, b.bgr, lg, e, tm, tc, groups, total, b.partial, b.counts);
+        DR_HIP(hipGetLastError());
+        DR_HIP(hipMemcpyAsync(tc_fifth_, b.counts + 4, 8, hipMemcpyDeviceToHost, int_stream_));
+      });
+      c5[4] = *tc_fifth_;
+      tc_stats_[1] = c5[0]; tc_stats_[2] = c5[1]; ++tc_stats_[3];
+    };
+    try {
+      body(to, lg, b, eval);
+    } catch (...) {
+      track_colour_reset();
+      throw;
+    }
+  }
+  void track_colour_system(const char *who, const uint8_t *h_bgr, const float *h_depth, const uint8_t *h_model_bgr, const float *h_model, const void *d_bgr,
+                           const void *d_depth, const void *d_model_bgr, const void *d_model, const float *model_pose16, const float *pose16,
+                           const drf_track_colour_options_t *opt, double *sums, uint64_t *counts) {
+    track_colour_reset();
+    if (!((h_bgr && h_depth) || (d_bgr && d_depth)) || !((h_model_bgr && h_model) || (d_model_bgr && d_model)) || !model_pose16 || !pose16 || !sums || !counts)
+      fail(DR_ERR_ARG, "%s: null argument", who);
+    with_track_colour(who, h_bgr, h_depth, d_bgr, d_depth, pose16, model_pose16, opt,
+                      [&](const TrackColourOpt &to, const LocateGrid &lg, const TrackColourBufs &b, auto &eval) {
+      const float *model = (const float *)d_model;
+      const unsigned char *model_bgr = (const unsigned char *)d_model_bgr;
+      if (h_model) {
+        DR_HIP(hipStreamSynchronize(int_stream_));  // the frame has left the pinned buffers
+        memcpy(h_bgr_in_, h_model_bgr, npix_ * 3);
+        memcpy(h_depth_in_, h_model, npix_ * 4);
+        DR_HIP(hipMemcpyAsync(b.model_bgr, h_bgr_in_, npix_ * 3, hipMemcpyHostToDevice, int_stream_));
+        DR_HIP(hipMemcpyAsync(b.model, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
+        model = b.model;
+        model_bgr = b.model_bgr;
+      }
+      hipLaunchKernelGGL(k_track_model_colour, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, model, model_bgr, lg, to.t.max_jump, b.map, b.Ym);
+      DR_HIP(hipGetLastError());
+      double c_src[3];
+      locate_centre_src(to.t.centre_depth, o_.voxel_size, c_src);
+      eval(align_eval(map_motion(pose16, o_.voxel_size), c_src, to.t.a, o_.voxel_size), model_pose16, sums, counts);
+    });
+  }
+  // returns what dr_last_error() says after a tracking that ran but found no pose (empty otherwise)
+  std::string track_colour_frame(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
+                                 const drf_track_colour_options_t *opt, float *pose16_out, drf_align_result_t *res) {
+    track_colour_reset();
+    if (!((h_bgr && h_depth) || (d_bgr && d_depth)) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+    drf_align_result_t r;
+    uint64_t c5[5] = {0, 0, 0, 0, 0};
+    with_track_colour(who, h_bgr, h_depth, d_bgr, d_depth, pose16, nullptr, opt,
+                      [&](const TrackColourOpt &to, const LocateGrid &lg, const TrackColourBufs &b, auto &eval) {
+      if (!track_colour_render_.cast) { track_colour_render_.cast = own_.event(); track_colour_render_.done = own_.event(); }
+      track_colour_render_.stream = int_stream_;
+      track_colour_render_.d_bgr = b.model_bgr;
+      track_colour_render_.d_band = (RayState *)b.map;
+      track_colour_render_.d_depth = b.model;
+      track_colour_render_.d_flag = b.flag;
+      auto render = [&](const float *p16) {
+        RenderStagePlan plan;
+        RenderBandPlan bands;
+        bool waited = false;
+        const float *poses[1] = {p16};
+        if (render_scope_ == DRF_RENDER_MAP) plan_render_call(who, poses, 1, plan, bands, waited);
+        render_passes(plan, bands, &track_colour_render_, poses, 1, false);
+        hipLaunchKernelGGL(k_track_model_colour, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, (const float *)b.model, (const unsigned char *)b.model_bgr, lg,
+                           to.t.max_jump, b.map, b.Ym);
+        DR_HIP(hipGetLastError());
+        ++tc_stats_[4];
+      };
+      track_colour_loop(render, eval, pose16, to, o_.voxel_size, r, c5);
+    });
+    for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
+    if (res) *res = r;
+    return no_pose_note(std::string(who) + ": the tracking", r,
+                        ", " + std::to_string((unsigned long long)c5[2]) + " unassociated, " + std::to_string((unsigned long long)c5[3]) + " rejected, " +
+                            std::to_string((unsigned long long)c5[4]) + " with a colour term; " + std::to_string((unsigned long long)tc_stats_[4]) + " renders; " +
+                            std::to_string(store_.size()) + " blocks are in the host store)");
+  }
+  void track_colour_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = tc_stats_[i]; }
+
  private:
   void track_reset() { for (auto &v : tk_stats_) v = 0; }
+  void track_colour_reset() { for (auto &v : tc_stats_) v = 0; }
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
   size_t host_free() const { return st_host_cap_ - std::min(st_host_cap_, store_.size()); }
@@ -2375,6 +2509,10 @@ class FusionEngine {
   DeviceBuf<unsigned char> tk_buf_;            // drf_track_*: partial sums, counters, model map, model depth and a host-given frame (sized once)
   uint64_t tk_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_track_stats
   Render track_render_{};                      // drf_track_frame's model render: int_stream_ and pointers into tk_buf_
+  DeviceBuf<unsigned char> tc_buf_;            // drf_track_colour_*: tk_buf_'s parts, the model's and the frame's colour and Ym (sized once)
+  uint64_t tc_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_track_colour_stats
+  unsigned long long *tc_fifth_ = nullptr;     // pinned: the fifth counter of an evaluation
+  Render track_colour_render_{};               // drf_track_colour_frame's model render: int_stream_ and pointers into tc_buf_
   int locate_scope_ = DRF_LOCATE_RESIDENT;     // drf_set_locate_scope
   size_t lc_cap_req_ = 0;
   uint64_t ls_stats_[4] = {0, 0, 0, 0};        // drf_locate_stage_stats
@@ -2619,6 +2757,37 @@ int drf_track_frame_device(drf_t *h, const void *d_depth, const float pose_init1
 }
 int drf_track_stats(drf_t *h, uint64_t out[6]) {
   return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_track_stats: null argument"); eng(h)->track_stats(out); });
+}
+int drf_track_colour_system(drf_t *h, const uint8_t *bgr, const float *depth, const uint8_t *model_bgr, const float *model_depth, const float model_pose16[16],
+                            const float pose16[16], const drf_track_colour_options_t *opt, double sums[28], uint64_t counts[5]) {
+  return guarded([&] {
+    eng(h)->track_colour_system("drf_track_colour_system", bgr, depth, model_bgr, model_depth, nullptr, nullptr, nullptr, nullptr, model_pose16, pose16, opt, sums, counts);
+  });
+}
+int drf_track_colour_system_device(drf_t *h, const void *d_bgr, const void *d_depth, const void *d_model_bgr, const void *d_model_depth, const float model_pose16[16],
+                                   const float pose16[16], const drf_track_colour_options_t *opt, double sums[28], uint64_t counts[5]) {
+  return guarded([&] {
+    eng(h)->track_colour_system("drf_track_colour_system_device", nullptr, nullptr, nullptr, nullptr, d_bgr, d_depth, d_model_bgr, d_model_depth, model_pose16, pose16, opt,
+                                sums, counts);
+  });
+}
+static int track_colour_frame_call(drf_t *h, const char *who, const uint8_t *bgr, const float *depth, const void *d_bgr, const void *d_depth, const float *pose_init16,
+                                   const drf_track_colour_options_t *opt, float *pose16_out, drf_align_result_t *res) {
+  std::string note;
+  const int rc = guarded([&] { note = eng(h)->track_colour_frame(who, bgr, depth, d_bgr, d_depth, pose_init16, opt, pose16_out, res); });
+  if (rc == DR_OK && !note.empty()) dr::last_error_slot() = note;
+  return rc;
+}
+int drf_track_colour_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float pose_init16[16], const drf_track_colour_options_t *opt, float pose16_out[16],
+                           drf_align_result_t *res) {
+  return track_colour_frame_call(h, "drf_track_colour_frame", bgr, depth, nullptr, nullptr, pose_init16, opt, pose16_out, res);
+}
+int drf_track_colour_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float pose_init16[16], const drf_track_colour_options_t *opt,
+                                  float pose16_out[16], drf_align_result_t *res) {
+  return track_colour_frame_call(h, "drf_track_colour_frame_device", nullptr, nullptr, d_bgr, d_depth, pose_init16, opt, pose16_out, res);
+}
+int drf_track_colour_stats(drf_t *h, uint64_t out[6]) {
+  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_track_colour_stats: null argument"); eng(h)->track_colour_stats(out); });
 }
 int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_locate_scope(scope, stage_capacity_blocks); }); }
 int drf_locate_stage_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->locate_stage_stats(out); }); }

@@ -1255,8 +1255,10 @@ inline TrackModel track_model(const float *model_pose16, const TrackOpt &o, floa
 // the pixel (floor(u' + 0.5), floor(v' + 0.5)); outside the image or an invalid model pixel is UNASSOCIATED (returns 0).  The model
 // vertex vm is that pixel's back-projection at its z, as locate_pixel computes a point; d = m - vm; a sample for which
 // |d|^2 <= lim2 is false is REJECTED (returns 2).  Otherwise r = (n0 d0 + n1 d1) + n2 d2 with the pixel's normal widened to
-// double, nw = Rm n, and align_accumulate adds the sample (returns 1).
-DR_HOST_DEVICE inline int track_point(const AlignEval &e, const TrackModel &t, const LocateGrid &lg, double g0, double g1, double g2, double acc[28]) {
+// double, nw = Rm n, and tail(r, nw0, nw1, nw2, q, m, u', v') adds the sample's terms and returns the code (1 for track_point).
+// The tail is where track_point and track_colour_point differ: one term, or two.
+template <class Tail>
+DR_HOST_DEVICE inline int track_sample(const AlignEval &e, const TrackModel &t, const LocateGrid &lg, double g0, double g1, double g2, Tail &&tail) {
   double q[3], m[3];
   DR_UNROLL
   for (int k = 0; k < 3; ++k) q[k] = ((e.m.R[3 * k] * g0 + e.m.R[3 * k + 1] * g1) + e.m.R[3 * k + 2] * g2) + e.m.tv[k];
@@ -1280,8 +1282,14 @@ DR_HOST_DEVICE inline int track_point(const AlignEval &e, const TrackModel &t, c
   const double w0 = (t.m.R[0] * n0 + t.m.R[1] * n1) + t.m.R[2] * n2;
   const double w1 = (t.m.R[3] * n0 + t.m.R[4] * n1) + t.m.R[5] * n2;
   const double w2 = (t.m.R[6] * n0 + t.m.R[7] * n1) + t.m.R[8] * n2;
-  align_accumulate(e, r, w0, w1, w2, q, acc);
-  return 1;
+  return tail(r, w0, w1, w2, q, m, up, vp);
+}
+// The geometric term alone: align_accumulate adds the sample.
+DR_HOST_DEVICE inline int track_point(const AlignEval &e, const TrackModel &t, const LocateGrid &lg, double g0, double g1, double g2, double acc[28]) {
+  return track_sample(e, t, lg, g0, g1, g2, [&](double r, double w0, double w1, double w2, const double *q, const double *, double, double) {
+    align_accumulate(e, r, w0, w1, w2, q, acc);
+    return 1;
+  });
 }
 // Group i in the wave's order (locate_group's); counts += {samples, valid, unassociated, rejected}.
 inline void track_group(const AlignEval &e, const TrackModel &t, const LocateGrid &lg, const float *depth, long i, double out[28], uint64_t counts[4]) {
@@ -1361,6 +1369,159 @@ inline void track_frame_host(const LocateGrid &lg, const float *depth, RenderDep
              [&](const AlignEval &e, const float *p16, double sums[28], uint64_t c4[4]) {
                track_system_host(lg, depth, track_model(p16, o, voxel_size, map.data()), e, sums, c4);
              }, pose_init16, o, voxel_size, res, last4, stats2, trace);
+}
+
+// ---- tracking with colour (drf_track_colour_system / drf_track_colour_frame; DESIGN.md §7c "Tracking with colour").  The tracking
+// above sees geometry only, and a map of planes leaves the motion inside the planes open.  Every voxel carries a colour and the
+// ray-cast renders it, so a sample whose geometric term was added contributes a second, photometric term: the difference between
+// the model's colour image, interpolated where the sample projects, and the frame's own pixel, as intensities, scaled to voxels by
+// photo_weight.  Its gradient with respect to the point is a 3-vector like the plane's normal, so both terms go through the one
+// align_accumulate into the same 28 sums, and step, loop and outer loop are the geometric call's, unchanged.  Stated once, here;
+// the header of the C ABI restates it.  Compiled by g++ and by hipcc (k_track_model_colour, k_track_colour), both without
+// contraction; + - * / sqrt and floor only.
+#if defined(__HIPCC__)
+#define DR_NO_UNROLL _Pragma("unroll 1")
+#else
+#define DR_NO_UNROLL
+#endif
+struct TrackColourOpt {  // drf_track_colour_options_t with its defaults resolved
+  TrackOpt t;
+  float photo_weight;  // voxels per intensity unit
+};
+// null: all defaults.  photo_weight 0 is (float)(1.0 / 27.0) * huber in fp32, huber resolved first: a colour residual of 27 units
+// of the three-channel sum -- 9 grey levels of 255 -- weighs what a geometric residual at Huber's threshold weighs.
+inline const char *track_colour_options(const drf_track_colour_options_t *opt, float voxel_size, TrackColourOpt &o) {
+  static const drf_track_colour_options_t zero = {{0, 0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0, 0.0, 0.0}, 0.0f};
+  const drf_track_colour_options_t &u = opt ? *opt : zero;
+  if (const char *bad = track_options(&u.track, voxel_size, o.t)) return bad;
+  if (!(u.photo_weight >= 0.0f) || !std::isfinite(u.photo_weight)) return "photo_weight";
+  o.photo_weight = u.photo_weight != 0.0f ? u.photo_weight : (float)(1.0 / 27.0) * o.t.a.huber;
+  return nullptr;
+}
+// the intensity of a BGR pixel: a whole number in 0..765
+DR_HOST_DEVICE inline float track_intensity(const unsigned char *bgr) { return ((float)bgr[0] + (float)bgr[1]) + (float)bgr[2]; }
+// One pixel of the model intensity map Ym: the intensity of the model colour image where the model map's pixel is valid, -1
+// elsewhere -- misses, the border and depth discontinuities are excluded by the test the geometric term uses.
+DR_HOST_DEVICE inline float track_model_intensity(const TrackPixel &p, const unsigned char *bgr) { return p.z > 0.0f ? track_intensity(bgr) : -1.0f; }
+inline void track_model_colour_host(const LocateGrid &lg, float max_jump, const float *Dm, const unsigned char *Cm, TrackPixel *out, float *Ym) {
+  for (int v = 0; v < lg.H; ++v)
+    for (int u = 0; u < lg.W; ++u) {
+      const size_t at = (size_t)v * lg.W + u;
+      out[at] = track_normal(lg, max_jump, Dm, u, v);
+      Ym[at] = track_model_intensity(out[at], Cm + 3 * at);
+    }
+}
+// what an evaluation with colour reads besides the TrackModel: Ym and lambda = (double)photo_weight
+struct TrackColour {
+  const float *Ym;
+  double weight;
+};
+inline TrackColour track_colour(const TrackColourOpt &o, const float *Ym) {
+  TrackColour c;
+  c.Ym = Ym; c.weight = (double)o.photo_weight;
+  return c;
+}
+struct TrackPair { float a, b; };  // two neighbours of a row of Ym: one 8-byte read at a 4-byte aligned address
+// The photometric term of a sample that track_sample accepted, from its m, u', v' and the frame's intensity yf at the sample's
+// own pixel.  u0 = floor(u'), v0 = floor(v'), a = u' - u0, b = v' - v0; the term is SKIPPED (returns false) unless 0 <= u0,
+// u0 + 1 <= W - 1, 0 <= v0, v0 + 1 <= H - 1 and the four corners y00 = Ym(u0, v0), y10 = Ym(u0 + 1, v0), y01 = Ym(u0, v0 + 1),
+// y11 = Ym(u0 + 1, v0 + 1) are all >= 0.  In double, oa = 1 - a, ob = 1 - b:
+//   I  = ob * (oa * y00 + a * y10) + b * (oa * y01 + a * y11)
+//   Iu = ob * (y10 - y00) + b * (y11 - y01),  Iv = oa * (y01 - y00) + a * (y11 - y10)     the exact gradient of that interpolant
+//   gm0 = (Iu * fx) / m2, gm1 = (Iv * fy) / m2, gm2 = -((gm0 * m0 + gm1 * m1) / m2)          dI/dm through u' = fx m0 / m2 + cx
+//   r = lambda * (I - yf),  n_k = lambda * ((Rm[k][0] gm0 + Rm[k][1] gm1) + Rm[k][2] gm2)   dr/dq = Rm dr/dm, as for the plane
+DR_HOST_DEVICE inline bool track_photo_term(const TrackModel &t, const TrackColour &tc, const LocateGrid &lg, const double m[3], double up, double vp, float yf,
+                                            double &r, double n[3]) {
+  const double fu = floor(up), fv = floor(vp);
+  if (!(fu >= 0.0 && fu + 1.0 <= (double)(lg.W - 1) && fv >= 0.0 && fv + 1.0 <= (double)(lg.H - 1))) return false;
+  const size_t at = (size_t)(int)fv * (size_t)lg.W + (size_t)(int)fu;
+  TrackPair top, bot;
+  memcpy(&top, tc.Ym + at, sizeof top);
+  memcpy(&bot, tc.Ym + at + (size_t)lg.W, sizeof bot);
+  if (!(top.a >= 0.0f && top.b >= 0.0f && bot.a >= 0.0f && bot.b >= 0.0f)) return false;
+  const double y00 = (double)top.a, y10 = (double)top.b, y01 = (double)bot.a, y11 = (double)bot.b;
+  const double a = up - fu, b = vp - fv, oa = 1.0 - a, ob = 1.0 - b;
+  const double I = ob * (oa * y00 + a * y10) + b * (oa * y01 + a * y11);
+  const double Iu = ob * (y10 - y00) + b * (y11 - y01), Iv = oa * (y01 - y00) + a * (y11 - y10);
+  const double gm0 = (Iu * (double)lg.fx) / m[2], gm1 = (Iv * (double)lg.fy) / m[2];
+  const double gm2 = -((gm0 * m[0] + gm1 * m[1]) / m[2]);
+  r = tc.weight * (I - (double)yf);
+  n[0] = tc.weight * ((t.m.R[0] * gm0 + t.m.R[1] * gm1) + t.m.R[2] * gm2);
+  n[1] = tc.weight * ((t.m.R[3] * gm0 + t.m.R[4] * gm1) + t.m.R[5] * gm2);
+  n[2] = tc.weight * ((t.m.R[6] * gm0 + t.m.R[7] * gm1) + t.m.R[8] * gm2);
+  return true;
+}
+// One sample with colour: track_sample's codes 0 (unassociated) and 2 (rejected) add nothing; otherwise the geometric term is
+// added first and, where track_photo_term has one, the photometric term second: returns 1 for the one, 3 for both.  The two are
+// trips of one loop, so that align_accumulate stands once in the kernel's instruction stream.
+DR_HOST_DEVICE inline int track_colour_point(const AlignEval &e, const TrackModel &t, const TrackColour &tc, const LocateGrid &lg, double g0, double g1, double g2,
+                                             float yf, double acc[28]) {
+  return track_sample(e, t, lg, g0, g1, g2, [&](double r, double w0, double w1, double w2, const double *q, const double *m, double up, double vp) {
+    double pr = 0.0, pn[3] = {0.0, 0.0, 0.0};
+    const bool photo = track_photo_term(t, tc, lg, m, up, vp, yf, pr, pn);
+    const int terms = photo ? 2 : 1;
+    DR_NO_UNROLL
+    for (int k = 0; k < terms; ++k) {
+      const bool second = k == 1;
+      align_accumulate(e, second ? pr : r, second ? pn[0] : w0, second ? pn[1] : w1, second ? pn[2] : w2, q, acc);
+    }
+    return photo ? 3 : 1;
+  });
+}
+// Group i in the wave's order (locate_group's); counts += {samples, valid, unassociated, rejected, photometric terms added}.
+inline void track_colour_group(const AlignEval &e, const TrackModel &t, const TrackColour &tc, const LocateGrid &lg, const unsigned char *bgr, const float *depth,
+                               long i, double out[28], uint64_t counts[5]) {
+  double x[64][28];
+  const long total = locate_positions(lg);
+  for (int l = 0; l < 64; ++l) {
+    for (int c = 0; c < 28; ++c) x[l][c] = 0.0;
+    for (int k = 0; k < 8; ++k) {
+      const long n = 512 * i + l + 64 * k;
+      double g[3];
+      if (n >= total || !locate_pixel(lg, e.vs, (int)n, depth, g)) continue;
+      ++counts[0];
+      const int r = track_colour_point(e, t, tc, lg, g[0], g[1], g[2], track_intensity(bgr + 3 * locate_offset(lg, (int)n)), x[l]);
+      ++counts[(r & 1) ? 1 : r == 0 ? 2 : 3];
+      if (r == 3) ++counts[4];
+    }
+  }
+  align_butterfly(x);
+  for (int c = 0; c < 28; ++c) out[c] = x[0][c];
+}
+inline void track_colour_system_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, const TrackModel &t, const TrackColour &tc,
+                                     const AlignEval &e, double sums[28], uint64_t counts[5]) {
+  for (int c = 0; c < 5; ++c) counts[c] = 0;
+  const size_t n = (size_t)locate_groups(lg);
+  std::vector<double> partial(n * 28);
+  for (size_t i = 0; i < n; ++i) track_colour_group(e, t, tc, lg, bgr, depth, (long)i, &partial[i * 28], counts);
+  align_fold_host(partial.data(), n, sums);
+}
+// track_loop over an evaluator with five counters: the loop sees the first four, last5 (if given) receives all five of the last
+// evaluation.  The render callback builds the model map and Ym from the colour and the depth it rendered.
+template <class Render, class Eval>
+inline void track_colour_loop(Render &&render, Eval &&eval, const float *pose_init16, const TrackColourOpt &o, float voxel_size, drf_align_result_t &res,
+                              uint64_t *last5 = nullptr, uint64_t *stats2 = nullptr, std::vector<std::array<double, 28>> *trace = nullptr) {
+  track_loop(render, [&](const AlignEval &e, const float *p16, double sums[28], uint64_t c4[4]) {
+    uint64_t c5[5];
+    eval(e, p16, sums, c5);
+    memcpy(c4, c5, 4 * sizeof(uint64_t));
+    if (last5) memcpy(last5, c5, sizeof c5);
+  }, pose_init16, o.t, voxel_size, res, nullptr, stats2, trace);
+}
+// The whole tracking with colour on the CPU over any renderer render(const float pose16[16], unsigned char *Cm, float *Dm): the
+// library's reference for drf_track_colour_frame, and what the sanitizer program runs.
+template <class RenderBoth>
+inline void track_colour_frame_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, RenderBoth &&render_both, const float *pose_init16,
+                                    const TrackColourOpt &o, float voxel_size, drf_align_result_t &res, uint64_t *last5 = nullptr, uint64_t *stats2 = nullptr,
+                                    std::vector<std::array<double, 28>> *trace = nullptr) {
+  const size_t npix = (size_t)lg.W * (size_t)lg.H;
+  std::vector<float> Dm(npix), Ym(npix);
+  std::vector<unsigned char> Cm(npix * 3);
+  std::vector<TrackPixel> map(npix);
+  track_colour_loop([&](const float *p16) { render_both(p16, Cm.data(), Dm.data()); track_model_colour_host(lg, o.t.max_jump, Dm.data(), Cm.data(), map.data(), Ym.data()); },
+                    [&](const AlignEval &e, const float *p16, double sums[28], uint64_t c5[5]) {
+                      track_colour_system_host(lg, bgr, depth, track_model(p16, o.t, voxel_size, map.data()), track_colour(o, Ym.data()), e, sums, c5);
+                    }, pose_init16, o, voxel_size, res, last5, stats2, trace);
 }
 
 }  // namespace dr

@@ -480,6 +480,68 @@ class DrFusion:
         check(self._L.drf_track_stats(self._h, out))
         return tuple(int(v) for v in out)
 
+    # ---- tracking with colour (include/dr_mi355x.h drf_track_colour_frame, DESIGN.md "Tracking with colour") ----
+    @staticmethod
+    def _track_colour_options(photo_weight, opt):
+        if not opt and not photo_weight:
+            return None
+        unknown = set(opt) - {f[0] for f in _lib.TrackOptions._fields_}
+        if unknown:
+            raise TypeError("unknown track option(s): %s" % ", ".join(sorted(unknown)))
+        return _lib.TrackColourOptions(_lib.TrackOptions(**opt), photo_weight)
+
+    def _track_colour_image(self, bgr):
+        """(is a device pointer, the argument, what keeps it alive)"""
+        if isinstance(bgr, (int, np.integer)):
+            return True, C.c_void_p(int(bgr)), None
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        assert bgr.size == self._hw[0] * self._hw[1] * 3
+        return False, C.c_void_p(bgr.ctypes.data), bgr
+
+    def track_colour_system(self, bgr, depth, model_bgr, model_depth, model_pose, pose, photo_weight=0.0, **opt):
+        """One evaluation of the tracking's system with the photometric term: the frame (bgr H*W*3 uint8, depth H*W float32) at the
+        pose against the model's colour and depth, a ray-cast at model_pose (all four on the host or all four integer device
+        pointers): (sums (28,) float64, (samples, valid, unassociated, rejected, photometric terms added)).  photo_weight: voxels
+        per intensity unit, 0 = 1/27 times huber; opt: the fields of drf_track_options_t.  No map is read."""
+        dev, d, keep = self._locate_depth(depth)
+        mdev, m, mkeep = self._locate_depth(model_depth)
+        cdev, c, ckeep = self._track_colour_image(bgr)
+        mcdev, mc, mckeep = self._track_colour_image(model_bgr)
+        assert dev == mdev == cdev == mcdev, "all four images on the host or all four on the device"
+        pose = np.ascontiguousarray(pose, np.float32).reshape(16)
+        mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
+        o = self._track_colour_options(photo_weight, opt)
+        sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 5)()
+        call = self._L.drf_track_colour_system_device if dev else self._L.drf_track_colour_system
+        check(call(self._h, c, d, mc, m, fptr(mpose), fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
+        return sums, tuple(int(v) for v in counts)
+
+    def track_colour_frame(self, bgr, depth, pose_init, raise_on_failure=True, photo_weight=0.0, **opt):
+        """track_frame with the frame's colour image (as IntegrateScanAsync takes it) and a photometric term next to the geometric
+        one: it holds the motion inside a plane, which track_frame leaves open (on one wall track_frame is ALIGN_DEGENERATE, this
+        call is not).  Both images on the host, or both integer device pointers.  Returns an AlignResult whose cost carries both
+        terms; ALIGN_DEGENERATE or ALIGN_LOST raises AlignError unless raise_on_failure is false."""
+        dev, d, keep = self._locate_depth(depth)
+        cdev, c, ckeep = self._track_colour_image(bgr)
+        assert dev == cdev, "both images on the host or both on the device"
+        pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
+        o = self._track_colour_options(photo_weight, opt)
+        T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
+        call = self._L.drf_track_colour_frame_device if dev else self._L.drf_track_colour_frame
+        check(call(self._h, c, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
+        res = AlignResult(T=np.array(r.T, np.float64).reshape(4, 4), T32=T32.reshape(4, 4), sums=np.array(r.sums, np.float64), samples=int(r.samples),
+                          valid0=int(r.valid0), valid=int(r.valid), cost0=float(r.cost0), cost=float(r.cost), iterations=int(r.iterations),
+                          status=int(r.status))
+        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
+            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
+        return res
+
+    def track_colour_stats(self):
+        """Last track_colour_system / track_colour_frame: track_stats' fields; the device bytes are a buffer of these calls' own."""
+        out = (C.c_uint64 * 6)()
+        check(self._L.drf_track_colour_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
     def set_render_scope(self, scope, stage_capacity_blocks=0):
         """RENDER_RESIDENT (default): renders read the pool; RENDER_MAP: the pool and the host store -- any pose renders as on an
         engine whose pool never ran out, the stored blocks in reach staged through stage_capacity_blocks blocks of device scratch

@@ -132,6 +132,15 @@ public:
     check(drf_track_frame(impl, depth, pose_init16, opt, pose16_out, &res));
     return res.status;
   }
+  // the same with the frame's colour image (bgr as IntegrateScanAsync takes it) and a photometric term next to the geometric one
+  // (dr_mi355x.h drf_track_colour_frame): it holds the motion inside a plane, which TrackDepthFrame leaves open -- on a single wall
+  // TrackDepthFrame is DRF_ALIGN_DEGENERATE and this call is not.  opt null = its defaults.  Returns the status, DRF_ALIGN_*.
+  int TrackColourFrame(unsigned char const *bgr, float const *depth, float const *pose_init16, float *pose16_out,
+                       drf_track_colour_options_t const *opt = nullptr) {
+    drf_align_result_t res;
+    check(drf_track_colour_frame(impl, bgr, depth, pose_init16, opt, pose16_out, &res));
+    return res.status;
+  }
   // DRF_LOCATE_MAP: LocateDepthFrame reads resident and host-stored blocks together, without moving one (capacity 0 = the default
   // staging); DRF_LOCATE_RESIDENT, the default: the pool only
   void SetLocateScope(int scope, size_t capacity = 0) { check(drf_set_locate_scope(impl, scope, capacity)); }

@@ -16,6 +16,10 @@ one warm-up, all runs listed:
   locate_after_s     one DrFusion.locate_frame from the pose the tracking ended on, with its iterations, status and pose error
 As information: locate_frame alone from the start pose (its status), the pose errors after the tracking and after the
 localisation (rotation in degrees, translation of the camera centre in voxels), valid / samples.
+--colour adds the same figures for drf_track_colour_frame (the frame's own colour image next to its depth) under "colour", from the same
+start in the same session: frame_s, frame_device_s, one_s, eval_s, render_s, the pose error after the tracking, and
+eval_ratio = its eval_s / the geometric eval_s -- the colour evaluation gathers three elements per sample where the geometric one
+gathers one.
 Not measured: the kernels alone; k_track's fp64 share and the latency of its model gather (that takes counter runs of this tool, in
 runs of their own).
 One JSON line on stdout; --out writes it, ending with the box's gpu_state."""
@@ -51,6 +55,7 @@ def main():
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--num-blocks", type=int, default=400000)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--colour", action="store_true", help="also time drf_track_colour_frame")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.reps >= 3, "each figure is the median of at least 3 runs"
@@ -79,15 +84,39 @@ def main():
         r = f.track_frame(d, start, raise_on_failure=False, **dict(o, **kw))
         return r, f.track_stats()
 
-    (r, st), frame_s, frame_all = timed(lambda: track(depth), args.reps)
-    (rd, _), frame_device_s, frame_device_all = timed(lambda: track(dptr), args.reps)
-    assert np.array_equal(r.T, rd.T) and r.iterations == rd.iterations
-    (r1, st1), one_s, one_all = timed(lambda: track(dptr, max_renders=1, inner_iters=1), args.reps)
-    (r4, st4), four_s, four_all = timed(lambda: track(dptr, max_renders=1, inner_iters=4), args.reps)
-    (r2, st2), two_s, two_all = timed(lambda: track(dptr, max_renders=2, inner_iters=1), args.reps)
-    assert st1[3:5] == (1, 1) and st2[3:5] == (2, 2) and st4[4] == 1
-    eval_s = (four_s - one_s) / (st4[3] - 1) if st4[3] > 1 else None
-    render_s = (two_s - one_s) - eval_s if eval_s is not None else None
+    def figures(track, d_host, d_dev):
+        """the timings of one tracking call: host pointer, device pointer, one render + one evaluation, a further evaluation, a further render"""
+        (r, st), frame_s, frame_all = timed(lambda: track(d_host), args.reps)
+        (rd, _), frame_device_s, frame_device_all = timed(lambda: track(d_dev), args.reps)
+        assert np.array_equal(r.T, rd.T) and r.iterations == rd.iterations
+        (r1, st1), one_s, one_all = timed(lambda: track(d_dev, max_renders=1, inner_iters=1), args.reps)
+        (r4, st4), four_s, four_all = timed(lambda: track(d_dev, max_renders=1, inner_iters=4), args.reps)
+        (r2, st2), two_s, two_all = timed(lambda: track(d_dev, max_renders=2, inner_iters=1), args.reps)
+        assert st1[3:5] == (1, 1) and st2[3:5] == (2, 2) and st4[4] == 1
+        eval_s = (four_s - one_s) / (st4[3] - 1) if st4[3] > 1 else None
+        render_s = (two_s - one_s) - eval_s if eval_s is not None else None
+        return r, st, st4, dict(frame_s=frame_s, frame_all=frame_all, frame_device_s=frame_device_s, frame_device_all=frame_device_all, one_s=one_s, one_all=one_all,
+                                four_s=four_s, four_all=four_all, two_s=two_s, two_all=two_all, eval_s=eval_s, render_s=render_s)
+
+    r, st, st4, t = figures(track, depth, dptr)
+    frame_s, frame_all, frame_device_s, frame_device_all = t["frame_s"], t["frame_all"], t["frame_device_s"], t["frame_device_all"]
+    one_s, one_all, four_s, four_all, two_s, two_all, eval_s, render_s = (t[k] for k in ("one_s", "one_all", "four_s", "four_all", "two_s", "two_all", "eval_s", "render_s"))
+    colour = None
+    if args.colour:
+        bgr, d_bgr = np.ascontiguousarray(frames["bgr"][k], np.uint8), C.c_void_p()
+        assert L.dr_device_alloc(0, bgr.nbytes, C.byref(d_bgr)) == 0 and L.dr_memcpy_h2d(d_bgr, bgr.ctypes.data_as(C.c_void_p), bgr.nbytes) == 0
+
+        def track_colour(d, **kw):
+            b, dd = (int(d_bgr.value), d) if isinstance(d, int) else (bgr, d)
+            rc = f.track_colour_frame(b, dd, start, raise_on_failure=False, **dict(o, **kw))
+            return rc, f.track_colour_stats()
+
+        rc, stc, stc4, colour = figures(track_colour, depth, dptr)
+        L.dr_device_free(d_bgr)
+        rotc, trc = pose_error(rc.T, pose, vs)
+        colour.update(renders=stc[4], evaluations=stc[3], four_evaluations=stc4[3], status=ALIGN_STATUS[rc.status], device_bytes=stc[5], valid_at_start=rc.valid0,
+                      valid_at_end=rc.valid, cost0=rc.cost0, cost=rc.cost, track_error_rotation_deg=rotc, track_error_translation_voxels=trc,
+                      eval_ratio=(colour["eval_s"] / eval_s) if colour["eval_s"] and eval_s else None)
     la, locate_after_s, locate_after_all = timed(lambda: f.locate_frame(dptr, r.T32, raise_on_failure=False, centre_depth=cd), args.reps)
     alone = f.locate_frame(dptr, start, raise_on_failure=False, centre_depth=cd)
     L.dr_device_free(d_depth)
@@ -103,6 +132,8 @@ def main():
                locate_alone_status=ALIGN_STATUS[alone.status], locate_alone_valid=alone.valid, start_error_rotation_deg=rot0, start_error_translation_voxels=tr0,
                track_error_rotation_deg=rot, track_error_translation_voxels=tr, locate_error_rotation_deg=rotl, locate_error_translation_voxels=trl,
                not_measured="the kernels alone; k_track's fp64 share and the latency of its model gather; the phases of a render (plan, ray-cast, model map) apart")
+    if colour is not None:
+        out["colour"] = colour
     f.close()
     out["gpu_state"] = gpu_state()
     print(json.dumps(out), flush=True)
