@@ -471,7 +471,7 @@ int drf_transform_stats(drf_t *h, uint64_t out[6]);
  * The engine lends its device, its streams, its pinned buffers and its voxel_size; its own map is neither read nor changed, exactly
  * as for drf_transform_map.  drf_align_system evaluates the system once at T16: the score of a pose hypothesis (sums[27] /
  * counts[1] is the mean robust squared residual in voxels^2; counts[1] / counts[0] the overlap).
- * The rule (one text, fusion_host.h, compiled for the host and for the kernel; double and fp32 without contraction):
+ * The rule (one text, pose_host.h, compiled for the host and for the kernel; double and fp32 without contraction):
  *   motion    Rd[i][j] = T16[4 i + j], tv[j] = T16[4 j + 3] / voxel_size in double, as for drf_transform_map; during the iterations
  *             the pose is held as (Rd, tv) in double.
  *   centre    once, from the source's block coordinates, integers in double: c_src[k] = 4 (min_k + max_k + 1) (0 for an empty
@@ -584,7 +584,7 @@ int drf_align_stats(drf_t *h, uint64_t out[6]);
  *              DR_ERR_CAPACITY before anything is evaluated (a later pose of a refinement whose selection exceeds it ends the
  *              call the same way); the message gives both counts.  Raise the capacity, or use drf_stream_in_region.  Depth bands
  *              (drf_set_render_bands) do not apply to this call.
- * The rule (one text, fusion_host.h, compiled for the host and for the kernel; double and fp32 without contraction; only + - * /
+ * The rule (one text, pose_host.h, compiled for the host and for the kernel; double and fp32 without contraction; only + - * /
  * sqrt and floor are used):
  *   pose      pose16 is the engine's own convention: row-major, camera-to-world, metres.  Rd[i][j] = pose16[4 i + j],
  *             tv[j] = pose16[4 j + 3] / voxel_size in double; during the iterations the pose is held as (Rd, tv) in double.
@@ -661,7 +661,7 @@ int drf_locate_stage_stats(drf_t *h, uint64_t out[4]);
  * renders again.  The public render buffers, drf_get_render_device and the render protocol are not touched; the map is neither
  * changed nor grown.  The call runs on the integration stream behind any pending scan and returns when it is done.
  * drf_track_system is one evaluation against a model depth image the caller supplies (a ray-cast at model_pose16): it reads no map.
- * The rule (one text, fusion_host.h, compiled for the host and for the kernels; double and fp32 without contraction; only + - * /
+ * The rule (one text, pose_host.h, compiled for the host and for the kernels; double and fp32 without contraction; only + - * /
  * sqrt and floor are used):
  *   model map Per pixel (u, v) of the model depth image Dm (height x width floats, a ray-cast at the pose Pm) four fp32 values
  *             (nx, ny, nz, z), all 0 where the pixel is INVALID.  A miss of the ray-cast is the 0.0f it writes for a ray that found
@@ -735,7 +735,7 @@ int drf_track_stats(drf_t *h, uint64_t out[6]);
  * stream, the map left unchanged, the legality and the refusals (in that order, the colour images among the null checks) holds
  * here.  Out of scope: an affine brightness or exposure model (frame and map are taken to share their exposure), an image
  * pyramid, a global search, and photometric terms in drf_locate_*.
- * The rule (the same text of fusion_host.h; double and fp32 without contraction; + - * / sqrt floor):
+ * The rule (the same text of pose_host.h; double and fp32 without contraction; + - * / sqrt floor):
  *   intensity   a BGR pixel is y = ((float)b + (float)g) + (float)r, a whole number in 0..765.
  *   Ym          the model intensity map, one float per pixel of the model colour image Cm: Ym(u, v) = the pixel's y where the model
  *               map's pixel is valid (its z > 0), -1.0f elsewhere: misses, the border and depth discontinuities carry no colour.

@@ -1,5 +1,5 @@
 // align_kernels.h -- drf_align_system / drf_align_map on the device: one evaluation of the registration's Gauss-Newton system
-// (the rule: fusion_host.h align_voxel; DESIGN.md §7c "Registering two maps").  Included by dr_fusion.hip inside namespace dr, behind
+// (the rule: pose_host.h align_voxel; DESIGN.md §7c "Registering two maps").  Included by dr_fusion.hip inside namespace dr, behind
 // stream_kernels.h, whose table search (xf_find) and block look-up (XfFetch) the reference map is read through.
 
 // One wave per source block i in [0, n_src) of the ascending key table (no grid stride: the workgroup's four waves meet at one

@@ -1509,14 +1509,14 @@ class FusionEngine {
     if (!ok) fail(DR_ERR_IO, "drf_merge_map: %s (the blocks merged so far stay merged: drf_merge_stats)", err.c_str());
     loaded_ = true;
   }
-  void merge_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = mg_stats_[i]; }
+  const uint64_t *merge_stats() const { return mg_stats_; }
 
   // Operations on map files alone (map_ops.h: map_transform, map_align_system, map_align).  The engine lends mio_ -- its device,
   // int_stream_, the pinned pair, voxel_size -- and states where in its call order they may run; its own map is neither read nor changed.
   void transform_map(const char *src, const float *T16, const char *dst, size_t chunk_blocks) {
     map_transform(mio_, src, T16, dst, chunk_blocks, [&] { expect_integrate("drf_transform_map"); });
   }
-  void transform_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = mio_.xf_stats[i]; }
+  const uint64_t *transform_stats() const { return mio_.xf_stats; }
   void align_system(const char *src, const char *ref, const float *T16, const drf_align_options_t *opt, double *sums, uint64_t *counts) {
     map_align_system(mio_, src, ref, T16, opt, sums, counts, [&](const char *who) { expect_integrate(who); });
   }
@@ -1524,31 +1524,59 @@ class FusionEngine {
   std::string align_map(const char *src, const char *ref, const float *T16, const drf_align_options_t *opt, float *T16_out, drf_align_result_t *res) {
     return map_align(mio_, src, ref, T16, opt, T16_out, res, [&](const char *who) { expect_integrate(who); });
   }
-  void align_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = mio_.al_stats[i]; }
+  const uint64_t *align_stats() const { return mio_.al_stats; }
 
-  // A depth frame located in the map this engine holds (the rule: fusion_host.h locate_pixel / align_point; DESIGN.md §7c "Locating a
-  // depth frame in the map").  The map is read where it lives, through find_block; nothing of it is uploaded, changed or allocated.
-  // with_locate does what both calls share -- the refusals in their order, pending work settled, a host depth image through the
-  // scan's pinned input buffer into device scratch that is sized once (partial sums, counters, the image) -- and hands body an
-  // evaluator: k_map_locate + k_align_fold on int_stream_, 28 doubles and 4 counters back through the pinned pair.
-  template <class Body>
-  void with_locate(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_locate_options_t *opt, Body &&body) {
-    locate_reset();
-    LocateOpt lo;
-    if (const char *bad = locate_options(opt, o_.truncation_distance, lo)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
+  // ---- a camera pose from a frame: drf_locate_*, drf_track_*, drf_track_colour_* (the rules: pose_host.h; DESIGN.md "Where the
+  // frame-pose code lives").  What the three families open with, written once.  frame_prologue: the refusals in their one order --
+  // the options (bad_option: what the family's resolver returned), the call order, blocks in the host store while streaming is
+  // off, the pose, the model pose (the *_system calls of the tracking) -- then pending work settled.
+  void frame_prologue(const char *who, const char *bad_option, const float *pose16, const float *model_pose16) {
+    if (bad_option) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad_option);
     expect_integrate(who);
     if (st_radius_ <= 0.0f && !store_.empty())
       fail(DR_ERR_PROTOCOL, "%s: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", who, store_.size());
     if (const char *why = transform_pose_fault(pose16)) fail(DR_ERR_ARG, "%s: the pose %s", who, why);
+    if (model_pose16)
+      if (const char *why = transform_pose_fault(model_pose16)) fail(DR_ERR_ARG, "%s: the model pose %s", who, why);
     settle();  // behind any pending scan; the pinned buffers are idle and every eviction is in the host store
-    const LocateGrid lg = locate_grid(o_, lo.step);
-    const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
-    const size_t max_groups = (npix_ + 511) / 512;  // step = 1
-    const size_t bytes = max_groups * 224 + 32 + npix_ * 4;
-    lc_buf_.reserve(bytes, int_stream_);
+  }
+  // the sample grid of a call and what a launch over it needs; max_groups (step = 1) sizes the scratch once for every step
+  struct FrameGrid { LocateGrid lg; int total, groups; size_t max_groups; };
+  FrameGrid frame_grid(int step) const {
+    const LocateGrid lg = locate_grid(o_, step);
+    return {lg, (int)locate_positions(lg), (int)locate_groups(lg), (npix_ + 511) / 512};
+  }
+  // A host image pair, or a depth image alone (d_bgr null), through the scan's pinned input buffers into scratch.  again: the
+  // buffers carry this call's frame, which must have left them first.
+  void upload_frame(const uint8_t *h_bgr, const float *h_depth, unsigned char *d_bgr, float *d_depth, bool again = false) {
+    if (again) DR_HIP(hipStreamSynchronize(int_stream_));
+    if (d_bgr) memcpy(h_bgr_in_, h_bgr, npix_ * 3);
+    memcpy(h_depth_in_, h_depth, npix_ * 4);
+    if (d_bgr) DR_HIP(hipMemcpyAsync(d_bgr, h_bgr_in_, npix_ * 3, hipMemcpyHostToDevice, int_stream_));
+    DR_HIP(hipMemcpyAsync(d_depth, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
+  }
+
+  // A depth frame located in the map this engine holds (the rule: pose_host.h locate_pixel / align_point; DESIGN.md §7c "Locating a
+  // depth frame in the map").  The map is read where it lives, through find_block; nothing of it is uploaded, changed or allocated.
+  // with_locate does what both calls share -- the prologue, device scratch that is sized once -- and hands body an evaluator:
+  // k_map_locate + k_align_fold on int_stream_, 28 doubles and 4 counters back through the pinned pair.
+  template <class Body>
+  void with_locate(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_locate_options_t *opt, Body &&body) {
+    locate_reset();
+    LocateOpt lo;
+    frame_prologue(who, locate_options(opt, o_.truncation_distance, lo), pose16, nullptr);
+    const FrameGrid fg = frame_grid(lo.step);
+    const LocateGrid &lg = fg.lg;
+    const int total = fg.total, groups = fg.groups;
+    double *partial = nullptr;
+    unsigned long long *counts = nullptr;
+    float *mine = nullptr;  // a host-given depth image
+    carve(lc_buf_, int_stream_, [&](Carver &c) {
+      partial = c.take<double>(fg.max_groups * 28);
+      counts = c.take<unsigned long long>(4);
+      mine = c.take<float>(npix_);
+    });
     mio_.ensure(1);
-    double *partial = (double *)lc_buf_.get();
-    unsigned long long *counts = (unsigned long long *)(partial + max_groups * 28);
     // Map scope (drf_set_locate_scope): the stored blocks an evaluation at the pose can read go through the render's staging, rs_
     // -- no render reads it here: the call is legal only where a scan is, and the device is idle.  A staging serves the poses that
     // follow while locate_stage_serves says so; a pose beyond that selects and stages again.  With an empty store or an empty
@@ -1569,9 +1597,7 @@ class FusionEngine {
     }
     const float *depth = (const float *)d_depth;
     if (h_depth) {
-      float *mine = (float *)(counts + 4);
-      memcpy(h_depth_in_, h_depth, npix_ * 4);
-      DR_HIP(hipMemcpyAsync(mine, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
+      upload_frame(nullptr, h_depth, nullptr, mine);
       depth = mine;
     }
     lc_stats_[0] = (uint64_t)total; lc_stats_[4] = lc_buf_.capacity(); lc_stats_[5] = store_.size();
@@ -1655,7 +1681,7 @@ class FusionEngine {
                             std::to_string(store_.size()) + " blocks are in the host store" +
                             (locate_scope_ == DRF_LOCATE_MAP ? ", " + std::to_string((unsigned long long)ls_stats_[1]) + " of them staged" : std::string()) + ")");
   }
-  void locate_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = lc_stats_[i]; }
+  const uint64_t *locate_stats() const { return lc_stats_; }
   // DRF_LOCATE_RESIDENT: drf_locate_* read the pool (the default); DRF_LOCATE_MAP: the pool and the host store together.
   // stage_capacity_blocks bounds what one evaluation may stage (0 = the render's default); rs_ holds the larger of the two needs.
   void set_locate_scope(int scope, size_t stage_capacity_blocks) {
@@ -1669,251 +1695,157 @@ class FusionEngine {
     for (int i = 0; i < 4; ++i) out[i] = ls_stats_[i];
   }
 
-  // A depth frame tracked against the ray-cast model (the rule: fusion_host.h track_normal / track_point / track_loop; DESIGN.md §7c
-  // "Tracking a depth frame against the ray-cast model").  with_track does what the calls share -- the refusals in their order,
-  // pending work settled, device scratch that is sized once: partial sums | 4 counters | the ray-cast's flag counter | model map |
-  // model depth | the frame -- and hands body an evaluator: k_track + k_align_fold on int_stream_.  The model's render goes through
-  // the engine's one submit (render_passes) on int_stream_ into that scratch: depth into `model depth`; the colour image and, in a
-  // banded render, the per-pixel ray state, which nobody reads afterwards, into the bytes k_track_model then overwrites with the
-  // model map.  renders_, free_slot_, next_ and the render statistics are not touched.
-  struct TrackBufs { double *partial; unsigned long long *counts; int *flag; TrackPixel *map; float *model, *frame; const float *depth; };
-  template <class Body>
-  void with_track(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const float *model_pose16, const drf_track_options_t *opt,
-                  Body &&body) {
-    track_reset();
-    TrackOpt to;
-    if (const char *bad = track_options(opt, o_.voxel_size, to)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
-    expect_integrate(who);
-    if (st_radius_ <= 0.0f && !store_.empty())
-      fail(DR_ERR_PROTOCOL, "%s: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", who, store_.size());
-    if (const char *why = transform_pose_fault(pose16)) fail(DR_ERR_ARG, "%s: the pose %s", who, why);
-    if (model_pose16)
-      if (const char *why = transform_pose_fault(model_pose16)) fail(DR_ERR_ARG, "%s: the model pose %s", who, why);
-    settle();  // behind any pending scan; the pinned buffers are idle and every eviction is in the host store
-    const LocateGrid lg = locate_grid(o_, to.step);
-    const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
-    const size_t max_groups = (npix_ + 511) / 512;  // step = 1
-    const size_t head = max_groups * 224 + 32 + 32;  // a multiple of 32: the model map is 16-byte aligned
-    tk_buf_.reserve(head + npix_ * 24, int_stream_);
-    mio_.ensure(1);
-    TrackBufs b;
-    b.partial = (double *)tk_buf_.get();
-    b.counts = (unsigned long long *)(b.partial + max_groups * 28);
-    b.flag = (int *)(b.counts + 4);
-    b.map = (TrackPixel *)(tk_buf_.get() + head);
-    b.model = (float *)(b.map + npix_);
-    b.frame = b.model + npix_;
-    b.depth = (const float *)d_depth;
-    if (h_depth) {
-      memcpy(h_depth_in_, h_depth, npix_ * 4);
-      DR_HIP(hipMemcpyAsync(b.frame, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
-      b.depth = b.frame;
-    }
-    tk_stats_[0] = (uint64_t)total; tk_stats_[5] = tk_buf_.capacity();
-    auto eval = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t c4[4]) {
-      const TrackModel tm = track_model(mp16, to, o_.voxel_size, b.map);
-      mio_.evaluate(b.partial, groups, b.counts, 4, sums, c4, [&] {
-        hipLaunchKernelGGL(k_track, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, b.depth, lg, e, tm, groups, total, b.partial, b.counts);
-        DR_HIP(hipGetLastError());
-      });
-      tk_stats_[1] = c4[0]; tk_stats_[2] = c4[1]; ++tk_stats_[3];
-    };
-    try {
-      body(to, lg, b, eval);
-    } catch (...) {
-      track_reset();
-      throw;
-    }
-  }
-  void track_system(const char *who, const float *h_depth, const float *h_model, const void *d_depth, const void *d_model, const float *model_pose16,
-                    const float *pose16, const drf_track_options_t *opt, double *sums, uint64_t *counts) {
-    track_reset();
-    if (!(h_depth || d_depth) || !(h_model || d_model) || !model_pose16 || !pose16 || !sums || !counts) fail(DR_ERR_ARG, "%s: null argument", who);
-    with_track(who, h_depth, d_depth, pose16, model_pose16, opt, [&](const TrackOpt &to, const LocateGrid &lg, const TrackBufs &b, auto &eval) {
-      const float *model = (const float *)d_model;
-      if (h_model) {
-        DR_HIP(hipStreamSynchronize(int_stream_));  // the frame has left the pinned buffer
-        memcpy(h_depth_in_, h_model, npix_ * 4);
-        DR_HIP(hipMemcpyAsync(b.model, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
-        model = b.model;
-      }
-      hipLaunchKernelGGL(k_track_model, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, model, lg, to.max_jump, b.map);
-      DR_HIP(hipGetLastError());
-      double c_src[3];
-      locate_centre_src(to.centre_depth, o_.voxel_size, c_src);
-      eval(align_eval(map_motion(pose16, o_.voxel_size), c_src, to.a, o_.voxel_size), model_pose16, sums, counts);
+  // A frame tracked against the ray-cast model, by its depth alone (F = TrackGeometric, drf_track_*; DESIGN.md §7c "Tracking a depth
+  // frame against the ray-cast model") or with the photometric term (F = TrackWithColour, drf_track_colour_*; "Tracking with
+  // colour").  The rule: pose_host.h track_normal / track_point / track_colour_point / track_loop.  One path for both; what differs
+  // is decided by F at compile time: the options, the scratch and statistics (tk_ or tc_: the colour calls leave drf_track_stats
+  // and its buffer what they were), the kernels, and the fifth counter -- k_align_fold hands back four; the photometric terms
+  // added leave through a pinned word.
+  // with_track does what the calls share -- the prologue, device scratch that is sized once -- and hands body the resolved options,
+  // the spans, an evaluator (k_track or k_track_colour + k_align_fold on int_stream_) and the model kernel's launch.  The model's
+  // render goes through the engine's one submit (render_passes) on int_stream_ into the scratch; renders_, free_slot_, next_ and
+  // the render statistics are not touched.
+  struct TrackSide {
+    DeviceBuf<unsigned char> buf;            // sized once
+    uint64_t stats[6] = {0, 0, 0, 0, 0, 0};  // drf_track_stats / drf_track_colour_stats
+    Render render{};                         // the *_frame call's model render: int_stream_ and pointers into buf
+    void reset() { for (auto &v : stats) v = 0; }
+  };
+  struct TrackBufs {
+    double *partial; unsigned long long *counts; int *flag; TrackPixel *map; float *model, *Ym, *frame; unsigned char *model_bgr, *frame_bgr;  // the spans
+    unsigned char *render_bgr; RayState *render_band;  // where the model's render puts its colour image and a banded render's ray state
+    const float *depth; const unsigned char *bgr;      // the frame: the caller's device images, or the spans a host frame went to
+  };
+  template <class F>
+  TrackSide &track_side() { return F::N == 5 ? tc_ : tk_; }
+  // the frame's images (colour: both of them) on the host, or on the device
+  template <class F>
+  static bool track_has(const void *bgr, const void *depth) { return depth && (F::N == 4 || bgr); }
+  template <class F, class Body>
+  void with_track(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16, const float *model_pose16,
+                  const typename F::Options *opt, Body &&body) {
+    constexpr bool colour = F::N == 5;
+    TrackSide &s = track_side<F>();
+    s.reset();
+    typename F::Opt to;
+    frame_prologue(who, F::options(opt, o_.voxel_size, to), pose16, model_pose16);
+    const TrackOpt &geo = F::geo(to);
+    const FrameGrid fg = frame_grid(geo.step);
+    TrackBufs b{};
+    carve(s.buf, int_stream_, [&](Carver &c) {
+      b.partial = c.take<double>(fg.max_groups * 28);
+      b.counts = c.take<unsigned long long>(colour ? 6 : 4);  // four that k_align_fold hands back; with colour the fifth (and one unused)
+      b.flag = c.take<int>(1);                                // the ray-cast's flag counter
+      b.map = c.take<TrackPixel>(npix_, 32);                  // the model map
+      b.model = c.take<float>(npix_);                         // the model's depth: rendered, or a host-given one
+      if (colour) b.Ym = c.take<float>(npix_);
+      b.frame = c.take<float>(npix_);                         // a host-given frame
+      if (colour) { b.model_bgr = c.take<unsigned char>(npix_ * 3); b.frame_bgr = c.take<unsigned char>(npix_ * 3); }
+      // The one aliasing: what of a render nobody reads once the model kernel runs lies in the bytes that kernel then overwrites
+      // with the model map -- a banded render's per-pixel ray state, and in the geometric call the colour image too (with colour
+      // k_track_model_colour reads it: it has the span model_bgr).
+      b.render_bgr = colour ? b.model_bgr : (unsigned char *)b.map;
+      b.render_band = (RayState *)(colour ? (unsigned char *)b.map : (unsigned char *)b.map + npix_ * 8);
     });
-  }
-  // returns what dr_last_error() says after a tracking that ran but found no pose (empty otherwise)
-  std::string track_frame(const char *who, const float *h_depth, const void *d_depth, const float *pose16, const drf_track_options_t *opt, float *pose16_out,
-                          drf_align_result_t *res) {
-    track_reset();
-    if (!(h_depth || d_depth) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
-    drf_align_result_t r;
-    uint64_t c4[4] = {0, 0, 0, 0};
-    with_track(who, h_depth, d_depth, pose16, nullptr, opt, [&](const TrackOpt &to, const LocateGrid &lg, const TrackBufs &b, auto &eval) {
-      if (!track_render_.cast) { track_render_.cast = own_.event(); track_render_.done = own_.event(); }
-      track_render_.stream = int_stream_;
-      track_render_.d_bgr = (unsigned char *)b.map;
-      track_render_.d_band = (RayState *)((unsigned char *)b.map + npix_ * 8);
-      track_render_.d_depth = b.model;
-      track_render_.d_flag = b.flag;
-      auto render = [&](const float *p16) {
-        RenderStagePlan plan;
-        RenderBandPlan bands;
-        bool waited = false;
-        const float *poses[1] = {p16};
-        if (render_scope_ == DRF_RENDER_MAP) plan_render_call(who, poses, 1, plan, bands, waited);
-        render_passes(plan, bands, &track_render_, poses, 1, false);
-        hipLaunchKernelGGL(k_track_model, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, (const float *)b.model, lg, to.max_jump, b.map);
-        DR_HIP(hipGetLastError());
-        ++tk_stats_[4];
-      };
-      track_loop(render, eval, pose16, to, o_.voxel_size, r, c4);
-    });
-    for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
-    if (res) *res = r;
-    return no_pose_note(std::string(who) + ": the tracking", r,
-                        ", " + std::to_string((unsigned long long)c4[2]) + " unassociated, " + std::to_string((unsigned long long)c4[3]) + " rejected; " +
-                            std::to_string((unsigned long long)tk_stats_[4]) + " renders; " + std::to_string(store_.size()) + " blocks are in the host store)");
-  }
-  void track_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = tk_stats_[i]; }
-
-  // The same with the photometric term (the rule: fusion_host.h track_photo_term / track_colour_point; DESIGN.md §7c "Tracking with
-  // colour").  with_track_colour is with_track for these calls: the same refusals in the same order, a scratch of its own that is
-  // sized once -- partial sums | 5 counters and the ray-cast's flag counter (64 bytes) | model map | model depth | Ym | the frame's
-  // depth | model colour | the frame's colour -- so that tk_buf_ and drf_track_stats stay what they were.  The render's colour image
-  // is read by k_track_model_colour and has bytes of its own; the banded render's ray state, which nobody reads afterwards, still
-  // goes where the model map is then written.  k_align_fold hands back four counters; the fifth leaves through a pinned word.
-  struct TrackColourBufs { double *partial; unsigned long long *counts; int *flag; TrackPixel *map; float *model, *Ym, *frame; unsigned char *model_bgr, *frame_bgr;
-                           const float *depth; const unsigned char *bgr; };
-  template <class Body>
-  void with_track_colour(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
-                         const float *model_pose16, const drf_track_colour_options_t *opt, Body &&body) {
-    track_colour_reset();
-    TrackColourOpt to;
-    if (const char *bad = track_colour_options(opt, o_.voxel_size, to)) fail(DR_ERR_ARG, "%s: option %s is negative or not finite", who, bad);
-    expect_integrate(who);
-    if (st_radius_ <= 0.0f && !store_.empty())
-      fail(DR_ERR_PROTOCOL, "%s: %zu blocks are in the host store while streaming is off; bring them back with drf_stream_in_region first", who, store_.size());
-    if (const char *why = transform_pose_fault(pose16)) fail(DR_ERR_ARG, "%s: the pose %s", who, why);
-    if (model_pose16)
-      if (const char *why = transform_pose_fault(model_pose16)) fail(DR_ERR_ARG, "%s: the model pose %s", who, why);
-    settle();  // behind any pending scan; the pinned buffers are idle and every eviction is in the host store
-    const LocateGrid lg = locate_grid(o_, to.t.step);
-    const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
-    const size_t max_groups = (npix_ + 511) / 512;  // step = 1
-    const size_t head = max_groups * 224 + 64;      // a multiple of 32: the model map is 16-byte aligned
-    tc_buf_.reserve(head + npix_ * 34, int_stream_);
-    if (!tc_fifth_) tc_fifth_ = own_.pinned<unsigned long long>(1);
+    if (colour && !tc_fifth_) tc_fifth_ = own_.pinned<unsigned long long>(1);
     mio_.ensure(1);
-    TrackColourBufs b;
-    b.partial = (double *)tc_buf_.get();
-    b.counts = (unsigned long long *)(b.partial + max_groups * 28);
-    b.flag = (int *)(b.counts + 6);
-    b.map = (TrackPixel *)(tc_buf_.get() + head);
-    b.model = (float *)(b.map + npix_);
-    b.Ym = b.model + npix_;
-    b.frame = b.Ym + npix_;
-    b.model_bgr = (unsigned char *)(b.frame + npix_);
-    b.frame_bgr = b.model_bgr + npix_ * 3;
     b.depth = (const float *)d_depth;
     b.bgr = (const unsigned char *)d_bgr;
-    if (h_depth) {  // the frame goes through the pinned input buffers as a scan's does
-      memcpy(h_bgr_in_, h_bgr, npix_ * 3);
-      memcpy(h_depth_in_, h_depth, npix_ * 4);
-      DR_HIP(hipMemcpyAsync(b.frame_bgr, h_bgr_in_, npix_ * 3, hipMemcpyHostToDevice, int_stream_));
-      DR_HIP(hipMemcpyAsync(b.frame, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
+    if (h_depth) {
+      upload_frame(h_bgr, h_depth, b.frame_bgr, b.frame);
       b.depth = b.frame;
       b.bgr = b.frame_bgr;
     }
-    tc_stats_[0] = (uint64_t)total; tc_stats_[5] = tc_buf_.capacity();
-    auto eval = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t c5[5]) {
-      const TrackModel tm = track_model(mp16, to.t, o_.voxel_size, b.map);
-      const TrackColour tc = track_colour(to, b.Ym);
-      mio_.evaluate(b.partial, groups, b.counts, 4, sums, c5, [&] {
-        DR_HIP(hipMemsetAsync(b.counts + 4, 0, 8, int_stream_));
-        hipLaunchKernelGGL(k_track_colour, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, b.depth, b.bgr, lg, e, tm, tc, groups, total, b.partial, b.counts);
-        DR_HIP(hipGetLastError());
-        DR_HIP(hipMemcpyAsync(tc_fifth_, b.counts + 4, 8, hipMemcpyDeviceToHost, int_stream_));
+    s.stats[0] = (uint64_t)fg.total; s.stats[5] = s.buf.capacity();
+    auto model = [&](const float *depth_m, const unsigned char *bgr_m) {  // the model map (and Ym) of one model image
+      if constexpr (colour) hipLaunchKernelGGL(k_track_model_colour, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, depth_m, bgr_m, fg.lg, geo.max_jump, b.map, b.Ym);
+      else hipLaunchKernelGGL(k_track_model, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, depth_m, fg.lg, geo.max_jump, b.map);
+      DR_HIP(hipGetLastError());
+    };
+    auto eval = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t *c) {  // c[F::N]
+      const TrackModel tm = track_model(mp16, geo, o_.voxel_size, b.map);
+      mio_.evaluate(b.partial, fg.groups, b.counts, 4, sums, c, [&] {
+        if constexpr (colour) {
+          DR_HIP(hipMemsetAsync(b.counts + 4, 0, 8, int_stream_));
+          hipLaunchKernelGGL(k_track_colour, dim3(cdiv(fg.groups, 4)), dim3(256), 0, int_stream_, b.depth, b.bgr, fg.lg, e, tm, track_colour(to, b.Ym), fg.groups, fg.total,
+                             b.partial, b.counts);
+          DR_HIP(hipGetLastError());
+          DR_HIP(hipMemcpyAsync(tc_fifth_, b.counts + 4, 8, hipMemcpyDeviceToHost, int_stream_));
+        } else {
+          hipLaunchKernelGGL(k_track, dim3(cdiv(fg.groups, 4)), dim3(256), 0, int_stream_, b.depth, fg.lg, e, tm, fg.groups, fg.total, b.partial, b.counts);
+          DR_HIP(hipGetLastError());
+        }
       });
-      c5[4] = *tc_fifth_;
-      tc_stats_[1] = c5[0]; tc_stats_[2] = c5[1]; ++tc_stats_[3];
+      if constexpr (colour) c[4] = *tc_fifth_;
+      s.stats[1] = c[0]; s.stats[2] = c[1]; ++s.stats[3];
     };
     try {
-      body(to, lg, b, eval);
+      body(geo, b, eval, model);
     } catch (...) {
-      track_colour_reset();
+      s.reset();
       throw;
     }
   }
-  void track_colour_system(const char *who, const uint8_t *h_bgr, const float *h_depth, const uint8_t *h_model_bgr, const float *h_model, const void *d_bgr,
-                           const void *d_depth, const void *d_model_bgr, const void *d_model, const float *model_pose16, const float *pose16,
-                           const drf_track_colour_options_t *opt, double *sums, uint64_t *counts) {
-    track_colour_reset();
-    if (!((h_bgr && h_depth) || (d_bgr && d_depth)) || !((h_model_bgr && h_model) || (d_model_bgr && d_model)) || !model_pose16 || !pose16 || !sums || !counts)
+  // one evaluation against a model image the caller gives (geometric: every bgr argument is null)
+  template <class F>
+  void track_system(const char *who, const uint8_t *h_bgr, const float *h_depth, const uint8_t *h_model_bgr, const float *h_model, const void *d_bgr, const void *d_depth,
+                    const void *d_model_bgr, const void *d_model, const float *model_pose16, const float *pose16, const typename F::Options *opt, double *sums,
+                    uint64_t *counts) {
+    track_side<F>().reset();
+    if (!(track_has<F>(h_bgr, h_depth) || track_has<F>(d_bgr, d_depth)) || !(track_has<F>(h_model_bgr, h_model) || track_has<F>(d_model_bgr, d_model)) || !model_pose16 ||
+        !pose16 || !sums || !counts)
       fail(DR_ERR_ARG, "%s: null argument", who);
-    with_track_colour(who, h_bgr, h_depth, d_bgr, d_depth, pose16, model_pose16, opt,
-                      [&](const TrackColourOpt &to, const LocateGrid &lg, const TrackColourBufs &b, auto &eval) {
-      const float *model = (const float *)d_model;
-      const unsigned char *model_bgr = (const unsigned char *)d_model_bgr;
+    with_track<F>(who, h_bgr, h_depth, d_bgr, d_depth, pose16, model_pose16, opt, [&](const TrackOpt &geo, const TrackBufs &b, auto &eval, auto &model) {
       if (h_model) {
-        DR_HIP(hipStreamSynchronize(int_stream_));  // the frame has left the pinned buffers
-        memcpy(h_bgr_in_, h_model_bgr, npix_ * 3);
-        memcpy(h_depth_in_, h_model, npix_ * 4);
-        DR_HIP(hipMemcpyAsync(b.model_bgr, h_bgr_in_, npix_ * 3, hipMemcpyHostToDevice, int_stream_));
-        DR_HIP(hipMemcpyAsync(b.model, h_depth_in_, npix_ * 4, hipMemcpyHostToDevice, int_stream_));
-        model = b.model;
-        model_bgr = b.model_bgr;
+        upload_frame(h_model_bgr, h_model, b.model_bgr, b.model, true);
+        model(b.model, b.model_bgr);
+      } else {
+        model((const float *)d_model, (const unsigned char *)d_model_bgr);
       }
-      hipLaunchKernelGGL(k_track_model_colour, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, model, model_bgr, lg, to.t.max_jump, b.map, b.Ym);
-      DR_HIP(hipGetLastError());
       double c_src[3];
-      locate_centre_src(to.t.centre_depth, o_.voxel_size, c_src);
-      eval(align_eval(map_motion(pose16, o_.voxel_size), c_src, to.t.a, o_.voxel_size), model_pose16, sums, counts);
+      locate_centre_src(geo.centre_depth, o_.voxel_size, c_src);
+      eval(align_eval(map_motion(pose16, o_.voxel_size), c_src, geo.a, o_.voxel_size), model_pose16, sums, counts);
     });
   }
   // returns what dr_last_error() says after a tracking that ran but found no pose (empty otherwise)
-  std::string track_colour_frame(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
-                                 const drf_track_colour_options_t *opt, float *pose16_out, drf_align_result_t *res) {
-    track_colour_reset();
-    if (!((h_bgr && h_depth) || (d_bgr && d_depth)) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+  template <class F>
+  std::string track_frame(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
+                          const typename F::Options *opt, float *pose16_out, drf_align_result_t *res) {
+    TrackSide &s = track_side<F>();
+    s.reset();
+    if (!(track_has<F>(h_bgr, h_depth) || track_has<F>(d_bgr, d_depth)) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
     drf_align_result_t r;
-    uint64_t c5[5] = {0, 0, 0, 0, 0};
-    with_track_colour(who, h_bgr, h_depth, d_bgr, d_depth, pose16, nullptr, opt,
-                      [&](const TrackColourOpt &to, const LocateGrid &lg, const TrackColourBufs &b, auto &eval) {
-      if (!track_colour_render_.cast) { track_colour_render_.cast = own_.event(); track_colour_render_.done = own_.event(); }
-      track_colour_render_.stream = int_stream_;
-      track_colour_render_.d_bgr = b.model_bgr;
-      track_colour_render_.d_band = (RayState *)b.map;
-      track_colour_render_.d_depth = b.model;
-      track_colour_render_.d_flag = b.flag;
+    uint64_t c[F::N] = {};
+    with_track<F>(who, h_bgr, h_depth, d_bgr, d_depth, pose16, nullptr, opt, [&](const TrackOpt &geo, const TrackBufs &b, auto &eval, auto &model) {
+      if (!s.render.cast) { s.render.cast = own_.event(); s.render.done = own_.event(); }
+      s.render.stream = int_stream_;
+      s.render.d_bgr = b.render_bgr;
+      s.render.d_band = b.render_band;
+      s.render.d_depth = b.model;
+      s.render.d_flag = b.flag;
       auto render = [&](const float *p16) {
         RenderStagePlan plan;
         RenderBandPlan bands;
         bool waited = false;
         const float *poses[1] = {p16};
         if (render_scope_ == DRF_RENDER_MAP) plan_render_call(who, poses, 1, plan, bands, waited);
-        render_passes(plan, bands, &track_colour_render_, poses, 1, false);
-        hipLaunchKernelGGL(k_track_model_colour, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, (const float *)b.model, (const unsigned char *)b.model_bgr, lg,
-                           to.t.max_jump, b.map, b.Ym);
-        DR_HIP(hipGetLastError());
-        ++tc_stats_[4];
+        render_passes(plan, bands, &s.render, poses, 1, false);
+        model(b.model, b.model_bgr);
+        ++s.stats[4];
       };
-      track_colour_loop(render, eval, pose16, to, o_.voxel_size, r, c5);
+      track_loop<F::N>(render, eval, pose16, geo, o_.voxel_size, r, c);
     });
     for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
     if (res) *res = r;
     return no_pose_note(std::string(who) + ": the tracking", r,
-                        ", " + std::to_string((unsigned long long)c5[2]) + " unassociated, " + std::to_string((unsigned long long)c5[3]) + " rejected, " +
-                            std::to_string((unsigned long long)c5[4]) + " with a colour term; " + std::to_string((unsigned long long)tc_stats_[4]) + " renders; " +
-                            std::to_string(store_.size()) + " blocks are in the host store)");
+                        ", " + std::to_string((unsigned long long)c[2]) + " unassociated, " + std::to_string((unsigned long long)c[3]) + " rejected" +
+                            (F::N == 5 ? ", " + std::to_string((unsigned long long)c[F::N - 1]) + " with a colour term; " : std::string("; ")) +
+                            std::to_string((unsigned long long)s.stats[4]) + " renders; " + std::to_string(store_.size()) + " blocks are in the host store)");
   }
-  void track_colour_stats(uint64_t out[6]) const { for (int i = 0; i < 6; ++i) out[i] = tc_stats_[i]; }
+  const uint64_t *track_stats() const { return tk_.stats; }
+  const uint64_t *track_colour_stats() const { return tc_.stats; }
 
  private:
-  void track_reset() { for (auto &v : tk_stats_) v = 0; }
-  void track_colour_reset() { for (auto &v : tc_stats_) v = 0; }
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
   size_t host_free() const { return st_host_cap_ - std::min(st_host_cap_, store_.size()); }
@@ -2506,13 +2438,8 @@ class FusionEngine {
   uint64_t mg_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_merge_stats
   DeviceBuf<unsigned char> lc_buf_;            // drf_locate_*: partial sums, counters and a host-given depth image (sized once)
   uint64_t lc_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_locate_stats
-  DeviceBuf<unsigned char> tk_buf_;            // drf_track_*: partial sums, counters, model map, model depth and a host-given frame (sized once)
-  uint64_t tk_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_track_stats
-  Render track_render_{};                      // drf_track_frame's model render: int_stream_ and pointers into tk_buf_
-  DeviceBuf<unsigned char> tc_buf_;            // drf_track_colour_*: tk_buf_'s parts, the model's and the frame's colour and Ym (sized once)
-  uint64_t tc_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_track_colour_stats
-  unsigned long long *tc_fifth_ = nullptr;     // pinned: the fifth counter of an evaluation
-  Render track_colour_render_{};               // drf_track_colour_frame's model render: int_stream_ and pointers into tc_buf_
+  TrackSide tk_, tc_;                          // drf_track_*, drf_track_colour_*: each its own scratch, statistics and model render (with_track)
+  unsigned long long *tc_fifth_ = nullptr;     // pinned: the fifth counter of an evaluation with colour
   int locate_scope_ = DRF_LOCATE_RESIDENT;     // drf_set_locate_scope
   size_t lc_cap_req_ = 0;
   uint64_t ls_stats_[4] = {0, 0, 0, 0};        // drf_locate_stage_stats
@@ -2529,6 +2456,23 @@ struct drf_s {
 static inline dr::FusionEngine *eng(drf_s *h) {
   if (!h || !h->e) dr::fail(DR_ERR_ARG, "NULL handle");
   return h->e.get();
+}
+// A search for a pose (drf_align_map, drf_*_frame): DEGENERATE and LOST are results, not failures -- DR_OK, with the reason, the note
+// call() returns, where a failure's message would be.
+template <class Call>
+static int guarded_note(Call &&call) {
+  std::string note;
+  const int rc = guarded([&] { note = call(); });
+  if (rc == DR_OK && !note.empty()) dr::last_error_slot() = note;
+  return rc;
+}
+// the six statistics of an operation's last call, through the engine's getter
+static int stats6(drf_s *h, const char *who, uint64_t *out, const uint64_t *(dr::FusionEngine::*get)() const) {
+  return guarded([&] {
+    if (!out) dr::fail(DR_ERR_ARG, "%s: null argument", who);
+    const uint64_t *s = (eng(h)->*get)();
+    for (int i = 0; i < 6; ++i) out[i] = s[i];
+  });
 }
 
 extern "C" {
@@ -2685,110 +2629,78 @@ int drf_map_info(const char *path, float *voxel_size, uint64_t *n_blocks) {
 int drf_save_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->save_map(path, chunk_blocks); }); }
 int drf_load_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->load_map(path, chunk_blocks); }); }
 int drf_merge_map(drf_t *h, const char *path, size_t chunk_blocks) { return guarded([&] { eng(h)->merge_map(path, chunk_blocks); }); }
-int drf_merge_stats(drf_t *h, uint64_t out[6]) {
-  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_merge_stats: null argument"); eng(h)->merge_stats(out); });
-}
+int drf_merge_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_merge_stats", out, &dr::FusionEngine::merge_stats); }
 int drf_transform_map(drf_t *h, const char *src_path, const float T16[16], const char *dst_path, size_t chunk_blocks) {
   return guarded([&] { eng(h)->transform_map(src_path, T16, dst_path, chunk_blocks); });
 }
-int drf_transform_stats(drf_t *h, uint64_t out[6]) {
-  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_transform_stats: null argument"); eng(h)->transform_stats(out); });
-}
+int drf_transform_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_transform_stats", out, &dr::FusionEngine::transform_stats); }
 int drf_align_system(drf_t *h, const char *src_path, const char *ref_path, const float T16[16], const drf_align_options_t *opt, double sums[28],
                      uint64_t counts[3]) {
   return guarded([&] { eng(h)->align_system(src_path, ref_path, T16, opt, sums, counts); });
 }
 int drf_align_map(drf_t *h, const char *src_path, const char *ref_path, const float T_init16[16], const drf_align_options_t *opt, float T16_out[16],
                   drf_align_result_t *res) {
-  // DEGENERATE and LOST are results, not failures: DR_OK, with the reason where a failure's message would be
-  std::string note;
-  const int rc = guarded([&] { note = eng(h)->align_map(src_path, ref_path, T_init16, opt, T16_out, res); });
-  if (rc == DR_OK && !note.empty()) dr::last_error_slot() = note;
-  return rc;
+  return guarded_note([&] { return eng(h)->align_map(src_path, ref_path, T_init16, opt, T16_out, res); });
 }
-int drf_align_stats(drf_t *h, uint64_t out[6]) {
-  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_align_stats: null argument"); eng(h)->align_stats(out); });
-}
+int drf_align_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_align_stats", out, &dr::FusionEngine::align_stats); }
 int drf_locate_system(drf_t *h, const float *depth, const float pose16[16], const drf_locate_options_t *opt, double sums[28], uint64_t counts[4]) {
   return guarded([&] { eng(h)->locate_system("drf_locate_system", depth, nullptr, pose16, opt, sums, counts); });
 }
 int drf_locate_system_device(drf_t *h, const void *d_depth, const float pose16[16], const drf_locate_options_t *opt, double sums[28], uint64_t counts[4]) {
   return guarded([&] { eng(h)->locate_system("drf_locate_system_device", nullptr, d_depth, pose16, opt, sums, counts); });
 }
-// DEGENERATE and LOST are results, not failures: DR_OK, with the reason where a failure's message would be (as drf_align_map)
-static int locate_frame_call(drf_t *h, const char *who, const float *depth, const void *d_depth, const float *pose_init16, const drf_locate_options_t *opt,
-                             float *pose16_out, drf_align_result_t *res) {
-  std::string note;
-  const int rc = guarded([&] { note = eng(h)->locate_frame(who, depth, d_depth, pose_init16, opt, pose16_out, res); });
-  if (rc == DR_OK && !note.empty()) dr::last_error_slot() = note;
-  return rc;
-}
 int drf_locate_frame(drf_t *h, const float *depth, const float pose_init16[16], const drf_locate_options_t *opt, float pose16_out[16], drf_align_result_t *res) {
-  return locate_frame_call(h, "drf_locate_frame", depth, nullptr, pose_init16, opt, pose16_out, res);
+  return guarded_note([&] { return eng(h)->locate_frame("drf_locate_frame", depth, nullptr, pose_init16, opt, pose16_out, res); });
 }
 int drf_locate_frame_device(drf_t *h, const void *d_depth, const float pose_init16[16], const drf_locate_options_t *opt, float pose16_out[16],
                             drf_align_result_t *res) {
-  return locate_frame_call(h, "drf_locate_frame_device", nullptr, d_depth, pose_init16, opt, pose16_out, res);
+  return guarded_note([&] { return eng(h)->locate_frame("drf_locate_frame_device", nullptr, d_depth, pose_init16, opt, pose16_out, res); });
 }
-int drf_locate_stats(drf_t *h, uint64_t out[6]) {
-  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_locate_stats: null argument"); eng(h)->locate_stats(out); });
-}
+int drf_locate_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_locate_stats", out, &dr::FusionEngine::locate_stats); }
 int drf_track_system(drf_t *h, const float *depth, const float *model_depth, const float model_pose16[16], const float pose16[16], const drf_track_options_t *opt,
                      double sums[28], uint64_t counts[4]) {
-  return guarded([&] { eng(h)->track_system("drf_track_system", depth, model_depth, nullptr, nullptr, model_pose16, pose16, opt, sums, counts); });
+  return guarded([&] {
+    eng(h)->track_system<dr::TrackGeometric>("drf_track_system", nullptr, depth, nullptr, model_depth, nullptr, nullptr, nullptr, nullptr, model_pose16, pose16, opt, sums, counts);
+  });
 }
 int drf_track_system_device(drf_t *h, const void *d_depth, const void *d_model_depth, const float model_pose16[16], const float pose16[16],
                             const drf_track_options_t *opt, double sums[28], uint64_t counts[4]) {
-  return guarded([&] { eng(h)->track_system("drf_track_system_device", nullptr, nullptr, d_depth, d_model_depth, model_pose16, pose16, opt, sums, counts); });
-}
-static int track_frame_call(drf_t *h, const char *who, const float *depth, const void *d_depth, const float *pose_init16, const drf_track_options_t *opt,
-                            float *pose16_out, drf_align_result_t *res) {
-  std::string note;
-  const int rc = guarded([&] { note = eng(h)->track_frame(who, depth, d_depth, pose_init16, opt, pose16_out, res); });
-  if (rc == DR_OK && !note.empty()) dr::last_error_slot() = note;
-  return rc;
+  return guarded([&] {
+    eng(h)->track_system<dr::TrackGeometric>("drf_track_system_device", nullptr, nullptr, nullptr, nullptr, nullptr, d_depth, nullptr, d_model_depth, model_pose16, pose16, opt,
+                                             sums, counts);
+  });
 }
 int drf_track_frame(drf_t *h, const float *depth, const float pose_init16[16], const drf_track_options_t *opt, float pose16_out[16], drf_align_result_t *res) {
-  return track_frame_call(h, "drf_track_frame", depth, nullptr, pose_init16, opt, pose16_out, res);
+  return guarded_note([&] { return eng(h)->track_frame<dr::TrackGeometric>("drf_track_frame", nullptr, depth, nullptr, nullptr, pose_init16, opt, pose16_out, res); });
 }
 int drf_track_frame_device(drf_t *h, const void *d_depth, const float pose_init16[16], const drf_track_options_t *opt, float pose16_out[16],
                            drf_align_result_t *res) {
-  return track_frame_call(h, "drf_track_frame_device", nullptr, d_depth, pose_init16, opt, pose16_out, res);
+  return guarded_note([&] { return eng(h)->track_frame<dr::TrackGeometric>("drf_track_frame_device", nullptr, nullptr, nullptr, d_depth, pose_init16, opt, pose16_out, res); });
 }
-int drf_track_stats(drf_t *h, uint64_t out[6]) {
-  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_track_stats: null argument"); eng(h)->track_stats(out); });
-}
+int drf_track_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_track_stats", out, &dr::FusionEngine::track_stats); }
 int drf_track_colour_system(drf_t *h, const uint8_t *bgr, const float *depth, const uint8_t *model_bgr, const float *model_depth, const float model_pose16[16],
                             const float pose16[16], const drf_track_colour_options_t *opt, double sums[28], uint64_t counts[5]) {
   return guarded([&] {
-    eng(h)->track_colour_system("drf_track_colour_system", bgr, depth, model_bgr, model_depth, nullptr, nullptr, nullptr, nullptr, model_pose16, pose16, opt, sums, counts);
+    eng(h)->track_system<dr::TrackWithColour>("drf_track_colour_system", bgr, depth, model_bgr, model_depth, nullptr, nullptr, nullptr, nullptr, model_pose16, pose16, opt, sums,
+                                              counts);
   });
 }
 int drf_track_colour_system_device(drf_t *h, const void *d_bgr, const void *d_depth, const void *d_model_bgr, const void *d_model_depth, const float model_pose16[16],
                                    const float pose16[16], const drf_track_colour_options_t *opt, double sums[28], uint64_t counts[5]) {
   return guarded([&] {
-    eng(h)->track_colour_system("drf_track_colour_system_device", nullptr, nullptr, nullptr, nullptr, d_bgr, d_depth, d_model_bgr, d_model_depth, model_pose16, pose16, opt,
-                                sums, counts);
+    eng(h)->track_system<dr::TrackWithColour>("drf_track_colour_system_device", nullptr, nullptr, nullptr, nullptr, d_bgr, d_depth, d_model_bgr, d_model_depth, model_pose16,
+                                              pose16, opt, sums, counts);
   });
-}
-static int track_colour_frame_call(drf_t *h, const char *who, const uint8_t *bgr, const float *depth, const void *d_bgr, const void *d_depth, const float *pose_init16,
-                                   const drf_track_colour_options_t *opt, float *pose16_out, drf_align_result_t *res) {
-  std::string note;
-  const int rc = guarded([&] { note = eng(h)->track_colour_frame(who, bgr, depth, d_bgr, d_depth, pose_init16, opt, pose16_out, res); });
-  if (rc == DR_OK && !note.empty()) dr::last_error_slot() = note;
-  return rc;
 }
 int drf_track_colour_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float pose_init16[16], const drf_track_colour_options_t *opt, float pose16_out[16],
                            drf_align_result_t *res) {
-  return track_colour_frame_call(h, "drf_track_colour_frame", bgr, depth, nullptr, nullptr, pose_init16, opt, pose16_out, res);
+  return guarded_note([&] { return eng(h)->track_frame<dr::TrackWithColour>("drf_track_colour_frame", bgr, depth, nullptr, nullptr, pose_init16, opt, pose16_out, res); });
 }
 int drf_track_colour_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float pose_init16[16], const drf_track_colour_options_t *opt,
                                   float pose16_out[16], drf_align_result_t *res) {
-  return track_colour_frame_call(h, "drf_track_colour_frame_device", nullptr, nullptr, d_bgr, d_depth, pose_init16, opt, pose16_out, res);
+  return guarded_note([&] { return eng(h)->track_frame<dr::TrackWithColour>("drf_track_colour_frame_device", nullptr, nullptr, d_bgr, d_depth, pose_init16, opt, pose16_out, res); });
 }
-int drf_track_colour_stats(drf_t *h, uint64_t out[6]) {
-  return guarded([&] { if (!out) dr::fail(DR_ERR_ARG, "drf_track_colour_stats: null argument"); eng(h)->track_colour_stats(out); });
-}
+int drf_track_colour_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_track_colour_stats", out, &dr::FusionEngine::track_colour_stats); }
 int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_locate_scope(scope, stage_capacity_blocks); }); }
 int drf_locate_stage_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->locate_stage_stats(out); }); }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }

@@ -1,6 +1,7 @@
 // map_ops.h -- the map-file layer of the DrFusion engine (included by dr_fusion.hip after the kernel headers).  One rule: what every
 // map-file operation does the same way is written here once -- MapIo: the pinned chunk pair and the device index buffers, the reader
-// opening, the read pump, the write pump, the evaluator tail of align and locate; CallMemory: device memory of a single call -- and
+// opening, the read pump, the write pump, the evaluator tail of align, locate and track; CallMemory: device memory of a single call;
+// Carver: the layout of a scratch buffer as typed spans in order (drf_locate_*, drf_track_*, drf_track_colour_*) -- and
 // the operations that touch no live map (drf_transform_map, drf_align_system, drf_align_map) live here whole, as functions over
 // MapIo.  save / load / merge / locate read or change the engine's map and stay members of FusionEngine, written over the same pumps.
 // DESIGN.md "Where the map-file operations live" says who waits, who records and who verifies.
@@ -133,6 +134,34 @@ class CallMemory {
  private:
   void *p_ = nullptr;
 };
+
+// Typed spans taken in order from one scratch buffer: the order of the take() calls is the layout, each span at its type's alignment
+// or the one stated.  carve() runs a layout twice -- over no buffer for the size, then, the buffer grown to it (DeviceBuf: never
+// shrunk, 256-byte aligned), over its bytes -- so a layout is written once and its size cannot disagree with it.
+class Carver {
+ public:
+  explicit Carver(unsigned char *base = nullptr) : base_((uintptr_t)base) {}
+  template <class T>
+  T *take(size_t n, size_t align = alignof(T)) {
+    at_ = (at_ + align - 1) / align * align;
+    T *p = (T *)(base_ + at_);
+    at_ += n * sizeof(T);
+    return p;
+  }
+  size_t bytes() const { return at_; }
+
+ private:
+  uintptr_t base_;
+  size_t at_ = 0;
+};
+template <class Layout>
+void carve(DeviceBuf<unsigned char> &buf, hipStream_t stream, Layout &&layout) {
+  Carver size;
+  layout(size);
+  buf.reserve(size.bytes(), stream);
+  Carver spans(buf.get());
+  layout(spans);
+}
 
 // What dr_last_error() says after a registration or refinement that ran but found no pose: `what` (who and which search), how far it
 // got, `rest` (the caller's own figures); empty for every other status.  No fixed buffer: paths of any length must not cut it off.

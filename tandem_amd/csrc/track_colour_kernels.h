@@ -1,5 +1,5 @@
 // track_colour_kernels.h -- drf_track_colour_system / drf_track_colour_frame on the device: the model map and the model intensity
-// map of one render, and one evaluation of the system with the photometric term (the rule: fusion_host.h track_model_intensity /
+// map of one render, and one evaluation of the system with the photometric term (the rule: pose_host.h track_model_intensity /
 // track_photo_term / track_colour_point; DESIGN.md §7c "Tracking with colour").  Included by dr_fusion.hip inside namespace dr,
 // behind track_kernels.h; k_align_fold folds the groups.
 

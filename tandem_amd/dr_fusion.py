@@ -315,13 +315,32 @@ class DrFusion:
         return tuple(int(v) for v in out)
 
     @staticmethod
-    def _align_options(opt):
+    def _options(struct, word, opt):
+        """opt as the options struct of the align / locate / track calls (None: all defaults)"""
         if not opt:
             return None
-        unknown = set(opt) - {f[0] for f in _lib.AlignOptions._fields_}
+        unknown = set(opt) - {f[0] for f in struct._fields_}
         if unknown:
-            raise TypeError("unknown align option(s): %s" % ", ".join(sorted(unknown)))
-        return _lib.AlignOptions(**opt)
+            raise TypeError("unknown %s option(s): %s" % (word, ", ".join(sorted(unknown))))
+        return struct(**opt)
+
+    def _image(self, dtype, channels, image):
+        """An H*W*channels image of the engine's camera, or an integer device pointer to one: (is a device pointer, the argument,
+        what keeps it alive)"""
+        if isinstance(image, (int, np.integer)):
+            return True, C.c_void_p(int(image)), None
+        image = np.ascontiguousarray(image, dtype)
+        assert image.size == self._hw[0] * self._hw[1] * channels
+        return False, fptr(image) if dtype is np.float32 else C.c_void_p(image.ctypes.data), image
+
+    def _align_result(self, r, T32, raise_on_failure):
+        """What align_map, locate_frame, track_frame and track_colour_frame return, or raise as an AlignError that carries it"""
+        res = AlignResult(T=np.array(r.T, np.float64).reshape(4, 4), T32=T32.reshape(4, 4), sums=np.array(r.sums, np.float64), samples=int(r.samples),
+                          valid0=int(r.valid0), valid=int(r.valid), cost0=float(r.cost0), cost=float(r.cost), iterations=int(r.iterations),
+                          status=int(r.status))
+        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
+            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
+        return res
 
     def align_system(self, src, ref, T, **opt):
         """The registration's Gauss-Newton system at the pose T (4x4, row-major, rigid, src-world to ref-world): (sums (28,)
@@ -329,7 +348,7 @@ class DrFusion:
         pose hypothesis -- and valid / samples the overlap.  opt: the fields of drf_align_options_t (include/dr_mi355x.h states
         the rule).  The engine's own map is not touched."""
         T = np.ascontiguousarray(T, np.float32).reshape(16)
-        o = self._align_options(opt)
+        o = self._options(_lib.AlignOptions, "align", opt)
         sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 3)()
         check(self._L.drf_align_system(self._h, os.fsencode(src), os.fsencode(ref), fptr(T), C.byref(o) if o else None,
                                        sums.ctypes.data_as(_lib.f64p), counts))
@@ -341,15 +360,10 @@ class DrFusion:
         refines: T_init must bring the source surface inside the reference's truncation band.  A registration that ends
         ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the result) unless raise_on_failure is false."""
         T = np.ascontiguousarray(np.eye(4) if T_init is None else T_init, np.float32).reshape(16)
-        o = self._align_options(opt)
+        o = self._options(_lib.AlignOptions, "align", opt)
         T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
         check(self._L.drf_align_map(self._h, os.fsencode(src), os.fsencode(ref), fptr(T), C.byref(o) if o else None, fptr(T32), C.byref(r)))
-        res = AlignResult(T=np.array(r.T, np.float64).reshape(4, 4), T32=T32.reshape(4, 4), sums=np.array(r.sums, np.float64), samples=int(r.samples),
-                          valid0=int(r.valid0), valid=int(r.valid), cost0=float(r.cost0), cost=float(r.cost), iterations=int(r.iterations),
-                          status=int(r.status))
-        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
-            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
-        return res
+        return self._align_result(r, T32, raise_on_failure)
 
     def align_stats(self):
         """Last align_system / align_map: (source blocks, reference blocks, samples, valid samples at the last evaluation, system
@@ -359,31 +373,14 @@ class DrFusion:
         return tuple(int(v) for v in out)
 
     # ---- locating a depth frame in the map (include/dr_mi355x.h drf_locate_frame, DESIGN.md "Locating a depth frame in the map") ----
-    @staticmethod
-    def _locate_options(opt):
-        if not opt:
-            return None
-        unknown = set(opt) - {f[0] for f in _lib.LocateOptions._fields_}
-        if unknown:
-            raise TypeError("unknown locate option(s): %s" % ", ".join(sorted(unknown)))
-        return _lib.LocateOptions(**opt)
-
-    def _locate_depth(self, depth):
-        """(is a device pointer, the argument, what keeps it alive)"""
-        if isinstance(depth, (int, np.integer)):
-            return True, C.c_void_p(int(depth)), None
-        depth = np.ascontiguousarray(depth, np.float32)
-        assert depth.size == self._hw[0] * self._hw[1]
-        return False, fptr(depth), depth
-
     def locate_system(self, depth, pose, **opt):
         """The localisation's Gauss-Newton system of the depth image (H*W float32 metres, or an integer device pointer to one) at
         the pose (16 float32, row-major, camera-to-world) against the map this engine holds: (sums (28,) float64, (samples, valid,
         unobserved, outside)).  sums[27] / valid is the mean robust squared residual in voxels^2, the score of a pose hypothesis.
         opt: the fields of drf_locate_options_t.  The map is not touched."""
-        dev, d, keep = self._locate_depth(depth)
+        dev, d, keep = self._image(np.float32, 1, depth)
         pose = np.ascontiguousarray(pose, np.float32).reshape(16)
-        o = self._locate_options(opt)
+        o = self._options(_lib.LocateOptions, "locate", opt)
         sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 4)()
         call = self._L.drf_locate_system_device if dev else self._L.drf_locate_system
         check(call(self._h, d, fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
@@ -395,18 +392,13 @@ class DrFusion:
         pose_init must bring the points inside the truncation band (from farther off, track_frame first).  Only resident blocks are read (locate_stats()[5] counts the
         blocks in the host store) unless set_locate_scope(LOCATE_MAP) was called.  A refinement that ends ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the
         result) unless raise_on_failure is false."""
-        dev, d, keep = self._locate_depth(depth)
+        dev, d, keep = self._image(np.float32, 1, depth)
         pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
-        o = self._locate_options(opt)
+        o = self._options(_lib.LocateOptions, "locate", opt)
         T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
         call = self._L.drf_locate_frame_device if dev else self._L.drf_locate_frame
         check(call(self._h, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
-        res = AlignResult(T=np.array(r.T, np.float64).reshape(4, 4), T32=T32.reshape(4, 4), sums=np.array(r.sums, np.float64), samples=int(r.samples),
-                          valid0=int(r.valid0), valid=int(r.valid), cost0=float(r.cost0), cost=float(r.cost), iterations=int(r.iterations),
-                          status=int(r.status))
-        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
-            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
-        return res
+        return self._align_result(r, T32, raise_on_failure)
 
     def locate_stats(self):
         """Last locate_system / locate_frame: (grid positions, samples, valid samples at the last evaluation, system evaluations,
@@ -430,25 +422,16 @@ class DrFusion:
         return tuple(int(v) for v in out)
 
     # ---- tracking a depth frame against the ray-cast model (include/dr_mi355x.h drf_track_frame, DESIGN.md "Tracking a depth frame") ----
-    @staticmethod
-    def _track_options(opt):
-        if not opt:
-            return None
-        unknown = set(opt) - {f[0] for f in _lib.TrackOptions._fields_}
-        if unknown:
-            raise TypeError("unknown track option(s): %s" % ", ".join(sorted(unknown)))
-        return _lib.TrackOptions(**opt)
-
     def track_system(self, depth, model_depth, model_pose, pose, **opt):
         """One evaluation of the tracking's Gauss-Newton system: the depth image at the pose against model_depth, a ray-cast at
         model_pose (both images H*W float32 metres, or both integer device pointers): (sums (28,) float64, (samples, valid,
         unassociated, rejected)).  opt: the fields of drf_track_options_t.  No map is read."""
-        dev, d, keep = self._locate_depth(depth)
-        mdev, m, mkeep = self._locate_depth(model_depth)
+        dev, d, keep = self._image(np.float32, 1, depth)
+        mdev, m, mkeep = self._image(np.float32, 1, model_depth)
         assert dev == mdev, "both images on the host or both on the device"
         pose = np.ascontiguousarray(pose, np.float32).reshape(16)
         mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
-        o = self._track_options(opt)
+        o = self._options(_lib.TrackOptions, "track", opt)
         sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 4)()
         call = self._L.drf_track_system_device if dev else self._L.drf_track_system
         check(call(self._h, d, m, fptr(mpose), fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
@@ -460,18 +443,13 @@ class DrFusion:
         locate_frame's reach: track first, then locate_frame(depth, result.T32) for the sub-voxel part.  The renders follow
         set_render_scope and set_render_bands; the public render buffers and the map are not touched.  ALIGN_MAX_ITERS is a usable
         pose; ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the result) unless raise_on_failure is false."""
-        dev, d, keep = self._locate_depth(depth)
+        dev, d, keep = self._image(np.float32, 1, depth)
         pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
-        o = self._track_options(opt)
+        o = self._options(_lib.TrackOptions, "track", opt)
         T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
         call = self._L.drf_track_frame_device if dev else self._L.drf_track_frame
         check(call(self._h, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
-        res = AlignResult(T=np.array(r.T, np.float64).reshape(4, 4), T32=T32.reshape(4, 4), sums=np.array(r.sums, np.float64), samples=int(r.samples),
-                          valid0=int(r.valid0), valid=int(r.valid), cost0=float(r.cost0), cost=float(r.cost), iterations=int(r.iterations),
-                          status=int(r.status))
-        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
-            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
-        return res
+        return self._align_result(r, T32, raise_on_failure)
 
     def track_stats(self):
         """Last track_system / track_frame: (grid positions, samples, valid samples at the last evaluation, system evaluations,
@@ -485,28 +463,17 @@ class DrFusion:
     def _track_colour_options(photo_weight, opt):
         if not opt and not photo_weight:
             return None
-        unknown = set(opt) - {f[0] for f in _lib.TrackOptions._fields_}
-        if unknown:
-            raise TypeError("unknown track option(s): %s" % ", ".join(sorted(unknown)))
-        return _lib.TrackColourOptions(_lib.TrackOptions(**opt), photo_weight)
-
-    def _track_colour_image(self, bgr):
-        """(is a device pointer, the argument, what keeps it alive)"""
-        if isinstance(bgr, (int, np.integer)):
-            return True, C.c_void_p(int(bgr)), None
-        bgr = np.ascontiguousarray(bgr, np.uint8)
-        assert bgr.size == self._hw[0] * self._hw[1] * 3
-        return False, C.c_void_p(bgr.ctypes.data), bgr
+        return _lib.TrackColourOptions(DrFusion._options(_lib.TrackOptions, "track", opt) or _lib.TrackOptions(), photo_weight)
 
     def track_colour_system(self, bgr, depth, model_bgr, model_depth, model_pose, pose, photo_weight=0.0, **opt):
         """One evaluation of the tracking's system with the photometric term: the frame (bgr H*W*3 uint8, depth H*W float32) at the
         pose against the model's colour and depth, a ray-cast at model_pose (all four on the host or all four integer device
         pointers): (sums (28,) float64, (samples, valid, unassociated, rejected, photometric terms added)).  photo_weight: voxels
         per intensity unit, 0 = 1/27 times huber; opt: the fields of drf_track_options_t.  No map is read."""
-        dev, d, keep = self._locate_depth(depth)
-        mdev, m, mkeep = self._locate_depth(model_depth)
-        cdev, c, ckeep = self._track_colour_image(bgr)
-        mcdev, mc, mckeep = self._track_colour_image(model_bgr)
+        dev, d, keep = self._image(np.float32, 1, depth)
+        mdev, m, mkeep = self._image(np.float32, 1, model_depth)
+        cdev, c, ckeep = self._image(np.uint8, 3, bgr)
+        mcdev, mc, mckeep = self._image(np.uint8, 3, model_bgr)
         assert dev == mdev == cdev == mcdev, "all four images on the host or all four on the device"
         pose = np.ascontiguousarray(pose, np.float32).reshape(16)
         mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
@@ -521,20 +488,15 @@ class DrFusion:
         one: it holds the motion inside a plane, which track_frame leaves open (on one wall track_frame is ALIGN_DEGENERATE, this
         call is not).  Both images on the host, or both integer device pointers.  Returns an AlignResult whose cost carries both
         terms; ALIGN_DEGENERATE or ALIGN_LOST raises AlignError unless raise_on_failure is false."""
-        dev, d, keep = self._locate_depth(depth)
-        cdev, c, ckeep = self._track_colour_image(bgr)
+        dev, d, keep = self._image(np.float32, 1, depth)
+        cdev, c, ckeep = self._image(np.uint8, 3, bgr)
         assert dev == cdev, "both images on the host or both on the device"
         pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
         o = self._track_colour_options(photo_weight, opt)
         T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
         call = self._L.drf_track_colour_frame_device if dev else self._L.drf_track_colour_frame
         check(call(self._h, c, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
-        res = AlignResult(T=np.array(r.T, np.float64).reshape(4, 4), T32=T32.reshape(4, 4), sums=np.array(r.sums, np.float64), samples=int(r.samples),
-                          valid0=int(r.valid0), valid=int(r.valid), cost0=float(r.cost0), cost=float(r.cost), iterations=int(r.iterations),
-                          status=int(r.status))
-        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
-            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
-        return res
+        return self._align_result(r, T32, raise_on_failure)
 
     def track_colour_stats(self):
         """Last track_colour_system / track_colour_frame: track_stats' fields; the device bytes are a buffer of these calls' own."""
