@@ -653,7 +653,7 @@ int drf_locate_stage_stats(drf_t *h, uint64_t out[4]);
  * decimetres and some ten degrees.  It ends close enough for drf_locate_frame to do the sub-voxel part -- the ray-cast stops up to
  * one voxel in front of the surface, so this call alone is good to about a voxel.  From a rough pose: drf_track_frame, then
  * drf_locate_frame from the pose it returns.  Out of scope: a global search, a test that compares
- * the frame's own normals with the model's, and an image pyramid.  With the frame's colour image at hand call
+ * the frame's own normals with the model's; for an image pyramid call drf_track_pyramid_frame.  With the frame's colour image at hand call
  * drf_track_colour_frame, below: its photometric term holds the motion inside a plane, which this call leaves open.
  * drf_track_frame renders the map at the current estimate into buffers of its own -- the engine's ray-cast, under
  * drf_set_render_scope and drf_set_render_bands as drf_render_async plans it (DRF_RENDER_MAP reads the host store too, and a
@@ -733,8 +733,8 @@ int drf_track_stats(drf_t *h, uint64_t out[6]);
  * frame's own pixel.  bgr is the frame's colour image as drf_integrate_scan_async takes it (height x width x 3 bytes, B G R),
  * model_bgr the ray-cast's at model_pose16.  Everything that drf_track_* say above about the render, its scope and bands, the
  * stream, the map left unchanged, the legality and the refusals (in that order, the colour images among the null checks) holds
- * here.  Out of scope: an affine brightness or exposure model (frame and map are taken to share their exposure), an image
- * pyramid, a global search, and photometric terms in drf_locate_*.
+ * here.  Out of scope: an affine brightness or exposure model (frame and map are taken to share their exposure), a
+ * global search, and photometric terms in drf_locate_*; the image pyramid is drf_track_pyramid_frame, below.
  * The rule (the same text of pose_host.h; double and fp32 without contraction; + - * / sqrt floor):
  *   intensity   a BGR pixel is y = ((float)b + (float)g) + (float)r, a whole number in 0..765.
  *   Ym          the model intensity map, one float per pixel of the model colour image Cm: Ym(u, v) = the pixel's y where the model
@@ -776,6 +776,65 @@ int drf_track_colour_frame_device(drf_t *h, const void *d_bgr, const void *d_dep
  * (the partial sums, 64 bytes of counters, 16 W H model map, 4 W H model depth, 3 W H model colour, 4 W H Ym, 4 W H + 3 W H for a
  * frame given by host pointer); drf_track_stats()[5] does not change. */
 int drf_track_colour_stats(drf_t *h, uint64_t out[6]);
+/* Tracks a frame coarse to fine, over an image pyramid (no reference counterpart; DESIGN.md §7c "Tracking coarse to fine").
+ * drf_track_frame and drf_track_colour_frame run at the camera's resolution: where the map's texture is finer than a rendered pixel
+ * the render aliases it and the cost has minima at the texture's scale.  These calls run the same rule on images halved L times,
+ * level L = levels - 1 down to 0, each level from the pose the one above ended on.  The pyramid is a cure for aliasing and for
+ * texture-scale local minima; it is NOT a global search: a start whose samples fall outside the model is DRF_ALIGN_LOST at every
+ * level.  Track with the pyramid, then drf_locate_frame from the pose it returns.  bgr null: geometry only (drf_track_frame's rule
+ * at every level).  The rule (the same text of pose_host.h; fp32 without contraction; + - * / sqrt floor and integers):
+ *   level       s = 2^L.  W_L = W / s, H_L = H / s by integer division: remainder columns and rows are dropped.  In fp32
+ *               fx_L = fx / s, fy_L = fy / s, cx_L = (cx + 0.5f) / s - 0.5f, cy_L likewise; level 0 is the camera itself.  step, the
+ *               sensor depth limits, dist_max, huber, photo_weight, min_valid and the epsilons are unchanged;
+ *               max_jump_L = (float)s * max_jump, max_jump resolved first.  A level with W_L < 8 or H_L < 8 is refused, as is
+ *               levels > 5.
+ *   reduction   of a (bgr, depth) pair to level L, the same for frame and model.  Level pixel (u, v) covers the block
+ *               [u s, u s + s) x [v s, v s + s).  A pixel is VALID iff z > 0 in fp32 (a NaN is not).  z0 = the smallest valid depth
+ *               of the block; none: depth 0.0f, colour 0, 0, 0.  A pixel is ACCEPTED iff it is valid and z - z0 <= max_jump_L in
+ *               fp32; n = the accepted pixels.  2 n < s s: depth 0.0f, colour 0, 0, 0.  Otherwise depth = S / (float)n: a pixel that
+ *               is not accepted contributes +0.0f; each row of the block is summed by the butterfly t[i] = t[i] + t[i ^ off] for
+ *               off = s / 2 .. 1, the row's sum is t[0]; the rows are added in ascending order from the first row's sum.  Per
+ *               channel, c = the integer sum over the accepted pixels, the output is (2 c + n) / (2 n) by integer division (half up).
+ *   evaluation  drf_track_colour_*'s rule (drf_track_*'s without colour) on the reduced images with the level's camera.
+ *   schedule    The frame is reduced once per call to every level >= 1.  For L = levels - 1 down to 1 the outer loop of drf_track_*
+ *               runs at level L with max_renders = coarse_renders; a round renders the model at FULL resolution (the engine's one
+ *               submit: bit for bit a drf_render_async at that pose), reduces it to level L, builds the model map (and Ym) and
+ *               evaluates.  A level that ends DRF_ALIGN_LOST or DRF_ALIGN_DEGENERATE is ABANDONED: the pose it started from goes to
+ *               the next finer level.  Any other level hands on its T rounded to float.  Level 0 is then the existing call's loop
+ *               from that pose with max_renders as given, and res is level 0's result, exactly: levels = 1 is
+ *               drf_track_colour_frame, with bgr null drf_track_frame, bit for bit.
+ * drf_track_reduce is the reduction alone: full-resolution images in, W_L x H_L images out; max_jump is the level's own (not scaled
+ * again; it must be finite and >= 0); bgr null reduces the depth alone (bgr_out is not written).  drf_track_pyramid_system is one
+ * evaluation at `level`: both pairs are given at full resolution and reduced first; counts[4] is 0 without colour.
+ * Legality and refusals in drf_track_colour_frame's order, levels and coarse_renders among the options (after the colour options'
+ * own): DR_ERR_ARG naming the option for a negative value, levels > 5 and a level below 8 pixels; `level` of drf_track_reduce and
+ * drf_track_pyramid_system is judged with the options.  All statistics are zero after a refusal.  The render's DR_ERR_CAPACITY, its
+ * scope and bands are as for drf_track_frame.  The public render buffers, drf_track_stats, drf_track_colour_stats and the map are
+ * untouched: these calls have a scratch buffer of their own, sized once per engine for five levels. */
+typedef struct {
+  drf_track_colour_options_t colour;
+  int levels;           /* 0 -> 3 */
+  int coarse_renders;   /* renders per level above 0; 0 -> 3 */
+} drf_track_pyramid_options_t;
+int drf_track_reduce(drf_t *h, int level, float max_jump, const uint8_t *bgr, const float *depth, uint8_t *bgr_out, float *depth_out);
+int drf_track_pyramid_system(drf_t *h, int level, const uint8_t *bgr, const float *depth, const uint8_t *model_bgr, const float *model_depth,
+                             const float model_pose16[16], const float pose16[16], const drf_track_pyramid_options_t *opt, double sums[28], uint64_t counts[5]);
+int drf_track_pyramid_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float pose_init16[16], const drf_track_pyramid_options_t *opt,
+                            float pose16_out[16], drf_align_result_t *res);
+/* the same with every image, the outputs of the reduction included, in device memory */
+int drf_track_reduce_device(drf_t *h, int level, float max_jump, const void *d_bgr, const void *d_depth, void *d_bgr_out, void *d_depth_out);
+int drf_track_pyramid_system_device(drf_t *h, int level, const void *d_bgr, const void *d_depth, const void *d_model_bgr, const void *d_model_depth,
+                                    const float model_pose16[16], const float pose16[16], const drf_track_pyramid_options_t *opt, double sums[28],
+                                    uint64_t counts[5]);
+int drf_track_pyramid_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float pose_init16[16], const drf_track_pyramid_options_t *opt,
+                                   float pose16_out[16], drf_align_result_t *res);
+/* last drf_track_pyramid_* / drf_track_reduce: [0] grid positions, [1] samples and [2] valid samples at a level's last evaluation,
+ * each summed over the levels that ran; [3] evaluations and [4] renders in all; [5] device bytes held; [6] levels run; [7] levels
+ * abandoned (all 0 after a call that was refused; after drf_track_reduce only [5] is set) */
+int drf_track_pyramid_stats(drf_t *h, uint64_t out[8]);
+/* level 0 .. 4 of the last drf_track_pyramid_frame: [0] its status, [1] renders, [2] evaluations, [3] valid samples at its last
+ * evaluation; all 0 for a level that did not run ([2] = 0 says so).  After drf_track_pyramid_system: the one evaluation at its level. */
+int drf_track_pyramid_level_stats(drf_t *h, int level, uint64_t out[4]);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

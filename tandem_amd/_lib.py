@@ -158,6 +158,14 @@ SIGNATURES = {
     "drf_track_colour_system_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
     "drf_track_colour_frame_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
     "drf_track_colour_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_track_reduce": (C.c_int, [vp, C.c_int, C.c_float, C.c_void_p, f32p, C.c_void_p, f32p]),
+    "drf_track_reduce_device": (C.c_int, [vp, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "drf_track_pyramid_system": (C.c_int, [vp, C.c_int, C.c_void_p, f32p, C.c_void_p, f32p, f32p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_track_pyramid_system_device": (C.c_int, [vp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_track_pyramid_frame": (C.c_int, [vp, C.c_void_p, f32p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_track_pyramid_frame_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_track_pyramid_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_track_pyramid_level_stats": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint64)]),
 }
 
 
@@ -182,6 +190,11 @@ class TrackOptions(C.Structure):
 class TrackColourOptions(C.Structure):
     """drf_track_colour_options_t: a zero field means its default."""
     _fields_ = [("track", TrackOptions), ("photo_weight", C.c_float)]
+
+
+class TrackPyramidOptions(C.Structure):
+    """drf_track_pyramid_options_t: a zero field means its default."""
+    _fields_ = [("colour", TrackColourOptions), ("levels", C.c_int), ("coarse_renders", C.c_int)]
 
 
 class AlignResultStruct(C.Structure):

@@ -675,6 +675,7 @@ __global__ void k_fill_keys(unsigned long long *keys, size_t n) {
 #include "locate_kernels.h"  // k_map_locate (drf_locate_system, drf_locate_frame)
 #include "track_kernels.h"   // k_track_model, k_track (drf_track_system, drf_track_frame)
 #include "track_colour_kernels.h"  // k_track_model_colour, k_track_colour (drf_track_colour_system, drf_track_colour_frame)
+#include "track_pyramid_kernels.h"  // k_track_reduce (drf_track_reduce, drf_track_pyramid_system, drf_track_pyramid_frame)
 
 }  // namespace dr
 #include "mesh_kernels.h"
@@ -1845,6 +1846,220 @@ class FusionEngine {
   const uint64_t *track_stats() const { return tk_.stats; }
   const uint64_t *track_colour_stats() const { return tc_.stats; }
 
+  // A frame tracked coarse to fine (drf_track_reduce, drf_track_pyramid_*; DESIGN.md §7c "Tracking coarse to fine").  The rule:
+  // pose_host.h track_level_grid / track_reduce_host / track_pyramid_schedule.  with_track's shape, with colour decided by the
+  // images given (bgr null: the geometric kernels) and every launch given its level: k_track_reduce brings a full-resolution pair
+  // to the level, k_track_model(_colour) and k_track(_colour) run unchanged on the level's LocateGrid.  Scratch and statistics are
+  // these calls' own (tp_), sized once for five levels with nothing aliased; tk_, tc_ and the public render are not touched.
+  struct PyramidSide {
+    DeviceBuf<unsigned char> buf;  // sized once
+    uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // drf_track_pyramid_stats
+    uint64_t level[kTrackMaxLevels][4] = {};       // drf_track_pyramid_level_stats
+    Render render{};                               // the model's full-resolution render: int_stream_ and pointers into buf
+    void reset() { memset(stats, 0, sizeof stats); memset(level, 0, sizeof level); }
+  };
+  struct PyramidBufs {
+    double *partial; unsigned long long *counts; int *flag; TrackPixel *map; RayState *band;
+    float *model, *level, *Ym, *frame, *pyr[kTrackMaxLevels];                          // the full-resolution model, its level, Ym, a host-given frame, the frame's levels >= 1
+    unsigned char *model_bgr, *level_bgr, *frame_bgr, *pyr_bgr[kTrackMaxLevels];
+    const float *depth; const unsigned char *bgr;  // the frame at full resolution: the caller's device images, or the spans a host frame went to
+  };
+  PyramidBufs pyramid_bufs() {
+    PyramidBufs b{};
+    const size_t max_groups = (npix_ + 511) / 512;
+    auto level_pixels = [&](int L) { return std::max<size_t>(1, (size_t)(o_.width >> L) * (size_t)(o_.height >> L)); };
+    carve(tp_.buf, int_stream_, [&](Carver &c) {
+      b.partial = c.take<double>(max_groups * 28);
+      b.counts = c.take<unsigned long long>(6);
+      b.flag = c.take<int>(1);
+      b.map = c.take<TrackPixel>(npix_, 32);
+      b.band = c.take<RayState>(npix_, 8);
+      b.model = c.take<float>(npix_);
+      b.level = c.take<float>(level_pixels(1));
+      b.Ym = c.take<float>(npix_);
+      b.frame = c.take<float>(npix_);
+      for (int L = 1; L < kTrackMaxLevels; ++L) b.pyr[L] = c.take<float>(level_pixels(L));
+      b.model_bgr = c.take<unsigned char>(npix_ * 3);
+      b.level_bgr = c.take<unsigned char>(level_pixels(1) * 3);
+      b.frame_bgr = c.take<unsigned char>(npix_ * 3);
+      for (int L = 1; L < kTrackMaxLevels; ++L) b.pyr_bgr[L] = c.take<unsigned char>(level_pixels(L) * 3);
+    });
+    return b;
+  }
+  void launch_reduce(const float *depth, const unsigned char *bgr, int L, float max_jump, float *depth_out, unsigned char *bgr_out) {
+    const int WL = o_.width >> L, HL = o_.height >> L;
+    const int threads = (WL * HL) << L;  // at most width * height
+    hipLaunchKernelGGL(k_track_reduce, dim3(cdiv(threads, 256)), dim3(256), 0, int_stream_, depth, bgr, o_.width, WL, HL, L, max_jump, depth_out, bgr_out);
+    DR_HIP(hipGetLastError());
+  }
+  // level null: drf_track_pyramid_frame; otherwise the level of a drf_track_pyramid_system, judged with the options.  body(po, b,
+  // colour, fg, model, eval): model(L, lo) turns the full-resolution model in b.model / b.model_bgr into level L's model map (and
+  // Ym); eval(L, lo, e, model_pose16, sums, counts) is one evaluation of level L against it.
+  template <class Body>
+  void with_track_pyramid(const char *who, const int *level, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
+                          const float *model_pose16, const drf_track_pyramid_options_t *opt, Body &&body) {
+    tp_.reset();
+    TrackPyramidOpt po;
+    if (const char *bad = track_pyramid_options(opt, o_.voxel_size, o_.width, o_.height, po))
+      fail(DR_ERR_ARG, "%s: option %s is negative, not finite or out of range (levels <= %d, every level at least %d pixels on a side)", who, bad, kTrackMaxLevels,
+           kTrackMinLevelSide);
+    if (level && !track_level_fits(o_.width, o_.height, *level))
+      fail(DR_ERR_ARG, "%s: level %d is outside 0..%d or below %d pixels on a side of the %dx%d camera", who, *level, kTrackMaxLevels - 1, kTrackMinLevelSide, o_.height,
+           o_.width);
+    frame_prologue(who, nullptr, pose16, model_pose16);
+    const bool colour = h_depth ? h_bgr != nullptr : d_bgr != nullptr;
+    const FrameGrid fg = frame_grid(po.c.t.step);
+    PyramidBufs b = pyramid_bufs();
+    if (colour && !tc_fifth_) tc_fifth_ = own_.pinned<unsigned long long>(1);
+    mio_.ensure(1);
+    b.depth = (const float *)d_depth;
+    b.bgr = (const unsigned char *)d_bgr;
+    if (h_depth) {
+      upload_frame(h_bgr, h_depth, colour ? b.frame_bgr : nullptr, b.frame);
+      b.depth = b.frame;
+      b.bgr = colour ? b.frame_bgr : nullptr;
+    }
+    tp_.stats[5] = tp_.buf.capacity();
+    auto model = [&](int L, const TrackColourOpt &lo) {
+      const LocateGrid lg = track_level_grid(fg.lg, L);
+      const float *dm = b.model;
+      const unsigned char *cm = b.model_bgr;
+      if (L > 0) {
+        launch_reduce(b.model, colour ? b.model_bgr : nullptr, L, lo.t.max_jump, b.level, b.level_bgr);
+        dm = b.level; cm = b.level_bgr;
+      }
+      const int np = lg.W * lg.H;
+      if (colour) hipLaunchKernelGGL(k_track_model_colour, dim3(cdiv(np, 256)), dim3(256), 0, int_stream_, dm, cm, lg, lo.t.max_jump, b.map, b.Ym);
+      else hipLaunchKernelGGL(k_track_model, dim3(cdiv(np, 256)), dim3(256), 0, int_stream_, dm, lg, lo.t.max_jump, b.map);
+      DR_HIP(hipGetLastError());
+    };
+    auto eval = [&](int L, const TrackColourOpt &lo, const AlignEval &e, const float *mp16, double sums[28], uint64_t *c) {  // c[5] with colour, c[4] without
+      const LocateGrid lg = track_level_grid(fg.lg, L);
+      const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
+      const float *fd = L == 0 ? b.depth : b.pyr[L];
+      const unsigned char *fc = L == 0 ? b.bgr : b.pyr_bgr[L];
+      const TrackModel tm = track_model(mp16, lo.t, o_.voxel_size, b.map);
+      mio_.evaluate(b.partial, groups, b.counts, 4, sums, c, [&] {
+        if (colour) {
+          DR_HIP(hipMemsetAsync(b.counts + 4, 0, 8, int_stream_));
+          hipLaunchKernelGGL(k_track_colour, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, fd, fc, lg, e, tm, track_colour(lo, b.Ym), groups, total, b.partial, b.counts);
+          DR_HIP(hipGetLastError());
+          DR_HIP(hipMemcpyAsync(tc_fifth_, b.counts + 4, 8, hipMemcpyDeviceToHost, int_stream_));
+        } else {
+          hipLaunchKernelGGL(k_track, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, fd, lg, e, tm, groups, total, b.partial, b.counts);
+          DR_HIP(hipGetLastError());
+        }
+      });
+      if (colour) c[4] = *tc_fifth_;
+    };
+    try {
+      body(po, b, colour, fg, model, eval);
+    } catch (...) {
+      tp_.reset();
+      throw;
+    }
+  }
+  // the reduction alone: host images through the scratch, or device images in place
+  void track_reduce(const char *who, int level, float max_jump, const uint8_t *h_bgr, const float *h_depth, uint8_t *h_bgr_out, float *h_depth_out, const void *d_bgr,
+                    const void *d_depth, void *d_bgr_out, void *d_depth_out) {
+    tp_.reset();
+    const bool host = h_depth != nullptr;
+    if (host ? (!h_depth_out || (h_bgr && !h_bgr_out)) : (!d_depth || !d_depth_out || (d_bgr && !d_bgr_out))) fail(DR_ERR_ARG, "%s: null argument", who);
+    if (!(max_jump >= 0.0f) || !std::isfinite(max_jump)) fail(DR_ERR_ARG, "%s: option max_jump is negative or not finite", who);
+    if (!track_level_fits(o_.width, o_.height, level))
+      fail(DR_ERR_ARG, "%s: level %d is outside 0..%d or below %d pixels on a side of the %dx%d camera", who, level, kTrackMaxLevels - 1, kTrackMinLevelSide, o_.height,
+           o_.width);
+    expect_integrate(who);
+    settle();
+    const size_t nl = (size_t)(o_.width >> level) * (size_t)(o_.height >> level);
+    if (host) {
+      PyramidBufs b = pyramid_bufs();
+      upload_frame(h_bgr, h_depth, h_bgr ? b.frame_bgr : nullptr, b.frame);
+      launch_reduce(b.frame, h_bgr ? b.frame_bgr : nullptr, level, max_jump, b.model, b.model_bgr);  // the model's full-resolution spans hold any level
+      DR_HIP(hipMemcpyAsync(h_depth_out, b.model, nl * 4, hipMemcpyDeviceToHost, int_stream_));
+      if (h_bgr) DR_HIP(hipMemcpyAsync(h_bgr_out, b.model_bgr, nl * 3, hipMemcpyDeviceToHost, int_stream_));
+    } else {
+      launch_reduce((const float *)d_depth, (const unsigned char *)d_bgr, level, max_jump, (float *)d_depth_out, (unsigned char *)d_bgr_out);
+    }
+    DR_HIP(hipStreamSynchronize(int_stream_));
+    tp_.stats[5] = tp_.buf.capacity();
+  }
+  // one evaluation at `level` against a full-resolution model pair the caller gives (bgr null: geometric, counts[4] = 0)
+  void track_pyramid_system(const char *who, int level, const uint8_t *h_bgr, const float *h_depth, const uint8_t *h_model_bgr, const float *h_model, const void *d_bgr,
+                            const void *d_depth, const void *d_model_bgr, const void *d_model, const float *model_pose16, const float *pose16,
+                            const drf_track_pyramid_options_t *opt, double *sums, uint64_t *counts) {
+    tp_.reset();
+    const bool host = h_depth != nullptr;
+    const bool colour = host ? h_bgr != nullptr : d_bgr != nullptr;
+    const bool model_ok = host ? (h_model && (!colour || h_model_bgr)) : (d_depth && d_model && (!colour || d_model_bgr));
+    if (!model_ok || !model_pose16 || !pose16 || !sums || !counts) fail(DR_ERR_ARG, "%s: null argument", who);
+    with_track_pyramid(who, &level, h_bgr, h_depth, d_bgr, d_depth, pose16, model_pose16, opt,
+                       [&](const TrackPyramidOpt &po, const PyramidBufs &b, bool col, const FrameGrid &fg, auto &model, auto &eval) {
+      const TrackColourOpt lo = track_level_options(po, level);
+      if (level > 0) launch_reduce(b.depth, col ? b.bgr : nullptr, level, lo.t.max_jump, b.pyr[level], b.pyr_bgr[level]);
+      if (host) {
+        upload_frame(h_model_bgr, h_model, col ? b.model_bgr : nullptr, b.model, true);
+      } else {  // a device-given model goes to the scratch like a render: model() reads it there
+        DR_HIP(hipMemcpyAsync(b.model, d_model, npix_ * 4, hipMemcpyDeviceToDevice, int_stream_));
+        if (col) DR_HIP(hipMemcpyAsync(b.model_bgr, d_model_bgr, npix_ * 3, hipMemcpyDeviceToDevice, int_stream_));
+      }
+      model(level, lo);
+      double c_src[3];
+      locate_centre_src(lo.t.centre_depth, o_.voxel_size, c_src);
+      uint64_t c[5] = {0, 0, 0, 0, 0};
+      eval(level, lo, align_eval(map_motion(pose16, o_.voxel_size), c_src, lo.t.a, o_.voxel_size), model_pose16, sums, c);
+      for (int i = 0; i < 5; ++i) counts[i] = c[i];
+      const LocateGrid lg = track_level_grid(fg.lg, level);
+      tp_.stats[0] = (uint64_t)locate_positions(lg); tp_.stats[1] = c[0]; tp_.stats[2] = c[1]; tp_.stats[3] = 1; tp_.stats[6] = 1;
+      tp_.level[level][2] = 1; tp_.level[level][3] = c[1];
+    });
+  }
+  // returns what dr_last_error() says after a tracking that ran but found no pose (empty otherwise)
+  std::string track_pyramid_frame(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
+                                  const drf_track_pyramid_options_t *opt, float *pose16_out, drf_align_result_t *res) {
+    tp_.reset();
+    if (!(h_depth || d_depth) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+    drf_align_result_t r;
+    uint64_t last[5] = {0, 0, 0, 0, 0};
+    with_track_pyramid(who, nullptr, h_bgr, h_depth, d_bgr, d_depth, pose16, nullptr, opt,
+                       [&](const TrackPyramidOpt &po, const PyramidBufs &b, bool col, const FrameGrid &fg, auto &model, auto &eval) {
+      Render &rd = tp_.render;
+      if (!rd.cast) { rd.cast = own_.event(); rd.done = own_.event(); }
+      rd.stream = int_stream_;
+      rd.d_bgr = b.model_bgr;
+      rd.d_band = b.band;
+      rd.d_depth = b.model;
+      rd.d_flag = b.flag;
+      for (int L = 1; L < po.levels; ++L)  // the frame, reduced once per call
+        launch_reduce(b.depth, col ? b.bgr : nullptr, L, track_level_options(po, L).t.max_jump, b.pyr[L], b.pyr_bgr[L]);
+      track_pyramid_schedule([&](int L, const float *p16, const TrackColourOpt &lo, drf_align_result_t &lr, uint64_t *lc, uint64_t *st2) {
+        auto render = [&](const float *p) {  // the engine's one submit at full resolution, then the level's model map
+          RenderStagePlan plan;
+          RenderBandPlan bands;
+          bool waited = false;
+          const float *poses[1] = {p};
+          if (render_scope_ == DRF_RENDER_MAP) plan_render_call(who, poses, 1, plan, bands, waited);
+          render_passes(plan, bands, &rd, poses, 1, false);
+          model(L, lo);
+        };
+        auto ev = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t *c) { eval(L, lo, e, mp16, sums, c); };
+        if (col) track_loop<5>(render, ev, p16, lo.t, o_.voxel_size, lr, lc, st2);
+        else track_loop<4>(render, ev, p16, lo.t, o_.voxel_size, lr, lc, st2);
+      }, fg.lg, pose16, po, r, tp_.stats, tp_.level, last);
+    });
+    for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
+    if (res) *res = r;
+    return no_pose_note(std::string(who) + ": the tracking", r,
+                        ", " + std::to_string((unsigned long long)last[2]) + " unassociated, " + std::to_string((unsigned long long)last[3]) + " rejected; " +
+                            std::to_string((unsigned long long)tp_.stats[6]) + " levels, " + std::to_string((unsigned long long)tp_.stats[7]) + " abandoned, " +
+                            std::to_string((unsigned long long)tp_.stats[4]) + " renders; " + std::to_string(store_.size()) + " blocks are in the host store)");
+  }
+  const uint64_t *track_pyramid_stats() const { return tp_.stats; }
+  const uint64_t *track_pyramid_level_stats(int level) const {
+    if (level < 0 || level >= kTrackMaxLevels) fail(DR_ERR_ARG, "drf_track_pyramid_level_stats: level %d is outside 0..%d", level, kTrackMaxLevels - 1);
+    return tp_.level[level];
+  }
+
  private:
   enum Next { kIntegrate, kRender, kGetRender };
   static constexpr int kStageBlocks = 8192;  // blocks per eviction chain / per stream-in launch (32 MiB of pinned staging each way)
@@ -2439,6 +2654,7 @@ class FusionEngine {
   DeviceBuf<unsigned char> lc_buf_;            // drf_locate_*: partial sums, counters and a host-given depth image (sized once)
   uint64_t lc_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_locate_stats
   TrackSide tk_, tc_;                          // drf_track_*, drf_track_colour_*: each its own scratch, statistics and model render (with_track)
+  PyramidSide tp_;                             // drf_track_reduce, drf_track_pyramid_*: their own scratch, statistics and model render (with_track_pyramid)
   unsigned long long *tc_fifth_ = nullptr;     // pinned: the fifth counter of an evaluation with colour
   int locate_scope_ = DRF_LOCATE_RESIDENT;     // drf_set_locate_scope
   size_t lc_cap_req_ = 0;
@@ -2701,6 +2917,53 @@ int drf_track_colour_frame_device(drf_t *h, const void *d_bgr, const void *d_dep
   return guarded_note([&] { return eng(h)->track_frame<dr::TrackWithColour>("drf_track_colour_frame_device", nullptr, nullptr, d_bgr, d_depth, pose_init16, opt, pose16_out, res); });
 }
 int drf_track_colour_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_track_colour_stats", out, &dr::FusionEngine::track_colour_stats); }
+int drf_track_reduce(drf_t *h, int level, float max_jump, const uint8_t *bgr, const float *depth, uint8_t *bgr_out, float *depth_out) {
+  return guarded([&] {
+    eng(h)->track_reduce("drf_track_reduce", level, max_jump, bgr, depth, bgr_out, depth_out, nullptr, nullptr, nullptr, nullptr);
+  });
+}
+int drf_track_reduce_device(drf_t *h, int level, float max_jump, const void *d_bgr, const void *d_depth, void *d_bgr_out, void *d_depth_out) {
+  return guarded([&] { eng(h)->track_reduce("drf_track_reduce_device", level, max_jump, nullptr, nullptr, nullptr, nullptr, d_bgr, d_depth, d_bgr_out, d_depth_out); });
+}
+int drf_track_pyramid_system(drf_t *h, int level, const uint8_t *bgr, const float *depth, const uint8_t *model_bgr, const float *model_depth,
+                             const float model_pose16[16], const float pose16[16], const drf_track_pyramid_options_t *opt, double sums[28], uint64_t counts[5]) {
+  return guarded([&] {
+    eng(h)->track_pyramid_system("drf_track_pyramid_system", level, bgr, depth, model_bgr, model_depth, nullptr, nullptr, nullptr, nullptr, model_pose16, pose16, opt, sums,
+                                 counts);
+  });
+}
+int drf_track_pyramid_system_device(drf_t *h, int level, const void *d_bgr, const void *d_depth, const void *d_model_bgr, const void *d_model_depth,
+                                    const float model_pose16[16], const float pose16[16], const drf_track_pyramid_options_t *opt, double sums[28],
+                                    uint64_t counts[5]) {
+  return guarded([&] {
+    eng(h)->track_pyramid_system("drf_track_pyramid_system_device", level, nullptr, nullptr, nullptr, nullptr, d_bgr, d_depth, d_model_bgr, d_model_depth, model_pose16,
+                                 pose16, opt, sums, counts);
+  });
+}
+int drf_track_pyramid_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float pose_init16[16], const drf_track_pyramid_options_t *opt,
+                            float pose16_out[16], drf_align_result_t *res) {
+  return guarded_note([&] {
+    return eng(h)->track_pyramid_frame("drf_track_pyramid_frame", bgr, depth, nullptr, nullptr, pose_init16, opt, pose16_out, res);
+  });
+}
+int drf_track_pyramid_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float pose_init16[16], const drf_track_pyramid_options_t *opt,
+                                   float pose16_out[16], drf_align_result_t *res) {
+  return guarded_note([&] { return eng(h)->track_pyramid_frame("drf_track_pyramid_frame_device", nullptr, nullptr, d_bgr, d_depth, pose_init16, opt, pose16_out, res); });
+}
+int drf_track_pyramid_stats(drf_t *h, uint64_t out[8]) {
+  return guarded([&] {
+    if (!out) dr::fail(DR_ERR_ARG, "drf_track_pyramid_stats: null argument");
+    const uint64_t *s = eng(h)->track_pyramid_stats();
+    for (int i = 0; i < 8; ++i) out[i] = s[i];
+  });
+}
+int drf_track_pyramid_level_stats(drf_t *h, int level, uint64_t out[4]) {
+  return guarded([&] {
+    if (!out) dr::fail(DR_ERR_ARG, "drf_track_pyramid_level_stats: null argument");
+    const uint64_t *s = eng(h)->track_pyramid_level_stats(level);
+    for (int i = 0; i < 4; ++i) out[i] = s[i];
+  });
+}
 int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_locate_scope(scope, stage_capacity_blocks); }); }
 int drf_locate_stage_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->locate_stage_stats(out); }); }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }

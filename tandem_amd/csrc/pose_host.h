@@ -752,4 +752,187 @@ inline void track_frame_host(const LocateGrid &lg, const float *depth, RenderDep
                              voxel_size, res, last4, stats2, trace);
 }
 
+// ---- tracking coarse to fine (drf_track_reduce / drf_track_pyramid_system / drf_track_pyramid_frame; DESIGN.md §7c "Tracking coarse
+// to fine").  Both calls above run at the camera's resolution, where a render aliases a texture finer than a pixel and the cost has
+// minima at the texture's scale.  Level L = 0 .. levels - 1 halves the images L times, s = 2^L: frame and model are REDUCED by one
+// rule, the camera is scaled, and the level's evaluation is the rule above on the reduced images -- track_normal,
+// track_model_intensity, track_point and track_colour_point as they stand, given the level's LocateGrid.  The levels run from the
+// coarsest down, each track_loop from the pose the one above ended on; level 0 is the call above, bit for bit.  Stated once,
+// here; the header of the C ABI restates it.  Compiled by g++ and by hipcc (k_track_reduce), both without contraction; + - * / sqrt
+// floor and integer arithmetic only.
+constexpr int kTrackMaxLevels = 5, kTrackMinLevelSide = 8;
+// The camera of level L from the camera lg0 of level 0 (its step is kept): W_L = W / s, H_L = H / s by integer division -- the
+// remainder columns and rows are dropped -- fx_L = fx / s, cx_L = (cx + 0.5f) / s - 0.5f in fp32 (a pixel's centre is at its index:
+// a block's centre in level units), fy_L and cy_L likewise; the depth limits are unchanged.  Level 0 is lg0 itself.
+inline LocateGrid track_level_grid(const LocateGrid &lg0, int L) {
+  if (L == 0) return lg0;
+  LocateGrid g = lg0;
+  const int s = 1 << L;
+  const float sf = (float)s;
+  g.W = lg0.W / s; g.H = lg0.H / s;
+  g.Wg = (g.W + g.step - 1) / g.step; g.Hg = (g.H + g.step - 1) / g.step;
+  g.fx = lg0.fx / sf; g.fy = lg0.fy / sf;
+  g.cx = (lg0.cx + 0.5f) / sf - 0.5f; g.cy = (lg0.cy + 0.5f) / sf - 0.5f;
+  return g;
+}
+inline bool track_level_fits(int W, int H, int L) { return L >= 0 && L < kTrackMaxLevels && (W >> L) >= kTrackMinLevelSide && (H >> L) >= kTrackMinLevelSide; }
+struct TrackPyramidOpt {  // drf_track_pyramid_options_t with its defaults resolved
+  TrackColourOpt c;
+  int levels, coarse_renders;
+};
+// null: all defaults.  Returns null, or which option is refused: the colour options' own first, then levels (negative, above 5, or
+// its coarsest level below 8 pixels on a side of the W x H camera), then coarse_renders (negative).
+inline const char *track_pyramid_options(const drf_track_pyramid_options_t *opt, float voxel_size, int W, int H, TrackPyramidOpt &o) {
+  if (const char *bad = track_colour_options(opt ? &opt->colour : nullptr, voxel_size, o.c)) return bad;
+  const int levels = opt ? opt->levels : 0, coarse = opt ? opt->coarse_renders : 0;
+  if (levels < 0 || levels > kTrackMaxLevels) return "levels";
+  o.levels = levels ? levels : 3;
+  if (!track_level_fits(W, H, o.levels - 1)) return "levels";
+  if (coarse < 0) return "coarse_renders";
+  o.coarse_renders = coarse ? coarse : 3;
+  return nullptr;
+}
+// the options of level L: max_jump_L = (float)s * max_jump (max_jump resolved first), and above level 0 max_renders = coarse_renders
+inline TrackColourOpt track_level_options(const TrackPyramidOpt &o, int L) {
+  TrackColourOpt c = o.c;
+  c.t.max_jump = (float)(1 << L) * o.c.t.max_jump;
+  if (L > 0) c.t.max_renders = o.coarse_renders;
+  return c;
+}
+// The pieces of the reduction that the host and k_track_reduce share.  A pixel is VALID iff z > 0 (a NaN is not); it is ACCEPTED
+// iff it is valid and z - z0 <= max_jump in fp32, z0 the smallest valid depth of its block (an infinite z is never accepted:
+// inf - z0 is inf or NaN).  A channel's output from its integer sum c over the n accepted pixels: (2 c + n) / (2 n), half up.
+DR_HOST_DEVICE inline bool track_reduce_valid(float z) { return z > 0.0f; }
+DR_HOST_DEVICE inline bool track_reduce_accepted(float z, float z0, float max_jump) { return z > 0.0f && z - z0 <= max_jump; }
+DR_HOST_DEVICE inline unsigned char track_reduce_colour(int c, int n) { return (unsigned char)((2 * c + n) / (2 * n)); }
+// A (bgr, depth) pair of W x H reduced to level L (bgr null: the depth alone): level pixel (u, v) covers the block
+// [u s, u s + s) x [v s, v s + s).  z0 = the smallest valid depth of the block; none valid: depth 0.0f, colour 0, 0, 0.  n = the
+// accepted pixels; 2 n < s s: the same zeros.  Otherwise depth = S / (float)n, where a pixel that is not accepted contributes
+// +0.0f, each row of the block is summed by the butterfly t[i] = t[i] + t[i ^ off], off = s / 2 .. 1, its sum t[0], and the rows
+// are added in ascending order from the first row's sum; and each channel is track_reduce_colour of its sum over the accepted.
+// The butterfly is what a wave does across the s lanes that hold a row of the block.  max_jump is the level's own.
+inline void track_reduce_host(int W, int H, int L, float max_jump, const unsigned char *bgr, const float *depth, unsigned char *bgr_out, float *depth_out) {
+  const int s = 1 << L, WL = W / s, HL = H / s;
+  for (int v = 0; v < HL; ++v)
+    for (int u = 0; u < WL; ++u) {
+      const size_t at = (size_t)(v * s) * (size_t)W + (size_t)(u * s), to = (size_t)v * (size_t)WL + (size_t)u;
+      bool any = false;
+      float z0 = 0.0f;
+      for (int r = 0; r < s; ++r)
+        for (int i = 0; i < s; ++i) {
+          const float z = depth[at + (size_t)r * W + i];
+          if (track_reduce_valid(z) && (!any || z < z0)) { z0 = z; any = true; }
+        }
+      int n = 0, c[3] = {0, 0, 0};
+      float S = 0.0f;
+      for (int r = 0; r < s && any; ++r) {
+        float t[16];
+        for (int i = 0; i < s; ++i) {
+          const size_t px = at + (size_t)r * W + i;
+          const bool acc = track_reduce_accepted(depth[px], z0, max_jump);
+          t[i] = acc ? depth[px] : 0.0f;
+          if (!acc) continue;
+          ++n;
+          if (bgr) { c[0] += bgr[3 * px]; c[1] += bgr[3 * px + 1]; c[2] += bgr[3 * px + 2]; }
+        }
+        for (int off = s >> 1; off > 0; off >>= 1) {
+          float y[16];
+          for (int i = 0; i < s; ++i) y[i] = t[i] + t[i ^ off];
+          memcpy(t, y, sizeof(float) * (size_t)s);
+        }
+        S = r == 0 ? t[0] : S + t[0];
+      }
+      const bool keep = any && 2 * n >= s * s;
+      depth_out[to] = keep ? S / (float)n : 0.0f;
+      if (bgr)
+        for (int k = 0; k < 3; ++k) bgr_out[3 * to + k] = keep ? track_reduce_colour(c[k], n) : (unsigned char)0;
+    }
+}
+// The schedule of drf_track_pyramid_frame over run(L, p16, level options, res, last[5], stats2[2]), one track_loop at level L from
+// p16 (the engine's, over its kernels, or track_pyramid_frame_host's).  L = levels - 1 down to 1: a level that ends LOST or
+// DEGENERATE is ABANDONED, the pose it started from goes to the next finer level; any other level hands on its T rounded to
+// float.  Level 0 then runs with max_renders as given and res is its result, exactly.  stats8 = {[0] grid positions, [1] samples and
+// [2] valid samples at the last evaluation, each summed over the levels; [3] evaluations and [4] renders in all; [5] left to the
+// caller; [6] levels run; [7] levels abandoned}; level4[L] = {status, renders, evaluations, valid at the last evaluation}.
+template <class Run>
+inline void track_pyramid_schedule(Run &&run, const LocateGrid &lg0, const float *pose_init16, const TrackPyramidOpt &o, drf_align_result_t &res, uint64_t stats8[8],
+                                   uint64_t level4[kTrackMaxLevels][4], uint64_t *last5 = nullptr) {
+  float p16[16];
+  memcpy(p16, pose_init16, sizeof p16);
+  for (int i = 0; i < 8; ++i) stats8[i] = i == 5 ? stats8[5] : 0;
+  memset(level4, 0, sizeof(uint64_t) * kTrackMaxLevels * 4);
+  for (int L = o.levels - 1; L >= 0; --L) {
+    const TrackColourOpt lo = track_level_options(o, L);
+    drf_align_result_t r;
+    uint64_t last[5] = {0, 0, 0, 0, 0}, st2[2] = {0, 0};
+    run(L, p16, lo, r, last, st2);
+    level4[L][0] = (uint64_t)r.status; level4[L][1] = st2[1]; level4[L][2] = st2[0]; level4[L][3] = last[1];
+    stats8[0] += (uint64_t)locate_positions(track_level_grid(lg0, L));
+    stats8[1] += last[0]; stats8[2] += last[1]; stats8[3] += st2[0]; stats8[4] += st2[1];
+    ++stats8[6];
+    if (L == 0) {
+      res = r;
+      if (last5) memcpy(last5, last, sizeof last);
+      break;
+    }
+    if (r.status == DRF_ALIGN_LOST || r.status == DRF_ALIGN_DEGENERATE) { ++stats8[7]; continue; }
+    for (int i = 0; i < 16; ++i) p16[i] = (float)r.T[i];
+  }
+}
+// One evaluation at level L on the CPU: both full-resolution pairs reduced (max_jump_L), the level's model map (and Ym), then the
+// system of the rule above with the level's camera.  bgr null: the geometric system, counts[4] = 0.
+inline void track_pyramid_system_host(const LocateGrid &lg0, int L, const unsigned char *bgr, const float *depth, const unsigned char *model_bgr, const float *model_depth,
+                                      const float *model_pose16, const float *pose16, const TrackPyramidOpt &o, float voxel_size, double sums[28], uint64_t counts[5]) {
+  const bool colour = bgr != nullptr;
+  const TrackColourOpt lo = track_level_options(o, L);
+  const LocateGrid lg = track_level_grid(lg0, L);
+  const size_t npix = (size_t)lg.W * (size_t)lg.H;
+  std::vector<float> fd(npix), md(npix), Ym(colour ? npix : 0);
+  std::vector<unsigned char> fc(colour ? 3 * npix : 0), mc(colour ? 3 * npix : 0);
+  track_reduce_host(lg0.W, lg0.H, L, lo.t.max_jump, bgr, depth, fc.data(), fd.data());
+  track_reduce_host(lg0.W, lg0.H, L, lo.t.max_jump, colour ? model_bgr : nullptr, model_depth, mc.data(), md.data());
+  std::vector<TrackPixel> map(npix);
+  if (colour) track_model_colour_host(lg, lo.t.max_jump, md.data(), mc.data(), map.data(), Ym.data());
+  else track_model_host(lg, lo.t.max_jump, md.data(), map.data());
+  double c_src[3];
+  locate_centre_src(lo.t.centre_depth, voxel_size, c_src);
+  const AlignEval e = align_eval(map_motion(pose16, voxel_size), c_src, lo.t.a, voxel_size);
+  const TrackModel tm = track_model(model_pose16, lo.t, voxel_size, map.data());
+  counts[4] = 0;
+  if (colour) track_colour_system_host(lg, fc.data(), fd.data(), tm, track_colour(lo, Ym.data()), e, sums, counts);
+  else track_system_host(lg, fd.data(), tm, e, sums, counts);
+}
+// The whole coarse-to-fine tracking on the CPU over a renderer of the FULL-resolution images, render_both(pose16, Cm, Dm): the
+// library's reference for drf_track_pyramid_frame (bgr null: geometry only, Cm is not read), and what the sanitizer program runs.
+// A round of a level above 0 renders at full resolution, reduces to the level, and from there is track_colour_frame_host's.
+template <class RenderBoth>
+inline void track_pyramid_frame_host(const LocateGrid &lg0, const unsigned char *bgr, const float *depth, RenderBoth &&render_both, const float *pose_init16,
+                                     const TrackPyramidOpt &o, float voxel_size, drf_align_result_t &res, uint64_t stats8[8], uint64_t level4[kTrackMaxLevels][4],
+                                     uint64_t *last5 = nullptr, std::vector<std::array<double, 28>> *trace = nullptr) {
+  const bool colour = bgr != nullptr;
+  const size_t npix0 = (size_t)lg0.W * (size_t)lg0.H;
+  std::vector<float> Dm(npix0);
+  std::vector<unsigned char> Cm(npix0 * 3);
+  std::vector<std::vector<float>> fd((size_t)o.levels);
+  std::vector<std::vector<unsigned char>> fc((size_t)o.levels);
+  for (int L = 1; L < o.levels; ++L) {  // the frame, reduced once per call
+    const LocateGrid lg = track_level_grid(lg0, L);
+    fd[L].resize((size_t)lg.W * lg.H);
+    fc[L].resize(colour ? (size_t)lg.W * lg.H * 3 : 0);
+    track_reduce_host(lg0.W, lg0.H, L, track_level_options(o, L).t.max_jump, bgr, depth, fc[L].data(), fd[L].data());
+  }
+  track_pyramid_schedule([&](int L, const float *p16, const TrackColourOpt &lo, drf_align_result_t &r, uint64_t *last, uint64_t *st2) {
+    const LocateGrid lg = track_level_grid(lg0, L);
+    auto render_level = [&](const float *p, unsigned char *Cl, float *Dl) {
+      if (L == 0) { render_both(p, colour ? Cl : Cm.data(), Dl); return; }  // the renderer always has a colour image to write
+      render_both(p, Cm.data(), Dm.data());
+      track_reduce_host(lg0.W, lg0.H, L, lo.t.max_jump, colour ? Cm.data() : nullptr, Dm.data(), Cl, Dl);
+    };
+    const unsigned char *fbgr = L == 0 ? bgr : fc[L].data();
+    const float *fdepth = L == 0 ? depth : fd[L].data();
+    if (colour) track_colour_frame_host<5>(lg, fbgr, fdepth, render_level, p16, lo, voxel_size, r, last, st2, trace);
+    else track_colour_frame_host<4>(lg, nullptr, fdepth, render_level, p16, lo, voxel_size, r, last, st2, trace);
+  }, lg0, pose_init16, o, res, stats8, level4, last5);
+}
+
 }  // namespace dr

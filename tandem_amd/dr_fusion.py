@@ -504,6 +504,84 @@ class DrFusion:
         check(self._L.drf_track_colour_stats(self._h, out))
         return tuple(int(v) for v in out)
 
+    # ---- tracking coarse to fine (include/dr_mi355x.h drf_track_pyramid_frame, DESIGN.md "Tracking coarse to fine") ----
+    @staticmethod
+    def _track_pyramid_options(levels, coarse_renders, photo_weight, opt):
+        if not opt and not photo_weight and not levels and not coarse_renders:
+            return None
+        colour = DrFusion._track_colour_options(photo_weight, opt) or _lib.TrackColourOptions()
+        return _lib.TrackPyramidOptions(colour, levels, coarse_renders)
+
+    def track_reduce(self, level, max_jump, bgr, depth):
+        """The pyramid's reduction of a full-resolution pair to `level` (2^level x 2^level blocks; max_jump in metres is the
+        level's own): (bgr (H_L, W_L, 3) uint8 or None, depth (H_L, W_L) float32).  bgr None reduces the depth alone.  With integer
+        device pointers, bgr and depth are (input, output) pairs of them and nothing is returned."""
+        if isinstance(depth, tuple):
+            cin, cout = bgr if bgr is not None else (None, None)
+            check(self._L.drf_track_reduce_device(self._h, int(level), float(max_jump), cin, depth[0], cout, depth[1]))
+            return None
+        dev, d, keep = self._image(np.float32, 1, depth)
+        assert not dev
+        hl, wl = (self._hw[0] >> level, self._hw[1] >> level) if 0 <= level < 31 else (0, 0)
+        dout = np.zeros((hl, wl), np.float32)
+        c, cout = None, None
+        if bgr is not None:
+            _, c, ckeep = self._image(np.uint8, 3, bgr)
+            cout = np.zeros((hl, wl, 3), np.uint8)
+        check(self._L.drf_track_reduce(self._h, int(level), float(max_jump), c, d, C.c_void_p(cout.ctypes.data) if cout is not None else None,
+                                       dout.ctypes.data_as(_lib.f32p)))
+        return cout, dout
+
+    def track_pyramid_system(self, level, bgr, depth, model_bgr, model_depth, model_pose, pose, levels=0, coarse_renders=0, photo_weight=0.0, **opt):
+        """One evaluation at `level` of the pyramid: both full-resolution pairs are reduced to the level, then
+        track_colour_system's rule (bgr and model_bgr None: track_system's) with the level's camera: (sums (28,) float64, (samples,
+        valid, unassociated, rejected, photometric terms added)).  All images on the host or all integer device pointers."""
+        dev, d, keep = self._image(np.float32, 1, depth)
+        mdev, m, mkeep = self._image(np.float32, 1, model_depth)
+        assert dev == mdev, "all images on the host or all on the device"
+        c = mc = None
+        if bgr is not None:
+            cdev, c, ckeep = self._image(np.uint8, 3, bgr)
+            mcdev, mc, mckeep = self._image(np.uint8, 3, model_bgr)
+            assert dev == cdev == mcdev, "all images on the host or all on the device"
+        pose = np.ascontiguousarray(pose, np.float32).reshape(16)
+        mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
+        o = self._track_pyramid_options(levels, coarse_renders, photo_weight, opt)
+        sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 5)()
+        call = self._L.drf_track_pyramid_system_device if dev else self._L.drf_track_pyramid_system
+        check(call(self._h, int(level), c, d, mc, m, fptr(mpose), fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
+        return sums, tuple(int(v) for v in counts)
+
+    def track_pyramid_frame(self, bgr, depth, pose_init, raise_on_failure=True, levels=0, coarse_renders=0, photo_weight=0.0, **opt):
+        """track_colour_frame (bgr None: track_frame) coarse to fine: `levels` (0 = 3) halvings of frame and model, the coarsest
+        first with `coarse_renders` (0 = 3) renders each, then the full-resolution call from the pose they reach.  It cures a
+        render that aliases the map's texture and minima at the texture's scale; it is no global search.  levels=1 is the
+        single-level call bit for bit.  Returns level 0's AlignResult; then locate_frame(depth, result.T32)."""
+        dev, d, keep = self._image(np.float32, 1, depth)
+        c = None
+        if bgr is not None:
+            cdev, c, ckeep = self._image(np.uint8, 3, bgr)
+            assert dev == cdev, "both images on the host or both on the device"
+        pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
+        o = self._track_pyramid_options(levels, coarse_renders, photo_weight, opt)
+        T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
+        call = self._L.drf_track_pyramid_frame_device if dev else self._L.drf_track_pyramid_frame
+        check(call(self._h, c, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
+        return self._align_result(r, T32, raise_on_failure)
+
+    def track_pyramid_stats(self):
+        """Last track_reduce / track_pyramid_*: (grid positions, samples, valid samples -- each summed over the levels' last
+        evaluations -- evaluations, renders, device bytes held, levels run, levels abandoned)."""
+        out = (C.c_uint64 * 8)()
+        check(self._L.drf_track_pyramid_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def track_pyramid_level_stats(self, level):
+        """Level `level` of the last track_pyramid_frame: (status, renders, evaluations, valid samples at its last evaluation)."""
+        out = (C.c_uint64 * 4)()
+        check(self._L.drf_track_pyramid_level_stats(self._h, int(level), out))
+        return tuple(int(v) for v in out)
+
     def set_render_scope(self, scope, stage_capacity_blocks=0):
         """RENDER_RESIDENT (default): renders read the pool; RENDER_MAP: the pool and the host store -- any pose renders as on an
         engine whose pool never ran out, the stored blocks in reach staged through stage_capacity_blocks blocks of device scratch

@@ -141,6 +141,14 @@ public:
     check(drf_track_colour_frame(impl, bgr, depth, pose_init16, opt, pose16_out, &res));
     return res.status;
   }
+  // the same coarse to fine over an image pyramid (dr_mi355x.h drf_track_pyramid_frame): the cure where the map's texture is finer
+  // than a rendered pixel; no global search.  bgr null = geometry only, opt null = 3 levels.  Returns level 0's status.
+  int TrackPyramidFrame(unsigned char const *bgr, float const *depth, float const *pose_init16, float *pose16_out,
+                        drf_track_pyramid_options_t const *opt = nullptr) {
+    drf_align_result_t res;
+    check(drf_track_pyramid_frame(impl, bgr, depth, pose_init16, opt, pose16_out, &res));
+    return res.status;
+  }
   // DRF_LOCATE_MAP: LocateDepthFrame reads resident and host-stored blocks together, without moving one (capacity 0 = the default
   // staging); DRF_LOCATE_RESIDENT, the default: the pool only
   void SetLocateScope(int scope, size_t capacity = 0) { check(drf_set_locate_scope(impl, scope, capacity)); }

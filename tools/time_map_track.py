@@ -20,6 +20,10 @@ localisation (rotation in degrees, translation of the camera centre in voxels), 
 start in the same session: frame_s, frame_device_s, one_s, eval_s, render_s, the pose error after the tracking, and
 eval_ratio = its eval_s / the geometric eval_s -- the colour evaluation gathers three elements per sample where the geometric one
 gathers one.
+--pyramid adds, under "pyramid", drf_track_pyramid_frame with colour at 1, 3 and 4 levels (device pointers) next to
+drf_track_colour_frame from the same start in the same session: the call, where the camera centre ends, the per-level outcomes, one
+drf_track_reduce_device call per level 1 to 3, and coarse_round_s, one render + reduction + evaluation at the coarsest level (the
+difference of two calls of one render and one evaluation per level, with and without that level).
 Not measured: the kernels alone; k_track's fp64 share and the latency of its model gather (that takes counter runs of this tool, in
 runs of their own).
 One JSON line on stdout; --out writes it, ending with the box's gpu_state."""
@@ -56,6 +60,7 @@ def main():
     ap.add_argument("--num-blocks", type=int, default=400000)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--colour", action="store_true", help="also time drf_track_colour_frame")
+    ap.add_argument("--pyramid", action="store_true", help="also time drf_track_pyramid_frame at 1, 3 and 4 levels against drf_track_colour_frame")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.reps >= 3, "each figure is the median of at least 3 runs"
@@ -117,6 +122,40 @@ def main():
         colour.update(renders=stc[4], evaluations=stc[3], four_evaluations=stc4[3], status=ALIGN_STATUS[rc.status], device_bytes=stc[5], valid_at_start=rc.valid0,
                       valid_at_end=rc.valid, cost0=rc.cost0, cost=rc.cost, track_error_rotation_deg=rotc, track_error_translation_voxels=trc,
                       eval_ratio=(colour["eval_s"] / eval_s) if colour["eval_s"] and eval_s else None)
+    pyramid = None
+    if args.pyramid:
+        bgr, d_bgr = np.ascontiguousarray(frames["bgr"][k], np.uint8), C.c_void_p()
+        assert L.dr_device_alloc(0, bgr.nbytes, C.byref(d_bgr)) == 0 and L.dr_memcpy_h2d(d_bgr, bgr.ctypes.data_as(C.c_void_p), bgr.nbytes) == 0
+        bptr = int(d_bgr.value)
+        (rc, base_s, base_all) = timed(lambda: f.track_colour_frame(bptr, dptr, start, raise_on_failure=False, **o), args.reps)
+        rotc, trc = pose_error(rc.T, pose, vs)
+        pyramid = dict(colour_frame_device_s=base_s, colour_frame_device_all=base_all, colour_status=ALIGN_STATUS[rc.status], colour_error_rotation_deg=rotc,
+                       colour_error_translation_voxels=trc, levels={}, reduce_s={},
+                       not_measured="k_track_reduce alone (the reduce figures are whole calls with their synchronisation); what the unneeded full-resolution rays of "
+                                    "a coarse render cost against a render at the level's resolution; counters")
+        mj = 5.0 * vs
+        d_out, c_out = C.c_void_p(), C.c_void_p()
+        assert L.dr_device_alloc(0, depth.nbytes, C.byref(d_out)) == 0 and L.dr_device_alloc(0, bgr.nbytes, C.byref(c_out)) == 0
+        for lvl in (1, 2, 3):
+            _, s, runs = timed(lambda: f.track_reduce(lvl, mj * (1 << lvl), (bptr, int(c_out.value)), (dptr, int(d_out.value))), args.reps)
+            pyramid["reduce_s"][str(lvl)] = dict(s=s, all=runs)
+        L.dr_device_free(d_out)
+        L.dr_device_free(c_out)
+        for levels in (1, 3, 4):
+            rp, s, runs = timed(lambda: f.track_pyramid_frame(bptr, dptr, start, raise_on_failure=False, levels=levels, **o), args.reps)
+            stp = f.track_pyramid_stats()
+            rotp, trp = pose_error(rp.T, pose, vs)
+            entry = dict(frame_device_s=s, frame_device_all=runs, status=ALIGN_STATUS[rp.status], evaluations=stp[3], renders=stp[4], device_bytes=stp[5], levels_run=stp[6],
+                         levels_abandoned=stp[7], per_level={str(lv): f.track_pyramid_level_stats(lv) for lv in range(levels)}, error_rotation_deg=rotp,
+                         error_translation_voxels=trp)
+            if levels > 1:  # one coarse round at the coarsest level: (one render and evaluation there and at level 0) - (the same at level 0 alone)
+                _, two_l, _ = timed(lambda: f.track_pyramid_frame(bptr, dptr, start, raise_on_failure=False, levels=levels, coarse_renders=1,
+                                                                  **dict(o, max_renders=1, inner_iters=1)), args.reps)
+                _, two_m, _ = timed(lambda: f.track_pyramid_frame(bptr, dptr, start, raise_on_failure=False, levels=levels - 1, coarse_renders=1,
+                                                                  **dict(o, max_renders=1, inner_iters=1)), args.reps)
+                entry["coarse_round_s"] = two_l - two_m
+            pyramid["levels"][str(levels)] = entry
+        L.dr_device_free(d_bgr)
     la, locate_after_s, locate_after_all = timed(lambda: f.locate_frame(dptr, r.T32, raise_on_failure=False, centre_depth=cd), args.reps)
     alone = f.locate_frame(dptr, start, raise_on_failure=False, centre_depth=cd)
     L.dr_device_free(d_depth)
@@ -134,6 +173,8 @@ def main():
                not_measured="the kernels alone; k_track's fp64 share and the latency of its model gather; the phases of a render (plan, ray-cast, model map) apart")
     if colour is not None:
         out["colour"] = colour
+    if pyramid is not None:
+        out["pyramid"] = pyramid
     f.close()
     out["gpu_state"] = gpu_state()
     print(json.dumps(out), flush=True)
