@@ -723,6 +723,16 @@ __global__ __launch_bounds__(256) void k_publish(const unsigned char *__restrict
   for (size_t i = (qb << 4) + t; i < nb; i += nt) hb[i] = b[i];
 }
 
+// A (bgr, depth) image pair of the engine's camera as a tracking call is given it: both on the host, or both on the device.
+// bgr null: the depth alone.
+struct FramePair {
+  const void *bgr, *depth;
+  bool on_host;
+  static FramePair host(const uint8_t *bgr, const float *depth) { return {bgr, depth, true}; }
+  static FramePair device(const void *bgr, const void *depth) { return {bgr, depth, false}; }
+  bool has(bool colour) const { return depth && (!colour || bgr); }  // the images a call with or without colour reads
+};
+
 // ------------------------------------------------------------------ engine
 constexpr int kDefaultFusionPriority = 1;  // 0 least (the reference's), 1 normal (measured best in the TandemBackend loop), 2 greatest
 class FusionEngine {
@@ -1527,8 +1537,8 @@ class FusionEngine {
   }
   const uint64_t *align_stats() const { return mio_.al_stats; }
 
-  // ---- a camera pose from a frame: drf_locate_*, drf_track_*, drf_track_colour_* (the rules: pose_host.h; DESIGN.md "Where the
-  // frame-pose code lives").  What the three families open with, written once.  frame_prologue: the refusals in their one order --
+  // ---- a camera pose from a frame: drf_locate_*, drf_track_*, drf_track_colour_*, drf_track_pyramid_* (the rules: pose_host.h;
+  // DESIGN.md "Where the frame-pose code lives").  What the families open with, written once.  frame_prologue: the refusals in their one order --
   // the options (bad_option: what the family's resolver returned), the call order, blocks in the host store while streaming is
   // off, the pose, the model pose (the *_system calls of the tracking) -- then pending work settled.
   void frame_prologue(const char *who, const char *bad_option, const float *pose16, const float *model_pose16) {
@@ -1696,195 +1706,108 @@ class FusionEngine {
     for (int i = 0; i < 4; ++i) out[i] = ls_stats_[i];
   }
 
-  // A frame tracked against the ray-cast model, by its depth alone (F = TrackGeometric, drf_track_*; DESIGN.md §7c "Tracking a depth
-  // frame against the ray-cast model") or with the photometric term (F = TrackWithColour, drf_track_colour_*; "Tracking with
-  // colour").  The rule: pose_host.h track_normal / track_point / track_colour_point / track_loop.  One path for both; what differs
-  // is decided by F at compile time: the options, the scratch and statistics (tk_ or tc_: the colour calls leave drf_track_stats
-  // and its buffer what they were), the kernels, and the fifth counter -- k_align_fold hands back four; the photometric terms
-  // added leave through a pinned word.
-  // with_track does what the calls share -- the prologue, device scratch that is sized once -- and hands body the resolved options,
-  // the spans, an evaluator (k_track or k_track_colour + k_align_fold on int_stream_) and the model kernel's launch.  The model's
-  // render goes through the engine's one submit (render_passes) on int_stream_ into the scratch; renders_, free_slot_, next_ and
-  // the render statistics are not touched.
+  // A frame tracked against the ray-cast model: by its depth alone (drf_track_*; DESIGN.md §7c "Tracking a depth frame against the
+  // ray-cast model"), with the photometric term (drf_track_colour_*; "Tracking with colour"), or coarse to fine (drf_track_reduce,
+  // drf_track_pyramid_*; "Tracking coarse to fine").  The rule: pose_host.h track_normal / track_point / track_colour_point /
+  // track_loop and track_level_grid / track_reduce_host / track_pyramid_schedule.  One path for the three families (what it
+  // guarantees: DESIGN.md "Where the frame-pose code lives").  Every launch is given its level, and level 0 is the single-level
+  // call (track_level_grid returns the grid itself), so drf_track_* and drf_track_colour_* are the schedule with one level; colour
+  // is a run-time flag.  What differs is the side -- tk_, tc_ or tp_: each family its own scratch, in its own layout, its own
+  // statistics and model render, so a call of one family leaves the others' statistics and buffers what they were -- and what each
+  // entry does itself: its null arguments, its options, its refusal texts.
+  // with_track does what the calls share behind the prologue -- device scratch that is sized once, the frame's intake, the
+  // statistics reset when an exception passes -- and hands body the call: the spans and what track_launch_model, track_evaluate
+  // (k_track or k_track_colour + k_align_fold on int_stream_; k_align_fold hands back four counters, the photometric terms added
+  // leave through a pinned word) and track_render need.  The model's render goes through the engine's one submit (render_passes)
+  // on int_stream_ into the scratch; renders_, free_slot_, next_ and the render statistics are not touched.
   struct TrackSide {
-    DeviceBuf<unsigned char> buf;            // sized once
-    uint64_t stats[6] = {0, 0, 0, 0, 0, 0};  // drf_track_stats / drf_track_colour_stats
-    Render render{};                         // the *_frame call's model render: int_stream_ and pointers into buf
-    void reset() { for (auto &v : stats) v = 0; }
+    DeviceBuf<unsigned char> buf;             // sized once
+    uint64_t stats[8] = {};                   // drf_track_stats / drf_track_colour_stats (the first six), drf_track_pyramid_stats
+    uint64_t level[kTrackMaxLevels][4] = {};  // drf_track_pyramid_level_stats
+    Render render{};                          // the *_frame call's full-resolution model render: int_stream_ and pointers into buf
+    void reset() { memset(stats, 0, sizeof stats); memset(level, 0, sizeof level); }
   };
-  struct TrackBufs {
-    double *partial; unsigned long long *counts; int *flag; TrackPixel *map; float *model, *Ym, *frame; unsigned char *model_bgr, *frame_bgr;  // the spans
+  struct TrackBufs {  // the spans; a layout leaves null what it does not have
+    double *partial; unsigned long long *counts; int *flag; TrackPixel *map;
+    float *model, *level, *Ym, *frame, *pyr[kTrackMaxLevels];  // the full-resolution model, its level, Ym, a host-given frame, the frame's levels >= 1
+    unsigned char *model_bgr, *level_bgr, *frame_bgr, *pyr_bgr[kTrackMaxLevels];
     unsigned char *render_bgr; RayState *render_band;  // where the model's render puts its colour image and a banded render's ray state
-    const float *depth; const unsigned char *bgr;      // the frame: the caller's device images, or the spans a host frame went to
+    const float *depth; const unsigned char *bgr;      // the frame at full resolution: the caller's device images, or the spans a host frame went to
   };
-  template <class F>
-  TrackSide &track_side() { return F::N == 5 ? tc_ : tk_; }
-  // the frame's images (colour: both of them) on the host, or on the device
-  template <class F>
-  static bool track_has(const void *bgr, const void *depth) { return depth && (F::N == 4 || bgr); }
-  template <class F, class Body>
-  void with_track(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16, const float *model_pose16,
-                  const typename F::Options *opt, Body &&body) {
-    constexpr bool colour = F::N == 5;
-    TrackSide &s = track_side<F>();
-    s.reset();
-    typename F::Opt to;
-    frame_prologue(who, F::options(opt, o_.voxel_size, to), pose16, model_pose16);
-    const TrackOpt &geo = F::geo(to);
-    const FrameGrid fg = frame_grid(geo.step);
+  struct TrackCall { const char *who; TrackSide &s; bool colour; FrameGrid fg; TrackBufs b; };
+  // The three layouts (DESIGN.md "What the carver guarantees").  What of a render nobody reads once the model kernel runs may lie
+  // in the bytes that kernel then overwrites with the model map: a banded render's per-pixel ray state in both single-level
+  // layouts, and in the geometric one the colour image too (with colour k_track_model_colour reads it: it has the span model_bgr).
+  // The pyramid's is sized for five levels with nothing aliased.
+  TrackBufs track_spans(TrackSide &s) {
     TrackBufs b{};
-    carve(s.buf, int_stream_, [&](Carver &c) {
-      b.partial = c.take<double>(fg.max_groups * 28);
-      b.counts = c.take<unsigned long long>(colour ? 6 : 4);  // four that k_align_fold hands back; with colour the fifth (and one unused)
-      b.flag = c.take<int>(1);                                // the ray-cast's flag counter
-      b.map = c.take<TrackPixel>(npix_, 32);                  // the model map
-      b.model = c.take<float>(npix_);                         // the model's depth: rendered, or a host-given one
-      if (colour) b.Ym = c.take<float>(npix_);
-      b.frame = c.take<float>(npix_);                         // a host-given frame
-      if (colour) { b.model_bgr = c.take<unsigned char>(npix_ * 3); b.frame_bgr = c.take<unsigned char>(npix_ * 3); }
-      // The one aliasing: what of a render nobody reads once the model kernel runs lies in the bytes that kernel then overwrites
-      // with the model map -- a banded render's per-pixel ray state, and in the geometric call the colour image too (with colour
-      // k_track_model_colour reads it: it has the span model_bgr).
-      b.render_bgr = colour ? b.model_bgr : (unsigned char *)b.map;
-      b.render_band = (RayState *)(colour ? (unsigned char *)b.map : (unsigned char *)b.map + npix_ * 8);
-    });
+    const size_t max_groups = frame_grid(1).max_groups;
+    auto head = [&](Carver &c, size_t counters) {
+      b.partial = c.take<double>(max_groups * 28);
+      b.counts = c.take<unsigned long long>(counters);  // four that k_align_fold hands back; with colour the fifth (and one unused)
+      b.flag = c.take<int>(1);                          // the ray-cast's flag counter
+      b.map = c.take<TrackPixel>(npix_, 32);            // the model map
+    };
+    if (&s == &tk_) {
+      carve(s.buf, int_stream_, [&](Carver &c) {
+        head(c, 4);
+        b.model = c.take<float>(npix_);  // the model's depth: rendered, or a host-given one
+        b.frame = c.take<float>(npix_);
+        b.render_bgr = (unsigned char *)b.map;
+        b.render_band = (RayState *)((unsigned char *)b.map + npix_ * 8);
+      });
+    } else if (&s == &tc_) {
+      carve(s.buf, int_stream_, [&](Carver &c) {
+        head(c, 6);
+        b.model = c.take<float>(npix_);
+        b.Ym = c.take<float>(npix_);
+        b.frame = c.take<float>(npix_);
+        b.model_bgr = c.take<unsigned char>(npix_ * 3);
+        b.frame_bgr = c.take<unsigned char>(npix_ * 3);
+        b.render_bgr = b.model_bgr;
+        b.render_band = (RayState *)b.map;
+      });
+    } else {
+      auto level_pixels = [&](int L) { return std::max<size_t>(1, (size_t)(o_.width >> L) * (size_t)(o_.height >> L)); };
+      carve(s.buf, int_stream_, [&](Carver &c) {
+        head(c, 6);
+        b.render_band = c.take<RayState>(npix_, 8);
+        b.model = c.take<float>(npix_);
+        b.level = c.take<float>(level_pixels(1));
+        b.Ym = c.take<float>(npix_);
+        b.frame = c.take<float>(npix_);
+        for (int L = 1; L < kTrackMaxLevels; ++L) b.pyr[L] = c.take<float>(level_pixels(L));
+        b.model_bgr = c.take<unsigned char>(npix_ * 3);
+        b.level_bgr = c.take<unsigned char>(level_pixels(1) * 3);
+        b.frame_bgr = c.take<unsigned char>(npix_ * 3);
+        for (int L = 1; L < kTrackMaxLevels; ++L) b.pyr_bgr[L] = c.take<unsigned char>(level_pixels(L) * 3);
+        b.render_bgr = b.model_bgr;
+      });
+    }
+    return b;
+  }
+  // the frame: device images where they lie, or a host pair (without colour: the depth alone) through upload_frame into the spans
+  void track_intake(TrackBufs &b, bool colour, const FramePair &frame) {
+    b.depth = (const float *)frame.depth;
+    b.bgr = (const unsigned char *)frame.bgr;
+    if (!frame.on_host) return;
+    upload_frame((const uint8_t *)frame.bgr, (const float *)frame.depth, colour ? b.frame_bgr : nullptr, b.frame);
+    b.depth = b.frame;
+    b.bgr = colour ? b.frame_bgr : nullptr;
+  }
+  template <class Body>
+  void with_track(const char *who, TrackSide &s, bool colour, const FramePair &frame, int step, Body &&body) {
+    TrackCall t{who, s, colour, frame_grid(step), track_spans(s)};
     if (colour && !tc_fifth_) tc_fifth_ = own_.pinned<unsigned long long>(1);
     mio_.ensure(1);
-    b.depth = (const float *)d_depth;
-    b.bgr = (const unsigned char *)d_bgr;
-    if (h_depth) {
-      upload_frame(h_bgr, h_depth, b.frame_bgr, b.frame);
-      b.depth = b.frame;
-      b.bgr = b.frame_bgr;
-    }
-    s.stats[0] = (uint64_t)fg.total; s.stats[5] = s.buf.capacity();
-    auto model = [&](const float *depth_m, const unsigned char *bgr_m) {  // the model map (and Ym) of one model image
-      if constexpr (colour) hipLaunchKernelGGL(k_track_model_colour, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, depth_m, bgr_m, fg.lg, geo.max_jump, b.map, b.Ym);
-      else hipLaunchKernelGGL(k_track_model, dim3(cdiv((int)npix_, 256)), dim3(256), 0, int_stream_, depth_m, fg.lg, geo.max_jump, b.map);
-      DR_HIP(hipGetLastError());
-    };
-    auto eval = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t *c) {  // c[F::N]
-      const TrackModel tm = track_model(mp16, geo, o_.voxel_size, b.map);
-      mio_.evaluate(b.partial, fg.groups, b.counts, 4, sums, c, [&] {
-        if constexpr (colour) {
-          DR_HIP(hipMemsetAsync(b.counts + 4, 0, 8, int_stream_));
-          hipLaunchKernelGGL(k_track_colour, dim3(cdiv(fg.groups, 4)), dim3(256), 0, int_stream_, b.depth, b.bgr, fg.lg, e, tm, track_colour(to, b.Ym), fg.groups, fg.total,
-                             b.partial, b.counts);
-          DR_HIP(hipGetLastError());
-          DR_HIP(hipMemcpyAsync(tc_fifth_, b.counts + 4, 8, hipMemcpyDeviceToHost, int_stream_));
-        } else {
-          hipLaunchKernelGGL(k_track, dim3(cdiv(fg.groups, 4)), dim3(256), 0, int_stream_, b.depth, fg.lg, e, tm, fg.groups, fg.total, b.partial, b.counts);
-          DR_HIP(hipGetLastError());
-        }
-      });
-      if constexpr (colour) c[4] = *tc_fifth_;
-      s.stats[1] = c[0]; s.stats[2] = c[1]; ++s.stats[3];
-    };
+    track_intake(t.b, colour, frame);
+    s.stats[5] = s.buf.capacity();
     try {
-      body(geo, b, eval, model);
+      body(t);
     } catch (...) {
       s.reset();
       throw;
     }
-  }
-  // one evaluation against a model image the caller gives (geometric: every bgr argument is null)
-  template <class F>
-  void track_system(const char *who, const uint8_t *h_bgr, const float *h_depth, const uint8_t *h_model_bgr, const float *h_model, const void *d_bgr, const void *d_depth,
-                    const void *d_model_bgr, const void *d_model, const float *model_pose16, const float *pose16, const typename F::Options *opt, double *sums,
-                    uint64_t *counts) {
-    track_side<F>().reset();
-    if (!(track_has<F>(h_bgr, h_depth) || track_has<F>(d_bgr, d_depth)) || !(track_has<F>(h_model_bgr, h_model) || track_has<F>(d_model_bgr, d_model)) || !model_pose16 ||
-        !pose16 || !sums || !counts)
-      fail(DR_ERR_ARG, "%s: null argument", who);
-    with_track<F>(who, h_bgr, h_depth, d_bgr, d_depth, pose16, model_pose16, opt, [&](const TrackOpt &geo, const TrackBufs &b, auto &eval, auto &model) {
-      if (h_model) {
-        upload_frame(h_model_bgr, h_model, b.model_bgr, b.model, true);
-        model(b.model, b.model_bgr);
-      } else {
-        model((const float *)d_model, (const unsigned char *)d_model_bgr);
-      }
-      double c_src[3];
-      locate_centre_src(geo.centre_depth, o_.voxel_size, c_src);
-      eval(align_eval(map_motion(pose16, o_.voxel_size), c_src, geo.a, o_.voxel_size), model_pose16, sums, counts);
-    });
-  }
-  // returns what dr_last_error() says after a tracking that ran but found no pose (empty otherwise)
-  template <class F>
-  std::string track_frame(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
-                          const typename F::Options *opt, float *pose16_out, drf_align_result_t *res) {
-    TrackSide &s = track_side<F>();
-    s.reset();
-    if (!(track_has<F>(h_bgr, h_depth) || track_has<F>(d_bgr, d_depth)) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
-    drf_align_result_t r;
-    uint64_t c[F::N] = {};
-    with_track<F>(who, h_bgr, h_depth, d_bgr, d_depth, pose16, nullptr, opt, [&](const TrackOpt &geo, const TrackBufs &b, auto &eval, auto &model) {
-      if (!s.render.cast) { s.render.cast = own_.event(); s.render.done = own_.event(); }
-      s.render.stream = int_stream_;
-      s.render.d_bgr = b.render_bgr;
-      s.render.d_band = b.render_band;
-      s.render.d_depth = b.model;
-      s.render.d_flag = b.flag;
-      auto render = [&](const float *p16) {
-        RenderStagePlan plan;
-        RenderBandPlan bands;
-        bool waited = false;
-        const float *poses[1] = {p16};
-        if (render_scope_ == DRF_RENDER_MAP) plan_render_call(who, poses, 1, plan, bands, waited);
-        render_passes(plan, bands, &s.render, poses, 1, false);
-        model(b.model, b.model_bgr);
-        ++s.stats[4];
-      };
-      track_loop<F::N>(render, eval, pose16, geo, o_.voxel_size, r, c);
-    });
-    for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
-    if (res) *res = r;
-    return no_pose_note(std::string(who) + ": the tracking", r,
-                        ", " + std::to_string((unsigned long long)c[2]) + " unassociated, " + std::to_string((unsigned long long)c[3]) + " rejected" +
-                            (F::N == 5 ? ", " + std::to_string((unsigned long long)c[F::N - 1]) + " with a colour term; " : std::string("; ")) +
-                            std::to_string((unsigned long long)s.stats[4]) + " renders; " + std::to_string(store_.size()) + " blocks are in the host store)");
-  }
-  const uint64_t *track_stats() const { return tk_.stats; }
-  const uint64_t *track_colour_stats() const { return tc_.stats; }
-
-  // A frame tracked coarse to fine (drf_track_reduce, drf_track_pyramid_*; DESIGN.md §7c "Tracking coarse to fine").  The rule:
-  // pose_host.h track_level_grid / track_reduce_host / track_pyramid_schedule.  with_track's shape, with colour decided by the
-  // images given (bgr null: the geometric kernels) and every launch given its level: k_track_reduce brings a full-resolution pair
-  // to the level, k_track_model(_colour) and k_track(_colour) run unchanged on the level's LocateGrid.  Scratch and statistics are
-  // these calls' own (tp_), sized once for five levels with nothing aliased; tk_, tc_ and the public render are not touched.
-  struct PyramidSide {
-    DeviceBuf<unsigned char> buf;  // sized once
-    uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // drf_track_pyramid_stats
-    uint64_t level[kTrackMaxLevels][4] = {};       // drf_track_pyramid_level_stats
-    Render render{};                               // the model's full-resolution render: int_stream_ and pointers into buf
-    void reset() { memset(stats, 0, sizeof stats); memset(level, 0, sizeof level); }
-  };
-  struct PyramidBufs {
-    double *partial; unsigned long long *counts; int *flag; TrackPixel *map; RayState *band;
-    float *model, *level, *Ym, *frame, *pyr[kTrackMaxLevels];                          // the full-resolution model, its level, Ym, a host-given frame, the frame's levels >= 1
-    unsigned char *model_bgr, *level_bgr, *frame_bgr, *pyr_bgr[kTrackMaxLevels];
-    const float *depth; const unsigned char *bgr;  // the frame at full resolution: the caller's device images, or the spans a host frame went to
-  };
-  PyramidBufs pyramid_bufs() {
-    PyramidBufs b{};
-    const size_t max_groups = (npix_ + 511) / 512;
-    auto level_pixels = [&](int L) { return std::max<size_t>(1, (size_t)(o_.width >> L) * (size_t)(o_.height >> L)); };
-    carve(tp_.buf, int_stream_, [&](Carver &c) {
-      b.partial = c.take<double>(max_groups * 28);
-      b.counts = c.take<unsigned long long>(6);
-      b.flag = c.take<int>(1);
-      b.map = c.take<TrackPixel>(npix_, 32);
-      b.band = c.take<RayState>(npix_, 8);
-      b.model = c.take<float>(npix_);
-      b.level = c.take<float>(level_pixels(1));
-      b.Ym = c.take<float>(npix_);
-      b.frame = c.take<float>(npix_);
-      for (int L = 1; L < kTrackMaxLevels; ++L) b.pyr[L] = c.take<float>(level_pixels(L));
-      b.model_bgr = c.take<unsigned char>(npix_ * 3);
-      b.level_bgr = c.take<unsigned char>(level_pixels(1) * 3);
-      b.frame_bgr = c.take<unsigned char>(npix_ * 3);
-      for (int L = 1; L < kTrackMaxLevels; ++L) b.pyr_bgr[L] = c.take<unsigned char>(level_pixels(L) * 3);
-    });
-    return b;
   }
   void launch_reduce(const float *depth, const unsigned char *bgr, int L, float max_jump, float *depth_out, unsigned char *bgr_out) {
     const int WL = o_.width >> L, HL = o_.height >> L;
@@ -1892,13 +1815,143 @@ class FusionEngine {
     hipLaunchKernelGGL(k_track_reduce, dim3(cdiv(threads, 256)), dim3(256), 0, int_stream_, depth, bgr, o_.width, WL, HL, L, max_jump, depth_out, bgr_out);
     DR_HIP(hipGetLastError());
   }
-  // level null: drf_track_pyramid_frame; otherwise the level of a drf_track_pyramid_system, judged with the options.  body(po, b,
-  // colour, fg, model, eval): model(L, lo) turns the full-resolution model in b.model / b.model_bgr into level L's model map (and
-  // Ym); eval(L, lo, e, model_pose16, sums, counts) is one evaluation of level L against it.
-  template <class Body>
-  void with_track_pyramid(const char *who, const int *level, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
-                          const float *model_pose16, const drf_track_pyramid_options_t *opt, Body &&body) {
-    tp_.reset();
+  // level L's model map (with colour: and Ym) from a full-resolution model pair, reduced to the level first above level 0.  The
+  // geometric kernels never read bgr_m: in the geometric layout the render's colour image lies in the model map.
+  void track_launch_model(const TrackCall &t, const float *depth_m, const unsigned char *bgr_m, int L, const TrackColourOpt &lo) {
+    const LocateGrid lg = track_level_grid(t.fg.lg, L);
+    if (L > 0) {
+      launch_reduce(depth_m, t.colour ? bgr_m : nullptr, L, lo.t.max_jump, t.b.level, t.b.level_bgr);
+      depth_m = t.b.level; bgr_m = t.b.level_bgr;
+    }
+    const int np = lg.W * lg.H;
+    if (t.colour) hipLaunchKernelGGL(k_track_model_colour, dim3(cdiv(np, 256)), dim3(256), 0, int_stream_, depth_m, bgr_m, lg, lo.t.max_jump, t.b.map, t.b.Ym);
+    else hipLaunchKernelGGL(k_track_model, dim3(cdiv(np, 256)), dim3(256), 0, int_stream_, depth_m, lg, lo.t.max_jump, t.b.map);
+    DR_HIP(hipGetLastError());
+  }
+  // one evaluation of level L against the model map; c[5] with colour, c[4] without
+  void track_evaluate(const TrackCall &t, int L, const TrackColourOpt &lo, const AlignEval &e, const float *model_pose16, double sums[28], uint64_t *c) {
+    const TrackBufs &b = t.b;
+    const LocateGrid lg = track_level_grid(t.fg.lg, L);
+    const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
+    const float *fd = L == 0 ? b.depth : b.pyr[L];
+    const unsigned char *fc = L == 0 ? b.bgr : b.pyr_bgr[L];
+    const TrackModel tm = track_model(model_pose16, lo.t, o_.voxel_size, b.map);
+    mio_.evaluate(b.partial, groups, b.counts, 4, sums, c, [&] {
+      if (t.colour) {
+        DR_HIP(hipMemsetAsync(b.counts + 4, 0, 8, int_stream_));
+        hipLaunchKernelGGL(k_track_colour, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, fd, fc, lg, e, tm, track_colour(lo, b.Ym), groups, total, b.partial, b.counts);
+        DR_HIP(hipGetLastError());
+        DR_HIP(hipMemcpyAsync(tc_fifth_, b.counts + 4, 8, hipMemcpyDeviceToHost, int_stream_));
+      } else {
+        hipLaunchKernelGGL(k_track, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, fd, lg, e, tm, groups, total, b.partial, b.counts);
+        DR_HIP(hipGetLastError());
+      }
+    });
+    if (t.colour) c[4] = *tc_fifth_;
+  }
+  // the model of a *_frame round: the engine's one submit at full resolution into the spans, then level L's model map
+  void track_render(const TrackCall &t, int L, const TrackColourOpt &lo, const float *pose16) {
+    Render &rd = t.s.render;
+    if (!rd.cast) { rd.cast = own_.event(); rd.done = own_.event(); }
+    rd.stream = int_stream_;
+    rd.d_bgr = t.b.render_bgr;
+    rd.d_band = t.b.render_band;
+    rd.d_depth = t.b.model;
+    rd.d_flag = t.b.flag;
+    RenderStagePlan plan;
+    RenderBandPlan bands;
+    bool waited = false;
+    const float *poses[1] = {pose16};
+    if (render_scope_ == DRF_RENDER_MAP) plan_render_call(t.who, poses, 1, plan, bands, waited);
+    render_passes(plan, bands, &rd, poses, 1, false);
+    track_launch_model(t, t.b.model, t.b.model_bgr, L, lo);
+  }
+  // The body of every *_system call: one evaluation at `level` against a full-resolution model pair the caller gives, n counters
+  // out.  A host-given model goes through upload_frame into the spans.  A device-given one is read in place by the single-level
+  // calls and copied into the spans by the pyramid's: track_launch_model could read that one in place too, but the copy is part
+  // of what drf_track_pyramid_system_device enqueues, and stays.
+  void track_system_at(const char *who, TrackSide &s, bool colour, int level, const TrackPyramidOpt &po, const FramePair &frame, const FramePair &model,
+                       const float *model_pose16, const float *pose16, double *sums, uint64_t *counts, int n) {
+    with_track(who, s, colour, frame, po.c.t.step, [&](TrackCall &t) {
+      const TrackBufs &b = t.b;
+      const TrackColourOpt lo = track_level_options(po, level);
+      if (level > 0) launch_reduce(b.depth, b.bgr, level, lo.t.max_jump, b.pyr[level], b.pyr_bgr[level]);
+      const float *depth_m = b.model;
+      const unsigned char *bgr_m = b.model_bgr;
+      if (model.on_host) {
+        upload_frame((const uint8_t *)model.bgr, (const float *)model.depth, colour ? b.model_bgr : nullptr, b.model, true);
+      } else if (&s == &tp_) {
+        DR_HIP(hipMemcpyAsync(b.model, model.depth, npix_ * 4, hipMemcpyDeviceToDevice, int_stream_));
+        if (colour) DR_HIP(hipMemcpyAsync(b.model_bgr, model.bgr, npix_ * 3, hipMemcpyDeviceToDevice, int_stream_));
+      } else {
+        depth_m = (const float *)model.depth; bgr_m = (const unsigned char *)model.bgr;
+      }
+      track_launch_model(t, depth_m, bgr_m, level, lo);
+      double c_src[3];
+      locate_centre_src(lo.t.centre_depth, o_.voxel_size, c_src);
+      uint64_t c[5] = {0, 0, 0, 0, 0};
+      track_evaluate(t, level, lo, align_eval(map_motion(pose16, o_.voxel_size), c_src, lo.t.a, o_.voxel_size), model_pose16, sums, c);
+      for (int i = 0; i < n; ++i) counts[i] = c[i];
+      s.stats[0] = (uint64_t)locate_positions(track_level_grid(t.fg.lg, level)); s.stats[1] = c[0]; s.stats[2] = c[1]; s.stats[3] = 1; s.stats[6] = 1;
+      s.level[level][2] = 1; s.level[level][3] = c[1];
+    });
+  }
+  // The body of every *_frame call: the frame reduced once to every level above 0, then track_pyramid_schedule over track_loop;
+  // po.levels = 1 is the single-level call.  r: level 0's result; last: the counters of its last evaluation.
+  void track_levels(const char *who, TrackSide &s, bool colour, const TrackPyramidOpt &po, const FramePair &frame, const float *pose16, drf_align_result_t &r,
+                    uint64_t last[5]) {
+    with_track(who, s, colour, frame, po.c.t.step, [&](TrackCall &t) {
+      for (int L = 1; L < po.levels; ++L) launch_reduce(t.b.depth, t.b.bgr, L, track_level_options(po, L).t.max_jump, t.b.pyr[L], t.b.pyr_bgr[L]);
+      track_pyramid_schedule([&](int L, const float *p16, const TrackColourOpt &lo, drf_align_result_t &lr, uint64_t *lc, uint64_t *st2) {
+        auto render = [&](const float *p) { track_render(t, L, lo, p); };
+        auto eval = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t *c) { track_evaluate(t, L, lo, e, mp16, sums, c); };
+        if (colour) track_loop<5>(render, eval, p16, lo.t, o_.voxel_size, lr, lc, st2);
+        else track_loop<4>(render, eval, p16, lo.t, o_.voxel_size, lr, lc, st2);
+      }, t.fg.lg, pose16, po, r, s.stats, s.level, last);
+    });
+  }
+  // hands out the pose and returns what dr_last_error() says after a tracking that ran but found no pose (empty otherwise)
+  std::string track_note(const char *who, const TrackSide &s, const drf_align_result_t &r, const uint64_t last[5], const std::string &own, float *pose16_out,
+                         drf_align_result_t *res) {
+    for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
+    if (res) *res = r;
+    return no_pose_note(std::string(who) + ": the tracking", r,
+                        ", " + std::to_string((unsigned long long)last[2]) + " unassociated, " + std::to_string((unsigned long long)last[3]) + " rejected" + own +
+                            std::to_string((unsigned long long)s.stats[4]) + " renders; " + std::to_string(store_.size()) + " blocks are in the host store)");
+  }
+  // The single-level families: Options is drf_track_options_t (geometric: every bgr is null) or drf_track_colour_options_t.
+  static const char *track_options_of(const drf_track_options_t *u, float voxel_size, TrackColourOpt &o) { o.photo_weight = 0.0f; return track_options(u, voxel_size, o.t); }
+  static const char *track_options_of(const drf_track_colour_options_t *u, float voxel_size, TrackColourOpt &o) { return track_colour_options(u, voxel_size, o); }
+  template <class Options>
+  void track_system(const char *who, const FramePair &frame, const FramePair &model, const float *model_pose16, const float *pose16, const Options *opt, double *sums,
+                    uint64_t *counts) {
+    constexpr bool colour = std::is_same<Options, drf_track_colour_options_t>::value;
+    TrackSide &s = colour ? tc_ : tk_;
+    s.reset();
+    if (!frame.has(colour) || !model.has(colour) || !model_pose16 || !pose16 || !sums || !counts) fail(DR_ERR_ARG, "%s: null argument", who);
+    TrackPyramidOpt po{{}, 1, 0};
+    frame_prologue(who, track_options_of(opt, o_.voxel_size, po.c), pose16, model_pose16);
+    track_system_at(who, s, colour, 0, po, frame, model, model_pose16, pose16, sums, counts, colour ? 5 : 4);
+  }
+  template <class Options>
+  std::string track_frame(const char *who, const FramePair &frame, const float *pose16, const Options *opt, float *pose16_out, drf_align_result_t *res) {
+    constexpr bool colour = std::is_same<Options, drf_track_colour_options_t>::value;
+    TrackSide &s = colour ? tc_ : tk_;
+    s.reset();
+    if (!frame.has(colour) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+    TrackPyramidOpt po{{}, 1, 0};
+    frame_prologue(who, track_options_of(opt, o_.voxel_size, po.c), pose16, nullptr);
+    drf_align_result_t r;
+    uint64_t last[5] = {0, 0, 0, 0, 0};
+    track_levels(who, s, colour, po, frame, pose16, r, last);
+    return track_note(who, s, r, last, colour ? ", " + std::to_string((unsigned long long)last[4]) + " with a colour term; " : std::string("; "), pose16_out, res);
+  }
+  const uint64_t *track_stats() const { return tk_.stats; }
+  const uint64_t *track_colour_stats() const { return tc_.stats; }
+
+  // The pyramid family: colour is decided by the images given (bgr null: the geometric kernels).
+  // level null: drf_track_pyramid_frame; otherwise the level of a drf_track_pyramid_system, judged with the options.
+  TrackPyramidOpt track_pyramid_resolve(const char *who, const drf_track_pyramid_options_t *opt, const int *level) {
     TrackPyramidOpt po;
     if (const char *bad = track_pyramid_options(opt, o_.voxel_size, o_.width, o_.height, po))
       fail(DR_ERR_ARG, "%s: option %s is negative, not finite or out of range (levels <= %d, every level at least %d pixels on a side)", who, bad, kTrackMaxLevels,
@@ -1906,153 +1959,52 @@ class FusionEngine {
     if (level && !track_level_fits(o_.width, o_.height, *level))
       fail(DR_ERR_ARG, "%s: level %d is outside 0..%d or below %d pixels on a side of the %dx%d camera", who, *level, kTrackMaxLevels - 1, kTrackMinLevelSide, o_.height,
            o_.width);
-    frame_prologue(who, nullptr, pose16, model_pose16);
-    const bool colour = h_depth ? h_bgr != nullptr : d_bgr != nullptr;
-    const FrameGrid fg = frame_grid(po.c.t.step);
-    PyramidBufs b = pyramid_bufs();
-    if (colour && !tc_fifth_) tc_fifth_ = own_.pinned<unsigned long long>(1);
-    mio_.ensure(1);
-    b.depth = (const float *)d_depth;
-    b.bgr = (const unsigned char *)d_bgr;
-    if (h_depth) {
-      upload_frame(h_bgr, h_depth, colour ? b.frame_bgr : nullptr, b.frame);
-      b.depth = b.frame;
-      b.bgr = colour ? b.frame_bgr : nullptr;
-    }
-    tp_.stats[5] = tp_.buf.capacity();
-    auto model = [&](int L, const TrackColourOpt &lo) {
-      const LocateGrid lg = track_level_grid(fg.lg, L);
-      const float *dm = b.model;
-      const unsigned char *cm = b.model_bgr;
-      if (L > 0) {
-        launch_reduce(b.model, colour ? b.model_bgr : nullptr, L, lo.t.max_jump, b.level, b.level_bgr);
-        dm = b.level; cm = b.level_bgr;
-      }
-      const int np = lg.W * lg.H;
-      if (colour) hipLaunchKernelGGL(k_track_model_colour, dim3(cdiv(np, 256)), dim3(256), 0, int_stream_, dm, cm, lg, lo.t.max_jump, b.map, b.Ym);
-      else hipLaunchKernelGGL(k_track_model, dim3(cdiv(np, 256)), dim3(256), 0, int_stream_, dm, lg, lo.t.max_jump, b.map);
-      DR_HIP(hipGetLastError());
-    };
-    auto eval = [&](int L, const TrackColourOpt &lo, const AlignEval &e, const float *mp16, double sums[28], uint64_t *c) {  // c[5] with colour, c[4] without
-      const LocateGrid lg = track_level_grid(fg.lg, L);
-      const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
-      const float *fd = L == 0 ? b.depth : b.pyr[L];
-      const unsigned char *fc = L == 0 ? b.bgr : b.pyr_bgr[L];
-      const TrackModel tm = track_model(mp16, lo.t, o_.voxel_size, b.map);
-      mio_.evaluate(b.partial, groups, b.counts, 4, sums, c, [&] {
-        if (colour) {
-          DR_HIP(hipMemsetAsync(b.counts + 4, 0, 8, int_stream_));
-          hipLaunchKernelGGL(k_track_colour, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, fd, fc, lg, e, tm, track_colour(lo, b.Ym), groups, total, b.partial, b.counts);
-          DR_HIP(hipGetLastError());
-          DR_HIP(hipMemcpyAsync(tc_fifth_, b.counts + 4, 8, hipMemcpyDeviceToHost, int_stream_));
-        } else {
-          hipLaunchKernelGGL(k_track, dim3(cdiv(groups, 4)), dim3(256), 0, int_stream_, fd, lg, e, tm, groups, total, b.partial, b.counts);
-          DR_HIP(hipGetLastError());
-        }
-      });
-      if (colour) c[4] = *tc_fifth_;
-    };
-    try {
-      body(po, b, colour, fg, model, eval);
-    } catch (...) {
-      tp_.reset();
-      throw;
-    }
+    return po;
   }
-  // the reduction alone: host images through the scratch, or device images in place
-  void track_reduce(const char *who, int level, float max_jump, const uint8_t *h_bgr, const float *h_depth, uint8_t *h_bgr_out, float *h_depth_out, const void *d_bgr,
-                    const void *d_depth, void *d_bgr_out, void *d_depth_out) {
+  // the reduction alone: a host pair through the scratch, or device images in place
+  void track_reduce(const char *who, int level, float max_jump, const FramePair &in, void *bgr_out, void *depth_out) {
     tp_.reset();
-    const bool host = h_depth != nullptr;
-    if (host ? (!h_depth_out || (h_bgr && !h_bgr_out)) : (!d_depth || !d_depth_out || (d_bgr && !d_bgr_out))) fail(DR_ERR_ARG, "%s: null argument", who);
+    if (!in.depth || !depth_out || (in.bgr && !bgr_out)) fail(DR_ERR_ARG, "%s: null argument", who);
     if (!(max_jump >= 0.0f) || !std::isfinite(max_jump)) fail(DR_ERR_ARG, "%s: option max_jump is negative or not finite", who);
     if (!track_level_fits(o_.width, o_.height, level))
       fail(DR_ERR_ARG, "%s: level %d is outside 0..%d or below %d pixels on a side of the %dx%d camera", who, level, kTrackMaxLevels - 1, kTrackMinLevelSide, o_.height,
            o_.width);
     expect_integrate(who);
     settle();
-    const size_t nl = (size_t)(o_.width >> level) * (size_t)(o_.height >> level);
-    if (host) {
-      PyramidBufs b = pyramid_bufs();
-      upload_frame(h_bgr, h_depth, h_bgr ? b.frame_bgr : nullptr, b.frame);
-      launch_reduce(b.frame, h_bgr ? b.frame_bgr : nullptr, level, max_jump, b.model, b.model_bgr);  // the model's full-resolution spans hold any level
-      DR_HIP(hipMemcpyAsync(h_depth_out, b.model, nl * 4, hipMemcpyDeviceToHost, int_stream_));
-      if (h_bgr) DR_HIP(hipMemcpyAsync(h_bgr_out, b.model_bgr, nl * 3, hipMemcpyDeviceToHost, int_stream_));
+    if (in.on_host) {
+      const size_t nl = (size_t)(o_.width >> level) * (size_t)(o_.height >> level);
+      TrackBufs b = track_spans(tp_);
+      track_intake(b, in.bgr != nullptr, in);
+      launch_reduce(b.depth, b.bgr, level, max_jump, b.model, b.model_bgr);  // the model's full-resolution spans hold any level
+      DR_HIP(hipMemcpyAsync(depth_out, b.model, nl * 4, hipMemcpyDeviceToHost, int_stream_));
+      if (in.bgr) DR_HIP(hipMemcpyAsync(bgr_out, b.model_bgr, nl * 3, hipMemcpyDeviceToHost, int_stream_));
     } else {
-      launch_reduce((const float *)d_depth, (const unsigned char *)d_bgr, level, max_jump, (float *)d_depth_out, (unsigned char *)d_bgr_out);
+      launch_reduce((const float *)in.depth, (const unsigned char *)in.bgr, level, max_jump, (float *)depth_out, (unsigned char *)bgr_out);
     }
     DR_HIP(hipStreamSynchronize(int_stream_));
     tp_.stats[5] = tp_.buf.capacity();
   }
-  // one evaluation at `level` against a full-resolution model pair the caller gives (bgr null: geometric, counts[4] = 0)
-  void track_pyramid_system(const char *who, int level, const uint8_t *h_bgr, const float *h_depth, const uint8_t *h_model_bgr, const float *h_model, const void *d_bgr,
-                            const void *d_depth, const void *d_model_bgr, const void *d_model, const float *model_pose16, const float *pose16,
+  // one evaluation at `level` (without colour counts[4] = 0)
+  void track_pyramid_system(const char *who, int level, const FramePair &frame, const FramePair &model, const float *model_pose16, const float *pose16,
                             const drf_track_pyramid_options_t *opt, double *sums, uint64_t *counts) {
     tp_.reset();
-    const bool host = h_depth != nullptr;
-    const bool colour = host ? h_bgr != nullptr : d_bgr != nullptr;
-    const bool model_ok = host ? (h_model && (!colour || h_model_bgr)) : (d_depth && d_model && (!colour || d_model_bgr));
-    if (!model_ok || !model_pose16 || !pose16 || !sums || !counts) fail(DR_ERR_ARG, "%s: null argument", who);
-    with_track_pyramid(who, &level, h_bgr, h_depth, d_bgr, d_depth, pose16, model_pose16, opt,
-                       [&](const TrackPyramidOpt &po, const PyramidBufs &b, bool col, const FrameGrid &fg, auto &model, auto &eval) {
-      const TrackColourOpt lo = track_level_options(po, level);
-      if (level > 0) launch_reduce(b.depth, col ? b.bgr : nullptr, level, lo.t.max_jump, b.pyr[level], b.pyr_bgr[level]);
-      if (host) {
-        upload_frame(h_model_bgr, h_model, col ? b.model_bgr : nullptr, b.model, true);
-      } else {  // a device-given model goes to the scratch like a render: model() reads it there
-        DR_HIP(hipMemcpyAsync(b.model, d_model, npix_ * 4, hipMemcpyDeviceToDevice, int_stream_));
-        if (col) DR_HIP(hipMemcpyAsync(b.model_bgr, d_model_bgr, npix_ * 3, hipMemcpyDeviceToDevice, int_stream_));
-      }
-      model(level, lo);
-      double c_src[3];
-      locate_centre_src(lo.t.centre_depth, o_.voxel_size, c_src);
-      uint64_t c[5] = {0, 0, 0, 0, 0};
-      eval(level, lo, align_eval(map_motion(pose16, o_.voxel_size), c_src, lo.t.a, o_.voxel_size), model_pose16, sums, c);
-      for (int i = 0; i < 5; ++i) counts[i] = c[i];
-      const LocateGrid lg = track_level_grid(fg.lg, level);
-      tp_.stats[0] = (uint64_t)locate_positions(lg); tp_.stats[1] = c[0]; tp_.stats[2] = c[1]; tp_.stats[3] = 1; tp_.stats[6] = 1;
-      tp_.level[level][2] = 1; tp_.level[level][3] = c[1];
-    });
+    const bool colour = frame.bgr != nullptr;
+    if (!frame.depth || !model.has(colour) || !model_pose16 || !pose16 || !sums || !counts) fail(DR_ERR_ARG, "%s: null argument", who);
+    const TrackPyramidOpt po = track_pyramid_resolve(who, opt, &level);
+    frame_prologue(who, nullptr, pose16, model_pose16);
+    track_system_at(who, tp_, colour, level, po, frame, model, model_pose16, pose16, sums, counts, 5);
   }
-  // returns what dr_last_error() says after a tracking that ran but found no pose (empty otherwise)
-  std::string track_pyramid_frame(const char *who, const uint8_t *h_bgr, const float *h_depth, const void *d_bgr, const void *d_depth, const float *pose16,
-                                  const drf_track_pyramid_options_t *opt, float *pose16_out, drf_align_result_t *res) {
+  std::string track_pyramid_frame(const char *who, const FramePair &frame, const float *pose16, const drf_track_pyramid_options_t *opt, float *pose16_out,
+                                  drf_align_result_t *res) {
     tp_.reset();
-    if (!(h_depth || d_depth) || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+    if (!frame.depth || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+    const TrackPyramidOpt po = track_pyramid_resolve(who, opt, nullptr);
+    frame_prologue(who, nullptr, pose16, nullptr);
     drf_align_result_t r;
     uint64_t last[5] = {0, 0, 0, 0, 0};
-    with_track_pyramid(who, nullptr, h_bgr, h_depth, d_bgr, d_depth, pose16, nullptr, opt,
-                       [&](const TrackPyramidOpt &po, const PyramidBufs &b, bool col, const FrameGrid &fg, auto &model, auto &eval) {
-      Render &rd = tp_.render;
-      if (!rd.cast) { rd.cast = own_.event(); rd.done = own_.event(); }
-      rd.stream = int_stream_;
-      rd.d_bgr = b.model_bgr;
-      rd.d_band = b.band;
-      rd.d_depth = b.model;
-      rd.d_flag = b.flag;
-      for (int L = 1; L < po.levels; ++L)  // the frame, reduced once per call
-        launch_reduce(b.depth, col ? b.bgr : nullptr, L, track_level_options(po, L).t.max_jump, b.pyr[L], b.pyr_bgr[L]);
-      track_pyramid_schedule([&](int L, const float *p16, const TrackColourOpt &lo, drf_align_result_t &lr, uint64_t *lc, uint64_t *st2) {
-        auto render = [&](const float *p) {  // the engine's one submit at full resolution, then the level's model map
-          RenderStagePlan plan;
-          RenderBandPlan bands;
-          bool waited = false;
-          const float *poses[1] = {p};
-          if (render_scope_ == DRF_RENDER_MAP) plan_render_call(who, poses, 1, plan, bands, waited);
-          render_passes(plan, bands, &rd, poses, 1, false);
-          model(L, lo);
-        };
-        auto ev = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t *c) { eval(L, lo, e, mp16, sums, c); };
-        if (col) track_loop<5>(render, ev, p16, lo.t, o_.voxel_size, lr, lc, st2);
-        else track_loop<4>(render, ev, p16, lo.t, o_.voxel_size, lr, lc, st2);
-      }, fg.lg, pose16, po, r, tp_.stats, tp_.level, last);
-    });
-    for (int i = 0; i < 16; ++i) pose16_out[i] = (float)r.T[i];
-    if (res) *res = r;
-    return no_pose_note(std::string(who) + ": the tracking", r,
-                        ", " + std::to_string((unsigned long long)last[2]) + " unassociated, " + std::to_string((unsigned long long)last[3]) + " rejected; " +
-                            std::to_string((unsigned long long)tp_.stats[6]) + " levels, " + std::to_string((unsigned long long)tp_.stats[7]) + " abandoned, " +
-                            std::to_string((unsigned long long)tp_.stats[4]) + " renders; " + std::to_string(store_.size()) + " blocks are in the host store)");
+    track_levels(who, tp_, frame.bgr != nullptr, po, frame, pose16, r, last);
+    return track_note(who, tp_, r, last,
+                      "; " + std::to_string((unsigned long long)tp_.stats[6]) + " levels, " + std::to_string((unsigned long long)tp_.stats[7]) + " abandoned, ", pose16_out, res);
   }
   const uint64_t *track_pyramid_stats() const { return tp_.stats; }
   const uint64_t *track_pyramid_level_stats(int level) const {
@@ -2653,8 +2605,7 @@ class FusionEngine {
   uint64_t mg_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_merge_stats
   DeviceBuf<unsigned char> lc_buf_;            // drf_locate_*: partial sums, counters and a host-given depth image (sized once)
   uint64_t lc_stats_[6] = {0, 0, 0, 0, 0, 0};  // drf_locate_stats
-  TrackSide tk_, tc_;                          // drf_track_*, drf_track_colour_*: each its own scratch, statistics and model render (with_track)
-  PyramidSide tp_;                             // drf_track_reduce, drf_track_pyramid_*: their own scratch, statistics and model render (with_track_pyramid)
+  TrackSide tk_, tc_, tp_;                     // drf_track_*, drf_track_colour_*, drf_track_reduce / drf_track_pyramid_*: each its own scratch, statistics and model render (with_track)
   unsigned long long *tc_fifth_ = nullptr;     // pinned: the fifth counter of an evaluation with colour
   int locate_scope_ = DRF_LOCATE_RESIDENT;     // drf_set_locate_scope
   size_t lc_cap_req_ = 0;
@@ -2873,62 +2824,59 @@ int drf_locate_frame_device(drf_t *h, const void *d_depth, const float pose_init
   return guarded_note([&] { return eng(h)->locate_frame("drf_locate_frame_device", nullptr, d_depth, pose_init16, opt, pose16_out, res); });
 }
 int drf_locate_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_locate_stats", out, &dr::FusionEngine::locate_stats); }
+using dr::FramePair;
 int drf_track_system(drf_t *h, const float *depth, const float *model_depth, const float model_pose16[16], const float pose16[16], const drf_track_options_t *opt,
                      double sums[28], uint64_t counts[4]) {
   return guarded([&] {
-    eng(h)->track_system<dr::TrackGeometric>("drf_track_system", nullptr, depth, nullptr, model_depth, nullptr, nullptr, nullptr, nullptr, model_pose16, pose16, opt, sums, counts);
+    eng(h)->track_system("drf_track_system", FramePair::host(nullptr, depth), FramePair::host(nullptr, model_depth), model_pose16, pose16, opt, sums, counts);
   });
 }
 int drf_track_system_device(drf_t *h, const void *d_depth, const void *d_model_depth, const float model_pose16[16], const float pose16[16],
                             const drf_track_options_t *opt, double sums[28], uint64_t counts[4]) {
   return guarded([&] {
-    eng(h)->track_system<dr::TrackGeometric>("drf_track_system_device", nullptr, nullptr, nullptr, nullptr, nullptr, d_depth, nullptr, d_model_depth, model_pose16, pose16, opt,
-                                             sums, counts);
+    eng(h)->track_system("drf_track_system_device", FramePair::device(nullptr, d_depth), FramePair::device(nullptr, d_model_depth), model_pose16, pose16, opt, sums, counts);
   });
 }
 int drf_track_frame(drf_t *h, const float *depth, const float pose_init16[16], const drf_track_options_t *opt, float pose16_out[16], drf_align_result_t *res) {
-  return guarded_note([&] { return eng(h)->track_frame<dr::TrackGeometric>("drf_track_frame", nullptr, depth, nullptr, nullptr, pose_init16, opt, pose16_out, res); });
+  return guarded_note([&] { return eng(h)->track_frame("drf_track_frame", FramePair::host(nullptr, depth), pose_init16, opt, pose16_out, res); });
 }
 int drf_track_frame_device(drf_t *h, const void *d_depth, const float pose_init16[16], const drf_track_options_t *opt, float pose16_out[16],
                            drf_align_result_t *res) {
-  return guarded_note([&] { return eng(h)->track_frame<dr::TrackGeometric>("drf_track_frame_device", nullptr, nullptr, nullptr, d_depth, pose_init16, opt, pose16_out, res); });
+  return guarded_note([&] { return eng(h)->track_frame("drf_track_frame_device", FramePair::device(nullptr, d_depth), pose_init16, opt, pose16_out, res); });
 }
 int drf_track_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_track_stats", out, &dr::FusionEngine::track_stats); }
 int drf_track_colour_system(drf_t *h, const uint8_t *bgr, const float *depth, const uint8_t *model_bgr, const float *model_depth, const float model_pose16[16],
                             const float pose16[16], const drf_track_colour_options_t *opt, double sums[28], uint64_t counts[5]) {
   return guarded([&] {
-    eng(h)->track_system<dr::TrackWithColour>("drf_track_colour_system", bgr, depth, model_bgr, model_depth, nullptr, nullptr, nullptr, nullptr, model_pose16, pose16, opt, sums,
-                                              counts);
+    eng(h)->track_system("drf_track_colour_system", FramePair::host(bgr, depth), FramePair::host(model_bgr, model_depth), model_pose16, pose16, opt, sums, counts);
   });
 }
 int drf_track_colour_system_device(drf_t *h, const void *d_bgr, const void *d_depth, const void *d_model_bgr, const void *d_model_depth, const float model_pose16[16],
                                    const float pose16[16], const drf_track_colour_options_t *opt, double sums[28], uint64_t counts[5]) {
   return guarded([&] {
-    eng(h)->track_system<dr::TrackWithColour>("drf_track_colour_system_device", nullptr, nullptr, nullptr, nullptr, d_bgr, d_depth, d_model_bgr, d_model_depth, model_pose16,
-                                              pose16, opt, sums, counts);
+    eng(h)->track_system("drf_track_colour_system_device", FramePair::device(d_bgr, d_depth), FramePair::device(d_model_bgr, d_model_depth), model_pose16, pose16, opt, sums,
+                         counts);
   });
 }
 int drf_track_colour_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float pose_init16[16], const drf_track_colour_options_t *opt, float pose16_out[16],
                            drf_align_result_t *res) {
-  return guarded_note([&] { return eng(h)->track_frame<dr::TrackWithColour>("drf_track_colour_frame", bgr, depth, nullptr, nullptr, pose_init16, opt, pose16_out, res); });
+  return guarded_note([&] { return eng(h)->track_frame("drf_track_colour_frame", FramePair::host(bgr, depth), pose_init16, opt, pose16_out, res); });
 }
 int drf_track_colour_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float pose_init16[16], const drf_track_colour_options_t *opt,
                                   float pose16_out[16], drf_align_result_t *res) {
-  return guarded_note([&] { return eng(h)->track_frame<dr::TrackWithColour>("drf_track_colour_frame_device", nullptr, nullptr, d_bgr, d_depth, pose_init16, opt, pose16_out, res); });
+  return guarded_note([&] { return eng(h)->track_frame("drf_track_colour_frame_device", FramePair::device(d_bgr, d_depth), pose_init16, opt, pose16_out, res); });
 }
 int drf_track_colour_stats(drf_t *h, uint64_t out[6]) { return stats6(h, "drf_track_colour_stats", out, &dr::FusionEngine::track_colour_stats); }
 int drf_track_reduce(drf_t *h, int level, float max_jump, const uint8_t *bgr, const float *depth, uint8_t *bgr_out, float *depth_out) {
-  return guarded([&] {
-    eng(h)->track_reduce("drf_track_reduce", level, max_jump, bgr, depth, bgr_out, depth_out, nullptr, nullptr, nullptr, nullptr);
-  });
+  return guarded([&] { eng(h)->track_reduce("drf_track_reduce", level, max_jump, FramePair::host(bgr, depth), bgr_out, depth_out); });
 }
 int drf_track_reduce_device(drf_t *h, int level, float max_jump, const void *d_bgr, const void *d_depth, void *d_bgr_out, void *d_depth_out) {
-  return guarded([&] { eng(h)->track_reduce("drf_track_reduce_device", level, max_jump, nullptr, nullptr, nullptr, nullptr, d_bgr, d_depth, d_bgr_out, d_depth_out); });
+  return guarded([&] { eng(h)->track_reduce("drf_track_reduce_device", level, max_jump, FramePair::device(d_bgr, d_depth), d_bgr_out, d_depth_out); });
 }
 int drf_track_pyramid_system(drf_t *h, int level, const uint8_t *bgr, const float *depth, const uint8_t *model_bgr, const float *model_depth,
                              const float model_pose16[16], const float pose16[16], const drf_track_pyramid_options_t *opt, double sums[28], uint64_t counts[5]) {
   return guarded([&] {
-    eng(h)->track_pyramid_system("drf_track_pyramid_system", level, bgr, depth, model_bgr, model_depth, nullptr, nullptr, nullptr, nullptr, model_pose16, pose16, opt, sums,
+    eng(h)->track_pyramid_system("drf_track_pyramid_system", level, FramePair::host(bgr, depth), FramePair::host(model_bgr, model_depth), model_pose16, pose16, opt, sums,
                                  counts);
   });
 }
@@ -2936,19 +2884,17 @@ int drf_track_pyramid_system_device(drf_t *h, int level, const void *d_bgr, cons
                                     const float model_pose16[16], const float pose16[16], const drf_track_pyramid_options_t *opt, double sums[28],
                                     uint64_t counts[5]) {
   return guarded([&] {
-    eng(h)->track_pyramid_system("drf_track_pyramid_system_device", level, nullptr, nullptr, nullptr, nullptr, d_bgr, d_depth, d_model_bgr, d_model_depth, model_pose16,
+    eng(h)->track_pyramid_system("drf_track_pyramid_system_device", level, FramePair::device(d_bgr, d_depth), FramePair::device(d_model_bgr, d_model_depth), model_pose16,
                                  pose16, opt, sums, counts);
   });
 }
 int drf_track_pyramid_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float pose_init16[16], const drf_track_pyramid_options_t *opt,
                             float pose16_out[16], drf_align_result_t *res) {
-  return guarded_note([&] {
-    return eng(h)->track_pyramid_frame("drf_track_pyramid_frame", bgr, depth, nullptr, nullptr, pose_init16, opt, pose16_out, res);
-  });
+  return guarded_note([&] { return eng(h)->track_pyramid_frame("drf_track_pyramid_frame", FramePair::host(bgr, depth), pose_init16, opt, pose16_out, res); });
 }
 int drf_track_pyramid_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float pose_init16[16], const drf_track_pyramid_options_t *opt,
                                    float pose16_out[16], drf_align_result_t *res) {
-  return guarded_note([&] { return eng(h)->track_pyramid_frame("drf_track_pyramid_frame_device", nullptr, nullptr, d_bgr, d_depth, pose_init16, opt, pose16_out, res); });
+  return guarded_note([&] { return eng(h)->track_pyramid_frame("drf_track_pyramid_frame_device", FramePair::device(d_bgr, d_depth), pose_init16, opt, pose16_out, res); });
 }
 int drf_track_pyramid_stats(drf_t *h, uint64_t out[8]) {
   return guarded([&] {

@@ -628,22 +628,6 @@ inline const char *track_colour_options(const drf_track_colour_options_t *opt, f
   o.photo_weight = u.photo_weight != 0.0f ? u.photo_weight : (float)(1.0 / 27.0) * o.t.a.huber;
   return nullptr;
 }
-// The two tracking families as types: what the engine's one tracking path (dr_fusion.hip: with_track) is parameterised by besides
-// the kernels it launches.  N: the counters of an evaluation; geo: the geometric options inside.
-struct TrackGeometric {
-  using Options = drf_track_options_t;
-  using Opt = TrackOpt;
-  static constexpr int N = 4;
-  static const char *options(const Options *u, float voxel_size, Opt &o) { return track_options(u, voxel_size, o); }
-  static const TrackOpt &geo(const Opt &o) { return o; }
-};
-struct TrackWithColour {
-  using Options = drf_track_colour_options_t;
-  using Opt = TrackColourOpt;
-  static constexpr int N = 5;
-  static const char *options(const Options *u, float voxel_size, Opt &o) { return track_colour_options(u, voxel_size, o); }
-  static const TrackOpt &geo(const Opt &o) { return o.t; }
-};
 // the intensity of a BGR pixel: a whole number in 0..765
 DR_HOST_DEVICE inline float track_intensity(const unsigned char *bgr) { return ((float)bgr[0] + (float)bgr[1]) + (float)bgr[2]; }
 // One pixel of the model intensity map Ym: the intensity of the model colour image where the model map's pixel is valid, -1

@@ -422,20 +422,40 @@ class DrFusion:
         return tuple(int(v) for v in out)
 
     # ---- tracking a depth frame against the ray-cast model (include/dr_mi355x.h drf_track_frame, DESIGN.md "Tracking a depth frame") ----
+    def _track_images(self, images):
+        """The images of a tracking call in the C ABI's order, each (dtype, channels, image); an image None is one the call does
+        without.  (Are they device pointers, the arguments, what keeps them alive.)"""
+        got = [self._image(*i) if i[2] is not None else (None, None, None) for i in images]
+        where = {g[0] for g in got if g[0] is not None}
+        assert len(where) == 1, "all images on the host or all on the device"
+        return where.pop(), [g[1] for g in got], got
+
+    def _track_system(self, name, lead, images, model_pose, pose, o, ncounts):
+        """What track_system, track_colour_system and track_pyramid_system do behind their options o: one evaluation by the C
+        function `name` (or its _device twin), lead its arguments before the images, ncounts counters back."""
+        dev, args, keep = self._track_images(images)
+        pose = np.ascontiguousarray(pose, np.float32).reshape(16)
+        mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
+        sums, counts = np.zeros(28, np.float64), (C.c_uint64 * ncounts)()
+        call = getattr(self._L, name + "_device" if dev else name)
+        check(call(self._h, *lead, *args, fptr(mpose), fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
+        return sums, tuple(int(v) for v in counts)
+
+    def _track_frame(self, name, images, pose_init, o, raise_on_failure):
+        """What track_frame, track_colour_frame and track_pyramid_frame do behind their options o"""
+        dev, args, keep = self._track_images(images)
+        pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
+        T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
+        call = getattr(self._L, name + "_device" if dev else name)
+        check(call(self._h, *args, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
+        return self._align_result(r, T32, raise_on_failure)
+
     def track_system(self, depth, model_depth, model_pose, pose, **opt):
         """One evaluation of the tracking's Gauss-Newton system: the depth image at the pose against model_depth, a ray-cast at
         model_pose (both images H*W float32 metres, or both integer device pointers): (sums (28,) float64, (samples, valid,
         unassociated, rejected)).  opt: the fields of drf_track_options_t.  No map is read."""
-        dev, d, keep = self._image(np.float32, 1, depth)
-        mdev, m, mkeep = self._image(np.float32, 1, model_depth)
-        assert dev == mdev, "both images on the host or both on the device"
-        pose = np.ascontiguousarray(pose, np.float32).reshape(16)
-        mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
         o = self._options(_lib.TrackOptions, "track", opt)
-        sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 4)()
-        call = self._L.drf_track_system_device if dev else self._L.drf_track_system
-        check(call(self._h, d, m, fptr(mpose), fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
-        return sums, tuple(int(v) for v in counts)
+        return self._track_system("drf_track_system", (), [(np.float32, 1, depth), (np.float32, 1, model_depth)], model_pose, pose, o, 4)
 
     def track_frame(self, depth, pose_init, raise_on_failure=True, **opt):
         """Tracks the depth image against the ray-cast model of the map this engine holds from pose_init (camera-to-world), which
@@ -443,13 +463,8 @@ class DrFusion:
         locate_frame's reach: track first, then locate_frame(depth, result.T32) for the sub-voxel part.  The renders follow
         set_render_scope and set_render_bands; the public render buffers and the map are not touched.  ALIGN_MAX_ITERS is a usable
         pose; ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the result) unless raise_on_failure is false."""
-        dev, d, keep = self._image(np.float32, 1, depth)
-        pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
         o = self._options(_lib.TrackOptions, "track", opt)
-        T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
-        call = self._L.drf_track_frame_device if dev else self._L.drf_track_frame
-        check(call(self._h, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
-        return self._align_result(r, T32, raise_on_failure)
+        return self._track_frame("drf_track_frame", [(np.float32, 1, depth)], pose_init, o, raise_on_failure)
 
     def track_stats(self):
         """Last track_system / track_frame: (grid positions, samples, valid samples at the last evaluation, system evaluations,
@@ -470,33 +485,17 @@ class DrFusion:
         pose against the model's colour and depth, a ray-cast at model_pose (all four on the host or all four integer device
         pointers): (sums (28,) float64, (samples, valid, unassociated, rejected, photometric terms added)).  photo_weight: voxels
         per intensity unit, 0 = 1/27 times huber; opt: the fields of drf_track_options_t.  No map is read."""
-        dev, d, keep = self._image(np.float32, 1, depth)
-        mdev, m, mkeep = self._image(np.float32, 1, model_depth)
-        cdev, c, ckeep = self._image(np.uint8, 3, bgr)
-        mcdev, mc, mckeep = self._image(np.uint8, 3, model_bgr)
-        assert dev == mdev == cdev == mcdev, "all four images on the host or all four on the device"
-        pose = np.ascontiguousarray(pose, np.float32).reshape(16)
-        mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
         o = self._track_colour_options(photo_weight, opt)
-        sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 5)()
-        call = self._L.drf_track_colour_system_device if dev else self._L.drf_track_colour_system
-        check(call(self._h, c, d, mc, m, fptr(mpose), fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
-        return sums, tuple(int(v) for v in counts)
+        images = [(np.uint8, 3, bgr), (np.float32, 1, depth), (np.uint8, 3, model_bgr), (np.float32, 1, model_depth)]
+        return self._track_system("drf_track_colour_system", (), images, model_pose, pose, o, 5)
 
     def track_colour_frame(self, bgr, depth, pose_init, raise_on_failure=True, photo_weight=0.0, **opt):
         """track_frame with the frame's colour image (as IntegrateScanAsync takes it) and a photometric term next to the geometric
         one: it holds the motion inside a plane, which track_frame leaves open (on one wall track_frame is ALIGN_DEGENERATE, this
         call is not).  Both images on the host, or both integer device pointers.  Returns an AlignResult whose cost carries both
         terms; ALIGN_DEGENERATE or ALIGN_LOST raises AlignError unless raise_on_failure is false."""
-        dev, d, keep = self._image(np.float32, 1, depth)
-        cdev, c, ckeep = self._image(np.uint8, 3, bgr)
-        assert dev == cdev, "both images on the host or both on the device"
-        pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
         o = self._track_colour_options(photo_weight, opt)
-        T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
-        call = self._L.drf_track_colour_frame_device if dev else self._L.drf_track_colour_frame
-        check(call(self._h, c, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
-        return self._align_result(r, T32, raise_on_failure)
+        return self._track_frame("drf_track_colour_frame", [(np.uint8, 3, bgr), (np.float32, 1, depth)], pose_init, o, raise_on_failure)
 
     def track_colour_stats(self):
         """Last track_colour_system / track_colour_frame: track_stats' fields; the device bytes are a buffer of these calls' own."""
@@ -536,38 +535,17 @@ class DrFusion:
         """One evaluation at `level` of the pyramid: both full-resolution pairs are reduced to the level, then
         track_colour_system's rule (bgr and model_bgr None: track_system's) with the level's camera: (sums (28,) float64, (samples,
         valid, unassociated, rejected, photometric terms added)).  All images on the host or all integer device pointers."""
-        dev, d, keep = self._image(np.float32, 1, depth)
-        mdev, m, mkeep = self._image(np.float32, 1, model_depth)
-        assert dev == mdev, "all images on the host or all on the device"
-        c = mc = None
-        if bgr is not None:
-            cdev, c, ckeep = self._image(np.uint8, 3, bgr)
-            mcdev, mc, mckeep = self._image(np.uint8, 3, model_bgr)
-            assert dev == cdev == mcdev, "all images on the host or all on the device"
-        pose = np.ascontiguousarray(pose, np.float32).reshape(16)
-        mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
         o = self._track_pyramid_options(levels, coarse_renders, photo_weight, opt)
-        sums, counts = np.zeros(28, np.float64), (C.c_uint64 * 5)()
-        call = self._L.drf_track_pyramid_system_device if dev else self._L.drf_track_pyramid_system
-        check(call(self._h, int(level), c, d, mc, m, fptr(mpose), fptr(pose), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
-        return sums, tuple(int(v) for v in counts)
+        images = [(np.uint8, 3, bgr), (np.float32, 1, depth), (np.uint8, 3, model_bgr if bgr is not None else None), (np.float32, 1, model_depth)]
+        return self._track_system("drf_track_pyramid_system", (int(level),), images, model_pose, pose, o, 5)
 
     def track_pyramid_frame(self, bgr, depth, pose_init, raise_on_failure=True, levels=0, coarse_renders=0, photo_weight=0.0, **opt):
         """track_colour_frame (bgr None: track_frame) coarse to fine: `levels` (0 = 3) halvings of frame and model, the coarsest
         first with `coarse_renders` (0 = 3) renders each, then the full-resolution call from the pose they reach.  It cures a
         render that aliases the map's texture and minima at the texture's scale; it is no global search.  levels=1 is the
         single-level call bit for bit.  Returns level 0's AlignResult; then locate_frame(depth, result.T32)."""
-        dev, d, keep = self._image(np.float32, 1, depth)
-        c = None
-        if bgr is not None:
-            cdev, c, ckeep = self._image(np.uint8, 3, bgr)
-            assert dev == cdev, "both images on the host or both on the device"
-        pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
         o = self._track_pyramid_options(levels, coarse_renders, photo_weight, opt)
-        T32, r = np.zeros(16, np.float32), _lib.AlignResultStruct()
-        call = self._L.drf_track_pyramid_frame_device if dev else self._L.drf_track_pyramid_frame
-        check(call(self._h, c, d, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
-        return self._align_result(r, T32, raise_on_failure)
+        return self._track_frame("drf_track_pyramid_frame", [(np.uint8, 3, bgr), (np.float32, 1, depth)], pose_init, o, raise_on_failure)
 
     def track_pyramid_stats(self):
         """Last track_reduce / track_pyramid_*: (grid positions, samples, valid samples -- each summed over the levels' last
