@@ -22,40 +22,10 @@
 
 namespace dr {
 
-struct MarchArgs {
-  const int *tap2d;    // [NUP * TPC] in-plane tap offsets (positions of the staged plane)
-  MarchGeom geo;
-  int NPO;             // channel passes around the whole range (1 or 2)
-  int ncols, colsH, colsW;
-  int R, PS;           // ring slots, 16-byte LDS slots per ring slot (multiple of 128: an even number of 1 KiB DMA pieces)
-  int NP;              // staged positions per plane (TYI * TXI)
-  int nit;             // DMA pieces of a plane per producer wave (PS / 128)
-  int wsec;            // float4 per weight section (NUP * CT * 64)
-  int NU;              // K chunks per channel pass in the packed weight array (KZ * NUP)
-  int steps;           // ncols * Dc
-  int ncw;             // consumer waves (8, 10 or 12)
-  // Addressing (elements): position (image zc, marching index z, in-plane row y, x) of the input lies at
-  //   zc * i_sv + z * i_sz + y * i_sy + x * inC, the output likewise with o_*.
-  //   3-D layer  (KZ = 3, rm = 0): zc = 0, z = depth plane, y = row          i_sz = H*W*C, i_sy = W*C
-  //   2-D tiles  (KZ = 1, rm = 0): zc = image, z = 0, y = row                i_sv = H*W*C, i_sy = W*C
-  //   ROW MARCH  (KZ = 3, rm = 1): zc = image, z = ROW, no in-plane y        i_sv = H*W*C, i_sz = W*C, i_sy = 0
-  // The row march is the same ring protocol applied to a 2-D layer: a "plane" is one row strip of one image, a step produces one
-  // output row strip from the three row strips around it (sections = ky), so no row of the y halo is ever fetched twice.
-  int i_sv, i_sz, i_sy, o_sv, o_sz, o_sy;
-  int depth;           // loads a producer wave keeps in flight (1: publish every load before issuing the next)
-  int inHp;            // rows a plane has inside the tensor (inH, or 1 for the row march)
-  int rm;              // row march
-  int wino;            // 1, 2: the y axis in Winograd F(2,3) form: a position is a row PAIR, a.sy = 2, the in-plane tap table lists the x taps only
-                       //       (1: march_consumer_w, one output plane per step; 2: march_consumer_ws, the same products in plane-major order)
-  int *err;            // raised when a wait gave up (nullptr: not reported)
-};
-
 constexpr int kMarchProducers = 2;       // DMA producer waves (the fused-skip producers are four: kMarchFzProducers)
 constexpr int kMarchMaxConsumers = 12;   // consumer waves: 8 (two per SIMD), 10 (640-wide 2-D rows are 20 or 10 position tiles) or 12 (three per SIMD)
-constexpr int kMarchMaxIt = 24;          // DMA pieces per producer wave per plane (planes up to 48 KB)
 constexpr int kMarchSpinLimit = 1 << 18; // polls before a wait gives up (tens of milliseconds)
-// flag words (ints) behind the weights: [0..7] ready (one per producer wave), [8..19] released (one per consumer wave), [28] abort
-constexpr int kMarchFlagInts = 32, kMarchReleased = 8, kMarchAbort = 28;
+// (MarchArgs, kMarchMaxIt and the flag-word constants are in march_plan.h: the planner reads them)
 
 // the flag words are read and written with LDS instructions (ds_read / ds_write), never through flat addressing
 typedef __attribute__((address_space(3))) volatile int march_flag_t;

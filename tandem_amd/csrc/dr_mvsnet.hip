@@ -29,6 +29,10 @@ std::string &last_error_slot() {
   return s;
 }
 
+// An instance no plan asks for (DR_CONV_A_INSTANCES: its tiles are PT = 2's at half the work per wave) but one the library has always carried: instantiated
+// here so that the library's set of kernels does not depend on how launch_conv's dispatcher is written.
+template __global__ void k_conv_a<4, 1, 1>(const ConvArgs a);
+
 // ------------------------------------------------------------------ engine
 struct DevTensor {
   float *d = nullptr;
@@ -103,9 +107,7 @@ struct Rccl {
   }
 };
 
-static const char *conv_kind_name(const ConvLaunch &c) {
-  return c.async == 2 ? (c.march.rm ? "rowmarch" : (c.march.wino ? "winomarch" : "march")) : (c.async == 4 ? "wino" : (c.async ? "async" : ""));
-}
+static const char *conv_kind_name(const ConvLaunch &c) { return conv_family_name(conv_family(c)); }
 
 class MvsEngine {
  public:
@@ -277,7 +279,7 @@ class MvsEngine {
                          conv_kind_name(best_c), best_c.ci, best_c.ct, best_c.pt, best_c.args.TZ, best_c.args.TY, best_c.args.TXT * 16);
       if (print && best_rank != 0)
         fprintf(stderr, "TUNED    {%s,   %d, %d, %d, %d, %d, %d, %d},  // %s %.4f -> %.4f ms\n", o.sig.c_str(), best_c.ci, best_c.ct, best_c.pt, best_c.args.TZ,
-                best_c.args.TY, best_c.args.TXT, best_c.async == 2 ? (best_c.march.rm ? 3 : (best_c.march.wino ? 5 : 2)) : best_c.async, o.name.c_str(), t0, best);
+                best_c.args.TY, best_c.args.TXT, (int)conv_family(best_c), o.name.c_str(), t0, best);
       o.conv = best_c;
       t_before += t0; t_after += best;
     }
@@ -408,12 +410,7 @@ class MvsEngine {
       ms.push_back(t);
       const Op &o = ops_[i];
       char kn[64] = "misc";
-      if (o.kind == Op::CONV && o.conv.async == 2) snprintf(kn, sizeof kn, "k_conv_m<%d,%d,%d,%d,%d,%d,%d>", o.conv.ci, o.conv.nup, o.conv.ct, o.conv.pt, o.conv.fz, o.conv.ncw, o.conv.march.wino);  // rocprofv3's spelling of the instance
-      else if (o.kind == Op::CONV && o.conv.async == 4) snprintf(kn, sizeof kn, "k_conv_w<%d,%d,%d>", o.conv.ci, o.conv.ct, o.conv.pt);
-      else if (o.kind == Op::CONV && o.conv.async) snprintf(kn, sizeof kn, "k_conv_a<%d,%d,%d>", o.conv.ci, o.conv.ct, o.conv.pt);
-      else if (o.kind == Op::CONV && o.conv.bf3) snprintf(kn, sizeof kn, "k_conv_b<%d,%d,%d>", o.conv.ci, o.conv.ct, o.conv.pt);
-      else if (o.kind == Op::CONV && o.conv.args.class_loop > 0) snprintf(kn, sizeof kn, "k_conv_c<%d,%d,%d>", o.conv.ci, o.conv.ct, o.conv.pt);
-      else if (o.kind == Op::CONV) snprintf(kn, sizeof kn, "k_conv<%d,%d,%d,%d>", o.conv.ci, o.conv.ct, o.conv.pt, o.conv.fz);
+      if (o.kind == Op::CONV) conv_instance_name(o.conv, kn, sizeof kn);
       else if (o.kind == Op::COSTVOL) choose_costvol(costvol_shape(cv_[o.stage - 1]), sw_, o.stage).name(kn, sizeof kn);
       else if (o.kind == Op::PROB) choose_prob(prob_shape(pr_[o.stage - 1]), sw_, o.stage).name(kn, sizeof kn);
 #ifdef DR_PARITY_HOOKS
@@ -1463,7 +1460,7 @@ int drm_debug_conv(int device, const float *in, int D, int H, int W, int Cin, co
       const ConvLaunch &c = P.launches.at(0);
       fprintf(stderr, "debug_conv: %s<%d,%d,%d> nup %d tile %dx%dx%d lds %zu grid %ux%u (%d candidates)%s\n", *conv_kind_name(c) ? conv_kind_name(c) : (c.bf3 ? "bf16x3" : "sync"), c.ci, c.ct, c.pt,
               c.nup, c.args.TZ, c.args.TY, c.args.TXT * 16, c.lds_bytes, c.grid.x, c.grid.z, P.ncand,
-              c.args.class_loop ? ", class loop" : (c.async == 2 && c.march.wino ? (c.march.wino == 2 ? ", scatter order" : ", gather order") : ""));
+              c.args.class_loop ? ", class loop" : (conv_family(c) == CONV_FAM_WINOMARCH ? (c.march.wino == 2 ? ", scatter order" : ", gather order") : ""));
     }
     DR_HIP(hipMemcpy(out, d_out, on * 4, hipMemcpyDeviceToHost));
     if (out_dims) { out_dims[0] = oD; out_dims[1] = oH; out_dims[2] = oW; }

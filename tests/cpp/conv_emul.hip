@@ -394,8 +394,7 @@ static int run_case(const Case &cs, int max_plans) {
   int done = 0, fails = 0, n_async = 0, n_wino = 0;
   for (int rank = 0; rank < 400 && done < max_plans; rank += 3) {
     std::vector<float> out(on, -777.f);
-    DeviceArena arena;
-    arena.host_only = true;
+    HostArena arena;
     ConvLaunch c{};
     bool ok = true;
     int ncand = 0;
@@ -418,7 +417,7 @@ static int run_case(const Case &cs, int max_plans) {
     double worst = 0;
     for (size_t i = 0; i < on; ++i) worst = std::max(worst, (double)std::fabs(out[i] - ref[i]) / (1.0 + std::fabs(ref[i])));
     const bool pass = ok && worst < (c.bf3 ? 1e-4 : 2e-5) && (c.bf3 != 0) == (conv_bf3_policy() && cs.Cin % 8 == 0);  // (bf16 x 3: the dropped w_l x_l term and the lo terms' rounding, ~2^-16 per product)
-    printf("%-26s plan rank %3d %s ci=%d ct=%d pt=%d tile %dx%dx%d classes %u rows %d: %s (max rel err %.2e)\n", cs.name, rank, c.async == 4 ? "k_conv_w" : (c.async ? "k_conv_a" : (c.bf3 ? "k_conv_b" : "k_conv")), c.ci, c.ct, c.pt, c.args.TZ, c.args.TY,
+    printf("%-26s plan rank %3d %s ci=%d ct=%d pt=%d tile %dx%dx%d classes %u rows %d: %s (max rel err %.2e)\n", cs.name, rank, c.bf3 ? "k_conv_b" : conv_family_kernel(conv_family(c)), c.ci, c.ct, c.pt, c.args.TZ, c.args.TY,
            c.args.TXT * 16, c.args.class_loop > 0 ? (unsigned)c.args.class_loop : c.grid.y, c.args.rows_valid, pass ? "ok" : "FAIL", worst);
     ++done;
     if (!pass) ++fails;

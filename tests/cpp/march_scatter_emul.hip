@@ -279,8 +279,7 @@ static int run_case(const Case &cs, int max_plans, int &za_mid, int &two_cols) {
   const ConvMode mode = cs.Cout == 8 ? CONV_XPAIR : CONV_NORMAL;
   int done = 0, fails = 0;
   for (int rank = 0; rank < 400 && done < max_plans; ++rank) {
-    DeviceArena arena;
-    arena.host_only = true;
+    HostArena arena;
     std::vector<float> out(on);
     ConvPlanOut P = plan_conv(L, mode, in.data(), cs.D, cs.H, cs.W, cs.Cin, out.data(), cs.add ? add.data() : nullptr, 1, arena, rank);
     if (rank >= P.ncand) break;

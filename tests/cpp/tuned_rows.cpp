@@ -1,10 +1,10 @@
-// tuned_rows.hip -- host check of tandem_amd/csrc/conv_tuned.h (run by tests/test_conv_plan.py): every measured-best row must still name a
+// tuned_rows.cpp -- host check of tandem_amd/csrc/conv_tuned.h (run by tests/test_conv_plan.py): every measured-best row must still name a
 // plan the planner can build for its layer signature.  plan_conv silently falls back to its cost model when a row matches no candidate
 // (a kernel instance that was removed, a tile rule that changed), which would cost performance without failing any parity test.
 #include <cstdio>
 #include <random>
 
-#include "../../tandem_amd/csrc/conv_mfma.h"
+#include "../../tandem_amd/csrc/conv_plan.h"  // (alone: a g++ program, no HIP header)
 
 namespace dr {
 std::string &last_error_slot() {
@@ -30,11 +30,10 @@ int main() {
     L.weight = w.data();
     // plan_conv only reads the tensors' addresses: one float each is enough
     float in = 0.f, out = 0.f;
-    DeviceArena arena;
-    arena.host_only = true;
+    HostArena arena;
     ConvPlanOut P = plan_conv(L, (ConvMode)t.mode, &in, t.inD, t.inH, t.inW, t.Cin, &out, nullptr, 0, arena, 0);
     const ConvLaunch &c = P.launches.at(0);
-    const int async_ = c.async == 2 ? (c.march.rm ? 3 : (c.march.wino ? 5 : 2)) : c.async;
+    const int async_ = conv_family(c);
     const bool live = c.ci == t.ci && c.ct == t.ct && c.pt == t.pt && c.args.TZ == t.tz && c.args.TY == t.ty && c.args.TXT == t.txt && async_ == t.async_;
     if (!live) {
       ++stale;

@@ -1,8 +1,8 @@
-// tools/dump_plans.hip -- host tool: the launch plan of every CostRegNet layer at the headline shapes (640x480, planes 48/32/8), as plan_conv builds it with the
+// tools/dump_plans.cpp -- host tool: the launch plan of every CostRegNet layer at the headline shapes (640x480, planes 48/32/8), as plan_conv builds it with the
 // committed plan table: kernel form, channel pass width, tile, passes, K chunks, workgroups, LDS.  No device needed.
-//   hipcc --offload-arch=gfx950 -O1 -std=c++17 tools/dump_plans.hip -o /tmp/dump_plans && /tmp/dump_plans
+//   g++ -O1 -std=c++17 tools/dump_plans.cpp -o /tmp/dump_plans && /tmp/dump_plans
 #include <cstdio>
-#include "../tandem_amd/csrc/conv_mfma.h"
+#include "../tandem_amd/csrc/conv_plan.h"
 namespace dr { std::string &last_error_slot() { static std::string s; return s; } }
 using namespace dr;
 
@@ -12,10 +12,10 @@ static void layer(const char *name, int D, int H, int W, int Cin, int Cout, int 
   std::vector<float> w((size_t)Cin * Cout * 27, 0.01f);
   L.weight = w.data();
   float in = 0, out = 0;
-  DeviceArena arena; arena.host_only = true;
+  HostArena arena;
   ConvPlanOut P = plan_conv(L, mode, &in, D, H, W, Cin, &out, nullptr, 0, arena, 0);
   const ConvLaunch &c = P.launches.at(0);
-  const char *kind = c.async == 2 ? (c.march.rm ? "rowmarch" : (c.march.wino ? "winomarch" : "march")) : (c.async == 4 ? "k_conv_w" : (c.async ? "k_conv_a" : "k_conv"));
+  const char *kind = c.async == 2 ? conv_family_name(conv_family(c)) : conv_family_kernel(conv_family(c));
   printf("%-10s %2dx%3dx%3d %2d->%2d s%d%s  %-9s ci=%2d ct=%d pt=%d tile %dx%dx%-3d npass=%d grid=%ux%ux%u = %5u WG  lds=%3zu KB (%zu B, nuMax %d, halo %dx%dx%d)  %.2f GFLOP\n", name, D, H, W, Cin, Cout, sd, tr ? "T" : " ", kind, c.ci, c.ct,
          c.pt, c.args.TZ, c.args.TY, c.args.TXT * 16, c.args.npass, c.grid.x, c.grid.y, c.grid.z, c.grid.x * c.grid.y * c.grid.z, c.lds_bytes >> 10, c.lds_bytes, c.args.nuMax, c.args.TZI, c.args.TYI, c.args.TXI, c.flops / 1e9);
 }
