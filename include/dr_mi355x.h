@@ -155,6 +155,31 @@ int drm_debug_conv(int device, const float *in, int D, int H, int W, int Cin, co
 int drm_debug_tail(int device, const float *x, const float *skip, const float *w_deconv, const float *scale8, const float *bias8, const float *w_prob, int D,
                    int h, int w, int qy, int zchunk, int form, float *out);
 
+/* Kernel unit-test hooks for the last two operators of the depth pipeline, run alone on data the caller chooses.  All arrays are host memory.  The kernel is
+ * chosen from the environment switches by the engine's own rule and launched by the engine's own launcher (csrc/mvs_host.h choose_regress / choose_prob,
+ * csrc/mvs_launch.h): DR_PROB_ZCHUNK and DR_HIST_BLOCKS in both libraries, DR_REGRESS_GENERIC, DR_PROB_REGRESS and DR_FILTER_FUSED in the parity library only (the
+ * product ignores them, as its engine does; a choice that names a kernel the product does not contain answers DR_ERR_UNSUPPORTED).  Outputs no launch writes
+ * keep the poison word of csrc/guard_host.h (a NaN).
+ *
+ * The hypothesis planes of both regression hooks (csrc/mvs_kernels.h PlaneArgs): prev == NULL: d_k = dmin + interval * k; else prev is the previous stage's depth
+ * (hp, wp) = (h / 2, w / 2), cur its x2 bilinear upsampling, lo = max(cur - half_range, 1e-3), d_k = lo + full_range * (k / D).
+ *
+ * drm_debug_regress: logits (D, h, w) -> depth_out, conf_out (h, w) (module.py:1116-1133: softmax over D, its expectation over the planes, the sum of the four
+ * probabilities around trunc(E[k])).  kernel_name_out (64 bytes, may be NULL): "k_regress_r<D>" or "k_regress". */
+int drm_debug_regress(int device, const float *logits, int D, int h, int w, const float *prev, int hp, int wp, float dmin, float interval, float half_range,
+                      float full_range, float *depth_out, float *conf_out, char kernel_name_out[64]);
+/* drm_debug_prob_regress: x11 (D, h, w, 8) channels-last and w_prob (1, 8, 3, 3, 3) in torch layout -> logits_out (D, h, w), then the regression of those logits:
+ * in the same launch where the engine would run it so (D = 8 in one z chunk: "k_prob2_regress<8>"), else as a second launch ("k_prob2<1>+k_regress_r<8>"). */
+int drm_debug_prob_regress(int device, const float *x11, const float *w_prob, int D, int h, int w, const float *prev, int hp, int wp, float dmin, float interval,
+                           float half_range, float full_range, float *logits_out, float *depth_out, float *conf_out, char kernel_name_out[64]);
+/* drm_debug_edge_filter: the edge measure of depth (H, W) -> edge_out; the rank-th smallest edge value (0-based, rank < H W) by the three-level radix select ->
+ * *thr_bits_out (its bit pattern); depth_out / conf_out = depth / conf with the pixels whose edge value is > that threshold set to 0.  The launch sequence is
+ * the engine's (edge, three histogram levels, their scans as launches or as prologues, apply) on buffers of its own.  edge_in (may be NULL): copied over the
+ * edge buffer behind the edge kernel and before the first level -- the select and the mask then run on these values (non-negative floats), and edge_out
+ * returns them. */
+int drm_debug_edge_filter(int device, const float *depth, const float *conf, int H, int W, const float *edge_in, unsigned rank, float *edge_out, float *depth_out,
+                          float *conf_out, unsigned *thr_bits_out);
+
 /* Test hooks of the parity library (libdr_mi355x_hooks.so); in the product library all three return DR_ERR_UNSUPPORTED.  With guards on, every
  * device allocation of the library (engine tensors, plan uploads, voxel pool, tracker arrays, dr_device_alloc, ...) lies between two guard bands of
  * guard_bytes each, and guards and payload start as a poison pattern in which every aligned 32-bit word is a quiet NaN (csrc/guard_host.h).  A guard

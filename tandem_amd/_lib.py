@@ -59,7 +59,12 @@ SIGNATURES = {
                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p, f32p, C.c_int, f32p, C.c_int,
                                  f32p, C.POINTER(C.c_int)]),
     "drm_debug_tail": (C.c_int, [C.c_int, f32p, f32p, f32p, f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]),
-    "drm_autotune": (C.c_int, [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "drm_debug_regress": (C.c_int, [C.c_int, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, f32p, f32p,
+                                    C.c_char_p]),
+    "drm_debug_prob_regress": (C.c_int, [C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, f32p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                         f32p, f32p, f32p, C.c_char_p]),
+    "drm_debug_edge_filter": (C.c_int, [C.c_int, f32p, f32p, C.c_int, C.c_int, f32p, C.c_uint, f32p, f32p, f32p, C.POINTER(C.c_uint)]),
+    "drm_autotune":(C.c_int, [vp, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "drm_set_view_shard": (C.c_int, [vp, C.c_int]),
     "drm_forward_phase": (C.c_int, [vp, C.c_int]),
     "drm_comm_available": (C.c_int, []),

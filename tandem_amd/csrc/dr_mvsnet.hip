@@ -1003,7 +1003,7 @@ class MvsEngine {
     filt_ = {T("depth3").d, T("conf3").d, alloc("edge", 1, H, W, 1).d, alloc("depth", 1, H, W, 1).d, alloc("confidence", 1, H, W, 1).d, d_state_, d_hist_,
              H * W, H, W, sw_.hist_blocks, sw_.filter_fused};
     { Op o; o.kind = Op::EDGE; o.name = "filter.edge"; o.bytes = 8.0 * H * W; ops_.push_back(o); }
-    const int shifts[3] = {21, 10, 0}, bits[3] = {11, 11, 10};
+    const int *shifts = kSelectShift, *bits = kSelectBits;
     for (int i = 0; i < 3; ++i) {
       Op o; o.kind = Op::HIST; o.shift = shifts[i]; o.bits = bits[i]; o.stage = i; o.d0 = i ? shifts[i - 1] : 0; o.d1 = i ? bits[i - 1] : 0;
       o.name = "filter.hist" + std::to_string(i); o.bytes = 4.0 * H * W; ops_.push_back(o);
@@ -1501,6 +1501,138 @@ int drm_debug_tail(int device, const float *x, const float *skip, const float *w
     DR_HIP(hipGetLastError());
     DR_HIP(hipMemcpy(out, d_out, (size_t)D * h * w * 4, hipMemcpyDeviceToHost));
 #endif
+  });
+}
+
+/* ---- kernel unit-test hooks for the regression and the edge filter (include/dr_mi355x.h).  Every buffer comes from a DeviceArena (the guarded allocator of
+ * the parity build sees it), outputs start as the poison word, the switches are the engine's (MvsSwitches, read from the environment), and every launch goes
+ * through the launcher the engine calls (mvs_launch.h): the kernel an input reaches is the one the engine would run on it. */
+static void debug_device(int device, const char *who) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= device || device < 0) dr::fail(DR_ERR_DEVICE, "%s: no HIP device %d", who, device);
+  DR_HIP(hipSetDevice(device));
+}
+static float *debug_poison(dr::DeviceArena &arena, size_t n) {
+  float poison; memcpy(&poison, &dr::guard::kWord, 4);  // (guard_host.h: a position no launch writes stays a NaN)
+  return arena.upload(std::vector<float>(n, poison));
+}
+static void debug_check_planes(const char *who, int D, int h, int w, const float *prev, int hp, int wp) {
+  if (D <= 0 || h <= 0 || w <= 0 || D > 4096 || (long long)D * h * w > (1ll << 28)) dr::fail(DR_ERR_ARG, "%s: D, h, w must be positive (D <= 4096, D h w <= 2^28)", who);
+  // up2_bilinear reads prev at rows <= (h - 1) / 2 and columns <= (w - 1) / 2: the previous stage's map is exactly half the size
+  if (prev && (hp <= 0 || wp <= 0 || h != 2 * hp || w != 2 * wp)) dr::fail(DR_ERR_ARG, "%s: prev must be (h / 2, w / 2)", who);
+}
+static dr::RegressArgs debug_regress_args(dr::DeviceArena &arena, const float *d_logits, int D, int h, int w, const float *prev, int hp, int wp, float dmin,
+                                          float interval, float half_range, float full_range) {
+  dr::RegressArgs r{};
+  r.logits = d_logits;
+  r.depth = debug_poison(arena, (size_t)h * w);
+  r.conf = debug_poison(arena, (size_t)h * w);
+  r.planes.prev = prev ? arena.upload(std::vector<float>(prev, prev + (size_t)hp * wp)) : nullptr;
+  r.planes.hp = prev ? hp : 0; r.planes.wp = prev ? wp : 0;
+  r.planes.D = D; r.planes.dmin = dmin; r.planes.interval = interval;
+  r.planes.half_range = half_range; r.planes.full_range = full_range;
+  r.h = h; r.w = w;
+  return r;
+}
+static void debug_regress_name(char *out, size_t cap, int D, const dr::MvsSwitches &sw) {
+  const int d = dr::choose_regress(D, sw);
+  if (d) snprintf(out, cap, "k_regress_r<%d>", d);
+  else snprintf(out, cap, "k_regress");
+}
+
+int drm_debug_regress(int device, const float *logits, int D, int h, int w, const float *prev, int hp, int wp, float dmin, float interval, float half_range,
+                      float full_range, float *depth_out, float *conf_out, char kernel_name_out[64]) {
+  return guarded([&] {
+    using namespace dr;
+    if (!logits || !depth_out || !conf_out) fail(DR_ERR_ARG, "drm_debug_regress: null pointer");
+    debug_check_planes("drm_debug_regress", D, h, w, prev, hp, wp);
+    debug_device(device, "drm_debug_regress");
+    const MvsSwitches sw;  // read from the environment, as the engine's
+    DeviceArena arena;
+    const size_t hw = (size_t)h * w;
+    const float *d_logits = arena.upload(std::vector<float>(logits, logits + (size_t)D * hw));
+    const RegressArgs r = debug_regress_args(arena, d_logits, D, h, w, prev, hp, wp, dmin, interval, half_range, full_range);
+    launch_regress(r, sw, nullptr);
+    DR_HIP(hipDeviceSynchronize());
+    DR_HIP(hipGetLastError());
+    DR_HIP(hipMemcpy(depth_out, r.depth, hw * 4, hipMemcpyDeviceToHost));
+    DR_HIP(hipMemcpy(conf_out, r.conf, hw * 4, hipMemcpyDeviceToHost));
+    if (kernel_name_out) debug_regress_name(kernel_name_out, 64, D, sw);
+  });
+}
+
+int drm_debug_prob_regress(int device, const float *x11, const float *w_prob, int D, int h, int w, const float *prev, int hp, int wp, float dmin, float interval,
+                           float half_range, float full_range, float *logits_out, float *depth_out, float *conf_out, char kernel_name_out[64]) {
+  return guarded([&] {
+    using namespace dr;
+    if (!x11 || !w_prob || !logits_out || !depth_out || !conf_out) fail(DR_ERR_ARG, "drm_debug_prob_regress: null pointer");
+    debug_check_planes("drm_debug_prob_regress", D, h, w, prev, hp, wp);
+    debug_device(device, "drm_debug_prob_regress");
+    const MvsSwitches sw;
+    DeviceArena arena;
+    const size_t hw = (size_t)h * w;
+    ProbArgs p{};
+    p.x = arena.upload(std::vector<float>(x11, x11 + (size_t)D * hw * 8));
+    p.wt = arena.upload(prob_taps(std::vector<float>(w_prob, w_prob + 8 * 27)));
+    p.out = debug_poison(arena, (size_t)D * hw);
+    p.D = D; p.h = h; p.w = w;
+    const RegressArgs r = debug_regress_args(arena, p.out, D, h, w, prev, hp, wp, dmin, interval, half_range, full_range);
+    const int stage = 3;  // (choose_prob asks for a stage 1..3 and nothing else of it)
+    const ProbChoice k = choose_prob(prob_shape(p), sw, stage);
+    launch_prob(p, r, sw, stage, nullptr);
+    if (!k.regresses()) launch_regress(r, sw, nullptr);
+    DR_HIP(hipDeviceSynchronize());
+    DR_HIP(hipGetLastError());
+    DR_HIP(hipMemcpy(logits_out, p.out, (size_t)D * hw * 4, hipMemcpyDeviceToHost));
+    DR_HIP(hipMemcpy(depth_out, r.depth, hw * 4, hipMemcpyDeviceToHost));
+    DR_HIP(hipMemcpy(conf_out, r.conf, hw * 4, hipMemcpyDeviceToHost));
+    if (kernel_name_out) {
+      k.name(kernel_name_out, 64);
+      if (!k.regresses()) {  // two launches: "k_prob2<1>+k_regress_r<8>"
+        const size_t n = strlen(kernel_name_out);
+        kernel_name_out[n] = '+';
+        debug_regress_name(kernel_name_out + n + 1, 64 - n - 1, D, sw);
+      }
+    }
+  });
+}
+
+int drm_debug_edge_filter(int device, const float *depth, const float *conf, int H, int W, const float *edge_in, unsigned rank, float *edge_out, float *depth_out,
+                          float *conf_out, unsigned *thr_bits_out) {
+  return guarded([&] {
+    using namespace dr;
+    if (!depth || !conf || !edge_out || !depth_out || !conf_out || !thr_bits_out) fail(DR_ERR_ARG, "drm_debug_edge_filter: null pointer");
+    if (H <= 0 || W <= 0 || (long long)H * W > (1ll << 28)) fail(DR_ERR_ARG, "drm_debug_edge_filter: H, W must be positive, H W <= 2^28");
+    const size_t n = (size_t)H * W;
+    if (rank >= n) fail(DR_ERR_ARG, "drm_debug_edge_filter: rank %u of %zu values", rank, n);
+    debug_device(device, "drm_debug_edge_filter");
+    const MvsSwitches sw;
+    DeviceArena arena;
+    FilterArgs f{};
+    f.depth3 = arena.upload(std::vector<float>(depth, depth + n));
+    f.conf3 = arena.upload(std::vector<float>(conf, conf + n));
+    f.edge = debug_poison(arena, n);
+    f.depth = debug_poison(arena, n);
+    f.conf = debug_poison(arena, n);
+    f.state = arena.upload(std::vector<unsigned>(16, 0u));        // as the engine's: four 4-word slots, zero
+    f.hist = arena.upload(std::vector<unsigned>(3 * 2048, 0u));   // one zeroed histogram per level
+    f.n = (int)n; f.H = H; f.W = W;
+    f.hist_blocks = sw.hist_blocks; f.fused = sw.filter_fused;
+    // the EDGE, HIST x 3, (SCAN x 3,) APPLY sequence of MvsEngine::configure
+    launch_edge(f, rank, nullptr);
+    if (edge_in) DR_HIP(hipMemcpyAsync(f.edge, edge_in, n * 4, hipMemcpyHostToDevice, nullptr));  // in stream order: behind the edge kernel, before level 0
+    for (int i = 0; i < 3; ++i) {
+      launch_hist(f, i, i ? kSelectShift[i - 1] : 0, i ? kSelectBits[i - 1] : 0, kSelectShift[i], kSelectBits[i], nullptr);
+      if (!f.fused) launch_scan(f, kSelectShift[i], kSelectBits[i], nullptr);
+    }
+    launch_apply(f, kSelectShift[2], kSelectBits[2], nullptr);
+    DR_HIP(hipDeviceSynchronize());
+    DR_HIP(hipGetLastError());
+    DR_HIP(hipMemcpy(edge_out, f.edge, n * 4, hipMemcpyDeviceToHost));
+    DR_HIP(hipMemcpy(depth_out, f.depth, n * 4, hipMemcpyDeviceToHost));
+    DR_HIP(hipMemcpy(conf_out, f.conf, n * 4, hipMemcpyDeviceToHost));
+    // the threshold: word [3] of the select's state -- of the last slot in the fused form (one slot per level, mvs_kernels.h), of the only slot otherwise
+    DR_HIP(hipMemcpy(thr_bits_out, f.state + (f.fused ? 3 * 4 + 3 : 3), 4, hipMemcpyDeviceToHost));
   });
 }
 

@@ -16,6 +16,7 @@
 #include <utility>
 
 #include "dr_common.h"
+#include "edge_network.h"  // DR_EDGE_NETWORK: the selection network of edge_pixel
 #include "mvs_host.h"  // kMaxSrc, kProbTY / kProbTX: constants the host half shares with the kernels
 
 namespace dr {
@@ -1238,22 +1239,13 @@ __device__ inline void edge_pixel(const float *__restrict__ depth, float *__rest
   }
   edge[n] = kth;
 #else
-  // the same order statistic from a sorting network: Knuth's merge exchange (TAOCP 5.2.2 M) for 25 inputs has 138 comparators,
-  // the 113 below are the ones element 14 of the sorted order depends on (of which the compiler drops the unused min or max
-  // halves).  A k-th smallest VALUE does not depend on how it is found, so the result is the counting form's bit for bit.
+  // the same order statistic from a selection network (edge_network.h: 113 of the 138 comparators of Knuth's merge exchange for 25 inputs,
+  // checked on the host by tests/cpp/edge_network_check.cpp; the compiler drops the unused min or max halves).  A k-th smallest VALUE does not
+  // depend on how it is found, so the result is the counting form's bit for bit.
 #define CE(A, B) { const float lo_ = fminf(v[A], v[B]), hi_ = fmaxf(v[A], v[B]); v[A] = lo_; v[B] = hi_; }
-  CE(0,16) CE(1,17) CE(2,18) CE(3,19) CE(4,20) CE(5,21) CE(6,22) CE(7,23) CE(8,24) CE(0,8) CE(1,9) CE(2,10)
-  CE(3,11) CE(4,12) CE(5,13) CE(6,14) CE(7,15) CE(16,24) CE(8,16) CE(9,17) CE(10,18) CE(11,19) CE(12,20) CE(13,21)
-  CE(14,22) CE(15,23) CE(0,4) CE(1,5) CE(2,6) CE(3,7) CE(8,12) CE(9,13) CE(10,14) CE(11,15) CE(16,20) CE(17,21)
-  CE(18,22) CE(19,23) CE(4,16) CE(5,17) CE(6,18) CE(7,19) CE(12,24) CE(4,8) CE(5,9) CE(6,10) CE(7,11) CE(12,16)
-  CE(13,17) CE(14,18) CE(15,19) CE(20,24) CE(0,2) CE(1,3) CE(4,6) CE(5,7) CE(8,10) CE(9,11) CE(12,14) CE(13,15)
-  CE(16,18) CE(17,19) CE(20,22) CE(21,23) CE(2,16) CE(3,17) CE(6,20) CE(7,21) CE(10,24) CE(2,8) CE(3,9) CE(6,12)
-  CE(7,13) CE(10,16) CE(11,17) CE(14,20) CE(15,21) CE(18,24) CE(2,4) CE(3,5) CE(6,8) CE(7,9) CE(10,12) CE(11,13)
-  CE(14,16) CE(15,17) CE(18,20) CE(19,21) CE(22,24) CE(0,1) CE(2,3) CE(4,5) CE(6,7) CE(8,9) CE(10,11) CE(12,13)
-  CE(14,15) CE(16,17) CE(18,19) CE(20,21) CE(22,23) CE(1,16) CE(3,18) CE(5,20) CE(7,22) CE(9,24) CE(7,14) CE(9,16)
-  CE(11,18) CE(13,20) CE(11,14) CE(13,16) CE(13,14)
+  DR_EDGE_NETWORK(CE)
 #undef CE
-  edge[n] = v[14];  // k = 15 (1-based), module.py:1336,1343
+  edge[n] = v[DR_EDGE_WIRE];  // k = 15 (1-based), module.py:1336,1343
 #endif
 }
 __global__ __launch_bounds__(256) void k_edge(const float *__restrict__ depth, float *__restrict__ edge, int h, int w, unsigned *__restrict__ state, unsigned rank) {

@@ -183,6 +183,8 @@ struct FilterArgs {
   int hist_blocks;              // workgroups of a histogram level (MvsSwitches::hist_blocks)
   bool fused;                   // the scans run as the prologue of the kernels that follow them (MvsSwitches::filter_fused)
 };
+// the three levels of the select: key bits [21, 32), [10, 21), [0, 10)
+constexpr int kSelectShift[3] = {21, 10, 0}, kSelectBits[3] = {11, 11, 10};
 inline void launch_edge(const FilterArgs &f, unsigned rank, hipStream_t st) {
   if (f.fused) hipLaunchKernelGGL(k_edge2, dim3(cdiv(f.n, 256)), dim3(256), 0, st, f.depth3, f.edge, f.H, f.W, f.state, f.hist, rank);
   else hipLaunchKernelGGL(k_edge, dim3(cdiv(f.n, 256)), dim3(256), 0, st, f.depth3, f.edge, f.H, f.W, f.state, rank);

@@ -295,3 +295,57 @@ def debug_tail(x, skip, w_deconv, scale, bias, w_prob, qy=0, zchunk=0, form=1, d
     out = np.empty((D, h, w), np.float32)
     check(_lib.lib().drm_debug_tail(device, fptr(x), fptr(skip), fptr(wd), fptr(sc), fptr(bi), fptr(wp), D, h, w, int(qy), int(zchunk), int(form), fptr(out)))
     return out
+
+
+def _plane_args(h, w, prev):
+    """(the contiguous prev, kept alive by the caller; its pointer; hp; wp) of the two regression hooks -- (None, None, 0, 0) for uniform planes."""
+    if prev is None:
+        return None, None, 0, 0
+    prev = np.ascontiguousarray(prev, np.float32)
+    assert prev.shape == (h // 2, w // 2) and h % 2 == 0 and w % 2 == 0, (prev.shape, h, w)
+    return prev, fptr(prev), prev.shape[0], prev.shape[1]
+
+
+def debug_regress(logits, dmin=0.0, interval=1.0, prev=None, half_range=0.0, full_range=0.0, device=0):
+    """Kernel unit-test hook for k_regress / k_regress_r<D>: logits (D, h, w); prev None: uniform planes dmin + interval * k, else the previous stage's depth
+    (h / 2, w / 2) and the adaptive planes lo = max(up2(prev) - half_range, 1e-3), lo + full_range * k / D.  Returns (depth (h, w), conf (h, w), kernel name)."""
+    lg = np.ascontiguousarray(logits, np.float32)
+    D, h, w = lg.shape
+    keep, pp, hp, wp = _plane_args(h, w, prev)
+    depth, conf = np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    name = C.create_string_buffer(64)
+    check(_lib.lib().drm_debug_regress(device, fptr(lg), D, h, w, pp, hp, wp, float(dmin), float(interval), float(half_range), float(full_range),
+                                       fptr(depth), fptr(conf), name))
+    del keep
+    return depth, conf, name.value.decode()
+
+
+def debug_prob_regress(x11, w_prob, dmin=0.0, interval=1.0, prev=None, half_range=0.0, full_range=0.0, device=0):
+    """Kernel unit-test hook for k_prob2 / k_prob2_regress<8>: x11 (D, h, w, 8) channels-last, w_prob (1, 8, 3, 3, 3); the planes as debug_regress.
+    Returns (logits (D, h, w), depth (h, w), conf (h, w), kernel name(s), "+"-joined where the regression is a launch of its own)."""
+    x = np.ascontiguousarray(x11, np.float32)
+    wp_ = np.ascontiguousarray(w_prob, np.float32)
+    D, h, w, c = x.shape
+    assert c == 8 and wp_.shape == (1, 8, 3, 3, 3), (x.shape, wp_.shape)
+    keep, pp, hp, wp = _plane_args(h, w, prev)
+    logits, depth, conf = np.empty((D, h, w), np.float32), np.empty((h, w), np.float32), np.empty((h, w), np.float32)
+    name = C.create_string_buffer(64)
+    check(_lib.lib().drm_debug_prob_regress(device, fptr(x), fptr(wp_), D, h, w, pp, hp, wp, float(dmin), float(interval), float(half_range), float(full_range),
+                                            fptr(logits), fptr(depth), fptr(conf), name))
+    del keep
+    return logits, depth, conf, name.value.decode()
+
+
+def debug_edge_filter(depth, conf, rank, edge_in=None, device=0):
+    """Kernel unit-test hook for the edge filter (k_edge / k_edge2, the three-level radix select, k_apply / k_apply_s): depth, conf (H, W); rank: the 0-based
+    order statistic of the edge values that is the threshold; edge_in (H, W) or None: values that replace the edge measure before the select.
+    Returns (edge, filtered depth, filtered conf, threshold bits)."""
+    d, c = np.ascontiguousarray(depth, np.float32), np.ascontiguousarray(conf, np.float32)
+    H, W = d.shape
+    assert c.shape == (H, W)
+    e = None if edge_in is None else np.ascontiguousarray(edge_in, np.float32)
+    assert e is None or e.shape == (H, W)
+    edge, od, oc = np.empty((H, W), np.float32), np.empty((H, W), np.float32), np.empty((H, W), np.float32)
+    thr = C.c_uint()
+    check(_lib.lib().drm_debug_edge_filter(device, fptr(d), fptr(c), H, W, None if e is None else fptr(e), int(rank), fptr(edge), fptr(od), fptr(oc), C.byref(thr)))
+    return edge, od, oc, int(thr.value)

@@ -6,7 +6,9 @@ volume gathers its four taps from a zero-padded map (no grid_sample), the homogr
 are imported by
   tests/test_mvs_stage_ref.py    (CPU: the fp32 oracle against these = the reference's own rounding error, and what a
                                   one-line mistake moves)
-  tests/test_mvs_stages_gpu.py   (GPU: every stage tensor of the engine against these, fed the engine's own stage input).
+  tests/test_mvs_stages_gpu.py   (GPU: every stage tensor of the engine against these, fed the engine's own stage input)
+  tests/mvs_adversarial.py       (the regression run alone on inputs no network produces: adaptive_planes64 / uniform_planes64, regress64 and its
+                                  mutants regress_out64(mutant=); E_DEPTH_ADV / E_CONF_ADV are measured by tests/test_mvs_adversarial_ref.py).
 
 Layouts are the engine's logical ones (DrMvsnet.tensor): feature maps (V, h, w, C), volumes (D, h, w, C), x11 (D, h, w, 8),
 logits (D, h, w), planes (D, h, w); views in model order [ref, the others in window order].
@@ -45,6 +47,8 @@ E_VOL_PLAIN = {1: 5.20e-06, 2: 1.31e-05, 3: 2.45e-05}       # the plain-variance
 E_VOL_PLAIN_MEAN = {1: 8.68e-08, 2: 1.95e-07, 3: 3.69e-07}  # (maximum over test_mvs_stage_ref.PLAIN_WINDOWS)
 E_DEPTH = 4.77e-07
 E_CONF = 5.64e-07
+E_DEPTH_ADV = 6.66e-07  # the same two figures on the adversarial logits of tests/mvs_adversarial.py (regression run alone): recorded by
+E_CONF_ADV = 5.70e-07   #     python -m pytest tests/test_mvs_adversarial_ref.py -q -s -k reference_error
 E_FEAT = {1: 9.23e-07, 2: 9.44e-07, 3: 9.16e-07}
 E_LAYER = 1.72e-06  # one layer (THE LAYER RESTATEMENTS), of layer_scale(): the maximum over CPU_WINDOWS and SMALL_WINDOWS, every CostRegNet and FeatureNet layer
 # ---
@@ -152,10 +156,26 @@ def planes64(stage, engine_prev_depth, dmin, dmax, meta, h, w):
     if stage == 1:
         return np.broadcast_to(dmin + base * k, (D, h, w)).copy()
     delta = float(np.float32(meta["interval_ratio"][stage - 1])) * base
-    cur = _up2(engine_prev_depth, h, w)
-    lo = np.maximum(cur - (D / 2.0) * delta, 1e-3)
+    return adaptive_planes64(engine_prev_depth, D, delta, h, w)
+
+
+def adaptive_planes64(prev, D, delta, h, w, mutant=None):
+    """(D, h, w) planes around the x2 upsampled `prev` (h / 2, w / 2): lo = max(cur - D/2 delta, 1e-3), d_k = lo + (hi - lo) k / D, hi = lo + D delta.
+    The kernels' PlaneArgs in double: half_range = D/2 delta, full_range = D delta.  mutant "no_lo_clamp": the 1e-3 clamp left out."""
+    assert mutant in (None, "no_lo_clamp"), mutant
+    k = np.arange(D, dtype=np.float64).reshape(D, 1, 1)
+    cur = _up2(prev, h, w)
+    lo = cur - (D / 2.0) * delta
+    if mutant is None:
+        lo = np.maximum(lo, 1e-3)
     hi = lo + D * delta
     return lo[None] + (hi - lo)[None] * (k / D)
+
+
+def uniform_planes64(dmin, interval, D, h, w):
+    """(D, h, w) planes dmin + interval k (PlaneArgs with prev == NULL), from the float values the kernel receives."""
+    k = np.arange(D, dtype=np.float64).reshape(D, 1, 1)
+    return np.broadcast_to(float(np.float32(dmin)) + float(np.float32(interval)) * k, (D, h, w)).copy()
 
 
 # ------------------------------------------------------------------ cost volume
@@ -274,6 +294,43 @@ def regress64(logits, planes):
     pp = np.concatenate([np.zeros((1,) + p.shape[1:]), p, np.zeros((2,) + p.shape[1:])])
     sum4 = pp[0:D] + pp[1:D + 1] + pp[2:D + 2] + pp[3:D + 3]
     return depth, ek, sum4
+
+
+# deliberate one-line mistakes of the REGRESSION (tests/test_mvs_adversarial_ref.py shows each leaves the bound of, or breaks an exact comparison of,
+# tests/test_mvs_adversarial_gpu.py on that test's own inputs):
+#   no_max_subtraction   softmax as exp(x) / sum exp(x)
+#   rint                 the confidence window around rint(E[k]) instead of trunc(E[k])
+#   window_m1_p1         the window idx-1 .. idx+1
+#   window_m2_p1         the window idx-2 .. idx+1
+#   no_idx_clamp         index and window taken without the clamp to 0 .. D-1: a tap outside the range reads the plane modulo D instead of counting 0.
+#                        (The clamp of trunc(E[k]) ALONE cannot be reached by finite logits -- E[k] is a convex combination of 0 .. D-1, and the few ulps by
+#                        which an fp32 sum may exceed D-1 do not survive the truncation -- so the mutant removes it together with the range test of the taps.)
+# and of the PLANES: adaptive_planes64(mutant="no_lo_clamp").
+REGRESS_MUTANTS = ("no_max_subtraction", "rint", "window_m1_p1", "window_m2_p1", "no_idx_clamp")
+
+
+def regress_out64(logits, planes, mutant=None):
+    """(depth, conf) of regress64 with the confidence gathered at clamp(trunc(E[k])); mutant: one of REGRESS_MUTANTS."""
+    assert mutant is None or mutant in REGRESS_MUTANTS, mutant
+    lg = np.asarray(logits, np.float64)
+    D = lg.shape[0]
+    with np.errstate(over="ignore", invalid="ignore"):
+        e = np.exp(lg if mutant == "no_max_subtraction" else lg - lg.max(axis=0, keepdims=True))
+        p = e / e.sum(axis=0, keepdims=True)
+    depth = (p * np.asarray(planes, np.float64)).sum(axis=0)
+    ek = (p * np.arange(D, dtype=np.float64).reshape(D, 1, 1)).sum(axis=0)
+    with np.errstate(invalid="ignore"):
+        idx = np.nan_to_num(np.rint(ek) if mutant == "rint" else np.trunc(ek)).astype(np.int64)
+    lo, hi = {"window_m1_p1": (-1, 1), "window_m2_p1": (-2, 1)}.get(mutant, (-1, 2))
+    conf = np.zeros(ek.shape)
+    for o in range(lo, hi + 1):
+        k = idx + o
+        if mutant == "no_idx_clamp":
+            conf += np.take_along_axis(p, (k % D)[None], axis=0)[0]
+        else:
+            k0 = np.clip(idx, 0, D - 1) + o
+            conf += np.where((k0 >= 0) & (k0 < D), np.take_along_axis(p, np.clip(k0, 0, D - 1)[None], axis=0)[0], 0.0)
+    return depth, conf
 
 
 def conf_at(sum4, idx):

@@ -66,6 +66,27 @@ def test_no_gpu_means_loud_failure(built, trained_blob):
     assert e.value.code == 3
 
 
+def test_regression_and_filter_hooks_check_their_arguments_first(built):
+    """drm_debug_regress / drm_debug_prob_regress / drm_debug_edge_filter: wrong shapes are DR_ERR_ARG before any device is touched (so also here, without
+    one): a prev that is not (h / 2, w / 2) -- the x2 upsampling would read outside it --, no planes, a rank beyond the last value."""
+    from tandem_amd import dr_mvsnet as M
+    for prev in (np.ones((2, 3), np.float32), np.ones((3, 2), np.float32)):
+        with pytest.raises(AssertionError):
+            M.debug_regress(np.zeros((4, 4, 4), np.float32), prev=prev, half_range=0.1, full_range=0.2)
+    L, f32p = built.lib(), built.f32p
+    z = np.zeros(4 * 4 * 4 * 8, np.float32)
+    o = np.zeros(64, np.float32)
+    thr = C.c_uint()
+    p = lambda a: a.ctypes.data_as(f32p)  # noqa: E731
+    assert L.drm_debug_regress(0, p(z), 4, 4, 4, p(z), 2, 3, 0.5, 0.1, 0.1, 0.2, p(o), p(o), None) == 1
+    assert L.drm_debug_regress(0, p(z), 0, 4, 4, None, 0, 0, 0.5, 0.1, 0.0, 0.0, p(o), p(o), None) == 1
+    assert L.drm_debug_prob_regress(0, p(z), p(z), 4, 4, 4, p(z), 1, 1, 0.5, 0.1, 0.1, 0.2, p(z), p(o), p(o), None) == 1
+    assert L.drm_debug_prob_regress(0, p(z), None, 4, 4, 4, None, 0, 0, 0.5, 0.1, 0.0, 0.0, p(z), p(o), p(o), None) == 1
+    assert L.drm_debug_edge_filter(0, p(z), p(z), 4, 4, None, 16, p(o), p(o), p(o), C.byref(thr)) == 1
+    assert L.drm_debug_edge_filter(0, p(z), p(z), 0, 4, None, 0, p(o), p(o), p(o), C.byref(thr)) == 1
+    assert b"rank 16 of 16" in L.dr_last_error() or b"H, W" in L.dr_last_error()
+
+
 def test_missing_blob_is_an_io_error(built):
     from tandem_amd.dr_mvsnet import DrMvsnet
     with pytest.raises(built.DrError) as e:
