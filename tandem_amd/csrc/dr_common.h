@@ -114,7 +114,7 @@ inline T *dalloc(size_t n, const char *label = nullptr, const char *file = __bui
 }
 #else
 template <class T>
-inline T *dalloc(size_t n, const char * = nullptr) {
+inline T *dalloc(size_t n, const char * = nullptr, const char * = nullptr, int = 0) {  // (label, file and line name the buffer for the parity build's guards only)
   void *p = nullptr;
   DR_HIP(hipMalloc(&p, n * sizeof(T) > 0 ? n * sizeof(T) : 16));
   return reinterpret_cast<T *>(p);

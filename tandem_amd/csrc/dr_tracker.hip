@@ -16,6 +16,7 @@
 #include <memory>
 
 #include "dr_common.h"
+#include "hip_owner.h"  // HipOwner: what the engine takes from the runtime
 
 namespace dr {
 
@@ -238,16 +239,9 @@ class TrackerEngine {
     DR_HIP(hipSetDevice(device_));
     int lo, hi;
     DR_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    DR_HIP(hipStreamCreateWithPriority(&stream_, hipStreamNonBlocking, hi));  // cuda_coarse_tracker.cpp:63-68: greatest priority
+    stream_ = own_.stream(hi);  // cuda_coarse_tracker.cpp:63-68: greatest priority
   }
-  ~TrackerEngine() {
-    (void)hipSetDevice(device_);
-    (void)hipStreamSynchronize(stream_);
-    release();
-    if (ev0_) (void)hipEventDestroy(ev0_);
-    if (ev1_) (void)hipEventDestroy(ev1_);
-    (void)hipStreamDestroy(stream_);
-  }
+  ~TrackerEngine() { (void)hipSetDevice(device_); }  // (own_ lets go of everything on the device it was taken on)
   void set_k(int w, int h, float fx, float fy, float cx, float cy) {  // cuda_coarse_tracker.cpp:358-372
     if (w != w_ || h != h_) fail(DR_ERR_ARG, "CudaCoarseTracker::setK wrong h,w.");
     fx_ = fx; fy_ = fy; cx_ = cx; cy_ = cy;
@@ -264,13 +258,13 @@ class TrackerEngine {
     if (n_max_ != 0) fail(DR_ERR_PROTOCOL, "Cannot call CudaCoarseTracker::init more than once.");
     DR_HIP(hipSetDevice(device_));
     n_max_ = n_max > 0 ? n_max : w_ * h_;
-    for (int k = 0; k < 4; ++k) { pc_[k] = dalloc<float>(n_max_); DR_HIP(hipHostMalloc((void **)&h_pc_[k], (size_t)n_max_ * 4, hipHostMallocDefault)); }
-    for (int k = 0; k < 7; ++k) warped_[k] = dalloc<float>(n_max_);
-    dInew_ = dalloc<float>((size_t)3 * w_ * h_);
-    DR_HIP(hipHostMalloc((void **)&h_dInew_, (size_t)12 * w_ * h_, hipHostMallocDefault));
-    partial_ = dalloc<double>((size_t)std::max(cdiv(n_max_, kTrkThreads), kTrkMaxBlocks) * 45);
-    sums_ = dalloc<double>(64);
-    DR_HIP(hipHostMalloc((void **)&h_sums_, 64 * 8, hipHostMallocDefault));
+    for (int k = 0; k < 4; ++k) { pc_[k] = own_.device<float>(n_max_); h_pc_[k] = own_.pinned<float>(n_max_); }
+    for (int k = 0; k < 7; ++k) warped_[k] = own_.device<float>(n_max_);
+    dInew_ = own_.device<float>((size_t)3 * w_ * h_);
+    h_dInew_ = own_.pinned<float>((size_t)3 * w_ * h_);
+    partial_ = own_.device<double>((size_t)std::max(cdiv(n_max_, kTrkThreads), kTrkMaxBlocks) * 45);
+    sums_ = own_.device<double>(64);
+    h_sums_ = own_.pinned<double>(64);
   }
   void set_reference(int n, const float *u, const float *v, const float *id, const float *col, float ref_exposure, const double *ref_aff) {
     need_init();
@@ -362,8 +356,10 @@ class TrackerEngine {
     DR_HIP(hipSetDevice(device_));
     const size_t npix = (size_t)w_ * h_;
     if (!zbuf_) {
-      zbuf_ = dalloc<unsigned>(npix); rowcnt_ = dalloc<int>(h_ + 2);
-      up_depth_ = dalloc<float>(npix); up_idepth_ = dalloc<float>(npix); up_dip_ = dalloc<float>(npix * 3);
+      unsigned *z = own_.device<unsigned>(npix);
+      rowcnt_ = own_.device<int>(h_ + 2);
+      up_depth_ = own_.device<float>(npix); up_idepth_ = own_.device<float>(npix); up_dip_ = own_.device<float>(npix * 3);
+      zbuf_ = z;  // (set last: the group is there as a whole or, for the next call, not at all)
     }
     const float *d_depth = depth, *d_id = idepth0, *d_dip = dIp0;
     if (!on_device) {
@@ -416,7 +412,7 @@ class TrackerEngine {
   void start_timing() {  // cuda_coarse_tracker.cpp:374-381
     if (timing_) fail(DR_ERR_PROTOCOL, "CudaCoarseTracker::startTiming. Did not destroy events before correctly.");
     DR_HIP(hipSetDevice(device_));
-    if (!ev0_) { DR_HIP(hipEventCreate(&ev0_)); DR_HIP(hipEventCreate(&ev1_)); }
+    if (!ev1_) { ev0_ = own_.event(hipEventDefault); ev1_ = own_.event(hipEventDefault); }  // (with timing)
     DR_HIP(hipEventRecord(ev0_, stream_));
     timing_ = true;
   }
@@ -440,13 +436,6 @@ class TrackerEngine {
     for (int k = 0; k < 7; ++k) d.warped[k] = warped_[k];
     return d;
   }
-  void release() {
-    for (int k = 0; k < 4; ++k) { dfree(pc_[k]); if (h_pc_[k]) (void)hipHostFree(h_pc_[k]); }
-    for (int k = 0; k < 7; ++k) dfree(warped_[k]);
-    dfree(dInew_); if (h_dInew_) (void)hipHostFree(h_dInew_);
-    dfree(partial_); dfree(sums_); if (h_sums_) (void)hipHostFree(h_sums_);
-    dfree(zbuf_); dfree(rowcnt_); dfree(up_depth_); dfree(up_idepth_); dfree(up_dip_);
-  }
   int device_, w_, h_;
   float huber_;
   [[maybe_unused]] float cutoff_;  // setting_coarseCutoffTH: stored, never read -- as in the reference (calcRes gets cutoffTH per call)
@@ -456,6 +445,7 @@ class TrackerEngine {
   int n_ = 0, n_max_ = 0, num_terms_in_warped_ = 0;
   float ref_exposure_ = 0;
   double ref_aff_[2] = {0, 0};
+  HipOwner own_;  // the stream, the timing events, every array below
   hipStream_t stream_ = nullptr;
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
   float *pc_[4] = {}, *h_pc_[4] = {}, *warped_[7] = {};

@@ -1,6 +1,6 @@
-// What the DrFusion engine takes from the HIP runtime (included by dr_fusion.hip and map_ops.h): HipOwner for what lives as long as the engine, DeviceBuf /
-// PinnedBuf for scratch that grows with its use, BlockStaging for the double-buffered transport of stored voxel blocks to the device,
-// PinnedPair for the two page-locked chunk buffers of the map file.
+// What the engines take from the HIP runtime (included by dr_fusion.hip, map_ops.h, mvs_plan.h, dr_mvsnet.hip and dr_tracker.hip): HipOwner for what lives
+// as long as its holder (an engine, a DrMvsnet window plan, one measurement), and for DrFusion DeviceBuf / PinnedBuf for scratch that grows with its
+// use, BlockStaging for the double-buffered transport of stored voxel blocks to the device, PinnedPair for the two chunk buffers of the map file.
 #pragma once
 #include <vector>
 
@@ -8,25 +8,26 @@
 
 namespace dr {
 
-// Owner of what the engine takes from the runtime for its lifetime: device and pinned buffers, events, streams.  All of it is
-// released with the owner -- buffers first, then the events and streams that work on them used -- also when the engine's
-// constructor throws half way.  The raw pointers and handles go where they are used (FusionDev, StreamDev, McArgs: by value).
+// Owner of what its holder takes from the runtime for its lifetime: device and pinned buffers, events, streams.  All of it is
+// released with the owner -- buffers first, then the events and streams that work on them used -- also when the holder's
+// constructor throws half way; the current device at that moment is the one it was taken on (the holder sees to it).  The raw
+// pointers and handles go where they are used (FusionDev, StreamDev, McArgs: by value).
 class HipOwner {
  public:
   HipOwner() = default;
   HipOwner(const HipOwner &) = delete;
   void operator=(const HipOwner &) = delete;
   ~HipOwner() {
-    if (dev_.empty() && pin_.empty() && ev_.empty() && st_.empty()) return;  // nothing taken: no device of ours to wait for
-    (void)hipDeviceSynchronize();
+    // (nothing to wait for where nothing was taken, or events only: those of one measurement, in a function-local owner)
+    if (!dev_.empty() || !pin_.empty() || !st_.empty()) (void)hipDeviceSynchronize();
     for (void *p : dev_) dfree(p);
     for (void *p : pin_) (void)hipHostFree(p);
     for (hipEvent_t e : ev_) (void)hipEventDestroy(e);
     for (hipStream_t s : st_) (void)hipStreamDestroy(s);
   }
-  // device memory, cleared on stream `zero_on` if one is given
-  template <class T> T *device(size_t n, hipStream_t zero_on = nullptr) {
-    T *p = (T *)take(dev_, [&](void **q) { *q = dalloc<T>(n); });
+  // device memory, cleared on stream `zero_on` if one is given.  The guarded allocator of the parity build names the buffer `label`, or the caller's file and line.
+  template <class T> T *device(size_t n, hipStream_t zero_on = nullptr, const char *label = nullptr, const char *file = __builtin_FILE(), int line = __builtin_LINE()) {
+    T *p = (T *)take(dev_, [&](void **q) { *q = dalloc<T>(n, label, file, line); });
     if (zero_on) DR_HIP(hipMemsetAsync(p, 0, n * sizeof(T), zero_on));
     return p;
   }
@@ -41,6 +42,10 @@ class HipOwner {
   }
   hipStream_t stream(int priority = 0) {
     return take(st_, [&](hipStream_t *q) { DR_HIP(hipStreamCreateWithPriority(q, hipStreamNonBlocking, priority)); });
+  }
+  // the same from the call that names no priority (DrMvsnet: the runtime maps streams to hardware queues as they are created; its speed was measured with this call)
+  hipStream_t stream_plain() {
+    return take(st_, [&](hipStream_t *q) { DR_HIP(hipStreamCreateWithFlags(q, hipStreamNonBlocking)); });
   }
 
  private:

@@ -15,18 +15,21 @@ inline void launch_preprocess(const PreprocessArgs &a, hipStream_t st) {
   hipLaunchKernelGGL(k_preprocess, dim3((unsigned)((a.npix + 255) / 256)), dim3(256), 0, st, a.bgr, a.img, a.lut, a.npix);
 }
 inline void launch_cache_io(const CacheIoArgs &io, int V, hipStream_t st) { hipLaunchKernelGGL(k_cache_io, dim3(32, V), dim3(256), 0, st, io); }
-// out: the first logical pixel of a (V, H, W, 8) tensor with a zero border of `pad` pixels
-inline void launch_out3_border(float *out, const float *T, int V, int H, int W, int pad, hipStream_t st) {
-  const int per = 2 * (H + W) - 4, n = V * per * 8;
-  const int rs = (W + 2 * pad) * 8;
-  hipLaunchKernelGGL(k_out3_border, dim3(cdiv(n, 256)), dim3(256), 0, st, out, T, V, H, W, rs, (size_t)(H + 2 * pad) * rs);
+// out: the first logical pixel of a (V, H, W, 8) tensor with a zero border of `pad` pixels; T: the border correction (compose_out3)
+struct BorderFixArgs { float *out; const float *T; int V, H, W, pad; };
+inline void launch_out3_border(const BorderFixArgs &a, hipStream_t st) {
+  const int per = 2 * (a.H + a.W) - 4, n = a.V * per * 8;
+  const int rs = (a.W + 2 * a.pad) * 8;
+  hipLaunchKernelGGL(k_out3_border, dim3(cdiv(n, 256)), dim3(256), 0, st, a.out, a.T, a.V, a.H, a.W, rs, (size_t)(a.H + 2 * a.pad) * rs);
 }
-inline void launch_skip_up(const float *x, const float *w, const float *bias, const float *coarse, float *out, int V, int H, int W, hipStream_t st) {
+// x: (V, H, W, cin); w, bias: the 1x1 layer cin -> 32; coarse: (V, H / 2, W / 2, 32), added nearest-upsampled.  cin names the instance (8 is the one there is).
+struct SkipUpArgs { const float *x, *w, *bias, *coarse; float *out; int V, H, W, cin; };
+inline void launch_skip_up([[maybe_unused]] const SkipUpArgs &a, [[maybe_unused]] hipStream_t st) {
 #ifdef DR_PARITY_HOOKS
-  const size_t npix = (size_t)V * H * W;
+  const size_t npix = (size_t)a.V * a.H * a.W;
   const dim3 grid((unsigned)std::min<size_t>((npix + 31) / 32, 8192));
-  hipLaunchKernelGGL(k_skip_up<8>, grid, dim3(256), 0, st, x, w, bias, coarse, out, V, H, W);
-#endif  // (the product plans no SKIPUP op: MvsEngine::add_skip)
+  hipLaunchKernelGGL(k_skip_up<8>, grid, dim3(256), 0, st, a.x, a.w, a.bias, a.coarse, a.out, a.V, a.H, a.W);
+#endif  // (the product plans no SKIPUP op: MvsPlanBuilder::add_skip)
 }
 
 // The four result maps of a window go to the pinned host block in ONE kernel (16-byte stores over PCIe) instead of four
@@ -189,17 +192,20 @@ inline void launch_edge(const FilterArgs &f, unsigned rank, hipStream_t st) {
   if (f.fused) hipLaunchKernelGGL(k_edge2, dim3(cdiv(f.n, 256)), dim3(256), 0, st, f.depth3, f.edge, f.H, f.W, f.state, f.hist, rank);
   else hipLaunchKernelGGL(k_edge, dim3(cdiv(f.n, 256)), dim3(256), 0, st, f.depth3, f.edge, f.H, f.W, f.state, rank);
 }
-// level 0..2 of the select over key bits [shift, shift + bits); the fused form of levels 1 and 2 first scans the level before (shift_prev, bits_prev)
-inline void launch_hist(const FilterArgs &f, int level, int shift_prev, int bits_prev, int shift, int bits, hipStream_t st) {
+// level 0..2 of the select, over that level's key bits; the fused form of levels 1 and 2 first scans the level before
+inline void launch_hist(const FilterArgs &f, int level, hipStream_t st) {
   const dim3 grid(std::min(cdiv(f.n, 256), f.hist_blocks));
-  if (f.fused && level > 0) hipLaunchKernelGGL(k_hist_s, grid, dim3(256), 0, st, f.edge, f.n, shift_prev, bits_prev, shift, bits, level, f.state, f.hist);
+  const int shift = kSelectShift[level], bits = kSelectBits[level];
+  if (f.fused && level > 0)
+    hipLaunchKernelGGL(k_hist_s, grid, dim3(256), 0, st, f.edge, f.n, kSelectShift[level - 1], kSelectBits[level - 1], shift, bits, level, f.state, f.hist);
   else hipLaunchKernelGGL(k_hist, grid, dim3(256), 0, st, f.edge, f.n, shift, bits, f.state, f.hist);
 }
-inline void launch_scan(const FilterArgs &f, int shift, int bits, hipStream_t st) {
-  hipLaunchKernelGGL(k_scan, dim3(1), dim3(256), 0, st, f.state, f.hist, shift, bits);
+inline void launch_scan(const FilterArgs &f, int level, hipStream_t st) {
+  hipLaunchKernelGGL(k_scan, dim3(1), dim3(256), 0, st, f.state, f.hist, kSelectShift[level], kSelectBits[level]);
 }
-inline void launch_apply(const FilterArgs &f, int shift_last, int bits_last, hipStream_t st) {
-  if (f.fused) hipLaunchKernelGGL(k_apply_s, dim3(cdiv(f.n, 256)), dim3(256), 0, st, f.edge, f.state, f.hist, shift_last, bits_last, f.depth3, f.conf3, f.depth, f.conf, f.n);
+// (the fused form first scans the last level)
+inline void launch_apply(const FilterArgs &f, hipStream_t st) {
+  if (f.fused) hipLaunchKernelGGL(k_apply_s, dim3(cdiv(f.n, 256)), dim3(256), 0, st, f.edge, f.state, f.hist, kSelectShift[2], kSelectBits[2], f.depth3, f.conf3, f.depth, f.conf, f.n);
   else hipLaunchKernelGGL(k_apply, dim3(cdiv(f.n, 256)), dim3(256), 0, st, f.edge, f.state, f.depth3, f.conf3, f.depth, f.conf, f.n);
 }
 

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import mvs_stage_ref as R
-from guard_helpers import assert_same_bits, check, guarded
+from guard_helpers import assert_no_nan, assert_same_bits, check, guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -353,6 +353,67 @@ def test_engine_feature_cache_and_resolution_change_under_guards(trained_blob, p
     on_and_off(run, "feature cache")
 
 
+# ------------------------------------------------------------------ c2. what an engine leaves behind
+def _live():
+    """Guarded buffers alive right now (dr_guard_check), none of them written outside."""
+    st, rep = check()
+    assert st["violations"] == 0, rep
+    return st["live"]
+
+
+def test_a_plan_that_fails_half_way_leaves_nothing_behind(tmp_path, parity_hooks):
+    """depth_num = (16, 12, 4): stage 2's 12 planes are refused (DR_ERR_UNSUPPORTED) after FeatureNet and stage 1 have been allocated.
+    The engine then holds what it held before the call, and nothing once it is closed."""
+    from synth import scene
+    from tandem_amd import _lib
+    from tandem_amd import weights as Wt
+    from tandem_amd.dr_mvsnet import DrMvsnet
+    blob = str(tmp_path / "d12.tdmw")
+    Wt.write_blob(blob, Wt.random_state((16, 12, 4)), depth_num=(16, 12, 4))
+    win = scene.make_window(64, 96, 3, seed=2)
+    with guarded():
+        before = _live()
+        m = DrMvsnet(blob)
+        created = _live()
+        assert created > before  # (the engine's own constants: the count does see this library's allocations)
+        with pytest.raises(_lib.DrError) as e:
+            m.CallAsync(64, 96, 3, win["ref_index"], win["bgrs"], win["K"], list(win["c2ws"]), 0.5, 5.0, 2.5)
+        assert e.value.code == 6 and "depth_num[1]=12" in str(e.value), e.value
+        assert _live() == created
+        m.close(force=True)
+        assert _live() == before
+
+
+def test_a_full_engine_life_cycle_returns_every_buffer(trained_blob, parity_hooks):
+    """Window, feature cache on (re-plan with the single-view plan and its entries), two sliding windows, another window shape (re-plan),
+    autotune (re-planned candidates in the plan's arena), profile (its events), close."""
+    from synth import scene
+    from tandem_amd.dr_mvsnet import DrMvsnet
+    big = scene.make_window(64, 96, 5, seed=31)
+    win5 = scene.make_window(96, 128, 5, seed=7)
+
+    def call(m, H, W, w, views):
+        bgrs = [np.ascontiguousarray(w["bgrs"][v]) for v in views]
+        m.CallAsync(H, W, len(views), 1, bgrs, w["K"], [w["c2ws"][v] for v in views], 0.5, 5.0, 10.0)
+        assert_no_nan(m.GetResult().depth, "%dx%d views %s" % (H, W, list(views)))
+    with guarded():
+        before = _live()
+        m = DrMvsnet(trained_blob)
+        call(m, 64, 96, big, range(0, 3))
+        one_plan = _live()
+        m.set_feature_cache(4)
+        assert _live() > one_plan  # (the entries and the single-view tensors)
+        call(m, 64, 96, big, range(1, 4))
+        call(m, 64, 96, big, range(2, 5))
+        st = m.feature_cache_stats()
+        assert st["single_view_plan"] and st["views_from_cache"] == 2, st
+        call(m, 96, 128, win5, range(5))
+        m.autotune(2)
+        assert len(m.profile()) > 40
+        m.close(force=True)
+        assert _live() == before
+
+
 # ------------------------------------------------------------------ e. the tracker
 import test_tracker_gpu as TT  # noqa: E402
 
@@ -436,6 +497,31 @@ def test_tracker_append_dense_reference_under_guards(H, W, step, parity_hooks):
             g.close()
         return outs
     on_and_off(run, "append %dx%d step %d" % (H, W, step))
+
+
+def test_a_tracker_life_cycle_returns_every_buffer(parity_hooks):
+    """init, one reference, the dense hand-off (its lazily allocated group), one calcRes / calcG under the timing events, close."""
+    from tandem_amd.dr_tracker import DrCoarseTracker
+    H, W = 96, 128
+    p = TT.pair(H, W, 5, 0.03)
+    K = np.array([[p["fx"], 0, p["cx"]], [0, p["fy"], p["cy"]], [0, 0, 1]], np.float32)
+    T = np.linalg.inv(p["c2w_ref"]) @ p["c2w_new"]
+    KRKi = (K @ T[:3, :3].astype(np.float32)) @ np.linalg.inv(K.astype(np.float64)).astype(np.float32)
+    with guarded():
+        before = _live()
+        g = DrCoarseTracker(W, H, 9.0, 20.0)
+        g.setK(W, H, p["fx"], p["fy"], p["cx"], p["cy"])
+        g.init(H * W)
+        g.setReference(p["pc_u"], p["pc_v"], p["pc_idepth"], p["pc_color"], 1.0, [0, 0])
+        assert g.appendDenseReference(p["depth_new"], KRKi, K @ T[:3, 3].astype(np.float32), 2, True, None, p["dI_ref"]) > len(p["pc_u"])
+        g.setNew(p["dI_new"])
+        g.startTiming()
+        out = g.calcRes(p["refToNew"], 1.0, [0, 0], 20.0)
+        g.calcG(1.0, [0, 0])
+        assert g.endTimingMilliseconds() > 0 and np.isfinite(out[0])
+        assert _live() > before
+        g.close()
+        assert _live() == before
 
 
 # ------------------------------------------------------------------ d. DrFusion
