@@ -1,5 +1,6 @@
 // fusion_host.h -- the host half of DrFusion's map: block keys, streaming reach bounds, the host block store, the reach balls,
-// the planner of the map-scope mesh pass, the rule and planner of a map merge, the rule and planner of a rigid resample.  The pose
+// the planner of the map-scope mesh pass, the rule and planner of a map merge, the rule and planner of a rigid resample, the ledger of
+// the incremental mesh (MeshUpdateLedger; tests/cpp/mesh_ledger_check.cpp).  The pose
 // solvers over all this -- registration, localisation, tracking -- are pose_host.h, included at the end.  No device state and no
 // HIP header: plain C++17, so that all of it runs in the CPU tests (tests/cpp/fusion_host_check.cpp, tests/cpp/map_merge_check.cpp,
 // tests/cpp/map_transform_check.cpp).  The engine (dr_fusion.hip) keeps everything that throws or touches the GPU.
@@ -749,6 +750,50 @@ struct HostMapSource {
     auto it = at.find(k);
     if (it != at.end()) memcpy(v, vox + it->second * 4096 + (size_t)(((x & 7) << 6) | ((y & 7) << 3) | (z & 7)) * 8, 8);
   }
+};
+
+// ---- the bookkeeping of the incremental mesh (drf_extract_mesh_update_async .. drf_get_mesh_update_sync; DESIGN.md §7c
+// "Incremental mesh"): when an update must mesh every block of its box again, and which scans it folds in.  The baseline is the
+// last update FETCHED: its box and the round-trip redirect count at its launch.  The pending update is decided by begin(), before
+// anything is launched, and becomes the baseline at fetched().  The recorded poses are those of the scans since the last update
+// was LAUNCHED: they belong to the next one.  mesh_ops.h MeshExtractor holds one and keeps the device scratch itself.
+struct MuPose { float m[12]; };  // rows 0..2 of a scan's Ti (world -> camera); row 3 is 0 0 0 1
+class MeshUpdateLedger {
+ public:
+  struct Update {
+    bool valid = false, full = false;
+    float box[6] = {0, 0, 0, 0, 0, 0};
+    unsigned long long redirects = 0; size_t nblk = 0;  // nblk: rows of its patch table
+  };
+  // A scan was integrated at Ti16 (world -> camera).  A pose that is not a finite rigid motion (the reach bound assumes one) or one
+  // scan too many makes the next update full.
+  void record_scan(const float *Ti16) {
+    if (!pose_is_rigid(Ti16) || poses_.size() == (size_t)DRF_MESH_UPDATE_MAX_SCANS) { overflow_ = true; return; }
+    MuPose p;
+    memcpy(p.m, Ti16, 48);
+    poses_.push_back(p);
+  }
+  void begin(const float *lower, const float *upper, unsigned long long redirects) {
+    Update next;
+    next.valid = true;
+    next.redirects = redirects;
+    memcpy(next.box, lower, 12); memcpy(next.box + 3, upper, 12);
+    next.full = !base_.valid || force_full_ || overflow_ || memcmp(next.box, base_.box, 24) != 0 || next.redirects != base_.redirects;
+    next_ = next;
+  }
+  void set_rows(size_t nblk) { next_.nblk = nblk; }  // of the pending update's patch table, once the launch knows them
+  // the pending update is enqueued: the scans recorded so far belong to it, later ones to the next
+  void launched() { force_full_ = false; overflow_ = false; poses_.clear(); }
+  void fetched() { base_ = next_; }  // the baseline advances: this box, the voxel state at the launch
+  void force_full() { force_full_ = true; }  // the map changed by something no scan pose describes (load, merge, the caller's reset)
+  const Update &pending() const { return next_; }
+  const Update &baseline() const { return base_; }
+  const std::vector<MuPose> &poses() const { return poses_; }
+
+ private:
+  Update base_, next_;
+  std::vector<MuPose> poses_;
+  bool force_full_ = false, overflow_ = false;
 };
 
 }  // namespace dr

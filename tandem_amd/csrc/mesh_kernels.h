@@ -1,4 +1,4 @@
-// Marching-cubes mesh extraction over the hashed TSDF volume (included by dr_fusion.hip after the voxel/hash helpers).
+// Marching-cubes mesh extraction over the hashed TSDF volume (included by dr_fusion.hip after volume_kernels.h and the pose kernels; launched by mesh_ops.h).
 //
 // Reference behaviour being reproduced: ExtractMeshKernel / ExtractMeshAtPosition / TrilinearInterpolation /
 // VertexInterpolation, marching_cubes/mesh_extractor.cu:24-265, and the GetMeshSync output layout,

@@ -1,6 +1,6 @@
 // Incremental mesh ("mesh update", DESIGN.md §7c "Incremental mesh"): which blocks of a sorted key list must be meshed
 // again after the scans recorded since the baseline, and the patch table that names the blocks of the result.  Included
-// by dr_fusion.hip after mesh_kernels.h.  No reference counterpart.
+// by dr_fusion.hip after mesh_kernels.h; launched by mesh_ops.h.  No reference counterpart.
 //
 // A block's voxels can differ from the baseline only if k_cull's test (cull_block_visible, the same device function)
 // holds for its coordinates under the pose of a recorded scan; the update bound (a written voxel has vd < sd + trunc,
@@ -11,9 +11,7 @@
 
 namespace dr {
 
-struct MuPose { float m[12]; };  // rows 0..2 of a scan's Ti (world -> camera); row 3 is 0 0 0 1
-
-struct MuArgs {
+struct MuArgs {  // (MuPose: fusion_host.h, with the ledger that records them)
   const unsigned long long *keys;  // [n] ascending packed keys of the scope
   int n;
   int nposes;                      // <= DRF_MESH_UPDATE_MAX_SCANS

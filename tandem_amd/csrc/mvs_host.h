@@ -355,7 +355,7 @@ class HostCopier {
 // Every DR_* switch of the engine, read ONCE when the engine is created (nothing on the launch path calls getenv).  The product library reads
 // six of them (profiling, printing, tuning knobs: listed in INTEGRATION.md); every switch that selects a superseded kernel generation, the losing side of a
 // settled A/B or a forced fallback is read through hook_env(), i.e. only in the parity build (-DDR_PARITY_HOOKS, libdr_mi355x_hooks.so: what the tests
-// that compare generations load) -- in the product those members are constants.
+// that compare generations load) -- in the product hook_env() returns null, so those members keep their defaults whatever the environment says.
 struct MvsSwitches {
   static int num(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
   static bool on(const char *name) { return getenv(name) != nullptr; }

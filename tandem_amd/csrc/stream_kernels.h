@@ -1,5 +1,6 @@
 // stream_kernels.h -- moving voxel blocks between the device pool and the host store (DESIGN.md "Streaming voxel blocks").
-// Included by dr_fusion.hip inside namespace dr, after FusionDev and the block-index helpers.
+// Included by dr_fusion.hip inside namespace dr, after volume_kernels.h (FusionDev, the block-index helpers) and raycast_kernels.h.
+// The host side of streaming is stream_ops.h (BlockStreamer): it alone launches the k_ev_* chain.
 //
 // Eviction is one chain on the integration stream, launched after the scan's k_fold_counter:
 //   k_ev_select    one lane per pool block: blocks whose centre lies beyond the radius (or whose origin lies in a box) go to
