@@ -581,7 +581,7 @@ int drf_align_stats(drf_t *h, uint64_t out[6]);
  * pixel's point (depth-to-SDF, Gauss-Newton with Huber weights); it REFINES, as drf_align_map does: pose_init must bring the
  * points inside the truncation band.  No damping, no coarse-to-fine, no global search (from a pose that is only good to decimetres
  * and degrees call drf_track_frame, below, first: its basin is set by a projective association, not by the band, and it ends
- * inside this call's).  drf_locate_system evaluates the system
+ * inside this call's; with no pose at all but a place, drf_search_frame, further below, finds the start).  drf_locate_system evaluates the system
  * once at pose16: the score of a pose hypothesis (sums[27] / counts[1], counts[1] / counts[0]).
  * The map is read where it lives, through the dense grid and the far-block table: nothing is uploaded but the depth image (through
  * the engine's pinned input buffer; the _device forms take a device pointer as drf_integrate_device does -- a rendered depth from
@@ -860,6 +860,108 @@ int drf_track_pyramid_stats(drf_t *h, uint64_t out[8]);
 /* level 0 .. 4 of the last drf_track_pyramid_frame: [0] its status, [1] renders, [2] evaluations, [3] valid samples at its last
  * evaluation; all 0 for a level that did not run ([2] = 0 says so).  After drf_track_pyramid_system: the one evaluation at its level. */
 int drf_track_pyramid_level_stats(drf_t *h, int level, uint64_t out[4]);
+/* Finds a depth frame in the map from a lattice of poses (no reference counterpart; DESIGN.md §7c "Searching a pose lattice").  Every
+ * call above refines and says so: a start further off needs a guess from elsewhere.  These calls make that guess when a session has
+ * only a place-recognition hit, a stale key-frame pose or a lost tracker: drf_score_poses evaluates the localisation's cost, without
+ * its Jacobian, at n poses of one depth image in one kernel (one wave per pose) instead of n drf_locate_system calls, and
+ * drf_search_frame scores a lattice of poses around anchors, tracks the best few (drf_track_frame's rule), locates them
+ * (drf_locate_frame's rule) and picks one.  It is a geometric score: it has no appearance term and is ambiguous where geometry
+ * repeats (two alike corridors score alike) -- the runner-up entries of the result show it.
+ * SCOPE.  The score reads the resident map only: with streaming on, blocks in the host store read as absent (their samples are
+ * UNOBSERVED) and drf_search_stats()[7] tells how many there are; DRF_LOCATE_MAP does not apply to the score.  The refinement
+ * stages keep their own scopes (drf_set_render_scope for the tracking's renders, drf_set_locate_scope for the localisation).  The
+ * map, the public render buffers and the streaming state are untouched; drf_track_stats, drf_locate_stats and
+ * drf_locate_stage_stats afterwards describe the last refinement stage that ran.
+ * The rule (one text, pose_host.h, compiled for the host and for the kernels; double and fp32 without contraction; + - * / floor):
+ *   sample    drf_locate_*'s, to the letter: the grid of stride step, the sample test, the point g, q = Rd g + tv, b = floor(q),
+ *             f = (float)(q - b), the eight voxels, UNOBSERVED (a corner of weight < min_weight, or q outside (-2^30, 2^30)), the
+ *             trilinear fp32 phi, OUTSIDE (|phi| < band is false), r = (double)phi / vs, Huber's w = 1 if |r| <= huber else
+ *             huber / |r|.  A valid sample adds (w r) r to one double; no gradient, no J and no centre exist.
+ *   cost      the sum of (w r) r in drf_locate_system's order: groups of 512 grid positions, lane l of 64 on positions
+ *             512 i + l + 64 k, k = 0..7, from +0.0; x = x + x[lane ^ off], off = 32 .. 1, gives partial[i]; lane i % 64 adds
+ *             partial[i] in ascending i from +0.0 and the same butterfly folds the lanes.  For equal step, min_weight, band and
+ *             huber, cost is bit for bit sums[27] of drf_locate_system at that float pose, and counts = {samples, valid,
+ *             unobserved, outside} are its counts.
+ *   score     ((cost + oc * (double)outside) + uc * (double)unobserved) / (double)samples, in double in that order; samples = 0
+ *             gives uc.  LOWER IS BETTER.  oc = outside_cost, 0 -> (double)huber * ((double)band / vs), Huber's value at the band's
+ *             edge; uc = unobserved_cost, 0 -> 2 oc.
+ *   candidate (drf_search_frame) index c = (((a * n_rot + r) * Nx + ix) * Ny + iy) * Nz + iz, N = 2 half + 1.  The pose is formed on
+ *             the host in double; no trigonometry runs anywhere in the library: rotations9 are n_rot row-major 3x3 matrices in
+ *             double that the caller supplies.  (Ra, ta) = anchor a as every pose is read (ta = t / vs);
+ *             Rd[i][j] = (Rr[i][0] Ra[0][j] + Rr[i][1] Ra[1][j]) + Rr[i][2] Ra[2][j], a turn about the WORLD axes through the camera
+ *             centre; tv_k = ta_k + (double)(i_k - half_k) * ((double)trans_step / vs), offsets along the world axes.  The
+ *             candidate's float pose is Rd and tv * vs rounded to float (what drf_locate_frame hands out).
+ *   selection the top_k smallest scores, ties to the lower index (a NaN score ranks behind every number).
+ *   refinement  each selected candidate in rank order: drf_track_frame's rule from its float pose with the track options; if that
+ *             ends <= DRF_ALIGN_MAX_ITERS, drf_locate_frame's rule from the tracked pose16 with the locate options.  An entry
+ *             QUALIFIES if its locate status is <= DRF_ALIGN_MAX_ITERS.  The winner has the greatest located valid among the
+ *             qualifying, ties to the lower located cost, then to the better rank.  accept_valid > 0 ends the refinement at the
+ *             first qualifying entry with valid >= accept_valid * samples, and that entry wins.  res->status is the winner's
+ *             locate status and pose16_out its T rounded to float.  None qualifies: res->status = DRF_ALIGN_LOST, winner = -1,
+ *             pose16_out is the best-scoring candidate's float pose, the return is DR_OK and dr_last_error() holds a message.
+ *             score_only = 1: no refinement, winner = 0, status DRF_ALIGN_MAX_ITERS, pose16_out the best candidate's.
+ *   steps     rule of thumb: trans_step about 2 * truncation_distance (the default), rotations about truncation_distance / scene
+ *             depth apart (4 degrees at 8 cm and 1.2 m .. 2.3 m); DESIGN.md has the measurements behind it.
+ * Candidates are scored in chunks: device scratch is the points (25 bytes per grid position), the pose table (96 bytes per anchor x
+ * rotation, or per pose of a chunk) and 32 bytes per candidate of a chunk, whatever n is.
+ * Legality and refusals, in drf_locate_frame's order: a null argument (the option structs, res, all_scores, and for drf_score_poses any
+ * of the three outputs but not all, may be null); an option that is negative or not finite, a negative half, top_k >
+ * DRF_SEARCH_MAX_TOP: DR_ERR_ARG naming it (the score and search options first, then the track, then the locate options); n = 0
+ * or more than 2^24 candidates, DR_ERR_ARG; not where drf_integrate_scan_async is legal, DR_ERR_PROTOCOL; a pose, an anchor, a
+ * rotation (taken as a pose without translation) or a product Rr Ra that drf_transform_map would refuse, DR_ERR_ARG naming its
+ * index.  drf_search_stats is all zero after a refusal. */
+#define DRF_SEARCH_MAX_TOP 32
+typedef struct {
+  int   step;             /* pixel stride of the sample grid; 0 -> 4 */
+  int   min_weight;       /* 0 -> 1 */
+  float band;             /* metres; 0 -> truncation_distance */
+  float huber;            /* voxels; 0 -> 1.0 */
+  float outside_cost;     /* voxels per OUTSIDE sample; 0 -> huber * band / voxel_size */
+  float unobserved_cost;  /* voxels per UNOBSERVED sample; 0 -> 2 * outside_cost */
+} drf_score_options_t;
+/* n poses16 (n x 16 floats) scored against the resident map: cost[n], counts[n][4] = {samples, valid, unobserved, outside},
+ * score[n]; each output may be null */
+int drf_score_poses(drf_t *h, const float *depth, const float *poses16, size_t n, const drf_score_options_t *opt, double *cost, uint32_t *counts,
+                    double *score);
+int drf_score_poses_device(drf_t *h, const void *d_depth, const float *poses16, size_t n, const drf_score_options_t *opt, double *cost, uint32_t *counts,
+                           double *score);
+typedef struct {
+  drf_score_options_t score;
+  float  trans_step;    /* metres between neighbouring offsets; 0 -> 2 * truncation_distance */
+  int    half[3];       /* offsets -half .. half along world x, y, z; 0 0 0: the anchors are turned, not moved */
+  int    top_k;         /* candidates refined; 0 -> 8, at most DRF_SEARCH_MAX_TOP */
+  int    score_only;    /* 1: no refinement */
+  double accept_valid;  /* 0: refine all top_k; > 0: stop at the first entry whose located valid share reaches it */
+} drf_search_options_t;
+typedef struct {
+  uint64_t index;                       /* the candidate */
+  double   score, cost;                 /* of the score stage */
+  uint32_t counts[4];
+  int      track_status, locate_status; /* DRF_ALIGN_*; -1: the stage did not run */
+  uint64_t samples, valid;              /* of the localisation's last evaluation (0 if it did not run) */
+  double   located_cost;                /* its cost = sums[27] / valid */
+  double   T[16];                       /* camera-to-world: the located pose, else the tracked pose, else the candidate's float pose */
+} drf_search_entry_t;
+typedef struct {
+  int      status;                      /* DRF_ALIGN_*: the winner's locate status; DRF_ALIGN_LOST if no entry qualifies */
+  int      n_entries;                   /* min(top_k, candidates) */
+  int      winner;                      /* index into entries, -1: none */
+  int      refined;                     /* entries whose refinement ran */
+  uint64_t n_candidates;
+  drf_search_entry_t entries[DRF_SEARCH_MAX_TOP];  /* in rank order: ascending score */
+} drf_search_result_t;
+/* the search around n_anchors poses (n_anchors x 16 floats) turned by n_rot rotations (n_rot x 9 doubles); all_scores, if given,
+ * receives the score of every candidate in index order */
+int drf_search_frame(drf_t *h, const float *depth, const float *anchors16, size_t n_anchors, const double *rotations9, size_t n_rot,
+                     const drf_search_options_t *opt, const drf_track_options_t *track_opt, const drf_locate_options_t *locate_opt, float pose16_out[16],
+                     drf_search_result_t *res, double *all_scores);
+int drf_search_frame_device(drf_t *h, const void *d_depth, const float *anchors16, size_t n_anchors, const double *rotations9, size_t n_rot,
+                            const drf_search_options_t *opt, const drf_track_options_t *track_opt, const drf_locate_options_t *locate_opt, float pose16_out[16],
+                            drf_search_result_t *res, double *all_scores);
+/* last drf_score_poses / drf_search_frame: [0] candidates, [1] grid positions, [2] samples, [3] chunks, [4] renders and [5] system
+ * evaluations of the refinement, [6] device bytes held by the score stage, [7] blocks in the host store at the call (all 0 after a
+ * call that was refused) */
+int drf_search_stats(drf_t *h, uint64_t out[8]);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

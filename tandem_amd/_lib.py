@@ -171,6 +171,11 @@ SIGNATURES = {
     "drf_track_pyramid_frame_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
     "drf_track_pyramid_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "drf_track_pyramid_level_stats": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint64)]),
+    "drf_score_poses": (C.c_int, [vp, f32p, f32p, C.c_size_t, C.c_void_p, f64p, C.POINTER(C.c_uint32), f64p]),
+    "drf_score_poses_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_size_t, C.c_void_p, f64p, C.POINTER(C.c_uint32), f64p]),
+    "drf_search_frame": (C.c_int, [vp, f32p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f64p]),
+    "drf_search_frame_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f64p]),
+    "drf_search_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
 }
 
 
@@ -200,6 +205,33 @@ class TrackColourOptions(C.Structure):
 class TrackPyramidOptions(C.Structure):
     """drf_track_pyramid_options_t: a zero field means its default."""
     _fields_ = [("colour", TrackColourOptions), ("levels", C.c_int), ("coarse_renders", C.c_int)]
+
+
+SEARCH_MAX_TOP = 32  # DRF_SEARCH_MAX_TOP
+
+
+class ScoreOptions(C.Structure):
+    """drf_score_options_t: a zero field means its default."""
+    _fields_ = [("step", C.c_int), ("min_weight", C.c_int), ("band", C.c_float), ("huber", C.c_float), ("outside_cost", C.c_float),
+                ("unobserved_cost", C.c_float)]
+
+
+class SearchOptions(C.Structure):
+    """drf_search_options_t: a zero field means its default."""
+    _fields_ = [("score", ScoreOptions), ("trans_step", C.c_float), ("half", C.c_int * 3), ("top_k", C.c_int), ("score_only", C.c_int),
+                ("accept_valid", C.c_double)]
+
+
+class SearchEntryStruct(C.Structure):
+    """drf_search_entry_t."""
+    _fields_ = [("index", C.c_uint64), ("score", C.c_double), ("cost", C.c_double), ("counts", C.c_uint32 * 4), ("track_status", C.c_int),
+                ("locate_status", C.c_int), ("samples", C.c_uint64), ("valid", C.c_uint64), ("located_cost", C.c_double), ("T", C.c_double * 16)]
+
+
+class SearchResultStruct(C.Structure):
+    """drf_search_result_t."""
+    _fields_ = [("status", C.c_int), ("n_entries", C.c_int), ("winner", C.c_int), ("refined", C.c_int), ("n_candidates", C.c_uint64),
+                ("entries", SearchEntryStruct * SEARCH_MAX_TOP)]
 
 
 class AlignResultStruct(C.Structure):

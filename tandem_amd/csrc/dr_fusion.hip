@@ -2,7 +2,8 @@
 //
 // The engine (FusionEngine: call order, scans, renders, the map file, locate and track) and the C ABI.  The volume's device code and the
 // table of reference counterparts: volume_kernels.h.  What the engine lends its components: fusion_core.h (FusionCore); streaming:
-// stream_ops.h (BlockStreamer); meshing and the incremental mesh: mesh_ops.h (MeshExtractor).  DESIGN.md "Where streaming and meshing live".
+// stream_ops.h (BlockStreamer); meshing and the incremental mesh: mesh_ops.h (MeshExtractor); the score stage of the pose search: search_ops.h
+// (PoseScorer).  DESIGN.md "Where streaming and meshing live".
 #include <cfloat>
 #include <climits>
 #include <cstdio>
@@ -32,6 +33,7 @@ namespace dr {
 #include "track_kernels.h"   // k_track_model, k_track (drf_track_system, drf_track_frame)
 #include "track_colour_kernels.h"  // k_track_model_colour, k_track_colour (drf_track_colour_system, drf_track_colour_frame)
 #include "track_pyramid_kernels.h"  // k_track_reduce (drf_track_reduce, drf_track_pyramid_system, drf_track_pyramid_frame)
+#include "search_kernels.h"  // k_search_points, k_search_score (drf_score_poses, drf_search_frame)
 
 }  // namespace dr
 #include "mesh_kernels.h"
@@ -40,6 +42,7 @@ namespace dr {
 #include "fusion_core.h"  // FusionCore: what the engine lends its components
 #include "stream_ops.h"   // BlockStreamer
 #include "mesh_ops.h"     // MeshExtractor
+#include "search_ops.h"   // PoseScorer
 namespace dr {
 
 // cofactor inverse on the host in the reference's term order (matrix_utils.h:958-1083), fp32, no contraction
@@ -90,7 +93,7 @@ class FusionEngine {
   };
 
  public:
-  FusionEngine(const drf_options_t &o, int device) : core_(o, device), streamer_(core_), mesher_(core_, streamer_), mio_(core_.own, device, o.voxel_size, (size_t)std::min(o.num_blocks, kStageBlocks)) {
+  FusionEngine(const drf_options_t &o, int device) : core_(o, device), streamer_(core_), mesher_(core_, streamer_), scorer_(core_), mio_(core_.own, device, o.voxel_size, (size_t)std::min(o.num_blocks, kStageBlocks)) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= device) fail(DR_ERR_DEVICE, "DrFusion: no HIP device %d (found %d) -- the MI355X path has no CPU fallback", device, n);
     if (o.block_size != 8) fail(DR_ERR_UNSUPPORTED, "DrFusion: block_size must be 8 (got %d)", o.block_size);
@@ -1205,6 +1208,99 @@ class FusionEngine {
     return tp_.level[level];
   }
 
+  // A depth frame found in the map from many poses (the rule: pose_host.h score_point / search_candidate / search_refine; DESIGN.md
+  // §7c "Searching a pose lattice").  The score stage is scorer_'s (search_ops.h: k_search_points once, k_search_score in chunks, the
+  // resident map through find_block); what the engine adds is its call order -- frame_prologue -- the frame's
+  // intake, and the refinement: track_levels and with_locate + locate_loop as drf_track_frame and drf_locate_frame run them, on the
+  // device image the score read.  Nothing of the map, the public render buffers or the streaming state is written.
+  template <class Body>
+  void with_score(const char *who, const char *bad_option, int step, size_t table_entries, const float *h_depth, const void *d_depth, Body &&body) {
+    static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    frame_prologue(who, bad_option, identity, nullptr);  // the call's poses are many: body refuses them, each by its index
+    float *mine = scorer_.prepare(step, table_entries);
+    const float *depth = (const float *)d_depth;
+    if (h_depth) {
+      upload_frame(nullptr, h_depth, nullptr, mine);
+      depth = mine;
+    }
+    scorer_.stats[7] = streamer_.store().size();
+    try {
+      scorer_.points(depth);
+      body(depth);
+    } catch (...) {
+      scorer_.reset();
+      throw;
+    }
+  }
+  void score_poses(const char *who, const float *h_depth, const void *d_depth, const float *poses16, size_t n, const drf_score_options_t *opt, double *cost,
+                   uint32_t *counts, double *score) {
+    scorer_.reset();
+    if (!(h_depth || d_depth) || !poses16 || !(cost || counts || score)) fail(DR_ERR_ARG, "%s: null argument", who);
+    ScoreOpt so{};
+    const char *bad = score_options(opt, core_.o.truncation_distance, core_.o.voxel_size, so);
+    if (!bad && (n == 0 || n > kSearchMaxCandidates)) fail(DR_ERR_ARG, "%s: %zu poses (at least 1, at most 2^24)", who, n);
+    with_score(who, bad, so.step, std::min(n, scorer_.chunk_size()), h_depth, d_depth, [&](const float *) {
+      std::vector<double> table(n * 12);
+      for (size_t i = 0; i < n; ++i) {
+        if (const char *why = transform_pose_fault(poses16 + 16 * i)) fail(DR_ERR_ARG, "%s: pose %zu %s", who, i, why);
+        const MapMotion m = map_motion(poses16 + 16 * i, core_.o.voxel_size);
+        memcpy(&table[12 * i], m.R, 72);
+        memcpy(&table[12 * i + 9], m.tv, 24);
+      }
+      const SearchLattice plain = {{1, 1, 1}, {0, 0, 0}, 0.0, 1};
+      scorer_.score(plain, table.data(), n, n, so, cost, counts, score);
+    });
+  }
+  // returns what dr_last_error() says after a search that ran but found no pose (empty otherwise)
+  std::string search_frame(const char *who, const float *h_depth, const void *d_depth, const float *anchors16, size_t n_anchors, const double *rotations9, size_t n_rot,
+                           const drf_search_options_t *opt, const drf_track_options_t *topt, const drf_locate_options_t *lopt, float *pose16_out,
+                           drf_search_result_t *res, double *all_scores) {
+    scorer_.reset();
+    if (!(h_depth || d_depth) || !anchors16 || !rotations9 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+    SearchOpt so{};
+    TrackPyramidOpt po{{}, 1, 0};
+    LocateOpt lo;
+    const char *bad = search_options(opt, core_.o.truncation_distance, core_.o.voxel_size, so);
+    if (!bad) bad = track_options_of(topt, core_.o.voxel_size, po.c);
+    if (!bad) bad = locate_options(lopt, core_.o.truncation_distance, lo);
+    const size_t n = bad ? 1 : search_count(n_anchors, n_rot, so.L);
+    if (n == 0) fail(DR_ERR_ARG, "%s: %zu anchors x %zu rotations x %d x %d x %d offsets is no count of candidates (at least 1, at most 2^24)", who, n_anchors, n_rot,
+                     so.L.N[0], so.L.N[1], so.L.N[2]);
+    drf_search_result_t r;
+    with_score(who, bad, so.s.step, n_anchors * n_rot, h_depth, d_depth, [&](const float *depth) {
+      std::vector<double> table;
+      const std::string why = search_table(anchors16, n_anchors, rotations9, n_rot, core_.o.voxel_size, table);
+      if (!why.empty()) fail(DR_ERR_ARG, "%s: %s", who, why.c_str());
+      std::vector<double> cost(n), score(n);
+      std::vector<uint32_t> counts(4 * n);
+      scorer_.score(so.L, table.data(), n_anchors * n_rot, n, so.s, cost.data(), counts.data(), score.data());
+      if (all_scores) memcpy(all_scores, score.data(), n * 8);
+      const FramePair frame = FramePair::device(nullptr, depth);
+      search_refine(so, table.data(), search_select(score.data(), n, so.top_k), cost.data(), counts.data(), score.data(), n, core_.o.voxel_size,
+                    [&](const float *p16, drf_align_result_t &tr) {
+                      tk_.reset();
+                      uint64_t last[5] = {0, 0, 0, 0, 0};
+                      track_levels(who, tk_, false, po, frame, p16, tr, last);
+                      scorer_.stats[4] += tk_.stats[4]; scorer_.stats[5] += tk_.stats[3];
+                    },
+                    [&](const float *p16, drf_align_result_t &lr) {
+                      with_locate(who, nullptr, depth, p16, lopt, [&](const LocateOpt &l, auto &eval) { locate_loop(eval, map_motion(p16, core_.o.voxel_size), l, core_.o.voxel_size, lr); });
+                      scorer_.stats[5] += lc_stats_[3];
+                    },
+                    pose16_out, r);
+    });
+    if (res) *res = r;
+    if (r.status != DRF_ALIGN_LOST) return std::string();
+    return std::string(who) + ": no candidate of the best " + std::to_string(r.n_entries) + " of " + std::to_string((unsigned long long)n) +
+           " ended its tracking and its localisation with a pose (the best score is " + std::to_string(r.entries[0].score) + " voxels per sample with " +
+           std::to_string(r.entries[0].counts[1]) + " of " + std::to_string(r.entries[0].counts[0]) + " samples valid; " + std::to_string(streamer_.store().size()) +
+           " blocks are in the host store); pose16_out is the best-scoring candidate";
+  }
+  void search_stats(uint64_t out[8]) const {
+    if (!out) fail(DR_ERR_ARG, "drf_search_stats: null argument");
+    for (int i = 0; i < 8; ++i) out[i] = scorer_.stats[i];
+  }
+
  private:
   enum Next { kIntegrate, kRender, kGetRender };
   // the resident order: (blk_key, slot) pairs sorted by key, as mesh_tables sorts the keys -- the keys to res, keys and slots
@@ -1353,6 +1449,7 @@ class FusionEngine {
   FusionCore core_;          // first: its HipOwner is released after every other member
   BlockStreamer streamer_;   // the host store, evictions, stream-in (stream_ops.h)
   MeshExtractor mesher_;     // extraction, the map pass, the incremental mesh (mesh_ops.h)
+  PoseScorer scorer_;        // the score stage of drf_score_poses / drf_search_frame and their statistics (search_ops.h)
   hipEvent_t kernel_events_[3] = {nullptr, nullptr, nullptr};
   unsigned char *d_bgr_in_ = nullptr, *h_bgr_in_ = nullptr;
   float *d_depth_in_ = nullptr, *h_depth_in_ = nullptr;
@@ -1697,6 +1794,28 @@ int drf_track_pyramid_level_stats(drf_t *h, int level, uint64_t out[4]) {
     for (int i = 0; i < 4; ++i) out[i] = s[i];
   });
 }
+int drf_score_poses(drf_t *h, const float *depth, const float *poses16, size_t n, const drf_score_options_t *opt, double *cost, uint32_t *counts, double *score) {
+  return guarded([&] { eng(h)->score_poses("drf_score_poses", depth, nullptr, poses16, n, opt, cost, counts, score); });
+}
+int drf_score_poses_device(drf_t *h, const void *d_depth, const float *poses16, size_t n, const drf_score_options_t *opt, double *cost, uint32_t *counts,
+                           double *score) {
+  return guarded([&] { eng(h)->score_poses("drf_score_poses_device", nullptr, d_depth, poses16, n, opt, cost, counts, score); });
+}
+int drf_search_frame(drf_t *h, const float *depth, const float *anchors16, size_t n_anchors, const double *rotations9, size_t n_rot, const drf_search_options_t *opt,
+                     const drf_track_options_t *track_opt, const drf_locate_options_t *locate_opt, float pose16_out[16], drf_search_result_t *res, double *all_scores) {
+  return guarded_note([&] {
+    return eng(h)->search_frame("drf_search_frame", depth, nullptr, anchors16, n_anchors, rotations9, n_rot, opt, track_opt, locate_opt, pose16_out, res, all_scores);
+  });
+}
+int drf_search_frame_device(drf_t *h, const void *d_depth, const float *anchors16, size_t n_anchors, const double *rotations9, size_t n_rot,
+                            const drf_search_options_t *opt, const drf_track_options_t *track_opt, const drf_locate_options_t *locate_opt, float pose16_out[16],
+                            drf_search_result_t *res, double *all_scores) {
+  return guarded_note([&] {
+    return eng(h)->search_frame("drf_search_frame_device", nullptr, d_depth, anchors16, n_anchors, rotations9, n_rot, opt, track_opt, locate_opt, pose16_out, res,
+                                all_scores);
+  });
+}
+int drf_search_stats(drf_t *h, uint64_t out[8]) { return guarded([&] { eng(h)->search_stats(out); }); }
 int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_locate_scope(scope, stage_capacity_blocks); }); }
 int drf_locate_stage_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->locate_stage_stats(out); }); }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->set_render_scope(scope, stage_capacity_blocks); }); }

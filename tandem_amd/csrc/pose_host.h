@@ -1,10 +1,13 @@
 // pose_host.h -- the pose solvers of DrFusion: the rule, step and host driver of a map-to-map registration (align), of a depth
-// frame's localisation in the map (locate) and of its tracking against the ray-cast model, without and with colour (track).  One
+// frame's localisation in the map (locate), of its tracking against the ray-cast model, without and with colour (track), and of the
+// search that finds their start on a lattice of poses (search: the locate rule's cost without its Jacobian, at the file's end).  One
 // Gauss-Newton system (align_accumulate), one step (align_step), one loop (align_loop), one walk over a frame's sample grid
 // (frame_group) for all of them.  The DR_HOST_DEVICE functions are the text the kernels compile.  Plain C++17 over fusion_host.h,
 // which includes this file at its end: whoever includes either has both (tests/cpp/map_align_check.cpp, map_locate_check.cpp,
-// map_track_check.cpp, map_track_colour_check.cpp run it on the CPU).
+// map_track_check.cpp, map_track_colour_check.cpp, map_search_check.cpp run it on the CPU).
 #pragma once
+#include <string>
+
 #include "fusion_host.h"
 
 namespace dr {
@@ -917,6 +920,300 @@ inline void track_pyramid_frame_host(const LocateGrid &lg0, const unsigned char 
     if (colour) track_colour_frame_host<5>(lg, fbgr, fdepth, render_level, p16, lo, voxel_size, r, last, st2, trace);
     else track_colour_frame_host<4>(lg, nullptr, fdepth, render_level, p16, lo, voxel_size, r, last, st2, trace);
   }, lg0, pose_init16, o, res, stats8, level4, last5);
+}
+
+// ---- searching a pose lattice (drf_score_poses / drf_search_frame; DESIGN.md §7c "Searching a pose lattice").  Every call above
+// refines; the guess they start from is found here: one evaluation of the localisation WITHOUT its Jacobian at each of 10^4..10^6
+// poses of one depth image, the best few handed to track_loop and locate_loop as they stand.  The per-sample rule is align_point<true>'s
+// with s_src = 0, word for word up to phi -- grid, sample test, point, q, corners, trilinear fp32 phi, the three codes, r, Huber's w --
+// and keeps acc[27] alone.  Stated once, here; the header of the C ABI restates it.  Compiled by g++ and by hipcc (k_search_points,
+// k_search_score), both without contraction; + - * / and floor only.  No trigonometry: rotations are data.
+struct ScoreOpt {  // drf_score_options_t with its defaults resolved
+  int step, min_weight;
+  float band, huber;
+  double oc, uc;  // voxels per OUTSIDE / UNOBSERVED sample
+};
+// null: all defaults.  Returns null, or which option is negative or not finite
+inline const char *score_options(const drf_score_options_t *opt, float truncation_distance, float voxel_size, ScoreOpt &o) {
+  static const drf_score_options_t zero = {0, 0, 0.0f, 0.0f, 0.0f, 0.0f};
+  const drf_score_options_t &u = opt ? *opt : zero;
+  if (u.step < 0) return "step";
+  if (u.min_weight < 0) return "min_weight";
+  if (!(u.band >= 0.0f) || !std::isfinite(u.band)) return "band";
+  if (!(u.huber >= 0.0f) || !std::isfinite(u.huber)) return "huber";
+  if (!(u.outside_cost >= 0.0f) || !std::isfinite(u.outside_cost)) return "outside_cost";
+  if (!(u.unobserved_cost >= 0.0f) || !std::isfinite(u.unobserved_cost)) return "unobserved_cost";
+  o.step = u.step ? u.step : 4;
+  o.min_weight = u.min_weight ? u.min_weight : 1;
+  o.band = u.band != 0.0f ? u.band : truncation_distance;
+  o.huber = u.huber != 0.0f ? u.huber : 1.0f;
+  o.oc = u.outside_cost != 0.0f ? (double)u.outside_cost : (double)o.huber * ((double)o.band / (double)voxel_size);  // Huber's value at the band's edge
+  o.uc = u.unobserved_cost != 0.0f ? (double)u.unobserved_cost : 2.0 * o.oc;
+  return nullptr;
+}
+// what score_point reads of an AlignEval: the pose, huber, vs, band, min_weight (there is no centre: nothing turns)
+DR_HOST_DEVICE inline AlignEval score_eval(const MapMotion &m, const ScoreOpt &o, double vs) {
+  AlignEval e;
+  e.m = m;
+  e.c[0] = 0.0; e.c[1] = 0.0; e.c[2] = 0.0;
+  e.huber = (double)o.huber; e.vs = vs;
+  e.band = o.band; e.min_weight = o.min_weight;
+  return e;
+}
+// One sample at the camera-frame point g: align_point<true> with s_src = 0 up to phi, its codes (0 UNOBSERVED, 2 OUTSIDE, 1 valid),
+// and of its sums the last: cost = cost + (w r) r.
+template <class Fetch>
+DR_HOST_DEVICE inline int score_point(const AlignEval &e, double g0, double g1, double g2, Fetch &&fetch, double &cost) {
+  int b[3];
+  float f[3];
+  DR_UNROLL
+  for (int k = 0; k < 3; ++k) {
+    const double q = ((e.m.R[3 * k] * g0 + e.m.R[3 * k + 1] * g1) + e.m.R[3 * k + 2] * g2) + e.m.tv[k];
+    if (!(q > -1073741824.0 && q < 1073741824.0)) return 0;
+    const double fl = floor(q);
+    b[k] = (int)fl;
+    f[k] = (float)(q - fl);
+  }
+  float s[8];  // index 4 cx + 2 cy + cz
+  DR_UNROLL
+  for (int c = 0; c < 8; ++c) {
+    uint32_t v[2];
+    fetch(b[0] + (c >> 2), b[1] + ((c >> 1) & 1), b[2] + (c & 1), v);
+    if ((int)(v[1] >> 24) < e.min_weight) return 0;
+    memcpy(&s[c], &v[0], 4);
+  }
+  float ez[4];  // index 2 cx + cy
+  DR_UNROLL
+  for (int c = 0; c < 4; ++c) ez[c] = s[2 * c] + f[2] * (s[2 * c + 1] - s[2 * c]);
+  float d[2];
+  DR_UNROLL
+  for (int c = 0; c < 2; ++c) d[c] = ez[2 * c] + f[1] * (ez[2 * c + 1] - ez[2 * c]);
+  const float phi = d[0] + f[0] * (d[1] - d[0]);
+  const float ap = phi < 0.0f ? -phi : phi;
+  if (!(ap < e.band)) return 2;
+  const double r = (double)phi / e.vs;  // align_point's ((double)phi - (double)s_src) / vs with s_src = 0: the same bits
+  const double a = r < 0.0 ? -r : r;
+  const double w = a <= e.huber ? 1.0 : e.huber / a;
+  cost = cost + (w * r) * r;
+  return 1;
+}
+// score = ((cost + oc outside) + uc unobserved) / samples in double, in that order; no sample: uc.  Lower is better.
+DR_HOST_DEVICE inline double score_value(double cost, uint32_t samples, uint32_t unobserved, uint32_t outside, double oc, double uc) {
+  if (samples == 0) return uc;
+  return ((cost + oc * (double)outside) + uc * (double)unobserved) / (double)samples;
+}
+// The candidates of a call.  plain (drf_score_poses): candidate c is entry c of the pose table, as it stands.  Otherwise
+// (drf_search_frame) c = (((a n_rot + r) Nx + ix) Ny + iy) Nz + iz, N = 2 half + 1: entry a n_rot + r of the table holds (Rd, ta) --
+// 12 doubles, Rd row-major, then ta in lattice units -- and tv_k = ta_k + (double)(i_k - half_k) * dstep, dstep =
+// (double)trans_step / vs.  The kernel decodes the index with this very function.
+struct SearchLattice {
+  int N[3], half[3];
+  double dstep;
+  int plain;
+};
+inline size_t search_cells(const SearchLattice &L) { return (size_t)L.N[0] * (size_t)L.N[1] * (size_t)L.N[2]; }
+DR_HOST_DEVICE inline MapMotion search_candidate(const SearchLattice &L, const double *table, size_t table_first, size_t c) {
+  MapMotion m;
+  size_t ar = c;
+  int off[3] = {0, 0, 0};
+  if (!L.plain) {
+    const size_t iz = c % (size_t)L.N[2], cy = c / (size_t)L.N[2];
+    const size_t iy = cy % (size_t)L.N[1], cx = cy / (size_t)L.N[1];
+    const size_t ix = cx % (size_t)L.N[0];
+    ar = cx / (size_t)L.N[0];
+    off[0] = (int)ix - L.half[0]; off[1] = (int)iy - L.half[1]; off[2] = (int)iz - L.half[2];
+  }
+  const double *t = table + 12 * (ar - table_first);
+  DR_UNROLL
+  for (int i = 0; i < 9; ++i) m.R[i] = t[i];
+  DR_UNROLL
+  for (int k = 0; k < 3; ++k) m.tv[k] = L.plain ? t[9 + k] : t[9 + k] + (double)off[k] * L.dstep;
+  return m;
+}
+// The pose table of a search: per (anchor a, rotation r) Rd = Rr Ra, each entry (Rr[i][0] Ra[0][j] + Rr[i][1] Ra[1][j]) +
+// Rr[i][2] Ra[2][j] -- a turn about the world axes through the camera centre -- and ta, the anchor's translation in lattice units,
+// (Ra, ta) read from the anchor as every pose is read (map_motion).  Returns an empty string, or what is refused: an anchor, a
+// rotation (as a pose with no translation) or a product (as locate_pose16 makes it a pose16) that transform_pose_fault refuses.
+inline std::string search_table(const float *anchors16, size_t n_anchors, const double *rotations9, size_t n_rot, float voxel_size, std::vector<double> &table) {
+  table.assign(n_anchors * n_rot * 12, 0.0);
+  for (size_t a = 0; a < n_anchors; ++a)
+    if (const char *why = transform_pose_fault(anchors16 + 16 * a)) return "anchor " + std::to_string(a) + " " + why;
+  for (size_t r = 0; r < n_rot; ++r) {
+    float T[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) T[4 * i + j] = (float)rotations9[9 * r + 3 * i + j];
+    if (const char *why = transform_pose_fault(T)) return "rotation " + std::to_string(r) + " " + why;
+  }
+  for (size_t a = 0; a < n_anchors; ++a) {
+    const MapMotion ma = map_motion(anchors16 + 16 * a, voxel_size);
+    for (size_t r = 0; r < n_rot; ++r) {
+      const double *Rr = rotations9 + 9 * r;
+      MapMotion m = ma;
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) m.R[3 * i + j] = (Rr[3 * i] * ma.R[j] + Rr[3 * i + 1] * ma.R[3 + j]) + Rr[3 * i + 2] * ma.R[6 + j];
+      float T[16];
+      locate_pose16(m, voxel_size, T);
+      if (const char *why = transform_pose_fault(T)) return "rotation " + std::to_string(r) + " applied to anchor " + std::to_string(a) + " " + why;
+      double *t = &table[(a * n_rot + r) * 12];
+      memcpy(t, m.R, 72);
+      memcpy(t + 9, m.tv, 24);
+    }
+  }
+  return std::string();
+}
+struct SearchOpt {  // drf_search_options_t with its defaults resolved
+  ScoreOpt s;
+  SearchLattice L;
+  int top_k;
+  bool score_only;
+  double accept_valid;
+};
+constexpr size_t kSearchMaxCandidates = (size_t)1 << 24;
+// null: all defaults (half = 0 0 0: the anchors turned, not moved).  Returns null, or which option is refused
+inline const char *search_options(const drf_search_options_t *opt, float truncation_distance, float voxel_size, SearchOpt &o) {
+  static const drf_search_options_t zero = {{0, 0, 0.0f, 0.0f, 0.0f, 0.0f}, 0.0f, {0, 0, 0}, 0, 0, 0.0};
+  const drf_search_options_t &u = opt ? *opt : zero;
+  if (const char *bad = score_options(&u.score, truncation_distance, voxel_size, o.s)) return bad;
+  if (!(u.trans_step >= 0.0f) || !std::isfinite(u.trans_step)) return "trans_step";
+  for (int k = 0; k < 3; ++k)
+    if (u.half[k] < 0 || u.half[k] > (1 << 20)) return "half";
+  if (u.top_k < 0 || u.top_k > DRF_SEARCH_MAX_TOP) return "top_k";
+  if (u.score_only < 0 || u.score_only > 1) return "score_only";
+  if (!(u.accept_valid >= 0.0) || !std::isfinite(u.accept_valid)) return "accept_valid";
+  const float ts = u.trans_step != 0.0f ? u.trans_step : 2.0f * truncation_distance;
+  for (int k = 0; k < 3; ++k) { o.L.half[k] = u.half[k]; o.L.N[k] = 2 * u.half[k] + 1; }
+  o.L.dstep = (double)ts / (double)voxel_size;
+  o.L.plain = 0;
+  o.top_k = u.top_k ? u.top_k : 8;
+  o.score_only = u.score_only != 0;
+  o.accept_valid = u.accept_valid;
+  return nullptr;
+}
+// n_anchors * n_rot * Nx * Ny * Nz, or 0 if that is no count a call takes: zero, or above 2^24
+inline size_t search_count(size_t n_anchors, size_t n_rot, const SearchLattice &L) {
+  size_t n = 1;
+  for (size_t f : {n_anchors, n_rot, (size_t)L.N[0], (size_t)L.N[1], (size_t)L.N[2]}) {
+    if (f == 0 || f > kSearchMaxCandidates) return 0;
+    n *= f;
+    if (n > kSearchMaxCandidates) return 0;
+  }
+  return n;
+}
+// k_search_points on the host: per grid position of the groups (512 each, the last padded) its point g, locate_pixel's bits, and
+// whether it is a sample
+struct SearchPoints {
+  std::vector<double> g;  // 3 per position
+  std::vector<unsigned char> flag;
+};
+inline void search_points_host(const LocateGrid &lg, double vs, const float *depth, SearchPoints &p) {
+  const long total = locate_positions(lg), padded = 512 * locate_groups(lg);
+  p.g.assign((size_t)padded * 3, 0.0);
+  p.flag.assign((size_t)padded, 0);
+  for (long n = 0; n < total; ++n) p.flag[n] = locate_pixel(lg, vs, (int)n, depth, &p.g[3 * n]) ? 1 : 0;
+}
+// k_search_score's wave on the host: the groups in order, lane l on positions 512 i + l + 64 k, one double per lane, the
+// butterfly, partial i added in ascending i by lane i % 64 from +0.0, the butterfly again.  counts = {samples, valid,
+// unobserved, outside}.  Bit for bit sums[27] and the counts of locate_system_host at the same pose and options.
+template <class Fetch>
+inline void score_candidate_host(long groups, const SearchPoints &p, Fetch &&fetch, const AlignEval &e, double &cost, uint32_t counts[4]) {
+  auto butterfly = [](double x[64]) {
+    for (int off = 32; off > 0; off >>= 1) {
+      double y[64];
+      for (int l = 0; l < 64; ++l) y[l] = x[l] + x[l ^ off];
+      memcpy(x, y, sizeof y);
+    }
+  };
+  double fold[64];
+  for (int l = 0; l < 64; ++l) fold[l] = 0.0;
+  counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  for (long i = 0; i < groups; ++i) {
+    double x[64];
+    for (int l = 0; l < 64; ++l) {
+      x[l] = 0.0;
+      for (int k = 0; k < 8; ++k) {
+        const size_t n = (size_t)(512 * i + l + 64 * k);
+        if (!p.flag[n]) continue;
+        ++counts[0];
+        const int r = score_point(e, p.g[3 * n], p.g[3 * n + 1], p.g[3 * n + 2], fetch, x[l]);
+        ++counts[r == 1 ? 1 : r == 0 ? 2 : 3];
+      }
+    }
+    butterfly(x);
+    fold[i & 63] = fold[i & 63] + x[0];
+  }
+  butterfly(fold);
+  cost = fold[0];
+}
+// drf_score_poses / the score stage of drf_search_frame on the CPU: candidates [0, n) of the lattice over the table
+template <class Fetch>
+inline void score_candidates_host(const LocateGrid &lg, const float *depth, Fetch &&fetch, const SearchLattice &L, const double *table, size_t n, const ScoreOpt &o,
+                                  float voxel_size, double *cost, uint32_t *counts, double *score) {
+  SearchPoints p;
+  search_points_host(lg, (double)voxel_size, depth, p);
+  for (size_t c = 0; c < n; ++c) {
+    const AlignEval e = score_eval(search_candidate(L, table, 0, c), o, (double)voxel_size);
+    score_candidate_host(locate_groups(lg), p, fetch, e, cost[c], counts + 4 * c);
+    score[c] = score_value(cost[c], counts[4 * c], counts[4 * c + 2], counts[4 * c + 3], o.oc, o.uc);
+  }
+}
+// The top_k smallest scores, ties to the lower index, a NaN score behind every number: the indices in rank order
+inline std::vector<size_t> search_select(const double *score, size_t n, int top_k) {
+  std::vector<size_t> idx(n);
+  for (size_t i = 0; i < n; ++i) idx[i] = i;
+  const size_t k = std::min(n, (size_t)top_k);
+  auto key = [&](size_t i) { return score[i] == score[i] ? score[i] : HUGE_VAL; };
+  std::partial_sort(idx.begin(), idx.begin() + k, idx.end(), [&](size_t a, size_t b) { return key(a) < key(b) || (key(a) == key(b) && a < b); });
+  idx.resize(k);
+  return idx;
+}
+// What follows the score stage, over track(p16, res) and locate(p16, res), the *_frame calls' loops from a float pose: the entries
+// of the selected candidates, then each refined in rank order -- tracked from its float pose (locate_pose16 of its (Rd, tv)); if
+// that ends <= MAX_ITERS, located from the tracked pose rounded to float.  An entry QUALIFIES if its locate status is <= MAX_ITERS.
+// accept_valid > 0 ends the refinement at the first qualifying entry whose located valid >= accept_valid * samples: it wins.
+// Otherwise the winner has the greatest located valid among the qualifying, ties to the lower located cost, then the better rank.
+// None qualifies (or score_only): pose16_out is the best-scoring candidate's float pose, status LOST (score_only: MAX_ITERS, winner 0).
+template <class Track, class Locate>
+inline void search_refine(const SearchOpt &o, const double *table, const std::vector<size_t> &sel, const double *cost, const uint32_t *counts,
+                          const double *score, size_t n_candidates, float voxel_size, Track &&track, Locate &&locate, float pose16_out[16], drf_search_result_t &res) {
+  memset(&res, 0, sizeof res);
+  res.n_candidates = n_candidates;
+  res.n_entries = (int)sel.size();
+  res.winner = -1;
+  float p16[DRF_SEARCH_MAX_TOP][16];
+  for (size_t k = 0; k < sel.size(); ++k) {
+    drf_search_entry_t &en = res.entries[k];
+    const size_t c = sel[k];
+    en.index = c; en.score = score[c]; en.cost = cost[c];
+    for (int i = 0; i < 4; ++i) en.counts[i] = counts[4 * c + i];
+    en.track_status = en.locate_status = -1;
+    locate_pose16(search_candidate(o.L, table, 0, c), voxel_size, p16[k]);
+    for (int i = 0; i < 16; ++i) en.T[i] = (double)p16[k][i];
+  }
+  memcpy(pose16_out, p16[0], sizeof p16[0]);
+  if (o.score_only) { res.status = DRF_ALIGN_MAX_ITERS; res.winner = 0; return; }
+  res.status = DRF_ALIGN_LOST;
+  for (size_t k = 0; k < sel.size(); ++k) {
+    drf_search_entry_t &en = res.entries[k];
+    drf_align_result_t r;
+    track(p16[k], r);
+    ++res.refined;
+    en.track_status = r.status;
+    memcpy(en.T, r.T, sizeof en.T);
+    if (r.status > DRF_ALIGN_MAX_ITERS) continue;
+    float t16[16];
+    for (int i = 0; i < 16; ++i) t16[i] = (float)r.T[i];
+    locate(t16, r);
+    en.locate_status = r.status;
+    en.samples = r.samples; en.valid = r.valid; en.located_cost = r.cost;
+    memcpy(en.T, r.T, sizeof en.T);
+    if (r.status > DRF_ALIGN_MAX_ITERS) continue;
+    const drf_search_entry_t *w = res.winner >= 0 ? &res.entries[res.winner] : nullptr;
+    if (!w || en.valid > w->valid || (en.valid == w->valid && en.located_cost < w->located_cost)) res.winner = (int)k;
+    if (o.accept_valid > 0.0 && (double)en.valid >= o.accept_valid * (double)en.samples) { res.winner = (int)k; break; }
+  }
+  if (res.winner < 0) return;
+  res.status = res.entries[res.winner].locate_status;
+  for (int i = 0; i < 16; ++i) pose16_out[i] = (float)res.entries[res.winner].T[i];
 }
 
 }  // namespace dr

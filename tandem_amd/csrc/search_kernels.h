@@ -1,0 +1,74 @@
+// search_kernels.h -- drf_score_poses / drf_search_frame on the device: the localisation's cost, without its Jacobian, at many poses
+// of one depth image (the rule: pose_host.h score_point / search_candidate; DESIGN.md §7c "Searching a pose lattice").  Included by
+// dr_fusion.hip inside namespace dr, behind locate_kernels.h, whose LocateFetch reads the live map (the block kept across corners
+// and samples, far blocks through find_block).
+
+// Once per call: grid position n < padded = 512 groups -> its camera-frame point g (three doubles, locate_pixel's bits) and whether
+// it is a sample, in grid order.  No candidate then repeats the double divisions or reads the depth image.  Positions >= total (the
+// last group's tail) are no samples.
+__global__ __launch_bounds__(256) void k_search_points(const float *__restrict__ depth, const LocateGrid lg, double vs, int total, int padded,
+                                                       double *__restrict__ g, unsigned char *__restrict__ flag) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= padded) return;
+  double p[3] = {0.0, 0.0, 0.0};
+  const bool s = n < total && locate_pixel(lg, vs, n, depth, p);
+  g[3 * (size_t)n] = s ? p[0] : 0.0; g[3 * (size_t)n + 1] = s ? p[1] : 0.0; g[3 * (size_t)n + 2] = s ? p[2] : 0.0;
+  flag[n] = s ? 1 : 0;
+}
+
+struct SearchOut {  // 32 bytes per candidate of a chunk
+  double cost;
+  unsigned counts[4];  // samples, valid, unobserved, outside
+  double score;
+};
+
+// One wave per candidate first + local, local in [0, n) (no grid stride; the four waves of a workgroup share nothing).  The pose is
+// search_candidate's, from the table: wave-uniform, read once.  The wave walks the groups in order, lane l on positions
+// 512 i + l + 64 k, k = 0..7, one double per lane from +0.0 and three integer counters; the butterfly x = x + shfl_xor(x, off),
+// off = 32..1, leaves the group's partial in every lane, and lane i % 64 adds it to its fold accumulator: partial i in ascending i,
+// k_align_fold's order.  A group no lane of which added a term has partial +0.0, which changes no accumulator: its butterfly is
+// skipped (wave-uniform).  The last butterfly folds the lanes and the counters; lane 0 writes the candidate's 32 bytes.  No atomics,
+// no second launch.  The map is only read.
+__global__ __launch_bounds__(256) void k_search_score(const FusionDev d, const double *__restrict__ g, const unsigned char *__restrict__ flag, int groups,
+                                                      const double *__restrict__ table, const SearchLattice lat, size_t first, size_t table_first, int n,
+                                                      const ScoreOpt so, double vs, SearchOut *__restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int local = blockIdx.x * 4 + wave;
+  if (local >= n) return;
+  const AlignEval e = score_eval(search_candidate(lat, table, table_first, first + (size_t)local), so, vs);
+  double fold = 0.0;
+  unsigned ns = 0, nv = 0, nu = 0;
+  LocateFetch fetch(d);
+#pragma unroll 1
+  for (int i = 0; i < groups; ++i) {
+    double x = 0.0;
+    bool added = false;
+#pragma unroll 1
+    for (int k = 0; k < 8; ++k) {
+      const size_t p = (size_t)(512 * i + lane + 64 * k);
+      if (!flag[p]) continue;
+      ++ns;
+      fetch.corner = 0;
+      const int r = score_point(e, g[3 * p], g[3 * p + 1], g[3 * p + 2], fetch, x);
+      nv += r == 1 ? 1u : 0u;
+      nu += r == 0 ? 1u : 0u;
+      added = added || r == 1;
+    }
+    if (!__any(added)) continue;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x = x + __shfl_xor(x, off);
+    if (lane == (i & 63)) fold = fold + x;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    fold = fold + __shfl_xor(fold, off);
+    ns += __shfl_xor(ns, off); nv += __shfl_xor(nv, off); nu += __shfl_xor(nu, off);
+  }
+  if (lane == 0) {
+    SearchOut o;
+    o.cost = fold;
+    o.counts[0] = ns; o.counts[1] = nv; o.counts[2] = nu; o.counts[3] = ns - nv - nu;
+    o.score = score_value(fold, ns, nu, ns - nv - nu, so.oc, so.uc);
+    out[local] = o;
+  }
+}

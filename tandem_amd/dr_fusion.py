@@ -48,6 +48,36 @@ class AlignError(RuntimeError):
         self.result = result
 
 
+class SearchEntry(collections.namedtuple("SearchEntry", "index score cost counts track_status locate_status samples valid located_cost T")):
+    """drf_search_entry_t: the candidate's index, its score, cost and counts (samples, valid, unobserved, outside) of the score
+    stage, the statuses of its tracking and localisation (ALIGN_*, -1: did not run), the localisation's samples / valid / cost, and
+    T (4, 4) float64 camera-to-world: the located pose, else the tracked one, else the candidate's own."""
+    __slots__ = ()
+
+
+class SearchResult(collections.namedtuple("SearchResult", "T32 status winner refined n_candidates entries scores")):
+    """drf_search_result_t: T32 (4, 4) float32 the pose found (the winner's; the best-scoring candidate's if there is none), status
+    (ALIGN_*), winner (index into entries, -1: none), refined, n_candidates, entries (SearchEntry, ascending score) and scores (every
+    candidate's, in index order; None unless asked for)."""
+    __slots__ = ()
+
+
+def pose_rotations(yaw_deg=(0.0,), pitch_deg=(0.0,), roll_deg=(0.0,)):
+    """The rotations of a search lattice as search_frame takes them: an (n, 9) float64 array, one row-major matrix
+    Ry(yaw) Rx(pitch) Rz(roll) per combination, yaw outermost and roll innermost -- turns about the WORLD axes y, x and z.  The one
+    place that calls cos or sin: the library itself takes rotations as data."""
+    out = []
+    for y in np.atleast_1d(np.asarray(yaw_deg, np.float64)):
+        for p in np.atleast_1d(np.asarray(pitch_deg, np.float64)):
+            for r in np.atleast_1d(np.asarray(roll_deg, np.float64)):
+                cy, sy, cp, sp, cr, sr = (f(np.deg2rad(a)) for a in (y, p, r) for f in (np.cos, np.sin))
+                Ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+                Rx = np.array([[1.0, 0.0, 0.0], [0.0, cp, -sp], [0.0, sp, cp]])
+                Rz = np.array([[cr, -sr, 0.0], [sr, cr, 0.0], [0.0, 0.0, 1.0]])
+                out.append((Ry @ Rx @ Rz).reshape(9))
+    return np.ascontiguousarray(out, np.float64)
+
+
 def pack_block_key(coords):
     """The packed key that orders blocks in every extraction: x, then y, then z, each biased by 2^20 (21 bits each)."""
     c = np.asarray(coords, np.int64) + (1 << 20)
@@ -389,7 +419,7 @@ class DrFusion:
     def locate_frame(self, depth, pose_init, raise_on_failure=True, **opt):
         """Refines pose_init (camera-to-world) so that the depth image lies on the surface of the map this engine holds and returns
         an AlignResult (T, T32: camera-to-world); T32 is the pose IntegrateScanAsync takes to continue the map.  The call refines:
-        pose_init must bring the points inside the truncation band (from farther off, track_frame first).  Only resident blocks are read (locate_stats()[5] counts the
+        pose_init must bring the points inside the truncation band (from farther off, track_frame first; with only a place, search_frame).  Only resident blocks are read (locate_stats()[5] counts the
         blocks in the host store) unless set_locate_scope(LOCATE_MAP) was called.  A refinement that ends ALIGN_DEGENERATE or ALIGN_LOST raises AlignError (which carries the
         result) unless raise_on_failure is false."""
         dev, d, keep = self._image(np.float32, 1, depth)
@@ -471,6 +501,59 @@ class DrFusion:
         renders, device bytes held)."""
         out = (C.c_uint64 * 6)()
         check(self._L.drf_track_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    # ---- searching a pose lattice (include/dr_mi355x.h drf_search_frame, DESIGN.md "Searching a pose lattice") ----
+    def score_poses(self, depth, poses, **opt):
+        """The localisation's cost, without its Jacobian, of the depth image (H*W float32 metres, or an integer device pointer) at
+        each of the n poses ((n, 4, 4) or (n, 16) float32, camera-to-world) against the resident map, in one kernel: (cost (n,)
+        float64, counts (n, 4) uint32 = samples, valid, unobserved, outside, score (n,) float64; lower is better).  cost and
+        counts are locate_system's sums[27] and counts at that pose, bit for bit.  opt: the fields of drf_score_options_t."""
+        dev, d, keep = self._image(np.float32, 1, depth)
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+        n = len(poses)
+        o = self._options(_lib.ScoreOptions, "score", opt)
+        cost, counts, score = np.zeros(n, np.float64), np.zeros((n, 4), np.uint32), np.zeros(n, np.float64)
+        call = self._L.drf_score_poses_device if dev else self._L.drf_score_poses
+        check(call(self._h, d, fptr(poses), n, C.byref(o) if o else None, cost.ctypes.data_as(_lib.f64p), counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                   score.ctypes.data_as(_lib.f64p)))
+        return cost, counts, score
+
+    def search_frame(self, depth, anchors, rotations=None, half=(0, 0, 0), trans_step=0.0, top_k=0, score_only=False, accept_valid=0.0, score=None, track=None,
+                     locate=None, all_scores=False, raise_on_failure=True):
+        """Finds the depth image in the map from a lattice of poses: every anchor ((n, 4, 4) float32 camera-to-world) turned by
+        every rotation ((m, 9) float64, pose_rotations(); default: the identity) and moved by -half .. half offsets of trans_step
+        metres (0: 2 * truncation_distance) along the world axes is scored in one kernel, the top_k (0: 8) best are tracked
+        (track: drf_track_options_t fields) and located (locate: drf_locate_options_t fields), and the one with the most located
+        valid samples wins.  score: drf_score_options_t fields.  Returns a SearchResult; one that found no pose raises AlignError
+        (which carries it; T32 is then the best-scoring candidate) unless raise_on_failure is false."""
+        dev, d, keep = self._image(np.float32, 1, depth)
+        anchors = np.ascontiguousarray(anchors, np.float32).reshape(-1, 16)
+        rot = np.ascontiguousarray(np.eye(3).reshape(1, 9) if rotations is None else rotations, np.float64).reshape(-1, 9)
+        so = self._options(_lib.ScoreOptions, "score", score or {}) or _lib.ScoreOptions()
+        o = _lib.SearchOptions(score=so, trans_step=trans_step, half=(C.c_int * 3)(*[int(v) for v in half]), top_k=int(top_k), score_only=int(bool(score_only)),
+                               accept_valid=float(accept_valid))
+        to, lo = self._options(_lib.TrackOptions, "track", track or {}), self._options(_lib.LocateOptions, "locate", locate or {})
+        n = len(anchors) * len(rot) * int(np.prod([2 * int(v) + 1 for v in half]))
+        scores = np.zeros(max(n, 1), np.float64) if all_scores and 0 < n <= 1 << 24 else None
+        T32, r = np.zeros(16, np.float32), _lib.SearchResultStruct()
+        call = self._L.drf_search_frame_device if dev else self._L.drf_search_frame
+        check(call(self._h, d, fptr(anchors), len(anchors), rot.ctypes.data_as(_lib.f64p), len(rot), C.byref(o), C.byref(to) if to else None,
+                   C.byref(lo) if lo else None, fptr(T32), C.byref(r), scores.ctypes.data_as(_lib.f64p) if scores is not None else None))
+        entries = [SearchEntry(index=int(e.index), score=float(e.score), cost=float(e.cost), counts=tuple(int(v) for v in e.counts), track_status=int(e.track_status),
+                               locate_status=int(e.locate_status), samples=int(e.samples), valid=int(e.valid), located_cost=float(e.located_cost),
+                               T=np.array(e.T, np.float64).reshape(4, 4)) for e in r.entries[:r.n_entries]]
+        res = SearchResult(T32=T32.reshape(4, 4), status=int(r.status), winner=int(r.winner), refined=int(r.refined), n_candidates=int(r.n_candidates),
+                           entries=entries, scores=scores)
+        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
+            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
+        return res
+
+    def search_stats(self):
+        """Last score_poses / search_frame: (candidates, grid positions, samples, chunks, renders and system evaluations of the
+        refinement, device bytes held by the score stage, blocks in the host store at the call)."""
+        out = (C.c_uint64 * 8)()
+        check(self._L.drf_search_stats(self._h, out))
         return tuple(int(v) for v in out)
 
     # ---- tracking with colour (include/dr_mi355x.h drf_track_colour_frame, DESIGN.md "Tracking with colour") ----

@@ -149,6 +149,24 @@ public:
     check(drf_track_pyramid_frame(impl, bgr, depth, pose_init16, opt, pose16_out, &res));
     return res.status;
   }
+  // n poses16 (n x 16 floats, camera-to-world) scored against the resident map in one kernel (dr_mi355x.h drf_score_poses): score[n],
+  // lower is better; cost and counts (n x 4: samples, valid, unobserved, outside) may be null.  opt null = its defaults.
+  void ScorePoses(float const *depth, float const *poses16, size_t n, double *score, double *cost = nullptr, uint32_t *counts = nullptr,
+                  drf_score_options_t const *opt = nullptr) {
+    check(drf_score_poses(impl, depth, poses16, n, opt, cost, counts, score));
+  }
+  // a depth frame found in the map from a lattice of poses (dr_mi355x.h drf_search_frame): every anchor turned by every rotation
+  // (n_rot x 9 doubles, row-major, about the world axes) and moved by the offsets of opt is scored, the best few are tracked and
+  // located, one is picked.  The guess that TrackDepthFrame and LocateDepthFrame need when a session has only a place-recognition
+  // hit or a stale pose.  Returns the status, DRF_ALIGN_*; DRF_ALIGN_LOST: pose16_out is the best-scoring candidate, no more.
+  int SearchDepthFrame(float const *depth, float const *anchors16, size_t n_anchors, double const *rotations9, size_t n_rot, float *pose16_out,
+                       drf_search_options_t const *opt = nullptr, drf_search_result_t *result = nullptr, drf_track_options_t const *track_opt = nullptr,
+                       drf_locate_options_t const *locate_opt = nullptr) {
+    drf_search_result_t res;
+    check(drf_search_frame(impl, depth, anchors16, n_anchors, rotations9, n_rot, opt, track_opt, locate_opt, pose16_out, &res, nullptr));
+    if (result) *result = res;
+    return res.status;
+  }
   // DRF_LOCATE_MAP: LocateDepthFrame reads resident and host-stored blocks together, without moving one (capacity 0 = the default
   // staging); DRF_LOCATE_RESIDENT, the default: the pool only
   void SetLocateScope(int scope, size_t capacity = 0) { check(drf_set_locate_scope(impl, scope, capacity)); }
