@@ -1,7 +1,8 @@
 // fusion_host.h -- the host half of DrFusion's map: block keys, streaming reach bounds, the host block store, the reach balls,
 // the planner of the map-scope mesh pass, the rule and planner of a map merge, the rule and planner of a rigid resample, the ledger of
 // the incremental mesh (MeshUpdateLedger; tests/cpp/mesh_ledger_check.cpp).  The pose
-// solvers over all this -- registration, localisation, tracking -- are pose_host.h, included at the end.  No device state and no
+// solvers over all this -- registration, localisation, tracking -- are pose_host.h, and the engine's call order and restaging rule
+// engine_host.h (tests/cpp/engine_host_check.cpp), both included at the end.  No device state and no
 // HIP header: plain C++17, so that all of it runs in the CPU tests (tests/cpp/fusion_host_check.cpp, tests/cpp/map_merge_check.cpp,
 // tests/cpp/map_transform_check.cpp).  The engine (dr_fusion.hip) keeps everything that throws or touches the GPU.
 #pragma once
@@ -799,3 +800,4 @@ class MeshUpdateLedger {
 }  // namespace dr
 
 #include "pose_host.h"  // the pose solvers over all this: align, locate, track, colour
+#include "engine_host.h"  // the engine's call order and the locate scope's restaging rule, as values (CallOrder, LocateStageCursor)

@@ -1,6 +1,6 @@
 // locate_kernels.h -- drf_locate_system / drf_locate_frame on the device: one evaluation of the localisation's Gauss-Newton system
 // (the rule: pose_host.h locate_pixel / align_point; DESIGN.md §7c "Locating a depth frame in the map").  Included by
-// dr_fusion.hip inside namespace dr, behind align_kernels.h, whose k_align_fold folds the groups.  k_map_locate reads the pool;
+// dr_fusion.hip inside namespace dr, behind align_kernels.h, whose k_align_fold folds the groups; launched by pose_ops.h.  k_map_locate reads the pool;
 // k_map_locate_staged reads the pool and the stored blocks staged for the call (drf_set_locate_scope(DRF_LOCATE_MAP)), through
 // the RenderStage of raycast_kernels.h.
 

@@ -1,4 +1,4 @@
-// map_ops.h -- the map-file layer of the DrFusion engine (included by dr_fusion.hip after the kernel headers, before fusion_core.h and the two components).  One rule: what every
+// map_ops.h -- the map-file layer of the DrFusion engine (included by dr_fusion.hip after the kernel headers, before fusion_core.h and the components).  One rule: what every
 // map-file operation does the same way is written here once -- MapIo: the pinned chunk pair and the device index buffers, the reader
 // opening, the read pump, the write pump, the evaluator tail of align, locate and track; CallMemory: device memory of a single call;
 // Carver: the layout of a scratch buffer as typed spans in order (drf_locate_*, drf_track_*, drf_track_colour_*) -- and

@@ -1,4 +1,4 @@
-// The ray-cast of DrFusion (included by dr_fusion.hip after volume_kernels.h): k_raycast2 + k_raycast_fix (k_raycast: the
+// The ray-cast of DrFusion (included by dr_fusion.hip after volume_kernels.h; launched by render_ops.h): k_raycast2 + k_raycast_fix (k_raycast: the
 // literal form, parity build), resident and STAGED.  The STAGED form ray-casts the whole streamed map
 // (drf_set_render_scope(DRF_RENDER_MAP); DESIGN.md §7c "Rendering the whole map"):
 // The host selects the stored blocks a RenderAsync can read (fusion_host.h: select_render_blocks), packs their keys (ascending)

@@ -1,7 +1,7 @@
 // search_kernels.h -- drf_score_poses / drf_search_frame on the device: the localisation's cost, without its Jacobian, at many poses
 // of one depth image (the rule: pose_host.h score_point / search_candidate; DESIGN.md §7c "Searching a pose lattice").  Included by
 // dr_fusion.hip inside namespace dr, behind locate_kernels.h, whose LocateFetch reads the live map (the block kept across corners
-// and samples, far blocks through find_block).
+// and samples, far blocks through find_block).  Launched by search_ops.h.
 
 // Once per call: grid position n < padded = 512 groups -> its camera-frame point g (three doubles, locate_pixel's bits) and whether
 // it is a sample, in grid order.  No candidate then repeats the double divisions or reads the depth image.  Positions >= total (the

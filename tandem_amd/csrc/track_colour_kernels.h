@@ -1,7 +1,7 @@
 // track_colour_kernels.h -- drf_track_colour_system / drf_track_colour_frame on the device: the model map and the model intensity
 // map of one render, and one evaluation of the system with the photometric term (the rule: pose_host.h track_model_intensity /
 // track_photo_term / track_colour_point; DESIGN.md §7c "Tracking with colour").  Included by dr_fusion.hip inside namespace dr,
-// behind track_kernels.h; k_align_fold folds the groups.
+// behind track_kernels.h; launched by pose_ops.h; k_align_fold folds the groups.
 
 // One lane per pixel: k_track_model's element, and the pixel's intensity from its three colour bytes where that element is valid.
 __global__ __launch_bounds__(256) void k_track_model_colour(const float *__restrict__ Dm, const unsigned char *__restrict__ Cm, const LocateGrid lg, float max_jump,

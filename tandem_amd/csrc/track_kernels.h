@@ -1,6 +1,6 @@
 // track_kernels.h -- drf_track_system / drf_track_frame on the device: the model map of one render and one evaluation of the
 // tracking's Gauss-Newton system (the rule: pose_host.h track_normal / track_point; DESIGN.md §7c "Tracking a depth frame against
-// the ray-cast model").  Included by dr_fusion.hip inside namespace dr, behind locate_kernels.h; k_align_fold folds the groups.
+// the ray-cast model").  Included by dr_fusion.hip inside namespace dr, behind locate_kernels.h; launched by pose_ops.h; k_align_fold folds the groups.
 
 // One lane per pixel of the model depth image: the pixel's normal and depth as one 16-byte element, once per render, so that an
 // evaluation gathers one aligned element per sample instead of five depths.  A border pixel reads nothing but writes its zeros.

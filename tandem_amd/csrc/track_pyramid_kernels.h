@@ -1,7 +1,7 @@
 // track_pyramid_kernels.h -- drf_track_reduce / drf_track_pyramid_* on the device: the reduction of a (bgr, depth) pair to level L of
 // the image pyramid (the rule: pose_host.h track_reduce_host and its pieces; DESIGN.md §7c "Tracking coarse to fine").  The level's
 // model map and evaluation are launches of k_track_model(_colour) and k_track(_colour) with the level's LocateGrid.  Included by
-// dr_fusion.hip inside namespace dr, behind track_colour_kernels.h.
+// dr_fusion.hip inside namespace dr, behind track_colour_kernels.h; launched by pose_ops.h.
 
 // One lane per full-resolution pixel that a level pixel covers: thread t holds column i = t mod s of level pixel p = t / s
 // (s = 2^L <= 16 divides 64, so a block's row never leaves its wave), p = v W_L + u over the level image.  A wave therefore covers

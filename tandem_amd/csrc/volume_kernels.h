@@ -1,6 +1,6 @@
 // volume_kernels.h -- the TSDF volume on the device: the voxel, the block index (dense grid, presence bitmap, open-addressing
 // table, bump pool), the coordinate maps, allocation and integration, and the small kernels every engine path shares.  Included by
-// dr_fusion.hip first of the kernel headers; raycast_kernels.h, stream_kernels.h, the pose kernels and mesh_kernels.h build on it.
+// dr_fusion.hip first of the kernel headers (k_publish is launched by render_ops.h); raycast_kernels.h, stream_kernels.h, the pose kernels and mesh_kernels.h build on it.
 //
 // Replaces tandem/libdr/dr_fusion/src (CUDA, managed memory, try-lock hash inserts):
 //   HashTable / Heap        tsdfvh/hash_table.cu, heap.cu  -> dense direct-mapped block grid (512^3 cells, one load per
