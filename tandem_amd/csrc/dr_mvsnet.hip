@@ -2,18 +2,16 @@
 //
 // Replaces tandem/libdr/dr_mvsnet/src/dr_mvsnet.cpp (libtorch TorchScript interpreter + cuDNN)
 // with a fixed launch plan of hand-written gfx950 kernels (conv_mfma.h, mvs_kernels.h; launchers: mvs_launch.h; host logic: mvs_host.h; the plan: mvs_plan.h):
-//   CallAsync   dr_mvsnet.cpp:125-283  -> MvsEngine::stage_inputs + worker thread
-//   forward     dr_mvsnet.cpp:285-331  -> MvsEngine::forward (cva_mvsnet.py:98-184 as ~75 launches)
-//   GetResult   dr_mvsnet.cpp:95-107   -> drm_get_result
+//   CallAsync   dr_mvsnet.cpp:125-283  -> MvsEngine::stage_inputs (WindowStager, mvs_stage.h) + worker thread
+//   forward     dr_mvsnet.cpp:285-331  -> MvsEngine::forward (cva_mvsnet.py:98-184 as ~75 launches; what each op gets: ForwardCursor, mvs_engine_host.h)
+//   GetResult   dr_mvsnet.cpp:95-107   -> drm_get_result (ResultSlots, mvs_engine_host.h)
+// The key-frame feature cache is FeatureCacheDev (mvs_cache.h), the view shard and its RCCL binding ViewShard (mvs_shard.h).
 // The threading contract is the reference's: one worker thread, one mutex, two condition variables;
 // CallAsync blocks only while the previous input is still unprocessed.
-#include <atomic>
 #include <memory>
 
-#include <dlfcn.h>
-#include <rccl/rccl.h>  // types and prototypes only: the library is bound with dlopen when a communicator is asked for
-
-#include "mvs_plan.h"  // the kernels and their launchers, MvsPlan (what a window shape owns, which layers exist), HipOwner
+#include "mvs_stage.h"  // WindowStager; through it mvs_cache.h, mvs_engine_host.h and mvs_plan.h (the kernels and their launchers, MvsPlan, HipOwner)
+#include "mvs_shard.h"
 
 namespace dr {
 
@@ -27,50 +25,6 @@ std::string &last_error_slot() {
 template __global__ void k_conv_a<4, 1, 1>(const ConvArgs a);
 
 // ------------------------------------------------------------------ engine
-// RCCL, bound lazily (drm_comm_*): an engine that never view-shards does not need the library, and inside a PyTorch
-// process the same librccl.so.1 that torch.distributed loaded is picked up (one RCCL per process).
-struct Rccl {
-  void *lib = nullptr;
-  decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-  decltype(&ncclCommInitRank) CommInitRank = nullptr;
-  decltype(&ncclCommDestroy) CommDestroy = nullptr;
-  decltype(&ncclAllReduce) AllReduce = nullptr;
-  decltype(&ncclReduce) Reduce = nullptr;
-  decltype(&ncclBroadcast) Broadcast = nullptr;
-  decltype(&ncclGetErrorString) GetErrorString = nullptr;
-  decltype(&ncclCommCount) CommCount = nullptr;  // optional (reporting only)
-  static Rccl &get() {
-    static Rccl r;
-    static std::mutex m;
-    std::lock_guard<std::mutex> g(m);
-    if (!r.lib) {
-      // DR_RCCL_LIB: bind this library instead (tests/test_view_shard_gpu.py runs two ranks on one GPU against a
-      // shared-memory stand-in, tests/cpp/rccl_stub.cpp: RCCL itself refuses two ranks on one device)
-      if (const char *e = getenv("DR_RCCL_LIB")) r.lib = dlopen(e, RTLD_NOW | RTLD_GLOBAL);
-      else
-      for (const char *n : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-        if ((r.lib = dlopen(n, RTLD_NOW | RTLD_GLOBAL))) break;
-      if (!r.lib) fail(DR_ERR_UNSUPPORTED, "RCCL not found (librccl.so.1): %s", dlerror());
-      r.GetUniqueId = reinterpret_cast<decltype(r.GetUniqueId)>(dlsym(r.lib, "ncclGetUniqueId"));
-      r.CommInitRank = reinterpret_cast<decltype(r.CommInitRank)>(dlsym(r.lib, "ncclCommInitRank"));
-      r.CommDestroy = reinterpret_cast<decltype(r.CommDestroy)>(dlsym(r.lib, "ncclCommDestroy"));
-      r.AllReduce = reinterpret_cast<decltype(r.AllReduce)>(dlsym(r.lib, "ncclAllReduce"));
-      r.Reduce = reinterpret_cast<decltype(r.Reduce)>(dlsym(r.lib, "ncclReduce"));
-      r.Broadcast = reinterpret_cast<decltype(r.Broadcast)>(dlsym(r.lib, "ncclBroadcast"));
-      r.GetErrorString = reinterpret_cast<decltype(r.GetErrorString)>(dlsym(r.lib, "ncclGetErrorString"));
-      r.CommCount = reinterpret_cast<decltype(r.CommCount)>(dlsym(r.lib, "ncclCommCount"));
-      if (!r.GetUniqueId || !r.CommInitRank || !r.CommDestroy || !r.AllReduce || !r.Reduce || !r.Broadcast || !r.GetErrorString) {
-        r.lib = nullptr;
-        fail(DR_ERR_UNSUPPORTED, "RCCL: missing symbols in librccl");
-      }
-    }
-    return r;
-  }
-  void check(ncclResult_t e, const char *what) const {
-    if (e != ncclSuccess) fail(DR_ERR_DEVICE, "RCCL %s: %s", what, GetErrorString(e));
-  }
-};
-
 static const char *conv_kind_name(const ConvLaunch &c) { return conv_family_name(conv_family(c)); }
 
 class MvsEngine {
@@ -95,14 +49,14 @@ class MvsEngine {
   ~MvsEngine() {
     {
       std::unique_lock<std::mutex> lk(mu_);
-      done_cv_.wait(lk, [&] { return !unprocessed_; });
+      done_cv_.wait(lk, [&] { return !slots_.unprocessed(); });
       running_ = false;
       input_cv_.notify_all();
     }
     worker_.join();
     (void)hipSetDevice(device_);
     (void)hipStreamSynchronize(stream_);
-    if (comm_) { Rccl::get().CommDestroy(comm_); comm_ = nullptr; }
+    shard_.comm_destroy();
   }
 
   // --- reference-API surface -------------------------------------------------------------------
@@ -110,16 +64,16 @@ class MvsEngine {
                   float dmin, float dmax, float disc) {
     check_args(H, W, V, ref, bgrs, K9, c2ws);
     std::unique_lock<std::mutex> lk(mu_);  // held by the worker for the whole forward (dr_mvsnet.cpp:84-92)
-    done_cv_.wait(lk, [&] { return !unprocessed_; });
+    done_cv_.wait(lk, [&] { return !slots_.unprocessed(); });
     stage_inputs(H, W, V, ref, bgrs, K9, c2ws, dmin, dmax, disc, true);
-    unprocessed_ = true;
+    slots_.submit();
     input_cv_.notify_all();
   }
-  bool ready() { return !unprocessed_; }
+  bool ready() { return !slots_.unprocessed(); }
   void wait() {
     std::unique_lock<std::mutex> lk(mu_);
-    done_cv_.wait(lk, [&] { return !unprocessed_; });
-    rethrow_worker_error();
+    done_cv_.wait(lk, [&] { return !slots_.unprocessed(); });
+    slots_.rethrow();
   }
   void get_result(float *depth, float *conf, float *depth_dense, float *conf_dense) {
     std::unique_lock<std::mutex> lk(mu_);
@@ -145,20 +99,17 @@ class MvsEngine {
   void set_feature_cache(int capacity) {
     if (capacity < 0 || capacity > 64) fail(DR_ERR_ARG, "drm_set_feature_cache: capacity %d out of range (0 = off, up to 64 key frames)", capacity);
     std::unique_lock<std::mutex> lk(mu_);
-    done_cv_.wait(lk, [&] { return !unprocessed_; });
-    if (capacity == fcache_cap_) return;
-    fcache_cap_ = capacity;
+    done_cv_.wait(lk, [&] { return !slots_.unprocessed(); });
+    if (capacity == cache_.capacity()) return;
+    cache_.set_capacity(capacity);
     if (H_) {  // a configured engine is re-planned: the entries are sized for the window shape
       DR_HIP(hipSetDevice(device_));
-      const int H = H_, W = W_, V = V_;
-      H_ = W_ = V_ = 0;
-      configure(H, W, V);
-      has_output_ = false;
+      replan(H_, W_, V_);
     }
   }
   void feature_cache_stats(uint64_t out[6]) {
     std::unique_lock<std::mutex> lk(mu_);
-    out[0] = fc_.hits; out[1] = fc_.misses; out[2] = fc_.batch_windows; out[3] = fc_.collisions; out[4] = fn1_ok_ ? 1 : 0; out[5] = (uint64_t)fc_.size();
+    cache_.stats(out);
   }
 
   // --- device-resident hooks -------------------------------------------------------------------
@@ -166,7 +117,7 @@ class MvsEngine {
               float dmin, float dmax, float disc) {
     check_args(H, W, V, ref, bgrs, K9, c2ws);
     std::unique_lock<std::mutex> lk(mu_);
-    done_cv_.wait(lk, [&] { return !unprocessed_; });
+    done_cv_.wait(lk, [&] { return !slots_.unprocessed(); });
     stage_inputs(H, W, V, ref, bgrs, K9, c2ws, dmin, dmax, disc);
     DR_HIP(hipStreamSynchronize(stream_));
   }
@@ -174,7 +125,7 @@ class MvsEngine {
     std::unique_lock<std::mutex> lk(mu_);
     require_config();
     DR_HIP(hipSetDevice(device_));
-    InFlight windows(device_, false);  // (several engines driven through this hook at once count as windows in flight, like CallAsync's)
+    WindowTicket windows(device_);  // (several engines driven through this hook at once count as windows in flight, like CallAsync's)
     HipOwner timing;  // (two events: gone with the scope on every way out of it)
     const hipEvent_t e0 = timing.event(hipEventDefault), e1 = timing.event(hipEventDefault);
     DR_HIP(hipEventRecord(e0, stream_));
@@ -183,7 +134,7 @@ class MvsEngine {
     DR_HIP(hipStreamSynchronize(stream_));
     float t = 0;
     DR_HIP(hipEventElapsedTime(&t, e0, e1));
-    cache_mismatch_recovered();
+    cache_.mismatch_recovered([&] { forward(nullptr); });
     check_march();
     if (ms) *ms = t;
   }
@@ -194,7 +145,7 @@ class MvsEngine {
   void autotune(int k, float *before_ms, float *after_ms) {
     std::unique_lock<std::mutex> lk(mu_);
     require_config();
-    if (comm_ && shard_nsrc_) fail(DR_ERR_PROTOCOL, "autotune(): not on a view-sharded engine (tune the unsharded plan)");
+    if (shard_.collective()) fail(DR_ERR_PROTOCOL, "autotune(): not on a view-sharded engine (tune the unsharded plan)");
     DR_HIP(hipSetDevice(device_));
     HipOwner timing;
     const hipEvent_t e0 = timing.event(hipEventDefault), e1 = timing.event(hipEventDefault);
@@ -238,7 +189,7 @@ class MvsEngine {
     check_march();
     if (before_ms) *before_ms = (float)t_before;
     if (after_ms) *after_ms = (float)t_after;
-    if (fn1_ok_ && !plan_->match_fn1()) { fn1_ok_ = false; fc_.fast = false; }  // (the feature cache's single-view plan follows the batch plan's instances, or stands down)
+    cache_.follow_tuned_plan();
   }
 
   // ---- view sharding hooks (SURVEY 8e / BASELINE configs[2]; no reference counterpart) ----
@@ -246,43 +197,23 @@ class MvsEngine {
   // [regularise 3 .. edge filter].  Between phases the host sum-reduces "volume<p+1>" over the ranks.
   void set_view_shard(int nsrc_total) {
     std::unique_lock<std::mutex> lk(mu_);
-    if (nsrc_total < 0 || nsrc_total > kMaxSrc) fail(DR_ERR_ARG, "set_view_shard: %d source views unsupported (0..%d)", nsrc_total, kMaxSrc);
-    shard_nsrc_ = nsrc_total;
+    shard_.set_nsrc(nsrc_total);
   }
-  // The view-shard collective inside the engine: with a communicator set, every cost-volume launch of a sharded window
-  // is followed -- on the engine's stream, no host round trip -- by an in-place RCCL sum all-reduce of that volume over
-  // the ranks, so drm_forward / CallAsync run the whole sharded depth map as one stream of work; FeatureNet's stage-2/3
-  // heads on the side stream and the reduce of stage 1 overlap.  (The host-driven protocol of forward_phase stays as
-  // the test double: RCCL refuses two ranks on one device, gloo can emulate them.)
+  // the communicator of the view-shard collective inside the engine (ViewShard, mvs_shard.h)
   void comm_init(int rank, int world, const void *unique_id) {
     std::unique_lock<std::mutex> lk(mu_);
-    if (comm_) fail(DR_ERR_PROTOCOL, "comm_init: a communicator is already set");
-    if (!unique_id || rank < 0 || rank >= world) fail(DR_ERR_ARG, "comm_init: bad rank %d of %d", rank, world);
-    Rccl &r = Rccl::get();
-    DR_HIP(hipSetDevice(device_));
-    ncclUniqueId id;
-    memcpy(&id, unique_id, sizeof id);
-    r.check(r.CommInitRank(&comm_, world, id, rank), "ncclCommInitRank");
-    comm_rank_ = rank;
+    shard_.comm_init(device_, rank, world, unique_id);
   }
-  // ranks RCCL itself reports for the engine's communicator (ncclCommCount): what bench.py prints next to the sharded figure, so that a
-  // driver record shows how many GPUs the collective really spanned.  0: no communicator; -1: the bound library has no ncclCommCount.
   int comm_count() {
     std::unique_lock<std::mutex> lk(mu_);
-    if (!comm_) return 0;
-    Rccl &r = Rccl::get();
-    if (!r.CommCount) return -1;
-    int n = 0;
-    r.check(r.CommCount(comm_, &n), "ncclCommCount");
-    return n;
+    return shard_.comm_count();
   }
   void comm_destroy() {
     std::unique_lock<std::mutex> lk(mu_);
-    if (!comm_) return;
+    if (!shard_.has_comm()) return;
     (void)hipSetDevice(device_);
     (void)hipStreamSynchronize(stream_);
-    Rccl::get().CommDestroy(comm_);
-    comm_ = nullptr;
+    shard_.comm_destroy();
   }
   void forward_phase(int phase) {
     std::unique_lock<std::mutex> lk(mu_);
@@ -293,9 +224,10 @@ class MvsEngine {
     std::vector<size_t> cut{0};
     for (size_t i = 0; i < ops.size(); ++i) if (ops[i].kind == Op::COSTVOL) cut.push_back(i + 1);
     cut.push_back(ops.size());
-    phase_mode_ = true;  // the caller reduces between phases
-    try { forward(nullptr, cut[phase], cut[phase + 1]); } catch (...) { phase_mode_ = false; throw; }
-    phase_mode_ = false;
+    {
+      FlagScope phase_mode(shard_.phase_flag());  // the caller reduces between phases
+      forward(nullptr, cut[phase], cut[phase + 1]);
+    }
     DR_HIP(hipStreamSynchronize(stream_));
     check_march();
   }
@@ -344,7 +276,7 @@ class MvsEngine {
   void profile(std::string &names, std::vector<float> &ms) {
     std::unique_lock<std::mutex> lk(mu_);
     require_config();
-    if (comm_ && shard_nsrc_) fail(DR_ERR_PROTOCOL, "profile(): a view-sharded engine enqueues collectives -- every rank would have to profile in lockstep");
+    if (shard_.collective()) fail(DR_ERR_PROTOCOL, "profile(): a view-sharded engine enqueues collectives -- every rank would have to profile in lockstep");
     DR_HIP(hipSetDevice(device_));
     forward(nullptr);  // warm
     const std::vector<Op> &ops = plan_->ops;
@@ -379,7 +311,7 @@ class MvsEngine {
   // ---------------------------------------------------------------- plumbing
   void check_args(int H, int W, int V, int ref, const uint8_t *const *bgrs, const float *K9, const float *const *c2ws) {
     if (!bgrs || !K9 || !c2ws) fail(DR_ERR_ARG, "CallAsync: null pointer argument");
-    const int vmin = shard_nsrc_ ? 1 : 2;  // a view-shard rank may hold the reference view only
+    const int vmin = shard_.nsrc() ? 1 : 2;  // a view-shard rank may hold the reference view only
     if (V < vmin || V > kMaxSrc + 1) fail(DR_ERR_ARG, "CallAsync: view_num=%d unsupported (%d..%d)", V, vmin, kMaxSrc + 1);
     if (ref < 0 || ref >= V) fail(DR_ERR_ARG, "CallAsync: ref_index=%d out of range", ref);
     if (H <= 0 || W <= 0 || H % 32 || W % 32) fail(DR_ERR_ARG, "CallAsync: height/width must be positive multiples of 32 (got %dx%d)", H, W);
@@ -388,373 +320,124 @@ class MvsEngine {
         fail(DR_ERR_ARG, "ERROR: In Call Async passing the same data for index %d and %d", i, j);  // dr_mvsnet.cpp:153-160
   }
   void require_config() { if (!H_) fail(DR_ERR_PROTOCOL, "no window uploaded yet"); }
-  void rethrow_worker_error() {
-    if (!worker_error_.empty()) { std::string e = worker_error_; worker_error_.clear(); fail(DR_ERR_DEVICE, "%s", e.c_str()); }
-  }
   // GetResult's first half: waits for the window, rethrows what its worker threw and hands the pinned block of four maps out ONCE
   const float *take_result(std::unique_lock<std::mutex> &lk) {
-    done_cv_.wait(lk, [&] { return !unprocessed_; });
-    rethrow_worker_error();
-    if (!has_output_) fail(DR_ERR_PROTOCOL, "Output should be valid. Maybe you called GetResult more than once?");
-    has_output_ = false;
-    return plan_->h_out[out_cur_];
+    done_cv_.wait(lk, [&] { return !slots_.unprocessed(); });
+    return plan_->h_out[slots_.take()];
   }
-  // windows whose kernels are enqueued or running, per device, over all engines of the process (forward() forks onto its side stream only when it is alone)
-  static std::atomic<int> &windows_in_flight(int device) {
-    static std::atomic<int> n[16];
-    return n[device & 15];
-  }
-  struct InFlight {
-    int dev;
-    InFlight(int d, bool counted_already) : dev(d) { if (!counted_already) windows_in_flight(dev).fetch_add(1, std::memory_order_relaxed); }
-    ~InFlight() { windows_in_flight(dev).fetch_sub(1, std::memory_order_relaxed); }
-  };
   void loop() {  // dr_mvsnet.cpp:83-93
     std::unique_lock<std::mutex> lk(mu_);
     while (running_) {
-      if (unprocessed_) {
+      if (slots_.unprocessed()) {
         try {
+          const bool prelaunched = (bool)parked_;  // (CallAsync enqueued this window's forward itself: stage_inputs)
+          WindowTicket window = WindowTicket::take(parked_, device_);  // (counted from here, or from CallAsync's own launch, to the end of this block)
           DR_HIP(hipSetDevice(device_));
-          InFlight window(device_, prelaunched_);  // (counted from here, or from CallAsync's own launch, to the end of this block)
-          if (prelaunched_) prelaunched_ = false;  // (CallAsync enqueued this window's forward itself: stage_inputs)
-          else forward(nullptr);
-          const int blk = out_cur_ ^ 1;  // the block the previous result does NOT live in (drm_get_result_view: that one may still be read)
+          if (!prelaunched) forward(nullptr);
+          const int blk = slots_.next_block();
           publish(blk);
-          if (cache_mismatch_recovered()) publish(blk);  // a cache hit that was a key collision: the window ran again without the cache; publish THAT result
+          if (cache_.mismatch_recovered([&] { forward(nullptr); })) publish(blk);  // a cache hit that was a key collision: the window ran again without the cache; publish THAT result
           check_march();
-          out_cur_ = blk;
-          has_output_ = true;
-        } catch (const std::exception &e) { worker_error_ = e.what(); }
-        unprocessed_ = false;
+          slots_.done(blk);
+        } catch (const std::exception &e) { slots_.failed(e.what()); }
         done_cv_.notify_all();
       }
-      input_cv_.wait(lk, [&] { return unprocessed_ || !running_; });
+      input_cv_.wait(lk, [&] { return slots_.unprocessed() || !running_; });
     }
   }
 
   // the four result maps into pinned block `blk`, and the wait for them
   void publish(int blk) {
     const size_t n = (size_t)H_ * W_ * 4;
-    float *ho = plan_->h_out[blk];
-    if (sw_.d2h_copy) {  // DR_MVS_D2H=copy: the four copy-engine transfers of round 2 (A/B hook)
-      DR_HIP(hipMemcpyAsync(ho, plan_->filt.depth, n, hipMemcpyDeviceToHost, stream_));
-      DR_HIP(hipMemcpyAsync(ho + n / 4, plan_->filt.conf, n, hipMemcpyDeviceToHost, stream_));
-      DR_HIP(hipMemcpyAsync(ho + 2 * (n / 4), plan_->filt.depth3, n, hipMemcpyDeviceToHost, stream_));
-      DR_HIP(hipMemcpyAsync(ho + 3 * (n / 4), plan_->filt.conf3, n, hipMemcpyDeviceToHost, stream_));
-    } else launch_publish4(plan_->filt.depth, plan_->filt.conf, plan_->filt.depth3, plan_->filt.conf3, plan_->h_out_dev[blk], n / 16, stream_);
+    launch_publish4(plan_->filt.depth, plan_->filt.conf, plan_->filt.depth3, plan_->filt.conf3, plan_->h_out_dev[blk], n / 16, stream_);
     DR_HIP(hipStreamSynchronize(stream_));
   }
 
   DevTensor &T(const std::string &name) { return plan_->T(name); }  // (callers have a plan: require_config, or they run inside a forward)
-  void release() {
-    plan_.reset();
-    fc_.clear(); fn1_ok_ = false; fc_.fast = fc_.fill = false;  // (a new window shape evicts everything: the entries' buffers are the plan's)
-  }
 
   // (Re)builds the whole plan for a new window shape: the old one goes first (two plans never exist side by side), and the engine keeps
   // H_ = W_ = V_ = 0 ("not configured") and no plan until the new one is complete.  If the builder throws (out of memory, unsupported
   // depth_num, missing tensor) what it had allocated is gone with it, and the next call starts from scratch instead of running a half-built plan.
   void configure(int H, int W, int V) {
     if (H == H_ && W == W_ && V == V_) return;
+    replan(H, W, V);
+  }
+  // ... and for the shape the engine has, when what the plan is built from changed (the feature cache's capacity)
+  void replan(int H, int W, int V) {
     DR_HIP(hipStreamSynchronize(stream_));
-    release();
+    plan_.reset();
+    cache_.release();
     H_ = W_ = V_ = 0;
-    has_output_ = false;  // (the result blocks were the old plan's)
+    slots_.drop();  // (the result blocks were the old plan's)
     memset(win_.cv, 0, sizeof win_.cv);
     memset(win_.rg, 0, sizeof win_.rg);
-    std::unique_ptr<MvsPlan> plan = MvsPlanBuilder{blob_, sw_, device_, lut_, march_err_, H, W, V, shard_nsrc_, fcache_cap_}.build();
-    if (!plan->ops1.empty()) {  // the feature cache's single-view plan exists: what it needs of the engine, with its first use
-      if (!fc_flag_) { fc_flag_ = own_.pinned<int>(1); *fc_flag_ = 0; }
-      if (!up_stream_) { up_stream_ = own_.stream_plain(); ev_hits_ = own_.event(); }
-      fc_.resize(fcache_cap_);
-      fn1_ok_ = true;
-    }
+    std::unique_ptr<MvsPlan> plan = MvsPlanBuilder{blob_, sw_, device_, lut_, march_err_, H, W, V, shard_.nsrc(), cache_.capacity()}.build();
+    cache_.attach(*plan);
     plan_ = std::move(plan);
     H_ = H; W_ = W; V_ = V;
   }
 
-  // ---------------------------------------------------------------- key-frame feature cache (drm_set_feature_cache)
-  // In TANDEM six of a window's seven images were in the previous window (FullSystem.cpp:1162-1171 re-sends frameHessians[i]->image_bgr), and
-  // FeatureNet is per image.  With the cache on, the engine keeps feat1..3 (and the u8 image) of the last `capacity` images; a window whose images
-  // are all cached but at most ONE runs FeatureNet on that one view (its own single-view plan, the same kernel instances as the batch plan) and the
-  // plane sweep reads every view's features where the cache holds them (CostVolArgs::vfeat): 15 launches over 7 views become 11 over one.
-  //  * identity: a 128-bit key over a sample of the image (first / last 64 bytes + 512 evenly spaced 8-byte words) finds the entry; the hit is then
-  //    made EXACT on the device -- every uploaded image is compared byte for byte with the entry's copy (k_verify_image), and a difference (a key
-  //    collision) drops the whole cache and runs the window again without it, before any result leaves the engine;
-  //  * windows with two or more uncached images (the first one, a reset) take the batch path and fill the cache from its outputs;
-  //  * same bits with the cache on and off: the single-view plan is built from the batch plan's own choices (kernel family, channel pass, tiles per wave)
-  //    -- the products and their order per output value do not depend on the tile shape or the batch size (tests: test_feature_cache_is_bit_identical);
-  //  * OFF by default and in every leg of bench.py that feeds `value` / `single_window_ms` (they repeat one window: every image would hit).
-  // decides, for the window being staged, which views the cache answers (FeatureIndex::plan); the guards that need engine state are here
-  void plan_cache_use(int H, int W, int V, const uint8_t *const *bgrs, const int *order) {
-    fc_.stand_down();
-    if (!fn1_ok_ || shard_nsrc_ || comm_ || phase_mode_) return;  // (a view-shard rank computes its own views every time)
-    for (int s = 1; s <= 3; ++s)
-      if (choose_costvol(costvol_shape(win_.cv[s - 1]), sw_, s).family != CostVolChoice::V5) return;  // (only k_costvol5 reads the views by pointer)
-    uint64_t keys[kMaxSrc + 1][2];
-    for (int v = 0; v < V; ++v) image_key(bgrs[order[v]], (size_t)H * W * 3, H, W, keys[v]);
-    fc_.plan(V, keys);
-    // where the plane sweep finds each view
-    for (int s = 0; s < 3; ++s)
-      for (int v = 0; v < V; ++v)
-        if (fc_.fast) win_.cv[s].vfeat[v] = plan_->fcache[fc_.slot[v]].feat[s];
-  }
-  // one launch: the hits compared with their entries' images, the new image filed in its entry
-  void enqueue_cache_io() {
-    const size_t img_bytes = (size_t)H_ * W_ * 3;
-    CacheIoArgs io{};
-    for (int v = 0; v < V_; ++v) {
-      io.img[v] = reinterpret_cast<const uint4 *>(plan_->d_bgr + v * img_bytes);
-      io.entry[v] = reinterpret_cast<uint4 *>(plan_->fcache[fc_.slot[v]].bgr);
-    }
-    io.miss = fc_.miss; io.flag = fc_flag_dev(); io.n16 = img_bytes / 16;
-    launch_cache_io(io, V_, stream_);
-  }
-  // fast path of a forward: verify the hits, FeatureNet on the one uncached view, its outputs (and image) into the entry
-  void forward_cached_features() {
-    const size_t img_bytes = (size_t)H_ * W_ * 3;
-    if (!defer_cache_io_) enqueue_cache_io();
-    if (fc_.miss >= 0) {
-      const FcBuffers &e = plan_->fcache[fc_.slot[fc_.miss]];
-      for (const FnOut &p : plan_->fn1_out) {
-        Op &o = plan_->ops1[p.op];
-        (o.kind == Op::CONV ? o.conv.args.out : o.head3.out) = e.feat[p.stage] + p.offset;
-      }
-      // (the heads on the side stream, as the batch path runs them, were measured: device time 1.821 -> 1.825 ms, the sliding loop x 1.10 instead of x 1.12-1.15 --
-      // two cross-stream waits cost what the overlap of three small launches wins; not kept)
-      for (Op &o : plan_->ops1) {
-        if (o.kind == Op::FRONT) o.front.bgr = plan_->d_bgr + fc_.miss * img_bytes;
-        if (o.kind != Op::CONV && o.kind != Op::FRONT && o.kind != Op::HEAD3) fail(DR_ERR_UNSUPPORTED, "feature cache: op kind %d in the single-view plan", (int)o.kind);
-        launch_op(o, *plan_, win_, sw_, stream_);
-      }
-      fc_.set_valid(fc_.slot[fc_.miss]);
-    }
-  }
-  // batch path with the cache on: every view's features (and image) into its entry, behind the forward that produced them
-  void fill_cache_from_batch() {
-    const size_t img_bytes = (size_t)H_ * W_ * 3;
-    for (int v = 0; v < V_; ++v) {
-      const FcBuffers &e = plan_->fcache[fc_.slot[v]];
-      if (fc_.valid(fc_.slot[v])) continue;
-      for (int s = 0; s < 3; ++s) {
-        const DevTensor &t = T("feat" + std::to_string(s + 1));
-        const size_t n1 = t.n() / t.D;
-        DR_HIP(hipMemcpyAsync(e.feat[s], t.d + v * n1, n1 * 4, hipMemcpyDeviceToDevice, stream_));
-      }
-      DR_HIP(hipMemcpyAsync(e.bgr, plan_->d_bgr + v * img_bytes, img_bytes, hipMemcpyDeviceToDevice, stream_));
-      fc_.set_valid(fc_.slot[v]);
-    }
-  }
-  int *fc_flag_dev() { int *d = nullptr; DR_HIP(hipHostGetDevicePointer((void **)&d, fc_flag_, 0)); return d; }
-  // after a stream synchronise: a hit that was not one (key collision).  The cache is dropped and the staged window runs again on the batch path.
-  bool cache_mismatch_recovered() {
-    if (!fc_flag_ || !*fc_flag_) return false;
-    *fc_flag_ = 0;
-    ++fc_.collisions;
-    fc_.invalidate_all();
-    fc_.fast = false; fc_.fill = false;
-    for (int s = 0; s < 3; ++s) set_batch_vfeat(s);
-    forward(nullptr);
-    DR_HIP(hipStreamSynchronize(stream_));
-    return true;
-  }
-  void set_batch_vfeat(int s) {
-    const DevTensor &t = T("feat" + std::to_string(s + 1));
-    for (int v = 0; v < V_ && v <= kMaxSrc; ++v) win_.cv[s].vfeat[v] = t.d + (size_t)v * (t.n() / t.D);
-  }
-
-  // Copies the window into pinned memory in model order [ref, others] (dr_mvsnet.cpp:190-197), enqueues
-  // the H2D copy and derives every per-call kernel parameter.  Caller holds mu_.
+  // Takes the window to the device in model order [ref, others] and derives every per-call kernel parameter (WindowStager); decides what
+  // the feature cache answers.  A window that CallAsync may enqueue itself (the cache answers it) leaves its ticket parked for the worker.  Caller holds mu_.
   void stage_inputs(int H, int W, int V, int ref, const uint8_t *const *bgrs, const float *K9, const float *const *c2ws,
                     float dmin, float dmax, float disc, bool may_prelaunch = false) {
     DR_HIP(hipSetDevice(device_));
     configure(H, W, V);
-    const size_t img_bytes = (size_t)H * W * 3;
-    const WindowGeometry geo = plan_geometry(H, W, V, ref, K9, c2ws, dmin, dmax, disc, blob_, shard_nsrc_);  // cameras, plane ranges, filter rank (mvs_host.h)
-    const int *order = geo.order;  // model order [ref, others]
-    // view by view: the copy engine moves view v to the device while the host gathers view v + 1 into the pinned block (one 6.45 MB
-    // transfer behind seven memcpys cost their sum: 0.3 + 0.2 ms at 640 x 480 x 7 on the operator boundary's critical path)
-    // Images that already live in page-locked memory (drm_host_alloc, hipHostMalloc, hipHostRegister) go to the device straight from
-    // where they are -- no gather into the pinned block, which is the 0.3-0.4 ms memcpy on the operator boundary's critical path; the
-    // call still returns only when the copies have completed ("inputs are copied before return": the caller may reuse its buffers).
-    // "Page-locked" is decided for the WHOLE image, not for its first byte: the allocation (or registered range) the first byte lies in has
-    // to contain all img_bytes of it -- an image that starts inside a hipHostRegister'ed range and runs past its end takes the staging path.
-    bool pinned = true;
-    for (int v = 0; v < V && pinned; ++v) {
-      hipPointerAttribute_t at;
-      hipDeviceptr_t base = nullptr;
-      size_t span = 0;
-      if (hipPointerGetAttributes(&at, bgrs[v]) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer ||
-          hipMemGetAddressRange(&base, &span, (hipDeviceptr_t)at.devicePointer) != hipSuccess) {
-        (void)hipGetLastError();
-        pinned = false;
-      } else {
-        const char *lo = (const char *)base, *p = (const char *)at.devicePointer;
-        pinned = p >= lo && p + img_bytes <= lo + span;
-      }
-    }
-    for (int s = 1; s <= 3; ++s) {
-      const StageGeometry &g = geo.stage[s - 1];
-      const int sc = 1 << (3 - s), h = H / sc, w = W / sc, D = g.D, C = 32 >> (s - 1);
-      const std::string S = std::to_string(s);
-      const DevTensor &feat = T("feat" + S), &vol = T("volume" + S);
-      CostVolArgs &a = win_.cv[s - 1];
-      memset(&a, 0, sizeof a);
-      a.feat = feat.d; a.fpad = feat.pad;
-      a.vol = vol.d; a.split = vol.split;
-      a.V = V; a.h = h; a.w = w;
-      a.view_aggregation = blob_.view_aggregation;
-      a.dchunk = costvol_dchunk(s, D, a.view_aggregation, a.fpad, sw_);
-      a.nsrc_f = g.nsrc_f;
-      memcpy(a.M, g.M, sizeof a.M);
-      PlaneArgs &p = a.planes;
-      p.D = D; p.dmin = g.dmin; p.interval = g.interval;
-      p.half_range = g.half_range; p.full_range = g.full_range;
-      if (s > 1) { p.prev = T("depth" + std::to_string(s - 1)).d; p.hp = h / 2; p.wp = w / 2; }
-      if (blob_.view_aggregation) {
-        const GateFold gf = fold_gate(blob_, s, C);
-        memcpy(a.gw, gf.gw, sizeof a.gw);
-        a.gA1 = gf.gA1; a.gB1 = gf.gB1; a.gA2 = gf.gA2; a.gB2 = gf.gB2;
-      }
-      RegressArgs &r = win_.rg[s - 1];
-      r.logits = T("logits" + S).d;
-      r.depth = T("depth" + S).d;
-      r.conf = T("conf" + S).d;
-      r.planes = p; r.h = h; r.w = w;
-    }
-    for (int s = 0; s < 3; ++s) set_batch_vfeat(s);
-    if (fcache_cap_ > 0) plan_cache_use(H, W, V, bgrs, order);
+    const WindowGeometry geo = plan_geometry(H, W, V, ref, K9, c2ws, dmin, dmax, disc, blob_, shard_.nsrc());  // cameras, plane ranges, filter rank (mvs_host.h)
+    stager_.begin(H, W, V, bgrs, geo.order);
+    stager_.fill_args(H, W, V, geo, blob_);
+    cache_.to_batch_path();
+    if (cache_.capacity() > 0) cache_.plan_use(H, W, V, bgrs, geo.order, shard_.excludes_cache());
     win_.filter_rank = geo.filter_rank;
-    prelaunched_ = false;
-    // PRELAUNCH (CallAsync with the feature cache answering the window): the device needs ONE image -- the new one -- to start; the other six are only compared
-    // with their cache entries, which can happen last.  So the new image goes up first, the helper thread stages and uploads the rest on a second stream, and
-    // THIS thread enqueues the whole forward meanwhile; the comparison (k_cache_io) is enqueued behind it once the uploads are in flight.  The device starts
-    // ~0.3 ms earlier in TandemBackend's loop (it idles while a window is staged); the call still returns only when every image has been copied.
-    if (may_prelaunch && fc_.fast && up_stream_) {
-      auto up_one = [&, pinned](int v, hipStream_t st) {
-        const uint8_t *src = bgrs[order[v]];
-        if (!pinned) { memcpy(plan_->h_in + v * img_bytes, src, img_bytes); src = plan_->h_in + v * img_bytes; }
-        DR_HIP(hipMemcpyAsync(plan_->d_bgr + v * img_bytes, src, img_bytes, hipMemcpyHostToDevice, st));
-      };
-      const int miss = fc_.miss;
-      if (miss >= 0) {
-        up_one(miss, stream_);
-        if (pinned) {  // (read in place from the caller's page-locked image: waited for before the call returns)
-          if (!ev_h2d_) ev_h2d_ = own_.event();
-          DR_HIP(hipEventRecord(ev_h2d_, stream_));
-        }
-      }
-      copier_.run([&, miss] {
-        DR_HIP(hipSetDevice(device_));
-        for (int v = 0; v < V; ++v) if (v != miss) up_one(v, up_stream_);
-        DR_HIP(hipEventRecord(ev_hits_, up_stream_));
-      });
-      struct Count {  // this window counts as in flight from here; the worker's InFlight takes the count over once prelaunched_ is set
-        std::atomic<int> &n; bool handed_over = false;
-        explicit Count(std::atomic<int> &a) : n(a) { n.fetch_add(1, std::memory_order_relaxed); }
-        ~Count() { if (!handed_over) n.fetch_sub(1, std::memory_order_relaxed); }
-      } count(windows_in_flight(device_));
-      try {
-        defer_cache_io_ = true;
-        forward(nullptr);
-        defer_cache_io_ = false;
-      } catch (...) { defer_cache_io_ = false; copier_.wait_quiet(); throw; }
-      copier_.wait();
-      DR_HIP(hipStreamWaitEvent(stream_, ev_hits_, 0));
-      enqueue_cache_io();
-      if (pinned) {  // uploaded in place from the caller's page-locked images: they must have been read before the call returns
-        DR_HIP(hipEventSynchronize(ev_hits_));
-        if (miss >= 0) DR_HIP(hipEventSynchronize(ev_h2d_));
-      }
-      prelaunched_ = true;
-      count.handed_over = true;
-    } else {
-    auto upload_views = [&, pinned](int v0) {  // views v0, v0 + 2, ...: gather into the staging block (unless page-locked already), then the copy engine
-        DR_HIP(hipSetDevice(device_));
-        for (int v = v0; v < V; v += 2) {
-          const uint8_t *src = bgrs[order[v]];
-          if (!pinned) { memcpy(plan_->h_in + v * img_bytes, src, img_bytes); src = plan_->h_in + v * img_bytes; }
-          DR_HIP(hipMemcpyAsync(plan_->d_bgr + v * img_bytes, src, img_bytes, hipMemcpyHostToDevice, stream_));
-        }
-      };
-      if (!pinned) {
-        copier_.run([&] { upload_views(1); });  // the helper thread takes every other view
-        try { upload_views(0); } catch (...) { copier_.wait_quiet(); throw; }  // (the job refers to this frame's locals)
-        copier_.wait();
-      } else {
-        upload_views(1);
-        upload_views(0);
-      }
-      if (pinned) {
-        if (!ev_h2d_) ev_h2d_ = own_.event();
-        DR_HIP(hipEventRecord(ev_h2d_, stream_));
-        DR_HIP(hipEventSynchronize(ev_h2d_));
-      }
-
-    }
+    if (may_prelaunch && cache_.can_prelaunch()) parked_ = stager_.prelaunch(cache_, [&] { forward(nullptr); });
+    else stager_.upload_all();
   }
 
   // Enqueue one complete forward on stream_ (or the ops [first, last) of it).  ev (optional): plan_->ops.size()+1 events
-  // for per-op timing.
+  // for per-op timing.  What each op gets -- its stream, the fork's events, the view shard's collectives -- is ForwardCursor's answer
+  // (mvs_engine_host.h); this is the loop that executes it.
   //
   // A whole forward (no per-op events, no range) forks: the FeatureNet heads that only stages 2 and 3 need
   // (fn.skip2, fn.out2, fn.skip3, fn.out3 -- 0.5 ms at 640x480) run on a side stream under stage 1's cost volume and
   // regularisation, whose coarse UNet levels leave most CUs idle; stage 2 / 3's cost volume waits for feat2 / feat3.
   // The next forward's main-stream work is ordered after those waits, so the side stream never runs ahead of a reader.
   void forward(std::vector<hipEvent_t> *ev, size_t first = 0, size_t last = ~(size_t)0) {
-    if ((fc_.fast || fc_.fill) && !(first == 0 && last >= plan_->ops.size())) {  // a partial forward (phases, one op) cannot skip FeatureNet: the window goes back to the batch path
-      fc_.fast = fc_.fill = false;
-      for (int s = 0; s < 3; ++s) set_batch_vfeat(s);
-    }
-    const bool cached = fc_.fast;  // FeatureNet answered by the feature cache: its ops are skipped
+    const ForwardRange range{first, last, plan_->ops.size()};
+    if ((cache_.fast() || cache_.fill()) && !range.whole()) cache_.to_batch_path();  // a partial forward (phases, one op) cannot skip FeatureNet
+    const bool cached = cache_.fast();  // FeatureNet answered by the feature cache: its ops are skipped
     // ... unless other engines of this process have windows in flight on the device: their kernels already fill the idle CUs, and a second stream per
     // engine only adds queue contention (4 engines: 580 depth maps/s without the fork against 570 with it, profiles/r06_queues_side_stream.txt; alone: 2.150 ms
     // with it against 2.165).  Same kernels in the same per-stream order either way: the result does not depend on it.
     const bool alone = windows_in_flight(device_).load(std::memory_order_relaxed) <= 1;
-    const bool fork = sw_.side_stream && alone && !ev && first == 0 && last >= plan_->ops.size() && plan_->fork_lo < plan_->fork_hi && !cached;
-    if (cached) forward_cached_features();
-    // view shard, reduce-to-root form: between a stage's cost volume and its regression only rank 0 works
-    const bool rooted = comm_ && shard_nsrc_ && !phase_mode_ && !sw_.shard_allreduce;
-    bool idle_stage = false;
+    ForwardCursor cursor({range, ev != nullptr, alone, sw_.side_stream, cached, plan_->fork_lo, plan_->fork_hi, plan_->feat2_op,
+                          shard_.form(sw_), shard_.rank(), shard_.phase_mode(),
+                          {win_.cv[0].V - 1 > 0, win_.cv[1].V - 1 > 0, win_.cv[2].V - 1 > 0}});
+    if (cached) cache_.forward_cached_features();
     size_t i = 0;
     for (const Op &o : plan_->ops) {
       if (ev) DR_HIP(hipEventRecord((*ev)[i], stream_));
-      ++i;
-      if (i - 1 < first || i - 1 >= last) continue;
-      if (cached && i - 1 < plan_->fork_hi) continue;
-      if (idle_stage && o.kind != Op::REGRESS) continue;  // (CostRegNet and prob of this stage run on rank 0 only)
-      const bool on_side = fork && i - 1 >= plan_->fork_lo && i - 1 < plan_->fork_hi;
-      if (fork && i - 1 == plan_->fork_lo) { DR_HIP(hipEventRecord(ev_fork_, stream_)); DR_HIP(hipStreamWaitEvent(side_, ev_fork_, 0)); }
-      if (fork && o.kind == Op::COSTVOL && o.stage == 2) DR_HIP(hipStreamWaitEvent(stream_, ev_feat2_, 0));
-      if (fork && o.kind == Op::COSTVOL && o.stage == 3) DR_HIP(hipStreamWaitEvent(stream_, ev_feat3_, 0));
-      const hipStream_t st = on_side ? side_ : stream_;
+      const ForwardCursor::Step s = cursor.at(i++, o.kind == Op::COSTVOL, o.kind == Op::REGRESS, o.stage);
+      if (s.skip) continue;
+      if (s.open_fork) { DR_HIP(hipEventRecord(ev_fork_, stream_)); DR_HIP(hipStreamWaitEvent(side_, ev_fork_, 0)); }
+      if (s.wait_feat2) DR_HIP(hipStreamWaitEvent(stream_, ev_feat2_, 0));
+      if (s.wait_feat3) DR_HIP(hipStreamWaitEvent(stream_, ev_feat3_, 0));
+      const hipStream_t st = s.side ? side_ : stream_;
       // a view-shard rank that holds the reference view only: its partial volume is the empty sum (the kernels return without storing)
-      if (o.kind == Op::COSTVOL && win_.cv[o.stage - 1].V - 1 <= 0) { const DevTensor &vol = T("volume" + std::to_string(o.stage)); DR_HIP(hipMemsetAsync(vol.d, 0, vol.n() * 4, st)); }
-      if (!idle_stage) launch_op(o, *plan_, win_, sw_, st);  // (idle here: the REGRESS op of a stage that rank 0 alone regularised)
-      if (o.kind == Op::COSTVOL && comm_ && shard_nsrc_ && !phase_mode_) {  // view shard: sum the partial volumes of all ranks, in place, in stream order
-        const DevTensor &vol = T("volume" + std::to_string(o.stage));
-        Rccl &r = Rccl::get();
-        if (rooted) {
-          r.check(r.Reduce(vol.d, vol.d, vol.n(), ncclFloat, ncclSum, 0, comm_, st), "ncclReduce");
-          idle_stage = comm_rank_ != 0;
-        } else r.check(r.AllReduce(vol.d, vol.d, vol.n(), ncclFloat, ncclSum, comm_, st), "ncclAllReduce");
-      }
-      if (o.kind == Op::REGRESS && rooted) {  // the stage's depth map goes back to every rank: stage s + 1 centres its hypotheses on it; stage 3's
-        Rccl &c = Rccl::get();                // depth and confidence are the result (the edge filter then runs on every rank: 0.08 ms)
-        const DevTensor &dep = T("depth" + std::to_string(o.stage));
-        c.check(c.Broadcast(dep.d, dep.d, dep.n(), ncclFloat, 0, comm_, st), "ncclBroadcast");
-        if (o.stage == 3) {
-          const DevTensor &cf = T("conf3");
-          c.check(c.Broadcast(cf.d, cf.d, cf.n(), ncclFloat, 0, comm_, st), "ncclBroadcast");
-        }
-        idle_stage = false;
-      }
+      if (s.zero_volume) { const DevTensor &vol = T("volume" + std::to_string(o.stage)); DR_HIP(hipMemsetAsync(vol.d, 0, vol.n() * 4, st)); }
+      if (s.launch) launch_op(o, *plan_, win_, sw_, st);
+      // view shard: sum the partial volumes of all ranks, in place, in stream order
+      if (s.reduce) shard_.reduce(T("volume" + std::to_string(o.stage)), st);
+      if (s.all_reduce) shard_.all_reduce(T("volume" + std::to_string(o.stage)), st);
+      // the stage's depth map goes back to every rank: stage s + 1 centres its hypotheses on it; stage 3's depth and
+      // confidence are the result (the edge filter then runs on every rank: 0.08 ms)
+      if (s.broadcast_depth) shard_.broadcast(T("depth" + std::to_string(o.stage)), st);
+      if (s.broadcast_conf3) shard_.broadcast(T("conf3"), st);
       // the side stream's results are published after whichever op ends them (fn.out2; the LAST op of the fork range: a
       // convolution in the fused-skip form, the border kernel in the folded form) -- independent of the op kind
-      if (on_side && i - 1 == plan_->feat2_op) DR_HIP(hipEventRecord(ev_feat2_, side_));
-      if (on_side && i - 1 == plan_->fork_hi - 1) DR_HIP(hipEventRecord(ev_feat3_, side_));
+      if (s.record_feat2) DR_HIP(hipEventRecord(ev_feat2_, side_));
+      if (s.record_feat3) DR_HIP(hipEventRecord(ev_feat3_, side_));
     }
-    if (fc_.fill && first == 0 && last >= plan_->ops.size()) fill_cache_from_batch();
+    if (cache_.fill() && cursor.whole()) cache_.fill_from_batch();
     if (ev) DR_HIP(hipEventRecord((*ev)[i], stream_));
     DR_HIP(hipGetLastError());
   }
@@ -775,37 +458,20 @@ class MvsEngine {
   void check_march() {
     if (march_err_ && *march_err_) { const int c = *march_err_; *march_err_ = 0; fail(DR_ERR_DEVICE, "k_conv_m: a ring wait gave up (code %d): the LDS producer/consumer protocol stalled", c); }
   }
-  // key-frame feature cache (plan_cache_use .. set_batch_vfeat; the single-view plan and the entries' buffers are the plan's)
-  int fcache_cap_ = 0;             // entries (0: off, the default)
-  FeatureIndex fc_;                // which entry answers which view of the staged window; LRU; counters (mvs_host.h)
-  bool fn1_ok_ = false;            // the single-view plan exists and matches the batch plan's instances
-  int *fc_flag_ = nullptr;         // page-locked: raised by k_cache_io
-  hipStream_t up_stream_ = nullptr;  // uploads of the images the cache answers (prelaunch, stage_inputs)
-  hipEvent_t ev_hits_ = nullptr;
-  bool prelaunched_ = false;       // the staged window's forward is already on the stream (the worker only publishes)
-  bool defer_cache_io_ = false;    // ... and its image comparison follows once the uploads are in flight
-
-  int out_cur_ = 0;                // the result block (MvsPlan::h_out) the last result is in
-  hipEvent_t ev_h2d_ = nullptr;    // completion of a window uploaded straight from the caller's page-locked images
   int H_ = 0, W_ = 0, V_ = 0;
-  int shard_nsrc_ = 0;  // > 0: view-shard rank, cost-volume divisor = source views of the whole window
-  ncclComm_t comm_ = nullptr;  // view-shard communicator (drm_comm_init); the volumes are reduced in stream order when set
-  int comm_rank_ = 0;
-  // Collective form of a sharded forward (MvsSwitches::shard_allreduce).  Default: the partial volumes are REDUCED to rank 0, which
-  // alone regularises and regresses the stage, and the stage's depth map (what the next stage's hypotheses hang on: 77 / 307 /
-  // 1229 KB) is BROADCAST back -- (n-1)/n x 354 MB over xGMI per depth map instead of the all-reduce's 2(n-1)/n, and no redundant
-  // CostRegNet on the other ranks.  DR_SHARD_ALLREDUCE=1: round 2's form (sum all-reduce, every rank
-  // regularises redundantly; no broadcast).
-  bool phase_mode_ = false;
+  // the parts: what they take from the runtime is own_'s, so they hold nothing that outlives the members above
+  const MvsCore core_{sw_, device_, own_, stream_, plan_, win_, H_, W_, V_};
+  FeatureCacheDev cache_{core_};  // the key-frame feature cache (the single-view plan and the entries' buffers are the plan's)
+  ViewShard shard_;               // source-view total, communicator, collectives, phase mode
+  WindowTicket parked_;           // of a window whose forward CallAsync enqueued itself (the worker only publishes)
 
   std::thread worker_;
   HostCopier copier_;
+  WindowStager stager_{core_, copier_};
   std::mutex mu_;
   std::condition_variable input_cv_, done_cv_;
   bool running_ = true;
-  std::atomic<bool> unprocessed_{false};  // read without the lock by ready() (dr_mvsnet.cpp:54 does the same with a plain bool)
-  bool has_output_ = false;
-  std::string worker_error_;
+  ResultSlots slots_;  // unprocessed / has output / which result block / the worker's error
 };
 
 }  // namespace dr

@@ -392,7 +392,6 @@ struct MvsSwitches {
   bool prob_launch_order = hon("DR_PROB_LAUNCH_ORDER"), prob_on_conv = hon("DR_PROB_ON_CONV");
   bool skip_on_conv = hon("DR_SKIP_ON_CONV"), no_skip_fusion = hon("DR_NO_SKIP_FUSION");
   bool out3_folded = hnum("DR_OUT3_FOLDED", 1) != 0;     // 0: FeatureNet's stage-3 head in its literal order (fused-skip kernel)
-  bool d2h_copy = hook_env("DR_MVS_D2H") && !strcmp(hook_env("DR_MVS_D2H"), "copy");  // four copy-engine transfers instead of k_publish4
   // k_costvol5's two choices (round 6, profiles/r06_costvol_ab.txt): a sample whose footprint is the previous plane's issues no gathers (0.109 / 0.172 / 0.120 ->
   // 0.084 / 0.150 / 0.117 ms at depth chunks of 4 / 8 / 8 planes; 0.078 / 0.126 / 0.099 in the single-set form); the workgroup tile is four rows of a quarter segment
   // (0.108 -> 0.099 ms at stage 3, 0.126 -> 0.122 at stage 2, nothing at stage 1)

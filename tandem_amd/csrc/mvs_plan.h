@@ -63,7 +63,7 @@ struct FeatureNetOps {
 struct FnOut { size_t op; int stage; size_t offset; };  // launch `op` of the single-view plan stores into feat<stage + 1> at this float offset
 struct FcBuffers { float *feat[3] = {nullptr, nullptr, nullptr}; uint8_t *bgr = nullptr; };  // entry e of the feature cache's index (mvs_host.h): its three bordered feature maps and its image
 
-// what a call derives from its cameras and ranges (MvsEngine::stage_inputs): the plan's launches read it next to their own arguments
+// what a call derives from its cameras and ranges (WindowStager::fill_args, mvs_stage.h): the plan's launches read it next to their own arguments
 struct WindowArgs {
   CostVolArgs cv[3];
   RegressArgs rg[3];
@@ -105,7 +105,7 @@ struct MvsPlan {  // (not copyable: its owner is not)
   FilterArgs filt{};
   uint8_t *d_bgr = nullptr, *h_in = nullptr;  // the window's images on the device, and the pinned block they are gathered in
   float *h_out[2] = {nullptr, nullptr}, *h_out_dev[2] = {nullptr, nullptr};  // two pinned result blocks (4 maps each), used alternately, and the addresses the device uses for them
-  // key-frame feature cache (MvsEngine::plan_cache_use ..): FeatureNet for ONE view, where its three outputs go, the entries.  ops1 is empty where the
+  // key-frame feature cache (FeatureCacheDev, mvs_cache.h): FeatureNet for ONE view, where its three outputs go, the entries.  ops1 is empty where the
   // window shape, the switches or the planner's candidates do not allow it.
   std::vector<Op> ops1;
   std::vector<FnOut> fn1_out;
@@ -492,7 +492,7 @@ struct MvsPlanBuilder {
     return out;
   }
 
-  // The single-view plan of the key-frame feature cache (dr_mvsnet.hip has the whole story, above MvsEngine::plan_cache_use): FeatureNet once more, for one view and into
+  // The single-view plan of the key-frame feature cache (mvs_cache.h has the whole story, in its opening comment): FeatureNet once more, for one view and into
   // tensors of its own ("c1."), every launch the batch plan's kernel instance for that layer; the entries; which launches store feat1..3, and where.
   void build_fn1(int H, int W) {
     if (p_.ops.empty() || p_.ops[0].kind != Op::FRONT || sw_.costvol_v1 || shard_nsrc_) return;  // (the single-view plan patches k_fn_front's image pointer per call)
@@ -522,6 +522,17 @@ struct MvsPlanBuilder {
     if (p_.fn1_out.size() != 3) { p_.ops1.clear(); p_.fcache.clear(); }
   }
 
+};
+
+// What the engine's parts (mvs_stage.h, mvs_cache.h) read of the engine: references to members of its own, which outlive them.
+struct MvsCore {
+  const MvsSwitches &sw;
+  const int &device;
+  HipOwner &own;
+  const hipStream_t &stream;
+  const std::unique_ptr<MvsPlan> &plan;  // of the window shape H x W x V; null while the engine is not configured
+  WindowArgs &win;                       // of the staged window
+  const int &H, &W, &V;
 };
 
 }  // namespace dr
