@@ -866,7 +866,8 @@ int drf_track_pyramid_level_stats(drf_t *h, int level, uint64_t out[4]);
  * its Jacobian, at n poses of one depth image in one kernel (one wave per pose) instead of n drf_locate_system calls, and
  * drf_search_frame scores a lattice of poses around anchors, tracks the best few (drf_track_frame's rule), locates them
  * (drf_locate_frame's rule) and picks one.  It is a geometric score: it has no appearance term and is ambiguous where geometry
- * repeats (two alike corridors score alike) -- the runner-up entries of the result show it.
+ * repeats (two alike corridors score alike) -- the runner-up entries of the result show it; drf_search_colour_frame, further below,
+ * adds an appearance term from the voxel colours for frames that have a colour image.
  * SCOPE.  The score reads the resident map only: with streaming on, blocks in the host store read as absent (their samples are
  * UNOBSERVED) and drf_search_stats()[7] tells how many there are; DRF_LOCATE_MAP does not apply to the score.  The refinement
  * stages keep their own scopes (drf_set_render_scope for the tracking's renders, drf_set_locate_scope for the localisation).  The
@@ -962,6 +963,87 @@ int drf_search_frame_device(drf_t *h, const void *d_depth, const float *anchors1
  * evaluations of the refinement, [6] device bytes held by the score stage, [7] blocks in the host store at the call (all 0 after a
  * call that was refused) */
 int drf_search_stats(drf_t *h, uint64_t out[8]);
+/* The search with an appearance term from the voxel colours (no reference counterpart; DESIGN.md §7c "Searching with colour").  The
+ * score above is geometric, and it is ambiguous wherever geometry says nothing: on ONE wall every in-plane offset of the lattice
+ * scores alike, and the winner is whatever the tie rule picks.  Every voxel carries a colour, and the score's fetch of a corner
+ * already loads it; these calls keep it.  drf_score_colour_poses is drf_score_poses with a second sum, photo, and
+ * drf_search_colour_frame is drf_search_frame selecting on the colour score, tracking with the frame's colour image and picking the
+ * winner by the colour score of the located poses.  The geometric calls stay as they are, for frames without colour.
+ * The rule (pose_host.h score_colour_point, the one text the host and k_search_score_colour compile; + - * / floor):
+ *   sample    drf_score_poses', to the letter, up to and including cost = cost + (w r) r.  A valid sample goes on:
+ *   y[c]      ((float)c0 + (float)c1) + (float)c2 of corner c, c0, c1, c2 = bits 0-7, 8-15, 16-23 of the voxel's second word (its
+ *             stored B, G, R): a whole number in 0..765, the intensity of drf_track_colour_*.
+ *   Ym        the fp32 trilinear interpolant of y[] in phi's three stages and order (z, then y, then x) with the same f.
+ *   yf        the same intensity of the frame's BGR pixel at the sample's own (u, v).
+ *   term      rp = lambda * ((double)Ym - (double)yf), lambda = (double)photo_weight; wp = 1 if |rp| <= huber else huber / |rp|
+ *             (the geometric huber); tp = (wp rp) rp, and tp = pc where tp > pc: a sample whose colour disagrees costs at most
+ *             pc.  photo = photo + tp, after the geometric addition.
+ *   photo     reduced exactly as cost is: per lane from +0.0, the group butterfly, lane i % 64 adds partial i in ascending i, the
+ *             last butterfly.
+ *   score     (((cost + photo) + oc * (double)outside) + uc * (double)unobserved) / (double)samples; samples = 0 gives uc.
+ *   options   photo_weight 0 -> (float)(1.0 / 27.0) * huber in fp32, huber resolved first (drf_track_colour_options_t's default);
+ *             photo_cap 0 -> oc.
+ * Two invariants hold bit for bit: cost and counts equal drf_score_poses' at the same score options; on a map of one colour and
+ * a frame image of that colour photo is +0.0 at every pose and score has drf_score_poses' bits.
+ * drf_search_colour_frame: candidates, index order, the pose table and chunking are drf_search_frame's.  The selection takes the
+ * top_k smallest COLOUR scores, ties to the lower index, a NaN last.  Each selected entry in rank order: drf_track_pyramid_frame's
+ * rule with the frame's bgr from the candidate's float pose (track_opt null: its defaults; levels = 1: drf_track_colour_frame); if
+ * that ends <= DRF_ALIGN_MAX_ITERS, drf_locate_frame's rule; an entry qualifies as in drf_search_frame.  When the refinement has
+ * ended, the located float pose of every qualifying entry is scored once more by the colour score (one launch, in rank order):
+ * final_score, final_photo (0 for an entry that does not qualify).  The winner has the smallest final_score among the qualifying,
+ * ties to the better rank; accept_valid > 0 ends the refinement at the first qualifying entry that reaches the share, and that entry
+ * wins.  score_only, the LOST convention and the statuses are drf_search_frame's.
+ * Device scratch: drf_search_frame's plus 4 bytes per grid position (yf), a 40-byte record per candidate of a chunk (cost, photo,
+ * counts[4], score) instead of 32, and a colour image (3 bytes per pixel) for a host-given frame.
+ * SCOPE and side effects are drf_search_frame's: the resident map only, stored blocks counted in [7]; the map, the public render
+ * buffers and the streaming state untouched; drf_track_pyramid_stats and drf_locate_stats describe the last refinement stage that
+ * ran.  drf_search_stats describes the last call of either family; the final re-score is not counted in [0] or [3].
+ * OUT OF SCOPE: exposure or affine brightness (frame and map share their exposure, as for drf_track_colour_*); the stored blocks of
+ * a streamed map; selection on the device, a coarse-to-fine lattice, rotations about the camera's own axes.
+ * Legality and refusals follow drf_search_frame's order: a null argument (bgr among them: a null bgr is DR_ERR_ARG -- the
+ * geometric call is for frames without colour; for drf_score_colour_poses any of the four outputs but not all may be null); the
+ * score or search options, then photo_weight and photo_cap (negative or not finite), then the track, then the locate options; the
+ * count of candidates; the call order; the poses by index. */
+typedef struct {
+  drf_score_options_t score;
+  float photo_weight;  /* voxels per intensity unit; 0 -> (1 / 27) * huber */
+  float photo_cap;     /* voxels^2: the most one sample's colour term adds; 0 -> outside_cost */
+} drf_score_colour_options_t;
+/* cost[n], photo[n], counts[n][4], score[n]; each output may be null, not all */
+int drf_score_colour_poses(drf_t *h, const uint8_t *bgr, const float *depth, const float *poses16, size_t n, const drf_score_colour_options_t *opt, double *cost,
+                           double *photo, uint32_t *counts, double *score);
+int drf_score_colour_poses_device(drf_t *h, const void *d_bgr, const void *d_depth, const float *poses16, size_t n, const drf_score_colour_options_t *opt,
+                                  double *cost, double *photo, uint32_t *counts, double *score);
+typedef struct {
+  drf_search_options_t search;
+  float photo_weight;
+  float photo_cap;
+} drf_search_colour_options_t;
+typedef struct {  /* drf_search_entry_t's fields, then the colour sums */
+  uint64_t index;
+  double   score, cost;                 /* of the score stage: the colour score, the geometric sum */
+  uint32_t counts[4];
+  int      track_status, locate_status;
+  uint64_t samples, valid;
+  double   located_cost;
+  double   T[16];
+  double   photo;                       /* of the score stage */
+  double   final_score, final_photo;    /* the colour score of the located float pose (0: the entry did not qualify) */
+} drf_search_colour_entry_t;
+typedef struct {
+  int      status;
+  int      n_entries;
+  int      winner;
+  int      refined;
+  uint64_t n_candidates;
+  drf_search_colour_entry_t entries[DRF_SEARCH_MAX_TOP];  /* in rank order: ascending colour score */
+} drf_search_colour_result_t;
+int drf_search_colour_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float *anchors16, size_t n_anchors, const double *rotations9, size_t n_rot,
+                            const drf_search_colour_options_t *opt, const drf_track_pyramid_options_t *track_opt, const drf_locate_options_t *locate_opt,
+                            float pose16_out[16], drf_search_colour_result_t *res, double *all_scores);
+int drf_search_colour_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float *anchors16, size_t n_anchors, const double *rotations9,
+                                   size_t n_rot, const drf_search_colour_options_t *opt, const drf_track_pyramid_options_t *track_opt,
+                                   const drf_locate_options_t *locate_opt, float pose16_out[16], drf_search_colour_result_t *res, double *all_scores);
 
 /* --- incremental mesh: an extraction that returns only the blocks whose triangles may have changed (no reference counterpart;
  * DESIGN.md §7c "Incremental mesh", INTEGRATION.md "Incremental mesh").

@@ -176,6 +176,11 @@ SIGNATURES = {
     "drf_search_frame": (C.c_int, [vp, f32p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f64p]),
     "drf_search_frame_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f64p]),
     "drf_search_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_score_colour_poses": (C.c_int, [vp, C.c_void_p, f32p, f32p, C.c_size_t, C.c_void_p, f64p, f64p, C.POINTER(C.c_uint32), f64p]),
+    "drf_score_colour_poses_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, C.c_size_t, C.c_void_p, f64p, f64p, C.POINTER(C.c_uint32), f64p]),
+    "drf_search_colour_frame": (C.c_int, [vp, C.c_void_p, f32p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f64p]),
+    "drf_search_colour_frame_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p,
+                                                 f64p]),
 }
 
 
@@ -232,6 +237,27 @@ class SearchResultStruct(C.Structure):
     """drf_search_result_t."""
     _fields_ = [("status", C.c_int), ("n_entries", C.c_int), ("winner", C.c_int), ("refined", C.c_int), ("n_candidates", C.c_uint64),
                 ("entries", SearchEntryStruct * SEARCH_MAX_TOP)]
+
+
+class ScoreColourOptions(C.Structure):
+    """drf_score_colour_options_t: a zero field means its default."""
+    _fields_ = [("score", ScoreOptions), ("photo_weight", C.c_float), ("photo_cap", C.c_float)]
+
+
+class SearchColourOptions(C.Structure):
+    """drf_search_colour_options_t: a zero field means its default."""
+    _fields_ = [("search", SearchOptions), ("photo_weight", C.c_float), ("photo_cap", C.c_float)]
+
+
+class SearchColourEntryStruct(C.Structure):
+    """drf_search_colour_entry_t: drf_search_entry_t's fields, then the colour sums."""
+    _fields_ = SearchEntryStruct._fields_ + [("photo", C.c_double), ("final_score", C.c_double), ("final_photo", C.c_double)]
+
+
+class SearchColourResultStruct(C.Structure):
+    """drf_search_colour_result_t."""
+    _fields_ = [("status", C.c_int), ("n_entries", C.c_int), ("winner", C.c_int), ("refined", C.c_int), ("n_candidates", C.c_uint64),
+                ("entries", SearchColourEntryStruct * SEARCH_MAX_TOP)]
 
 
 class AlignResultStruct(C.Structure):

@@ -35,7 +35,7 @@ namespace dr {
 #include "track_kernels.h"   // k_track_model, k_track (drf_track_system, drf_track_frame)
 #include "track_colour_kernels.h"  // k_track_model_colour, k_track_colour (drf_track_colour_system, drf_track_colour_frame)
 #include "track_pyramid_kernels.h"  // k_track_reduce (drf_track_reduce, drf_track_pyramid_system, drf_track_pyramid_frame)
-#include "search_kernels.h"  // k_search_points, k_search_score (drf_score_poses, drf_search_frame)
+#include "search_kernels.h"  // k_search_points, k_search_score (drf_score_poses, drf_search_frame) and their colour forms (drf_score_colour_poses, drf_search_colour_frame)
 
 }  // namespace dr
 #include "mesh_kernels.h"
@@ -934,6 +934,30 @@ int drf_search_frame_device(drf_t *h, const void *d_depth, const float *anchors1
   });
 }
 int drf_search_stats(drf_t *h, uint64_t out[8]) { return guarded([&] { eng(h)->search().search_stats(out); }); }
+int drf_score_colour_poses(drf_t *h, const uint8_t *bgr, const float *depth, const float *poses16, size_t n, const drf_score_colour_options_t *opt, double *cost,
+                           double *photo, uint32_t *counts, double *score) {
+  return guarded([&] { eng(h)->search().score_colour_poses("drf_score_colour_poses", bgr, depth, nullptr, nullptr, poses16, n, opt, cost, photo, counts, score); });
+}
+int drf_score_colour_poses_device(drf_t *h, const void *d_bgr, const void *d_depth, const float *poses16, size_t n, const drf_score_colour_options_t *opt,
+                                  double *cost, double *photo, uint32_t *counts, double *score) {
+  return guarded([&] { eng(h)->search().score_colour_poses("drf_score_colour_poses_device", nullptr, nullptr, d_bgr, d_depth, poses16, n, opt, cost, photo, counts, score); });
+}
+int drf_search_colour_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float *anchors16, size_t n_anchors, const double *rotations9, size_t n_rot,
+                            const drf_search_colour_options_t *opt, const drf_track_pyramid_options_t *track_opt, const drf_locate_options_t *locate_opt,
+                            float pose16_out[16], drf_search_colour_result_t *res, double *all_scores) {
+  return guarded_note([&] {
+    return eng(h)->search().search_colour_frame("drf_search_colour_frame", bgr, depth, nullptr, nullptr, anchors16, n_anchors, rotations9, n_rot, opt, track_opt, locate_opt,
+                                                pose16_out, res, all_scores);
+  });
+}
+int drf_search_colour_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float *anchors16, size_t n_anchors, const double *rotations9,
+                                   size_t n_rot, const drf_search_colour_options_t *opt, const drf_track_pyramid_options_t *track_opt,
+                                   const drf_locate_options_t *locate_opt, float pose16_out[16], drf_search_colour_result_t *res, double *all_scores) {
+  return guarded_note([&] {
+    return eng(h)->search().search_colour_frame("drf_search_colour_frame_device", nullptr, nullptr, d_bgr, d_depth, anchors16, n_anchors, rotations9, n_rot, opt, track_opt,
+                                                locate_opt, pose16_out, res, all_scores);
+  });
+}
 int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->locate().set_locate_scope(scope, stage_capacity_blocks); }); }
 int drf_locate_stage_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->locate().locate_stage_stats(out); }); }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->render().set_render_scope(scope, stage_capacity_blocks); }); }

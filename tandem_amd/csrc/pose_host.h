@@ -1216,4 +1216,225 @@ inline void search_refine(const SearchOpt &o, const double *table, const std::ve
   for (int i = 0; i < 16; ++i) pose16_out[i] = (float)res.entries[res.winner].T[i];
 }
 
+// ---- searching with colour (drf_score_colour_poses / drf_search_colour_frame; DESIGN.md §7c "Searching with colour").  The score
+// above is geometric: on one wall every in-plane offset of the lattice scores alike.  Every voxel carries a colour, and the fetch
+// of a corner already returns it as the second word of its load; the colour score keeps those bytes and adds an appearance term
+// per valid sample -- the trilinear model intensity against the frame's pixel -- into a second sum, photo, reduced exactly as cost
+// is.  cost and counts keep drf_score_poses' bits.  Frame and map share their exposure, as for drf_track_colour_*.
+struct ScoreColourOpt {  // drf_score_colour_options_t with its defaults resolved
+  ScoreOpt s;
+  float photo_weight;  // voxels per intensity unit
+  double lambda, pc;   // (double)photo_weight; the most one sample's colour term costs
+};
+// the two colour fields behind a resolved ScoreOpt.  Returns null, or which is negative or not finite
+inline const char *score_photo_options(float photo_weight, float photo_cap, const ScoreOpt &s, ScoreColourOpt &o) {
+  if (!(photo_weight >= 0.0f) || !std::isfinite(photo_weight)) return "photo_weight";
+  if (!(photo_cap >= 0.0f) || !std::isfinite(photo_cap)) return "photo_cap";
+  o.s = s;
+  o.photo_weight = photo_weight != 0.0f ? photo_weight : (float)(1.0 / 27.0) * s.huber;  // track_colour_options' default, for its reason
+  o.lambda = (double)o.photo_weight;
+  o.pc = photo_cap != 0.0f ? (double)photo_cap : s.oc;
+  return nullptr;
+}
+// null: all defaults.  The score options' own refusals first
+inline const char *score_colour_options(const drf_score_colour_options_t *opt, float truncation_distance, float voxel_size, ScoreColourOpt &o) {
+  ScoreOpt s{};
+  if (const char *bad = score_options(opt ? &opt->score : nullptr, truncation_distance, voxel_size, s)) return bad;
+  return score_photo_options(opt ? opt->photo_weight : 0.0f, opt ? opt->photo_cap : 0.0f, s, o);
+}
+struct SearchColourOpt {  // drf_search_colour_options_t with its defaults resolved
+  SearchOpt s;
+  ScoreColourOpt c;
+};
+inline const char *search_colour_options(const drf_search_colour_options_t *opt, float truncation_distance, float voxel_size, SearchColourOpt &o) {
+  if (const char *bad = search_options(opt ? &opt->search : nullptr, truncation_distance, voxel_size, o.s)) return bad;
+  return score_photo_options(opt ? opt->photo_weight : 0.0f, opt ? opt->photo_cap : 0.0f, o.s.s, o.c);
+}
+// One sample at the camera-frame point g whose frame intensity is yf: score_point word for word up to cost = cost + (w r) r, the
+// colour bytes of the eight corners kept, and for a valid sample the colour term behind the geometric one: y[c] = the intensity of
+// corner c's three bytes (bits 0-7, 8-15, 16-23 of its second word), Ym their fp32 trilinear interpolant in phi's stages and order
+// with the same f, rp = lambda (Ym - yf) in double, Huber's weight with the geometric huber, the term capped at pc.
+template <class Fetch>
+DR_HOST_DEVICE inline int score_colour_point(const AlignEval &e, double lambda, double pc, double g0, double g1, double g2, float yf, Fetch &&fetch, double &cost,
+                                             double &photo) {
+  int b[3];
+  float f[3];
+  DR_UNROLL
+  for (int k = 0; k < 3; ++k) {
+    const double q = ((e.m.R[3 * k] * g0 + e.m.R[3 * k + 1] * g1) + e.m.R[3 * k + 2] * g2) + e.m.tv[k];
+    if (!(q > -1073741824.0 && q < 1073741824.0)) return 0;
+    const double fl = floor(q);
+    b[k] = (int)fl;
+    f[k] = (float)(q - fl);
+  }
+  float s[8];  // index 4 cx + 2 cy + cz
+  uint32_t col[8];
+  DR_UNROLL
+  for (int c = 0; c < 8; ++c) {
+    uint32_t v[2];
+    fetch(b[0] + (c >> 2), b[1] + ((c >> 1) & 1), b[2] + (c & 1), v);
+    if ((int)(v[1] >> 24) < e.min_weight) return 0;
+    memcpy(&s[c], &v[0], 4);
+    col[c] = v[1];
+  }
+  float ez[4];  // index 2 cx + cy
+  DR_UNROLL
+  for (int c = 0; c < 4; ++c) ez[c] = s[2 * c] + f[2] * (s[2 * c + 1] - s[2 * c]);
+  float d[2];
+  DR_UNROLL
+  for (int c = 0; c < 2; ++c) d[c] = ez[2 * c] + f[1] * (ez[2 * c + 1] - ez[2 * c]);
+  const float phi = d[0] + f[0] * (d[1] - d[0]);
+  const float ap = phi < 0.0f ? -phi : phi;
+  if (!(ap < e.band)) return 2;
+  const double r = (double)phi / e.vs;  // align_point's ((double)phi - (double)s_src) / vs with s_src = 0: the same bits
+  const double a = r < 0.0 ? -r : r;
+  const double w = a <= e.huber ? 1.0 : e.huber / a;
+  cost = cost + (w * r) * r;
+  float y[8];
+  DR_UNROLL
+  for (int c = 0; c < 8; ++c) y[c] = ((float)(col[c] & 255u) + (float)((col[c] >> 8) & 255u)) + (float)((col[c] >> 16) & 255u);
+  float yz[4];
+  DR_UNROLL
+  for (int c = 0; c < 4; ++c) yz[c] = y[2 * c] + f[2] * (y[2 * c + 1] - y[2 * c]);
+  float yd[2];
+  DR_UNROLL
+  for (int c = 0; c < 2; ++c) yd[c] = yz[2 * c] + f[1] * (yz[2 * c + 1] - yz[2 * c]);
+  const float Ym = yd[0] + f[0] * (yd[1] - yd[0]);
+  const double rp = lambda * ((double)Ym - (double)yf);
+  const double app = rp < 0.0 ? -rp : rp;
+  const double wp = app <= e.huber ? 1.0 : e.huber / app;
+  double tp = (wp * rp) * rp;
+  if (tp > pc) tp = pc;
+  photo = photo + tp;
+  return 1;
+}
+// (((cost + photo) + oc outside) + uc unobserved) / samples in double, in that order; no sample: uc
+DR_HOST_DEVICE inline double score_colour_value(double cost, double photo, uint32_t samples, uint32_t unobserved, uint32_t outside, double oc, double uc) {
+  if (samples == 0) return uc;
+  return (((cost + photo) + oc * (double)outside) + uc * (double)unobserved) / (double)samples;
+}
+// k_search_points_colour on the host: search_points_host's arrays and per padded grid position the frame intensity yf --
+// track_intensity of the sample's own pixel, 0 where the position is no sample
+struct SearchColourPoints {
+  SearchPoints p;
+  std::vector<float> yf;
+};
+inline void search_points_colour_host(const LocateGrid &lg, double vs, const unsigned char *bgr, const float *depth, SearchColourPoints &p) {
+  search_points_host(lg, vs, depth, p.p);
+  const long total = locate_positions(lg);
+  p.yf.assign(p.p.flag.size(), 0.0f);
+  for (long n = 0; n < total; ++n)
+    if (p.p.flag[n]) p.yf[n] = track_intensity(bgr + 3 * locate_offset(lg, (int)n));
+}
+// k_search_score_colour's wave on the host: score_candidate_host with a second double per lane and a second fold accumulator,
+// both reduced in the one order
+template <class Fetch>
+inline void score_colour_candidate_host(long groups, const SearchColourPoints &p, Fetch &&fetch, const AlignEval &e, double lambda, double pc, double &cost, double &photo,
+                                        uint32_t counts[4]) {
+  auto butterfly = [](double x[64]) {
+    for (int off = 32; off > 0; off >>= 1) {
+      double y[64];
+      for (int l = 0; l < 64; ++l) y[l] = x[l] + x[l ^ off];
+      memcpy(x, y, sizeof y);
+    }
+  };
+  double fold[64], foldp[64];
+  for (int l = 0; l < 64; ++l) fold[l] = foldp[l] = 0.0;
+  counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  for (long i = 0; i < groups; ++i) {
+    double x[64], xp[64];
+    for (int l = 0; l < 64; ++l) {
+      x[l] = xp[l] = 0.0;
+      for (int k = 0; k < 8; ++k) {
+        const size_t n = (size_t)(512 * i + l + 64 * k);
+        if (!p.p.flag[n]) continue;
+        ++counts[0];
+        const int r = score_colour_point(e, lambda, pc, p.p.g[3 * n], p.p.g[3 * n + 1], p.p.g[3 * n + 2], p.yf[n], fetch, x[l], xp[l]);
+        ++counts[r == 1 ? 1 : r == 0 ? 2 : 3];
+      }
+    }
+    butterfly(x);
+    butterfly(xp);
+    fold[i & 63] = fold[i & 63] + x[0];
+    foldp[i & 63] = foldp[i & 63] + xp[0];
+  }
+  butterfly(fold);
+  butterfly(foldp);
+  cost = fold[0];
+  photo = foldp[0];
+}
+// drf_score_colour_poses / the score stage of drf_search_colour_frame on the CPU: candidates [0, n) of the lattice over the table
+template <class Fetch>
+inline void score_colour_candidates_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, Fetch &&fetch, const SearchLattice &L, const double *table,
+                                         size_t n, const ScoreColourOpt &o, float voxel_size, double *cost, double *photo, uint32_t *counts, double *score) {
+  SearchColourPoints p;
+  search_points_colour_host(lg, (double)voxel_size, bgr, depth, p);
+  for (size_t c = 0; c < n; ++c) {
+    const AlignEval e = score_eval(search_candidate(L, table, 0, c), o.s, (double)voxel_size);
+    score_colour_candidate_host(locate_groups(lg), p, fetch, e, o.lambda, o.pc, cost[c], photo[c], counts + 4 * c);
+    score[c] = score_colour_value(cost[c], photo[c], counts[4 * c], counts[4 * c + 2], counts[4 * c + 3], o.s.oc, o.s.uc);
+  }
+}
+// What follows the colour score, over track(p16, res), locate(p16, res) and rescore(poses16, n, final_score, final_photo):
+// search_refine's entries and stages -- the tracking is the pyramid's with the frame's bgr -- then, when the refinement has ended,
+// the located float poses of the qualifying entries scored once more by the colour score, in rank order, in one call of rescore.
+// The winner has the smallest final_score among the qualifying, ties to the better rank; accept_valid > 0 ends the refinement at
+// the first qualifying entry whose located valid >= accept_valid * samples, and that entry wins.  An entry that does not qualify
+// keeps final_score = final_photo = 0.  None qualifies, or score_only: as search_refine.
+template <class Track, class Locate, class Rescore>
+inline void search_colour_refine(const SearchColourOpt &o, const double *table, const std::vector<size_t> &sel, const double *cost, const double *photo,
+                                 const uint32_t *counts, const double *score, size_t n_candidates, float voxel_size, Track &&track, Locate &&locate, Rescore &&rescore,
+                                 float pose16_out[16], drf_search_colour_result_t &res) {
+  memset(&res, 0, sizeof res);
+  res.n_candidates = n_candidates;
+  res.n_entries = (int)sel.size();
+  res.winner = -1;
+  float p16[DRF_SEARCH_MAX_TOP][16];
+  for (size_t k = 0; k < sel.size(); ++k) {
+    drf_search_colour_entry_t &en = res.entries[k];
+    const size_t c = sel[k];
+    en.index = c; en.score = score[c]; en.cost = cost[c]; en.photo = photo[c];
+    for (int i = 0; i < 4; ++i) en.counts[i] = counts[4 * c + i];
+    en.track_status = en.locate_status = -1;
+    locate_pose16(search_candidate(o.s.L, table, 0, c), voxel_size, p16[k]);
+    for (int i = 0; i < 16; ++i) en.T[i] = (double)p16[k][i];
+  }
+  memcpy(pose16_out, p16[0], sizeof p16[0]);
+  if (o.s.score_only) { res.status = DRF_ALIGN_MAX_ITERS; res.winner = 0; return; }
+  res.status = DRF_ALIGN_LOST;
+  int accepted = -1, qual[DRF_SEARCH_MAX_TOP], nq = 0;
+  for (size_t k = 0; k < sel.size(); ++k) {
+    drf_search_colour_entry_t &en = res.entries[k];
+    drf_align_result_t r;
+    track(p16[k], r);
+    ++res.refined;
+    en.track_status = r.status;
+    memcpy(en.T, r.T, sizeof en.T);
+    if (r.status > DRF_ALIGN_MAX_ITERS) continue;
+    float t16[16];
+    for (int i = 0; i < 16; ++i) t16[i] = (float)r.T[i];
+    locate(t16, r);
+    en.locate_status = r.status;
+    en.samples = r.samples; en.valid = r.valid; en.located_cost = r.cost;
+    memcpy(en.T, r.T, sizeof en.T);
+    if (r.status > DRF_ALIGN_MAX_ITERS) continue;
+    qual[nq++] = (int)k;
+    if (o.s.accept_valid > 0.0 && (double)en.valid >= o.s.accept_valid * (double)en.samples) { accepted = (int)k; break; }
+  }
+  if (nq == 0) return;
+  float q16[DRF_SEARCH_MAX_TOP][16];
+  double fs[DRF_SEARCH_MAX_TOP], fp[DRF_SEARCH_MAX_TOP];
+  for (int j = 0; j < nq; ++j)
+    for (int i = 0; i < 16; ++i) q16[j][i] = (float)res.entries[qual[j]].T[i];
+  rescore(&q16[0][0], (size_t)nq, fs, fp);
+  for (int j = 0; j < nq; ++j) {
+    drf_search_colour_entry_t &en = res.entries[qual[j]];
+    en.final_score = fs[j]; en.final_photo = fp[j];
+    if (res.winner < 0 || en.final_score < res.entries[res.winner].final_score) res.winner = qual[j];
+  }
+  if (accepted >= 0) res.winner = accepted;
+  res.status = res.entries[res.winner].locate_status;
+  for (int i = 0; i < 16; ++i) pose16_out[i] = (float)res.entries[res.winner].T[i];
+}
+
 }  // namespace dr

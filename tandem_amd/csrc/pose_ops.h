@@ -233,6 +233,7 @@ class FrameTracker {
     void reset() { memset(stats, 0, sizeof stats); memset(level, 0, sizeof level); }
   };
   TrackSide &geometric() { return tk_; }  // drf_search_frame tracks its candidates on the side of drf_track_frame
+  TrackSide &pyramid() { return tp_; }    // drf_search_colour_frame on the side of drf_track_pyramid_frame
   // The body of every *_frame call: the frame reduced once to every level above 0, then track_pyramid_schedule over track_loop;
   // po.levels = 1 is the single-level call.  r: level 0's result; last: the counters of its last evaluation.
   void track_levels(const char *who, TrackSide &s, bool colour, const TrackPyramidOpt &po, const FramePair &frame, const float *pose16, drf_align_result_t &r,

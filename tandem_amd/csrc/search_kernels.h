@@ -72,3 +72,81 @@ __global__ __launch_bounds__(256) void k_search_score(const FusionDev d, const d
     out[local] = o;
   }
 }
+
+// ---- the score with colour (drf_score_colour_poses / drf_search_colour_frame; the rule: pose_host.h score_colour_point; DESIGN.md
+// §7c "Searching with colour").  Two kernels beside the two above, which keep the instructions they have.
+
+// k_search_points plus yf: the frame intensity of the sample's own pixel (track_intensity of its BGR bytes), 0 where the position
+// is no sample.  No candidate then reads the colour image.
+__global__ __launch_bounds__(256) void k_search_points_colour(const float *__restrict__ depth, const unsigned char *__restrict__ bgr, const LocateGrid lg, double vs,
+                                                              int total, int padded, double *__restrict__ g, unsigned char *__restrict__ flag, float *__restrict__ yf) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= padded) return;
+  double p[3] = {0.0, 0.0, 0.0};
+  const bool s = n < total && locate_pixel(lg, vs, n, depth, p);
+  g[3 * (size_t)n] = s ? p[0] : 0.0; g[3 * (size_t)n + 1] = s ? p[1] : 0.0; g[3 * (size_t)n + 2] = s ? p[2] : 0.0;
+  flag[n] = s ? 1 : 0;
+  yf[n] = s ? track_intensity(bgr + 3 * locate_offset(lg, n)) : 0.0f;
+}
+
+struct SearchColourOut {  // 40 bytes per candidate of a chunk
+  double cost, photo;
+  unsigned counts[4];  // samples, valid, unobserved, outside
+  double score;
+};
+
+// k_search_score with score_colour_point: its text repeated, not routed through a shared body, for the reason k_map_locate_staged
+// gives -- k_search_score is held to the instructions it has.  Two doubles per lane and two fold accumulators; a group no lane of
+// which added a term is skipped for both sums (both partials are +0.0); the last butterfly folds both.  Lane 0 writes the
+// candidate's 40 bytes with plain stores.  No atomics, no LDS, no second launch; the pose is wave-uniform; the map is only read.
+__global__ __launch_bounds__(256) void k_search_score_colour(const FusionDev d, const double *__restrict__ g, const unsigned char *__restrict__ flag,
+                                                             const float *__restrict__ yf, int groups, const double *__restrict__ table, const SearchLattice lat,
+                                                             size_t first, size_t table_first, int n, const ScoreColourOpt so, double vs,
+                                                             SearchColourOut *__restrict__ out) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int local = blockIdx.x * 4 + wave;
+  if (local >= n) return;
+  const AlignEval e = score_eval(search_candidate(lat, table, table_first, first + (size_t)local), so.s, vs);
+  double fold = 0.0, foldp = 0.0;
+  unsigned ns = 0, nv = 0, nu = 0;
+  LocateFetch fetch(d);
+#pragma unroll 1
+  for (int i = 0; i < groups; ++i) {
+    double x = 0.0, xp = 0.0;
+    bool added = false;
+#pragma unroll 1
+    for (int k = 0; k < 8; ++k) {
+      const size_t p = (size_t)(512 * i + lane + 64 * k);
+      if (!flag[p]) continue;
+      ++ns;
+      fetch.corner = 0;
+      const int r = score_colour_point(e, so.lambda, so.pc, g[3 * p], g[3 * p + 1], g[3 * p + 2], yf[p], fetch, x, xp);
+      nv += r == 1 ? 1u : 0u;
+      nu += r == 0 ? 1u : 0u;
+      added = added || r == 1;
+    }
+    if (!__any(added)) continue;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      x = x + __shfl_xor(x, off);
+      xp = xp + __shfl_xor(xp, off);
+    }
+    if (lane == (i & 63)) {
+      fold = fold + x;
+      foldp = foldp + xp;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    fold = fold + __shfl_xor(fold, off);
+    foldp = foldp + __shfl_xor(foldp, off);
+    ns += __shfl_xor(ns, off); nv += __shfl_xor(nv, off); nu += __shfl_xor(nu, off);
+  }
+  if (lane == 0) {
+    SearchColourOut o;
+    o.cost = fold; o.photo = foldp;
+    o.counts[0] = ns; o.counts[1] = nv; o.counts[2] = nu; o.counts[3] = ns - nv - nu;
+    o.score = score_colour_value(fold, foldp, ns, nu, ns - nv - nu, so.s.oc, so.s.uc);
+    out[local] = o;
+  }
+}

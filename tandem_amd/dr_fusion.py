@@ -62,6 +62,12 @@ class SearchResult(collections.namedtuple("SearchResult", "T32 status winner ref
     __slots__ = ()
 
 
+class SearchColourEntry(collections.namedtuple("SearchColourEntry", SearchEntry._fields + ("photo", "final_score", "final_photo"))):
+    """drf_search_colour_entry_t: SearchEntry's fields (score is the colour score), photo of the score stage, and final_score /
+    final_photo: the colour score of the located float pose (0 for an entry that did not qualify)."""
+    __slots__ = ()
+
+
 def pose_rotations(yaw_deg=(0.0,), pitch_deg=(0.0,), roll_deg=(0.0,)):
     """The rotations of a search lattice as search_frame takes them: an (n, 9) float64 array, one row-major matrix
     Ry(yaw) Rx(pitch) Rz(roll) per combination, yaw outermost and roll innermost -- turns about the WORLD axes y, x and z.  The one
@@ -550,11 +556,63 @@ class DrFusion:
         return res
 
     def search_stats(self):
-        """Last score_poses / search_frame: (candidates, grid positions, samples, chunks, renders and system evaluations of the
+        """Last score_poses / search_frame or their colour forms: (candidates, grid positions, samples, chunks, renders and system evaluations of the
         refinement, device bytes held by the score stage, blocks in the host store at the call)."""
         out = (C.c_uint64 * 8)()
         check(self._L.drf_search_stats(self._h, out))
         return tuple(int(v) for v in out)
+
+    # ---- searching with colour (include/dr_mi355x.h drf_search_colour_frame, DESIGN.md "Searching with colour") ----
+    def score_colour_poses(self, bgr, depth, poses, **opt):
+        """score_poses with the appearance term from the voxel colours: the frame's colour image (H*W*3 uint8 BGR, as
+        IntegrateScanAsync takes it) beside its depth, both on the host or both integer device pointers.  Returns (cost, photo,
+        counts, score): cost and counts are score_poses' bit for bit, photo (n,) float64 is the capped, Huber-weighted sum of the
+        squared intensity differences between the map's trilinear colour and the frame at the valid samples, and score carries both.
+        opt: the fields of drf_score_options_t, photo_weight and photo_cap."""
+        dev, args, keep = self._track_images([(np.uint8, 3, bgr), (np.float32, 1, depth)])
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 16)
+        n = len(poses)
+        o = None
+        if opt:
+            opt = dict(opt)
+            w, cap = opt.pop("photo_weight", 0.0), opt.pop("photo_cap", 0.0)
+            o = _lib.ScoreColourOptions(self._options(_lib.ScoreOptions, "score", opt) or _lib.ScoreOptions(), w, cap)
+        cost, photo, counts, score = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros((n, 4), np.uint32), np.zeros(n, np.float64)
+        call = self._L.drf_score_colour_poses_device if dev else self._L.drf_score_colour_poses
+        check(call(self._h, *args, fptr(poses), n, C.byref(o) if o else None, cost.ctypes.data_as(_lib.f64p), photo.ctypes.data_as(_lib.f64p),
+                   counts.ctypes.data_as(C.POINTER(C.c_uint32)), score.ctypes.data_as(_lib.f64p)))
+        return cost, photo, counts, score
+
+    def search_colour_frame(self, bgr, depth, anchors, rotations=None, half=(0, 0, 0), trans_step=0.0, top_k=0, score_only=False, accept_valid=0.0, photo_weight=0.0,
+                            photo_cap=0.0, score=None, track=None, levels=0, coarse_renders=0, track_photo_weight=0.0, locate=None, all_scores=False,
+                            raise_on_failure=True):
+        """search_frame where geometry alone is ambiguous -- one wall, a corridor: the candidates are scored with the appearance
+        term (score_colour_poses), the top_k smallest colour scores are tracked with the frame's colour image (track_pyramid_frame's
+        rule: track, levels, coarse_renders, track_photo_weight) and located, and the entry whose located pose has the smallest
+        colour score (final_score) wins.  bgr and depth both on the host or both integer device pointers.  Returns a SearchResult
+        whose entries are SearchColourEntry; one that found no pose raises AlignError unless raise_on_failure is false."""
+        dev, args, keep = self._track_images([(np.uint8, 3, bgr), (np.float32, 1, depth)])
+        anchors = np.ascontiguousarray(anchors, np.float32).reshape(-1, 16)
+        rot = np.ascontiguousarray(np.eye(3).reshape(1, 9) if rotations is None else rotations, np.float64).reshape(-1, 9)
+        so = self._options(_lib.ScoreOptions, "score", score or {}) or _lib.ScoreOptions()
+        o = _lib.SearchColourOptions(_lib.SearchOptions(score=so, trans_step=trans_step, half=(C.c_int * 3)(*[int(v) for v in half]), top_k=int(top_k),
+                                                        score_only=int(bool(score_only)), accept_valid=float(accept_valid)), photo_weight, photo_cap)
+        to, lo = self._track_pyramid_options(levels, coarse_renders, track_photo_weight, track or {}), self._options(_lib.LocateOptions, "locate", locate or {})
+        n = len(anchors) * len(rot) * int(np.prod([2 * int(v) + 1 for v in half]))
+        scores = np.zeros(max(n, 1), np.float64) if all_scores and 0 < n <= 1 << 24 else None
+        T32, r = np.zeros(16, np.float32), _lib.SearchColourResultStruct()
+        call = self._L.drf_search_colour_frame_device if dev else self._L.drf_search_colour_frame
+        check(call(self._h, *args, fptr(anchors), len(anchors), rot.ctypes.data_as(_lib.f64p), len(rot), C.byref(o), C.byref(to) if to else None,
+                   C.byref(lo) if lo else None, fptr(T32), C.byref(r), scores.ctypes.data_as(_lib.f64p) if scores is not None else None))
+        entries = [SearchColourEntry(index=int(e.index), score=float(e.score), cost=float(e.cost), counts=tuple(int(v) for v in e.counts),
+                                     track_status=int(e.track_status), locate_status=int(e.locate_status), samples=int(e.samples), valid=int(e.valid),
+                                     located_cost=float(e.located_cost), T=np.array(e.T, np.float64).reshape(4, 4), photo=float(e.photo),
+                                     final_score=float(e.final_score), final_photo=float(e.final_photo)) for e in r.entries[:r.n_entries]]
+        res = SearchResult(T32=T32.reshape(4, 4), status=int(r.status), winner=int(r.winner), refined=int(r.refined), n_candidates=int(r.n_candidates),
+                           entries=entries, scores=scores)
+        if raise_on_failure and res.status in (ALIGN_DEGENERATE, ALIGN_LOST):
+            raise AlignError(res, self._L.dr_last_error().decode(errors="replace"))
+        return res
 
     # ---- tracking with colour (include/dr_mi355x.h drf_track_colour_frame, DESIGN.md "Tracking with colour") ----
     @staticmethod

@@ -167,6 +167,22 @@ public:
     if (result) *result = res;
     return res.status;
   }
+  // ScorePoses with the appearance term from the voxel colours (dr_mi355x.h drf_score_colour_poses): bgr is the frame's colour image
+  // as IntegrateScanAsync takes it; photo[n] is the colour sum, score carries both.
+  void ScoreColourPoses(uint8_t const *bgr, float const *depth, float const *poses16, size_t n, double *score, double *cost = nullptr, double *photo = nullptr,
+                        uint32_t *counts = nullptr, drf_score_colour_options_t const *opt = nullptr) {
+    check(drf_score_colour_poses(impl, bgr, depth, poses16, n, opt, cost, photo, counts, score));
+  }
+  // SearchDepthFrame where geometry alone is ambiguous -- one wall, a corridor (dr_mi355x.h drf_search_colour_frame): selection and
+  // winner by the colour score, tracking with the frame's colour image (the pyramid's rule).  Returns the status, DRF_ALIGN_*.
+  int SearchColourFrame(uint8_t const *bgr, float const *depth, float const *anchors16, size_t n_anchors, double const *rotations9, size_t n_rot, float *pose16_out,
+                        drf_search_colour_options_t const *opt = nullptr, drf_search_colour_result_t *result = nullptr,
+                        drf_track_pyramid_options_t const *track_opt = nullptr, drf_locate_options_t const *locate_opt = nullptr) {
+    drf_search_colour_result_t res;
+    check(drf_search_colour_frame(impl, bgr, depth, anchors16, n_anchors, rotations9, n_rot, opt, track_opt, locate_opt, pose16_out, &res, nullptr));
+    if (result) *result = res;
+    return res.status;
+  }
   // DRF_LOCATE_MAP: LocateDepthFrame reads resident and host-stored blocks together, without moving one (capacity 0 = the default
   // staging); DRF_LOCATE_RESIDENT, the default: the pool only
   void SetLocateScope(int scope, size_t capacity = 0) { check(drf_set_locate_scope(impl, scope, capacity)); }
