@@ -969,7 +969,7 @@ int drf_search_stats(drf_t *h, uint64_t out[8]);
  * already loads it; these calls keep it.  drf_score_colour_poses is drf_score_poses with a second sum, photo, and
  * drf_search_colour_frame is drf_search_frame selecting on the colour score, tracking with the frame's colour image and picking the
  * winner by the colour score of the located poses.  The geometric calls stay as they are, for frames without colour.
- * The rule (pose_host.h score_colour_point, the one text the host and k_search_score_colour compile; + - * / floor):
+ * The rule (pose_host.h score_sample with colour, the one text the host and k_search_score_colour compile; + - * / floor):
  *   sample    drf_score_poses', to the letter, up to and including cost = cost + (w r) r.  A valid sample goes on:
  *   y[c]      ((float)c0 + (float)c1) + (float)c2 of corner c, c0, c1, c2 = bits 0-7, 8-15, 16-23 of the voxel's second word (its
  *             stored B, G, R): a whole number in 0..765, the intensity of drf_track_colour_*.

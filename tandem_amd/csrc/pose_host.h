@@ -928,10 +928,14 @@ inline void track_pyramid_frame_host(const LocateGrid &lg0, const unsigned char 
 // with s_src = 0, word for word up to phi -- grid, sample test, point, q, corners, trilinear fp32 phi, the three codes, r, Huber's w --
 // and keeps acc[27] alone.  Stated once, here; the header of the C ABI restates it.  Compiled by g++ and by hipcc (k_search_points,
 // k_search_score), both without contraction; + - * / and floor only.  No trigonometry: rotations are data.
+// The colour family (ScoreColourOpt, SearchColourOpt, below) runs the same text: what is written once for both is a template over
+// the options, which say their family (colour) and hand out the part the other family consists of (geo, search, score).
 struct ScoreOpt {  // drf_score_options_t with its defaults resolved
+  static constexpr bool colour = false;
   int step, min_weight;
   float band, huber;
   double oc, uc;  // voxels per OUTSIDE / UNOBSERVED sample
+  DR_HOST_DEVICE const ScoreOpt &geo() const { return *this; }
 };
 // null: all defaults.  Returns null, or which option is negative or not finite
 inline const char *score_options(const drf_score_options_t *opt, float truncation_distance, float voxel_size, ScoreOpt &o) {
@@ -951,7 +955,7 @@ inline const char *score_options(const drf_score_options_t *opt, float truncatio
   o.uc = u.unobserved_cost != 0.0f ? (double)u.unobserved_cost : 2.0 * o.oc;
   return nullptr;
 }
-// what score_point reads of an AlignEval: the pose, huber, vs, band, min_weight (there is no centre: nothing turns)
+// what score_sample reads of an AlignEval: the pose, huber, vs, band, min_weight (there is no centre: nothing turns)
 DR_HOST_DEVICE inline AlignEval score_eval(const MapMotion &m, const ScoreOpt &o, double vs) {
   AlignEval e;
   e.m = m;
@@ -960,10 +964,14 @@ DR_HOST_DEVICE inline AlignEval score_eval(const MapMotion &m, const ScoreOpt &o
   e.band = o.band; e.min_weight = o.min_weight;
   return e;
 }
-// One sample at the camera-frame point g: align_point<true> with s_src = 0 up to phi, its codes (0 UNOBSERVED, 2 OUTSIDE, 1 valid),
-// and of its sums the last: cost = cost + (w r) r.
-template <class Fetch>
-DR_HOST_DEVICE inline int score_point(const AlignEval &e, double g0, double g1, double g2, Fetch &&fetch, double &cost) {
+// One sample at the camera-frame point g, the one text of both families: align_point<true> with s_src = 0 up to phi, its codes
+// (0 UNOBSERVED, 2 OUTSIDE, 1 valid), and of its sums the last: cost = cost + (w r) r.  With colour (Opt::colour; yf is the frame's
+// intensity at the sample) the colour bytes of the eight corners are kept, and a valid sample adds the colour term behind the
+// geometric one: y[c] = the intensity of corner c's three bytes (bits 0-7, 8-15, 16-23 of its second word), Ym their fp32 trilinear
+// interpolant in phi's stages and order with the same f, rp = lambda (Ym - yf) in double, Huber's weight with the geometric huber,
+// the term capped at pc.  Without colour o, yf and photo are not touched.
+template <class Opt, class Fetch>
+DR_HOST_DEVICE inline int score_sample(const AlignEval &e, const Opt &o, double g0, double g1, double g2, float yf, Fetch &&fetch, double &cost, double &photo) {
   int b[3];
   float f[3];
   DR_UNROLL
@@ -975,12 +983,14 @@ DR_HOST_DEVICE inline int score_point(const AlignEval &e, double g0, double g1, 
     f[k] = (float)(q - fl);
   }
   float s[8];  // index 4 cx + 2 cy + cz
+  [[maybe_unused]] uint32_t col[8];
   DR_UNROLL
   for (int c = 0; c < 8; ++c) {
     uint32_t v[2];
     fetch(b[0] + (c >> 2), b[1] + ((c >> 1) & 1), b[2] + (c & 1), v);
     if ((int)(v[1] >> 24) < e.min_weight) return 0;
     memcpy(&s[c], &v[0], 4);
+    if constexpr (Opt::colour) col[c] = v[1];
   }
   float ez[4];  // index 2 cx + cy
   DR_UNROLL
@@ -995,9 +1005,32 @@ DR_HOST_DEVICE inline int score_point(const AlignEval &e, double g0, double g1, 
   const double a = r < 0.0 ? -r : r;
   const double w = a <= e.huber ? 1.0 : e.huber / a;
   cost = cost + (w * r) * r;
+  if constexpr (Opt::colour) {
+    float y[8];
+    DR_UNROLL
+    for (int c = 0; c < 8; ++c) y[c] = ((float)(col[c] & 255u) + (float)((col[c] >> 8) & 255u)) + (float)((col[c] >> 16) & 255u);
+    float yz[4];
+    DR_UNROLL
+    for (int c = 0; c < 4; ++c) yz[c] = y[2 * c] + f[2] * (y[2 * c + 1] - y[2 * c]);
+    float yd[2];
+    DR_UNROLL
+    for (int c = 0; c < 2; ++c) yd[c] = yz[2 * c] + f[1] * (yz[2 * c + 1] - yz[2 * c]);
+    const float Ym = yd[0] + f[0] * (yd[1] - yd[0]);
+    const double rp = o.lambda * ((double)Ym - (double)yf);
+    const double app = rp < 0.0 ? -rp : rp;
+    const double wp = app <= e.huber ? 1.0 : e.huber / app;
+    double tp = (wp * rp) * rp;
+    if (tp > o.pc) tp = o.pc;
+    photo = photo + tp;
+  }
   return 1;
 }
-// score = ((cost + oc outside) + uc unobserved) / samples in double, in that order; no sample: uc.  Lower is better.
+// the geometric sample by itself: what tests/cpp/map_search_check.cpp holds to align_point<true>
+template <class Fetch>
+DR_HOST_DEVICE inline int score_point(const AlignEval &e, double g0, double g1, double g2, Fetch &&fetch, double &cost) {
+  double none = 0.0;
+  return score_sample(e, ScoreOpt{}, g0, g1, g2, 0.0f, fetch, cost, none);
+}// score = ((cost + oc outside) + uc unobserved) / samples in double, in that order; no sample: uc.  Lower is better.
 DR_HOST_DEVICE inline double score_value(double cost, uint32_t samples, uint32_t unobserved, uint32_t outside, double oc, double uc) {
   if (samples == 0) return uc;
   return ((cost + oc * (double)outside) + uc * (double)unobserved) / (double)samples;
@@ -1062,11 +1095,14 @@ inline std::string search_table(const float *anchors16, size_t n_anchors, const 
   return std::string();
 }
 struct SearchOpt {  // drf_search_options_t with its defaults resolved
+  static constexpr bool colour = false;
   ScoreOpt s;
   SearchLattice L;
   int top_k;
   bool score_only;
   double accept_valid;
+  const SearchOpt &search() const { return *this; }
+  const ScoreOpt &score() const { return s; }
 };
 constexpr size_t kSearchMaxCandidates = (size_t)1 << 24;
 // null: all defaults (half = 0 0 0: the anchors turned, not moved).  Returns null, or which option is refused
@@ -1099,63 +1135,6 @@ inline size_t search_count(size_t n_anchors, size_t n_rot, const SearchLattice &
   }
   return n;
 }
-// k_search_points on the host: per grid position of the groups (512 each, the last padded) its point g, locate_pixel's bits, and
-// whether it is a sample
-struct SearchPoints {
-  std::vector<double> g;  // 3 per position
-  std::vector<unsigned char> flag;
-};
-inline void search_points_host(const LocateGrid &lg, double vs, const float *depth, SearchPoints &p) {
-  const long total = locate_positions(lg), padded = 512 * locate_groups(lg);
-  p.g.assign((size_t)padded * 3, 0.0);
-  p.flag.assign((size_t)padded, 0);
-  for (long n = 0; n < total; ++n) p.flag[n] = locate_pixel(lg, vs, (int)n, depth, &p.g[3 * n]) ? 1 : 0;
-}
-// k_search_score's wave on the host: the groups in order, lane l on positions 512 i + l + 64 k, one double per lane, the
-// butterfly, partial i added in ascending i by lane i % 64 from +0.0, the butterfly again.  counts = {samples, valid,
-// unobserved, outside}.  Bit for bit sums[27] and the counts of locate_system_host at the same pose and options.
-template <class Fetch>
-inline void score_candidate_host(long groups, const SearchPoints &p, Fetch &&fetch, const AlignEval &e, double &cost, uint32_t counts[4]) {
-  auto butterfly = [](double x[64]) {
-    for (int off = 32; off > 0; off >>= 1) {
-      double y[64];
-      for (int l = 0; l < 64; ++l) y[l] = x[l] + x[l ^ off];
-      memcpy(x, y, sizeof y);
-    }
-  };
-  double fold[64];
-  for (int l = 0; l < 64; ++l) fold[l] = 0.0;
-  counts[0] = counts[1] = counts[2] = counts[3] = 0;
-  for (long i = 0; i < groups; ++i) {
-    double x[64];
-    for (int l = 0; l < 64; ++l) {
-      x[l] = 0.0;
-      for (int k = 0; k < 8; ++k) {
-        const size_t n = (size_t)(512 * i + l + 64 * k);
-        if (!p.flag[n]) continue;
-        ++counts[0];
-        const int r = score_point(e, p.g[3 * n], p.g[3 * n + 1], p.g[3 * n + 2], fetch, x[l]);
-        ++counts[r == 1 ? 1 : r == 0 ? 2 : 3];
-      }
-    }
-    butterfly(x);
-    fold[i & 63] = fold[i & 63] + x[0];
-  }
-  butterfly(fold);
-  cost = fold[0];
-}
-// drf_score_poses / the score stage of drf_search_frame on the CPU: candidates [0, n) of the lattice over the table
-template <class Fetch>
-inline void score_candidates_host(const LocateGrid &lg, const float *depth, Fetch &&fetch, const SearchLattice &L, const double *table, size_t n, const ScoreOpt &o,
-                                  float voxel_size, double *cost, uint32_t *counts, double *score) {
-  SearchPoints p;
-  search_points_host(lg, (double)voxel_size, depth, p);
-  for (size_t c = 0; c < n; ++c) {
-    const AlignEval e = score_eval(search_candidate(L, table, 0, c), o, (double)voxel_size);
-    score_candidate_host(locate_groups(lg), p, fetch, e, cost[c], counts + 4 * c);
-    score[c] = score_value(cost[c], counts[4 * c], counts[4 * c + 2], counts[4 * c + 3], o.oc, o.uc);
-  }
-}
 // The top_k smallest scores, ties to the lower index, a NaN score behind every number: the indices in rank order
 inline std::vector<size_t> search_select(const double *score, size_t n, int top_k) {
   std::vector<size_t> idx(n);
@@ -1166,55 +1145,6 @@ inline std::vector<size_t> search_select(const double *score, size_t n, int top_
   idx.resize(k);
   return idx;
 }
-// What follows the score stage, over track(p16, res) and locate(p16, res), the *_frame calls' loops from a float pose: the entries
-// of the selected candidates, then each refined in rank order -- tracked from its float pose (locate_pose16 of its (Rd, tv)); if
-// that ends <= MAX_ITERS, located from the tracked pose rounded to float.  An entry QUALIFIES if its locate status is <= MAX_ITERS.
-// accept_valid > 0 ends the refinement at the first qualifying entry whose located valid >= accept_valid * samples: it wins.
-// Otherwise the winner has the greatest located valid among the qualifying, ties to the lower located cost, then the better rank.
-// None qualifies (or score_only): pose16_out is the best-scoring candidate's float pose, status LOST (score_only: MAX_ITERS, winner 0).
-template <class Track, class Locate>
-inline void search_refine(const SearchOpt &o, const double *table, const std::vector<size_t> &sel, const double *cost, const uint32_t *counts,
-                          const double *score, size_t n_candidates, float voxel_size, Track &&track, Locate &&locate, float pose16_out[16], drf_search_result_t &res) {
-  memset(&res, 0, sizeof res);
-  res.n_candidates = n_candidates;
-  res.n_entries = (int)sel.size();
-  res.winner = -1;
-  float p16[DRF_SEARCH_MAX_TOP][16];
-  for (size_t k = 0; k < sel.size(); ++k) {
-    drf_search_entry_t &en = res.entries[k];
-    const size_t c = sel[k];
-    en.index = c; en.score = score[c]; en.cost = cost[c];
-    for (int i = 0; i < 4; ++i) en.counts[i] = counts[4 * c + i];
-    en.track_status = en.locate_status = -1;
-    locate_pose16(search_candidate(o.L, table, 0, c), voxel_size, p16[k]);
-    for (int i = 0; i < 16; ++i) en.T[i] = (double)p16[k][i];
-  }
-  memcpy(pose16_out, p16[0], sizeof p16[0]);
-  if (o.score_only) { res.status = DRF_ALIGN_MAX_ITERS; res.winner = 0; return; }
-  res.status = DRF_ALIGN_LOST;
-  for (size_t k = 0; k < sel.size(); ++k) {
-    drf_search_entry_t &en = res.entries[k];
-    drf_align_result_t r;
-    track(p16[k], r);
-    ++res.refined;
-    en.track_status = r.status;
-    memcpy(en.T, r.T, sizeof en.T);
-    if (r.status > DRF_ALIGN_MAX_ITERS) continue;
-    float t16[16];
-    for (int i = 0; i < 16; ++i) t16[i] = (float)r.T[i];
-    locate(t16, r);
-    en.locate_status = r.status;
-    en.samples = r.samples; en.valid = r.valid; en.located_cost = r.cost;
-    memcpy(en.T, r.T, sizeof en.T);
-    if (r.status > DRF_ALIGN_MAX_ITERS) continue;
-    const drf_search_entry_t *w = res.winner >= 0 ? &res.entries[res.winner] : nullptr;
-    if (!w || en.valid > w->valid || (en.valid == w->valid && en.located_cost < w->located_cost)) res.winner = (int)k;
-    if (o.accept_valid > 0.0 && (double)en.valid >= o.accept_valid * (double)en.samples) { res.winner = (int)k; break; }
-  }
-  if (res.winner < 0) return;
-  res.status = res.entries[res.winner].locate_status;
-  for (int i = 0; i < 16; ++i) pose16_out[i] = (float)res.entries[res.winner].T[i];
-}
 
 // ---- searching with colour (drf_score_colour_poses / drf_search_colour_frame; DESIGN.md §7c "Searching with colour").  The score
 // above is geometric: on one wall every in-plane offset of the lattice scores alike.  Every voxel carries a colour, and the fetch
@@ -1222,9 +1152,11 @@ inline void search_refine(const SearchOpt &o, const double *table, const std::ve
 // per valid sample -- the trilinear model intensity against the frame's pixel -- into a second sum, photo, reduced exactly as cost
 // is.  cost and counts keep drf_score_poses' bits.  Frame and map share their exposure, as for drf_track_colour_*.
 struct ScoreColourOpt {  // drf_score_colour_options_t with its defaults resolved
+  static constexpr bool colour = true;
   ScoreOpt s;
   float photo_weight;  // voxels per intensity unit
   double lambda, pc;   // (double)photo_weight; the most one sample's colour term costs
+  DR_HOST_DEVICE const ScoreOpt &geo() const { return s; }
 };
 // the two colour fields behind a resolved ScoreOpt.  Returns null, or which is negative or not finite
 inline const char *score_photo_options(float photo_weight, float photo_cap, const ScoreOpt &s, ScoreColourOpt &o) {
@@ -1243,94 +1175,54 @@ inline const char *score_colour_options(const drf_score_colour_options_t *opt, f
   return score_photo_options(opt ? opt->photo_weight : 0.0f, opt ? opt->photo_cap : 0.0f, s, o);
 }
 struct SearchColourOpt {  // drf_search_colour_options_t with its defaults resolved
+  static constexpr bool colour = true;
   SearchOpt s;
   ScoreColourOpt c;
+  const SearchOpt &search() const { return s; }
+  const ScoreColourOpt &score() const { return c; }
 };
 inline const char *search_colour_options(const drf_search_colour_options_t *opt, float truncation_distance, float voxel_size, SearchColourOpt &o) {
   if (const char *bad = search_options(opt ? &opt->search : nullptr, truncation_distance, voxel_size, o.s)) return bad;
   return score_photo_options(opt ? opt->photo_weight : 0.0f, opt ? opt->photo_cap : 0.0f, o.s.s, o.c);
-}
-// One sample at the camera-frame point g whose frame intensity is yf: score_point word for word up to cost = cost + (w r) r, the
-// colour bytes of the eight corners kept, and for a valid sample the colour term behind the geometric one: y[c] = the intensity of
-// corner c's three bytes (bits 0-7, 8-15, 16-23 of its second word), Ym their fp32 trilinear interpolant in phi's stages and order
-// with the same f, rp = lambda (Ym - yf) in double, Huber's weight with the geometric huber, the term capped at pc.
-template <class Fetch>
-DR_HOST_DEVICE inline int score_colour_point(const AlignEval &e, double lambda, double pc, double g0, double g1, double g2, float yf, Fetch &&fetch, double &cost,
-                                             double &photo) {
-  int b[3];
-  float f[3];
-  DR_UNROLL
-  for (int k = 0; k < 3; ++k) {
-    const double q = ((e.m.R[3 * k] * g0 + e.m.R[3 * k + 1] * g1) + e.m.R[3 * k + 2] * g2) + e.m.tv[k];
-    if (!(q > -1073741824.0 && q < 1073741824.0)) return 0;
-    const double fl = floor(q);
-    b[k] = (int)fl;
-    f[k] = (float)(q - fl);
-  }
-  float s[8];  // index 4 cx + 2 cy + cz
-  uint32_t col[8];
-  DR_UNROLL
-  for (int c = 0; c < 8; ++c) {
-    uint32_t v[2];
-    fetch(b[0] + (c >> 2), b[1] + ((c >> 1) & 1), b[2] + (c & 1), v);
-    if ((int)(v[1] >> 24) < e.min_weight) return 0;
-    memcpy(&s[c], &v[0], 4);
-    col[c] = v[1];
-  }
-  float ez[4];  // index 2 cx + cy
-  DR_UNROLL
-  for (int c = 0; c < 4; ++c) ez[c] = s[2 * c] + f[2] * (s[2 * c + 1] - s[2 * c]);
-  float d[2];
-  DR_UNROLL
-  for (int c = 0; c < 2; ++c) d[c] = ez[2 * c] + f[1] * (ez[2 * c + 1] - ez[2 * c]);
-  const float phi = d[0] + f[0] * (d[1] - d[0]);
-  const float ap = phi < 0.0f ? -phi : phi;
-  if (!(ap < e.band)) return 2;
-  const double r = (double)phi / e.vs;  // align_point's ((double)phi - (double)s_src) / vs with s_src = 0: the same bits
-  const double a = r < 0.0 ? -r : r;
-  const double w = a <= e.huber ? 1.0 : e.huber / a;
-  cost = cost + (w * r) * r;
-  float y[8];
-  DR_UNROLL
-  for (int c = 0; c < 8; ++c) y[c] = ((float)(col[c] & 255u) + (float)((col[c] >> 8) & 255u)) + (float)((col[c] >> 16) & 255u);
-  float yz[4];
-  DR_UNROLL
-  for (int c = 0; c < 4; ++c) yz[c] = y[2 * c] + f[2] * (y[2 * c + 1] - y[2 * c]);
-  float yd[2];
-  DR_UNROLL
-  for (int c = 0; c < 2; ++c) yd[c] = yz[2 * c] + f[1] * (yz[2 * c + 1] - yz[2 * c]);
-  const float Ym = yd[0] + f[0] * (yd[1] - yd[0]);
-  const double rp = lambda * ((double)Ym - (double)yf);
-  const double app = rp < 0.0 ? -rp : rp;
-  const double wp = app <= e.huber ? 1.0 : e.huber / app;
-  double tp = (wp * rp) * rp;
-  if (tp > pc) tp = pc;
-  photo = photo + tp;
-  return 1;
 }
 // (((cost + photo) + oc outside) + uc unobserved) / samples in double, in that order; no sample: uc
 DR_HOST_DEVICE inline double score_colour_value(double cost, double photo, uint32_t samples, uint32_t unobserved, uint32_t outside, double oc, double uc) {
   if (samples == 0) return uc;
   return (((cost + photo) + oc * (double)outside) + uc * (double)unobserved) / (double)samples;
 }
-// k_search_points_colour on the host: search_points_host's arrays and per padded grid position the frame intensity yf --
-// track_intensity of the sample's own pixel, 0 where the position is no sample
-struct SearchColourPoints {
-  SearchPoints p;
+// either score, by the family of the options
+template <class Opt>
+DR_HOST_DEVICE inline double score_of(const Opt &o, double cost, double photo, uint32_t samples, uint32_t unobserved, uint32_t outside) {
+  if constexpr (Opt::colour) return score_colour_value(cost, photo, samples, unobserved, outside, o.s.oc, o.s.uc);
+  else return score_value(cost, samples, unobserved, outside, o.oc, o.uc);
+}
+
+// ---- what both families run (Opt: ScoreOpt or ScoreColourOpt, SearchOpt or SearchColourOpt)
+// k_search_points(_colour) on the host: per grid position of the groups (512 each, the last padded) its point g, locate_pixel's
+// bits, and whether it is a sample; given bgr, per position also the frame intensity yf -- track_intensity of the sample's own
+// pixel, 0 where the position is no sample.  bgr null (the geometric form): yf is empty.
+struct SearchPoints {
+  std::vector<double> g;  // 3 per position
+  std::vector<unsigned char> flag;
   std::vector<float> yf;
 };
-inline void search_points_colour_host(const LocateGrid &lg, double vs, const unsigned char *bgr, const float *depth, SearchColourPoints &p) {
-  search_points_host(lg, vs, depth, p.p);
-  const long total = locate_positions(lg);
-  p.yf.assign(p.p.flag.size(), 0.0f);
-  for (long n = 0; n < total; ++n)
-    if (p.p.flag[n]) p.yf[n] = track_intensity(bgr + 3 * locate_offset(lg, (int)n));
+inline void search_points_host(const LocateGrid &lg, double vs, const unsigned char *bgr, const float *depth, SearchPoints &p) {
+  const long total = locate_positions(lg), padded = 512 * locate_groups(lg);
+  p.g.assign((size_t)padded * 3, 0.0);
+  p.flag.assign((size_t)padded, 0);
+  p.yf.assign(bgr ? (size_t)padded : 0, 0.0f);
+  for (long n = 0; n < total; ++n) {
+    p.flag[n] = locate_pixel(lg, vs, (int)n, depth, &p.g[3 * n]) ? 1 : 0;
+    if (bgr && p.flag[n]) p.yf[n] = track_intensity(bgr + 3 * locate_offset(lg, (int)n));
+  }
 }
-// k_search_score_colour's wave on the host: score_candidate_host with a second double per lane and a second fold accumulator,
-// both reduced in the one order
-template <class Fetch>
-inline void score_colour_candidate_host(long groups, const SearchColourPoints &p, Fetch &&fetch, const AlignEval &e, double lambda, double pc, double &cost, double &photo,
-                                        uint32_t counts[4]) {
+// k_search_score(_colour)'s wave on the host: the groups in order, lane l on positions 512 i + l + 64 k, per sum (cost; with colour
+// also photo) one double per lane, the butterfly, partial i added in ascending i by lane i % 64 from +0.0, the butterfly again:
+// every sum in the one order.  sums = {cost, photo} (photo untouched without colour), counts = {samples, valid, unobserved,
+// outside}.  cost and counts: bit for bit sums[27] and the counts of locate_system_host at the same pose and options.
+template <class Opt, class Fetch>
+inline void score_candidate_host(long groups, const SearchPoints &p, Fetch &&fetch, const AlignEval &e, const Opt &o, double sums[2], uint32_t counts[4]) {
+  constexpr int NS = Opt::colour ? 2 : 1;
   auto butterfly = [](double x[64]) {
     for (int off = 32; off > 0; off >>= 1) {
       double y[64];
@@ -1338,73 +1230,81 @@ inline void score_colour_candidate_host(long groups, const SearchColourPoints &p
       memcpy(x, y, sizeof y);
     }
   };
-  double fold[64], foldp[64];
-  for (int l = 0; l < 64; ++l) fold[l] = foldp[l] = 0.0;
+  double fold[NS][64];
+  for (int s = 0; s < NS; ++s)
+    for (int l = 0; l < 64; ++l) fold[s][l] = 0.0;
   counts[0] = counts[1] = counts[2] = counts[3] = 0;
   for (long i = 0; i < groups; ++i) {
-    double x[64], xp[64];
+    double x[2][64];
     for (int l = 0; l < 64; ++l) {
-      x[l] = xp[l] = 0.0;
+      x[0][l] = x[1][l] = 0.0;
       for (int k = 0; k < 8; ++k) {
         const size_t n = (size_t)(512 * i + l + 64 * k);
-        if (!p.p.flag[n]) continue;
+        if (!p.flag[n]) continue;
         ++counts[0];
-        const int r = score_colour_point(e, lambda, pc, p.p.g[3 * n], p.p.g[3 * n + 1], p.p.g[3 * n + 2], p.yf[n], fetch, x[l], xp[l]);
+        const int r = score_sample(e, o, p.g[3 * n], p.g[3 * n + 1], p.g[3 * n + 2], Opt::colour ? p.yf[n] : 0.0f, fetch, x[0][l], x[1][l]);
         ++counts[r == 1 ? 1 : r == 0 ? 2 : 3];
       }
     }
-    butterfly(x);
-    butterfly(xp);
-    fold[i & 63] = fold[i & 63] + x[0];
-    foldp[i & 63] = foldp[i & 63] + xp[0];
+    for (int s = 0; s < NS; ++s) {
+      butterfly(x[s]);
+      fold[s][i & 63] = fold[s][i & 63] + x[s][0];
+    }
   }
-  butterfly(fold);
-  butterfly(foldp);
-  cost = fold[0];
-  photo = foldp[0];
+  for (int s = 0; s < NS; ++s) {
+    butterfly(fold[s]);
+    sums[s] = fold[s][0];
+  }
 }
-// drf_score_colour_poses / the score stage of drf_search_colour_frame on the CPU: candidates [0, n) of the lattice over the table
-template <class Fetch>
-inline void score_colour_candidates_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, Fetch &&fetch, const SearchLattice &L, const double *table,
-                                         size_t n, const ScoreColourOpt &o, float voxel_size, double *cost, double *photo, uint32_t *counts, double *score) {
-  SearchColourPoints p;
-  search_points_colour_host(lg, (double)voxel_size, bgr, depth, p);
+// The score calls and the score stage of the searches on the CPU: candidates [0, n) of the lattice over the table.  Without colour
+// bgr is not read and photo not written (both may be null).
+template <class Opt, class Fetch>
+inline void score_candidates_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, Fetch &&fetch, const SearchLattice &L, const double *table, size_t n,
+                                  const Opt &o, float voxel_size, double *cost, double *photo, uint32_t *counts, double *score) {
+  SearchPoints p;
+  search_points_host(lg, (double)voxel_size, Opt::colour ? bgr : nullptr, depth, p);
   for (size_t c = 0; c < n; ++c) {
-    const AlignEval e = score_eval(search_candidate(L, table, 0, c), o.s, (double)voxel_size);
-    score_colour_candidate_host(locate_groups(lg), p, fetch, e, o.lambda, o.pc, cost[c], photo[c], counts + 4 * c);
-    score[c] = score_colour_value(cost[c], photo[c], counts[4 * c], counts[4 * c + 2], counts[4 * c + 3], o.s.oc, o.s.uc);
+    const AlignEval e = score_eval(search_candidate(L, table, 0, c), o.geo(), (double)voxel_size);
+    double sums[2] = {0.0, 0.0};
+    score_candidate_host(locate_groups(lg), p, fetch, e, o, sums, counts + 4 * c);
+    cost[c] = sums[0];
+    if (Opt::colour) photo[c] = sums[1];
+    score[c] = score_of(o, sums[0], sums[1], counts[4 * c], counts[4 * c + 2], counts[4 * c + 3]);
   }
 }
-// What follows the colour score, over track(p16, res), locate(p16, res) and rescore(poses16, n, final_score, final_photo):
-// search_refine's entries and stages -- the tracking is the pyramid's with the frame's bgr -- then, when the refinement has ended,
-// the located float poses of the qualifying entries scored once more by the colour score, in rank order, in one call of rescore.
-// The winner has the smallest final_score among the qualifying, ties to the better rank; accept_valid > 0 ends the refinement at
-// the first qualifying entry whose located valid >= accept_valid * samples, and that entry wins.  An entry that does not qualify
-// keeps final_score = final_photo = 0.  None qualifies, or score_only: as search_refine.
-template <class Track, class Locate, class Rescore>
-inline void search_colour_refine(const SearchColourOpt &o, const double *table, const std::vector<size_t> &sel, const double *cost, const double *photo,
-                                 const uint32_t *counts, const double *score, size_t n_candidates, float voxel_size, Track &&track, Locate &&locate, Rescore &&rescore,
-                                 float pose16_out[16], drf_search_colour_result_t &res) {
+// What follows the score stage of either search, over track(p16, res) and locate(p16, res), the *_frame calls' loops from a float
+// pose (with colour the tracking is the pyramid's with the frame's bgr): the entries of the selected candidates (photo: with colour
+// only), then each refined in rank order -- tracked from its float pose (locate_pose16 of its (Rd, tv)); if that ends <= MAX_ITERS,
+// located from the tracked pose rounded to float.  An entry QUALIFIES if its locate status is <= MAX_ITERS.  accept_valid > 0 ends
+// the refinement at the first qualifying entry whose located valid >= accept_valid * samples: it wins.  Otherwise the winner is
+// winner(res, qual, nq)'s, the family's rule over the nq >= 1 qualifying entries in rank order (search_winner,
+// search_colour_winner; it runs in either case).  None qualifies (or score_only): pose16_out is the best-scoring candidate's float
+// pose, status LOST (score_only: MAX_ITERS, winner 0).
+template <class Opt, class Result, class Track, class Locate, class Winner>
+inline void search_refine(const Opt &opt, const double *table, const std::vector<size_t> &sel, const double *cost, const double *photo, const uint32_t *counts,
+                          const double *score, size_t n_candidates, float voxel_size, Track &&track, Locate &&locate, Winner &&winner, float pose16_out[16], Result &res) {
+  const SearchOpt &o = opt.search();
   memset(&res, 0, sizeof res);
   res.n_candidates = n_candidates;
   res.n_entries = (int)sel.size();
   res.winner = -1;
   float p16[DRF_SEARCH_MAX_TOP][16];
   for (size_t k = 0; k < sel.size(); ++k) {
-    drf_search_colour_entry_t &en = res.entries[k];
+    auto &en = res.entries[k];
     const size_t c = sel[k];
-    en.index = c; en.score = score[c]; en.cost = cost[c]; en.photo = photo[c];
+    en.index = c; en.score = score[c]; en.cost = cost[c];
+    if constexpr (Opt::colour) en.photo = photo[c];
     for (int i = 0; i < 4; ++i) en.counts[i] = counts[4 * c + i];
     en.track_status = en.locate_status = -1;
-    locate_pose16(search_candidate(o.s.L, table, 0, c), voxel_size, p16[k]);
+    locate_pose16(search_candidate(o.L, table, 0, c), voxel_size, p16[k]);
     for (int i = 0; i < 16; ++i) en.T[i] = (double)p16[k][i];
   }
   memcpy(pose16_out, p16[0], sizeof p16[0]);
-  if (o.s.score_only) { res.status = DRF_ALIGN_MAX_ITERS; res.winner = 0; return; }
+  if (o.score_only) { res.status = DRF_ALIGN_MAX_ITERS; res.winner = 0; return; }
   res.status = DRF_ALIGN_LOST;
   int accepted = -1, qual[DRF_SEARCH_MAX_TOP], nq = 0;
   for (size_t k = 0; k < sel.size(); ++k) {
-    drf_search_colour_entry_t &en = res.entries[k];
+    auto &en = res.entries[k];
     drf_align_result_t r;
     track(p16[k], r);
     ++res.refined;
@@ -1419,22 +1319,64 @@ inline void search_colour_refine(const SearchColourOpt &o, const double *table, 
     memcpy(en.T, r.T, sizeof en.T);
     if (r.status > DRF_ALIGN_MAX_ITERS) continue;
     qual[nq++] = (int)k;
-    if (o.s.accept_valid > 0.0 && (double)en.valid >= o.s.accept_valid * (double)en.samples) { accepted = (int)k; break; }
+    if (o.accept_valid > 0.0 && (double)en.valid >= o.accept_valid * (double)en.samples) { accepted = (int)k; break; }
   }
   if (nq == 0) return;
+  res.winner = winner(res, qual, nq);
+  if (accepted >= 0) res.winner = accepted;
+  res.status = res.entries[res.winner].locate_status;
+  for (int i = 0; i < 16; ++i) pose16_out[i] = (float)res.entries[res.winner].T[i];
+}
+// drf_search_frame's winner: the greatest located valid among the qualifying, ties to the lower located cost, then the better rank
+inline int search_winner(const drf_search_result_t &res, const int *qual, int nq) {
+  int w = qual[0];
+  for (int j = 1; j < nq; ++j) {
+    const drf_search_entry_t &en = res.entries[qual[j]], &best = res.entries[w];
+    if (en.valid > best.valid || (en.valid == best.valid && en.located_cost < best.located_cost)) w = qual[j];
+  }
+  return w;
+}
+// drf_search_colour_frame's, over rescore(poses16, n, final_score, final_photo): the located float poses of the qualifying entries
+// are scored once more by the colour score, in rank order, in one call of rescore; the smallest final_score wins, ties to the
+// better rank.  An entry that does not qualify keeps final_score = final_photo = 0.
+template <class Rescore>
+inline int search_colour_winner(drf_search_colour_result_t &res, const int *qual, int nq, Rescore &&rescore) {
   float q16[DRF_SEARCH_MAX_TOP][16];
   double fs[DRF_SEARCH_MAX_TOP], fp[DRF_SEARCH_MAX_TOP];
   for (int j = 0; j < nq; ++j)
     for (int i = 0; i < 16; ++i) q16[j][i] = (float)res.entries[qual[j]].T[i];
   rescore(&q16[0][0], (size_t)nq, fs, fp);
+  int w = qual[0];
   for (int j = 0; j < nq; ++j) {
     drf_search_colour_entry_t &en = res.entries[qual[j]];
     en.final_score = fs[j]; en.final_photo = fp[j];
-    if (res.winner < 0 || en.final_score < res.entries[res.winner].final_score) res.winner = qual[j];
+    if (en.final_score < res.entries[w].final_score) w = qual[j];
   }
-  if (accepted >= 0) res.winner = accepted;
-  res.status = res.entries[res.winner].locate_status;
-  for (int i = 0; i < 16; ++i) pose16_out[i] = (float)res.entries[res.winner].T[i];
+  return w;
+}
+// The two families by the names and argument lists they had before they were one text, each one call of it: what the host checks
+// (tests/cpp/map_search_check.cpp, map_search_colour_check.cpp) call, so that they hold the shared text to the unchanged tests.
+template <class Fetch>
+inline void score_candidates_host(const LocateGrid &lg, const float *depth, Fetch &&fetch, const SearchLattice &L, const double *table, size_t n, const ScoreOpt &o,
+                                  float voxel_size, double *cost, uint32_t *counts, double *score) {
+  score_candidates_host(lg, nullptr, depth, fetch, L, table, n, o, voxel_size, cost, nullptr, counts, score);
+}
+template <class Fetch>
+inline void score_colour_candidates_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, Fetch &&fetch, const SearchLattice &L, const double *table,
+                                         size_t n, const ScoreColourOpt &o, float voxel_size, double *cost, double *photo, uint32_t *counts, double *score) {
+  score_candidates_host(lg, bgr, depth, fetch, L, table, n, o, voxel_size, cost, photo, counts, score);
+}
+template <class Track, class Locate>
+inline void search_refine(const SearchOpt &o, const double *table, const std::vector<size_t> &sel, const double *cost, const uint32_t *counts, const double *score,
+                          size_t n_candidates, float voxel_size, Track &&track, Locate &&locate, float pose16_out[16], drf_search_result_t &res) {
+  search_refine(o, table, sel, cost, nullptr, counts, score, n_candidates, voxel_size, track, locate, search_winner, pose16_out, res);
+}
+template <class Track, class Locate, class Rescore>
+inline void search_colour_refine(const SearchColourOpt &o, const double *table, const std::vector<size_t> &sel, const double *cost, const double *photo,
+                                 const uint32_t *counts, const double *score, size_t n_candidates, float voxel_size, Track &&track, Locate &&locate, Rescore &&rescore,
+                                 float pose16_out[16], drf_search_colour_result_t &res) {
+  search_refine(o, table, sel, cost, photo, counts, score, n_candidates, voxel_size, track, locate,
+                [&](drf_search_colour_result_t &r, const int *qual, int nq) { return search_colour_winner(r, qual, nq, rescore); }, pose16_out, res);
 }
 
 }  // namespace dr

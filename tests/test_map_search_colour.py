@@ -1,5 +1,5 @@
 """CPU: the host half of drf_score_colour_poses / drf_search_colour_frame (include/dr_mi355x.h "The search with an appearance term
-from the voxel colours", DESIGN.md §7c "Searching with colour").  score_colour_point, score_colour_candidates_host and
+from the voxel colours", DESIGN.md §7c "Searching with colour").  score_sample with colour, score_colour_candidates_host and
 search_colour_refine of tandem_amd/csrc/pose_host.h compiled with plain g++ (tests/cpp/map_search_colour_check.cpp) and held, bit
 for bit, to np_score_colour_candidates / np_search_colour_frame -- the reference of tests/test_fusion_search_colour_gpu.py too.  The
 restatement is np_score_candidates of tests/test_map_search.py plus the lines of the colour rule, and its cost and counts are held
