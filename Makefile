@@ -17,7 +17,7 @@ LDFLAGS := -shared -fPIC -Wl,-Bsymbolic
 all: $(LIB) $(HLIB) oracle/libtsdf_oracle.so oracle/libtsdf_oracle_omp.so oracle/libtracker_oracle.so oracle/libtracker_oracle_left.so
 
 MVS_DEPS := $(CSRC)/dr_mvsnet.hip $(CSRC)/edge_network.h $(CSRC)/conv_mfma.h $(CSRC)/conv_plan.h $(CSRC)/conv_bf3.h $(CSRC)/conv_march.h $(CSRC)/conv_wino.h $(CSRC)/march_plan.h $(CSRC)/conv_tuned.h $(CSRC)/mvs_kernels.h $(CSRC)/mvs_launch.h $(CSRC)/mvs_host.h $(CSRC)/mvs_plan.h $(CSRC)/mvs_engine_host.h $(CSRC)/mvs_stage.h $(CSRC)/mvs_cache.h $(CSRC)/mvs_shard.h $(CSRC)/hip_owner.h $(CSRC)/tail_kernels.h $(CSRC)/fn_front.h $(CSRC)/fn_head3.h $(CSRC)/dr_common.h $(CSRC)/guard_host.h $(CSRC)/dr_host.h include/dr_mi355x.h
-FUS_DEPS := $(CSRC)/dr_fusion.hip $(CSRC)/fusion_host.h $(CSRC)/pose_host.h $(CSRC)/map_file.h $(CSRC)/map_ops.h $(CSRC)/volume_kernels.h $(CSRC)/engine_host.h $(CSRC)/fusion_core.h $(CSRC)/stream_ops.h $(CSRC)/mesh_ops.h $(CSRC)/render_ops.h $(CSRC)/pose_ops.h $(CSRC)/stream_kernels.h $(CSRC)/align_kernels.h $(CSRC)/locate_kernels.h $(CSRC)/track_kernels.h $(CSRC)/track_colour_kernels.h $(CSRC)/track_pyramid_kernels.h $(CSRC)/search_kernels.h $(CSRC)/search_ops.h $(CSRC)/raycast_kernels.h $(CSRC)/hip_owner.h $(CSRC)/mesh_kernels.h $(CSRC)/mesh_update_kernels.h $(CSRC)/mc_tables.h $(CSRC)/dr_common.h $(CSRC)/guard_host.h $(CSRC)/dr_host.h include/dr_mi355x.h
+FUS_DEPS := $(CSRC)/dr_fusion.hip $(CSRC)/fusion_host.h $(CSRC)/pose_host.h $(CSRC)/map_file.h $(CSRC)/map_ops.h $(CSRC)/volume_kernels.h $(CSRC)/engine_host.h $(CSRC)/fusion_core.h $(CSRC)/stream_ops.h $(CSRC)/mesh_ops.h $(CSRC)/render_ops.h $(CSRC)/pose_ops.h $(CSRC)/stream_kernels.h $(CSRC)/align_kernels.h $(CSRC)/locate_kernels.h $(CSRC)/track_kernels.h $(CSRC)/track_colour_kernels.h $(CSRC)/track_pyramid_kernels.h $(CSRC)/track_exposure_kernels.h $(CSRC)/search_kernels.h $(CSRC)/search_ops.h $(CSRC)/raycast_kernels.h $(CSRC)/hip_owner.h $(CSRC)/mesh_kernels.h $(CSRC)/mesh_update_kernels.h $(CSRC)/mc_tables.h $(CSRC)/dr_common.h $(CSRC)/guard_host.h $(CSRC)/dr_host.h include/dr_mi355x.h
 # the depth pipeline is held to a float tolerance, not to bit-exactness: let hipcc contract a*b+c into FMAs there (the
 # vector-pipe kernels -- cost volume, prob -- are VALU-bound, and the reference's cuDNN/ATen kernels use FMAs too)
 $(CSRC)/dr_mvsnet.o: $(MVS_DEPS)

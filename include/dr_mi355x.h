@@ -758,8 +758,8 @@ int drf_track_stats(drf_t *h, uint64_t out[6]);
  * frame's own pixel.  bgr is the frame's colour image as drf_integrate_scan_async takes it (height x width x 3 bytes, B G R),
  * model_bgr the ray-cast's at model_pose16.  Everything that drf_track_* say above about the render, its scope and bands, the
  * stream, the map left unchanged, the legality and the refusals (in that order, the colour images among the null checks) holds
- * here.  Out of scope: an affine brightness or exposure model (frame and map are taken to share their exposure), a
- * global search, and photometric terms in drf_locate_*; the image pyramid is drf_track_pyramid_frame, below.
+ * here.  Frame and map are taken to share their exposure: a frame whose exposure differs is drf_track_exposure_frame's, below.
+ * Out of scope: a global search, and photometric terms in drf_locate_*; the image pyramid is drf_track_pyramid_frame, below.
  * The rule (the same text of pose_host.h; double and fp32 without contraction; + - * / sqrt floor):
  *   intensity   a BGR pixel is y = ((float)b + (float)g) + (float)r, a whole number in 0..765.
  *   Ym          the model intensity map, one float per pixel of the model colour image Cm: Ym(u, v) = the pixel's y where the model
@@ -860,6 +860,77 @@ int drf_track_pyramid_stats(drf_t *h, uint64_t out[8]);
 /* level 0 .. 4 of the last drf_track_pyramid_frame: [0] its status, [1] renders, [2] evaluations, [3] valid samples at its last
  * evaluation; all 0 for a level that did not run ([2] = 0 says so).  After drf_track_pyramid_system: the one evaluation at its level. */
 int drf_track_pyramid_level_stats(drf_t *h, int level, uint64_t out[4]);
+/* Tracks a frame whose exposure differs from the map's (the counterpart of the two affine brightness parameters the reference's
+ * CoarseTracker / cuda_coarse_tracker solves next to its pose; DESIGN.md §7c "Tracking under a change of exposure").  Every colour
+ * call above takes frame and map to share their exposure.  A camera changes it from frame to frame, and where geometry says nothing
+ * -- one wall, a corridor: what the colour term is for -- a brightness change then puts the pose in the wrong place, with no status
+ * that says so.  These calls are drf_track_pyramid_* with colour (bgr is required) and two more unknowns in the solver's state:
+ * frame intensity ~ G * (model intensity) + B, gain G and offset B in double, B in units of the intensity (the three-channel sum
+ * 0..765).  The rule (the same text of pose_host.h; double without contraction; + - * / sqrt floor, no exp):
+ *   sample, association, geometric term   drf_track_*'s, unchanged, added FIRST, and to the 28 pose sums only.
+ *   photometric term   from drf_track_colour_*'s I and gm (its conditions, unchanged) and the frame's yf:
+ *               r = lambda * ((G * I + B) - (double)yf), n_k = (lambda * ((Rm[k][0] gm0 + Rm[k][1] gm1) + Rm[k][2] gm2)) * G;
+ *               G = 1, B = 0 gives drf_track_colour_*'s bits.  J = ((q - c) cross n, n) and Huber's weight w on |r| as there, the
+ *               28 pose sums as there; J6 = lambda * I (dr/dG), J7 = lambda (dr/dB), and 17 more sums, each (w * J_a) * J_b or
+ *               (w * J_a) * r: H(i,6) for i = 0..5, H(i,7) for i = 0..5, H66, H67, H77, b6, b7.
+ *   sums[45]    [0..27] the pose system in drf_track_colour_system's layout, [27] the cost of both terms; [28..44] the 17 above.
+ *               counts[5] are drf_track_colour_system's.  Groups, lanes, butterfly and fold are drf_track_colour_system's.
+ *   step        the 8 x 8 system solved by drf_align_map's Cholesky, its pivot test p > 1e-12 top with top over the 8 diagonals.  A
+ *               failing pivot 0..5 is DRF_ALIGN_DEGENERATE.  A failing pivot 6 or 7 HOLDS the exposure (a map of one colour, no
+ *               photometric term): the step is drf_track_*'s own on sums[0..27], G and B keep their values, `held` goes up.
+ *               Otherwise a NaN in d is DEGENERATE; CONVERGED (not applied) needs the rotation and translation below eps_rot and
+ *               eps_trans, |d6| < eps_gain and |d7| < eps_offset; any other step moves the pose as drf_align_map's does and sets
+ *               G = min(max(G + d6, gain_min), gain_max), B = min(max(B + d7, -765), 765).  The gain is bounded because an
+ *               unbounded one can go negative from a far start (contrast inversion) and end tens of voxels off.
+ *   loop        drf_track_pyramid_frame's, with (G, B) part of the state: LOST restores the last good pose and exposure; the
+ *               exposure carries from round to round and from level to level; an abandoned level hands on the pose and the
+ *               exposure it started from; level 0's result is the call's.
+ * Legality, the call order, render scope and bands, DR_ERR_CAPACITY and the note after a tracking that ran but found no pose are
+ * drf_track_pyramid_frame's; level 0 is the camera itself and fits a camera of any size, as for drf_track_colour_*: levels = 1 is
+ * not refused below 8 pixels on a side, nor is level 0 of drf_track_exposure_system.  Refusals in the pyramid options' order, then (DR_ERR_ARG naming the option) gain_init, offset_init,
+ * gain_min, gain_max, eps_gain, eps_offset negative (not offset_init) or not finite; gain_min > gain_max; gain_init outside the
+ * bounds; |offset_init| > 765; a null bgr is DR_ERR_ARG among the null arguments.  The public render buffers, the map, the
+ * streaming state and the other families' statistics and buffers are untouched: these calls have a scratch buffer of their own
+ * (the pyramid's layout with 45 doubles per group of 512 grid positions), sized once per engine.
+ * OUT OF SCOPE: exposure in drf_score_colour_poses and in drf_locate_*; the tracking stage of drf_search_colour_frame, which keeps
+ * calling the pyramid rule; per-channel gains, response curves and vignetting; compensation on the device (the frame is
+ * compensated on the host before it is integrated: INTEGRATION.md, compensate_exposure). */
+typedef struct {
+  drf_track_pyramid_options_t pyramid;
+  float gain_init;      /* 0 -> 1 */
+  float offset_init;    /* used as given; |offset_init| <= 765 */
+  float gain_min;       /* 0 -> 0.25 */
+  float gain_max;       /* 0 -> 4 */
+  double eps_gain;      /* 0 -> 1e-4 */
+  double eps_offset;    /* 0 -> 1e-2 (intensity units) */
+} drf_track_exposure_options_t;
+typedef struct {
+  drf_align_result_t pose;  /* level 0's result, as drf_track_pyramid_frame's */
+  double gain, offset;      /* the exposure the call ended on */
+  double ext[17];           /* sums[28..44] of the last evaluation */
+  uint64_t photometric;     /* photometric terms added at the last evaluation */
+  uint64_t held;            /* evaluations, over all levels, whose step held the exposure */
+} drf_exposure_result_t;
+/* one evaluation at `level`, pose16 and the exposure (gain, offset) against the model pair ray-cast at model_pose16 */
+int drf_track_exposure_system(drf_t *h, int level, const uint8_t *bgr, const float *depth, const uint8_t *model_bgr, const float *model_depth,
+                              const float model_pose16[16], const float pose16[16], double gain, double offset, const drf_track_exposure_options_t *opt,
+                              double sums[45], uint64_t counts[5]);
+/* the tracking from pose_init16 and (gain_init, offset_init); pose16_out = res->pose.T rounded to float */
+int drf_track_exposure_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float pose_init16[16], const drf_track_exposure_options_t *opt,
+                             float pose16_out[16], drf_exposure_result_t *res);
+/* the same with the images in device memory */
+int drf_track_exposure_system_device(drf_t *h, int level, const void *d_bgr, const void *d_depth, const void *d_model_bgr, const void *d_model_depth,
+                                     const float model_pose16[16], const float pose16[16], double gain, double offset, const drf_track_exposure_options_t *opt,
+                                     double sums[45], uint64_t counts[5]);
+int drf_track_exposure_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float pose_init16[16], const drf_track_exposure_options_t *opt,
+                                    float pose16_out[16], drf_exposure_result_t *res);
+/* last drf_track_exposure_*: drf_track_pyramid_stats' fields.  [5]: the bytes of these calls' own buffer, with n = width * height,
+ * g = ceil(n / 512), n_L = max(1, (width >> L) * (height >> L)), the spans laid one behind the other, each at the alignment of its
+ * element (the model map at 32 bytes, the ray state at 8): 360 g partial sums, 48 of counters, 4 of the ray-cast's flag, 16 n model
+ * map, 8 n ray state, 4 n model depth, 4 n_1 its level, 4 n Ym, 4 n frame depth, 4 n_L for L = 1..4, 3 n model colour, 3 n_1 its
+ * level, 3 n frame colour, 3 n_L for L = 1..4. */
+int drf_track_exposure_stats(drf_t *h, uint64_t out[8]);
+int drf_track_exposure_level_stats(drf_t *h, int level, uint64_t out[4]);
 /* Finds a depth frame in the map from a lattice of poses (no reference counterpart; DESIGN.md §7c "Searching a pose lattice").  Every
  * call above refines and says so: a start further off needs a guess from elsewhere.  These calls make that guess when a session has
  * only a place-recognition hit, a stale key-frame pose or a lost tracker: drf_score_poses evaluates the localisation's cost, without
@@ -998,7 +1069,8 @@ int drf_search_stats(drf_t *h, uint64_t out[8]);
  * SCOPE and side effects are drf_search_frame's: the resident map only, stored blocks counted in [7]; the map, the public render
  * buffers and the streaming state untouched; drf_track_pyramid_stats and drf_locate_stats describe the last refinement stage that
  * ran.  drf_search_stats describes the last call of either family; the final re-score is not counted in [0] or [3].
- * OUT OF SCOPE: exposure or affine brightness (frame and map share their exposure, as for drf_track_colour_*); the stored blocks of
+ * OUT OF SCOPE: exposure or affine brightness (frame and map share their exposure here; drf_track_exposure_frame solves for it, and
+ * the tracking stage of this search keeps the pyramid rule); the stored blocks of
  * a streamed map; selection on the device, a coarse-to-fine lattice, rotations about the camera's own axes.
  * Legality and refusals follow drf_search_frame's order: a null argument (bgr among them: a null bgr is DR_ERR_ARG -- the
  * geometric call is for frames without colour; for drf_score_colour_poses any of the four outputs but not all may be null); the

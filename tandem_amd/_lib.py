@@ -171,6 +171,13 @@ SIGNATURES = {
     "drf_track_pyramid_frame_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
     "drf_track_pyramid_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "drf_track_pyramid_level_stats": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint64)]),
+    "drf_track_exposure_system": (C.c_int, [vp, C.c_int, C.c_void_p, f32p, C.c_void_p, f32p, f32p, f32p, C.c_double, C.c_double, C.c_void_p, f64p, C.POINTER(C.c_uint64)]),
+    "drf_track_exposure_system_device": (C.c_int, [vp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32p, f32p, C.c_double, C.c_double, C.c_void_p, f64p,
+                                                   C.POINTER(C.c_uint64)]),
+    "drf_track_exposure_frame": (C.c_int, [vp, C.c_void_p, f32p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_track_exposure_frame_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f32p, C.c_void_p]),
+    "drf_track_exposure_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_track_exposure_level_stats": (C.c_int, [vp, C.c_int, C.POINTER(C.c_uint64)]),
     "drf_score_poses": (C.c_int, [vp, f32p, f32p, C.c_size_t, C.c_void_p, f64p, C.POINTER(C.c_uint32), f64p]),
     "drf_score_poses_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_size_t, C.c_void_p, f64p, C.POINTER(C.c_uint32), f64p]),
     "drf_search_frame": (C.c_int, [vp, f32p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f64p]),
@@ -210,6 +217,12 @@ class TrackColourOptions(C.Structure):
 class TrackPyramidOptions(C.Structure):
     """drf_track_pyramid_options_t: a zero field means its default."""
     _fields_ = [("colour", TrackColourOptions), ("levels", C.c_int), ("coarse_renders", C.c_int)]
+
+
+class TrackExposureOptions(C.Structure):
+    """drf_track_exposure_options_t: a zero field means its default (offset_init is used as given)."""
+    _fields_ = [("pyramid", TrackPyramidOptions), ("gain_init", C.c_float), ("offset_init", C.c_float), ("gain_min", C.c_float), ("gain_max", C.c_float),
+                ("eps_gain", C.c_double), ("eps_offset", C.c_double)]
 
 
 SEARCH_MAX_TOP = 32  # DRF_SEARCH_MAX_TOP
@@ -264,6 +277,11 @@ class AlignResultStruct(C.Structure):
     """drf_align_result_t."""
     _fields_ = [("T", C.c_double * 16), ("sums", C.c_double * 28), ("samples", C.c_uint64), ("valid0", C.c_uint64), ("valid", C.c_uint64),
                 ("cost0", C.c_double), ("cost", C.c_double), ("iterations", C.c_int), ("status", C.c_int)]
+
+
+class ExposureResultStruct(C.Structure):
+    """drf_exposure_result_t."""
+    _fields_ = [("pose", AlignResultStruct), ("gain", C.c_double), ("offset", C.c_double), ("ext", C.c_double * 17), ("photometric", C.c_uint64), ("held", C.c_uint64)]
 
 
 HOOKS_LIB_PATH = os.path.join(_HERE, "libdr_mi355x_hooks.so")  # the PARITY build (-DDR_PARITY_HOOKS): superseded kernel generations selectable

@@ -35,6 +35,7 @@ namespace dr {
 #include "track_kernels.h"   // k_track_model, k_track (drf_track_system, drf_track_frame)
 #include "track_colour_kernels.h"  // k_track_model_colour, k_track_colour (drf_track_colour_system, drf_track_colour_frame)
 #include "track_pyramid_kernels.h"  // k_track_reduce (drf_track_reduce, drf_track_pyramid_system, drf_track_pyramid_frame)
+#include "track_exposure_kernels.h"  // k_track_exposure, k_exposure_fold (drf_track_exposure_system, drf_track_exposure_frame)
 #include "search_kernels.h"  // k_search_points, k_search_score (drf_score_poses, drf_search_frame) and their colour forms (drf_score_colour_poses, drf_search_colour_frame)
 
 }  // namespace dr
@@ -605,7 +606,7 @@ class FusionEngine {
   MapRenderer renderer_;     // the render slots, the one submit, render scope and depth bands (render_ops.h)
   FramePose frame_;          // what the pose families open with (pose_ops.h)
   FrameLocator locator_;     // drf_locate_* and the locate scope (pose_ops.h)
-  FrameTracker tracker_;     // drf_track_*, drf_track_colour_*, drf_track_reduce / drf_track_pyramid_* (pose_ops.h)
+  FrameTracker tracker_;     // drf_track_*, drf_track_colour_*, drf_track_reduce / drf_track_pyramid_*, drf_track_exposure_* (pose_ops.h)
   PoseSearch search_;        // drf_score_poses / drf_search_frame over the score stage, the tracker and the locator (search_ops.h)
   hipEvent_t kernel_events_[3] = {nullptr, nullptr, nullptr};
   int integrate_grid_ = 4096;
@@ -909,6 +910,44 @@ int drf_track_pyramid_level_stats(drf_t *h, int level, uint64_t out[4]) {
   return guarded([&] {
     if (!out) dr::fail(DR_ERR_ARG, "drf_track_pyramid_level_stats: null argument");
     const uint64_t *s = eng(h)->track().track_pyramid_level_stats(level);
+    for (int i = 0; i < 4; ++i) out[i] = s[i];
+  });
+}
+int drf_track_exposure_system(drf_t *h, int level, const uint8_t *bgr, const float *depth, const uint8_t *model_bgr, const float *model_depth,
+                              const float model_pose16[16], const float pose16[16], double gain, double offset, const drf_track_exposure_options_t *opt,
+                              double sums[45], uint64_t counts[5]) {
+  return guarded([&] {
+    eng(h)->track().track_exposure_system("drf_track_exposure_system", level, FramePair::host(bgr, depth), FramePair::host(model_bgr, model_depth), model_pose16, pose16, gain,
+                                          offset, opt, sums, counts);
+  });
+}
+int drf_track_exposure_system_device(drf_t *h, int level, const void *d_bgr, const void *d_depth, const void *d_model_bgr, const void *d_model_depth,
+                                     const float model_pose16[16], const float pose16[16], double gain, double offset, const drf_track_exposure_options_t *opt,
+                                     double sums[45], uint64_t counts[5]) {
+  return guarded([&] {
+    eng(h)->track().track_exposure_system("drf_track_exposure_system_device", level, FramePair::device(d_bgr, d_depth), FramePair::device(d_model_bgr, d_model_depth),
+                                          model_pose16, pose16, gain, offset, opt, sums, counts);
+  });
+}
+int drf_track_exposure_frame(drf_t *h, const uint8_t *bgr, const float *depth, const float pose_init16[16], const drf_track_exposure_options_t *opt,
+                             float pose16_out[16], drf_exposure_result_t *res) {
+  return guarded_note([&] { return eng(h)->track().track_exposure_frame("drf_track_exposure_frame", FramePair::host(bgr, depth), pose_init16, opt, pose16_out, res); });
+}
+int drf_track_exposure_frame_device(drf_t *h, const void *d_bgr, const void *d_depth, const float pose_init16[16], const drf_track_exposure_options_t *opt,
+                                    float pose16_out[16], drf_exposure_result_t *res) {
+  return guarded_note([&] { return eng(h)->track().track_exposure_frame("drf_track_exposure_frame_device", FramePair::device(d_bgr, d_depth), pose_init16, opt, pose16_out, res); });
+}
+int drf_track_exposure_stats(drf_t *h, uint64_t out[8]) {
+  return guarded([&] {
+    if (!out) dr::fail(DR_ERR_ARG, "drf_track_exposure_stats: null argument");
+    const uint64_t *s = eng(h)->track().track_exposure_stats();
+    for (int i = 0; i < 8; ++i) out[i] = s[i];
+  });
+}
+int drf_track_exposure_level_stats(drf_t *h, int level, uint64_t out[4]) {
+  return guarded([&] {
+    if (!out) dr::fail(DR_ERR_ARG, "drf_track_exposure_level_stats: null argument");
+    const uint64_t *s = eng(h)->track().track_exposure_level_stats(level);
     for (int i = 0; i < 4; ++i) out[i] = s[i];
   });
 }

@@ -108,6 +108,19 @@ struct MapIo {
     memcpy(sums, pair.host(), 224);
     memcpy(cnt, pair.host() + 224, (size_t)ncnt * 8);
   }
+  // The same for drf_track_exposure_*: rows of 45 partial sums, k_exposure_fold, 45 sums and five counters copied out -- 400 bytes of
+  // the pair's slot, which ensure() never makes smaller than one block's 4096.
+  template <class Launch>
+  void evaluate_exposure(const double *partial, int groups, unsigned long long *counts, double sums[45], uint64_t cnt[5], Launch &&launch) {
+    static_assert(45 * sizeof(double) + 5 * sizeof(uint64_t) <= 4096, "the pinned pair's smallest slot holds the exposure system");
+    DR_HIP(hipMemsetAsync(counts, 0, 40, stream));
+    launch();
+    hipLaunchKernelGGL(k_exposure_fold, dim3(45), dim3(64), 0, stream, partial, groups, counts, (double *)pair.dev());
+    DR_HIP(hipGetLastError());
+    DR_HIP(hipStreamSynchronize(stream));
+    memcpy(sums, pair.host(), 360);
+    memcpy(cnt, pair.host() + 360, 40);
+  }
 };
 
 // Device memory of one call, freed on every way out.  It goes through device_alloc, so the parity build's guarded allocator sees it.

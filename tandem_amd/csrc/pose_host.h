@@ -4,9 +4,10 @@
 // Gauss-Newton system (align_accumulate), one step (align_step), one loop (align_loop), one walk over a frame's sample grid
 // (frame_group) for all of them.  The DR_HOST_DEVICE functions are the text the kernels compile.  Plain C++17 over fusion_host.h,
 // which includes this file at its end: whoever includes either has both (tests/cpp/map_align_check.cpp, map_locate_check.cpp,
-// map_track_check.cpp, map_track_colour_check.cpp, map_search_check.cpp run it on the CPU).
+// map_track_check.cpp, map_track_colour_check.cpp, map_track_exposure_check.cpp, map_search_check.cpp run it on the CPU).
 #pragma once
 #include <string>
+#include <type_traits>
 
 #include "fusion_host.h"
 
@@ -158,12 +159,14 @@ template <class Fetch>
 DR_HOST_DEVICE inline bool align_voxel(const AlignEval &e, int gx, int gy, int gz, float s_src, Fetch &&fetch, double acc[28]) {
   return align_point<false>(e, (double)gx, (double)gy, (double)gz, s_src, fetch, acc) == 1;
 }
-// x[l] = x[l] + x[l ^ off] for off = 32, 16, 8, 4, 2, 1 over 64 lanes of 28 values: afterwards every lane holds the same sum
-inline void align_butterfly(double x[64][28]) {
+// x[l] = x[l] + x[l ^ off] for off = 32, 16, 8, 4, 2, 1 over 64 lanes of S values (28; 45 with the exposure): afterwards every lane
+// holds the same sum
+template <int S>
+inline void align_butterfly(double x[64][S]) {
   for (int off = 32; off > 0; off >>= 1) {
-    double y[64][28];
+    double y[64][S];
     for (int l = 0; l < 64; ++l)
-      for (int i = 0; i < 28; ++i) y[l][i] = x[l][i] + x[l ^ off][i];
+      for (int i = 0; i < S; ++i) y[l][i] = x[l][i] + x[l ^ off][i];
     memcpy(x, y, sizeof y);
   }
 }
@@ -190,17 +193,19 @@ inline void align_block(const AlignEval &e, const int blk[3], const uint8_t *src
   align_butterfly(x);
   for (int i = 0; i < 28; ++i) out[i] = x[0][i];
 }
-// k_align_fold on the host: per component lane l adds partial[l], partial[l + 64], ... from +0.0 and the butterfly folds the lanes
-inline void align_fold_host(const double *partial, size_t n, double sums[28]) {
-  double x[64][28];
+// k_align_fold (S = 45: k_exposure_fold) on the host: per component lane l adds partial[l], partial[l + 64], ... from +0.0 and the
+// butterfly folds the lanes
+template <int S = 28>
+inline void align_fold_host(const double *partial, size_t n, double sums[S]) {
+  double x[64][S];
   for (int l = 0; l < 64; ++l)
-    for (int c = 0; c < 28; ++c) {
+    for (int c = 0; c < S; ++c) {
       double a = 0.0;
-      for (size_t i = (size_t)l; i < n; i += 64) a = a + partial[i * 28 + c];
+      for (size_t i = (size_t)l; i < n; i += 64) a = a + partial[i * S + c];
       x[l][c] = a;
     }
   align_butterfly(x);
-  for (int c = 0; c < 28; ++c) sums[c] = x[0][c];
+  for (int c = 0; c < S; ++c) sums[c] = x[0][c];
 }
 // The system at one pose over the whole source (keys ascending, n x 4096 bytes): align_block per block into partial[i], then
 // per component lane l adds partial[l], partial[l + 64], ... from +0.0 and the butterfly folds the lanes.
@@ -216,40 +221,37 @@ inline void align_system_host(const std::vector<unsigned long long> &src_keys, c
   }
   align_fold_host(partial.data(), n, sums);
 }
-// One Gauss-Newton step from the system sums at pose m (centre c = e.c of that evaluation).  Returns DRF_ALIGN_DEGENERATE (m
-// unchanged), DRF_ALIGN_CONVERGED (the step is below both thresholds and is not applied) or -1 (m moved).  + - * / sqrt only.
-inline int align_step(const double sums[28], const double c[3], double eps_rot, double eps_trans, MapMotion &m) {
-  double H[6][6], L[6][6] = {{0.0}}, y[6] = {0.0}, d[6] = {0.0};
-  int idx = 0;
-  for (int i = 0; i < 6; ++i)
-    for (int j = i; j < 6; ++j) { H[i][j] = sums[idx]; H[j][i] = sums[idx]; ++idx; }
-  double top = H[0][0];
-  for (int j = 1; j < 6; ++j) top = H[j][j] > top ? H[j][j] : top;
-  if (!(top > 0.0)) return DRF_ALIGN_DEGENERATE;
-  for (int j = 0; j < 6; ++j) {
+// The Cholesky solve that every step shares, H d = -b for a symmetric N x N H (6; 8 with the exposure): the pivot test is
+// p > 1e-12 top, top the largest diagonal entry.  Returns the index of the first pivot that fails it, or -1 with d solved.
+template <int N>
+inline int align_solve(const double H[N][N], const double b[N], double top, double d[N]) {
+  double L[N][N] = {{0.0}}, y[N] = {0.0};
+  for (int i = 0; i < N; ++i) d[i] = 0.0;
+  for (int j = 0; j < N; ++j) {
     double p = H[j][j];
     for (int k = 0; k < j; ++k) p = p - L[j][k] * L[j][k];
-    if (!(p > 1e-12 * top)) return DRF_ALIGN_DEGENERATE;
+    if (!(p > 1e-12 * top)) return j;
     L[j][j] = std::sqrt(p);
-    for (int i = j + 1; i < 6; ++i) {
+    for (int i = j + 1; i < N; ++i) {
       double t = H[i][j];
       for (int k = 0; k < j; ++k) t = t - L[i][k] * L[j][k];
       L[i][j] = t / L[j][j];
     }
   }
-  for (int i = 0; i < 6; ++i) {
-    double t = -sums[21 + i];
+  for (int i = 0; i < N; ++i) {
+    double t = -b[i];
     for (int k = 0; k < i; ++k) t = t - L[i][k] * y[k];
     y[i] = t / L[i][i];
   }
-  for (int i = 5; i >= 0; --i) {
+  for (int i = N - 1; i >= 0; --i) {
     double t = y[i];
-    for (int k = i + 1; k < 6; ++k) t = t - L[k][i] * d[k];
+    for (int k = i + 1; k < N; ++k) t = t - L[k][i] * d[k];
     d[i] = t / L[i][i];
   }
-  const double oo = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2], vv = (d[3] * d[3] + d[4] * d[4]) + d[5] * d[5];
-  if (!(oo == oo) || !(vv == vv)) return DRF_ALIGN_DEGENERATE;  // a system that held a NaN
-  if (std::sqrt(oo) < eps_rot && std::sqrt(vv) < eps_trans) return DRF_ALIGN_CONVERGED;
+  return -1;
+}
+// the pose moved by the step d[0..5] (rotation vector about c, translation), oo = |d[0..2]|^2
+inline void align_move(const double d[6], double oo, const double c[3], MapMotion &m) {
   const double a = 1.0 / std::sqrt(1.0 + oo / 4.0);
   const double qw = a, qx = (a * d[0]) / 2.0, qy = (a * d[1]) / 2.0, qz = (a * d[2]) / 2.0;
   const double Rq[9] = {1.0 - 2.0 * (qy * qy + qz * qz), 2.0 * (qx * qy - qw * qz), 2.0 * (qx * qz + qw * qy),
@@ -262,16 +264,45 @@ inline int align_step(const double sums[28], const double c[3], double eps_rot, 
     o.tv[i] = (c[i] + ((Rq[3 * i] * e[0] + Rq[3 * i + 1] * e[1]) + Rq[3 * i + 2] * e[2])) + d[3 + i];
   }
   m = o;
+}
+// One Gauss-Newton step from the system sums at pose m (centre c = e.c of that evaluation).  Returns DRF_ALIGN_DEGENERATE (m
+// unchanged), DRF_ALIGN_CONVERGED (the step is below both thresholds and is not applied) or -1 (m moved).  + - * / sqrt only.
+inline int align_step(const double sums[28], const double c[3], double eps_rot, double eps_trans, MapMotion &m) {
+  double H[6][6], d[6];
+  int idx = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { H[i][j] = sums[idx]; H[j][i] = sums[idx]; ++idx; }
+  double top = H[0][0];
+  for (int j = 1; j < 6; ++j) top = H[j][j] > top ? H[j][j] : top;
+  if (!(top > 0.0)) return DRF_ALIGN_DEGENERATE;
+  if (align_solve<6>(H, sums + 21, top, d) >= 0) return DRF_ALIGN_DEGENERATE;
+  const double oo = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2], vv = (d[3] * d[3] + d[4] * d[4]) + d[5] * d[5];
+  if (!(oo == oo) || !(vv == vv)) return DRF_ALIGN_DEGENERATE;  // a system that held a NaN
+  if (std::sqrt(oo) < eps_rot && std::sqrt(vv) < eps_trans) return DRF_ALIGN_CONVERGED;
+  align_move(d, oo, c, m);
   return -1;
 }
+// What a solver's state holds beside the pose: nothing, for every call but drf_track_exposure_* (ExposureState, below).  The loops
+// ask it to keep() the state an evaluation passed with, to go back() to it when a later one is LOST, and for the step.
+struct PoseState {
+  void keep() {}
+  void back() {}
+  void level_begin() {}
+  void level_abandoned() {}
+  int step(const double sums[28], const double c[3], double eps_rot, double eps_trans, MapMotion &m) { return align_step(sums, c, eps_rot, eps_trans, m); }
+};
 // The loop of every solver over any evaluator eval(const AlignEval &, double sums[28], uint64_t counts[N]): the host's or the
 // engine's (the kernels).  The loop reads counts[0] = samples and counts[1] = valid; what else an evaluator counts (N = 3 for the
 // registration, 4 for a frame, 5 with colour) passes through: last, if given, receives the N counters of the last evaluation, and
-// trace the sums of every evaluation.
-template <int N = 3, class Eval>
+// trace the sums of every evaluation.  state: what the solver holds beside the pose (an evaluator that reads it is given it by its
+// own means); LOST restores the last good pose and state.
+template <int N = 3, class Eval, class State = PoseState>
 inline void align_loop(Eval &&eval, const MapMotion &m0, const double c_src[3], const AlignOpt &o, float voxel_size, drf_align_result_t &res,
-                       uint64_t *last = nullptr, std::vector<std::array<double, 28>> *trace = nullptr) {
+                       uint64_t *last = nullptr, std::vector<std::array<double, 28>> *trace = nullptr, State *state = nullptr) {
   MapMotion m = m0, good = m0;
+  State none{};
+  State &x = state ? *state : none;
+  x.keep();
   memset(&res, 0, sizeof res);
   res.status = DRF_ALIGN_MAX_ITERS;
   for (int it = 0; it < o.max_iters; ++it) {
@@ -284,9 +315,10 @@ inline void align_loop(Eval &&eval, const MapMotion &m0, const double c_src[3], 
     res.samples = counts[0]; res.valid = counts[1];
     res.cost = counts[1] ? res.sums[27] / (double)counts[1] : 0.0;
     if (it == 0) { res.valid0 = res.valid; res.cost0 = res.cost; }
-    if ((double)counts[1] < o.min_valid * (double)counts[0] || counts[1] < 6) { res.status = DRF_ALIGN_LOST; m = good; break; }
+    if ((double)counts[1] < o.min_valid * (double)counts[0] || counts[1] < 6) { res.status = DRF_ALIGN_LOST; m = good; x.back(); break; }
     good = m;
-    const int s = align_step(res.sums, e.c, o.eps_rot, o.eps_trans, m);
+    x.keep();
+    const int s = x.step(res.sums, e.c, o.eps_rot, o.eps_trans, m);
     if (s >= 0) { res.status = s; break; }
   }
   for (int i = 0; i < 3; ++i) {
@@ -383,13 +415,13 @@ inline void locate_pose16(const MapMotion &m, float voxel_size, float pose16[16]
 // The walk every evaluation over a frame shares, group i in the wave's order: lane l takes grid positions 512 i + l + 64 k,
 // k = 0..7 (those >= Wg * Hg are no samples), then the butterfly.  sample(n, g, acc) adds the sample at grid position n, camera-frame
 // point g, to acc[28] and returns its code; count(code) names the counter the code adds to besides counts[0], the samples.
-// out[28] = the group's sums.
-template <class Sample, class Count>
-inline void frame_group(const AlignEval &e, const LocateGrid &lg, const float *depth, long i, Sample &&sample, Count &&count, double out[28], uint64_t *counts) {
-  double x[64][28];
+// out[S] = the group's sums (S = 28; 45 with the exposure).
+template <int S = 28, class Sample, class Count>
+inline void frame_group(const AlignEval &e, const LocateGrid &lg, const float *depth, long i, Sample &&sample, Count &&count, double out[S], uint64_t *counts) {
+  double x[64][S];
   const long total = locate_positions(lg);
   for (int l = 0; l < 64; ++l) {
-    for (int c = 0; c < 28; ++c) x[l][c] = 0.0;
+    for (int c = 0; c < S; ++c) x[l][c] = 0.0;
     for (int k = 0; k < 8; ++k) {
       const long n = 512 * i + l + 64 * k;
       double g[3];
@@ -399,17 +431,17 @@ inline void frame_group(const AlignEval &e, const LocateGrid &lg, const float *d
     }
   }
   align_butterfly(x);
-  for (int c = 0; c < 28; ++c) out[c] = x[0][c];
+  for (int c = 0; c < S; ++c) out[c] = x[0][c];
 }
 // The system at one pose over the whole sample grid: N counters from zero, frame_group per group into partial[i], then
 // k_align_fold's fold.
-template <int N, class Sample, class Count>
-inline void frame_system_host(const LocateGrid &lg, const float *depth, const AlignEval &e, Sample &&sample, Count &&count, double sums[28], uint64_t counts[N]) {
+template <int N, int S = 28, class Sample, class Count>
+inline void frame_system_host(const LocateGrid &lg, const float *depth, const AlignEval &e, Sample &&sample, Count &&count, double sums[S], uint64_t counts[N]) {
   for (int c = 0; c < N; ++c) counts[c] = 0;
   const size_t n = (size_t)locate_groups(lg);
-  std::vector<double> partial(n * 28);
-  for (size_t i = 0; i < n; ++i) frame_group(e, lg, depth, (long)i, sample, count, &partial[i * 28], counts);
-  align_fold_host(partial.data(), n, sums);
+  std::vector<double> partial(n * S);
+  for (size_t i = 0; i < n; ++i) frame_group<S>(e, lg, depth, (long)i, sample, count, &partial[i * S], counts);
+  align_fold_host<S>(partial.data(), n, sums);
 }
 // the codes of align_point<true> and track_point: 1 valid, 0 counts[2] (unobserved / unassociated), 2 counts[3] (outside / rejected)
 inline void frame_count(int r, uint64_t *counts) { ++counts[r == 1 ? 1 : r == 0 ? 2 : 3]; }
@@ -573,9 +605,10 @@ inline void track_system_host(const LocateGrid &lg, const float *depth, const Tr
 // ends CONVERGED at its first evaluation ends it CONVERGED; any other round hands its pose on, and after max_renders rounds the
 // call is MAX_ITERS.  res: T, sums, samples, valid, cost of the last round; valid0, cost0 of the first; iterations = evaluations in
 // all.  stats2 = {evaluations, renders}; last the N counters of the last evaluation.
-template <int N = 4, class Render, class Eval>
+// state (align_loop's) carries from round to round.
+template <int N = 4, class Render, class Eval, class State = PoseState>
 inline void track_loop(Render &&render, Eval &&eval, const float *pose_init16, const TrackOpt &o, float voxel_size, drf_align_result_t &res,
-                       uint64_t *last = nullptr, uint64_t *stats2 = nullptr, std::vector<std::array<double, 28>> *trace = nullptr) {
+                       uint64_t *last = nullptr, uint64_t *stats2 = nullptr, std::vector<std::array<double, 28>> *trace = nullptr, State *state = nullptr) {
   double c_src[3];
   locate_centre_src(o.centre_depth, voxel_size, c_src);
   float p16[16];
@@ -591,7 +624,7 @@ inline void track_loop(Render &&render, Eval &&eval, const float *pose_init16, c
     align_loop<N>([&](const AlignEval &e, double sums[28], uint64_t *counts) {
       eval(e, p16, sums, counts);
       if (stats2) ++stats2[0];
-    }, map_motion(p16, voxel_size), c_src, o.a, voxel_size, in, last, trace);
+    }, map_motion(p16, voxel_size), c_src, o.a, voxel_size, in, last, trace, state);
     evaluations += in.iterations;
     if (r == 0) { valid0 = in.valid0; cost0 = in.cost0; }
     res = in;
@@ -701,22 +734,25 @@ DR_HOST_DEVICE inline int track_colour_point(const AlignEval &e, const TrackMode
     return photo ? 3 : 1;
   });
 }
+// the codes of track_colour_point: 3 is valid and adds to the fifth counter
+inline void track_colour_count(int r, uint64_t *c) { ++c[(r & 1) ? 1 : r == 0 ? 2 : 3]; if (r == 3) ++c[4]; }
 // The system at one pose over the whole sample grid (frame_system_host); counts = {samples, valid, unassociated, rejected,
-// photometric terms added}: code 3 is valid and adds to the fifth.
+// photometric terms added}.
 inline void track_colour_system_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, const TrackModel &t, const TrackColour &tc,
                                      const AlignEval &e, double sums[28], uint64_t counts[5]) {
   frame_system_host<5>(lg, depth, e, [&](int n, const double *g, double *acc) {
     return track_colour_point(e, t, tc, lg, g[0], g[1], g[2], track_intensity(bgr + 3 * locate_offset(lg, n)), acc);
-  }, [](int r, uint64_t *c) { ++c[(r & 1) ? 1 : r == 0 ? 2 : 3]; if (r == 3) ++c[4]; }, sums, counts);
+  }, track_colour_count, sums, counts);
 }
 // The whole tracking on the CPU over any renderer render(const float pose16[16], unsigned char *Cm, float *Dm): the library's
 // reference for drf_track_colour_frame (N = 5: track_loop's render builds the model map and Ym from the colour and the depth it
 // rendered) and, without the colour images, for drf_track_frame (N = 4: bgr is not read, Cm is empty, o.photo_weight is not read);
 // what the sanitizer programs run.  last, if given, receives the N counters of the last evaluation.
-template <int N = 5, class RenderBoth>
+// state: null, or the ExposureState of drf_track_exposure_frame (below), whose evaluation then takes the colour one's place.
+template <int N = 5, class RenderBoth, class State = PoseState>
 inline void track_colour_frame_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, RenderBoth &&render_both, const float *pose_init16,
                                     const TrackColourOpt &o, float voxel_size, drf_align_result_t &res, uint64_t *last = nullptr, uint64_t *stats2 = nullptr,
-                                    std::vector<std::array<double, 28>> *trace = nullptr) {
+                                    std::vector<std::array<double, 28>> *trace = nullptr, State *state = nullptr) {
   constexpr bool colour = N == 5;
   const size_t npix = (size_t)lg.W * (size_t)lg.H;
   std::vector<float> Dm(npix), Ym(colour ? npix : 0);
@@ -728,9 +764,10 @@ inline void track_colour_frame_host(const LocateGrid &lg, const unsigned char *b
     else track_model_host(lg, o.t.max_jump, Dm.data(), map.data());
   }, [&](const AlignEval &e, const float *p16, double sums[28], uint64_t *c) {
     const TrackModel tm = track_model(p16, o.t, voxel_size, map.data());
-    if (colour) track_colour_system_host(lg, bgr, depth, tm, track_colour(o, Ym.data()), e, sums, c);
+    if constexpr (!std::is_same<State, PoseState>::value) state->evaluate_host(lg, bgr, depth, tm, track_colour(o, Ym.data()), e, sums, c);
+    else if (colour) track_colour_system_host(lg, bgr, depth, tm, track_colour(o, Ym.data()), e, sums, c);
     else track_system_host(lg, depth, tm, e, sums, c);
-  }, pose_init16, o.t, voxel_size, res, last, stats2, trace);
+  }, pose_init16, o.t, voxel_size, res, last, stats2, trace, state);
 }
 template <class RenderDepth>
 inline void track_frame_host(const LocateGrid &lg, const float *depth, RenderDepth &&render_depth, const float *pose_init16, const TrackOpt &o, float voxel_size,
@@ -892,10 +929,12 @@ inline void track_pyramid_system_host(const LocateGrid &lg0, int L, const unsign
 // The whole coarse-to-fine tracking on the CPU over a renderer of the FULL-resolution images, render_both(pose16, Cm, Dm): the
 // library's reference for drf_track_pyramid_frame (bgr null: geometry only, Cm is not read), and what the sanitizer program runs.
 // A round of a level above 0 renders at full resolution, reduces to the level, and from there is track_colour_frame_host's.
-template <class RenderBoth>
+// state: null, or the ExposureState of drf_track_exposure_frame (below; bgr is then given): it carries from level to level, and an
+// abandoned level hands on the state it started from.
+template <class RenderBoth, class State = PoseState>
 inline void track_pyramid_frame_host(const LocateGrid &lg0, const unsigned char *bgr, const float *depth, RenderBoth &&render_both, const float *pose_init16,
                                      const TrackPyramidOpt &o, float voxel_size, drf_align_result_t &res, uint64_t stats8[8], uint64_t level4[kTrackMaxLevels][4],
-                                     uint64_t *last5 = nullptr, std::vector<std::array<double, 28>> *trace = nullptr) {
+                                     uint64_t *last5 = nullptr, std::vector<std::array<double, 28>> *trace = nullptr, State *state = nullptr) {
   const bool colour = bgr != nullptr;
   const size_t npix0 = (size_t)lg0.W * (size_t)lg0.H;
   std::vector<float> Dm(npix0);
@@ -917,9 +956,228 @@ inline void track_pyramid_frame_host(const LocateGrid &lg0, const unsigned char 
     };
     const unsigned char *fbgr = L == 0 ? bgr : fc[L].data();
     const float *fdepth = L == 0 ? depth : fd[L].data();
-    if (colour) track_colour_frame_host<5>(lg, fbgr, fdepth, render_level, p16, lo, voxel_size, r, last, st2, trace);
+    if (state) state->level_begin();
+    if (colour) track_colour_frame_host<5>(lg, fbgr, fdepth, render_level, p16, lo, voxel_size, r, last, st2, trace, state);
     else track_colour_frame_host<4>(lg, nullptr, fdepth, render_level, p16, lo, voxel_size, r, last, st2, trace);
+    if (state && L > 0 && (r.status == DRF_ALIGN_LOST || r.status == DRF_ALIGN_DEGENERATE)) state->level_abandoned();
   }, lg0, pose_init16, o, res, stats8, level4, last5);
+}
+
+// ---- tracking under a change of exposure (drf_track_exposure_system / drf_track_exposure_frame; DESIGN.md §7c "Tracking under a
+// change of exposure").  Every colour call above takes frame and map to share their exposure; a camera that changes it between
+// frames puts the photometric term, and with it the pose, in the wrong place.  These calls solve for two more unknowns beside the
+// six of the pose, as the reference's dense tracker does: frame intensity ~ G * (model intensity) + B, gain G and offset B in
+// double, B in units of the intensity (the three-channel sum 0..765).  The sample, the association and the geometric term are
+// track_sample's, unchanged; the photometric term reads track_photo_model's I and gm and the state; the 8 x 8 system is 45 sums.
+// G = 1, B = 0 gives track_photo_term's bits.  Stated once, here; the header of the C ABI restates it.  Compiled by g++ and by
+// hipcc (k_track_exposure), both without contraction; + - * / sqrt and floor only -- no exp: G is the gain itself, not its logarithm.
+struct TrackExposure { double gain, offset; };  // what an evaluation reads of the state
+// track_photo_term's conditions and interpolation up to I and gm, which the term under an exposure is made of: the same operations
+// in the same order.  (track_photo_term itself is not written over this function: k_track_colour keeps its instructions and its
+// registers only while its text stays as it is -- sharing the lines cost it 12 bytes of scratch.)
+DR_HOST_DEVICE inline bool track_photo_model(const TrackColour &tc, const LocateGrid &lg, const double m[3], double up, double vp, double &I, double gm[3]) {
+  const double fu = floor(up), fv = floor(vp);
+  if (!(fu >= 0.0 && fu + 1.0 <= (double)(lg.W - 1) && fv >= 0.0 && fv + 1.0 <= (double)(lg.H - 1))) return false;
+  const size_t at = (size_t)(int)fv * (size_t)lg.W + (size_t)(int)fu;
+  TrackPair top, bot;
+  memcpy(&top, tc.Ym + at, sizeof top);
+  memcpy(&bot, tc.Ym + at + (size_t)lg.W, sizeof bot);
+  if (!(top.a >= 0.0f && top.b >= 0.0f && bot.a >= 0.0f && bot.b >= 0.0f)) return false;
+  const double y00 = (double)top.a, y10 = (double)top.b, y01 = (double)bot.a, y11 = (double)bot.b;
+  const double a = up - fu, b = vp - fv, oa = 1.0 - a, ob = 1.0 - b;
+  I = ob * (oa * y00 + a * y10) + b * (oa * y01 + a * y11);
+  const double Iu = ob * (y10 - y00) + b * (y11 - y01), Iv = oa * (y01 - y00) + a * (y11 - y10);
+  gm[0] = (Iu * (double)lg.fx) / m[2]; gm[1] = (Iv * (double)lg.fy) / m[2];
+  gm[2] = -((gm[0] * m[0] + gm[1] * m[1]) / m[2]);
+  return true;
+}
+// The 17 sums of a photometric term beside align_accumulate's 28, from the same J (recomputed by the same operations) and Huber's
+// weight: ext[i] += (w J_i) J6 and ext[6 + i] += (w J_i) J7 for the pose's i = 0..5, then H66, H67, H77, b6, b7.  J6 = lambda I is
+// dr/dG, J7 = lambda is dr/dB.
+DR_HOST_DEVICE inline void exposure_accumulate(const AlignEval &e, double J6, double J7, double r, double n0, double n1, double n2, const double q[3], double ext[17]) {
+  const double x0 = q[0] - e.c[0], x1 = q[1] - e.c[1], x2 = q[2] - e.c[2];
+  const double J[6] = {x1 * n2 - x2 * n1, x2 * n0 - x0 * n2, x0 * n1 - x1 * n0, n0, n1, n2};
+  const double a = r < 0.0 ? -r : r;
+  const double w = a <= e.huber ? 1.0 : e.huber / a;
+  DR_UNROLL
+  for (int i = 0; i < 6; ++i) {
+    const double wj = w * J[i];
+    ext[i] = ext[i] + wj * J6;
+    ext[6 + i] = ext[6 + i] + wj * J7;
+  }
+  const double w6 = w * J6, w7 = w * J7;
+  ext[12] = ext[12] + w6 * J6;
+  ext[13] = ext[13] + w6 * J7;
+  ext[14] = ext[14] + w7 * J7;
+  ext[15] = ext[15] + w6 * r;
+  ext[16] = ext[16] + w7 * r;
+}
+// One sample with colour under the exposure x: track_colour_point's codes and order -- the geometric term first, into acc[0..27]
+// alone; then, where track_photo_model has one, the photometric term r = lambda ((G I + B) - yf), n_k = (lambda (Rm gm)_k) G
+// through align_accumulate into acc[0..27] and exposure_accumulate into acc[28..44].
+DR_HOST_DEVICE inline int track_exposure_point(const AlignEval &e, const TrackModel &t, const TrackColour &tc, const TrackExposure &x, const LocateGrid &lg, double g0,
+                                               double g1, double g2, float yf, double acc[45]) {
+  return track_sample(e, t, lg, g0, g1, g2, [&](double r, double w0, double w1, double w2, const double *q, const double *m, double up, double vp) {
+    double I = 0.0, gm[3] = {0.0, 0.0, 0.0};
+    const bool photo = track_photo_model(tc, lg, m, up, vp, I, gm);
+    const double pr = tc.weight * ((x.gain * I + x.offset) - (double)yf);
+    const double pn[3] = {(tc.weight * ((t.m.R[0] * gm[0] + t.m.R[1] * gm[1]) + t.m.R[2] * gm[2])) * x.gain,
+                          (tc.weight * ((t.m.R[3] * gm[0] + t.m.R[4] * gm[1]) + t.m.R[5] * gm[2])) * x.gain,
+                          (tc.weight * ((t.m.R[6] * gm[0] + t.m.R[7] * gm[1]) + t.m.R[8] * gm[2])) * x.gain};
+    const int terms = photo ? 2 : 1;
+    DR_NO_UNROLL
+    for (int k = 0; k < terms; ++k) {
+      const bool second = k == 1;
+      align_accumulate(e, second ? pr : r, second ? pn[0] : w0, second ? pn[1] : w1, second ? pn[2] : w2, q, acc);
+    }
+    if (photo) exposure_accumulate(e, tc.weight * I, tc.weight, pr, pn[0], pn[1], pn[2], q, acc + 28);
+    return photo ? 3 : 1;
+  });
+}
+// The system at one pose and exposure over the whole sample grid: sums[45] = the pose system in drf_track_colour_system's layout
+// ([27] the cost of both terms), then the 17 sums; counts[5] are drf_track_colour_system's.
+inline void track_exposure_system_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, const TrackModel &t, const TrackColour &tc,
+                                       const TrackExposure &x, const AlignEval &e, double sums[45], uint64_t counts[5]) {
+  frame_system_host<5, 45>(lg, depth, e, [&](int n, const double *g, double *acc) {
+    return track_exposure_point(e, t, tc, x, lg, g[0], g[1], g[2], track_intensity(bgr + 3 * locate_offset(lg, n)), acc);
+  }, track_colour_count, sums, counts);
+}
+struct TrackExposureOpt {  // drf_track_exposure_options_t with its defaults resolved
+  TrackPyramidOpt p;
+  double gain_init, offset_init, gain_min, gain_max, eps_gain, eps_offset;
+};
+constexpr double kExposureOffsetMax = 765.0;
+// null: all defaults.  Returns null, or which option is refused: the pyramid options' own first (levels = 1 on any camera); then gain_init, offset_init,
+// gain_min, gain_max, eps_gain, eps_offset where one is negative (not offset_init) or not finite; then gain_min (above gain_max),
+// gain_init (outside the bounds), offset_init (beyond +-765).
+// Level 0 is the camera itself and fits a camera of any size, as for drf_track_colour_*: with levels = 1 the rule of 8 pixels on
+// a side, which binds the levels above 0, refuses nothing (track_exposure_level_fits is the same for a system's level).
+inline bool track_exposure_level_fits(int W, int H, int L) { return L == 0 || track_level_fits(W, H, L); }
+inline const char *track_exposure_options(const drf_track_exposure_options_t *opt, float voxel_size, int W, int H, TrackExposureOpt &o) {
+  const bool single = opt && opt->pyramid.levels == 1;
+  if (const char *bad = track_pyramid_options(opt ? &opt->pyramid : nullptr, voxel_size, single ? std::max(W, kTrackMinLevelSide) : W,
+                                              single ? std::max(H, kTrackMinLevelSide) : H, o.p))
+    return bad;
+  static const drf_track_exposure_options_t zero = {};
+  const drf_track_exposure_options_t &u = opt ? *opt : zero;
+  if (!(u.gain_init >= 0.0f) || !std::isfinite(u.gain_init)) return "gain_init";
+  if (!std::isfinite(u.offset_init)) return "offset_init";
+  if (!(u.gain_min >= 0.0f) || !std::isfinite(u.gain_min)) return "gain_min";
+  if (!(u.gain_max >= 0.0f) || !std::isfinite(u.gain_max)) return "gain_max";
+  if (!(u.eps_gain >= 0.0) || !std::isfinite(u.eps_gain)) return "eps_gain";
+  if (!(u.eps_offset >= 0.0) || !std::isfinite(u.eps_offset)) return "eps_offset";
+  o.gain_init = u.gain_init != 0.0f ? (double)u.gain_init : 1.0;
+  o.offset_init = (double)u.offset_init;
+  o.gain_min = u.gain_min != 0.0f ? (double)u.gain_min : 0.25;
+  o.gain_max = u.gain_max != 0.0f ? (double)u.gain_max : 4.0;
+  o.eps_gain = u.eps_gain != 0.0 ? u.eps_gain : 1e-4;
+  o.eps_offset = u.eps_offset != 0.0 ? u.eps_offset : 1e-2;
+  if (o.gain_min > o.gain_max) return "gain_min";
+  if (o.gain_init < o.gain_min || o.gain_init > o.gain_max) return "gain_init";
+  if (o.offset_init < -kExposureOffsetMax || o.offset_init > kExposureOffsetMax) return "offset_init";
+  return nullptr;
+}
+// What the loops hold beside the pose (PoseState's interface): G and B, the 17 sums of the last evaluation -- an evaluator leaves
+// them in ext next to the 28 it hands the loop -- the bounds and thresholds, and how many evaluations held the exposure.
+struct ExposureState {
+  double gain = 1.0, offset = 0.0, ext[17] = {};
+  double gain_min = 0.25, gain_max = 4.0, eps_gain = 1e-4, eps_offset = 1e-2;
+  uint64_t held = 0;
+  double good[2] = {1.0, 0.0}, level[2] = {1.0, 0.0};
+  ExposureState() = default;
+  explicit ExposureState(const TrackExposureOpt &o)
+      : gain(o.gain_init), offset(o.offset_init), gain_min(o.gain_min), gain_max(o.gain_max), eps_gain(o.eps_gain), eps_offset(o.eps_offset) {}
+  TrackExposure at() const { return {gain, offset}; }
+  void keep() { good[0] = gain; good[1] = offset; }
+  void back() { gain = good[0]; offset = good[1]; }
+  void level_begin() { level[0] = gain; level[1] = offset; }
+  void level_abandoned() { gain = level[0]; offset = level[1]; }
+  inline int step(const double sums[28], const double c[3], double eps_rot, double eps_trans, MapMotion &m);
+  void evaluate_host(const LocateGrid &lg, const unsigned char *bgr, const float *depth, const TrackModel &t, const TrackColour &tc, const AlignEval &e, double sums[28],
+                     uint64_t counts[5]) {
+    double s45[45];
+    track_exposure_system_host(lg, bgr, depth, t, tc, at(), e, s45, counts);
+    memcpy(sums, s45, 28 * sizeof(double));
+    memcpy(ext, s45 + 28, sizeof ext);
+  }
+};
+// One Gauss-Newton step of the 8 x 8 system from sums[45] at pose m and exposure (G, B).  H is the pose block of sums[0..20], the
+// columns H(i,6) = sums[28 + i], H(i,7) = sums[34 + i], H66, H67, H77 = sums[40..42]; b = sums[21..26], sums[43], sums[44].
+// align_solve's pivot test with top over the 8 diagonals: a failing pivot 0..5 is DRF_ALIGN_DEGENERATE; a failing pivot 6 or 7
+// HOLDS the exposure -- a map of one colour, or no photometric term: the step is align_step on sums[0..27] as it stands, G and B
+// keep their values, held goes up.  Otherwise: a NaN in d is DEGENERATE; CONVERGED (not applied) needs the rotation and the
+// translation below their thresholds, |d6| < eps_gain and |d7| < eps_offset; any other step moves the pose as align_step does,
+// G = min(max(G + d6, gain_min), gain_max), B = min(max(B + d7, -765), 765), and returns -1.
+inline int exposure_step(const double sums[45], const double c[3], double eps_rot, double eps_trans, ExposureState &x, MapMotion &m) {
+  double H[8][8], b[8], d[8];
+  int idx = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) { H[i][j] = sums[idx]; H[j][i] = sums[idx]; ++idx; }
+  for (int i = 0; i < 6; ++i) {
+    H[i][6] = H[6][i] = sums[28 + i];
+    H[i][7] = H[7][i] = sums[34 + i];
+    b[i] = sums[21 + i];
+  }
+  H[6][6] = sums[40]; H[6][7] = H[7][6] = sums[41]; H[7][7] = sums[42];
+  b[6] = sums[43]; b[7] = sums[44];
+  double top = H[0][0];
+  for (int j = 1; j < 8; ++j) top = H[j][j] > top ? H[j][j] : top;
+  if (!(top > 0.0)) return DRF_ALIGN_DEGENERATE;
+  const int failed = align_solve<8>(H, b, top, d);
+  if (failed >= 6) { ++x.held; return align_step(sums, c, eps_rot, eps_trans, m); }
+  if (failed >= 0) return DRF_ALIGN_DEGENERATE;
+  const double oo = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2], vv = (d[3] * d[3] + d[4] * d[4]) + d[5] * d[5];
+  if (!(oo == oo) || !(vv == vv) || !(d[6] == d[6]) || !(d[7] == d[7])) return DRF_ALIGN_DEGENERATE;
+  const double a6 = d[6] < 0.0 ? -d[6] : d[6], a7 = d[7] < 0.0 ? -d[7] : d[7];
+  if (std::sqrt(oo) < eps_rot && std::sqrt(vv) < eps_trans && a6 < x.eps_gain && a7 < x.eps_offset) return DRF_ALIGN_CONVERGED;
+  align_move(d, oo, c, m);
+  const double G = x.gain + d[6], B = x.offset + d[7];
+  x.gain = std::min(std::max(G, x.gain_min), x.gain_max);
+  x.offset = std::min(std::max(B, -kExposureOffsetMax), kExposureOffsetMax);
+  return -1;
+}
+inline int ExposureState::step(const double sums[28], const double c[3], double eps_rot, double eps_trans, MapMotion &m) {
+  double s45[45];
+  memcpy(s45, sums, 28 * sizeof(double));
+  memcpy(s45 + 28, ext, sizeof ext);
+  return exposure_step(s45, c, eps_rot, eps_trans, *this, m);
+}
+// the call's result from level 0's and the state it ended in
+inline void exposure_result(const drf_align_result_t &pose, const ExposureState &x, const uint64_t last5[5], drf_exposure_result_t &res) {
+  res.pose = pose;
+  res.gain = x.gain; res.offset = x.offset;
+  memcpy(res.ext, x.ext, sizeof res.ext);
+  res.photometric = last5[4]; res.held = x.held;
+}
+// One evaluation at level L on the CPU: track_pyramid_system_host's reductions and model map, then the system above.
+inline void track_exposure_system_at_host(const LocateGrid &lg0, int L, const unsigned char *bgr, const float *depth, const unsigned char *model_bgr,
+                                          const float *model_depth, const float *model_pose16, const float *pose16, double gain, double offset, const TrackExposureOpt &o,
+                                          float voxel_size, double sums[45], uint64_t counts[5]) {
+  const TrackColourOpt lo = track_level_options(o.p, L);
+  const LocateGrid lg = track_level_grid(lg0, L);
+  const size_t npix = (size_t)lg.W * (size_t)lg.H;
+  std::vector<float> fd(npix), md(npix), Ym(npix);
+  std::vector<unsigned char> fc(3 * npix), mc(3 * npix);
+  track_reduce_host(lg0.W, lg0.H, L, lo.t.max_jump, bgr, depth, fc.data(), fd.data());
+  track_reduce_host(lg0.W, lg0.H, L, lo.t.max_jump, model_bgr, model_depth, mc.data(), md.data());
+  std::vector<TrackPixel> map(npix);
+  track_model_colour_host(lg, lo.t.max_jump, md.data(), mc.data(), map.data(), Ym.data());
+  double c_src[3];
+  locate_centre_src(lo.t.centre_depth, voxel_size, c_src);
+  const AlignEval e = align_eval(map_motion(pose16, voxel_size), c_src, lo.t.a, voxel_size);
+  track_exposure_system_host(lg, fc.data(), fd.data(), track_model(model_pose16, lo.t, voxel_size, map.data()), track_colour(lo, Ym.data()), {gain, offset}, e, sums, counts);
+}
+// The whole tracking on the CPU over a renderer of the full-resolution images: track_pyramid_frame_host with the exposure as the
+// solver's state -- the library's reference for drf_track_exposure_frame, and what the sanitizer program runs.
+template <class RenderBoth>
+inline void track_exposure_frame_host(const LocateGrid &lg0, const unsigned char *bgr, const float *depth, RenderBoth &&render_both, const float *pose_init16,
+                                      const TrackExposureOpt &o, float voxel_size, drf_exposure_result_t &res, uint64_t stats8[8], uint64_t level4[kTrackMaxLevels][4],
+                                      std::vector<std::array<double, 28>> *trace = nullptr) {
+  ExposureState x(o);
+  drf_align_result_t r;
+  uint64_t last5[5] = {0, 0, 0, 0, 0};
+  track_pyramid_frame_host(lg0, bgr, depth, render_both, pose_init16, o.p, voxel_size, r, stats8, level4, last5, trace, &x);
+  exposure_result(r, x, last5, res);
 }
 
 // ---- searching a pose lattice (drf_score_poses / drf_search_frame; DESIGN.md §7c "Searching a pose lattice").  Every call above
@@ -1150,7 +1408,7 @@ inline std::vector<size_t> search_select(const double *score, size_t n, int top_
 // above is geometric: on one wall every in-plane offset of the lattice scores alike.  Every voxel carries a colour, and the fetch
 // of a corner already returns it as the second word of its load; the colour score keeps those bytes and adds an appearance term
 // per valid sample -- the trilinear model intensity against the frame's pixel -- into a second sum, photo, reduced exactly as cost
-// is.  cost and counts keep drf_score_poses' bits.  Frame and map share their exposure, as for drf_track_colour_*.
+// is.  cost and counts keep drf_score_poses' bits.  Frame and map share their exposure, as for drf_track_colour_* (drf_track_exposure_* solve for it).
 struct ScoreColourOpt {  // drf_score_colour_options_t with its defaults resolved
   static constexpr bool colour = true;
   ScoreOpt s;

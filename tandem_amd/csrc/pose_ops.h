@@ -1,6 +1,6 @@
 // pose_ops.h -- a camera pose from a frame, as components over FusionCore: drf_locate_*, drf_track_*, drf_track_colour_*,
-// drf_track_pyramid_* (the rules: pose_host.h; the kernels: locate_kernels.h, track_kernels.h, track_colour_kernels.h,
-// track_pyramid_kernels.h, k_align_fold of align_kernels.h; DESIGN.md "Where the frame-pose code lives", "Where rendering and the
+// drf_track_pyramid_*, drf_track_exposure_* (the rules: pose_host.h; the kernels: locate_kernels.h, track_kernels.h,
+// track_colour_kernels.h, track_pyramid_kernels.h, track_exposure_kernels.h, k_align_fold of align_kernels.h; DESIGN.md "Where the frame-pose code lives", "Where rendering and the
 // frame pose live").  FramePose is what the families open with, written once; FrameLocator is the localisation with its scope over
 // the map staging (render_ops.h MapStage) and the restaging rule (engine_host.h LocateStageCursor); FrameTracker the three tracking
 // families, whose model render goes through MapRenderer's plan_render_call and render_passes.  Of the call order they only ask
@@ -214,8 +214,9 @@ class FrameLocator {
 };
 
 // A frame tracked against the ray-cast model: by its depth alone (drf_track_*; DESIGN.md §7c "Tracking a depth frame against the
-// ray-cast model"), with the photometric term (drf_track_colour_*; "Tracking with colour"), or coarse to fine (drf_track_reduce,
-// drf_track_pyramid_*; "Tracking coarse to fine").  The rule: pose_host.h track_normal / track_point / track_colour_point /
+// ray-cast model"), with the photometric term (drf_track_colour_*; "Tracking with colour"), coarse to fine (drf_track_reduce,
+// drf_track_pyramid_*; "Tracking coarse to fine"), or with the frame's gain and offset beside the pose (drf_track_exposure_*;
+// "Tracking under a change of exposure").  The rule: pose_host.h track_normal / track_point / track_colour_point /
 // track_loop and track_level_grid / track_reduce_host / track_pyramid_schedule.  One path for the three families (what it
 // guarantees: DESIGN.md "Where the frame-pose code lives").  Every launch is given its level, and level 0 is the single-level
 // call (track_level_grid returns the grid itself), so drf_track_* and drf_track_colour_* are the schedule with one level; colour
@@ -236,15 +237,27 @@ class FrameTracker {
   TrackSide &pyramid() { return tp_; }    // drf_search_colour_frame on the side of drf_track_pyramid_frame
   // The body of every *_frame call: the frame reduced once to every level above 0, then track_pyramid_schedule over track_loop;
   // po.levels = 1 is the single-level call.  r: level 0's result; last: the counters of its last evaluation.
+  // x: null, or the exposure of drf_track_exposure_frame -- the solver's state beside the pose (pose_host.h ExposureState): it
+  // carries from level to level, and an abandoned level hands on the one it started from.
   void track_levels(const char *who, TrackSide &s, bool colour, const TrackPyramidOpt &po, const FramePair &frame, const float *pose16, drf_align_result_t &r,
-                    uint64_t last[5]) {
+                    uint64_t last[5], ExposureState *x = nullptr) {
     with_track(who, s, colour, frame, po.c.t.step, [&](TrackCall &t) {
       for (int L = 1; L < po.levels; ++L) launch_reduce(t.b.depth, t.b.bgr, L, track_level_options(po, L).t.max_jump, t.b.pyr[L], t.b.pyr_bgr[L]);
       track_pyramid_schedule([&](int L, const float *p16, const TrackColourOpt &lo, drf_align_result_t &lr, uint64_t *lc, uint64_t *st2) {
         auto render = [&](const float *p) { track_render(t, L, lo, p); };
-        auto eval = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t *c) { track_evaluate(t, L, lo, e, mp16, sums, c); };
-        if (colour) track_loop<5>(render, eval, p16, lo.t, core_.o.voxel_size, lr, lc, st2);
-        else track_loop<4>(render, eval, p16, lo.t, core_.o.voxel_size, lr, lc, st2);
+        auto eval = [&](const AlignEval &e, const float *mp16, double sums[28], uint64_t *c) {
+          if (x) track_evaluate_exposure(t, L, lo, e, mp16, *x, sums, c);
+          else track_evaluate(t, L, lo, e, mp16, sums, c);
+        };
+        if (x) {
+          x->level_begin();
+          track_loop<5>(render, eval, p16, lo.t, core_.o.voxel_size, lr, lc, st2, nullptr, x);
+          if (L > 0 && (lr.status == DRF_ALIGN_LOST || lr.status == DRF_ALIGN_DEGENERATE)) x->level_abandoned();
+        } else if (colour) {
+          track_loop<5>(render, eval, p16, lo.t, core_.o.voxel_size, lr, lc, st2);
+        } else {
+          track_loop<4>(render, eval, p16, lo.t, core_.o.voxel_size, lr, lc, st2);
+        }
       }, t.fg.lg, pose16, po, r, s.stats, s.level, last);
     });
   }
@@ -330,6 +343,44 @@ class FrameTracker {
     return tp_.level[level];
   }
 
+  // The exposure family (DESIGN.md §7c "Tracking under a change of exposure"): the pyramid's calls with colour and the exposure in
+  // the solver's state, on a side of their own.  The colour images are judged behind the options.
+  void track_exposure_system(const char *who, int level, const FramePair &frame, const FramePair &model, const float *model_pose16, const float *pose16, double gain,
+                             double offset, const drf_track_exposure_options_t *opt, double *sums, uint64_t *counts) {
+    te_.reset();
+    if (!frame.depth || !model.depth || !model_pose16 || !pose16 || !sums || !counts) fail(DR_ERR_ARG, "%s: null argument", who);
+    const TrackExposureOpt xo = track_exposure_resolve(who, opt, &level);
+    if (!frame.bgr || !model.bgr) fail(DR_ERR_ARG, "%s: bgr is null: the call needs the colour images", who);
+    if (!std::isfinite(gain) || !std::isfinite(offset)) fail(DR_ERR_ARG, "%s: the exposure (%g, %g) is not finite", who, gain, offset);
+    frame_.frame_prologue(who, nullptr, pose16, model_pose16);
+    ExposureState x(xo);
+    x.gain = gain; x.offset = offset;
+    double pose_sums[28];
+    track_system_at(who, te_, true, level, xo.p, frame, model, model_pose16, pose16, pose_sums, counts, 5, &x);
+    memcpy(sums, pose_sums, sizeof pose_sums);
+    memcpy(sums + 28, x.ext, sizeof x.ext);
+  }
+  std::string track_exposure_frame(const char *who, const FramePair &frame, const float *pose16, const drf_track_exposure_options_t *opt, float *pose16_out,
+                                   drf_exposure_result_t *res) {
+    te_.reset();
+    if (!frame.depth || !pose16 || !pose16_out) fail(DR_ERR_ARG, "%s: null argument", who);
+    const TrackExposureOpt xo = track_exposure_resolve(who, opt, nullptr);
+    if (!frame.bgr) fail(DR_ERR_ARG, "%s: bgr is null: the call needs the colour image", who);
+    frame_.frame_prologue(who, nullptr, pose16, nullptr);
+    ExposureState x(xo);
+    drf_align_result_t r;
+    uint64_t last[5] = {0, 0, 0, 0, 0};
+    track_levels(who, te_, true, xo.p, frame, pose16, r, last, &x);
+    if (res) exposure_result(r, x, last, *res);
+    return track_note(who, te_, r, last,
+                      "; " + std::to_string((unsigned long long)te_.stats[6]) + " levels, " + std::to_string((unsigned long long)te_.stats[7]) + " abandoned, ", pose16_out, nullptr);
+  }
+  const uint64_t *track_exposure_stats() const { return te_.stats; }
+  const uint64_t *track_exposure_level_stats(int level) const {
+    if (level < 0 || level >= kTrackMaxLevels) fail(DR_ERR_ARG, "drf_track_exposure_level_stats: level %d is outside 0..%d", level, kTrackMaxLevels - 1);
+    return te_.level[level];
+  }
+
  private:
   // with_track does what the calls share behind the prologue -- device scratch that is sized once, the frame's intake, the
   // statistics reset when an exception passes -- and hands body the call: the spans and what track_launch_model, track_evaluate
@@ -344,15 +395,15 @@ class FrameTracker {
     const float *depth; const unsigned char *bgr;      // the frame at full resolution: the caller's device images, or the spans a host frame went to
   };
   struct TrackCall { const char *who; TrackSide &s; bool colour; FrameGrid fg; TrackBufs b; };
-  // The three layouts (DESIGN.md "What the carver guarantees").  What of a render nobody reads once the model kernel runs may lie
+  // The layouts (DESIGN.md "What the carver guarantees").  What of a render nobody reads once the model kernel runs may lie
   // in the bytes that kernel then overwrites with the model map: a banded render's per-pixel ray state in both single-level
   // layouts, and in the geometric one the colour image too (with colour k_track_model_colour reads it: it has the span model_bgr).
-  // The pyramid's is sized for five levels with nothing aliased.
+  // The pyramid's is sized for five levels with nothing aliased; the exposure's is the pyramid's with 45 doubles per group.
   TrackBufs track_spans(TrackSide &s) {
     TrackBufs b{};
     const size_t max_groups = frame_.frame_grid(1).max_groups;
-    auto head = [&](Carver &c, size_t counters) {
-      b.partial = c.take<double>(max_groups * 28);
+    auto head = [&](Carver &c, size_t counters, size_t width = 28) {
+      b.partial = c.take<double>(max_groups * width);
       b.counts = c.take<unsigned long long>(counters);  // four that k_align_fold hands back; with colour the fifth (and one unused)
       b.flag = c.take<int>(1);                          // the ray-cast's flag counter
       b.map = c.take<TrackPixel>(core_.npix, 32);            // the model map
@@ -379,7 +430,7 @@ class FrameTracker {
     } else {
       auto level_pixels = [&](int L) { return std::max<size_t>(1, (size_t)(core_.o.width >> L) * (size_t)(core_.o.height >> L)); };
       carve(s.buf, core_.int_stream, [&](Carver &c) {
-        head(c, 6);
+        head(c, 6, &s == &te_ ? 45 : 28);
         b.render_band = c.take<RayState>(core_.npix, 8);
         b.model = c.take<float>(core_.npix);
         b.level = c.take<float>(level_pixels(1));
@@ -458,6 +509,25 @@ class FrameTracker {
     });
     if (t.colour) c[4] = *tc_fifth_;
   }
+  // one evaluation of level L under the exposure x: 45 sums and five counters back through the pair; the loop is handed the 28 of
+  // the pose, the 17 others are left in x.ext for its step
+  void track_evaluate_exposure(const TrackCall &t, int L, const TrackColourOpt &lo, const AlignEval &e, const float *model_pose16, ExposureState &x, double sums[28],
+                               uint64_t c[5]) {
+    const TrackBufs &b = t.b;
+    const LocateGrid lg = track_level_grid(t.fg.lg, L);
+    const int total = (int)locate_positions(lg), groups = (int)locate_groups(lg);
+    const float *fd = L == 0 ? b.depth : b.pyr[L];
+    const unsigned char *fc = L == 0 ? b.bgr : b.pyr_bgr[L];
+    const TrackModel tm = track_model(model_pose16, lo.t, core_.o.voxel_size, b.map);
+    double s45[45];
+    mio_.evaluate_exposure(b.partial, groups, b.counts, s45, c, [&] {
+      hipLaunchKernelGGL(k_track_exposure, dim3(cdiv(groups, 4)), dim3(256), 0, core_.int_stream, fd, fc, lg, e, tm, track_colour(lo, b.Ym), x.at(), groups, total, b.partial,
+                         b.counts);
+      DR_HIP(hipGetLastError());
+    });
+    memcpy(sums, s45, 28 * sizeof(double));
+    memcpy(x.ext, s45 + 28, sizeof x.ext);
+  }
   // the model of a *_frame round: the renderer's one submit at full resolution into the spans, then level L's model map
   void track_render(const TrackCall &t, int L, const TrackColourOpt &lo, const float *pose16) {
     Render &rd = t.s.render;
@@ -480,7 +550,7 @@ class FrameTracker {
   // calls and copied into the spans by the pyramid's: track_launch_model could read that one in place too, but the copy is part
   // of what drf_track_pyramid_system_device enqueues, and stays.
   void track_system_at(const char *who, TrackSide &s, bool colour, int level, const TrackPyramidOpt &po, const FramePair &frame, const FramePair &model,
-                       const float *model_pose16, const float *pose16, double *sums, uint64_t *counts, int n) {
+                       const float *model_pose16, const float *pose16, double *sums, uint64_t *counts, int n, ExposureState *x = nullptr) {
     with_track(who, s, colour, frame, po.c.t.step, [&](TrackCall &t) {
       const TrackBufs &b = t.b;
       const TrackColourOpt lo = track_level_options(po, level);
@@ -499,7 +569,9 @@ class FrameTracker {
       double c_src[3];
       locate_centre_src(lo.t.centre_depth, core_.o.voxel_size, c_src);
       uint64_t c[5] = {0, 0, 0, 0, 0};
-      track_evaluate(t, level, lo, align_eval(map_motion(pose16, core_.o.voxel_size), c_src, lo.t.a, core_.o.voxel_size), model_pose16, sums, c);
+      const AlignEval e = align_eval(map_motion(pose16, core_.o.voxel_size), c_src, lo.t.a, core_.o.voxel_size);
+      if (x) track_evaluate_exposure(t, level, lo, e, model_pose16, *x, sums, c);
+      else track_evaluate(t, level, lo, e, model_pose16, sums, c);
       for (int i = 0; i < n; ++i) counts[i] = c[i];
       s.stats[0] = (uint64_t)locate_positions(track_level_grid(t.fg.lg, level)); s.stats[1] = c[0]; s.stats[2] = c[1]; s.stats[3] = 1; s.stats[6] = 1;
       s.level[level][2] = 1; s.level[level][3] = c[1];
@@ -525,13 +597,24 @@ class FrameTracker {
            core_.o.width);
     return po;
   }
+  // level null: drf_track_exposure_frame; otherwise the level of a drf_track_exposure_system, judged with the options.
+  TrackExposureOpt track_exposure_resolve(const char *who, const drf_track_exposure_options_t *opt, const int *level) {
+    TrackExposureOpt xo;
+    if (const char *bad = track_exposure_options(opt, core_.o.voxel_size, core_.o.width, core_.o.height, xo))
+      fail(DR_ERR_ARG, "%s: option %s is negative, not finite or out of range (levels <= %d, every level at least %d pixels on a side; gain_min <= gain_init <= gain_max, |offset_init| <= 765)",
+           who, bad, kTrackMaxLevels, kTrackMinLevelSide);
+    if (level && !track_exposure_level_fits(core_.o.width, core_.o.height, *level))
+      fail(DR_ERR_ARG, "%s: level %d is outside 0..%d or below %d pixels on a side of the %dx%d camera", who, *level, kTrackMaxLevels - 1, kTrackMinLevelSide, core_.o.height,
+           core_.o.width);
+    return xo;
+  }
 
   FramePose &frame_;
   FusionCore &core_;
   BlockStreamer &streamer_;
   MapIo &mio_;
   MapRenderer &renderer_;
-  TrackSide tk_, tc_, tp_;                  // drf_track_*, drf_track_colour_*, drf_track_reduce / drf_track_pyramid_*: each its own scratch, statistics and model render (with_track)
+  TrackSide tk_, tc_, tp_, te_;             // drf_track_*, drf_track_colour_*, drf_track_reduce / drf_track_pyramid_*, drf_track_exposure_*: each its own scratch, statistics and model render (with_track)
   unsigned long long *tc_fifth_ = nullptr;  // pinned: the fifth counter of an evaluation with colour
 };
 

@@ -40,6 +40,21 @@ class AlignResult(collections.namedtuple("AlignResult", "T T32 sums samples vali
     __slots__ = ()
 
 
+class ExposureResult(collections.namedtuple("ExposureResult", AlignResult._fields + ("gain", "offset", "ext", "photometric", "held"))):
+    """drf_exposure_result_t: AlignResult's fields (level 0's), the gain and offset the call ended on (frame intensity ~ gain *
+    model intensity + offset, the offset in units of the three-channel sum), ext (17,) = sums[28..44] of the last evaluation, the
+    photometric terms it added, and the evaluations whose step held the exposure."""
+    __slots__ = ()
+
+
+def compensate_exposure(bgr, gain, offset):
+    """The frame's colour image brought to the map's exposure, on the host: per channel clip(floor((c - offset / 3) / gain + 0.5),
+    0, 255), the inverse of frame ~ gain * model + offset with the offset split evenly over the three channels.  bgr (H, W, 3)
+    uint8; gain and offset as track_exposure_frame returns them.  What saturated in the frame stays lost."""
+    c = np.asarray(bgr, np.uint8).astype(np.float64)
+    return np.clip(np.floor((c - float(offset) / 3.0) / float(gain) + 0.5), 0.0, 255.0).astype(np.uint8)
+
+
 class AlignError(RuntimeError):
     """A registration that ran but found no pose (ALIGN_DEGENERATE, ALIGN_LOST); .result is the AlignResult."""
 
@@ -699,6 +714,62 @@ class DrFusion:
         """Level `level` of the last track_pyramid_frame: (status, renders, evaluations, valid samples at its last evaluation)."""
         out = (C.c_uint64 * 4)()
         check(self._L.drf_track_pyramid_level_stats(self._h, int(level), out))
+        return tuple(int(v) for v in out)
+
+    # ---- tracking under a change of exposure (include/dr_mi355x.h drf_track_exposure_frame, DESIGN.md "Tracking under a change of exposure") ----
+    _EXPOSURE_FIELDS = ("gain_init", "offset_init", "gain_min", "gain_max", "eps_gain", "eps_offset")
+
+    @staticmethod
+    def _track_exposure_options(levels, coarse_renders, photo_weight, opt):
+        own = {k: opt.pop(k) for k in DrFusion._EXPOSURE_FIELDS if k in opt}
+        pyramid = DrFusion._track_pyramid_options(levels, coarse_renders, photo_weight, opt)
+        if pyramid is None and not own:
+            return None
+        return _lib.TrackExposureOptions(pyramid or _lib.TrackPyramidOptions(), **own)
+
+    def track_exposure_system(self, level, bgr, depth, model_bgr, model_depth, model_pose, pose, gain=1.0, offset=0.0, levels=0, coarse_renders=0, photo_weight=0.0, **opt):
+        """One evaluation at `level` of the 8 x 8 system of pose, gain and offset, at the pose and the exposure (gain, offset):
+        (sums (45,) float64 -- [0..27] track_pyramid_system's layout, [28..44] the gain and offset columns -- and (samples, valid,
+        unassociated, rejected, photometric terms added)).  At (1, 0) sums[:28] are track_pyramid_system's bits.  All four images
+        on the host or all integer device pointers; the colour images are required."""
+        o = self._track_exposure_options(levels, coarse_renders, photo_weight, dict(opt))
+        dev, args, keep = self._track_images([(np.uint8, 3, bgr), (np.float32, 1, depth), (np.uint8, 3, model_bgr), (np.float32, 1, model_depth)])
+        pose = np.ascontiguousarray(pose, np.float32).reshape(16)
+        mpose = np.ascontiguousarray(model_pose, np.float32).reshape(16)
+        sums, counts = np.zeros(45, np.float64), (C.c_uint64 * 5)()
+        call = self._L.drf_track_exposure_system_device if dev else self._L.drf_track_exposure_system
+        check(call(self._h, int(level), *args, fptr(mpose), fptr(pose), float(gain), float(offset), C.byref(o) if o else None, sums.ctypes.data_as(_lib.f64p), counts))
+        return sums, tuple(int(v) for v in counts)
+
+    def track_exposure_frame(self, bgr, depth, pose_init, raise_on_failure=True, levels=0, coarse_renders=0, photo_weight=0.0, **opt):
+        """track_pyramid_frame with colour for a frame whose exposure differs from the map's: gain and offset (frame ~ gain * model
+        + offset) are solved next to the pose, from gain_init (0 = 1) and offset_init, the gain kept in [gain_min, gain_max] (0 =
+        0.25, 4).  On a map of one colour the exposure is held and the call is track_pyramid_frame bit for bit.  Returns an
+        ExposureResult; compensate_exposure(bgr, result.gain, result.offset) is the frame to integrate."""
+        o = self._track_exposure_options(levels, coarse_renders, photo_weight, dict(opt))
+        dev, args, keep = self._track_images([(np.uint8, 3, bgr), (np.float32, 1, depth)])
+        pose = np.ascontiguousarray(pose_init, np.float32).reshape(16)
+        T32, r = np.zeros(16, np.float32), _lib.ExposureResultStruct()
+        call = self._L.drf_track_exposure_frame_device if dev else self._L.drf_track_exposure_frame
+        check(call(self._h, *args, fptr(pose), C.byref(o) if o else None, fptr(T32), C.byref(r)))
+        try:
+            a = self._align_result(r.pose, T32, raise_on_failure)
+        except AlignError as e:
+            a = e.result
+            e.result = ExposureResult(*a, gain=float(r.gain), offset=float(r.offset), ext=np.array(r.ext, np.float64), photometric=int(r.photometric), held=int(r.held))
+            raise
+        return ExposureResult(*a, gain=float(r.gain), offset=float(r.offset), ext=np.array(r.ext, np.float64), photometric=int(r.photometric), held=int(r.held))
+
+    def track_exposure_stats(self):
+        """Last track_exposure_*: track_pyramid_stats' fields; the device bytes are a buffer of these calls' own."""
+        out = (C.c_uint64 * 8)()
+        check(self._L.drf_track_exposure_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def track_exposure_level_stats(self, level):
+        """Level `level` of the last track_exposure_frame: (status, renders, evaluations, valid samples at its last evaluation)."""
+        out = (C.c_uint64 * 4)()
+        check(self._L.drf_track_exposure_level_stats(self._h, int(level), out))
         return tuple(int(v) for v in out)
 
     def set_render_scope(self, scope, stage_capacity_blocks=0):

@@ -149,6 +149,25 @@ public:
     check(drf_track_pyramid_frame(impl, bgr, depth, pose_init16, opt, pose16_out, &res));
     return res.status;
   }
+  // the same for a frame whose exposure differs from the map's (dr_mi355x.h drf_track_exposure_frame): gain and offset of
+  // frame ~ gain * model + offset are solved next to the pose and handed out (either may be null).  bgr is required; opt null = 3
+  // levels, the gain from 1 within [0.25, 4].  Returns level 0's status.  Compensate the frame with them before IntegrateScanAsync.
+  int TrackExposureFrame(unsigned char const *bgr, float const *depth, float const *pose_init16, float *pose16_out, double *gain_out = nullptr,
+                         double *offset_out = nullptr, drf_track_exposure_options_t const *opt = nullptr) {
+    drf_exposure_result_t res;
+    check(drf_track_exposure_frame(impl, bgr, depth, pose_init16, opt, pose16_out, &res));
+    if (gain_out) *gain_out = res.gain;
+    if (offset_out) *offset_out = res.offset;
+    return res.pose.status;
+  }
+  // one evaluation of its 8 x 8 system at `level`, a pose and an exposure against a model pair: sums[45], counts[5]
+  void TrackExposureSystem(int level, unsigned char const *bgr, float const *depth, unsigned char const *model_bgr, float const *model_depth,
+                           float const *model_pose16, float const *pose16, double gain, double offset, double *sums45, unsigned long long *counts5,
+                           drf_track_exposure_options_t const *opt = nullptr) {
+    uint64_t c[5];
+    check(drf_track_exposure_system(impl, level, bgr, depth, model_bgr, model_depth, model_pose16, pose16, gain, offset, opt, sums45, c));
+    for (int i = 0; i < 5; ++i) counts5[i] = c[i];
+  }
   // n poses16 (n x 16 floats, camera-to-world) scored against the resident map in one kernel (dr_mi355x.h drf_score_poses): score[n],
   // lower is better; cost and counts (n x 4: samples, valid, unobserved, outside) may be null.  opt null = its defaults.
   void ScorePoses(float const *depth, float const *poses16, size_t n, double *score, double *cost = nullptr, uint32_t *counts = nullptr,
