@@ -939,11 +939,22 @@ int drf_track_exposure_level_stats(drf_t *h, int level, uint64_t out[4]);
  * (drf_locate_frame's rule) and picks one.  It is a geometric score: it has no appearance term and is ambiguous where geometry
  * repeats (two alike corridors score alike) -- the runner-up entries of the result show it; drf_search_colour_frame, further below,
  * adds an appearance term from the voxel colours for frames that have a colour image.
- * SCOPE.  The score reads the resident map only: with streaming on, blocks in the host store read as absent (their samples are
- * UNOBSERVED) and drf_search_stats()[7] tells how many there are; DRF_LOCATE_MAP does not apply to the score.  The refinement
- * stages keep their own scopes (drf_set_render_scope for the tracking's renders, drf_set_locate_scope for the localisation).  The
- * map, the public render buffers and the streaming state are untouched; drf_track_stats, drf_locate_stats and
- * drf_locate_stage_stats afterwards describe the last refinement stage that ran.
+ * SCOPE (drf_set_search_scope, below).  DRF_SEARCH_RESIDENT, the default: the score reads the resident map only: with streaming
+ * on, blocks in the host store read as absent (their samples are UNOBSERVED) and drf_search_stats()[7] tells how many there are;
+ * DRF_LOCATE_MAP does not apply to the score.  What applies is DRF_SEARCH_MAP: the score stage of all four calls and their _device
+ * forms, the colour search's final re-score included, reads the pool and the host store together -- cost, photo, counts and score of
+ * every candidate, all_scores, the selection and so the entries, the winner and the pose are, bit for bit, those of an engine whose
+ * pool holds the whole map, whatever the split between pool and store, the staging's capacity and the chunking are.  No block
+ * moves.  The host plans the table once (DESIGN.md §7c "Searching the whole map"): a run of candidates with one rotation whose
+ * camera centres lie in a box is served by the render scope's selection at the box's centre, widened by the box's half-diagonal;
+ * whole table entries first, halved along ix while a selection exceeds stage_capacity_blocks (0: min(num_blocks, 8192), the
+ * render's default), neighbours merged while their union fits; each pass is staged once and scored in chunks.  A single ix-slab
+ * of the lattice (a single pose of drf_score_poses) that can read more than the capacity: DR_ERR_CAPACITY before anything is
+ * evaluated, naming both counts, drf_set_search_scope and drf_stream_in_region; nothing is written and all statistics are 0.
+ * With an empty store or a pass that selects nothing the resident kernel runs and nothing is staged.  The refinement stages keep
+ * their own scopes (drf_set_render_scope for the tracking's renders, drf_set_locate_scope for the localisation): a search of the
+ * whole map wants all three set.  The map, the public render buffers and the streaming state are untouched; drf_track_stats,
+ * drf_locate_stats and drf_locate_stage_stats afterwards describe the last refinement stage that ran.
  * The rule (one text, pose_host.h, compiled for the host and for the kernels; double and fp32 without contraction; + - * / floor):
  *   sample    drf_locate_*'s, to the letter: the grid of stride step, the sample test, the point g, q = Rd g + tv, b = floor(q),
  *             f = (float)(q - b), the eight voxels, UNOBSERVED (a corner of weight < min_weight, or q outside (-2^30, 2^30)), the
@@ -1034,6 +1045,16 @@ int drf_search_frame_device(drf_t *h, const void *d_depth, const float *anchors1
  * evaluations of the refinement, [6] device bytes held by the score stage, [7] blocks in the host store at the call (all 0 after a
  * call that was refused) */
 int drf_search_stats(drf_t *h, uint64_t out[8]);
+/* What the score stage of drf_score_poses, drf_score_colour_poses, drf_search_frame, drf_search_colour_frame and their _device forms
+ * reads (SCOPE above).  Unknown scope: DR_ERR_ARG; between RenderAsync and GetRenderResult: DR_ERR_PROTOCOL, as for
+ * drf_set_locate_scope (the render, the locate and the search scope share the staging, which holds the largest of their needs). */
+#define DRF_SEARCH_RESIDENT 0   /* the default: today's behaviour, bit for bit */
+#define DRF_SEARCH_MAP      1
+int drf_set_search_scope(drf_t *h, int scope, size_t stage_capacity_blocks);
+/* last search call of either family: [0] stagings made, [1] blocks in the largest staging, [2] blocks staged in total, [3] score
+ * launches that read a staging, the final re-score's included (all 0 in resident scope, with nothing to stage, or after a call that
+ * was refused) */
+int drf_search_stage_stats(drf_t *h, uint64_t out[4]);
 /* The search with an appearance term from the voxel colours (no reference counterpart; DESIGN.md §7c "Searching with colour").  The
  * score above is geometric, and it is ambiguous wherever geometry says nothing: on ONE wall every in-plane offset of the lattice
  * scores alike, and the winner is whatever the tie rule picks.  Every voxel carries a colour, and the score's fetch of a corner
@@ -1066,12 +1087,12 @@ int drf_search_stats(drf_t *h, uint64_t out[8]);
  * wins.  score_only, the LOST convention and the statuses are drf_search_frame's.
  * Device scratch: drf_search_frame's plus 4 bytes per grid position (yf), a 40-byte record per candidate of a chunk (cost, photo,
  * counts[4], score) instead of 32, and a colour image (3 bytes per pixel) for a host-given frame.
- * SCOPE and side effects are drf_search_frame's: the resident map only, stored blocks counted in [7]; the map, the public render
+ * SCOPE and side effects are drf_search_frame's: the resident map only by default, stored blocks counted in [7], and with
+ * drf_set_search_scope(DRF_SEARCH_MAP) pool and host store together, the final re-score included; the map, the public render
  * buffers and the streaming state untouched; drf_track_pyramid_stats and drf_locate_stats describe the last refinement stage that
  * ran.  drf_search_stats describes the last call of either family; the final re-score is not counted in [0] or [3].
  * OUT OF SCOPE: exposure or affine brightness (frame and map share their exposure here; drf_track_exposure_frame solves for it, and
- * the tracking stage of this search keeps the pyramid rule); the stored blocks of
- * a streamed map; selection on the device, a coarse-to-fine lattice, rotations about the camera's own axes.
+ * the tracking stage of this search keeps the pyramid rule); selection on the device, a coarse-to-fine lattice, rotations about the camera's own axes.
  * Legality and refusals follow drf_search_frame's order: a null argument (bgr among them: a null bgr is DR_ERR_ARG -- the
  * geometric call is for frames without colour; for drf_score_colour_poses any of the four outputs but not all may be null); the
  * score or search options, then photo_weight and photo_cap (negative or not finite), then the track, then the locate options; the

@@ -183,6 +183,8 @@ SIGNATURES = {
     "drf_search_frame": (C.c_int, [vp, f32p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f64p]),
     "drf_search_frame_device": (C.c_int, [vp, C.c_void_p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f64p]),
     "drf_search_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "drf_set_search_scope": (C.c_int, [vp, C.c_int, C.c_size_t]),
+    "drf_search_stage_stats": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "drf_score_colour_poses": (C.c_int, [vp, C.c_void_p, f32p, f32p, C.c_size_t, C.c_void_p, f64p, f64p, C.POINTER(C.c_uint32), f64p]),
     "drf_score_colour_poses_device": (C.c_int, [vp, C.c_void_p, C.c_void_p, f32p, C.c_size_t, C.c_void_p, f64p, f64p, C.POINTER(C.c_uint32), f64p]),
     "drf_search_colour_frame": (C.c_int, [vp, C.c_void_p, f32p, f32p, C.c_size_t, f64p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, f32p, C.c_void_p, f64p]),

@@ -82,7 +82,7 @@ class FusionEngine {
   FusionEngine(const drf_options_t &o, int device)
       : core_(o, device), streamer_(core_), mesher_(core_, streamer_), mio_(core_.own, device, o.voxel_size, (size_t)std::min(o.num_blocks, kStageBlocks)),
         stage_(core_, streamer_), renderer_(core_, streamer_, stage_), frame_(core_, streamer_, mio_), locator_(frame_, stage_), tracker_(frame_, renderer_),
-        search_(frame_, tracker_, locator_) {
+        search_(frame_, tracker_, locator_, stage_) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= device) fail(DR_ERR_DEVICE, "DrFusion: no HIP device %d (found %d) -- the MI355X path has no CPU fallback", device, n);
     if (o.block_size != 8) fail(DR_ERR_UNSUPPORTED, "DrFusion: block_size must be 8 (got %d)", o.block_size);
@@ -997,6 +997,8 @@ int drf_search_colour_frame_device(drf_t *h, const void *d_bgr, const void *d_de
                                                 locate_opt, pose16_out, res, all_scores);
   });
 }
+int drf_set_search_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->search().set_search_scope(scope, stage_capacity_blocks); }); }
+int drf_search_stage_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->search().search_stage_stats(out); }); }
 int drf_set_locate_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->locate().set_locate_scope(scope, stage_capacity_blocks); }); }
 int drf_locate_stage_stats(drf_t *h, uint64_t out[4]) { return guarded([&] { eng(h)->locate().locate_stage_stats(out); }); }
 int drf_set_render_scope(drf_t *h, int scope, size_t stage_capacity_blocks) { return guarded([&] { eng(h)->render().set_render_scope(scope, stage_capacity_blocks); }); }

@@ -1,9 +1,12 @@
-// engine_host.h -- two decisions of the DrFusion engine as values with no HIP in them: the order in which its calls may come
-// (CallOrder) and when a map-scope localisation must select and stage stored blocks again (LocateStageCursor).  Plain C++17 over
-// dr_host.h (fail) and fusion_host.h, which includes this header at its end: tests/cpp/engine_host_check.cpp runs both on the CPU.
-// The engine and its components (fusion_core.h, render_ops.h, pose_ops.h) keep everything that touches the device.
+// engine_host.h -- three decisions of the DrFusion engine as values with no HIP in them: the order in which its calls may come
+// (CallOrder), when a map-scope localisation must select and stage stored blocks again (LocateStageCursor), and what the score of
+// a map-scope search stages for which candidates (plan_search_stage).  Plain C++17 over dr_host.h (fail) and fusion_host.h, which
+// includes this header at its end: tests/cpp/engine_host_check.cpp and tests/cpp/search_scope_check.cpp run them on the CPU.
+// The engine and its components (fusion_core.h, render_ops.h, pose_ops.h, search_ops.h) keep everything that touches the device.
 #pragma once
+#include <iterator>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "dr_host.h"
@@ -82,5 +85,90 @@ class LocateStageCursor {
   float pose_[16] = {};
   bool current_ = false;  // the selection has been handed out by at()
 };
+
+// Which stored blocks the score stage of a search in map scope stages, and for which candidates (the rule: fusion_host.h "the
+// search scope").  A pure function of the store, the options and the candidates: the passes in candidate order, each a run of
+// candidates [first, first + count) and the ascending, de-duplicated keys every one of them may read.  Candidates are independent,
+// so any such split scores the same bits.  A lattice (pose_host.h SearchLattice) starts from whole table entries -- candidates
+// (((e) Nx + ix) Ny + iy) Nz + iz over all offsets of entry e = a n_rot + r, a contiguous range, as is every ix-range [x0, x1) of
+// it.  A unit whose selection exceeds `capacity` is halved along ix, the lower half taking the floor, down to single ix-slabs; a
+// single slab -- or, in a plain table, a single pose -- above the capacity fails the plan with its count.  Consecutive units are
+// merged greedily into one pass while the union of their keys stays within the capacity.  An empty store: one pass without keys.
+struct SearchStagePass {
+  size_t first, count;
+  std::vector<unsigned long long> keys;
+};
+struct SearchStagePlan {
+  bool ok = true;
+  size_t too_many = 0;  // !ok: what the candidates of one slab (one plain pose) can read
+  std::vector<SearchStagePass> passes;
+};
+// the selection of candidates [x0, x1) x all iy x all iz of table entry e (plain: the pose e; x0, x1 are not read): ascending
+inline std::vector<unsigned long long> select_search_unit(const HostBlockStore &store, const drf_options_t &o, const double *table, const SearchLattice &L, size_t e,
+                                                          int x0, int x1) {
+  MapMotion m;
+  memcpy(m.R, table + 12 * e, 72);
+  memcpy(m.tv, table + 12 * e + 9, 24);
+  double extra = 0.0;
+  if (!L.plain) {
+    // the unit's offset box: ix - half_x in [x0 - half_x, x1 - 1 - half_x], iy - half_y in [-half_y, half_y], iz alike
+    const double hx = 0.5 * (double)(x1 - 1 - x0), hy = (double)L.half[1], hz = (double)L.half[2];
+    m.tv[0] += (0.5 * (double)(x0 + x1 - 1) - (double)L.half[0]) * L.dstep;
+    extra = search_unit_extra(std::sqrt(hx * hx + hy * hy + hz * hz) * L.dstep * (double)o.voxel_size);
+  }
+  float p16[16];
+  locate_pose16(m, o.voxel_size, p16);
+  std::vector<unsigned long long> keys;
+  select_render_blocks(store, o, p16, keys, nullptr, extra);
+  std::sort(keys.begin(), keys.end());
+  keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+  return keys;
+}
+inline SearchStagePlan plan_search_stage(const HostBlockStore &store, const drf_options_t &o, const double *table, const SearchLattice &L, size_t n, size_t capacity) {
+  SearchStagePlan p;
+  if (store.empty() || n == 0) {
+    p.passes.push_back({0, n, {}});
+    return p;
+  }
+  const size_t slab = L.plain ? 1 : (size_t)L.N[1] * (size_t)L.N[2], cells = L.plain ? 1 : slab * (size_t)L.N[0];
+  std::vector<unsigned long long> merged;
+  // one unit, in candidate order: into the open pass if the union fits, else it opens the next one
+  auto add = [&](size_t first, size_t count, std::vector<unsigned long long> &keys) {
+    if (!p.passes.empty()) {
+      SearchStagePass &last = p.passes.back();
+      merged.clear();
+      std::set_union(last.keys.begin(), last.keys.end(), keys.begin(), keys.end(), std::back_inserter(merged));
+      if (merged.size() <= capacity) {
+        last.keys.swap(merged);
+        last.count += count;
+        return;
+      }
+    }
+    p.passes.push_back({first, count, std::move(keys)});
+  };
+  for (size_t e = 0; e * cells < n && p.ok; ++e) {
+    // the ix-ranges of entry e still to place, the lowest on top
+    std::vector<std::pair<int, int>> todo(1, {0, L.plain ? 1 : L.N[0]});
+    while (!todo.empty()) {
+      const std::pair<int, int> u = todo.back();
+      todo.pop_back();
+      std::vector<unsigned long long> keys = select_search_unit(store, o, table, L, e, u.first, u.second);
+      if (keys.size() <= capacity) {
+        add(e * cells + (size_t)u.first * slab, (size_t)(u.second - u.first) * slab, keys);
+        continue;
+      }
+      if (u.second - u.first == 1) {
+        p.ok = false;
+        p.too_many = keys.size();
+        p.passes.clear();
+        break;
+      }
+      const int mid = u.first + (u.second - u.first) / 2;
+      todo.push_back({mid, u.second});
+      todo.push_back({u.first, mid});
+    }
+  }
+  return p;
+}
 
 }  // namespace dr

@@ -249,10 +249,12 @@ inline bool pose_is_rigid(const float *pose16) {
 // finite rigid motion, or options the bound is not defined for.
 // bz, if given, receives per appended block its camera-frame depth b_z (the third coordinate of R^T (centre - t)), or NaN where the
 // cut was not applied: what plan_render_bands slices the selection by.
+// extra >= 0, in metres, widens the selection (the search scope, below): the sphere's reach and every half-space margin grow by it.
+// With extra = 0 every sum below adds 0.0 to a positive number: the selection is the one without the argument, bit for bit.
 inline bool select_render_blocks(const HostBlockStore &store, const drf_options_t &o, const float *pose16, std::vector<unsigned long long> &out,
-                                 std::vector<double> *bz = nullptr) {
+                                 std::vector<double> *bz = nullptr, double extra = 0.0) {
   const double reach = stream_options_ok(o) ? render_reach(o) : HUGE_VAL;
-  if (!pose_is_rigid(pose16) || !std::isfinite(reach)) {
+  if (!pose_is_rigid(pose16) || !std::isfinite(reach) || !(extra >= 0.0) || !std::isfinite(extra)) {
     store.for_each([&](unsigned long long k, const uint8_t *) { out.push_back(k); });
     if (bz) bz->resize(bz->size() + store.size(), (double)NAN);
     return false;
@@ -260,16 +262,16 @@ inline bool select_render_blocks(const HostBlockStore &store, const drf_options_
   double p[3];
   camera_centre(pose16, p);
   const size_t first = out.size();
-  const double m = render_margin(o), vs = o.voxel_size, D = o.max_sensor_depth;
+  const double m = render_margin(o) + extra, vs = o.voxel_size, D = o.max_sensor_depth;
   // R R^T differs from I by < 1e-3 per entry (norm < 3e-3): R scales lengths by at most 1.5e-3, and b = R^T (c - t), which
   // stands in for the inverse below, is off by less than 4e-3 |c - t|.  Where the 8 s + vs of margin covers that, sphere and cut
   // stand as derived; where it does not (depth above ~10^4 voxels) the sphere grows by the error and the cut is not applied.
   if (4e-3 * reach > 8.0 * std::sqrt(3.0) * vs + vs) {
-    store.query_sphere(p, reach * (1.0 + 4e-3), o.voxel_size, out);
+    store.query_sphere(p, reach * (1.0 + 4e-3) + extra, o.voxel_size, out);
     if (bz) bz->resize(bz->size() + (out.size() - first), (double)NAN);
     return true;
   }
-  store.query_sphere(p, reach, o.voxel_size, out);
+  store.query_sphere(p, reach + extra, o.voxel_size, out);
   const double lx[2] = {(0.0 - o.cx) / o.fx, ((double)o.width - 1.0 - o.cx) / o.fx};
   const double ly[2] = {(0.0 - o.cy) / o.fy, ((double)o.height - 1.0 - o.cy) / o.fy};
   // unit inward normals of the four side planes through the camera centre: x >= lx0 z, x <= lx1 z, y >= ly0 z, y <= ly1 z
@@ -351,6 +353,24 @@ inline std::vector<unsigned long long> select_locate_blocks(const HostBlockStore
   keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
   return keys;
 }
+// ---- the search scope (DRF_SEARCH_MAP; DESIGN.md §7c "Searching the whole map"): which stored blocks the score of a whole set of
+// candidates can read.  A unit is a run of consecutive candidates with one rotation R whose translations lie in a box: centre t_c,
+// half-diagonal h (metres).  The sample points of a candidate are R g + t over the frame's points g, so those of candidate t are
+// those of the centre pose moved by t - t_c: by at most h, whatever R is.  A block the candidate reads has its centre within
+// 4.5 sqrt(3) vs of one of its sample points (the locate scope's argument, above), so within 4.5 sqrt(3) vs + h of a sample point
+// of the centre pose.  select_render_blocks keeps what lies within render_margin of an intersection of six half-spaces and a ball
+// that holds those sample points; a point within h of the intersection is within h of each half-space and of the ball, so with every
+// margin and the reach grown by `extra` >= h the selection at the centre pose holds every block any candidate of the unit reads.
+// The same reading gives the statement the tests hold it to: a block of the plain selection at the candidate lies within margin
+// of each half-space taken at t, hence within margin + |R^T (t - t_c)| of the one taken at t_c.  |R^T d| <= (1 + 1.5e-3) |d| for
+// a pose that is rigid within pose_is_rigid's 1e-3, and b = R^T (c - t_c) is then off by 4e-3 of a length that is now up to
+// reach + h, of which locate_stage_slack charges 4e-3 reach to the spare 8 sqrt(3) vs: extra = (1 + 4e-3) h covers both.
+// Rounding: the candidates are evaluated at the double poses of the table (search_candidate) and only the centre pose is rounded
+// to the floats select_render_blocks takes -- locate_pose16's bound, less than one voxel for every sample point, the vs that
+// locate_stage_slack leaves out of the slack.  The box's centre and h are computed in double from exact small integers times
+// dstep: their rounding is 2^-52 relative, far inside the same voxel.  A plain pose is a unit by itself with h = 0: the locate
+// scope's selection.  plan_search_stage (engine_host.h) cuts a table of candidates into such units and the units into stagings.
+inline double search_unit_extra(double half_diagonal) { return half_diagonal * (1.0 + 4e-3); }
 // ---- depth bands (drf_set_render_bands; DESIGN.md §7c "Rendering beyond the staging"): a union that exceeds the staging is
 // ray-cast in passes over consecutive slabs of camera-frame depth [z_j, z_j+1), common to all poses of the call.  A loop sample
 // of pass j lies at depth cur in [z_j, z_j+1), its final colour sample in [cur - trunc, cur + vs), and a sample at depth z reads

@@ -1,8 +1,8 @@
 // render_ops.h -- the ray-cast renders of DrFusion as two components over FusionCore (the kernels: raycast_kernels.h, k_publish in
 // volume_kernels.h; the host rules: fusion_host.h; DESIGN.md §7c "Rendering the whole map", "Rendering beyond the staging").
-// MapStage is the staging of host-stored blocks for the kernels that read them on the device; it has three readers -- map-scope
-// renders, the tracking's model render (both through MapRenderer::render_passes) and the locate scope (pose_ops.h FrameLocator) --
-// and states its capacity rule and its slot release once.  MapRenderer owns the render slots, the one submit, the render scope, the
+// MapStage is the staging of host-stored blocks for the kernels that read them on the device; it has four readers -- map-scope
+// renders, the tracking's model render (both through MapRenderer::render_passes), the locate scope (pose_ops.h FrameLocator) and the
+// search scope (search_ops.h PoseScorer) -- and states its capacity rule and its slot release once.  MapRenderer owns the render slots, the one submit, the render scope, the
 // depth bands, their statistics and the parity build's ray-cast switches.  Included by dr_fusion.hip after stream_ops.h.
 #pragma once
 #include <cstdio>
@@ -21,11 +21,14 @@ namespace dr {
 class MapStage {
  public:
   MapStage(FusionCore &core, BlockStreamer &streamer) : core_(core), streamer_(streamer) {}
-  // what its users may stage at a time, in blocks (0 = min(num_blocks, kStageBlocks)); the locate scope counts only while it is on
+  // what its users may stage at a time, in blocks (0 = min(num_blocks, kStageBlocks)); the locate and the search scope count only
+  // while they are on
   void set_render_need(size_t blocks) { rs_cap_req_ = blocks; }
   void set_locate_need(size_t blocks, bool on) { lc_cap_req_ = blocks; lc_on_ = on; }
+  void set_search_need(size_t blocks, bool on) { sc_cap_req_ = blocks; sc_on_ = on; }
   size_t capacity_for_render() const { return rs_cap_req_ ? rs_cap_req_ : (size_t)std::min(core_.o.num_blocks, kStageBlocks); }
   size_t capacity_for_locate() const { return lc_cap_req_ ? lc_cap_req_ : (size_t)std::min(core_.o.num_blocks, kStageBlocks); }
+  size_t capacity_for_search() const { return sc_cap_req_ ? sc_cap_req_ : (size_t)std::min(core_.o.num_blocks, kStageBlocks); }
   void ensure(size_t n) {
     if (!rs_.stream()) {
       rs_.open(core_.own);
@@ -33,7 +36,9 @@ class MapStage {
         for (int l = 0; l < kSuperLevels; ++l) f[l] = core_.own.device<unsigned char>((size_t)1 << (3 * (kGridBits - kSuperShift[l])), rs_.stream());
     }
     if (n <= rs_blocks_) return;
-    const size_t cap = lc_on_ ? std::max(capacity_for_render(), capacity_for_locate()) : capacity_for_render();  // the larger need of its two users
+    size_t cap = capacity_for_render();  // the largest need of its three users
+    if (lc_on_) cap = std::max(cap, capacity_for_locate());
+    if (sc_on_) cap = std::max(cap, capacity_for_search());
     const size_t want = std::min(cap, std::max(2 * rs_blocks_, (n + 1023) & ~(size_t)1023));
     DR_HIP(hipDeviceSynchronize());  // no copy or kernel reads the old allocations
     rs_.reserve((want + 1) * 8 + want * 4096);
@@ -84,8 +89,8 @@ class MapStage {
   BlockStaging rs_;
   DeviceBuf<unsigned long long> rs_table_[2];  // per slot of rs_: the open-addressing table and the two staged superblock flag arrays
   unsigned char *rs_super_[2][2] = {};
-  size_t rs_cap_req_ = 0, lc_cap_req_ = 0, rs_blocks_ = 0;
-  bool lc_on_ = false;
+  size_t rs_cap_req_ = 0, lc_cap_req_ = 0, sc_cap_req_ = 0, rs_blocks_ = 0;
+  bool lc_on_ = false, sc_on_ = false;
 };
 
 // One render slot: a stream, the device images, the double-buffered pinned results, the two events.  MapRenderer owns the public

@@ -51,17 +51,22 @@ using SearchOutOf = std::conditional_t<Opt::colour, SearchColourOut, SearchOut>;
 // has partial +0.0 in every sum, which changes no accumulator: its butterfly is skipped (wave-uniform).  The last butterfly folds
 // the lanes and the counters; lane 0 writes the candidate's record (32 bytes, 40 with colour) with plain stores.  No atomics, no
 // LDS, no second launch.  The map is only read.  yf is read with colour only.
-template <class Opt>
+// A template over the staging too (drf_set_search_scope; DESIGN.md §7c "Searching the whole map"): NoStage (raycast_kernels.h) is the
+// resident score over LocateFetch, a RenderStage the map-scope score over LocateFetchStaged, pool and staged blocks together; what
+// differs is the fetch and nothing else.  The staging is only read.
+__device__ __forceinline__ LocateFetch search_fetch(const FusionDev &d, const NoStage &) { return LocateFetch(d); }
+__device__ __forceinline__ LocateFetchStaged search_fetch(const FusionDev &d, const RenderStage &sg) { return LocateFetchStaged(d, sg); }
+template <class Opt, class Stage>
 __device__ __forceinline__ void search_score_wave(const FusionDev &d, const double *__restrict__ g, const unsigned char *__restrict__ flag, const float *__restrict__ yf,
                                                   int groups, const double *__restrict__ table, const SearchLattice &lat, size_t first, size_t table_first, int n,
-                                                  const Opt &so, double vs, SearchOutOf<Opt> *__restrict__ out) {
+                                                  const Opt &so, double vs, SearchOutOf<Opt> *__restrict__ out, const Stage &sg) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int local = blockIdx.x * 4 + wave;
   if (local >= n) return;
   const AlignEval e = score_eval(search_candidate(lat, table, table_first, first + (size_t)local), so.geo(), vs);
   double fold = 0.0, foldp = 0.0;
   unsigned ns = 0, nv = 0, nu = 0;
-  LocateFetch fetch(d);
+  auto fetch = search_fetch(d, sg);
 #pragma unroll 1
   for (int i = 0; i < groups; ++i) {
     double x = 0.0, xp = 0.0;
@@ -108,11 +113,23 @@ __device__ __forceinline__ void search_score_wave(const FusionDev &d, const doub
 __global__ __launch_bounds__(256) void k_search_score(const FusionDev d, const double *__restrict__ g, const unsigned char *__restrict__ flag, int groups,
                                                       const double *__restrict__ table, const SearchLattice lat, size_t first, size_t table_first, int n,
                                                       const ScoreOpt so, double vs, SearchOut *__restrict__ out) {
-  search_score_wave(d, g, flag, nullptr, groups, table, lat, first, table_first, n, so, vs, out);
+  search_score_wave(d, g, flag, nullptr, groups, table, lat, first, table_first, n, so, vs, out, NoStage{});
 }
 __global__ __launch_bounds__(256) void k_search_score_colour(const FusionDev d, const double *__restrict__ g, const unsigned char *__restrict__ flag,
                                                              const float *__restrict__ yf, int groups, const double *__restrict__ table, const SearchLattice lat,
                                                              size_t first, size_t table_first, int n, const ScoreColourOpt so, double vs,
                                                              SearchColourOut *__restrict__ out) {
-  search_score_wave(d, g, flag, yf, groups, table, lat, first, table_first, n, so, vs, out);
+  search_score_wave(d, g, flag, yf, groups, table, lat, first, table_first, n, so, vs, out, NoStage{});
+}
+// The map-scope forms: the resident kernels' arguments, then the staging (by value).
+__global__ __launch_bounds__(256) void k_search_score_staged(const FusionDev d, const double *__restrict__ g, const unsigned char *__restrict__ flag, int groups,
+                                                             const double *__restrict__ table, const SearchLattice lat, size_t first, size_t table_first, int n,
+                                                             const ScoreOpt so, double vs, SearchOut *__restrict__ out, const RenderStage sg) {
+  search_score_wave(d, g, flag, nullptr, groups, table, lat, first, table_first, n, so, vs, out, sg);
+}
+__global__ __launch_bounds__(256) void k_search_score_colour_staged(const FusionDev d, const double *__restrict__ g, const unsigned char *__restrict__ flag,
+                                                                    const float *__restrict__ yf, int groups, const double *__restrict__ table,
+                                                                    const SearchLattice lat, size_t first, size_t table_first, int n, const ScoreColourOpt so,
+                                                                    double vs, SearchColourOut *__restrict__ out, const RenderStage sg) {
+  search_score_wave(d, g, flag, yf, groups, table, lat, first, table_first, n, so, vs, out, sg);
 }

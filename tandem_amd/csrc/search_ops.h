@@ -1,8 +1,8 @@
 // search_ops.h -- drf_score_poses / drf_search_frame and their colour forms (drf_score_colour_poses / drf_search_colour_frame) as two
 // components over FusionCore (the rule: pose_host.h score_sample / search_candidate / search_refine; the kernels: search_kernels.h;
-// DESIGN.md §7c "Searching a pose lattice", "Searching with colour").  PoseScorer owns the score stage's device scratch and the
-// statistics of the search calls.  PoseSearch holds it and is the entry points: the prologue and the frame's intake (pose_ops.h
-// FramePose), the score, and the refinement composed from FrameTracker::track_levels and FrameLocator::with_locate + locate_loop as
+// DESIGN.md §7c "Searching a pose lattice", "Searching with colour", "Searching the whole map").  PoseScorer owns the score stage's
+// device scratch, the search scope and the statistics of the search calls.  PoseSearch holds it and is the entry points: the
+// prologue and the frame's intake (pose_ops.h FramePose), the score, and the refinement composed from FrameTracker::track_levels and FrameLocator::with_locate + locate_loop as
 // drf_track_frame and drf_locate_frame run them -- there is no second copy of either loop.  Each of the two has one score and one
 // search, a template over the resolved options (pose_host.h: ScoreOpt / ScoreColourOpt, SearchOpt / SearchColourOpt), whose
 // family fixes the layout of the scratch, the kernel, the track side and the winner rule.  Included by dr_fusion.hip after
@@ -18,9 +18,13 @@ namespace dr {
 
 class PoseScorer {
  public:
-  explicit PoseScorer(FusionCore &core) : core_(core) {}
-  uint64_t stats[8] = {};  // drf_search_stats
-  void reset() { for (auto &v : stats) v = 0; }
+  PoseScorer(FusionCore &core, BlockStreamer &streamer, MapStage &stage) : core_(core), streamer_(streamer), stage_(stage) {}
+  uint64_t stats[8] = {};        // drf_search_stats
+  uint64_t stage_stats[4] = {};  // drf_search_stage_stats: stagings, the largest in blocks, blocks staged, score launches over a staging
+  void reset() {
+    for (auto &v : stats) v = 0;
+    for (auto &v : stage_stats) v = 0;
+  }
 
   // candidates per launch: 32 bytes of results each (40 with colour), and with a plain table 96 bytes of poses
   size_t chunk_size() const {
@@ -65,44 +69,100 @@ class PoseScorer {
   // k_search_score_colour; cost, photo (colour only), counts (4 per candidate) and score may each be null.  A plain table (one pose
   // per candidate) is uploaded chunk by chunk, a search's (n_anchors x n_rot entries) once.  counted false: the final re-score of
   // a search, which leaves the candidates, the samples and the chunks of the statistics what the score stage made them.
+  // Map scope (drf_set_search_scope; DESIGN.md §7c "Searching the whole map"): the table is planned once (engine_host.h
+  // plan_search_stage) -- a plan that does not fit is refused before a candidate is evaluated -- and each pass stages its keys
+  // through the map staging, scores its candidates in chunks with the staged kernel and releases the slot behind them, on the
+  // throwing path too: the score holds no slot when the refinement starts.  No render reads the staging here: the call is legal only
+  // where a scan is, and the device is idle.  A pass without keys, an empty store and the resident scope launch the resident kernel.
   template <class Opt>
-  void score(const SearchLattice &L, const double *table, size_t table_entries, size_t n, const Opt &so, double *cost, double *photo, uint32_t *counts, double *score,
-             bool counted = true) {
+  void score(const char *who, const SearchLattice &L, const double *table, size_t table_entries, size_t n, const Opt &so, double *cost, double *photo,
+             uint32_t *counts, double *score, bool counted = true) {
     using Out = SearchOutOf<Opt>;
     Out *out = (Out *)out_;
+    SearchStagePlan plan;
+    if (scope_ == DRF_SEARCH_MAP) {
+      plan = plan_search_stage(streamer_.store(), core_.o, table, L, n, stage_.capacity_for_search());
+      if (!plan.ok)
+        fail(DR_ERR_CAPACITY, "%s: %s can read %zu stored blocks, the search staging holds %zu (drf_set_search_scope with a larger capacity, or drf_stream_in_region)",
+             who, L.plain ? "one pose" : "the candidates of one slab of the lattice", plan.too_many, stage_.capacity_for_search());
+    } else {
+      plan.passes.push_back({0, n, {}});
+    }
     std::vector<Out> host(std::min(n, chunk_));
     if (!L.plain) DR_HIP(hipMemcpyAsync(table_, table, table_entries * 96, hipMemcpyHostToDevice, core_.int_stream));
-    for (size_t first = 0; first < n; first += chunk_) {
-      const size_t m = std::min(chunk_, n - first), table_first = L.plain ? first : 0;
-      if (L.plain) DR_HIP(hipMemcpyAsync(table_, table + 12 * first, m * 96, hipMemcpyHostToDevice, core_.int_stream));
-      const dim3 grid(cdiv((int)m, 4)), block(256);
-      if constexpr (Opt::colour)
-        hipLaunchKernelGGL(k_search_score_colour, grid, block, 0, core_.int_stream, core_.d, g_, flag_, yf_, groups_, table_, L, first, table_first, (int)m, so,
-                           (double)core_.o.voxel_size, out);
-      else
-        hipLaunchKernelGGL(k_search_score, grid, block, 0, core_.int_stream, core_.d, g_, flag_, groups_, table_, L, first, table_first, (int)m, so,
-                           (double)core_.o.voxel_size, out);
-      DR_HIP(hipGetLastError());
-      DR_HIP(hipMemcpyAsync(host.data(), out, m * sizeof(Out), hipMemcpyDeviceToHost, core_.int_stream));
-      DR_HIP(hipStreamSynchronize(core_.int_stream));
-      for (size_t i = 0; i < m; ++i) {
-        const Out &o = host[i];
-        const size_t c = first + i;
-        if (cost) cost[c] = o.cost;
-        if constexpr (Opt::colour)
-          if (photo) photo[c] = o.photo;
-        if (counts) memcpy(counts + 4 * c, o.counts, 16);
-        if (score) score[c] = o.score;
+    RenderStage sg{};
+    bool staged = false;
+    // the slot's flags go back to zero behind the launches that read it (they are on core_.int_stream)
+    auto release = [&](bool may_throw) {
+      if (!staged) return;
+      staged = false;
+      hipError_t err = hipEventRecord(stage_.used(), core_.int_stream);
+      if (err == hipSuccess) err = hipStreamWaitEvent(stage_.stream(), stage_.used(), 0);
+      if (err == hipSuccess) {
+        stage_.launch_clear(sg);
+        err = hipGetLastError();
       }
-      if (!counted) continue;
-      ++stats[3];
-      if (first == 0) stats[2] = host[0].counts[0];
+      if (may_throw) DR_HIP(err);
+    };
+    try {
+      for (const SearchStagePass &pass : plan.passes) {
+        if (!pass.keys.empty()) {
+          sg = stage_.stage(pass.keys);
+          staged = true;
+          stage_.wait_ready(core_.int_stream);
+          ++stage_stats[0]; stage_stats[1] = std::max<uint64_t>(stage_stats[1], pass.keys.size()); stage_stats[2] += pass.keys.size();
+        }
+        for (size_t first = pass.first; first < pass.first + pass.count; first += chunk_) {
+          const size_t m = std::min(chunk_, pass.first + pass.count - first), table_first = L.plain ? first : 0;
+          if (L.plain) DR_HIP(hipMemcpyAsync(table_, table + 12 * first, m * 96, hipMemcpyHostToDevice, core_.int_stream));
+          const dim3 grid(cdiv((int)m, 4)), block(256);
+          const double vs = (double)core_.o.voxel_size;
+          if constexpr (Opt::colour) {
+            if (staged) hipLaunchKernelGGL(k_search_score_colour_staged, grid, block, 0, core_.int_stream, core_.d, g_, flag_, yf_, groups_, table_, L, first, table_first, (int)m, so, vs, out, sg);
+            else hipLaunchKernelGGL(k_search_score_colour, grid, block, 0, core_.int_stream, core_.d, g_, flag_, yf_, groups_, table_, L, first, table_first, (int)m, so, vs, out);
+          } else {
+            if (staged) hipLaunchKernelGGL(k_search_score_staged, grid, block, 0, core_.int_stream, core_.d, g_, flag_, groups_, table_, L, first, table_first, (int)m, so, vs, out, sg);
+            else hipLaunchKernelGGL(k_search_score, grid, block, 0, core_.int_stream, core_.d, g_, flag_, groups_, table_, L, first, table_first, (int)m, so, vs, out);
+          }
+          DR_HIP(hipGetLastError());
+          DR_HIP(hipMemcpyAsync(host.data(), out, m * sizeof(Out), hipMemcpyDeviceToHost, core_.int_stream));
+          DR_HIP(hipStreamSynchronize(core_.int_stream));
+          for (size_t i = 0; i < m; ++i) {
+            const Out &o = host[i];
+            const size_t c = first + i;
+            if (cost) cost[c] = o.cost;
+            if constexpr (Opt::colour)
+              if (photo) photo[c] = o.photo;
+            if (counts) memcpy(counts + 4 * c, o.counts, 16);
+            if (score) score[c] = o.score;
+          }
+          if (staged) ++stage_stats[3];
+          if (!counted) continue;
+          ++stats[3];
+          if (first == 0) stats[2] = host[0].counts[0];
+        }
+        release(true);
+      }
+    } catch (...) {
+      release(false);
+      throw;
     }
     if (counted) stats[0] = n;
+  }
+  // DRF_SEARCH_RESIDENT: the score reads the pool (the default); DRF_SEARCH_MAP: the pool and the host store together.
+  // stage_capacity_blocks bounds what one pass may stage (0 = the render's default); the staging holds the largest need of its users.
+  void set_scope(int scope, size_t stage_capacity_blocks) {
+    if (scope != DRF_SEARCH_RESIDENT && scope != DRF_SEARCH_MAP) fail(DR_ERR_ARG, "drf_set_search_scope: unknown scope %d", scope);
+    if (core_.order.render_pending()) fail(DR_ERR_PROTOCOL, "drf_set_search_scope: a render is pending, call GetRenderResult first");
+    scope_ = scope;
+    stage_.set_search_need(stage_capacity_blocks, scope == DRF_SEARCH_MAP);
   }
 
  private:
   FusionCore &core_;
+  BlockStreamer &streamer_;
+  MapStage &stage_;
+  int scope_ = DRF_SEARCH_RESIDENT;  // drf_set_search_scope
   DeviceBuf<unsigned char> buf_;  // sized by the largest call so far
   LocateGrid lg_{};
   int total_ = 0, groups_ = 0;
@@ -114,12 +174,14 @@ class PoseScorer {
 };
 
 // A depth frame found in the map from many poses.  The score stage is scorer_'s (k_search_points once, k_search_score in chunks, the
-// resident map through find_block); what is added here is the call order -- frame_prologue -- the frame's intake, and the
+// resident map through find_block -- in map scope k_search_score_staged over the passes of a plan, pool and staged blocks together);
+// what is added here is the call order -- frame_prologue -- the frame's intake, and the
 // refinement: track_levels and with_locate + locate_loop on the device image the score read.  Nothing of the map, the public
 // render buffers or the streaming state is written.
 class PoseSearch {
  public:
-  PoseSearch(FramePose &frame, FrameTracker &tracker, FrameLocator &locator) : frame_(frame), core_(frame.core), streamer_(frame.streamer), tracker_(tracker), locator_(locator), scorer_(frame.core) {}
+  PoseSearch(FramePose &frame, FrameTracker &tracker, FrameLocator &locator, MapStage &stage)
+      : frame_(frame), core_(frame.core), streamer_(frame.streamer), tracker_(tracker), locator_(locator), scorer_(frame.core, frame.streamer, stage) {}
   void score_poses(const char *who, const float *h_depth, const void *d_depth, const float *poses16, size_t n, const drf_score_options_t *opt, double *cost,
                    uint32_t *counts, double *score) {
     score_any(who, pair_of(nullptr, h_depth, nullptr, d_depth), poses16, n, opt, score_options, cost, nullptr, counts, score);
@@ -148,6 +210,11 @@ class PoseSearch {
     if (!out) fail(DR_ERR_ARG, "drf_search_stats: null argument");
     for (int i = 0; i < 8; ++i) out[i] = scorer_.stats[i];
   }
+  void set_search_scope(int scope, size_t stage_capacity_blocks) { scorer_.set_scope(scope, stage_capacity_blocks); }
+  void search_stage_stats(uint64_t out[4]) const {
+    if (!out) fail(DR_ERR_ARG, "drf_search_stage_stats: null argument");
+    for (int i = 0; i < 4; ++i) out[i] = scorer_.stage_stats[i];
+  }
 
  private:
   static constexpr SearchLattice kPlain = {{1, 1, 1}, {0, 0, 0}, 0.0, 1};  // drf_score_*_poses: candidate c is entry c of the table
@@ -162,7 +229,7 @@ class PoseSearch {
     if (!bad && (n == 0 || n > kSearchMaxCandidates)) fail(DR_ERR_ARG, "%s: %zu poses (at least 1, at most 2^24)", who, n);
     with_score(who, bad, so.geo().step, std::min(n, scorer_.chunk_size()), in, Opt::colour, [&](const unsigned char *, const float *) {
       const std::vector<double> table = plain_table(who, poses16, n);
-      scorer_.score(kPlain, table.data(), n, n, so, cost, photo, counts, score);
+      scorer_.score(who, kPlain, table.data(), n, n, so, cost, photo, counts, score);
     });
   }
   // The searches (Opt: SearchOpt with drf_track_options_t and a drf_search_result_t; SearchColourOpt with
@@ -197,7 +264,7 @@ class PoseSearch {
       if (!why.empty()) fail(DR_ERR_ARG, "%s: %s", who, why.c_str());
       std::vector<double> cost(n), photo(colour ? n : 0), score(n);
       std::vector<uint32_t> counts(4 * n);
-      scorer_.score(L, table.data(), entries, n, so.score(), cost.data(), photo.data(), counts.data(), score.data());
+      scorer_.score(who, L, table.data(), entries, n, so.score(), cost.data(), photo.data(), counts.data(), score.data());
       if (all_scores) memcpy(all_scores, score.data(), n * 8);
       const FramePair frame = FramePair::device(bgr, depth);
       FrameTracker::TrackSide &side = colour ? tracker_.pyramid() : tracker_.geometric();
@@ -216,7 +283,7 @@ class PoseSearch {
                       if constexpr (colour) {
                         return search_colour_winner(rr, qual, nq, [&](const float *poses16, size_t m, double *final_score, double *final_photo) {
                           const std::vector<double> located = plain_table(who, poses16, m);
-                          scorer_.score(kPlain, located.data(), m, m, so.score(), nullptr, final_photo, nullptr, final_score, false);
+                          scorer_.score(who, kPlain, located.data(), m, m, so.score(), nullptr, final_photo, nullptr, final_score, false);
                         });
                       } else {
                         return search_winner(rr, qual, nq);

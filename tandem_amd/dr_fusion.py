@@ -26,6 +26,8 @@ MESH_RESIDENT, MESH_MAP = 0, 1
 RENDER_RESIDENT, RENDER_MAP = 0, 1
 # drf_set_locate_scope: what locate_system / locate_frame read
 LOCATE_RESIDENT, LOCATE_MAP = 0, 1
+# drf_set_search_scope: what the score stage of score_poses / search_frame and their colour forms reads
+SEARCH_RESIDENT, SEARCH_MAP = 0, 1
 
 
 MESH_UPDATE_MAX_SCANS = 16  # DRF_MESH_UPDATE_MAX_SCANS: one scan more between two updates makes the next one full
@@ -575,6 +577,22 @@ class DrFusion:
         refinement, device bytes held by the score stage, blocks in the host store at the call)."""
         out = (C.c_uint64 * 8)()
         check(self._L.drf_search_stats(self._h, out))
+        return tuple(int(v) for v in out)
+
+    def set_search_scope(self, scope, stage_capacity_blocks=0):
+        """SEARCH_RESIDENT (default): the score stage of score_poses / search_frame and their colour forms reads the pool;
+        SEARCH_MAP: the pool and the host store -- the same bits as on an engine whose pool holds the whole map, and no block
+        moves.  The candidates are planned into passes whose stored blocks fit stage_capacity_blocks blocks of device scratch
+        (0 = min(num_blocks, 8192)); a single slab of the lattice that needs more raises DrError DR_ERR_CAPACITY and changes
+        nothing.  The refinement keeps its own scopes: a search of the whole map wants set_render_scope(RENDER_MAP) and
+        set_locate_scope(LOCATE_MAP) too."""
+        check(self._L.drf_set_search_scope(self._h, int(scope), int(stage_capacity_blocks)))
+
+    def search_stage_stats(self):
+        """Last search call of either family: (stagings made, blocks in the largest staging, blocks staged in total, score
+        launches that read a staging); all 0 in resident scope or with nothing to stage."""
+        out = (C.c_uint64 * 4)()
+        check(self._L.drf_search_stage_stats(self._h, out))
         return tuple(int(v) for v in out)
 
     # ---- searching with colour (include/dr_mi355x.h drf_search_colour_frame, DESIGN.md "Searching with colour") ----

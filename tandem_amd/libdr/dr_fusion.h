@@ -205,6 +205,12 @@ public:
   // DRF_LOCATE_MAP: LocateDepthFrame reads resident and host-stored blocks together, without moving one (capacity 0 = the default
   // staging); DRF_LOCATE_RESIDENT, the default: the pool only
   void SetLocateScope(int scope, size_t capacity = 0) { check(drf_set_locate_scope(impl, scope, capacity)); }
+  // DRF_SEARCH_MAP: the score stage of ScorePoses / SearchDepthFrame and their colour forms reads resident and host-stored blocks
+  // together, without moving one (capacity 0 = the default staging); DRF_SEARCH_RESIDENT, the default: the pool only.  A search of
+  // the whole map wants the render, the locate and the search scope set (dr_mi355x.h drf_set_search_scope)
+  void SetSearchScope(int scope, size_t capacity = 0) { check(drf_set_search_scope(impl, scope, capacity)); }
+  // the last search call: stagings made, blocks in the largest, blocks staged in total, score launches that read a staging
+  void SearchStageStats(uint64_t out[4]) { check(drf_search_stage_stats(impl, out)); }
 
   // Incremental mesh (dr_mi355x.h "incremental mesh", INTEGRATION.md "Incremental mesh"): GetMeshUpdateSync fills dr_mesh_num /
   // dr_mesh_vert / dr_mesh_cols with the triangles of the listed blocks only, and the members below name the blocks: block i has
